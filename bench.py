@@ -2,7 +2,7 @@
 """Headline benchmark: Mrays/s (camera paths/s, the reference's own numerator, src/main.rs:1491-1492) of one whole
 frame of a BASELINE.json configuration on N MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W [--config c2|c3|c4] [--no-secondary]
+    python bench.py --gpus 1 --steps K --warmup W [--config c2|c3|c4] [--dump-outputs DIR] [--full [--no-secondary]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,8 +14,16 @@ A step = one whole frame: every rank renders its ImageBlocks (rotating diagonal 
 a private full-frame RGBA32F buffer and one RCCL sum-reduce brings the frame to rank 0 (strong scaling: the frame is
 fixed).  Scene, BVH and block lists are resident/derived before the timed region; nothing is read back inside it.
 
-The default run (c2 on one GPU) also times 3 frames each of c3 and c4 after the headline (`secondary`: value, ms_per_step,
-roofline per configuration; the CPU baseline is timed for the headline only).
+A plain run sets up, warms up, times the K frames and prints the line: nothing else is rendered or timed.  `--full` adds what
+the headline does not need: the CPU baseline (`cpu_baseline`, timed for the headline configuration only), one blocking frame
+after the timed region (`blocking_frame_ms`, `value_blocking`; null in a plain run) and, in the default c2 run on one GPU,
+3 frames each of c3 and c4 after the headline (`secondary`: value, ms_per_step, roofline per configuration).
+
+`--dump-outputs DIR` writes, after the timed region, what the timed path computed in its last step: the reduced RGBA32F
+accumulation buffer (sum w*rgb, sum w) that rank 0 holds, as DIR/frame.npy (H, W, 4) float32.  Frames of more than
+FRAME_DUMP_PIXELS pixels (c4, c5) are sampled instead: DIR/frame_sample.npy (n, 4) float32 holds the pixels whose flat
+indices y * W + x are DIR/frame_sample_pixels.npy (n,) float64, a fixed seeded choice that depends on W and H alone.  The
+inputs are the same from run to run (synthetic scene, --seed), so two builds compare output for output.
 
 Prints ONE JSON line on rank 0 with the contract fields plus
   roofline     - HBM roofline of the dominant kernel (k_path_wavefront).  `achieved` = the bytes the IMPLEMENTED
@@ -28,7 +36,7 @@ Prints ONE JSON line on rank 0 with the contract fields plus
                  profiles/r02_fetch_size_calibration.txt: gathers exact, wide coalesced reads counted at half).  `achieved` never
                  exceeds `traffic`.  `limited_by`, `valu_issue_frac` (share of the chip's VALU issue slots in use) and
                  `lane_fill` (active lanes per VALU instruction / 64) say what binds the kernel when it is not HBM.
-  cpu_baseline - the CPU oracle ("Nori-style" port) timed on this host on a bounded sample of the same workload
+  cpu_baseline - (--full) the CPU oracle ("Nori-style" port) timed on this host on a bounded sample of the same workload
 """
 import argparse
 import glob
@@ -60,6 +68,23 @@ CONFIGS = {
     "c5": dict(kind="cbox", short="cbox", tris=0, size=4096, spp=4096,
                name="cbox-synth {W}x{H} {spp}spp diffuse+emissive, 6332 triangles"),
 }
+
+
+FRAME_DUMP_PIXELS = 1 << 21        # --dump-outputs: whole frames up to 2048 x 1024 (32 MiB), a sample of 1 << 20 pixels beyond
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the (H, W, 4) float32 frame of the last timed step, whole or as a fixed seeded sample of its pixels."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    H, W = frame.shape[:2]
+    if H * W <= FRAME_DUMP_PIXELS:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return
+    pixels = np.sort(np.random.default_rng(20240601).choice(H * W, size=FRAME_DUMP_PIXELS // 2, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), frame.reshape(H * W, 4)[pixels])
+    np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), pixels.astype(np.float64))
 
 
 def host_cores():
@@ -134,6 +159,8 @@ def main_inproc(args, cfg):
         for i, st in enumerate(step()):
             per[i][0] += st["total_ms"]; per[i][1] += st["path_busy_ms"]; per[i][2] += st["paths"]; per[i][3] += st["closest_rays"] + st["shadow_rays"]
     elapsed = time.perf_counter() - t0                   # comm.reduce returns after every stream has been synchronised
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rs[0].read())    # GPU 0's framebuffer: the reduced frame of the last timed step
     paths = W * H * spp * args.steps
     out = {"metric": f"Mrays/s (camera paths/s) at {spp}spp, {cfg['short']} {W}x{H}", "value": round(paths / elapsed / 1e6, 3),
            "unit": "Mrays/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
@@ -207,10 +234,12 @@ def run_config(name, cfg, args, steps, warmup, hj, barrier):
     # path kernels' exclusive GPU time, and the work it was dealt (paths, rays)
     per_rank = hjdist.gather_over_ranks([mine, sr.timing["render_s"], sr.timing["reduce_s"], agg["path_busy_ms"] * 1e-3, agg["paths"],
                                          agg["closest_rays"] + agg["shadow_rays"]], device=sr.local)
-    # one BLOCKING frame after the timed region (not part of `value`): what a single frame takes from submission to the
+    if args.dump_outputs and name == args.config and rank == 0:
+        dump_outputs(args.dump_outputs, sr.fb.cpu().numpy())    # the reduced frame of the last timed step
+    # --full: one BLOCKING frame after the timed region (not part of `value`): what a single frame takes from submission to the
     # reduced result when nothing overlaps its end - the latency figure beside the back-to-back throughput
     latency_ms = None
-    if pipelined and not getattr(args, "no_latency_frame", False):
+    if pipelined and args.full and not getattr(args, "no_latency_frame", False):
         barrier()
         t1 = time.perf_counter()
         sr.render_frame(spp, args.seed, opts=opts, reduce=True)
@@ -234,13 +263,19 @@ def main():
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, one blocking frame after the timed region "
+                         "and (default c2 run on one GPU) 3 frames each of c3 and c4; the --no-* switches below trim it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the reduced frame of the last timed step to DIR/frame.npy (large frames: a fixed seeded "
+                         "sample, DIR/frame_sample.npy + DIR/frame_sample_pixels.npy), after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="only the headline configuration (the default c2 run on one GPU also times 3 frames each of c3 and c4)")
+                    help="--full with only the headline configuration (the default c2 run on one GPU also times 3 frames each of c3 and c4)")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="drain the batch pipeline after every frame (one blocking hj_render_frame per step, as in rounds 1-3)")
     ap.add_argument("--no-latency-frame", action="store_true",
-                    help="skip the one blocking frame after the timed region (`blocking_frame_ms`): profiling runs that count frames")
+                    help="--full without the one blocking frame after the timed region (`blocking_frame_ms`): profiling runs that count frames")
     ap.add_argument("--dump-frame", default=None, metavar="FILE.npy",
                     help="rank 0 saves the reduced RGBA32F accumulation buffer of the last timed frame (after the timed region)")
     ap.add_argument("--static-deal", action="store_true",
@@ -270,9 +305,9 @@ def main():
     hj = (hjdist, rank, world, local)
     res = run_config(args.config, cfg, args, args.steps, args.warmup, hj, barrier)
     W, H, spp, agg, elapsed = res["W"], res["H"], res["spp"], res["agg"], res["elapsed"]
-    # the secondary configurations run on every rank (they contain collectives) but only in the default one-GPU run
+    # --full: the secondary configurations run on every rank (they contain collectives) but only in the default one-GPU run
     secondary = {}
-    if args.config == "c2" and res["standard"] and world == 1 and not args.no_secondary:
+    if args.full and args.config == "c2" and res["standard"] and world == 1 and not args.no_secondary:
         for name in ("c3", "c4"):
             try:                                    # (the headline line is printed whatever happens here)
                 secondary[name] = run_config(name, CONFIGS[name], args, 3, 1, hj, barrier)
@@ -325,7 +360,7 @@ def main():
             out["imbalance_render"] = None if mean_render <= 0 else round(max(r[1] for r in pr) / mean_render, 4)
             out["reduce_ms"] = round(max(r[2] for r in pr) * k, 3)          # the slowest rank's share of a step spent in the collective
         oracle_counters = None
-        if not args.no_cpu_baseline and world == 1:        # the CPU baseline is a one-GPU-run item (rank 0, N = 1 only)
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is a one-GPU-run item (rank 0, N = 1 only)
             out["cpu_baseline"], oracle_counters = cpu_baseline(res["cs"], W, H, spp, args.seed, cfg["short"])
         out["roofline"] = roofline_block(args.config, agg, elapsed, args.steps, world, res["standard"], oracle_counters)
         busy_ms = agg["path_busy_ms"] or (1e3 * elapsed)

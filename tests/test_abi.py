@@ -113,14 +113,16 @@ def test_argument_checks_need_no_gpu():
     assert (L.hj_version() >> 8) & 0xFF >= 2                  # ABI 0.2: statistics grew, async / comm / progress entry points
 
 
-def test_walk_of_the_fused_kernel_is_spill_free():
+def test_walk_of_the_fused_kernel_is_spill_free(tmp_path, monkeypatch):
     """The fused kernel's own code is the BVH walk (top-up, hit compaction, the camera-packet walk and shade are called
     functions with their own register allocation): no scratch (spill) instruction may sit inside the walk's loops, nor
     inside the node loop of the packet stage - one reload there is a dependent memory trip per iteration (DESIGN.md
     section 4).  tools/spill_scan.py compiles the device code to gfx950 assembly and counts them."""
     import sys
+    import tempfile
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    os.environ.setdefault("TMPDIR", "/tmp")
+    monkeypatch.setenv("TMPDIR", str(tmp_path))                   # hipcc's temporaries and the assembly go to this test's own
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))      # directory, not to a fixed name that another user may own
     import spill_scan
     res = spill_scan.scan()
     walks = [e for e in res if e["name"].startswith("k_path_wavefront<USE_BVH=1")]

@@ -78,6 +78,36 @@ def _check_per_rank(out, n, paths_per_step):
 
 
 @pytest.mark.timeout(900)
+def test_bench_plain_run_is_lean_and_full_adds_the_extras(tmp_path):
+    """A plain run renders only the warm-up and the timed frames (no CPU baseline, no blocking frame, no c3 / c4) and
+    `--dump-outputs` writes the frame of its last timed step; `--full` measures the extras beside the same headline fields."""
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="8")
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full"])):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "8",
+               "--dump-frame", str(tmp_path / f"frame_{tag}.npy"), "--dump-outputs", str(tmp_path / tag)] + extra
+        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-6000:]
+        got = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1
+        lines[tag] = out = json.loads(got[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "Mrays/s" and out["dtype"] == "f32"
+        assert abs(out["value"] - 1024 * 1024 * 8 / (out["ms_per_step"] * 1e-3) / 1e6) < 0.01 * out["value"]
+        assert os.listdir(tmp_path / tag) == ["frame.npy"]
+        frame = np.load(tmp_path / tag / "frame.npy")
+        assert frame.dtype == np.float32 and frame.shape == (1024, 1024, 4) and (frame[..., 3] > 0).all()
+        assert (frame.view(np.uint32) == np.load(tmp_path / f"frame_{tag}.npy").view(np.uint32)).all()
+    plain, full = lines["plain"], lines["full"]
+    assert "cpu_baseline" not in plain and "secondary" not in plain and plain["blocking_frame_ms"] is None
+    assert full["cpu_baseline"]["value"] > 0 and full["blocking_frame_ms"] > 0
+    assert "secondary" not in full                     # (c3 / c4 follow the STANDARD c2 frame only)
+    a, b = np.load(tmp_path / "plain" / "frame.npy"), np.load(tmp_path / "full" / "frame.npy")
+    assert (a.view(np.uint32) == b.view(np.uint32)).all()         # same arguments, same inputs: the same frame
+
+
+@pytest.mark.timeout(900)
 def test_bench_static_deal_two_ranks(tmp_path):
     """`--static-deal`: all passes of a block on one rank (SURVEY 8(e)'s partition).  The line says so, and the reduced frame is the
     one-rank frame BIT FOR BIT away from the 2-pixel aprons of the block borders (a pixel's passes are then summed on one rank, in

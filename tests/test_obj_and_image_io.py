@@ -1,5 +1,7 @@
 """§8(f) rows: OBJ/MTL loader (Scene::from_obj, src/main.rs:414-530) and image output (src/main.rs:1395-1419)."""
+import gzip
 import os
+import shutil
 import struct
 import subprocess
 
@@ -9,7 +11,8 @@ import pytest
 from hijiki_amd import abi, host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_OBJ = "/root/reference/scenes/cbox/cbox.obj"
+# the reference's scenes/cbox/cbox.obj (stored gzip-compressed) + cbox.mtl, as data
+REF_CBOX = os.path.join(ROOT, "tests", "golden", "cbox")
 
 OBJ = """# test scene
 mtllib test.mtl
@@ -120,11 +123,13 @@ def test_put_cbox_spheres(obj_path):
     assert (cb.scale_u, cb.scale_v) == (np.float32(0.1), np.float32(0.2))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_OBJ), reason="reference checkout not present (GPU box)")
-def test_reference_cbox_counts(oracle):
+def test_reference_cbox_counts(oracle, tmp_path):
     """The reference's own scene through the loader: SURVEY.md F8 / §8: 6332 triangles, 3668 vertices after
     (v,vt,vn) re-indexing, 12663 BVH nodes, 2 emitter triangles, 5 diffuse + 1 emissive materials."""
-    cs = host.Scene.from_obj(REF_OBJ).compile()
+    with gzip.open(os.path.join(REF_CBOX, "cbox.obj.gz")) as f:
+        (tmp_path / "cbox.obj").write_bytes(f.read())
+    shutil.copy(os.path.join(REF_CBOX, "cbox.mtl"), tmp_path / "cbox.mtl")
+    cs = host.Scene.from_obj(str(tmp_path / "cbox.obj")).compile()
     d = cs.desc
     assert (d.num_triangles, d.num_vertices, d.num_bvh_nodes, d.num_emitters) == (6332, 3668, 12663, 2)
     assert (d.num_diffuse, d.num_emissive) == (5, 1) and tuple(d.emissive[0].power) == (15, 15, 15)

@@ -38,5 +38,5 @@ fi
 # bench line below quotes THESE counters and tests/test_roofline_inputs.py still regenerates the newest inputs file from its passes
 python3 tools/roofline_inputs.py build $out $cfg > $out/roofline_inputs.json
 bash tools/collect_profiles.sh $tag $cfg > /dev/null
-timeout 600 python3 bench.py --config $cfg --steps 5 > $out/bench.json 2> $out/bench.err || echo "bench failed"
+timeout 600 python3 bench.py --config $cfg --steps 5 --full > $out/bench.json 2> $out/bench.err || echo "bench failed"
 head -6 $out/kernel_stats.csv; cat $out/pmc_pass*.csv | grep -i "k_path\|^kernel" ; cat $out/roofline_inputs.json; tail -1 $out/bench.json | cut -c1-400

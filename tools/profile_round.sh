@@ -35,6 +35,6 @@ for k, (n, v) in sorted(agg.items()): print(f"{k},{n},{v:.0f}")
 PY
 done
 cd $root
-timeout 300 python3 bench.py --steps 5 > $out/bench.json 2> $out/bench.err || echo "bench failed"
+timeout 300 python3 bench.py --steps 5 --full > $out/bench.json 2> $out/bench.err || echo "bench failed"
 rm -rf $out/stats $out/FETCH_SIZE $out/WRITE_SIZE
 cat $out/kernel_stats.csv | head -8; cat $out/pmc_FETCH_SIZE.csv $out/pmc_WRITE_SIZE.csv; tail -1 $out/bench.json | cut -c1-200
