@@ -83,15 +83,12 @@ int dev_alloc(hj_context* ctx, DevBuf& b, size_t bytes) {
 }
 
 void release_scene(hj_context* ctx) {
-  for (auto& b : ctx->scene_bufs) b.release();
-  ctx->scene_bufs.clear();
+  ctx->scene_bufs.bufs.clear();
   ctx->have_scene = false;
 }
 
 void release_slot(hj_context::BatchSlot& sl) {
-  for (auto& b : sl.bufs) b.release();
-  sl.bufs.clear();
-  for (auto& b : sl.sample_bufs) b.release();
+  sl.bufs.clear();                           // (DevBuf frees its memory)
   sl.sample_bufs.clear();
   sl.alloc_positions = 0;
   sl.st = hj::BatchState{};

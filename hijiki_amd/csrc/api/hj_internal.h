@@ -2,7 +2,8 @@
 // small helpers every entry point uses.  Nothing here is part of the C ABI (include/hijiki_hip.h).
 //
 //   api/context.hip       context create / destroy, framebuffer, errors, environment switches            (no kernels)
-//   api/scene_upload.hip  hj_scene_upload: validation and the re-layout of the reference's scene arrays  (no kernels)
+//   api/scene_upload.hip  hj_scene_upload: validation, host re-layout, emitter records, light grid; one commit at the end  (no kernels)
+//   api/scene_relayout.hip the same re-layout on the device (large trees, the tree hj_build_bvh_device left there)
 //   api/render.hip        batch slots, the launches of kernels/hj_kernels.h, render calls, probes
 //   api/comm.hip          RCCL (dlopen), hj_comm_*, hj_reduce_framebuffers
 //   api/lbvh_build.hip    hj_build_bvh_device: host half of kernels/hj_lbvh.h
@@ -36,9 +37,14 @@ namespace hjapi {
 
 extern std::atomic<size_t> g_dev_bytes;   // device memory held through DevBuf by every context of the process
 
+// One device allocation and its owner: move-only, freed by release() or with the object.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(bytes, o.bytes); } return *this; }
+  ~DevBuf() { release(); }
   void release() {
     if (p) {
       (void)hipFree(p);
@@ -49,11 +55,55 @@ struct DevBuf {
   }
 };
 
+int dev_alloc(hj_context* ctx, DevBuf& b, size_t bytes);
+
+// The device buffers a call (or the scene, or a batch slot) owns: freed together with the set unless moved on first - a call
+// allocates into a set of its own and hands it over when everything it needed has succeeded.  ctx: where allocation errors go
+// (a set that only receives buffers needs none).
+struct DevBufs {
+  hj_context* ctx = nullptr;
+  std::vector<DevBuf> bufs;
+  explicit DevBufs(hj_context* c = nullptr) : ctx(c) {}
+  // `count` elements of T, at least 16 bytes, plus `slack` bytes
+  template <class T>
+  int alloc(T*& out, size_t count, size_t slack = 0) {
+    bufs.emplace_back();
+    const int rc = dev_alloc(ctx, bufs.back(), std::max<size_t>(sizeof(T) * count + slack, 16));
+    out = static_cast<T*>(bufs.back().p);
+    return rc;
+  }
+  DevBuf take(const void* p) {                        // moves the buffer that starts at p out of the set (none: an empty DevBuf)
+    DevBuf out;
+    for (auto& b : bufs) if (p && b.p == p) { out = std::move(b); break; }
+    return out;
+  }
+  void move_into(DevBufs& to) {                       // every buffer of this set joins `to`
+    for (auto& b : bufs) if (b.p) to.bufs.push_back(std::move(b));
+    bufs.clear();
+  }
+};
+
+// HJ_*_TIMING: a call's stage times on stderr (fmt: a "%s" and a "%f"), each since the previous mark, after draining `sync` if set
+struct StageClock {
+  bool on;
+  const char* fmt;
+  hipStream_t sync = nullptr;
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  void mark(const char* what) {
+    if (!on) return;
+    if (sync) (void)hipStreamSynchronize(sync);
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, fmt, what, std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
+  }
+};
+
 struct EventPair { hipEvent_t a, b; int kind; };
 
 }  // namespace hjapi
 
 using hjapi::DevBuf;
+using hjapi::DevBufs;
 using hjapi::EventPair;
 
 constexpr uint32_t kMaxSlots = 4;
@@ -67,7 +117,7 @@ struct hj_context {
   // scene
   bool have_scene = false;
   hj::DeviceScene scene{};
-  std::vector<DevBuf> scene_bufs;
+  DevBufs scene_bufs;
 
   // framebuffer
   float4* accum = nullptr;
@@ -164,7 +214,6 @@ std::string get_error(hj_context* ctx);
 // stayed on the device against an upload of OTHER geometry with the same counts (an accident, not an adversary).
 uint64_t shape_arrays_hash(const hj_scene_desc* s);
 void put_error(hj_context* ctx, const std::string& text);
-int dev_alloc(hj_context* ctx, DevBuf& b, size_t bytes);
 std::mutex& alloc_mutex();                           // process-wide: a context sizing its batch slots (api/render.hip run_submit)
 int validate_scene(hj_context* ctx, const hj_scene_desc* s);   // api/scene_upload.hip: every invariant an upload checks
 void release_scene(hj_context* ctx);
@@ -198,17 +247,20 @@ void drop_cached_comms(hj_context* ctx);             // api/comm.hip: the commun
                        hipGetErrorString(e_));                                                    \
   } while (0)
 
+// a step that returns an HJ_* status: a failure ends the calling function with it
+#define HJ_TRY(expr) do { const int rc_ = (expr); if (rc_ != HJ_OK) return rc_; } while (0)
+
 namespace hjapi {
 
+// `count` elements of T from the host into a new buffer of `bufs`
 template <class T>
-int upload(hj_context* ctx, const T* src, size_t count, const T** out) {
-  ctx->scene_bufs.emplace_back();
-  DevBuf& b = ctx->scene_bufs.back();
+int upload(DevBufs& bufs, const T* src, size_t count, const T** out) {
+  T* p = nullptr;
   // 64 bytes of slack: the walk's merged step reads two 16-byte parts of every shape record, a sphere has one
-  int rc = dev_alloc(ctx, b, count * sizeof(T) + 64);
+  int rc = bufs.alloc(p, count, 64);
   if (rc != HJ_OK) return rc;
-  if (count) HJ_HIP(ctx, hipMemcpy(b.p, src, count * sizeof(T), hipMemcpyHostToDevice));
-  *out = static_cast<const T*>(b.p);
+  if (count) HJ_HIP(bufs.ctx, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+  *out = p;
   return HJ_OK;
 }
 

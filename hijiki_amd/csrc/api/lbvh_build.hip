@@ -31,36 +31,20 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   // HJ_LBVH_TIMING=1: wall time of the build's stages on stderr (the stream is drained at every mark)
   const Tuning tn = ctx->tuning = Tuning::from_env();
   const bool timing = tn.lbvh_timing != 0;
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!timing) return;
-    (void)hipStreamSynchronize(ctx->stream);
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "hj_build_bvh_device: %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  mark("argument checks");
-  std::vector<DevBuf> bufs;
-  struct Release { std::vector<DevBuf>& b; ~Release() { for (auto& x : b) x.release(); } } release{bufs};
-  bufs.reserve(32);
-  auto dev = [&](size_t bytes, void** p) -> int {
-    bufs.emplace_back();
-    const int rc = dev_alloc(ctx, bufs.back(), std::max<size_t>(bytes, 16));
-    *p = bufs.back().p;
-    return rc;
-  };
+  StageClock clock{timing, "hj_build_bvh_device: %-28s %7.2f ms\n", ctx->stream};
+  clock.mark("argument checks");
+  DevBufs bufs(ctx);
   int rc = HJ_OK;
-#define HJ_DEVBUF(ptr, type, count) do { void* p_ = nullptr; rc = dev(sizeof(type) * (count), &p_); if (rc != HJ_OK) return rc; ptr = static_cast<type*>(p_); } while (0)
   hipStream_t st = ctx->stream;
   ctx->resident.release();                                  // (a tree of an earlier build that nobody took over)
   void *keep_sp = nullptr, *keep_qd = nullptr, *keep_tr = nullptr, *keep_vx = nullptr;
   hj::lbvh::Shapes sh{};
   {
     float4* sp = nullptr; float4* qd = nullptr; hj_triangle* tr = nullptr; hj_vertex* vx = nullptr;
-    HJ_DEVBUF(sp, float4, s->num_spheres);
-    HJ_DEVBUF(qd, float4, 3 * s->num_quads);
-    HJ_DEVBUF(tr, hj_triangle, s->num_triangles);
-    HJ_DEVBUF(vx, hj_vertex, s->num_vertices);
+    HJ_TRY(bufs.alloc(sp, s->num_spheres));
+    HJ_TRY(bufs.alloc(qd, 3 * s->num_quads));
+    HJ_TRY(bufs.alloc(tr, s->num_triangles));
+    HJ_TRY(bufs.alloc(vx, s->num_vertices));
     if (s->num_spheres) HJ_HIP(ctx, hipMemcpyAsync(sp, s->spheres, sizeof(float4) * s->num_spheres, hipMemcpyHostToDevice, st));
     if (s->num_quads) HJ_HIP(ctx, hipMemcpyAsync(qd, s->quads, sizeof(float4) * 3 * s->num_quads, hipMemcpyHostToDevice, st));
     if (s->num_triangles) HJ_HIP(ctx, hipMemcpyAsync(tr, s->triangles, sizeof(hj_triangle) * s->num_triangles, hipMemcpyHostToDevice, st));
@@ -72,34 +56,34 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   hj::lbvh::Tree t{};
   unsigned long long* keys_in = nullptr;
   hj_bvh_node* d_out = nullptr;
-  HJ_DEVBUF(t.leaf_lo, float4, n);
-  HJ_DEVBUF(t.leaf_hi, float4, n);
-  HJ_DEVBUF(t.bounds, int, 12);
-  HJ_DEVBUF(keys_in, unsigned long long, n);
-  HJ_DEVBUF(t.keys, unsigned long long, n);
-  HJ_DEVBUF(t.child, uint32_t, 2 * (n - 1));
-  HJ_DEVBUF(t.first, uint32_t, n - 1);
-  HJ_DEVBUF(t.count, uint32_t, n - 1);
-  HJ_DEVBUF(t.parent, uint32_t, total);
-  HJ_DEVBUF(t.node_lo, float4, n - 1);
-  HJ_DEVBUF(t.node_hi, float4, n - 1);
-  HJ_DEVBUF(t.arrived, uint32_t, n - 1);
-  HJ_DEVBUF(d_out, hj_bvh_node, total);
+  HJ_TRY(bufs.alloc(t.leaf_lo, n));
+  HJ_TRY(bufs.alloc(t.leaf_hi, n));
+  HJ_TRY(bufs.alloc(t.bounds, 12));
+  HJ_TRY(bufs.alloc(keys_in, n));
+  HJ_TRY(bufs.alloc(t.keys, n));
+  HJ_TRY(bufs.alloc(t.child, 2 * (n - 1)));
+  HJ_TRY(bufs.alloc(t.first, n - 1));
+  HJ_TRY(bufs.alloc(t.count, n - 1));
+  HJ_TRY(bufs.alloc(t.parent, total));
+  HJ_TRY(bufs.alloc(t.node_lo, n - 1));
+  HJ_TRY(bufs.alloc(t.node_hi, n - 1));
+  HJ_TRY(bufs.alloc(t.arrived, n - 1));
+  HJ_TRY(bufs.alloc(d_out, total));
   const uint32_t N = (uint32_t)n;
   const dim3 blk(256), grid_n((N + 255u) / 256u);
   uint32_t* d_nbig = nullptr;
-  HJ_DEVBUF(d_nbig, uint32_t, 1);
-  mark("allocations + shape upload");
+  HJ_TRY(bufs.alloc(d_nbig, 1));
+  clock.mark("allocations + shape upload");
   hipLaunchKernelGGL(hj::lbvh::k_init_bounds, dim3(1), dim3(64), 0, st, t.bounds);
   hipLaunchKernelGGL(hj::lbvh::k_shape_boxes, grid_n, blk, 0, st, sh, t, N);
   uint32_t idx_bits = 1;
   while ((1ull << idx_bits) < n) idx_bits++;
   const uint32_t axis_bits = std::min<uint32_t>(20u, (63u - idx_bits) / 3u);
   const unsigned long long idx_mask = (1ull << idx_bits) - 1ull;
-  void* sort_tmp = nullptr;
+  char* sort_tmp = nullptr;
   size_t sort_bytes = 0;
   HJ_HIP(ctx, rocprim::radix_sort_keys(nullptr, sort_bytes, keys_in, t.keys, n, 0, 64, st));
-  HJ_DEVBUF(sort_tmp, char, sort_bytes);
+  HJ_TRY(bufs.alloc(sort_tmp, sort_bytes));
   // Large shapes (hj_lbvh.h) stay out of the Morton tree; HJ_LBVH_BIG_PCT = threshold in per cent of the scene's box area
   // (0 = everything goes into the Morton tree).  They sort behind everything else (bit 63 of the key).
   float big_frac = (float)tn.lbvh_big_pct / 100.0f;
@@ -115,7 +99,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
     if (nbig == 0 || (nbig <= 256 && n - nbig >= 2)) break;
     big_frac = 0.f;                                          // too many large shapes (or nothing else): one Morton tree
   }
-  mark("boxes, keys, sort");
+  clock.mark("boxes, keys, sort");
   // ---- the Morton tree over the m = n - nbig small shapes
   const uint32_t m = N - nbig;
   const size_t sub_total = 2 * (size_t)m - 1;
@@ -136,13 +120,13 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   hj::lbvh::Clusters cl{};
   {
     uint32_t* base_w = nullptr; uint32_t* exit_w = nullptr;
-    HJ_DEVBUF(cl.count, uint32_t, 1);
-    HJ_DEVBUF(cl.slot_of, uint32_t, sub_total);
-    HJ_DEVBUF(cl.node, uint32_t, m);
-    HJ_DEVBUF(cl.lo, float4, m);
-    HJ_DEVBUF(cl.hi, float4, m);
-    HJ_DEVBUF(base_w, uint32_t, m);
-    HJ_DEVBUF(exit_w, uint32_t, m);
+    HJ_TRY(bufs.alloc(cl.count, 1));
+    HJ_TRY(bufs.alloc(cl.slot_of, sub_total));
+    HJ_TRY(bufs.alloc(cl.node, m));
+    HJ_TRY(bufs.alloc(cl.lo, m));
+    HJ_TRY(bufs.alloc(cl.hi, m));
+    HJ_TRY(bufs.alloc(base_w, m));
+    HJ_TRY(bufs.alloc(exit_w, m));
     cl.base = base_w; cl.exit = exit_w;
     HJ_HIP(ctx, hipMemsetAsync(cl.count, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(hj::lbvh::k_mark_clusters, grid_sub, blk, 0, st, t, m, cmax, idx_mask, cl, sah_clusters);
@@ -150,7 +134,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   uint32_t K = 0;
   HJ_HIP(ctx, hipMemcpyAsync(&K, cl.count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HJ_HIP(ctx, hipStreamSynchronize(st));
-  mark("hierarchy, refit, clusters");
+  clock.mark("hierarchy, refit, clusters");
   // the wave-per-cluster re-split starts NOW, into a staging array, and runs while the host builds the top of the tree over
   // the clusters' boxes; k_place_clusters moves the records to their places once those are known
   // (on a stream of its own - a batch slot's, idle outside render calls -, so that the small copies the host needs for the top
@@ -159,7 +143,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
   hipStream_t side = ctx->slots[0].stream;
   if (sah_wave) {
-    HJ_DEVBUF(d_staged, hj_bvh_node, 2 * (size_t)m);
+    HJ_TRY(bufs.alloc(d_staged, 2 * (size_t)m));
     HJ_HIP(ctx, hipEventCreateWithFlags(&ev.a, hipEventDisableTiming));
     HJ_HIP(ctx, hipEventCreateWithFlags(&ev.b, hipEventDisableTiming));
     HJ_HIP(ctx, hipEventRecord(ev.a, st));
@@ -189,7 +173,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
     if (nbig != 0) {   // boxes of the large shapes: the ones k_shape_boxes computed (src/shape.rs:13-20,46-54, src/main.rs:74-79)
       // one gather kernel + one copy for all of them (they sort behind the small shapes: keys [m, n))
       float4* d_big = nullptr;
-      HJ_DEVBUF(d_big, float4, 2 * (size_t)nbig);
+      HJ_TRY(bufs.alloc(d_big, 2 * (size_t)nbig));
       hipLaunchKernelGGL(hj::lbvh::k_gather_big, dim3((nbig + 63u) / 64u), dim3(64), 0, st, t, m, nbig, idx_mask, d_big);
       std::vector<float4> big(2 * (size_t)nbig);
       HJ_HIP(ctx, hipMemcpyAsync(big.data(), d_big, sizeof(float4) * big.size(), hipMemcpyDeviceToHost, st));
@@ -464,7 +448,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
       builder.emit(builder.task_trees[i], 0, lo, hi, place[i][0], place[i][1], top_records, cbase, cexit, nullptr);
     }
   }
-  mark("host SAH over the clusters");
+  clock.mark("host SAH over the clusters");
   HJ_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t*>(cl.base), cbase.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice, st));
   HJ_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t*>(cl.exit), cexit.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice, st));
   if (sah_wave) {
@@ -477,14 +461,14 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   else
     hipLaunchKernelGGL(hj::lbvh::k_emit_clusters, grid_sub, blk, 0, st, t, m, cl, idx_mask, d_out);
   HJ_HIP(ctx, hipGetLastError());
-  mark("cluster subtrees");
+  clock.mark("cluster subtrees");
   // ---- child order voted by a sample of the scene's own rays (kernels/hj_vote.h; HJ_LBVH_VOTE_PATHS camera paths, 0 = the order
   // by shape count the stages above produced): the host-built records join the others on the device first
   const size_t vote_paths = (size_t)tn.lbvh_vote_paths;
   hj_bvh_node* final_tree = nullptr;
   if (vote_paths != 0 && total >= 3) {
     hj_bvh_node* d_voted = nullptr;
-    HJ_DEVBUF(d_voted, hj_bvh_node, total);
+    HJ_TRY(bufs.alloc(d_voted, total));
     rc = put_records(ctx, top_records, d_out);
     if (rc != HJ_OK) return rc;
     const VoteShapes vsh{sh.spheres, sh.quads, sh.triangles, sh.vertices};
@@ -492,7 +476,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
     rc = vote_on_device(ctx, s, vsh, d_out, total, vote_paths, d_voted, timing, nullptr);
     if (rc != HJ_OK && rc != HJ_ERR_UNSUPPORTED) return rc;
     if (rc == HJ_ERR_UNSUPPORTED) put_error(ctx, error_before);      // the build succeeds without the vote: no stale message behind HJ_OK
-    mark("ray-voted child order");
+    clock.mark("ray-voted child order");
     // (a tree deeper than the exchange's level loop goes - thousands of shapes in a chain - keeps the order it has)
     final_tree = rc == HJ_OK ? d_voted : d_out;
     rc = HJ_OK;
@@ -503,20 +487,17 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   }
   if (out_nodes) HJ_HIP(ctx, hipMemcpyAsync(out_nodes, final_tree, sizeof(hj_bvh_node) * total, hipMemcpyDeviceToHost, st));
   HJ_HIP(ctx, hipStreamSynchronize(st));
-  mark("records to the host");
+  clock.mark("records to the host");
   // The tree and the shape arrays it was built over STAY on the device (hj_context::resident): hj_scene_upload with scene->bvh ==
   // NULL derives the kernels' records from them without a trip through the host; hj_bvh_device_read copies the tree out.
   {
-    auto take = [&](void* p, DevBuf& into) {
-      for (auto& b : bufs) if (b.p == p && p != nullptr) { into = b; b.p = nullptr; b.bytes = 0; return; }
-    };
     hj_context::ResidentTree& rt = ctx->resident;
-    take(final_tree, rt.nodes); take(keep_sp, rt.spheres); take(keep_qd, rt.quads); take(keep_tr, rt.triangles); take(keep_vx, rt.vertices);
+    rt.nodes = bufs.take(final_tree); rt.spheres = bufs.take(keep_sp); rt.quads = bufs.take(keep_qd);
+    rt.triangles = bufs.take(keep_tr); rt.vertices = bufs.take(keep_vx);
     rt.total = total; rt.ns = s->num_spheres; rt.nq = s->num_quads; rt.nt = s->num_triangles; rt.nv = s->num_vertices;
     rt.shapes_hash = shape_arrays_hash(s);
     rt.valid = rt.nodes.p != nullptr;
   }
-#undef HJ_DEVBUF
   if (out_num_nodes) *out_num_nodes = total;
   return HJ_OK;
 }

@@ -46,6 +46,11 @@ namespace hjapi {
 
 namespace {
 
+// Cells on meshes and in corners (bundle proofs) are tried for scenes of up to this many shapes: the pass keeps a plane and a corner
+// polygon of every flat shape (some 250 bytes each, in double) and its host time grows with the shape count, while scenes that large
+// have no grid by default at all (HJ_STREAM_MIN_NODES) - a grid forced on them gets the planar proofs alone.
+constexpr size_t kMeshCellsMaxShapes = 200000;
+
 struct Box { double lo[3], hi[3]; };
 inline Box empty_box() { return {{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}}; }
 inline void grow(Box& b, const double p[3]) { for (int k = 0; k < 3; k++) { b.lo[k] = std::min(b.lo[k], p[k]); b.hi[k] = std::max(b.hi[k], p[k]); } }
@@ -359,12 +364,11 @@ inline bool bundle_misses(const Poly& T, const Poly& E, const Poly& B, const Bun
 
 }  // namespace
 
-bool build_light_grid(const hj_scene_desc* s, uint32_t res, LightGrid& out) {
+bool build_light_grid(const hj_scene_desc* s, uint32_t res, bool mesh, bool timing, LightGrid& out) {
   out = LightGrid{};
   if (!s || res < 2 || res > 256 || s->num_emitters == 0 || s->num_bvh_nodes == 0) return false;
   const Geometry g{s, s->num_spheres, s->num_quads, s->num_triangles};
   const size_t shapes = g.ns + g.nq + g.nt, N = s->num_bvh_nodes;
-  const bool timing = Tuning::from_env().light_grid_timing;       // wall time of the stages on stderr (no context here: hj_debug_light_grid has none)
   auto t_last = std::chrono::steady_clock::now();
   auto mark = [&](const char* what) {
     if (!timing) return;
@@ -507,8 +511,8 @@ bool build_light_grid(const hj_scene_desc* s, uint32_t res, LightGrid& out) {
   std::vector<uint32_t> first(ncell, 0xFFFFFFFFu);
   std::vector<uint8_t> bad(ncell, 0);
   // cells on meshes (HJ_LIGHT_GRID_MESH): a cell that is not planar can still be proven when everything in it is FLAT - `hard` marks
-  // the cells that hold a sphere or a shape without a usable plane; `flat_ok` per shape.  Scenes of more than 200 000 shapes: not tried.
-  const bool mesh_cells = Tuning::from_env().light_grid_mesh != 0 && shapes <= 200000;
+  // the cells that hold a sphere or a shape without a usable plane; `flat_ok` per shape.  Scenes of more than kMeshCellsMaxShapes: not tried.
+  const bool mesh_cells = mesh && shapes <= kMeshCellsMaxShapes;
   std::vector<uint8_t> hard(mesh_cells ? ncell : 0, 0), flat_ok(mesh_cells ? shapes : 0, 0);
   struct Flat { Plane pl; Poly poly; };
   std::vector<Flat> flat(mesh_cells ? shapes : 0);                 // plane and corners of every flat shape, once
@@ -765,7 +769,7 @@ bool build_light_grid(const hj_scene_desc* s, uint32_t res, LightGrid& out) {
 
 // Test entries (no GPU needed): the grid hj_scene_upload would build for `s`.  bits: res^3 bytes (may be null: sizes only).
 namespace {
-int debug_grid(const hj_scene_desc* s, uint32_t res, hjapi::LightGrid& g) {
+int debug_grid(const hj_scene_desc* s, uint32_t res, const hjapi::Tuning& tn, hjapi::LightGrid& g) {
   // build_light_grid trusts what hj_scene_upload has validated; this entry takes a desc nobody has looked at: the same range checks
   // first (a desc that fails them has no grid)
   if (!s || !s->bvh || s->num_bvh_nodes == 0) return 0;
@@ -777,7 +781,7 @@ int debug_grid(const hj_scene_desc* s, uint32_t res, hjapi::LightGrid& g) {
   for (size_t i = 0; i < s->num_bvh_nodes; i++)
     if (s->bvh[i].shape_index != HJ_BVH_INNER && s->bvh[i].shape_index >= shapes) return 0;
   for (size_t e = 0; e < s->num_emitters; e++) if (s->emitters[e].shape >= shapes) return 0;
-  return hjapi::build_light_grid(s, res, g) ? (int)g.res : 0;
+  return hjapi::build_light_grid(s, res, tn.light_grid_mesh != 0, tn.light_grid_timing, g) ? (int)g.res : 0;
 }
 void debug_grid_out(const hjapi::LightGrid& g, float lo[3], float inv[3], uint64_t stats[3]) {
   for (int k = 0; k < 3; k++) { if (lo) lo[k] = g.lo[k]; if (inv) inv[k] = g.inv[k]; }
@@ -788,8 +792,9 @@ void debug_grid_out(const hjapi::LightGrid& g, float lo[3], float inv[3], uint64
 // bits = planar bits | mesh bits (the latter hold for hits that were not grazing only: hj_debug_light_grid_planes tells them apart)
 extern "C" __attribute__((visibility("default"))) int hj_debug_light_grid(const hj_scene_desc* s, uint32_t res, uint8_t* bits, float lo[3],
                                                                            float inv[3], uint64_t stats[3]) {
+  const hjapi::Tuning tn = hjapi::Tuning::from_env();
   hjapi::LightGrid g;
-  const int r = debug_grid(s, res, g);
+  const int r = debug_grid(s, res, tn, g);
   if (r == 0) return 0;
   if (bits) for (size_t i = 0; i < g.bits.size(); i++) bits[i] = (uint8_t)(g.bits[i] | (g.mesh_bits.empty() ? 0 : g.mesh_bits[i]));
   debug_grid_out(g, lo, inv, stats);
@@ -802,8 +807,9 @@ extern "C" __attribute__((visibility("default"))) int hj_debug_light_grid(const 
 extern "C" __attribute__((visibility("default"))) int hj_debug_light_grid_planes(const hj_scene_desc* s, uint32_t res, uint8_t* planar, uint8_t* mesh,
                                                                                   float* recs, float limits[2], float lo[3], float inv[3],
                                                                                   uint64_t stats[3]) {
+  const hjapi::Tuning tn = hjapi::Tuning::from_env();
   hjapi::LightGrid g;
-  const int r = debug_grid(s, res, g);
+  const int r = debug_grid(s, res, tn, g);
   if (r == 0) return 0;
   if (planar) std::memcpy(planar, g.bits.data(), g.bits.size());
   if (mesh) { if (g.mesh_bits.empty()) std::memset(mesh, 0, g.bits.size()); else std::memcpy(mesh, g.mesh_bits.data(), g.mesh_bits.size()); }

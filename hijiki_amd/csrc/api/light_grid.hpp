@@ -22,7 +22,8 @@ struct LightGrid {
   size_t cells_surface = 0, cells_planar = 0, pairs_clear = 0;
 };
 
-// False (and an empty grid) when nothing can be proven for this scene.  Pure host code: no device call.
-bool build_light_grid(const hj_scene_desc* s, uint32_t res, LightGrid& out);
+// False (and an empty grid) when nothing can be proven for this scene.  Pure host code: no device call, no environment read.
+// mesh: also cells on meshes and in corners (HJ_LIGHT_GRID_MESH); timing: stage times on stderr (HJ_LIGHT_GRID_TIMING).
+bool build_light_grid(const hj_scene_desc* s, uint32_t res, bool mesh, bool timing, LightGrid& out);
 
 }  // namespace hjapi

@@ -270,71 +270,67 @@ __global__ void k_rl_records(RL r, float4* __restrict__ dev) {
 
 namespace hjapi {
 
+int place_node_array(DevBufs& bufs, size_t rec_bytes, size_t kept, float4** out) {
+  // The walk adds 32 * index to the low word of the array's address without a carry (kernels/hj_walk.h): the array must not
+  // cross a 4 GiB boundary.  Allocate twice the size and start at the boundary if it would.
+  const size_t bytes = std::max<size_t>(rec_bytes, 16) + 128;   // (slack: a whole 128-byte line may be read around the last record)
+  if (bytes >= (1ull << 32)) return set_error(bufs.ctx, HJ_ERR_UNSUPPORTED, "BVH of %zu records: the device node array is limited to 4 GiB", kept);
+  uint8_t* p = nullptr;
+  HJ_TRY(bufs.alloc(p, bytes));
+  uintptr_t start = reinterpret_cast<uintptr_t>(p);
+  if ((start >> 32) != ((start + bytes - 1) >> 32)) {
+    bufs.take(p).release();
+    HJ_TRY(bufs.alloc(p, 2 * bytes));
+    start = reinterpret_cast<uintptr_t>(p);
+    if ((start >> 32) != ((start + bytes - 1) >> 32)) start = ((start >> 32) + 1) << 32;
+  }
+  *out = reinterpret_cast<float4*>(start);
+  return HJ_OK;
+}
+
 int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangle* d_tris, const hj_vertex* d_verts, bool pairs_on,
-                       int node_order, float collapse_thr, bool timing, RelayoutOut& out, const hj_bvh_node* d_tree) {
+                       int node_order, float collapse_thr, bool timing, DevBufs& keep, RelayoutOut& out, const hj_bvh_node* d_tree) {
   // d_tree: the skip-link array is on the device already (hj_build_bvh_device's tree: hj_context::resident); s->bvh is not read then
   out = RelayoutOut{};
   const size_t N = s->num_bvh_nodes;
   if (N < 3 || N >= 0x3FFFFFFFu) return HJ_ERR_UNSUPPORTED;
   hipStream_t st = ctx->stream;
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!timing) return;
-    (void)hipStreamSynchronize(st);
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "hj_scene_upload (device): %-24s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  std::vector<DevBuf> tmp;                                  // released on return
-  struct Release { std::vector<DevBuf>& b; ~Release() { for (auto& x : b) x.release(); } } release{tmp};
-  tmp.reserve(32);
+  StageClock clock{timing, "hj_scene_upload (device): %-24s %8.2f ms\n", st};
+  DevBufs tmp(ctx);                                         // scratch: released on return
   int rc = HJ_OK;
-  auto scratch = [&](size_t bytes, void** p) -> int {
-    tmp.emplace_back();
-    const int rc2 = dev_alloc(ctx, tmp.back(), std::max<size_t>(bytes, 16));
-    *p = tmp.back().p;
-    return rc2;
-  };
-#define HJ_TMP(ptr, type, count) do { void* p_ = nullptr; rc = scratch(sizeof(type) * (count), &p_); if (rc != HJ_OK) return rc; ptr = static_cast<type*>(p_); } while (0)
-  auto keep = [&](size_t bytes, void** p) -> int {           // buffers that stay with the scene
-    ctx->scene_bufs.emplace_back();
-    const int rc2 = dev_alloc(ctx, ctx->scene_bufs.back(), std::max<size_t>(bytes, 16));
-    *p = ctx->scene_bufs.back().p;
-    return rc2;
-  };
   const uint32_t n32 = (uint32_t)N, nt = (uint32_t)s->num_triangles;
   const dim3 blk(256), grid((n32 + 255) / 256);
 
   // triangle records
   float4 *isect = nullptr, *shade = nullptr;
-  { void* p = nullptr; rc = keep(sizeof(float4) * 3 * (size_t)nt + 64, &p); if (rc != HJ_OK) return rc; isect = static_cast<float4*>(p); }
-  { void* p = nullptr; rc = keep(sizeof(float4) * 4 * (size_t)nt + 64, &p); if (rc != HJ_OK) return rc; shade = static_cast<float4*>(p); }
+  HJ_TRY(keep.alloc(isect, 3 * (size_t)nt, 64));
+  HJ_TRY(keep.alloc(shade, 4 * (size_t)nt, 64));
   if (nt) hipLaunchKernelGGL(k_rl_triangles, dim3((nt + 255) / 256), blk, 0, st, d_tris, d_verts, nt, isect, shade);
-  mark("triangle records");
+  clock.mark("triangle records");
 
   // the skip-link array as it is
   hj_bvh_node* d_bvh = const_cast<hj_bvh_node*>(d_tree);      // (the kernels only read it)
   if (!d_bvh) {
-    HJ_TMP(d_bvh, hj_bvh_node, N);
+    HJ_TRY(tmp.alloc(d_bvh, N));
     HJ_HIP(ctx, hipMemcpyAsync(d_bvh, s->bvh, sizeof(hj_bvh_node) * N, hipMemcpyHostToDevice, st));
   }
   RL r{};
   r.bvh = d_bvh; r.N = n32; r.first_tri = (uint32_t)(s->num_spheres + s->num_quads);
   r.nshapes = (uint32_t)(s->num_spheres + s->num_quads + s->num_triangles);
   r.thr = collapse_thr;
-  HJ_TMP(r.sa, float, N); HJ_TMP(r.anc, float, N); HJ_TMP(r.parent, uint32_t, N); HJ_TMP(r.nparents, uint32_t, N);
-  HJ_TMP(r.depth, uint32_t, N); HJ_TMP(r.del, uint8_t, N); HJ_TMP(r.is_hot, uint8_t, N); HJ_TMP(r.pair_flag, uint32_t, N);
-  HJ_TMP(r.pair_idx, uint32_t, N + 1); HJ_TMP(r.map, uint32_t, N); HJ_TMP(r.tsub, uint32_t, N); HJ_TMP(r.goff, uint32_t, N);
-  HJ_TMP(r.err, uint32_t, 4);
+  HJ_TRY(tmp.alloc(r.sa, N)); HJ_TRY(tmp.alloc(r.anc, N)); HJ_TRY(tmp.alloc(r.parent, N)); HJ_TRY(tmp.alloc(r.nparents, N));
+  HJ_TRY(tmp.alloc(r.depth, N)); HJ_TRY(tmp.alloc(r.del, N)); HJ_TRY(tmp.alloc(r.is_hot, N)); HJ_TRY(tmp.alloc(r.pair_flag, N));
+  HJ_TRY(tmp.alloc(r.pair_idx, N + 1)); HJ_TRY(tmp.alloc(r.map, N)); HJ_TRY(tmp.alloc(r.tsub, N)); HJ_TRY(tmp.alloc(r.goff, N));
+  HJ_TRY(tmp.alloc(r.err, 4));
   uint32_t *flag = nullptr, *rank = nullptr, *keys = nullptr, *vals = nullptr, *keys2 = nullptr, *vals2 = nullptr;
-  HJ_TMP(flag, uint32_t, N); HJ_TMP(rank, uint32_t, N + 1); HJ_TMP(keys, uint32_t, N); HJ_TMP(vals, uint32_t, N);
-  HJ_TMP(keys2, uint32_t, N); HJ_TMP(vals2, uint32_t, N);
+  HJ_TRY(tmp.alloc(flag, N)); HJ_TRY(tmp.alloc(rank, N + 1)); HJ_TRY(tmp.alloc(keys, N)); HJ_TRY(tmp.alloc(vals, N));
+  HJ_TRY(tmp.alloc(keys2, N)); HJ_TRY(tmp.alloc(vals2, N));
   HJ_HIP(ctx, hipMemsetAsync(r.err, 0, sizeof(uint32_t) * 4, st));
   size_t scan_bytes = 0, sort_bytes = 0;
   HJ_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, flag, rank, 0u, N, rocprim::plus<uint32_t>(), st));
   HJ_HIP(ctx, rocprim::radix_sort_pairs_desc(nullptr, sort_bytes, keys, keys2, vals, vals2, N, 0, 32, st));
-  void* prim_tmp = nullptr;
-  HJ_TMP(prim_tmp, uint8_t, std::max(scan_bytes, sort_bytes));
+  uint8_t* prim_tmp = nullptr;
+  HJ_TRY(tmp.alloc(prim_tmp, std::max(scan_bytes, sort_bytes)));
   size_t prim_bytes = std::max(scan_bytes, sort_bytes);
   uint32_t h_err[4] = {0, 0, 0, 0};
   auto read_err = [&]() -> int {
@@ -370,7 +366,7 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
   rc = read_err();
   if (rc != HJ_OK) return rc;
   if (h_err[0]) return HJ_ERR_UNSUPPORTED;                   // not a tree: the host path reasons about arbitrary arrays
-  mark("node upload + tree check");
+  clock.mark("node upload + tree check");
 
   // collapse, level by level (the levels end when one has no inner node)
   uint32_t levels = 0;
@@ -381,7 +377,7 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
     levels = h_err[2];                                       // deepest level + 1 that held an inner node
     if (levels < L + 16) break;
   }
-  mark("collapse");
+  clock.mark("collapse");
 
   // pair nodes
   uint32_t num_pairs = 0;
@@ -392,9 +388,9 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
     rc = last_of_scan(r.pair_flag, r.pair_idx, num_pairs);
     if (rc != HJ_OK) return rc;
   }
-  { void* p = nullptr; rc = keep(sizeof(float4) * 6 * (size_t)num_pairs + 64, &p); if (rc != HJ_OK) return rc; pairs = static_cast<float4*>(p); }
+  HJ_TRY(keep.alloc(pairs, 6 * (size_t)num_pairs, 64));
   if (num_pairs) hipLaunchKernelGGL(k_rl_pair_records, grid, blk, 0, st, r, isect, pairs);
-  mark("pair nodes");
+  clock.mark("pair nodes");
 
   // kept nodes, hot-first
   uint32_t M = 0;
@@ -406,7 +402,7 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
   HJ_HIP(ctx, rocprim::radix_sort_pairs_desc(prim_tmp, prim_bytes, keys, keys2, vals, vals2, M, 0, 32, st));   // stable: equal areas keep array order
   const uint32_t hot = std::min<uint32_t>(hj::kHotNodes, M);
   hipLaunchKernelGGL(k_rl_mark_hot, dim3((hot + 255) / 256), blk, 0, st, r, vals2, hot);
-  mark("hot-first sort");
+  clock.mark("hot-first sort");
 
   // order of the cold nodes
   uint32_t m_all = 0;
@@ -435,40 +431,24 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
     for (uint32_t L = 0; L <= levels; L++) hipLaunchKernelGGL(k_rl_group_offsets, grid, blk, 0, st, r, L);
     m_all = base + t_root;
   }
-  mark("node order");
+  clock.mark("node order");
 
   // device records (zero-filled padding), placed so that the array does not cross a 4 GiB boundary (kernels/hj_walk.h)
   if ((size_t)m_all + N >= hj::kEndOfWalk) return set_error(ctx, HJ_ERR_UNSUPPORTED, "BVH of %zu records: too large", (size_t)m_all + N);
   const size_t rec_bytes = sizeof(float4) * 2 * ((size_t)m_all + N);      // the two copies of the tree
-  const size_t bytes = std::max<size_t>(rec_bytes, 16) + 128;
-  if (bytes >= (1ull << 32)) return set_error(ctx, HJ_ERR_UNSUPPORTED, "BVH of %u records: the device node array is limited to 4 GiB", M);
-  ctx->scene_bufs.emplace_back();
-  {
-    DevBuf& b = ctx->scene_bufs.back();
-    rc = dev_alloc(ctx, b, bytes);
-    if (rc != HJ_OK) return rc;
-    uintptr_t start = reinterpret_cast<uintptr_t>(b.p);
-    if ((start >> 32) != ((start + bytes - 1) >> 32)) {
-      b.release();
-      rc = dev_alloc(ctx, b, 2 * bytes);
-      if (rc != HJ_OK) return rc;
-      start = reinterpret_cast<uintptr_t>(b.p);
-      if ((start >> 32) != ((start + bytes - 1) >> 32)) start = ((start >> 32) + 1) << 32;
-    }
-    float4* dev = reinterpret_cast<float4*>(start);
-    HJ_HIP(ctx, hipMemsetAsync(dev, 0, rec_bytes, st));
-    hipLaunchKernelGGL(k_rl_records, grid, blk, 0, st, r, dev);
-    hipLaunchKernelGGL(k_rl_records2, grid, blk, 0, st, r, dev, m_all);
-    out.nodes = dev;
-  }
+  float4* dev = nullptr;
+  HJ_TRY(place_node_array(keep, rec_bytes, M, &dev));
+  HJ_HIP(ctx, hipMemsetAsync(dev, 0, rec_bytes, st));
+  hipLaunchKernelGGL(k_rl_records, grid, blk, 0, st, r, dev);
+  hipLaunchKernelGGL(k_rl_records2, grid, blk, 0, st, r, dev, m_all);
+  out.nodes = dev;
   uint32_t root = 0;
   HJ_HIP(ctx, hipMemcpyAsync(&root, r.map, 4, hipMemcpyDeviceToHost, st));
   HJ_HIP(ctx, hipStreamSynchronize(st));
   HJ_HIP(ctx, hipGetLastError());
-  mark("device records");
+  clock.mark("device records");
   out.tri_isect = isect; out.tri_shade = shade; out.tri_pair = pairs;
   out.num_nodes = m_all + n32; out.root = root; out.root2 = m_all; out.num_hot = hot; out.num_pairs = num_pairs; out.kept = M;
-#undef HJ_TMP
   return HJ_OK;
 }
 

@@ -1,4 +1,6 @@
-// hj_scene_upload's re-layout on the device (scene_relayout.hip); the host path in scene_upload.hip is the reference for it.
+// hj_scene_upload's re-layout of the reference's tree into the kernels' records (kernels/hj_device.h): on the host
+// (scene_upload.hip, small trees and arrays that are not trees) or on the device (scene_relayout.hip, large trees and the tree
+// hj_build_bvh_device left there).  Both allocate what the scene keeps into the caller's set and fill the same RelayoutOut.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -16,10 +18,17 @@ struct RelayoutOut {
   size_t kept = 0;                     // records without padding
 };
 
+// The host path: every array comes from `s` (leaf guards, collapse, pair nodes, hot-first order, the second copy of the tree).
+int relayout_on_host(hj_context* ctx, const hj_scene_desc* s, const Tuning& tn, StageClock& clock, DevBufs& keep, RelayoutOut& out);
+
 // d_tris / d_verts: the scene's triangle and vertex arrays, already on the device.  node_order: HJ_NODE_ORDER (-1: by tree).
 // HJ_ERR_UNSUPPORTED: the array is not a tree (or a node has more kept children than the kernels enumerate) - the caller takes the
-// host path; buffers this call added to ctx->scene_bufs are the caller's to drop then.
+// host path; `keep` may hold some of this call's buffers then.
 int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangle* d_tris, const hj_vertex* d_verts, bool pairs_on,
-                       int node_order, float collapse_thr, bool timing, RelayoutOut& out, const hj_bvh_node* d_tree = nullptr);
+                       int node_order, float collapse_thr, bool timing, DevBufs& keep, RelayoutOut& out, const hj_bvh_node* d_tree = nullptr);
+
+// The node array (rec_bytes of records) in a new buffer of `bufs` that does not cross a 4 GiB boundary.  kept: records without
+// padding (for the error message).
+int place_node_array(DevBufs& bufs, size_t rec_bytes, size_t kept, float4** out);
 
 }  // namespace hjapi

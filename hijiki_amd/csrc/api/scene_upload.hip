@@ -115,103 +115,11 @@ void finish_tree_settings(hj::DeviceScene& d, const hjapi::Tuning& tn, size_t N,
 
 }  // namespace
 
-extern "C" {
+namespace hjapi {
 
-int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
-  if (!ctx) return HJ_ERR_INVALID;
-  HJ_NOT_BUSY(ctx);
-  HJ_NOT_PIPELINED(ctx);
-  if (!s) return set_error(ctx, HJ_ERR_INVALID, "null scene");
-  // HJ_UPLOAD_TIMING=1: wall time of the stages below on stderr
-  const Tuning tn = ctx->tuning = Tuning::from_env();
-  const bool timing = tn.upload_timing != 0;
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "hj_scene_upload: %-34s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  // scene->bvh == NULL: the tree hj_build_bvh_device left on this context's device, built over these very shape arrays
-  // (hj_context::resident) - no trip through the host for the tree, and the triangle / vertex arrays are on the device already
-  const bool resident = s->bvh == nullptr && s->num_bvh_nodes == 0;
-  hj_scene_desc with_tree;
-  if (resident) {
-    const hj_context::ResidentTree& rt = ctx->resident;
-    if (!rt.valid) return set_error(ctx, HJ_ERR_STATE, "scene->bvh is NULL and no tree is on the device: hj_build_bvh_device builds one");
-    if (rt.ns != s->num_spheres || rt.nq != s->num_quads || rt.nt != s->num_triangles || rt.nv != s->num_vertices ||
-        ((s->num_spheres == 0 || s->spheres) && (s->num_quads == 0 || s->quads) && (s->num_triangles == 0 || s->triangles) &&
-         (s->num_vertices == 0 || s->vertices) && rt.shapes_hash != shape_arrays_hash(s)))
-      return set_error(ctx, HJ_ERR_INVALID, "scene->bvh is NULL, but the tree on the device was built over other shape arrays (%zu / %zu / %zu shapes, %zu vertices)", rt.ns, rt.nq, rt.nt, rt.nv);
-  }
-  int rc = validate_scene(ctx, s);
-  if (rc != HJ_OK) return rc;
-  if (resident) { with_tree = *s; with_tree.num_bvh_nodes = ctx->resident.total; s = &with_tree; }   // (bvh stays NULL: nothing below reads it on this route)
-  mark("validation");
-  HJ_HIP(ctx, hipSetDevice(ctx->device));
-  rc = sync_all(ctx);
-  if (rc != HJ_OK) return rc;
-  release_scene(ctx);
-
-  hj::DeviceScene d{};
-  d.camera = s->camera;
-  d.tan_half_fov = (float)std::tan((double)(0.5f * s->camera.fov) * (3.14159265358979323846 / 180.0));
-  d.ns = (uint32_t)s->num_spheres;
-  d.nq = (uint32_t)s->num_quads;
-  d.nt = (uint32_t)s->num_triangles;
-  d.num_emitters = (uint32_t)s->num_emitters;
-  d.num_nodes = (uint32_t)s->num_bvh_nodes;
-  d.has_extinction = 0;
-  for (size_t i = 0; i < s->num_dielectric; i++)
-    if (s->dielectric[i].extinction[0] != 0.f || s->dielectric[i].extinction[1] != 0.f || s->dielectric[i].extinction[2] != 0.f)
-      d.has_extinction = 1;
-
-#define HJ_UP(expr) do { rc = (expr); if (rc != HJ_OK) { release_scene(ctx); return rc; } } while (0)
-  // Large trees: the whole re-layout below runs on the device (api/scene_relayout.hip: the arrays go up as they are, a dozen
-  // kernels derive the kernels' records) - 0.19 s of host work at 1 M triangles otherwise.  HJ_UPLOAD_DEVICE = 0 / 1 forces;
-  // default: from HJ_UPLOAD_DEVICE_MIN (100 000) nodes on.  An array that is not a tree takes the host path.
-  bool on_device = false;
-  {
-    const int env = tn.upload_device;
-    const bool want = resident || env == 1 || (env < 0 && s->num_bvh_nodes >= (size_t)tn.upload_device_min);
-    if (want && s->num_bvh_nodes >= 3) {
-      const size_t mark_bufs = ctx->scene_bufs.size();
-      if (resident) {                                         // the build's own copies become the scene's
-        ctx->scene_bufs.push_back(ctx->resident.triangles); d.triangles = static_cast<const hj_triangle*>(ctx->resident.triangles.p);
-        ctx->scene_bufs.push_back(ctx->resident.vertices); d.vertices = static_cast<const hj_vertex*>(ctx->resident.vertices.p);
-        ctx->resident.triangles = DevBuf{}; ctx->resident.vertices = DevBuf{};
-      } else {
-        HJ_UP(upload(ctx, s->triangles, s->num_triangles, &d.triangles));
-        HJ_UP(upload(ctx, s->vertices, s->num_vertices, &d.vertices));
-      }
-      mark("triangle + vertex upload");
-      const int pair_env = tn.pair_leaves;
-      const bool pairs_on = pair_env == 1 || (pair_env < 0 && s->num_bvh_nodes >= (size_t)tn.pair_min_nodes);
-      RelayoutOut ro;
-      rc = relayout_on_device(ctx, s, d.triangles, d.vertices, pairs_on, tn.node_order,
-                              (float)tn.collapse_pct / 100.0f, timing, ro,
-                              resident ? static_cast<const hj_bvh_node*>(ctx->resident.nodes.p) : nullptr);
-      if (resident && rc != HJ_OK) {                          // (no host array to fall back to)
-        release_scene(ctx);
-        ctx->resident.release();
-        return rc == HJ_ERR_UNSUPPORTED ? set_error(ctx, rc, "the tree on the device cannot be re-laid out there (fewer than 3 or too many records)") : rc;
-      }
-      if (rc == HJ_OK) {
-        on_device = true;
-        d.nodes = ro.nodes; d.tri_isect = ro.tri_isect; d.tri_shade = ro.tri_shade; d.tri_pair = ro.tri_pair;
-        d.num_nodes = ro.num_nodes; d.root = ro.root; d.root2 = ro.root2; d.num_hot = ro.num_hot; d.has_pairs = ro.num_pairs ? 1u : 0u;
-        finish_tree_settings(d, tn, s->num_bvh_nodes, ro.kept, ro.num_pairs != 0);
-      } else if (rc == HJ_ERR_UNSUPPORTED) {
-        while (ctx->scene_bufs.size() > mark_bufs) { ctx->scene_bufs.back().release(); ctx->scene_bufs.pop_back(); }
-        d.triangles = nullptr; d.vertices = nullptr;
-      } else {
-        release_scene(ctx);
-        return rc;
-      }
-    }
-  }
-  if (!on_device) {
-  // pre-gathered triangle records (see kernels/hj_device.h)
+// The host path of the re-layout (scene_relayout.hpp); scene_relayout.hip derives the same records on the device.
+int relayout_on_host(hj_context* ctx, const hj_scene_desc* s, const Tuning& tn, StageClock& clock, DevBufs& keep, RelayoutOut& out) {
+  out = RelayoutOut{};
   std::vector<float4> isect, shade;
   try {
     isect.resize(3 * s->num_triangles);
@@ -245,7 +153,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
     for (unsigned w = (unsigned)pool.size() + 1; w < hw; w++) gather(nt * w / hw, nt * (w + 1) / hw);   // (threads that could not be started)
     for (auto& th : pool) th.join();
   }
-  mark("triangle records");
+  clock.mark("triangle records");
   static_assert(sizeof(hj_bvh_node) == 2 * sizeof(float4), "node = 2 x float4");
   static_assert(sizeof(hj_quad) == 3 * sizeof(float4) && sizeof(hj_sphere) == sizeof(float4), "shape records");
   static_assert(sizeof(hj_diffuse_cb) == 2 * sizeof(float4), "checkerboard record");
@@ -384,7 +292,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
         anc[l] = anc[r] = del[i] ? anc[i] : sa[i];
       }
     }
-    mark("areas + collapse");
+    clock.mark("areas + collapse");
     // Pair nodes (kernels/hj_intersect.h leaf_test): an inner node whose two children are triangle leaves keeps its
     // record, the two leaves lose theirs (nothing but the pair's own walk ever reaches them: the left one is the
     // node's first child, the right one the left one's exit) and their triangles go side by side into `pairs`.
@@ -416,7 +324,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
         del[l] = del[r] = 1;                                              // no records for the two leaves
       }
     }
-    mark("pair nodes");
+    clock.mark("pair nodes");
     auto resolve = [&](size_t i) { while (i < N && del[i]) i++; return i; };   // first kept node of a subtree
     std::vector<uint32_t> order, map(N, 0);
     order.reserve(N);
@@ -431,7 +339,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
     for (size_t k = 0; k < hot; k++) { map[order[k]] = (uint32_t)k; is_hot[order[k]] = 1; }
     // (a treelet-blocked order - a node and its largest descendants per 128-byte line - was measured on the 1 M-triangle
     // scene before: within 1 % at 4, 8 and 16 records per treelet)
-    mark("hot-first sort");
+    clock.mark("hot-first sort");
     uint32_t next = hot;
     const int node_order = tn.node_order;                      // -1: by tree size (with the pair nodes)
     if (node_order == 0 || (node_order < 0 && pairs.empty())) {
@@ -464,7 +372,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
         for (size_t k = kids.size(); k-- > 0;) stack.push_back(kids[k]);
       }
     }
-    mark("node order");
+    clock.mark("node order");
     const size_t M_all = next;                                                       // records incl. padding
     std::vector<float4> dev(2 * M_all, make_float4(0.f, 0.f, 0.f, 0.f));
     for (size_t i = 0; i < N; i++) {
@@ -488,7 +396,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
     // records are never reached).  Rays that are not in general position start here (kernels/hj_intersect.h general_position):
     // for them the slab test is not monotone in a box's bounds, which the collapse and the guards rest on.
     const size_t N0 = s->num_bvh_nodes;
-    if (M_all + N0 >= hj::kEndOfWalk) { release_scene(ctx); return set_error(ctx, HJ_ERR_UNSUPPORTED, "BVH of %zu records: too large", M_all + N0); }
+    if (M_all + N0 >= hj::kEndOfWalk) return set_error(ctx, HJ_ERR_UNSUPPORTED, "BVH of %zu records: too large", M_all + N0);
     dev.resize(2 * (M_all + N0), make_float4(0.f, 0.f, 0.f, 0.f));
     for (size_t i = 0; i < N0; i++) {
       const hj_bvh_node& nd = s->bvh[i];
@@ -502,120 +410,209 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
       rec[0] = make_float4(nd.aabb_min[0], nd.aabb_min[1], nd.aabb_min[2], __builtin_bit_cast(float, a));
       rec[1] = make_float4(nd.aabb_max[0], nd.aabb_max[1], nd.aabb_max[2], __builtin_bit_cast(float, b));
     }
-    mark("device records");
-    HJ_UP(upload(ctx, pairs.data(), pairs.size(), &d.tri_pair));
-    d.has_pairs = pairs.empty() ? 0u : 1u;
-    d.num_nodes = (uint32_t)(M_all + N0);
-    d.root = N ? map[0] : 0u;
-    d.root2 = (uint32_t)M_all;
-    d.num_hot = hot;
-    finish_tree_settings(d, tn, s->num_bvh_nodes, M, !pairs.empty());
-    // The walk adds 32 * index to the low word of the array's address without a carry (kernels/hj_walk.h): the
-    // array must not cross a 4 GiB boundary.  Allocate twice the size and start at the boundary if it would.
-    {
-      const size_t bytes = std::max<size_t>(dev.size() * sizeof(float4), 16) + 128;   // (slack: a whole 128-byte line may be read around the last record)
-      if (bytes >= (1ull << 32)) { release_scene(ctx); return set_error(ctx, HJ_ERR_UNSUPPORTED, "BVH of %zu records: the device node array is limited to 4 GiB", M); }
-      ctx->scene_bufs.emplace_back();
-      DevBuf& b = ctx->scene_bufs.back();
-      HJ_UP(dev_alloc(ctx, b, bytes));
-      uintptr_t start = reinterpret_cast<uintptr_t>(b.p);
-      if ((start >> 32) != ((start + bytes - 1) >> 32)) {
-        b.release();
-        HJ_UP(dev_alloc(ctx, b, 2 * bytes));
-        start = reinterpret_cast<uintptr_t>(b.p);
-        if ((start >> 32) != ((start + bytes - 1) >> 32)) start = ((start >> 32) + 1) << 32;
-      }
-      if (hipMemcpy(reinterpret_cast<void*>(start), dev.data(), dev.size() * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) {
-        release_scene(ctx);
-        return set_error(ctx, HJ_ERR_DEVICE, "node upload failed");
-      }
-      d.nodes = reinterpret_cast<const float4*>(start);
-    }
+    clock.mark("device records");
+    HJ_TRY(upload(keep, pairs.data(), pairs.size(), &out.tri_pair));
+    out.num_pairs = (uint32_t)(pairs.size() / 6);
+    out.num_nodes = (uint32_t)(M_all + N0);
+    out.root = N ? map[0] : 0u;
+    out.root2 = (uint32_t)M_all;
+    out.num_hot = hot;
+    out.kept = M;
+    float4* nodes = nullptr;
+    HJ_TRY(place_node_array(keep, dev.size() * sizeof(float4), M, &nodes));
+    if (hipMemcpy(nodes, dev.data(), dev.size() * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess)
+      return set_error(ctx, HJ_ERR_DEVICE, "node upload failed");
+    out.nodes = nodes;
   }
-  mark("pair + node upload");
-  HJ_UP(upload(ctx, isect.data(), isect.size(), &d.tri_isect));
-  HJ_UP(upload(ctx, shade.data(), shade.size(), &d.tri_shade));
-  HJ_UP(upload(ctx, s->triangles, s->num_triangles, &d.triangles));
-  HJ_UP(upload(ctx, s->vertices, s->num_vertices, &d.vertices));
-  }   // (!on_device)
-  HJ_UP(upload(ctx, reinterpret_cast<const float4*>(s->spheres), s->num_spheres, &d.spheres));
-  HJ_UP(upload(ctx, reinterpret_cast<const float4*>(s->quads), 3 * s->num_quads, &d.quads));
-  HJ_UP(upload(ctx, s->materials, s->num_materials, &d.materials));
-  HJ_UP(upload(ctx, s->emitters, s->num_emitters, &d.emitters));
-  {
-    std::vector<float4> rec((size_t)hj::kEmitRecF4 * s->num_emitters, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (size_t i = 0; i < s->num_emitters; i++) {
-      float4* r = &rec[(size_t)hj::kEmitRecF4 * i];
-      const uint32_t shape = s->emitters[i].shape;
-      const hj_emissive& em = s->emissive[s->materials[shape] & HJ_MATERIAL_INDEX_MASK];
-      uint32_t kind;
-      if (shape < s->num_spheres) {
-        kind = 0;
-        const hj_sphere& sp = s->spheres[shape];
-        r[1] = make_float4(sp.center[0], sp.center[1], sp.center[2], 0.f);
-        r[0].z = sp.radius;
-      } else if (shape < s->num_spheres + s->num_quads) {
-        kind = 1;
-        const hj_quad& q = s->quads[shape - s->num_spheres];
-        r[1] = make_float4(q.origin[0], q.origin[1], q.origin[2], 0.f);
-        r[2] = make_float4(q.edge1[0], q.edge1[1], q.edge1[2], 0.f);
-        r[3] = make_float4(q.edge2[0], q.edge2[1], q.edge2[2], 0.f);
-      } else {
-        kind = 2;
-        const hj_triangle& t = s->triangles[shape - s->num_spheres - s->num_quads];
-        for (int k = 0; k < 3; k++) {
-          const hj_vertex& v = s->vertices[t.v[k]];
-          r[1 + k] = make_float4(v.pos[0], v.pos[1], v.pos[2], 0.f);
-          r[4 + k] = make_float4(v.normal[0], v.normal[1], v.normal[2], 0.f);
-        }
-      }
-      r[0].x = s->emitters[i].pdf;
-      r[0].y = __builtin_bit_cast(float, kind);
-      r[1].w = em.power[0]; r[2].w = em.power[1]; r[3].w = em.power[2];
-    }
-    HJ_UP(upload(ctx, rec.data(), rec.size(), &d.emit_rec));
+  clock.mark("pair + node upload");
+  HJ_TRY(upload(keep, isect.data(), isect.size(), &out.tri_isect));
+  HJ_TRY(upload(keep, shade.data(), shade.size(), &out.tri_shade));
+  return HJ_OK;
+}
+
+}  // namespace hjapi
+
+namespace {
+
+// The re-layout on the device (api/scene_relayout.hip): the triangle and vertex arrays go up as they are - or, on the resident route,
+// are the build's own, borrowed until hj_scene_upload commits.  What the attempt allocates joins `bufs` only when it succeeds:
+// HJ_ERR_UNSUPPORTED (the array is not a tree) drops exactly the attempt's buffers, and the host path runs instead (and sets
+// d.triangles / d.vertices again).
+int relayout_device_route(hj_context* ctx, const hj_scene_desc* s, const Tuning& tn, bool resident, StageClock& clock, DevBufs& bufs,
+                          hj::DeviceScene& d, RelayoutOut& ro) {
+  DevBufs attempt(ctx);
+  if (resident) {
+    d.triangles = static_cast<const hj_triangle*>(ctx->resident.triangles.p);
+    d.vertices = static_cast<const hj_vertex*>(ctx->resident.vertices.p);
+  } else {
+    HJ_TRY(upload(attempt, s->triangles, s->num_triangles, &d.triangles));
+    HJ_TRY(upload(attempt, s->vertices, s->num_vertices, &d.vertices));
   }
-  HJ_UP(upload(ctx, reinterpret_cast<const float4*>(s->diffuse), s->num_diffuse, &d.diffuse));
-  HJ_UP(upload(ctx, reinterpret_cast<const float4*>(s->diffusecb), 2 * s->num_diffusecb, &d.diffusecb));
-  HJ_UP(upload(ctx, reinterpret_cast<const float4*>(s->dielectric), s->num_dielectric, &d.dielectric));
-  HJ_UP(upload(ctx, reinterpret_cast<const float4*>(s->emissive), s->num_emissive, &d.emissive));
-  mark("other uploads");
-  // Light-shaft visibility grid (api/light_grid.cpp): which next-event shadow rays are unoccluded whatever happens.  HJ_LIGHT_GRID =
-  // cells per axis (0: none).  Default: 64 up to HJ_STREAM_MIN_NODES (300 000) tree nodes, none beyond - on the 1 M-triangle scene
-  // a third of the shadow rays is proven free and the frame rate does not move (they are the cheap rays: a dozen steps on
-  // LDS-resident nodes against the mesh rays' seventeen cold ones), while the build costs 50 ms of start-up there.
-  {
-    const int big = (int)(s->num_bvh_nodes >= (size_t)tn.stream_min_nodes);
-    const int res = Tuning::pick(tn.light_grid, big ? 0 : 64);
-    LightGrid lg;
-    bool have_grid = false;
-    std::vector<hj_bvh_node> host_tree;                       // (the grid is host code: a tree that lives on the device comes back for it)
-    hj_scene_desc for_grid = *s;
-    try {
-      if (res >= 2 && resident) {
-        host_tree.resize(ctx->resident.total);
-        if (hipMemcpy(host_tree.data(), ctx->resident.nodes.p, sizeof(hj_bvh_node) * host_tree.size(), hipMemcpyDeviceToHost) != hipSuccess) host_tree.clear();
-        for_grid.bvh = host_tree.data();
+  clock.mark("triangle + vertex upload");
+  const bool pairs_on = tn.pair_leaves == 1 || (tn.pair_leaves < 0 && s->num_bvh_nodes >= (size_t)tn.pair_min_nodes);
+  HJ_TRY(relayout_on_device(ctx, s, d.triangles, d.vertices, pairs_on, tn.node_order, (float)tn.collapse_pct / 100.0f, clock.on, attempt,
+                            ro, resident ? static_cast<const hj_bvh_node*>(ctx->resident.nodes.p) : nullptr));
+  attempt.move_into(bufs);
+  return HJ_OK;
+}
+
+// Per emitter, the kEmitRecF4 float4s next-event estimation samples it from (kernels/hj_device.h).
+std::vector<float4> emitter_records(const hj_scene_desc* s) {
+  std::vector<float4> rec((size_t)hj::kEmitRecF4 * s->num_emitters, make_float4(0.f, 0.f, 0.f, 0.f));
+  for (size_t i = 0; i < s->num_emitters; i++) {
+    float4* r = &rec[(size_t)hj::kEmitRecF4 * i];
+    const uint32_t shape = s->emitters[i].shape;
+    const hj_emissive& em = s->emissive[s->materials[shape] & HJ_MATERIAL_INDEX_MASK];
+    uint32_t kind;
+    if (shape < s->num_spheres) {
+      kind = 0;
+      const hj_sphere& sp = s->spheres[shape];
+      r[1] = make_float4(sp.center[0], sp.center[1], sp.center[2], 0.f);
+      r[0].z = sp.radius;
+    } else if (shape < s->num_spheres + s->num_quads) {
+      kind = 1;
+      const hj_quad& q = s->quads[shape - s->num_spheres];
+      r[1] = make_float4(q.origin[0], q.origin[1], q.origin[2], 0.f);
+      r[2] = make_float4(q.edge1[0], q.edge1[1], q.edge1[2], 0.f);
+      r[3] = make_float4(q.edge2[0], q.edge2[1], q.edge2[2], 0.f);
+    } else {
+      kind = 2;
+      const hj_triangle& t = s->triangles[shape - s->num_spheres - s->num_quads];
+      for (int k = 0; k < 3; k++) {
+        const hj_vertex& v = s->vertices[t.v[k]];
+        r[1 + k] = make_float4(v.pos[0], v.pos[1], v.pos[2], 0.f);
+        r[4 + k] = make_float4(v.normal[0], v.normal[1], v.normal[2], 0.f);
       }
-      have_grid = res >= 2 && (!resident || !host_tree.empty()) && build_light_grid(&for_grid, (uint32_t)res, lg);
-    } catch (const std::exception&) { have_grid = false; }   // (out of host memory: no grid)
-    if (have_grid) {
-      // cells (low byte: planar proofs; high byte: bundle proofs, for hits that were not grazing), then - 16-byte aligned - the
-      // records the shade stage checks a hit point against its shape with (kernels/hj_shade.h shadow_ray_proven_free)
-      const size_t ncell = lg.bits.size(), cells_u16 = (ncell + 7) & ~(size_t)7;
-      std::vector<uint16_t> cells(cells_u16 + lg.shape_recs.size() * 2, 0);
-      for (size_t i = 0; i < ncell; i++) cells[i] = (uint16_t)(lg.bits[i] | (lg.mesh_bits.empty() ? 0u : (uint32_t)lg.mesh_bits[i] << 8));
-      if (!lg.shape_recs.empty()) std::memcpy(cells.data() + cells_u16, lg.shape_recs.data(), lg.shape_recs.size() * sizeof(float));
-      HJ_UP(upload(ctx, cells.data(), cells.size(), &d.light_grid));
-      d.lg_res = lg.res | (lg.shape_recs.empty() ? 0u : hj::kLightGridHasRecords);
-      for (int k = 0; k < 3; k++) { d.lg_lo[k] = lg.lo[k]; d.lg_inv[k] = lg.inv[k]; }
-      if (timing) std::fprintf(stderr, "hj_scene_upload: light grid %u^3: %zu cells hold a surface, %zu a planar one, %zu (cell, emitter) pairs proven free\n",
-                               lg.res, lg.cells_surface, lg.cells_planar, lg.pairs_clear);
     }
+    r[0].x = s->emitters[i].pdf;
+    r[0].y = __builtin_bit_cast(float, kind);
+    r[1].w = em.power[0]; r[2].w = em.power[1]; r[3].w = em.power[2];
   }
-  mark("light-shaft grid");
-#undef HJ_UP
-  if (resident) ctx->resident.release();                     // consumed (hipFree waits for the kernels that read the tree)
+  return rec;
+}
+
+// Light-shaft visibility grid (api/light_grid.cpp): which next-event shadow rays are unoccluded whatever happens.  HJ_LIGHT_GRID =
+// cells per axis (0: none).  Default: 64 up to HJ_STREAM_MIN_NODES (300 000) tree nodes, none beyond - on the 1 M-triangle scene
+// a third of the shadow rays is proven free and the frame rate does not move (they are the cheap rays: a dozen steps on
+// LDS-resident nodes against the mesh rays' seventeen cold ones), while the build costs 50 ms of start-up there.
+// d_tree: the tree when it is on the device only (the grid is host code: the tree comes back for it).
+int upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, const hj_bvh_node* d_tree, hj::DeviceScene& d) {
+  const int res = Tuning::pick(tn.light_grid, s->num_bvh_nodes >= (size_t)tn.stream_min_nodes ? 0 : 64);
+  if (res < 2) return HJ_OK;
+  LightGrid lg;
+  std::vector<hj_bvh_node> host_tree;
+  hj_scene_desc for_grid = *s;
+  try {
+    if (d_tree) {
+      host_tree.resize(s->num_bvh_nodes);
+      if (hipMemcpy(host_tree.data(), d_tree, sizeof(hj_bvh_node) * host_tree.size(), hipMemcpyDeviceToHost) != hipSuccess) return HJ_OK;
+      for_grid.bvh = host_tree.data();
+    }
+    if (!build_light_grid(&for_grid, (uint32_t)res, tn.light_grid_mesh != 0, tn.light_grid_timing, lg)) return HJ_OK;
+  } catch (const std::exception&) { return HJ_OK; }         // (out of host memory: no grid)
+  // cells (low byte: planar proofs; high byte: bundle proofs, for hits that were not grazing), then - 16-byte aligned - the
+  // records the shade stage checks a hit point against its shape with (kernels/hj_shade.h shadow_ray_proven_free)
+  const size_t ncell = lg.bits.size(), cells_u16 = (ncell + 7) & ~(size_t)7;
+  std::vector<uint16_t> cells(cells_u16 + lg.shape_recs.size() * 2, 0);
+  for (size_t i = 0; i < ncell; i++) cells[i] = (uint16_t)(lg.bits[i] | (lg.mesh_bits.empty() ? 0u : (uint32_t)lg.mesh_bits[i] << 8));
+  if (!lg.shape_recs.empty()) std::memcpy(cells.data() + cells_u16, lg.shape_recs.data(), lg.shape_recs.size() * sizeof(float));
+  HJ_TRY(upload(bufs, cells.data(), cells.size(), &d.light_grid));
+  d.lg_res = lg.res | (lg.shape_recs.empty() ? 0u : hj::kLightGridHasRecords);
+  for (int k = 0; k < 3; k++) { d.lg_lo[k] = lg.lo[k]; d.lg_inv[k] = lg.inv[k]; }
+  if (tn.upload_timing) std::fprintf(stderr, "hj_scene_upload: light grid %u^3: %zu cells hold a surface, %zu a planar one, %zu (cell, emitter) pairs proven free\n",
+                                     lg.res, lg.cells_surface, lg.cells_planar, lg.pairs_clear);
+  return HJ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
+  if (!ctx) return HJ_ERR_INVALID;
+  HJ_NOT_BUSY(ctx);
+  HJ_NOT_PIPELINED(ctx);
+  if (!s) return set_error(ctx, HJ_ERR_INVALID, "null scene");
+  // HJ_UPLOAD_TIMING=1: wall time of the stages below on stderr
+  const Tuning tn = ctx->tuning = Tuning::from_env();
+  StageClock clock{tn.upload_timing != 0, "hj_scene_upload: %-34s %8.2f ms\n"};
+  // scene->bvh == NULL: the tree hj_build_bvh_device left on this context's device, built over these very shape arrays
+  // (hj_context::resident) - no trip through the host for the tree, and the triangle / vertex arrays are on the device already
+  const bool resident = s->bvh == nullptr && s->num_bvh_nodes == 0;
+  hj_context::ResidentTree& rt = ctx->resident;
+  if (resident) {
+    if (!rt.valid) return set_error(ctx, HJ_ERR_STATE, "scene->bvh is NULL and no tree is on the device: hj_build_bvh_device builds one");
+    if (rt.ns != s->num_spheres || rt.nq != s->num_quads || rt.nt != s->num_triangles || rt.nv != s->num_vertices ||
+        ((s->num_spheres == 0 || s->spheres) && (s->num_quads == 0 || s->quads) && (s->num_triangles == 0 || s->triangles) &&
+         (s->num_vertices == 0 || s->vertices) && rt.shapes_hash != shape_arrays_hash(s)))
+      return set_error(ctx, HJ_ERR_INVALID, "scene->bvh is NULL, but the tree on the device was built over other shape arrays (%zu / %zu / %zu shapes, %zu vertices)", rt.ns, rt.nq, rt.nt, rt.nv);
+  }
+  HJ_TRY(validate_scene(ctx, s));
+  hj_scene_desc with_tree;
+  if (resident) { with_tree = *s; with_tree.num_bvh_nodes = rt.total; s = &with_tree; }   // (bvh stays NULL: nothing below reads it on this route)
+  clock.mark("validation");
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  HJ_TRY(sync_all(ctx));
+  release_scene(ctx);                                        // (first: the new scene does not sit beside the old one)
+
+  // The stages build the new scene into `bufs` and `d`; it becomes the context's only when all of them have succeeded.  A failure
+  // frees what this call allocated and leaves the tree on the device (hj_context::resident) as it was: its arrays are borrowed.
+  DevBufs bufs(ctx);
+  hj::DeviceScene d{};
+  d.camera = s->camera;
+  d.tan_half_fov = (float)std::tan((double)(0.5f * s->camera.fov) * (3.14159265358979323846 / 180.0));
+  d.ns = (uint32_t)s->num_spheres;
+  d.nq = (uint32_t)s->num_quads;
+  d.nt = (uint32_t)s->num_triangles;
+  d.num_emitters = (uint32_t)s->num_emitters;
+  d.has_extinction = 0;
+  for (size_t i = 0; i < s->num_dielectric; i++)
+    if (s->dielectric[i].extinction[0] != 0.f || s->dielectric[i].extinction[1] != 0.f || s->dielectric[i].extinction[2] != 0.f)
+      d.has_extinction = 1;
+
+  // Large trees: the whole re-layout runs on the device (api/scene_relayout.hip: the arrays go up as they are, a dozen kernels
+  // derive the kernels' records) - 0.19 s of host work at 1 M triangles otherwise.  HJ_UPLOAD_DEVICE = 0 / 1 forces; default: from
+  // HJ_UPLOAD_DEVICE_MIN (100 000) nodes on.  An array that is not a tree takes the host path.
+  RelayoutOut ro;
+  int rc = HJ_ERR_UNSUPPORTED;
+  const int env = tn.upload_device;
+  if ((resident || env == 1 || (env < 0 && s->num_bvh_nodes >= (size_t)tn.upload_device_min)) && s->num_bvh_nodes >= 3)
+    rc = relayout_device_route(ctx, s, tn, resident, clock, bufs, d, ro);
+  if (rc == HJ_ERR_UNSUPPORTED && resident)                 // (no host array to fall back to)
+    return set_error(ctx, rc, "the tree on the device cannot be re-laid out there (fewer than 3 or too many records)");
+  if (rc == HJ_ERR_UNSUPPORTED) {
+    HJ_TRY(relayout_on_host(ctx, s, tn, clock, bufs, ro));
+    HJ_TRY(upload(bufs, s->triangles, s->num_triangles, &d.triangles));
+    HJ_TRY(upload(bufs, s->vertices, s->num_vertices, &d.vertices));
+  } else if (rc != HJ_OK) {
+    return rc;
+  }
+  d.nodes = ro.nodes; d.tri_isect = ro.tri_isect; d.tri_shade = ro.tri_shade; d.tri_pair = ro.tri_pair;
+  d.num_nodes = ro.num_nodes; d.root = ro.root; d.root2 = ro.root2; d.num_hot = ro.num_hot; d.has_pairs = ro.num_pairs ? 1u : 0u;
+  finish_tree_settings(d, tn, s->num_bvh_nodes, ro.kept, ro.num_pairs != 0);
+
+  HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->spheres), s->num_spheres, &d.spheres));
+  HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->quads), 3 * s->num_quads, &d.quads));
+  HJ_TRY(upload(bufs, s->materials, s->num_materials, &d.materials));
+  HJ_TRY(upload(bufs, s->emitters, s->num_emitters, &d.emitters));
+  const std::vector<float4> emit_rec = emitter_records(s);
+  HJ_TRY(upload(bufs, emit_rec.data(), emit_rec.size(), &d.emit_rec));
+  HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->diffuse), s->num_diffuse, &d.diffuse));
+  HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->diffusecb), 2 * s->num_diffusecb, &d.diffusecb));
+  HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->dielectric), s->num_dielectric, &d.dielectric));
+  HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->emissive), s->num_emissive, &d.emissive));
+  clock.mark("other uploads");
+  HJ_TRY(upload_light_grid(bufs, s, tn, resident ? static_cast<const hj_bvh_node*>(rt.nodes.p) : nullptr, d));
+  clock.mark("light-shaft grid");
+
+  // commit: the buffers become the scene's; on the resident route the build's triangle and vertex arrays join them and the rest of
+  // the tree is consumed (hipFree waits for the kernels that read it)
+  bufs.move_into(ctx->scene_bufs);
+  if (resident) {
+    ctx->scene_bufs.bufs.push_back(std::move(rt.triangles));
+    ctx->scene_bufs.bufs.push_back(std::move(rt.vertices));
+    rt.release();
+  }
   ctx->scene = d;
   ctx->have_scene = true;
   return HJ_OK;

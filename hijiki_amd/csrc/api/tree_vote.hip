@@ -10,23 +10,6 @@ using namespace hjapi;
 
 namespace hjapi {
 
-namespace {
-struct Scratch {
-  hj_context* ctx;
-  std::vector<DevBuf> bufs;
-  explicit Scratch(hj_context* c) : ctx(c) { bufs.reserve(24); }
-  ~Scratch() { for (auto& b : bufs) b.release(); }
-  int get(size_t bytes, void** p) {
-    bufs.emplace_back();
-    const int rc = dev_alloc(ctx, bufs.back(), std::max<size_t>(bytes, 16));
-    *p = bufs.back().p;
-    return rc;
-  }
-};
-}  // namespace
-
-#define HJ_SCRATCH(sc, ptr, type, count) do { void* p_ = nullptr; const int rc_ = (sc).get(sizeof(type) * (count), &p_); if (rc_ != HJ_OK) return rc_; ptr = static_cast<type*>(p_); } while (0)
-
 int vote_on_device(hj_context* ctx, const hj_scene_desc* s, const VoteShapes& shapes, const hj_bvh_node* d_nodes, size_t N, size_t paths,
                    hj_bvh_node* d_out, bool timing, VoteResult* result) {
   hipStream_t st = ctx->stream;
@@ -37,15 +20,8 @@ int vote_on_device(hj_context* ctx, const hj_scene_desc* s, const VoteShapes& sh
   }
   if (N >= 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_UNSUPPORTED, "tree of %zu records: too large for the device vote", N);
   paths = std::min<size_t>(paths, (size_t)1 << 24);
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!timing) return;
-    (void)hipStreamSynchronize(st);
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "ray-voted child order (device): %-20s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  Scratch sc(ctx);
+  StageClock clock{timing, "ray-voted child order (device): %-20s %8.2f ms\n", st};
+  DevBufs sc(ctx);
   const size_t nshapes = s->num_spheres + s->num_quads + s->num_triangles;
   hj::vote::Scene vs{};
   vs.spheres = shapes.spheres; vs.quads = shapes.quads; vs.triangles = shapes.triangles; vs.vertices = shapes.vertices;
@@ -56,37 +32,37 @@ int vote_on_device(hj_context* ctx, const hj_scene_desc* s, const VoteShapes& sh
   vs.w_shadow = (uint32_t)Tuning::pick(ctx->tuning.bvh_vote_shadow, N >= (size_t)ctx->tuning.stream_min_nodes ? 4 : 1);
   if (s->materials && s->num_materials == nshapes && nshapes) {
     uint32_t* m = nullptr;
-    HJ_SCRATCH(sc, m, uint32_t, nshapes);
+    HJ_TRY(sc.alloc(m, nshapes));
     HJ_HIP(ctx, hipMemcpyAsync(m, s->materials, sizeof(uint32_t) * nshapes, hipMemcpyHostToDevice, st));
     vs.materials = m;
   }
   if (s->emitters && s->num_emitters) {
     hj_emitter* e = nullptr;
-    HJ_SCRATCH(sc, e, hj_emitter, s->num_emitters);
+    HJ_TRY(sc.alloc(e, s->num_emitters));
     HJ_HIP(ctx, hipMemcpyAsync(e, s->emitters, sizeof(hj_emitter) * s->num_emitters, hipMemcpyHostToDevice, st));
     vs.emitters = e; vs.ne = (uint32_t)std::min<size_t>(s->num_emitters, 0x7FFFFFFFu);
   }
   if (s->dielectric && s->num_dielectric) {
     hj_dielectric* d = nullptr;
-    HJ_SCRATCH(sc, d, hj_dielectric, s->num_dielectric);
+    HJ_TRY(sc.alloc(d, s->num_dielectric));
     HJ_HIP(ctx, hipMemcpyAsync(d, s->dielectric, sizeof(hj_dielectric) * s->num_dielectric, hipMemcpyHostToDevice, st));
     vs.dielectric = d; vs.ndielectric = (uint32_t)std::min<size_t>(s->num_dielectric, 0x7FFFFFFFu);
   }
-  HJ_SCRATCH(sc, vs.gain_l, unsigned long long, N);
-  HJ_SCRATCH(sc, vs.gain_r, unsigned long long, N);
+  HJ_TRY(sc.alloc(vs.gain_l, N));
+  HJ_TRY(sc.alloc(vs.gain_r, N));
   HJ_HIP(ctx, hipMemsetAsync(vs.gain_l, 0, sizeof(unsigned long long) * N, st));
   HJ_HIP(ctx, hipMemsetAsync(vs.gain_r, 0, sizeof(unsigned long long) * N, st));
-  mark("uploads");
+  clock.mark("uploads");
   const uint32_t np = (uint32_t)paths;
   hipLaunchKernelGGL(hj::vote::k_vote_paths, dim3((np + 63u) / 64u), dim3(64), 0, st, vs, np);
-  mark("sampled paths");
+  clock.mark("sampled paths");
 
   hj::vote::Reorder r{};
   r.in = vs.nodes; r.out = reinterpret_cast<float4*>(d_out); r.N = vs.N; r.gain_l = vs.gain_l; r.gain_r = vs.gain_r;
-  HJ_SCRATCH(sc, r.depth, uint32_t, N);
-  HJ_SCRATCH(sc, r.npos, uint32_t, N);
-  HJ_SCRATCH(sc, r.nexit, uint32_t, N);
-  HJ_SCRATCH(sc, r.info, uint32_t, 4);
+  HJ_TRY(sc.alloc(r.depth, N));
+  HJ_TRY(sc.alloc(r.npos, N));
+  HJ_TRY(sc.alloc(r.nexit, N));
+  HJ_TRY(sc.alloc(r.info, 4));
   HJ_HIP(ctx, hipMemsetAsync(r.info, 0, sizeof(uint32_t) * 4, st));
   const dim3 blk(256), grid((vs.N + 255u) / 256u);
   hipLaunchKernelGGL(hj::vote::k_ro_init, grid, blk, 0, st, r);
@@ -101,7 +77,7 @@ int vote_on_device(hj_context* ctx, const hj_scene_desc* s, const VoteShapes& sh
   HJ_HIP(ctx, hipMemcpyAsync(info, r.info, sizeof info, hipMemcpyDeviceToHost, st));
   HJ_HIP(ctx, hipStreamSynchronize(st));
   HJ_HIP(ctx, hipGetLastError());
-  mark("exchange");
+  clock.mark("exchange");
   if (info[2] & 1u) return set_error(ctx, HJ_ERR_INVALID, "ray-voted child order: the array is not a pre-order skip-link tree");
   if (info[2] & 2u) return set_error(ctx, HJ_ERR_UNSUPPORTED, "ray-voted child order: the tree is deeper than 8192 levels");
   if (result) { result->exchanged = info[1]; result->levels = info[0]; }
@@ -112,14 +88,14 @@ int vote_on_device(hj_context* ctx, const hj_scene_desc* s, const VoteShapes& sh
 int put_records(hj_context* ctx, const std::vector<std::pair<uint32_t, hj_bvh_node>>& records, hj_bvh_node* d_array) {
   if (records.empty()) return HJ_OK;
   hipStream_t st = ctx->stream;
-  Scratch sc(ctx);
+  DevBufs sc(ctx);
   std::vector<uint32_t> pos(records.size());
   std::vector<hj_bvh_node> rec(records.size());
   for (size_t k = 0; k < records.size(); k++) { pos[k] = records[k].first; rec[k] = records[k].second; }
   uint32_t* d_pos = nullptr;
   hj_bvh_node* d_rec = nullptr;
-  HJ_SCRATCH(sc, d_pos, uint32_t, pos.size());
-  HJ_SCRATCH(sc, d_rec, hj_bvh_node, rec.size());
+  HJ_TRY(sc.alloc(d_pos, pos.size()));
+  HJ_TRY(sc.alloc(d_rec, rec.size()));
   HJ_HIP(ctx, hipMemcpyAsync(d_pos, pos.data(), sizeof(uint32_t) * pos.size(), hipMemcpyHostToDevice, st));
   HJ_HIP(ctx, hipMemcpyAsync(d_rec, rec.data(), sizeof(hj_bvh_node) * rec.size(), hipMemcpyHostToDevice, st));
   const uint32_t n = (uint32_t)records.size();
@@ -148,17 +124,17 @@ int hj_tune_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* out
   const Tuning tn = ctx->tuning = Tuning::from_env();
   const bool timing = tn.lbvh_timing != 0;
   hipStream_t st = ctx->stream;
-  Scratch sc(ctx);
+  DevBufs sc(ctx);
   float4 *sp = nullptr, *qd = nullptr;
   hj_triangle* tr = nullptr;
   hj_vertex* vx = nullptr;
   hj_bvh_node *d_in = nullptr, *d_out = nullptr;
-  HJ_SCRATCH(sc, sp, float4, s->num_spheres);
-  HJ_SCRATCH(sc, qd, float4, 3 * s->num_quads);
-  HJ_SCRATCH(sc, tr, hj_triangle, s->num_triangles);
-  HJ_SCRATCH(sc, vx, hj_vertex, s->num_vertices);
-  HJ_SCRATCH(sc, d_in, hj_bvh_node, N);
-  HJ_SCRATCH(sc, d_out, hj_bvh_node, N);
+  HJ_TRY(sc.alloc(sp, s->num_spheres));
+  HJ_TRY(sc.alloc(qd, 3 * s->num_quads));
+  HJ_TRY(sc.alloc(tr, s->num_triangles));
+  HJ_TRY(sc.alloc(vx, s->num_vertices));
+  HJ_TRY(sc.alloc(d_in, N));
+  HJ_TRY(sc.alloc(d_out, N));
   if (s->num_spheres) HJ_HIP(ctx, hipMemcpyAsync(sp, s->spheres, sizeof(float4) * s->num_spheres, hipMemcpyHostToDevice, st));
   if (s->num_quads) HJ_HIP(ctx, hipMemcpyAsync(qd, s->quads, sizeof(float4) * 3 * s->num_quads, hipMemcpyHostToDevice, st));
   if (s->num_triangles) HJ_HIP(ctx, hipMemcpyAsync(tr, s->triangles, sizeof(hj_triangle) * s->num_triangles, hipMemcpyHostToDevice, st));

@@ -238,7 +238,9 @@ void hj_default_render_opts(hj_render_opts* opts);
  * link structures return HJ_ERR_INVALID.
  * Limit: the device node array - 32 bytes per record, TWO copies of the tree (the re-laid-out one and the reference's own, which
  * rays with a zero or non-finite direction component walk: DESIGN.md 4) - must fit in 4 GiB: about 67 M records per tree = 33 M shapes;
- * larger trees return HJ_ERR_UNSUPPORTED. */
+ * larger trees return HJ_ERR_UNSUPPORTED.
+ * The previous scene is released first; the new one replaces it only when every stage has succeeded.  An upload that fails leaves
+ * the context without a scene, and leaves the tree on the device (hj_build_bvh_device) as it was, ready for a retry. */
 int hj_scene_upload(hj_context* ctx, const hj_scene_desc* scene);
 
 /* -------------------------------------------------------------- framebuffer */
@@ -312,7 +314,9 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* scene, hj_bvh_node
  *   hj_build_bvh_device(ctx, scene, NULL, 0, &n)      builds; nothing is copied to the host
  *   hj_scene_upload(ctx, scene) with scene->bvh == NULL and scene->num_bvh_nodes == 0
  *                                                     derives the kernels' records from that tree on the device (the same shape
- *                                                     counts as at the build: HJ_ERR_INVALID otherwise; no tree: HJ_ERR_STATE)
+ *                                                     counts as at the build: HJ_ERR_INVALID otherwise; no tree: HJ_ERR_STATE);
+ *                                                     the upload that succeeds consumes the tree, an upload that fails leaves
+ *                                                     the tree on the device
  *   hj_bvh_device_read(ctx, out_nodes, capacity, &n)  a copy of the tree for a host that wants one (out_nodes NULL: only n)
  * 1 M triangles: build + upload in tens of milliseconds (profiles/r06_startup_1M_triangles.txt).  Results are those of the same
  * tree handed over through the host, bit for bit. */

@@ -446,6 +446,70 @@ def test_device_tree_stays_on_the_device(oracle, kind, tris):
     gpu_renderer.close()
 
 
+_FAILED_UPLOAD_SCRIPT = r"""
+import os, sys
+sys.path.insert(0, os.getcwd())
+import numpy as np
+from hijiki_amd import abi, device, host
+cs = host.Scene.synthetic(host.SYNTH_CBOX, mesh_triangles=20000).compile(with_tree=False)
+W, H = 160, 96
+blocks = host.make_blocks(W, H, 3, 23)
+a = device.Renderer(0)
+a.build_bvh(cs, keep_on_device=True)
+nodes = a.read_device_bvh()
+# a second context takes what the allowance has left: the largest mesh scene that still fits (a refusal is a host-side check)
+b = device.Renderer(0)
+def fits(tris):
+    try:
+        b.upload_scene(host.Scene.synthetic(host.SYNTH_CBOX, mesh_triangles=tris).compile())
+        return True
+    except abi.HijikiError as e:
+        assert e.status == abi.HJ_ERR_NOMEM, str(e)
+        return False
+lo, hi = 0, 1 << 19
+assert fits(lo) and not fits(hi)
+while hi - lo > 1000:
+    mid = (lo + hi) // 2
+    if fits(mid):
+        lo = mid
+    else:
+        hi = mid
+assert fits(lo)
+try:
+    a.upload_scene(cs, device_tree=True)
+    raise SystemExit("the device-tree upload fitted beside the second context's scene")
+except abi.HijikiError as e:
+    assert e.status == abi.HJ_ERR_NOMEM, str(e)
+assert (a.read_device_bvh() == nodes).all(), "the failed upload changed the tree on the device"
+b.close()
+a.upload_scene(cs, device_tree=True)
+a.create_framebuffer(W, H)
+a.render_blocks(blocks)
+got = a.read().copy()
+cs.set_bvh(nodes)
+c = device.Renderer(0)
+c.upload_scene(cs)
+c.create_framebuffer(W, H)
+c.render_blocks(blocks)
+assert (got.view(np.uint32) == c.read().view(np.uint32)).all(), "device route after the failed upload against the host route"
+a.close()
+c.close()
+print("failed-upload-ok", lo)
+"""
+
+
+@pytest.mark.gpu
+def test_failed_device_tree_upload_leaves_the_tree_on_the_device():
+    """hj_scene_upload commits the new scene only when every stage has succeeded: an upload of the tree hj_build_bvh_device left on
+    the device that runs out of memory (HJ_ALLOC_LIMIT_MB, a second context holding the rest of the allowance) fails with
+    HJ_ERR_NOMEM, and the tree stays on the device as it was - the same records, and the retry once memory is free renders the
+    frame of the host route bit for bit.  Child process: the limit is read once per process."""
+    # (HJ_UPLOAD_DEVICE=0: the second context's scenes take the host re-layout, which holds no scratch - what fits is what stays)
+    env = dict(os.environ, HJ_ALLOC_LIMIT_MB="64", HJ_UPLOAD_DEVICE="0", GPU_MAX_HW_QUEUES="8")
+    p = subprocess.run([sys.executable, "-c", _FAILED_UPLOAD_SCRIPT], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "failed-upload-ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]
+
+
 def _record_multiset(nodes):
     """The records of a flattened tree without their links: (box, shape word), sorted."""
     n = np.asarray(nodes, np.uint32).reshape(-1, 8)
