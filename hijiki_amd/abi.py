@@ -11,6 +11,8 @@ STATUS_NAMES = {0: "HJ_OK", 1: "HJ_ERR_INVALID", 2: "HJ_ERR_DEVICE", 3: "HJ_ERR_
 
 # MaterialType discriminants (reference src/main.rs:34-45)
 MAT_DIFFUSE, MAT_DIFFUSECBOARD, MAT_MIRROR, MAT_DIELECTRIC, MAT_EMISSIVE = range(5)
+MAT_DIFFUSE_TEXTURED = 5          # no counterpart upstream: diffuse, colour from image texture `index`
+TEX_NEAREST, TEX_BILINEAR = 0, 1
 MATERIAL_TAG_SHIFT = 24
 MATERIAL_INDEX_MASK = 0x00FFFFFF
 BVH_INNER = 0xFFFFFFFF
@@ -99,6 +101,15 @@ class Emissive(C.Structure):
     _fields_ = [("power", f32 * 3), ("_pad", f32)]
 
 
+class Texture(C.Structure):
+    _fields_ = [("width", u32), ("height", u32), ("filter", u32), ("first_texel", u32)]
+
+
+class TextureSet(C.Structure):
+    _fields_ = [("textures", C.POINTER(Texture)), ("num_textures", C.c_size_t),
+                ("texels", C.POINTER(f32)), ("num_texels", C.c_size_t)]
+
+
 class ImageBlock(C.Structure):
     _fields_ = [("id", u32), ("seed", u32), ("origin", u32 * 2), ("dimension", u32 * 2),
                 ("original_dimension", u32 * 2), ("sample_offset", f32 * 2)]
@@ -141,7 +152,7 @@ class RenderStats(C.Structure):
 
 # byte sizes of SURVEY.md Appendix A
 _SIZES = {Camera: 48, SceneInfo: 64, BvhNode: 32, Sphere: 16, Quad: 48, Triangle: 12, Vertex: 32, Emitter: 16,
-          Diffuse: 16, DiffuseCB: 32, Dielectric: 16, Emissive: 16, ImageBlock: 40}
+          Diffuse: 16, DiffuseCB: 32, Dielectric: 16, Emissive: 16, ImageBlock: 40, Texture: 16}
 for _t, _n in _SIZES.items():
     assert C.sizeof(_t) == _n, (_t.__name__, C.sizeof(_t), _n)
 

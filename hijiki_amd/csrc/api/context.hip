@@ -84,6 +84,7 @@ int dev_alloc(hj_context* ctx, DevBuf& b, size_t bytes) {
 
 void release_scene(hj_context* ctx) {
   ctx->scene_bufs.bufs.clear();
+  ctx->num_textures = 0;
   ctx->have_scene = false;
 }
 
@@ -112,7 +113,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (3u << 8) | 0u; }   // 0.3.0: hj_render_stats grew (shadow_rays_proven_free), hj_scene_upload refuses non-tree link arrays
+uint32_t hj_version(void) { return (0u << 16) | (4u << 8) | 0u; }   // 0.4.0: image textures (hj_scene_upload_textured, hj_debug_texture_lookup)
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

@@ -8,6 +8,7 @@
 //   api/comm.hip          RCCL (dlopen), hj_comm_*, hj_reduce_framebuffers
 //   api/lbvh_build.hip    hj_build_bvh_device: host half of kernels/hj_lbvh.h
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
+//   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -118,6 +119,7 @@ struct hj_context {
   bool have_scene = false;
   hj::DeviceScene scene{};
   DevBufs scene_bufs;
+  uint32_t num_textures = 0;             // of the scene (scene.textures holds them: kernels/hj_texture.h)
 
   // framebuffer
   float4* accum = nullptr;
@@ -215,7 +217,10 @@ std::string get_error(hj_context* ctx);
 uint64_t shape_arrays_hash(const hj_scene_desc* s);
 void put_error(hj_context* ctx, const std::string& text);
 std::mutex& alloc_mutex();                           // process-wide: a context sizing its batch slots (api/render.hip run_submit)
-int validate_scene(hj_context* ctx, const hj_scene_desc* s);   // api/scene_upload.hip: every invariant an upload checks
+// api/scene_upload.hip: every invariant an upload checks; HJ_MAT_DIFFUSE_TEXTURED indices must be < num_textures
+int validate_scene(hj_context* ctx, const hj_scene_desc* s, size_t num_textures);
+int validate_textures(hj_context* ctx, const hj_texture_set* t);             // api/texture.hip
+int upload_textures(DevBufs& bufs, const hj_texture_set* t, const float4** out);
 void release_scene(hj_context* ctx);
 void release_slot(hj_context::BatchSlot& sl);
 void release_batch(hj_context* ctx);

@@ -13,7 +13,7 @@ namespace hjapi {
 // Same invariants the reference asserts while packing (src/main.rs:562-565)
 // plus every index range a kernel dereferences, and the monotonic-exit
 // property that makes the skip-link walk terminate on any input.
-int validate_scene(hj_context* ctx, const hj_scene_desc* s) {
+int validate_scene(hj_context* ctx, const hj_scene_desc* s, size_t num_textures) {
   const size_t shapes = s->num_spheres + s->num_quads + s->num_triangles;
   if (s->num_materials != shapes)
     return set_error(ctx, HJ_ERR_INVALID, "materials (%zu) != spheres+quads+triangles (%zu) (assert src/main.rs:562-565)",
@@ -71,6 +71,7 @@ int validate_scene(hj_context* ctx, const hj_scene_desc* s) {
       case HJ_MAT_MIRROR: lim = 1; break;
       case HJ_MAT_DIELECTRIC: lim = s->num_dielectric; break;
       case HJ_MAT_EMISSIVE: lim = s->num_emissive; break;
+      case HJ_MAT_DIFFUSE_TEXTURED: lim = num_textures; break;
       default: return set_error(ctx, HJ_ERR_INVALID, "shape %zu: unknown material tag %u", i, tag);
     }
     if (idx >= lim) return set_error(ctx, HJ_ERR_INVALID, "shape %zu: material index %u out of range for tag %u", i, idx, tag);
@@ -528,7 +529,9 @@ int upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, c
 
 extern "C" {
 
-int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
+int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) { return hj_scene_upload_textured(ctx, s, nullptr); }
+
+int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* s, const hj_texture_set* tex) {
   if (!ctx) return HJ_ERR_INVALID;
   HJ_NOT_BUSY(ctx);
   HJ_NOT_PIPELINED(ctx);
@@ -547,7 +550,8 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
          (s->num_vertices == 0 || s->vertices) && rt.shapes_hash != shape_arrays_hash(s)))
       return set_error(ctx, HJ_ERR_INVALID, "scene->bvh is NULL, but the tree on the device was built over other shape arrays (%zu / %zu / %zu shapes, %zu vertices)", rt.ns, rt.nq, rt.nt, rt.nv);
   }
-  HJ_TRY(validate_scene(ctx, s));
+  HJ_TRY(validate_textures(ctx, tex));
+  HJ_TRY(validate_scene(ctx, s, tex ? tex->num_textures : 0));
   hj_scene_desc with_tree;
   if (resident) { with_tree = *s; with_tree.num_bvh_nodes = rt.total; s = &with_tree; }   // (bvh stays NULL: nothing below reads it on this route)
   clock.mark("validation");
@@ -601,6 +605,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
   HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->diffusecb), 2 * s->num_diffusecb, &d.diffusecb));
   HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->dielectric), s->num_dielectric, &d.dielectric));
   HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->emissive), s->num_emissive, &d.emissive));
+  HJ_TRY(upload_textures(bufs, tex, &d.textures));
   clock.mark("other uploads");
   HJ_TRY(upload_light_grid(bufs, s, tn, resident ? static_cast<const hj_bvh_node*>(rt.nodes.p) : nullptr, d));
   clock.mark("light-shaft grid");
@@ -614,6 +619,7 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) {
     rt.release();
   }
   ctx->scene = d;
+  ctx->num_textures = d.textures ? (uint32_t)tex->num_textures : 0u;
   ctx->have_scene = true;
   return HJ_OK;
 }

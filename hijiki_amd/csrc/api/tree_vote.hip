@@ -117,7 +117,7 @@ int hj_tune_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* out
   if (!s || !out_nodes) return set_error(ctx, HJ_ERR_INVALID, "null argument");
   const size_t N = s->num_bvh_nodes;
   if (capacity < N) return set_error(ctx, HJ_ERR_INVALID, "node buffer holds %zu records, the tree has %zu", capacity, N);
-  int rc = validate_scene(ctx, s);
+  int rc = validate_scene(ctx, s, (size_t)HJ_MATERIAL_INDEX_MASK + 1);   // (the vote reads the tags of textured materials, not their textures)
   if (rc != HJ_OK) return rc;
   if (N == 0) return HJ_OK;
   HJ_HIP(ctx, hipSetDevice(ctx->device));

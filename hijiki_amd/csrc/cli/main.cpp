@@ -1,10 +1,11 @@
 // hijiki-hip — command line of the reference (`struct Opt` / `main`, src/main.rs:1426-1494) on the MI355X path:
 //
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
-//              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] <scene.obj | synthetic:KIND>
+//              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
-// no preview window, so --present-interval is accepted and ignored; --seed replaces the OS-seeded block RNG.
+// no preview window, so --present-interval is accepted and ignored; --seed replaces the OS-seeded block RNG; --textures (not
+// upstream) renders the MTL's map_Kd images on diffuse materials.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +21,7 @@
 namespace {
 
 struct Opt {
-  bool put_cbox_spheres = false, use_bvh = false, device_bvh = false;
+  bool put_cbox_spheres = false, use_bvh = false, device_bvh = false, textures = false;
   uint32_t width = 800, height = 600, present_interval = 128, sample_count = 64;
   uint64_t seed = 1;
   std::string output_image = "/tmp/output.exr", scene;
@@ -32,7 +33,8 @@ struct Opt {
                "USAGE: hijiki-hip [FLAGS] [OPTIONS] <scene>\n\n"
                "FLAGS:\n    --put-cbox-spheres    Add a mirror and glass sphere to the scene\n"
                "    --use-bvh             Use a BVH to optimize intersections\n"
-               "    --device-bvh          (not upstream) build the tree on the GPU (LBVH, stays there: fast start) instead of on the host (SAH)\n\n"
+               "    --device-bvh          (not upstream) build the tree on the GPU (LBVH, stays there: fast start) instead of on the host (SAH)\n"
+               "    --textures            (not upstream) diffuse materials with map_Kd take their colour from that image (PFM or P6 PPM)\n\n"
                "OPTIONS:\n    -h, --height <height>                        [default: 600]\n"
                "    -o, --output-image <output-image>            [default: /tmp/output.exr] (.exr, .pfm or .png)\n"
                "        --present-interval <present-interval>    [default: 128] (ignored: no preview window)\n"
@@ -54,6 +56,7 @@ Opt parse(int argc, char** argv) {
     if (a == "--put-cbox-spheres") o.put_cbox_spheres = true;
     else if (a == "--use-bvh") o.use_bvh = true;
     else if (a == "--device-bvh") o.device_bvh = true;
+    else if (a == "--textures") o.textures = true;
     else if (a == "-w" || a == "--width") o.width = (uint32_t)std::stoul(value(i));
     else if (a == "-h" || a == "--height") o.height = (uint32_t)std::stoul(value(i));
     else if (a == "--present-interval") o.present_interval = (uint32_t)std::stoul(value(i));
@@ -84,7 +87,7 @@ int main(int argc, char** argv) {
       scene = hijiki::make_synthetic(kind == "spheres" ? HJH_SYNTH_CBOX_SPHERES : kind == "mesh" ? HJH_SYNTH_CBOX_MESH : HJH_SYNTH_CBOX,
                                      kind == "mesh" ? 1000000u : 0u, 1);
     } else {
-      scene = hijiki::scene_from_obj(opt.scene);                       // Scene::from_obj, src/main.rs:1462
+      scene = hijiki::scene_from_obj(opt.scene, opt.textures);         // Scene::from_obj, src/main.rs:1462
     }
     if (opt.put_cbox_spheres) hijiki::put_cbox_spheres(scene);         // src/main.rs:1463-1483
     std::printf("Building BVH\n");                                     // src/main.rs:198
@@ -98,7 +101,8 @@ int main(int argc, char** argv) {
     if (opt.device_bvh) check(ctx, hj_build_bvh_device(ctx, &desc, nullptr, 0, &num_nodes), "device BVH build");
     std::printf("Built BVH with %zu nodes\n", num_nodes);              // src/main.rs:200
 
-    check(ctx, hj_scene_upload(ctx, &desc), "scene upload");
+    const hj_texture_set tex = cs.texture_set();
+    check(ctx, opt.textures ? hj_scene_upload_textured(ctx, &desc, &tex) : hj_scene_upload(ctx, &desc), "scene upload");
     check(ctx, hj_framebuffer_create(ctx, opt.width, opt.height, nullptr), "framebuffer");
     hj_render_opts ro;
     hj_default_render_opts(&ro);

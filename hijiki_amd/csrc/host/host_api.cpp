@@ -3,6 +3,7 @@
 #include <exception>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../../include/hijiki_host.h"
 #include "blockgen.hpp"
@@ -102,6 +103,35 @@ int hjh_scene_add_emissive(hjh_scene* s, const float power[3]) {
   return push_material(s, m);
 }
 
+int hjh_scene_add_texture(hjh_scene* s, uint32_t w, uint32_t h, const float* texels, uint32_t channels, uint32_t filter) {
+  if (!s || !texels) return -fail(HJ_ERR_INVALID, "null argument");
+  int idx = 0;
+  const int rc = guarded([&] {
+    idx = (int)add_texture(s->scene, w, h, texels, channels, filter);
+    return (int)HJ_OK;
+  });
+  return rc == HJ_OK ? idx : -rc;
+}
+int hjh_scene_add_texture_file(hjh_scene* s, const char* path, uint32_t filter) {
+  if (!s || !path) return -fail(HJ_ERR_INVALID, "null argument");
+  int idx = 0;
+  const int rc = guarded([&] {
+    uint32_t w = 0, h = 0;
+    std::vector<float> rgba;
+    read_texture_image(path, w, h, rgba);
+    idx = (int)add_texture(s->scene, w, h, rgba.data(), 4, filter);
+    return (int)HJ_OK;
+  });
+  return rc == HJ_OK ? idx : -rc;
+}
+int hjh_scene_add_diffuse_textured(hjh_scene* s, int texture) {
+  if (s && (texture < 0 || (size_t)texture >= s->scene.textures.size())) return -fail(HJ_ERR_INVALID, "unknown texture index");
+  Material m{};
+  m.tag = HJ_MAT_DIFFUSE_TEXTURED;
+  m.texture = (uint32_t)(texture < 0 ? 0 : texture);
+  return push_material(s, m);
+}
+
 long hjh_scene_add_vertices(hjh_scene* s, const hj_vertex* v, size_t n) {
   if (!s || (n && !v)) return -(long)fail(HJ_ERR_INVALID, "null argument");
   long first = (long)s->scene.vertices.size();
@@ -188,6 +218,11 @@ int hjh_compiled_desc(const hjh_compiled* c, hj_scene_desc* out) {
   *out = c->cs.desc();
   return HJ_OK;
 }
+int hjh_compiled_textures(const hjh_compiled* c, hj_texture_set* out) {
+  if (!c || !out) return fail(HJ_ERR_INVALID, "null argument");
+  *out = c->cs.texture_set();
+  return HJ_OK;
+}
 int hjh_compiled_set_bvh(hjh_compiled* c, const hj_bvh_node* nodes, size_t n) {
   if (!c || !nodes) return fail(HJ_ERR_INVALID, "null argument");
   const size_t shapes = c->cs.spheres.size() + c->cs.quads.size() + c->cs.triangles.size(), want = shapes ? 2 * shapes - 1 : 0;
@@ -219,6 +254,7 @@ int hjh_compiled_directional_bvh(const hjh_compiled* c, int mode, size_t vote_pa
 size_t hjh_compiled_packed_size(const hjh_compiled* c) { return c ? c->cs.packed_size() : 0; }
 int hjh_compiled_pack(const hjh_compiled* c, void* buffer, size_t size) {
   if (!c || !buffer) return fail(HJ_ERR_INVALID, "null argument");
+  if (!c->cs.textures.empty()) return fail(HJ_ERR_UNSUPPORTED, "the reference's scene buffer has no place for image textures");
   return c->cs.pack(buffer, size) ? (int)HJ_OK : fail(HJ_ERR_INVALID, "buffer size != packed size (assert at src/main.rs:604)");
 }
 
@@ -262,6 +298,21 @@ int hjh_scene_from_obj(const char* path, hjh_scene** out) {
     auto* s = new hjh_scene();
     try {
       s->scene = scene_from_obj(path);
+    } catch (...) {
+      delete s;
+      throw;
+    }
+    *out = s;
+    return (int)HJ_OK;
+  });
+}
+
+int hjh_scene_from_obj_textured(const char* path, hjh_scene** out) {
+  if (!path || !out) return fail(HJ_ERR_INVALID, "null argument");
+  return guarded([&] {
+    auto* s = new hjh_scene();
+    try {
+      s->scene = scene_from_obj(path, true);
     } catch (...) {
       delete s;
       throw;

@@ -1,10 +1,12 @@
 // Image output of the reference's `Renderer::save_image` (src/main.rs:1395-1419): three FLOAT channels R, G, B,
 // written as an OpenEXR scan-line file — here without the OpenEXR library, as an uncompressed single-part file
-// (any EXR reader accepts it) — plus the trivially inspectable PFM.
+// (any EXR reader accepts it) — plus the trivially inspectable PFM.  Image input for textures (no counterpart upstream):
+// PFM and binary PPM.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -19,6 +21,76 @@ void write_pfm(const std::string& path, uint32_t w, uint32_t h, const float* rgb
   for (uint32_t y = 0; y < h; y++)              // PFM stores the bottom row first
     std::fwrite(rgb + (size_t)(h - 1 - y) * w * 3, sizeof(float), (size_t)w * 3, f);
   if (std::fclose(f) != 0) throw std::runtime_error("write failed: " + path);
+}
+
+// Texture input: PFM ("PF" rgb / "Pf" grey, either byte order, bottom row first on disk) as linear values; binary PPM (P6, maxval
+// 255) through the sRGB EOTF.  Out: RGBA, row 0 on top, alpha 1.
+namespace {
+std::string header_token(FILE* f, const std::string& path) {    // whitespace-separated, '#' comments (PPM)
+  std::string tok;
+  int c;
+  while ((c = std::fgetc(f)) != EOF) {
+    if (c == '#' && tok.empty()) { while ((c = std::fgetc(f)) != EOF && c != '\n') {} continue; }
+    if (c == ' ' || c == '\t' || c == '\n' || c == '\r') { if (!tok.empty()) return tok; continue; }
+    tok.push_back((char)c);
+    if (tok.size() > 32) break;
+  }
+  if (tok.empty() || tok.size() > 32) throw std::runtime_error("truncated or malformed image header: " + path);
+  return tok;
+}
+uint32_t header_uint(FILE* f, const std::string& path) {
+  const std::string t = header_token(f, path);
+  char* end = nullptr;
+  const unsigned long v = std::strtoul(t.c_str(), &end, 10);
+  if (*end != 0 || v == 0 || v > (1ul << 24)) throw std::runtime_error("bad image size '" + t + "' in " + path);
+  return (uint32_t)v;
+}
+}  // namespace
+
+void read_texture_image(const std::string& path, uint32_t& w, uint32_t& h, std::vector<float>& rgba) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) throw std::runtime_error("cannot open texture " + path);
+  struct Closer { FILE* f; ~Closer() { std::fclose(f); } } closer{f};
+  char magic[2] = {0, 0};
+  if (std::fread(magic, 1, 2, f) != 2 || (magic[0] != 'P')) throw std::runtime_error(path + ": not a PFM or binary PPM (P6) file");
+  const char kind = magic[1];
+  if (kind != 'F' && kind != 'f' && kind != '6')
+    throw std::runtime_error(path + ": not a PFM or binary PPM (P6) file (PNG, JPEG and other formats are not read)");
+  w = header_uint(f, path);
+  h = header_uint(f, path);
+  if ((uint64_t)w * h > ((uint64_t)1 << 28)) throw std::runtime_error(path + ": image too large");
+  rgba.assign((size_t)w * h * 4, 1.0f);
+  if (kind == '6') {
+    const std::string maxval = header_token(f, path);
+    if (maxval != "255") throw std::runtime_error(path + ": P6 with maxval " + maxval + " (only 255 is read)");
+    std::vector<uint8_t> px((size_t)w * h * 3);
+    if (std::fread(px.data(), 1, px.size(), f) != px.size()) throw std::runtime_error(path + ": truncated pixel data");
+    float lut[256];
+    for (int i = 0; i < 256; i++) {          // sRGB EOTF (IEC 61966-2-1), in double, rounded once
+      const double c = i / 255.0;
+      lut[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
+    }
+    for (size_t i = 0; i < (size_t)w * h; i++)
+      for (int k = 0; k < 3; k++) rgba[4 * i + k] = lut[px[3 * i + k]];
+    return;
+  }
+  const std::string scale = header_token(f, path);
+  char* end = nullptr;
+  const double sc = std::strtod(scale.c_str(), &end);
+  if (*end != 0 || sc == 0.0 || !std::isfinite(sc)) throw std::runtime_error(path + ": bad PFM scale '" + scale + "'");
+  const bool big_endian = sc > 0.0;
+  const int ch = kind == 'F' ? 3 : 1;
+  std::vector<uint32_t> raw((size_t)w * h * ch);
+  if (std::fread(raw.data(), 4, raw.size(), f) != raw.size()) throw std::runtime_error(path + ": truncated pixel data");
+  for (size_t y = 0; y < h; y++)               // PFM stores the bottom row first
+    for (size_t x = 0; x < w; x++)
+      for (int k = 0; k < 3; k++) {
+        uint32_t b = raw[((h - 1 - y) * w + x) * ch + (ch == 3 ? k : 0)];
+        if (big_endian) b = __builtin_bswap32(b);
+        float v;
+        std::memcpy(&v, &b, 4);
+        rgba[4 * (y * w + x) + k] = v;
+      }
 }
 
 namespace {

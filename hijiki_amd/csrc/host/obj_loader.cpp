@@ -35,6 +35,7 @@ struct ObjMaterial {
   float ambient[3] = {0, 0, 0}, diffuse[3] = {0, 0, 0}, specular[3] = {0, 0, 0};
   float shininess = 0.f, optical_density = 1.f, dissolve = 1.f;
   std::map<std::string, std::string> unknown_param;
+  std::string map_kd, mtl_dir;   // `map_Kd` as written, the MTL's directory (textured load only)
 };
 
 std::vector<std::string> split_ws(const std::string& s) {
@@ -91,7 +92,11 @@ void load_mtl(const std::string& path, std::vector<ObjMaterial>& mats, std::map<
     else if (key == "Ns" && t.size() > 1) cur.shininess = to_f(t[1], path);
     else if (key == "Ni" && t.size() > 1) cur.optical_density = to_f(t[1], path);
     else if (key == "d" && t.size() > 1) cur.dissolve = to_f(t[1], path);
-    else if (key == "illum" || key == "map_Ka" || key == "map_Kd" || key == "map_Ks" || key == "map_Ns" || key == "map_d") {
+    else if (key == "map_Kd") {
+      // known to the crate, irrelevant to the reference; kept for the textured load (scene_from_obj(path, true))
+      cur.map_kd = trim(line.substr(key.size()));
+      cur.mtl_dir = dir_of(path);
+    } else if (key == "illum" || key == "map_Ka" || key == "map_Ks" || key == "map_Ns" || key == "map_d") {
       // known to the crate, irrelevant to the reference
     } else {
       cur.unknown_param[key] = trim(line.substr(key.size()));
@@ -210,7 +215,7 @@ void load_obj(const std::string& path, std::vector<ObjMesh>& models, std::vector
 }  // namespace
 
 // Scene::from_obj, src/main.rs:414-530
-Scene scene_from_obj(const std::string& path) {
+Scene scene_from_obj(const std::string& path, bool textures) {
   std::vector<ObjMesh> models;
   std::vector<ObjMaterial> materials;
   load_obj(path, models, materials);
@@ -220,6 +225,7 @@ Scene scene_from_obj(const std::string& path) {
   scene.vertices.clear();
   scene.materials.clear();
 
+  std::map<std::string, uint32_t> texture_of_file;
   for (const ObjMaterial& m : materials) {   // src/main.rs:432-458: material kind by NAME PREFIX
     Material out{};
     if (m.name.rfind("light", 0) == 0) {
@@ -234,6 +240,19 @@ Scene scene_from_obj(const std::string& path) {
       out.dielectric = hj_dielectric{{0.f, 0.f, 0.f}, 1.5f};   // DielectricMaterial::clear(1.5)
     } else if (m.name.rfind("mirror", 0) == 0) {
       out.tag = HJ_MAT_MIRROR;
+    } else if (textures && !m.map_kd.empty()) {   // (no counterpart upstream) the image replaces Kd
+      if (m.map_kd[0] == '-')
+        throw std::runtime_error("material '" + m.name + "': map_Kd options (" + split_ws(m.map_kd)[0] + " ...) are not supported");
+      const std::string file = m.mtl_dir + m.map_kd;
+      auto it = texture_of_file.find(file);
+      if (it == texture_of_file.end()) {
+        uint32_t w = 0, h = 0;
+        std::vector<float> rgba;
+        read_texture_image(file, w, h, rgba);
+        it = texture_of_file.emplace(file, add_texture(scene, w, h, rgba.data(), 4, HJ_TEX_BILINEAR)).first;
+      }
+      out.tag = HJ_MAT_DIFFUSE_TEXTURED;
+      out.texture = it->second;
     } else {
       out.tag = HJ_MAT_DIFFUSE;
       out.diffuse = hj_diffuse{{m.diffuse[0], m.diffuse[1], m.diffuse[2]}, 0.f};

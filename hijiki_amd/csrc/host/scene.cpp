@@ -451,6 +451,7 @@ Scene scene_of(const CompiledScene& cs) {
       case HJ_MAT_DIFFUSECBOARD: if (ix < cs.diffusecb.size()) m.cboard = cs.diffusecb[ix]; break;
       case HJ_MAT_DIELECTRIC: if (ix < cs.dielectric.size()) m.dielectric = cs.dielectric[ix]; break;
       case HJ_MAT_EMISSIVE: if (ix < cs.emissive.size()) m.emissive = cs.emissive[ix]; break;
+      case HJ_MAT_DIFFUSE_TEXTURED: m.texture = ix; break;
       default: break;
     }
     return m;
@@ -568,12 +569,23 @@ CompiledScene compile(const Scene& scene, bool with_tree) {
       case HJ_MAT_MIRROR: ix = 0; break;
       case HJ_MAT_DIELECTRIC: out.dielectric.push_back(m.dielectric); ix = (uint32_t)out.dielectric.size() - 1; break;
       case HJ_MAT_EMISSIVE: out.emissive.push_back(m.emissive); ix = (uint32_t)out.emissive.size() - 1; break;
+      case HJ_MAT_DIFFUSE_TEXTURED:   // (no record: the index names the texture)
+        if (m.texture >= scene.textures.size()) throw std::runtime_error("material refers to texture " + std::to_string(m.texture) + " of " + std::to_string(scene.textures.size()));
+        ix = m.texture;
+        break;
     }
     reprs.push_back(((uint32_t)m.tag << HJ_MATERIAL_TAG_SHIFT) + ix);
   }
   for (int m : sphere_mat) out.materials.push_back(reprs[m]);
   for (int m : quad_mat) out.materials.push_back(reprs[m]);
   for (int m : tri_mat) out.materials.push_back(reprs[m]);
+
+  // image textures (no counterpart upstream): the table and the texels in one array, in the scene's order
+  for (const Texture& t : scene.textures) {
+    if ((out.texels.size() / 4 + (size_t)t.width * t.height) > ((size_t)1 << 32)) throw std::runtime_error("textures: more than 2^32 texels");
+    out.textures.push_back(hj_texture{t.width, t.height, t.filter, (uint32_t)(out.texels.size() / 4)});
+    out.texels.insert(out.texels.end(), t.rgba.begin(), t.rgba.end());
+  }
 
   // uniform emitter table (src/main.rs:289-307)
   for (size_t ix = 0; ix < out.materials.size(); ix++)
@@ -587,6 +599,27 @@ CompiledScene compile(const Scene& scene, bool with_tree) {
     e.cdf = cdf;
   }
   return out;
+}
+
+hj_texture_set CompiledScene::texture_set() const {
+  hj_texture_set t{};
+  t.textures = textures.data(); t.num_textures = textures.size();
+  t.texels = texels.data(); t.num_texels = texels.size() / 4;
+  return t;
+}
+
+uint32_t add_texture(Scene& scene, uint32_t w, uint32_t h, const float* texels, uint32_t channels, uint32_t filter) {
+  if (w == 0 || h == 0 || w > (1u << 24) || h > (1u << 24)) throw std::runtime_error("texture of " + std::to_string(w) + " x " + std::to_string(h) + " texels");
+  if (channels != 3 && channels != 4) throw std::runtime_error("texture texels need 3 or 4 channels");
+  if (filter > HJ_TEX_BILINEAR) throw std::runtime_error("unknown texture filter " + std::to_string(filter));
+  if (scene.textures.size() >= HJ_MATERIAL_INDEX_MASK) throw std::runtime_error("too many textures");
+  Texture t;
+  t.width = w; t.height = h; t.filter = filter;
+  t.rgba.assign((size_t)w * h * 4, 1.0f);
+  for (size_t i = 0; i < (size_t)w * h; i++)
+    for (uint32_t k = 0; k < channels; k++) t.rgba[4 * i + k] = texels[channels * i + k];
+  scene.textures.push_back(std::move(t));
+  return (uint32_t)scene.textures.size() - 1;
 }
 
 hj_scene_desc CompiledScene::desc() const {

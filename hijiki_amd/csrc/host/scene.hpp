@@ -18,6 +18,13 @@ struct Material {
   hj_diffuse_cb cboard{};
   hj_dielectric dielectric{};
   hj_emissive emissive{};
+  uint32_t texture = 0;         // HJ_MAT_DIFFUSE_TEXTURED: index into Scene::textures
+};
+
+// An image texture (no counterpart upstream): RGBA32F, row 0 on top.
+struct Texture {
+  uint32_t width = 0, height = 0, filter = HJ_TEX_NEAREST;
+  std::vector<float> rgba;
 };
 
 // `enum Shape` (src/main.rs:47-52).
@@ -43,6 +50,7 @@ struct Scene {
   std::vector<std::pair<Shape, int>> objects;  // (shape, material index)
   std::vector<hj_vertex> vertices;
   std::vector<Material> materials;
+  std::vector<Texture> textures;
 
   Aabb shape_aabb(const Shape& s) const;  // src/main.rs:69-82, src/shape.rs:13-20,46-54
 };
@@ -61,8 +69,11 @@ struct CompiledScene {
   std::vector<hj_diffuse_cb> diffusecb;
   std::vector<hj_dielectric> dielectric;
   std::vector<hj_emissive> emissive;
+  std::vector<hj_texture> textures;   // what hj_scene_upload_textured takes (texture_set)
+  std::vector<float> texels;          // RGBA32F
 
   hj_scene_desc desc() const;
+  hj_texture_set texture_set() const;
   size_t packed_size() const;                        // src/main.rs:314-339
   bool pack(void* buffer, size_t size) const;        // src/main.rs:561-605
 };
@@ -111,11 +122,17 @@ void directional_bvh(const CompiledScene& cs, int mode, size_t vote_paths, int f
 Scene make_synthetic(int kind, uint32_t mesh_triangles, uint32_t gen_seed);
 
 // `Scene::from_obj` (src/main.rs:414-530) and `--put-cbox-spheres` (src/main.rs:1463-1483).
-Scene scene_from_obj(const std::string& path);
+// textures: a diffuse material (by name prefix) with `map_Kd FILE` becomes HJ_MAT_DIFFUSE_TEXTURED, FILE read next to the MTL
+// (read_texture_image), bilinear; without, map_Kd is ignored as the reference does.
+Scene scene_from_obj(const std::string& path, bool textures = false);
 void put_cbox_spheres(Scene& scene);
 
 // Image output (src/main.rs:1395-1419): rgb = W*H*3 floats, row 0 on top.
 void write_pfm(const std::string& path, uint32_t w, uint32_t h, const float* rgb);
+// Texture input (image_io.cpp): PFM (linear) or binary PPM P6 with maxval 255 (sRGB EOTF); rgba = w*h*4 floats, row 0 on top.
+void read_texture_image(const std::string& path, uint32_t& w, uint32_t& h, std::vector<float>& rgba);
+// Adds a texture to the scene (channels 3 or 4, rows top first); returns its index.  Throws std::runtime_error.
+uint32_t add_texture(Scene& scene, uint32_t w, uint32_t h, const float* texels, uint32_t channels, uint32_t filter);
 void write_exr(const std::string& path, uint32_t w, uint32_t h, const float* rgb);
 // 8-bit sRGB PNG of the same image: what the reference's preview window shows (shader/preview.glsl:9-12).
 void write_png(const std::string& path, uint32_t w, uint32_t h, const float* rgb);

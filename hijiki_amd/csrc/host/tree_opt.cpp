@@ -537,7 +537,7 @@ struct Voter {
       V3 pos, n;
       surface(r.hit, r, t, u, v, pos, n);
       V3 wo;
-      if (m.tag == HJ_MAT_DIFFUSE || m.tag == HJ_MAT_DIFFUSECBOARD) {
+      if (m.tag == HJ_MAT_DIFFUSE || m.tag == HJ_MAT_DIFFUSECBOARD || m.tag == HJ_MAT_DIFFUSE_TEXTURED) {
         if (!emitters.empty()) {                                          // scene.glsl:54-89
           const int32_t e = emitters[std::min<size_t>(emitters.size() - 1, (size_t)(g.uni() * (float)emitters.size()))];
           const V3 lp = point_on(e, g);

@@ -8,7 +8,11 @@
 namespace hj {
 
 constexpr uint32_t kSlotsPerBlock = HJ_BLOCK_SIZE * HJ_BLOCK_SIZE;  // fixed 128x128 slot grid per ImageBlock
+#ifdef HJ_TEXTURE_OWN_BIN   // measurement only ("Image textures"): textured hits in a sixth bin instead of the checkerboard's
+constexpr uint32_t kNumTags = 6;
+#else
 constexpr uint32_t kNumTags = 5;
+#endif
 // Pre-gathered emitter record, 7 x float4 (every value copied verbatim from the reference arrays):
 //   r0 = (emitter.pdf, kind bits [0 sphere, 1 quad, 2 triangle], sphere radius, -)
 //   r1..r3 = (sphere centre | quad origin, edge1, edge2 | triangle a, b, c).xyz, w = emissive power r, g, b
@@ -64,6 +68,7 @@ struct DeviceScene {
   const float4* diffusecb;      // 2 x float4 per record
   const float4* dielectric;
   const float4* emissive;
+  const float4* textures;       // image textures (hj_texture.h): a record per texture, the texels behind them; null: none
   uint32_t ns, nq, nt, num_emitters;
   uint32_t has_extinction;      // any dielectric with non-zero extinction
   uint32_t has_pairs;           // the node array holds pair nodes (tri_pair)

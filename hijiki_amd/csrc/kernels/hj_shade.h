@@ -1,8 +1,9 @@
 // What a hit needs: populate* (reference shader/shapes/*.glsl), emitter sampling (shader/scene.glsl:44-89), the checkerboard
-// texture (shader/materials/diffusecb.glsl) - used by the shade stage (hj_stages.h).
+// texture (shader/materials/diffusecb.glsl), image textures (hj_texture.h) - used by the shade stage (hj_stages.h).
 #pragma once
 #include "hj_intersect.h"
 #include "hj_light_grid_const.h"
+#include "hj_texture.h"
 
 #pragma clang fp contract(off)
 

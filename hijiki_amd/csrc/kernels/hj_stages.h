@@ -346,6 +346,10 @@ HJ_DEV void stage_camera_packets(const BatchState& st, const DeviceScene& sc, ui
 // stay close together in memory.  Paths whose ray missed are over (render.glsl:94-96): nothing refers to them again.
 // Starts with a barrier (all hit records written); needs sh.cnt_hit[] == 0; leaves the tag counts there.
 // `waves` = waves of the workgroup that take part.
+// The bin of a material tag: its own, except that textured diffuse hits share the checkerboard's (both are "diffuse with a colour
+// from (u, v)"; the bin count and the LDS counters stay as they were).  stage_shade tells the two apart by the material word.
+HJ_DEV uint32_t hit_bin(uint32_t tag) { return tag == HJ_MAT_DIFFUSE_TEXTURED && kNumTags == 5 ? (uint32_t)HJ_MAT_DIFFUSECBOARD : tag; }
+
 template <bool NT, uint32_t R>
 HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uint32_t g, uint32_t n, WgShared& sh,
                                 uint32_t waves) {
@@ -368,7 +372,7 @@ HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uin
       id[j] = (row + j < r1 && i < n) ? __float_as_int(ldp<NT>(hit, i).y) : -1;
     }
 #pragma unroll
-    for (uint32_t j = 0; j < R; j++) tag[j] = id[j] >= 0 ? sc.materials[id[j]] >> HJ_MATERIAL_TAG_SHIFT : 0xFFu;
+    for (uint32_t j = 0; j < R; j++) tag[j] = id[j] >= 0 ? hit_bin(sc.materials[id[j]] >> HJ_MATERIAL_TAG_SHIFT) : 0xFFu;
   };
   // second pass: the tags the first pass left in hit_tag (a byte per ray: 64 B per row instead of 1 KB + the material gather)
   uint8_t* __restrict__ htag = st.hit_tag + g * st.pool;
@@ -506,8 +510,12 @@ HJ_DEV void stage_shade(const BatchState& st, const DeviceScene& sc, uint32_t g,
           break;
         }
         case HJ_MAT_DIFFUSE:
-        case HJ_MAT_DIFFUSECBOARD: {
-          const v3 color = (tag == HJ_MAT_DIFFUSE) ? xyz(sc.diffuse[midx]) : checkerboard(sc, midx, its.u, its.v);
+        case HJ_MAT_DIFFUSECBOARD:
+        case HJ_MAT_DIFFUSE_TEXTURED: {     // (a bin of its own only with HJ_TEXTURE_OWN_BIN)
+          // (bin HJ_MAT_DIFFUSECBOARD also holds the HJ_MAT_DIFFUSE_TEXTURED hits: hit_bin)
+          const v3 color = (tag == HJ_MAT_DIFFUSE) ? xyz(sc.diffuse[midx])
+                           : (mat >> HJ_MATERIAL_TAG_SHIFT) == HJ_MAT_DIFFUSE_TEXTURED ? texture_rgb(sc.textures, midx, its.u, its.v)
+                                                                                        : checkerboard(sc, midx, its.u, its.v);
           uint32_t em = 0;
           const v3 imp = sample_emitter(sc, its.p, rng, sdir, stmax, em);                  // render.glsl:117-126
           if (len3(imp) > kEps && dot3(sdir, its.n) > 0.0f) {
@@ -562,7 +570,7 @@ HJ_DEV void stage_shade(const BatchState& st, const DeviceScene& sc, uint32_t g,
           break;
       }
       if (alive) {
-        const bool discrete = (tag != HJ_MAT_DIFFUSE && tag != HJ_MAT_DIFFUSECBOARD);     // render.glsl:135
+        const bool discrete = (tag != HJ_MAT_DIFFUSE && tag != HJ_MAT_DIFFUSECBOARD && tag != HJ_MAT_DIFFUSE_TEXTURED);   // render.glsl:135
         if (bounce >= rr_start) {                                                          // render.glsl:137-144
           const float qq = f_min(0.99f, f_max(T.x, f_max(T.y, T.z)));
           if (rng_float(rng) > qq) alive = false;

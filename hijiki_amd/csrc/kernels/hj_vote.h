@@ -229,7 +229,7 @@ __global__ __launch_bounds__(64) void k_vote_paths(Scene s, uint32_t num_paths) 
     v3 pos, n;
     surface(s, obj, r, h, pos, n);
     v3 wo;
-    if (tag == HJ_MAT_DIFFUSE || tag == HJ_MAT_DIFFUSECBOARD) {
+    if (tag == HJ_MAT_DIFFUSE || tag == HJ_MAT_DIFFUSECBOARD || tag == HJ_MAT_DIFFUSE_TEXTURED) {
       if (s.ne) {                                                          // scene.glsl:54-89
         uint32_t k = (uint32_t)(g.uni() * (float)s.ne);
         if (k >= s.ne) k = s.ne - 1;

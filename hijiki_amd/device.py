@@ -22,7 +22,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_pass_offset", "hj_block_owner", "hj_debug_trace", "hj_debug_samples", "hj_reduce_framebuffers",
            "hj_build_bvh_device", "hj_render_frame_async", "hj_sync", "hj_set_progress_callback", "hj_device_count",
            "hj_comm_create", "hj_comm_destroy", "hj_comm_reduce_framebuffers", "hj_reserve", "hj_framebuffer_bind",
-           "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read")
+           "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
+           "hj_scene_upload_textured", "hj_debug_texture_lookup")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -44,6 +45,8 @@ def lib():
         L.hj_default_render_opts.argtypes = [C.POINTER(abi.RenderOpts)]
         L.hj_default_render_opts.restype = None
         L.hj_scene_upload.argtypes = [vp, C.POINTER(abi.SceneDesc)]
+        L.hj_scene_upload_textured.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.TextureSet)]
+        L.hj_debug_texture_lookup.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float)]
         L.hj_framebuffer_create.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
         L.hj_framebuffer_clear.argtypes = [vp]
         L.hj_framebuffer_device_ptr.argtypes = [vp]
@@ -160,16 +163,23 @@ class Renderer:
         if rc != abi.HJ_OK:
             raise abi.HijikiError(rc, lib().hj_last_error(self._h).decode())
 
-    def upload_scene(self, compiled, device_tree=False):
-        """hj_scene_upload.  device_tree: scene->bvh = NULL - the tree `build_bvh(compiled, keep_on_device=True)` left on the device."""
+    def upload_scene(self, compiled, device_tree=False, textures=None):
+        """hj_scene_upload.  device_tree: scene->bvh = NULL - the tree `build_bvh(compiled, keep_on_device=True)` left on the device.
+        A compiled scene with image textures goes up with them (hj_scene_upload_textured); `textures` (an abi.TextureSet) overrides."""
         desc = compiled.desc if hasattr(compiled, "desc") else compiled
+        if textures is None and hasattr(compiled, "texture_set"):
+            t = compiled.texture_set
+            textures = t if t.num_textures else None
         if device_tree:
             d2 = abi.SceneDesc()
             C.memmove(C.byref(d2), C.byref(desc), C.sizeof(abi.SceneDesc))
             d2.bvh = None
             d2.num_bvh_nodes = 0
             desc = d2
-        self._check(lib().hj_scene_upload(self._h, C.byref(desc)))
+        if textures is not None:
+            self._check(lib().hj_scene_upload_textured(self._h, C.byref(desc), C.byref(textures)))
+        else:
+            self._check(lib().hj_scene_upload(self._h, C.byref(desc)))
 
     def create_framebuffer(self, width, height, external_device_ptr=None):
         self._check(lib().hj_framebuffer_create(self._h, width, height, external_device_ptr))
@@ -275,6 +285,14 @@ class Renderer:
         self._check(lib().hj_debug_trace(self._h, rays.ctypes.data_as(fp), len(rays), int(use_bvh), int(any_hit),
                                          hits.ctypes.data_as(fp)))
         return hits[:, 0].copy().view(np.int32), hits[:, 1], hits[:, 2], hits[:, 3]
+
+    def texture_lookup(self, texture, uv):
+        """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 3), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(lib().hj_debug_texture_lookup(self._h, int(texture), uv.ctypes.data_as(fp), len(uv), out.ctypes.data_as(fp)))
+        return out
 
     def samples(self, block, opts=None):
         """Intermediate image of one block: (dim_y, dim_x, 8) = (rgb, 1, normal, depth)."""

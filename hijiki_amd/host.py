@@ -36,6 +36,10 @@ def lib():
         L.hjh_scene_add_mirror.argtypes = [vp]
         L.hjh_scene_add_dielectric.argtypes = [vp, f3, C.c_float]
         L.hjh_scene_add_emissive.argtypes = [vp, f3]
+        L.hjh_scene_add_texture.argtypes = [vp, C.c_uint32, C.c_uint32, f3, C.c_uint32, C.c_uint32]
+        L.hjh_scene_add_texture_file.argtypes = [vp, C.c_char_p, C.c_uint32]
+        L.hjh_scene_add_diffuse_textured.argtypes = [vp, C.c_int]
+        L.hjh_compiled_textures.argtypes = [vp, C.POINTER(abi.TextureSet)]
         L.hjh_scene_add_vertices.argtypes = [vp, C.POINTER(abi.Vertex), C.c_size_t]
         L.hjh_scene_add_vertices.restype = C.c_long
         L.hjh_scene_add_sphere.argtypes = [vp, f3, C.c_float, C.c_int]
@@ -61,6 +65,7 @@ def lib():
                                       C.POINTER(abi.ImageBlock), C.c_size_t]
         L.hjh_make_blocks.restype = C.c_size_t
         L.hjh_scene_from_obj.argtypes = [C.c_char_p, C.POINTER(vp)]
+        L.hjh_scene_from_obj_textured.argtypes = [C.c_char_p, C.POINTER(vp)]
         L.hjh_scene_put_cbox_spheres.argtypes = [vp]
         L.hjh_write_exr.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, f3]
         L.hjh_write_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, f3]
@@ -115,10 +120,11 @@ class Scene:
         return Scene(_handle=h)
 
     @staticmethod
-    def from_obj(path):
-        """`Scene::from_obj` (src/main.rs:414-530)."""
+    def from_obj(path, textures=False):
+        """`Scene::from_obj` (src/main.rs:414-530).  textures=True (no counterpart upstream): a diffuse material with `map_Kd FILE`
+        takes its colour from that image (hjh_scene_from_obj_textured)."""
         h = C.c_void_p()
-        _check(lib().hjh_scene_from_obj(os.fsencode(path), C.byref(h)))
+        _check((lib().hjh_scene_from_obj_textured if textures else lib().hjh_scene_from_obj)(os.fsencode(path), C.byref(h)))
         return Scene(_handle=h)
 
     def put_cbox_spheres(self):
@@ -146,6 +152,22 @@ class Scene:
 
     def add_emissive(self, power):
         return _index(lib().hjh_scene_add_emissive(self._h, _f3(power)))
+
+    # image textures (no counterpart upstream)
+    def add_texture(self, texels, filter=abi.TEX_NEAREST):
+        """(H, W, 3 or 4) float32 texels, row 0 = the top of the image -> texture index."""
+        a = np.ascontiguousarray(texels, np.float32)
+        if a.ndim != 3 or a.shape[2] not in (3, 4):
+            raise ValueError("texels must be an (H, W, 3) or (H, W, 4) array")
+        h, w, ch = a.shape
+        return _index(lib().hjh_scene_add_texture(self._h, w, h, a.ctypes.data_as(C.POINTER(C.c_float)), ch, int(filter)))
+
+    def add_texture_file(self, path, filter=abi.TEX_BILINEAR):
+        """PFM (linear) or binary PPM P6 (sRGB-decoded) -> texture index."""
+        return _index(lib().hjh_scene_add_texture_file(self._h, os.fsencode(path), int(filter)))
+
+    def add_diffuse_textured(self, texture):
+        return _index(lib().hjh_scene_add_diffuse_textured(self._h, int(texture)))
 
     def add_vertices(self, pos, normal, uv=None):
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
@@ -244,6 +266,20 @@ class CompiledScene:
     @property
     def num_shapes(self):
         return self.desc.num_materials
+
+    @property
+    def texture_set(self):
+        """hjh_compiled_textures: the abi.TextureSet hj_scene_upload_textured takes (borrowed; valid while self lives)."""
+        t = abi.TextureSet()
+        _check(lib().hjh_compiled_textures(self._h, C.byref(t)))
+        return t
+
+    @property
+    def textures(self):
+        """[(width, height, filter, first_texel)] and the (num_texels, 4) float32 texel view."""
+        t = self.texture_set
+        table = [(r.width, r.height, r.filter, r.first_texel) for r in (t.textures[i] for i in range(t.num_textures))]
+        return table, _as_np(t.texels, t.num_texels, np.float32, 4)
 
     def set_bvh(self, nodes):
         """Replace the tree by `nodes` ((2 * shapes - 1, 8) uint32, the reference's record layout), e.g. the result

@@ -45,7 +45,8 @@ enum hj_material_tag {
   HJ_MAT_DIFFUSECBOARD = 1,
   HJ_MAT_MIRROR = 2,
   HJ_MAT_DIELECTRIC = 3,
-  HJ_MAT_EMISSIVE = 4
+  HJ_MAT_EMISSIVE = 4,
+  HJ_MAT_DIFFUSE_TEXTURED = 5   /* no counterpart upstream: diffuse, colour from image texture `index` (hj_texture_set) */
 };
 #define HJ_MATERIAL_TAG_SHIFT 24u
 #define HJ_MATERIAL_INDEX_MASK 0x00FFFFFFu
@@ -132,6 +133,19 @@ typedef struct hj_diffuse    { float color[3]; float _pad; } hj_diffuse;
 typedef struct hj_diffuse_cb { float color_a[3]; float scale_u; float color_b[3]; float scale_v; } hj_diffuse_cb;
 typedef struct hj_dielectric { float extinction[3]; float eta; } hj_dielectric;
 typedef struct hj_emissive   { float power[3]; float _pad; } hj_emissive;
+
+/* Image texture (no counterpart upstream: the reference's only texture is the procedural checkerboard,
+ * shader/materials/diffusecb.glsl).  16 bytes.  A HJ_MAT_DIFFUSE_TEXTURED word's index names a texture directly.
+ * Texels are RGBA32F (4 floats, linear, alpha ignored), row-major, row 0 = the TOP of the image (the v = 1 edge);
+ * the texture's texels start at texels[4 * first_texel].  The lookup is defined in DESIGN.md ("Image textures"). */
+#define HJ_TEX_NEAREST 0u
+#define HJ_TEX_BILINEAR 1u
+typedef struct hj_texture { uint32_t width, height; uint32_t filter; uint32_t first_texel; } hj_texture;
+/* The textures of a scene, borrowed for the duration of the call.  num_texels counts texels (4 floats each). */
+typedef struct hj_texture_set {
+  const hj_texture* textures; size_t num_textures;
+  const float*      texels;   size_t num_texels;
+} hj_texture_set;
 
 /* ImageBlock, src/main.rs:608-617 / shader/block.glsl:1-8.  40 bytes.
  * One per integrator+reconstruction dispatch pair in the reference
@@ -242,6 +256,12 @@ void hj_default_render_opts(hj_render_opts* opts);
  * The previous scene is released first; the new one replaces it only when every stage has succeeded.  An upload that fails leaves
  * the context without a scene, and leaves the tree on the device (hj_build_bvh_device) as it was, ready for a retry. */
 int hj_scene_upload(hj_context* ctx, const hj_scene_desc* scene);
+/* hj_scene_upload with image textures (no counterpart upstream); hj_scene_upload(ctx, s) is hj_scene_upload_textured(ctx, s, NULL).
+ * A HJ_MAT_DIFFUSE_TEXTURED word whose index is >= num_textures (any such word with textures == NULL), a texture with a zero
+ * width or height, a filter other than HJ_TEX_NEAREST / HJ_TEX_BILINEAR, or texels beyond num_texels: HJ_ERR_INVALID (checked
+ * before anything else happens, so a tree left by hj_build_bvh_device stays on the device); more than 2^32 texels, or a width or
+ * height above 2^24: HJ_ERR_UNSUPPORTED.  The texels are copied to the device with the rest of the scene. */
+int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* scene, const hj_texture_set* textures /* may be NULL */);
 
 /* -------------------------------------------------------------- framebuffer */
 
@@ -411,6 +431,10 @@ int hj_reduce_framebuffers(hj_context* const* ctxs, int n, int root);
  *   framebuffer untouched. */
 int hj_debug_trace(hj_context* ctx, const float* rays, size_t n, uint32_t use_bvh, uint32_t any_hit, float* hits);
 int hj_debug_samples(hj_context* ctx, const hj_image_block* block, const hj_render_opts* opts, float* samples);
+/* hj_debug_texture_lookup: the colour the shade stage takes from texture `texture` of the uploaded scene at n (u, v) pairs
+ *   (uv = n x 2 floats, rgb = n x 3 floats), by the same device function.  No scene: HJ_ERR_STATE; texture out of range:
+ *   HJ_ERR_INVALID. */
+int hj_debug_texture_lookup(hj_context* ctx, uint32_t texture, const float* uv, size_t n, float* rgb);
 /* hj_debug_light_grid: the light-shaft visibility grid hj_scene_upload would build for `scene` (pure host code: no context,
  *   no GPU).  Returns the cells per axis (0: nothing can be proven for this scene).  bits (may be NULL) = res^3 bytes, x fastest:
  *   bit e of a cell set = every next-event shadow ray from a hit point in that cell to emitter e is unoccluded; the cell of a

@@ -41,6 +41,15 @@ int hjh_scene_add_mirror(hjh_scene* s);
 int hjh_scene_add_dielectric(hjh_scene* s, const float extinction[3], float eta_ratio); /* clear(): extinction 0 */
 int hjh_scene_add_emissive(hjh_scene* s, const float power[3]);
 
+/* Image textures (no counterpart upstream: the reference's only texture is the checkerboard).  hjh_scene_add_texture copies
+ * w x h texels of `channels` (3 or 4) floats, row 0 = the top of the image, filter HJ_TEX_NEAREST or HJ_TEX_BILINEAR, and returns
+ * the texture index (>= 0) or a negative hj_status.  hjh_scene_add_texture_file reads PFM (linear values; rows bottom-up on disk,
+ * as hjh_write_pfm writes them) or binary PPM P6 with maxval 255 (sRGB-decoded to linear); other formats (PNG, JPEG, ...) are an
+ * error.  hjh_scene_add_diffuse_textured returns a material index: diffuse, colour from the texture (HJ_MAT_DIFFUSE_TEXTURED). */
+int hjh_scene_add_texture(hjh_scene* s, uint32_t width, uint32_t height, const float* texels, uint32_t channels, uint32_t filter);
+int hjh_scene_add_texture_file(hjh_scene* s, const char* path, uint32_t filter);
+int hjh_scene_add_diffuse_textured(hjh_scene* s, int texture);
+
 /* Vertices (src/main.rs:54-60, pushed at :465-474).  Returns the index of
  * the first vertex added, or negative status. */
 long hjh_scene_add_vertices(hjh_scene* s, const hj_vertex* v, size_t n);
@@ -66,6 +75,8 @@ int  hjh_scene_compile_shapes(const hjh_scene* s, hjh_compiled** out);
 void hjh_compiled_destroy(hjh_compiled* c);
 /* Borrowed view; valid while `c` lives. */
 int  hjh_compiled_desc(const hjh_compiled* c, hj_scene_desc* out);
+/* Borrowed view of the scene's textures (what hj_scene_upload_textured takes); valid while `c` lives.  No textures: all zero. */
+int  hjh_compiled_textures(const hjh_compiled* c, hj_texture_set* out);
 /* Replace the tree (e.g. by the one hj_build_bvh_device made from this scene's shapes); n must be 2 * shapes - 1. */
 int  hjh_compiled_set_bvh(hjh_compiled* c, const hj_bvh_node* nodes, size_t n);
 /* The tree passes of hjh_scene_compile on the INSTALLED tree (e.g. hj_build_bvh_device's): `reinsert_passes` passes of the
@@ -84,7 +95,7 @@ int  hjh_compiled_directional_bvh(const hjh_compiled* c, int mode, size_t vote_p
  * 256 B, src/main.rs:314-339) and the packing itself (src/main.rs:561-605),
  * for tools that want the reference's exact buffer image. */
 size_t hjh_compiled_packed_size(const hjh_compiled* c);
-int    hjh_compiled_pack(const hjh_compiled* c, void* buffer, size_t size);
+int    hjh_compiled_pack(const hjh_compiled* c, void* buffer, size_t size);   /* a scene with textures: HJ_ERR_UNSUPPORTED */
 
 /* --- ImageBlockGenerator, src/main.rs:619-682 (deterministic) ------------- */
 size_t hjh_num_blocks_per_pass(uint32_t width, uint32_t height, uint32_t block_size);
@@ -100,6 +111,10 @@ size_t hjh_make_blocks(uint32_t width, uint32_t height, uint32_t block_size, uin
  * (`light*` -> emissive with `Ke`, `glass*` -> dielectric 1.5, `mirror*` -> mirror, else diffuse `Kd`), every
  * vertex needs a normal, models without material contribute vertices only, hard-coded camera. */
 int hjh_scene_from_obj(const char* path, hjh_scene** out);
+/* The same, except that a material of the diffuse kind with `map_Kd FILE` becomes textured (hjh_scene_add_texture_file of FILE
+ * relative to the MTL's directory, bilinear filter).  map_Kd with option flags (-s, -o, -clamp, ...) is an error.
+ * hjh_scene_from_obj ignores map_Kd, as the reference does. */
+int hjh_scene_from_obj_textured(const char* path, hjh_scene** out);
 /* `--put-cbox-spheres`, src/main.rs:1463-1483. */
 int hjh_scene_put_cbox_spheres(hjh_scene* s);
 
