@@ -239,6 +239,7 @@ typedef struct hjo_counters {
 
 typedef struct {
   const hj_scene_desc* sc;
+  const hj_texture_set* tex;   /* image textures (NULL: none); checked by check_textures before any render */
   uint32_t ns, nq, nt;
   int use_bvh;
   hjo_counters* ctr;
@@ -265,6 +266,35 @@ static const hj_bvh_node* g_dir_arrays = NULL;
 HJO_EXPORT void hjo_set_directional_bvh(int mode, const hj_bvh_node* arrays) {
   g_dir_mode = (arrays || mode < 0) ? mode : 0;
   g_dir_arrays = arrays;
+}
+
+/* IMAGE TEXTURES (no counterpart upstream; DESIGN.md "Image textures"): the texture set of the scenes rendered next, borrowed
+ * until it is replaced; NULL = none.  Every entry point that shades checks it against the scene first (check_textures) and
+ * refuses - renders nothing - what hj_scene_upload_textured refuses. */
+static const hj_texture_set* g_textures = NULL;
+HJO_EXPORT void hjo_set_textures(const hj_texture_set* t) { g_textures = t; }
+
+static int check_texture_set(const hj_texture_set* t) {
+  if (!t) return HJ_OK;
+  if ((t->num_textures && !t->textures) || (t->num_texels && !t->texels)) return HJ_ERR_INVALID;
+  if (t->num_texels > ((size_t)1 << 32) || t->num_textures + t->num_texels > ((size_t)1 << 32)) return HJ_ERR_UNSUPPORTED;
+  for (size_t i = 0; i < t->num_textures; i++) {
+    const hj_texture* x = &t->textures[i];
+    if (x->width == 0 || x->height == 0 || x->filter > HJ_TEX_BILINEAR) return HJ_ERR_INVALID;
+    if (x->width > (1u << 24) || x->height > (1u << 24)) return HJ_ERR_UNSUPPORTED;
+    if ((uint64_t)x->first_texel + (uint64_t)x->width * x->height > (uint64_t)t->num_texels) return HJ_ERR_INVALID;
+  }
+  return HJ_OK;
+}
+/* The set, and every HJ_MAT_DIFFUSE_TEXTURED word of the scene names one of its textures. */
+static int check_textures(const hj_scene_desc* sc, const hj_texture_set* t) {
+  int rc = check_texture_set(t);
+  if (rc != HJ_OK) return rc;
+  const size_t n = t ? t->num_textures : 0;
+  for (size_t i = 0; i < sc->num_materials; i++)
+    if ((sc->materials[i] >> HJ_MATERIAL_TAG_SHIFT) == HJ_MAT_DIFFUSE_TEXTURED && (sc->materials[i] & HJ_MATERIAL_INDEX_MASK) >= n)
+      return HJ_ERR_INVALID;
+  return HJ_OK;
 }
 
 static inline v3 ld3(const float* p) { return V(p[0], p[1], p[2]); }
@@ -543,13 +573,51 @@ static inline v3 checkerboard(const hj_diffuse_cb* m, float u, float v) {
   return (a != b) ? ld3(m->color_b) : ld3(m->color_a);
 }
 
+/* Image textures (no counterpart upstream): DESIGN.md "Image textures" restated - repeat wrap, nearest or bilinear, float32
+ * without contraction, row 0 at v = 1.  Texture t of a set that check_texture_set accepted. */
+static inline v3 texel3(const hj_texture_set* ts, const hj_texture* x, uint32_t px, uint32_t py) {
+  return ld3(&ts->texels[4 * ((size_t)x->first_texel + (size_t)py * x->width + px)]);
+}
+static inline int32_t wrap_mod(int32_t i, int32_t n) { return i < 0 ? i + n : (i >= n ? i - n : i); }   /* i in [-n, 2n) */
+static v3 texture_rgb(const hj_texture_set* ts, uint32_t t, float u, float v) {
+  const hj_texture* x = &ts->textures[t];
+  const uint32_t W = x->width, H = x->height;
+  float s = u - floorf(u), q = v - floorf(v);          /* s or q may round to 1.0 */
+  if (!isfinite(s)) s = 0.0f;
+  if (!isfinite(q)) q = 0.0f;
+  const float fW = (float)W, fH = (float)H;
+  if (x->filter == HJ_TEX_NEAREST) {
+    uint32_t px = (uint32_t)(int32_t)(s * fW), py = (uint32_t)(int32_t)((1.0f - q) * fH);
+    if (px > W - 1u) px = W - 1u;
+    if (py > H - 1u) py = H - 1u;
+    return texel3(ts, x, px, py);
+  }
+  const float fx = s * fW - 0.5f, fy = (1.0f - q) * fH - 0.5f;
+  const float x0f = floorf(fx), y0f = floorf(fy);
+  const float ax = fx - x0f, ay = fy - y0f;
+  const int32_t x0 = (int32_t)x0f, y0 = (int32_t)y0f;
+  const uint32_t xa = (uint32_t)wrap_mod(x0, (int32_t)W), xb = (uint32_t)wrap_mod(x0 + 1, (int32_t)W);
+  const uint32_t ya = (uint32_t)wrap_mod(y0, (int32_t)H), yb = (uint32_t)wrap_mod(y0 + 1, (int32_t)H);
+  const v3 c00 = texel3(ts, x, xa, ya), c10 = texel3(ts, x, xb, ya), c01 = texel3(ts, x, xa, yb), c11 = texel3(ts, x, xb, yb);
+  const float bx = 1.0f - ax, by = 1.0f - ay;
+  return v_add(v_scale(v_add(v_scale(c00, bx), v_scale(c10, ax)), by), v_scale(v_add(v_scale(c01, bx), v_scale(c11, ax)), ay));
+}
+
+/* The diffuse materials: colour constant, from the checkerboard or from an image; NEE, cosine bounce, not discrete. */
+static inline int diffuse_tag(uint32_t tag) {
+  return tag == HJ_MAT_DIFFUSE || tag == HJ_MAT_DIFFUSECBOARD || tag == HJ_MAT_DIFFUSE_TEXTURED;
+}
+static inline v3 diffuse_color(const scene_t* S, uint32_t tag, uint32_t idx, const its_t* its) {
+  if (tag == HJ_MAT_DIFFUSE) return ld3(S->sc->diffuse[idx].color);
+  if (tag == HJ_MAT_DIFFUSECBOARD) return checkerboard(&S->sc->diffusecb[idx], its->u, its->v);
+  return texture_rgb(S->tex, idx, its->u, its->v);
+}
+
 /* shader/material.glsl:18-30 (cosine folded in; non-diffuse -> 0) */
 static inline v3 eval_bsdf(const scene_t* S, uint32_t mat, v3 wi, const its_t* its) {
   uint32_t tag = mat >> HJ_MATERIAL_TAG_SHIFT, idx = mat & HJ_MATERIAL_INDEX_MASK;
-  v3 color;
-  if (tag == HJ_MAT_DIFFUSE) color = ld3(S->sc->diffuse[idx].color);
-  else if (tag == HJ_MAT_DIFFUSECBOARD) color = checkerboard(&S->sc->diffusecb[idx], its->u, its->v);
-  else return V(0, 0, 0);
+  if (!diffuse_tag(tag)) return V(0, 0, 0);
+  v3 color = diffuse_color(S, tag, idx, its);
   float cs = dot3(its->n, wi);
   return v_scale(v_scale(color, cs), INV_PIF);
 }
@@ -567,15 +635,12 @@ static inline v3 sample_bsdf(const scene_t* S, uint32_t mat, v3 wi, const its_t*
   uint32_t tag = mat >> HJ_MATERIAL_TAG_SHIFT, idx = mat & HJ_MATERIAL_INDEX_MASK;
   *alive = 1;
   switch (tag) {
-    case HJ_MAT_DIFFUSE: {
+    case HJ_MAT_DIFFUSE:
+    case HJ_MAT_DIFFUSECBOARD:
+    case HJ_MAT_DIFFUSE_TEXTURED: {
       v3 l = rand_cos_hemisphere(rng);
       *wo = v_add(v_add(v_scale(its->ft, l.x), v_scale(its->fb, l.y)), v_scale(its->fn, l.z));
-      return ld3(S->sc->diffuse[idx].color);
-    }
-    case HJ_MAT_DIFFUSECBOARD: {
-      v3 l = rand_cos_hemisphere(rng);
-      *wo = v_add(v_add(v_scale(its->ft, l.x), v_scale(its->fb, l.y)), v_scale(its->fn, l.z));
-      return checkerboard(&S->sc->diffusecb[idx], its->u, its->v);
+      return diffuse_color(S, tag, idx, its);
     }
     case HJ_MAT_MIRROR:
       *wo = reflect3(wi, its->n);
@@ -697,7 +762,7 @@ static void integrate_ray(const scene_t* S, ray_t ray, uint32_t* rng, uint32_t m
     T = v_mul(T, V(hj_exp(-ext.x * dist), hj_exp(-ext.y * dist), hj_exp(-ext.z * dist)));
     if (tag == HJ_MAT_EMISSIVE && was_discrete)
       total = v_add(total, v_mul(T, ld3(S->sc->emissive[midx].power)));
-    if (tag == HJ_MAT_DIFFUSE || tag == HJ_MAT_DIFFUSECBOARD) {
+    if (diffuse_tag(tag)) {
       ray_t sh;
       c->nee_evals++;
       v3 imp = sample_emitter(S, its.p, rng, &sh);
@@ -718,7 +783,7 @@ static void integrate_ray(const scene_t* S, ray_t ray, uint32_t* rng, uint32_t m
     T = v_mul(T, wgt);
     if (!alive) break;
     ray.d = wo; ray.o = its.p; ray.tmin = 2.0f * M_EPSF; ray.tmax = INFINITY;
-    was_discrete = (tag != HJ_MAT_DIFFUSE && tag != HJ_MAT_DIFFUSECBOARD);
+    was_discrete = !diffuse_tag(tag);
     if (bounce >= rr_start) { /* `bounce > 3` (render.glsl:137) for rr_start = 4 */
       float q = f_min(0.99f, f_max(T.x, f_max(T.y, T.z)));
       if (rng_float(rng) > q) break;
@@ -799,7 +864,7 @@ typedef struct {
 } worker_t;
 
 struct job {
-  const hj_scene_desc* sc; const hj_render_opts* opts; const hj_image_block* blocks; size_t nblocks;
+  const hj_scene_desc* sc; const hj_texture_set* tex; const hj_render_opts* opts; const hj_image_block* blocks; size_t nblocks;
   uint32_t W, H; float* accum; int nthreads; float tanHalf;
   sample_t** smp;               /* per block-in-batch sample images */
   size_t batch_begin, batch_n;
@@ -812,7 +877,7 @@ struct job {
 static void* worker_main(void* arg) {
   worker_t* w = (worker_t*)arg; job_t* J = w->job;
   hjo_counters local; memset(&local, 0, sizeof local);   /* on this thread's stack: no false sharing between workers */
-  scene_t S; S.sc = J->sc; S.ns = (uint32_t)J->sc->num_spheres; S.nq = (uint32_t)J->sc->num_quads;
+  scene_t S; S.sc = J->sc; S.tex = J->tex; S.ns = (uint32_t)J->sc->num_spheres; S.nq = (uint32_t)J->sc->num_quads;
   S.nt = (uint32_t)J->sc->num_triangles; S.use_bvh = (int)J->opts->use_bvh; S.ctr = &local;
   const size_t chunks_per_block = (HJ_BLOCK_SIZE + ROW_CHUNK - 1) / ROW_CHUNK;
   for (;;) {
@@ -865,9 +930,11 @@ HJO_EXPORT int hjo_render_blocks(const hj_scene_desc* sc, const hj_image_block* 
   if (opts->recon_radius != 2) return HJ_ERR_UNSUPPORTED;
   if (!validate_blocks(blocks, nblocks, W, H)) return HJ_ERR_INVALID;
   if (sc->num_materials != sc->num_spheres + sc->num_quads + sc->num_triangles) return HJ_ERR_INVALID;
+  const int trc = check_textures(sc, g_textures);
+  if (trc != HJ_OK) return trc;
   if (nthreads < 1) nthreads = 1;
   job_t J; memset(&J, 0, sizeof J);
-  J.sc = sc; J.opts = opts; J.blocks = blocks; J.nblocks = nblocks; J.W = W; J.H = H; J.accum = accum;
+  J.sc = sc; J.tex = g_textures; J.opts = opts; J.blocks = blocks; J.nblocks = nblocks; J.W = W; J.H = H; J.accum = accum;
   J.nthreads = nthreads; J.tanHalf = tan_half_fov(sc->camera.fov);
   size_t max_batch = (size_t)nthreads * 4; if (max_batch < 16) max_batch = 16;
   J.smp = (sample_t**)calloc(max_batch, sizeof(sample_t*));
@@ -979,7 +1046,7 @@ HJO_EXPORT int hjo_intersect(const hj_scene_desc* sc, int use_bvh, const float* 
                              float* full) {
   hjo_counters c; memset(&c, 0, sizeof c);
   scene_t S; S.sc = sc; S.ns = (uint32_t)sc->num_spheres; S.nq = (uint32_t)sc->num_quads;
-  S.nt = (uint32_t)sc->num_triangles; S.use_bvh = use_bvh; S.ctr = &c;
+  S.nt = (uint32_t)sc->num_triangles; S.use_bvh = use_bvh; S.ctr = &c; S.tex = NULL;
   for (size_t i = 0; i < n; i++) {
     const float* r = &rays[i * 8];
     ray_t ray; ray.o = V(r[0], r[1], r[2]); ray.d = V(r[3], r[4], r[5]); ray.tmin = r[6]; ray.tmax = r[7];
@@ -1019,9 +1086,11 @@ HJO_EXPORT void hjo_camera_rays(const hj_camera* cam, uint32_t W, uint32_t H, co
  * (rgb, w, normal, depth) = layers 0 and 1 of the intermediate image. */
 HJO_EXPORT int hjo_integrate_block(const hj_scene_desc* sc, const hj_image_block* b, const hj_render_opts* opts,
                                    float* out, hjo_counters* ctr_out) {
+  const int trc = check_textures(sc, g_textures);
+  if (trc != HJ_OK) return trc;
   hjo_counters c; memset(&c, 0, sizeof c);
   scene_t S; S.sc = sc; S.ns = (uint32_t)sc->num_spheres; S.nq = (uint32_t)sc->num_quads;
-  S.nt = (uint32_t)sc->num_triangles; S.use_bvh = (int)opts->use_bvh; S.ctr = &c;
+  S.nt = (uint32_t)sc->num_triangles; S.use_bvh = (int)opts->use_bvh; S.ctr = &c; S.tex = g_textures;
   integrate_block(&S, b, opts, tan_half_fov(sc->camera.fov), (sample_t*)out, 0, b->dimension[1]);
   if (ctr_out) *ctr_out = c;
   return HJ_OK;
@@ -1048,7 +1117,7 @@ HJO_EXPORT void hjo_dielectric_probe(float eta, const float* n3, const float* wi
   hj_dielectric m = {{0.25f, 0.5f, 0.75f}, eta};
   hj_scene_desc sc; memset(&sc, 0, sizeof sc); sc.dielectric = &m; sc.num_dielectric = 1;
   hjo_counters c; memset(&c, 0, sizeof c);
-  scene_t S; S.sc = &sc; S.ns = S.nq = S.nt = 0; S.use_bvh = 1; S.ctr = &c;
+  scene_t S; S.sc = &sc; S.tex = NULL; S.ns = S.nq = S.nt = 0; S.use_bvh = 1; S.ctr = &c;
   its_t its; memset(&its, 0, sizeof its); its.n = V(n3[0], n3[1], n3[2]);
   v3 wo, ext = V(0, 0, 0); int alive;
   sample_bsdf(&S, (HJ_MAT_DIELECTRIC << HJ_MATERIAL_TAG_SHIFT), V(wi3[0], wi3[1], wi3[2]), &its, rng, &wo, &ext, &alive);
@@ -1061,9 +1130,11 @@ HJO_EXPORT void hjo_dielectric_probe(float eta, const float* n3, const float* wi
  * the tests of render.glsl:121 reject it), [4..6] shadow direction, [7] shadow tMax, [8..10] wo, [11..13] sampleBSDF weight,
  * [14] alive, [15] RNG state bits after the step, [16..18] extinction after the step, [19] emitted radiance .r if emissive. */
 HJO_EXPORT int hjo_shade_probe(const hj_scene_desc* sc, const float* rays, const uint32_t* rng_in, size_t n, float* out) {
+  const int trc = check_textures(sc, g_textures);
+  if (trc != HJ_OK) return trc;
   hjo_counters c; memset(&c, 0, sizeof c);
   scene_t S; S.sc = sc; S.ns = (uint32_t)sc->num_spheres; S.nq = (uint32_t)sc->num_quads;
-  S.nt = (uint32_t)sc->num_triangles; S.use_bvh = 1; S.ctr = &c;
+  S.nt = (uint32_t)sc->num_triangles; S.use_bvh = 1; S.ctr = &c; S.tex = g_textures;
   for (size_t i = 0; i < n; i++) {
     const float* r = &rays[i * 8];
     float* o = &out[i * 20];
@@ -1077,7 +1148,7 @@ HJO_EXPORT int hjo_shade_probe(const hj_scene_desc* sc, const float* rays, const
       uint32_t mat = sc->materials[its.id];
       uint32_t tag = mat >> HJ_MATERIAL_TAG_SHIFT, midx = mat & HJ_MATERIAL_INDEX_MASK;
       if (tag == HJ_MAT_EMISSIVE) o[19] = sc->emissive[midx].power[0];
-      if (tag == HJ_MAT_DIFFUSE || tag == HJ_MAT_DIFFUSECBOARD) {
+      if (diffuse_tag(tag)) {
         ray_t sh;
         v3 imp = sample_emitter(&S, its.p, &rng, &sh);
         o[4] = sh.d.x; o[5] = sh.d.y; o[6] = sh.d.z; o[7] = sh.tmax;
@@ -1093,6 +1164,20 @@ HJO_EXPORT int hjo_shade_probe(const hj_scene_desc* sc, const float* rays, const
     }
     memcpy(&o[0], &id, 4);
     memcpy(&o[15], &rng, 4);
+  }
+  return HJ_OK;
+}
+
+/* The colour a HJ_MAT_DIFFUSE_TEXTURED hit takes from texture t of set ts at n (u, v) pairs (uv n x 2, rgb n x 3): the probe of
+ * texture_rgb that hj_debug_texture_lookup is to the kernels'. */
+HJO_EXPORT int hjo_texture_lookup(const hj_texture_set* ts, uint32_t t, const float* uv, size_t n, float* rgb) {
+  if (!ts) return HJ_ERR_INVALID;
+  const int rc = check_texture_set(ts);
+  if (rc != HJ_OK) return rc;
+  if (t >= ts->num_textures) return HJ_ERR_INVALID;
+  for (size_t i = 0; i < n; i++) {
+    const v3 c = texture_rgb(ts, t, uv[2 * i], uv[2 * i + 1]);
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
   }
   return HJ_OK;
 }

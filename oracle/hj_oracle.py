@@ -3,6 +3,7 @@
 TEST INFRASTRUCTURE ONLY — imported by tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg; never by the product package.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -77,6 +78,9 @@ def lib():
         L.hjo_shade_probe.argtypes = [C.POINTER(abi.SceneDesc), fp, u32p, C.c_size_t, fp]
         L.hjo_set_directional_bvh.argtypes = [C.c_int, C.c_void_p]
         L.hjo_set_directional_bvh.restype = None
+        L.hjo_set_textures.argtypes = [C.POINTER(abi.TextureSet)]
+        L.hjo_set_textures.restype = None
+        L.hjo_texture_lookup.argtypes = [C.POINTER(abi.TextureSet), C.c_uint32, fp, C.c_size_t, fp]
         L.hjo_sizeof_counters.restype = C.c_size_t
         assert L.hjo_sizeof_counters() == C.sizeof(Counters)
         _LIB = L
@@ -87,8 +91,32 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+@contextlib.contextmanager
+def textures(compiled, texture_set=None):
+    """The image textures of `compiled` (its texture_set, as device.Renderer.upload_scene takes them) - or `texture_set`, an
+    abi.TextureSet that overrides them - for the oracle calls inside the block (hjo_set_textures); none after it."""
+    t = texture_set
+    if t is None and hasattr(compiled, "texture_set"):
+        t = compiled.texture_set
+        t = t if t.num_textures else None
+    L = lib()
+    L.hjo_set_textures(C.byref(t) if t is not None else None)
+    try:
+        yield
+    finally:
+        L.hjo_set_textures(None)
+
+
+def _status(name, rc):
+    """A refusal as abi.HijikiError (a RuntimeError) carrying the status."""
+    if rc != 0:
+        from hijiki_amd import abi
+        raise abi.HijikiError(rc, f"{name} failed")
+
+
 def render_blocks(compiled, blocks, width, height, opts=None, nthreads=None, accum=None):
-    """Render `blocks` (ctypes array of ImageBlock) in order.  Returns (accum[H,W,4], counters dict, seconds)."""
+    """Render `blocks` (ctypes array of ImageBlock) in order, with the compiled scene's image textures if it has any.  Returns
+    (accum[H,W,4], counters dict, seconds)."""
     from hijiki_amd import abi
     L = lib()
     opts = opts or abi.RenderOpts.default()
@@ -96,10 +124,10 @@ def render_blocks(compiled, blocks, width, height, opts=None, nthreads=None, acc
     if accum is None:
         accum = np.zeros((height, width, 4), np.float32)
     ctr, secs = Counters(), C.c_double(0)
-    rc = L.hjo_render_blocks(C.byref(compiled.desc), blocks, len(blocks), C.byref(opts), width, height, _fp(accum),
-                             nthreads, C.byref(ctr), C.byref(secs))
-    if rc != 0:
-        raise RuntimeError(f"hjo_render_blocks failed: {abi.STATUS_NAMES.get(rc, rc)}")
+    with textures(compiled):
+        rc = L.hjo_render_blocks(C.byref(compiled.desc), blocks, len(blocks), C.byref(opts), width, height, _fp(accum),
+                                 nthreads, C.byref(ctr), C.byref(secs))
+    _status("hjo_render_blocks", rc)
     return accum, ctr.as_dict(), secs.value
 
 
@@ -136,8 +164,19 @@ def shade_probe(compiled, rays, rng_states):
     rays = np.ascontiguousarray(rays, np.float32)
     rng = np.ascontiguousarray(rng_states, np.uint32)
     out = np.zeros((len(rays), 20), np.float32)
-    lib().hjo_shade_probe(C.byref(compiled.desc), _fp(rays), rng.ctypes.data_as(C.POINTER(C.c_uint32)), len(rays), _fp(out))
+    with textures(compiled):
+        _status("hjo_shade_probe", lib().hjo_shade_probe(C.byref(compiled.desc), _fp(rays), rng.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                         len(rays), _fp(out)))
     return out, out[:, 0].copy().view(np.int32), out[:, 15].copy().view(np.uint32)
+
+
+def texture_lookup(texture_set, texture, uv):
+    """hjo_texture_lookup: the colour texture `texture` of `texture_set` (abi.TextureSet) gives a HJ_MAT_DIFFUSE_TEXTURED hit at
+    (n, 2) float32 uv -> (n, 3) float32."""
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.zeros((len(uv), 3), np.float32)
+    _status("hjo_texture_lookup", lib().hjo_texture_lookup(C.byref(texture_set), int(texture), _fp(uv), len(uv), _fp(out)))
+    return out
 
 
 def camera_rays(camera, width, height, pix_xy):
@@ -153,7 +192,9 @@ def integrate_block(compiled, block, opts=None):
     opts = opts or abi.RenderOpts.default()
     out = np.zeros((block.dimension[1], block.dimension[0], 8), np.float32)
     ctr = Counters()
-    lib().hjo_integrate_block(C.byref(compiled.desc), C.byref(block), C.byref(opts), _fp(out), C.byref(ctr))
+    with textures(compiled):
+        _status("hjo_integrate_block", lib().hjo_integrate_block(C.byref(compiled.desc), C.byref(block), C.byref(opts), _fp(out),
+                                                                 C.byref(ctr)))
     return out, ctr.as_dict()
 
 

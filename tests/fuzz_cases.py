@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 import scenes
+import texture_scenes
 from hijiki_amd import abi, device, host
 from oracle import hj_oracle as O
 
@@ -34,7 +35,7 @@ def source_seed():
 
 
 def fuzz_scene(r, rng):
-    kind = int(rng.integers(0, 5))
+    kind = int(rng.integers(0, 6))
     if kind == 0:
         cs = scenes.random_scene(int(rng.integers(0, 10000)))
     elif kind == 1:
@@ -43,8 +44,13 @@ def fuzz_scene(r, rng):
         cs = host.Scene.synthetic(host.SYNTH_CBOX_SPHERES, mesh_triangles=int(rng.choice([320, 1280]))).compile()
     elif kind == 3:
         cs = host.Scene.synthetic(host.SYNTH_CBOX_MESH, mesh_triangles=int(rng.choice([2000, 20000]))).compile()
-    else:
+    elif kind == 4:
         cs = scenes.nasty_scene(int(rng.integers(0, 10000)))
+    elif rng.random() < 0.7:                        # image textures (the upload and the oracle take the scene's texture set)
+        cs = texture_scenes.random_textured_scene(int(rng.integers(0, 10000)), big=rng.random() < 0.3)
+    else:
+        cs = texture_scenes.mixed_bin_scene(int(rng.integers(0, 10000)), n=int(rng.choice([8, 24])),
+                                            filt=int(rng.integers(0, 2)))
     on_device = False
     if rng.random() < 0.25 and cs.num_shapes >= 2:
         if rng.random() < 0.5:                      # the tree STAYS on the device: hj_scene_upload takes it over (scene->bvh == NULL) ...
@@ -58,7 +64,7 @@ def fuzz_scene(r, rng):
 
 def fuzz_case(r, it, big=False):
     """Differential fuzz of hj_render_frame: random scene (random_scene / random_cluster_scene / nasty_scene - degenerate geometry
-    on purpose - / the synthetic box with a small mesh), compiled or device-built tree (handed over through the host or left on
+    on purpose - / the synthetic box with a small mesh / image-textured: random_textured_scene or mixed_bin_scene), compiled or device-built tree (handed over through the host or left on
     the device), random image size (not multiples of the
     block size), samples per pixel, master seed, pass range, rank of a random world size, options (bounce limit, roulette start,
     batch size, light-shaft grid on / off, split kernels, static deal) - against the oracle's render of the same ImageBlocks with

@@ -18,6 +18,7 @@ EPS = 1e-4                                      # math.glsl:2
 PI = 3.1415926535897932384626433832795          # math.glsl:1
 TAG_SHIFT = 24                                  # src/main.rs:776
 DIFFUSE, CBOARD, MIRROR, DIELECTRIC, EMISSIVE = range(5)   # src/main.rs:34-45 (strum discriminants)
+TEXTURED = 5                                    # no counterpart upstream: diffuse, colour from an image (DESIGN.md "Image textures")
 INNER = 0xFFFFFFFF                              # scene.glsl:105 (`shapeIndex != -1`)
 
 
@@ -58,6 +59,14 @@ class Scene:
         self.cam_pos = np.array(d.camera.position[:3], np.float64)
         self.cam_rot = np.array(d.camera.rotation[:4], np.float64)
         self.cam_fov = float(d.camera.fov)
+        self.textures = []                      # [(H, W, 4) float64 texels (row 0 on top), filter]
+        t = cs.texture_set if hasattr(cs, "texture_set") else None
+        if t is not None and t.num_textures:
+            texels = _view(t.texels, t.num_texels, np.float32, 4).astype(np.float64)
+            for i in range(t.num_textures):
+                r = t.textures[i]
+                first, w, h = int(r.first_texel), int(r.width), int(r.height)
+                self.textures.append((texels[first:first + w * h].reshape(h, w, 4), int(r.filter)))
 
 
 # ------------------------------------------------------------------ rand.glsl
@@ -341,6 +350,26 @@ def checkerboard(sc, idx, u, v):
     return np.where(((fu < 0.5) ^ (fv < 0.5))[:, None], m[:, 4:7], m[:, 0:3])
 
 
+def texture(tex, filt, u, v):
+    """DESIGN.md "Image textures" in float64: repeat wrap (a non-finite fraction counts as 0), row 0 at v = 1, nearest or
+    bilinear with wrapped neighbours."""
+    H, W = tex.shape[:2]
+    with np.errstate(invalid="ignore"):
+        s, t = u - np.floor(u), v - np.floor(v)
+    s, t = np.where(np.isfinite(s), s, 0.0), np.where(np.isfinite(t), t, 0.0)
+    if filt == 0:
+        x = np.minimum((s * W).astype(np.int64), W - 1)
+        y = np.minimum(((1 - t) * H).astype(np.int64), H - 1)
+        return tex[y, x, 0:3]
+    fx, fy = s * W - 0.5, (1 - t) * H - 0.5
+    x0, y0 = np.floor(fx), np.floor(fy)
+    ax, ay = (fx - x0)[:, None], (fy - y0)[:, None]
+    x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
+    xa, xb, ya, yb = x0 % W, (x0 + 1) % W, y0 % H, (y0 + 1) % H
+    return ((tex[ya, xa, 0:3] * (1 - ax) + tex[ya, xb, 0:3] * ax) * (1 - ay)
+            + (tex[yb, xa, 0:3] * (1 - ax) + tex[yb, xb, 0:3] * ax) * ay)
+
+
 def albedo(sc, tag, midx, u, v):
     col = np.zeros((len(tag), 3))
     md = tag == DIFFUSE
@@ -348,6 +377,10 @@ def albedo(sc, tag, midx, u, v):
     mc = tag == CBOARD
     if mc.any():
         col[mc] = checkerboard(sc, midx[mc], u[mc], v[mc])
+    mt = tag == TEXTURED
+    for i in np.unique(midx[mt]):
+        k = mt & (midx == i)
+        col[k] = texture(*sc.textures[i], u[k], v[k])
     return col
 
 
@@ -357,7 +390,7 @@ def sample_bsdf(sc, tag, midx, wi, its_n, its_ft, its_fb, its_u, its_v, ext, rng
     w, wo = np.zeros((n, 3)), np.zeros((n, 3))
     ext = ext.copy()
     alive = np.ones(n, bool)
-    md = (tag == DIFFUSE) | (tag == CBOARD)
+    md = (tag == DIFFUSE) | (tag == CBOARD) | (tag == TEXTURED)
     if md.any():                                                             # :37-46
         l = cos_hemisphere(rng, idx[md])
         wo[md] = its_ft[md] * l[:, 0:1] + its_fb[md] * l[:, 1:2] + its_n[md] * l[:, 2:3]
@@ -454,7 +487,7 @@ def integrate(sc, o, d, rng_state, max_bounces=1000, rr_start=4, use_bvh=True):
         T[a] *= np.exp(-ext[a] * dist[:, None])                              # :111-112
         me = (tag == EMISSIVE) & discrete[a]
         total[a[me]] += T[a[me]] * sc.emissive[midx[me], 0:3]                # :114-116
-        mdif = (tag == DIFFUSE) | (tag == CBOARD)
+        mdif = (tag == DIFFUSE) | (tag == CBOARD) | (tag == TEXTURED)
         if mdif.any():                                                       # :117-126
             k = a[mdif]
             imp, sdir, stmax = sample_emitter(sc, ip[mdif], rng, k)

@@ -100,6 +100,8 @@ def test_textured_frame_matches_oracle_twin(gpu_renderer, oracle, flags):
     bad = (bits(got) != bits(want)).any(axis=-1)
     assert not bad.any(), f"{int(bad.sum())} of {bad.size} pixels differ from the oracle's twin"
     assert st["closest_rays"] == ctr["closest_calls"] and st["shadow_rays"] == ctr["shadow_calls"]
+    want_tex, ctr_tex, _ = oracle.render_blocks(a, host.make_blocks(W, H, spp, seed), W, H)     # the oracle's own textured frame
+    assert (bits(want_tex) == bits(want)).all() and ctr_tex == ctr
     twin_img, st2 = frame(gpu_renderer, b, W, H, spp, seed, flags)
     assert (bits(twin_img) == bits(got)).all()
     assert st["shadow_rays_proven_free"] == st2["shadow_rays_proven_free"]
@@ -199,3 +201,108 @@ def test_cli_textures_renders_like_the_library(tmp_path):
         want2 = rr.resolve()
     assert (plain.view(np.uint32) == want2.view(np.uint32)).all()
     assert not (plain.view(np.uint32) == got.view(np.uint32)).all()
+
+
+# ------------------------------------------------------------------ frames whose colour varies across surfaces, against the oracle
+
+ROUTES = ("default", "split-kernels", "no-light-grid", "linear-scan", "device-re-layout", "device-built-tree", "resident-tree")
+
+
+def render_route(r, cs, route, W, H, spp, seed, monkeypatch):
+    """cs on one route of the renderer -> (frame, stats, the oracle's RenderOpts for the same frame)."""
+    o = opts({"split-kernels": abi.RENDER_SPLIT_KERNELS, "no-light-grid": abi.RENDER_NO_LIGHT_GRID}.get(route, 0))
+    if route == "linear-scan":
+        o.use_bvh = 0
+    if route == "device-re-layout":
+        monkeypatch.setenv("HJ_UPLOAD_DEVICE", "1")
+    else:
+        monkeypatch.delenv("HJ_UPLOAD_DEVICE", raising=False)
+    on_device = False
+    if route == "device-built-tree":
+        cs.set_bvh(r.build_bvh(cs))
+    elif route == "resident-tree":                    # hj_scene_upload_textured takes the tree over; the oracle walks its copy
+        r.build_bvh(cs, keep_on_device=True)
+        cs.set_bvh(r.read_device_bvh())
+        on_device = True
+    r.upload_scene(cs, device_tree=on_device)
+    r.create_framebuffer(W, H)
+    st = r.render_frame(spp, seed, opts=o)
+    return r.read(), st, o
+
+
+def assert_oracle_frame(oracle, cs, got, st, o, W, H, spp, seed, what, blocks=None):
+    blocks = host.make_blocks(W, H, spp, seed) if blocks is None else blocks
+    want, ctr, _ = oracle.render_blocks(cs, blocks, W, H, opts=o)
+    bad = (bits(got) != bits(want)).any(axis=-1)
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} pixels differ from the oracle"
+    assert (st["closest_rays"], st["shadow_rays"], st["hits"], st["paths"]) == \
+        (ctr["closest_calls"], ctr["shadow_calls"], ctr["hits"], ctr["paths"]), what
+
+
+@pytest.mark.parametrize("route", ROUTES)
+def test_textured_scenes_match_the_oracle(gpu_renderer, oracle, monkeypatch, route):
+    """Textured random scenes (tests/texture_scenes.py: both filters, a 1024 x 1024 texture in front of the small ones, uv in
+    [-3, 3] on integers and texel edges, textured quads and spheres) and the mixed-bin mesh (checkerboard, textured and plain
+    triangles side by side) bit for bit against the oracle, counters included, on every route of the renderer."""
+    linear = route == "linear-scan"
+    W, H, spp = (64, 40, 2) if linear else (96, 64, 3)
+    for name, cs, seed in (("random textured 1", ts.random_textured_scene(1), 5), ("random textured 2", ts.random_textured_scene(2), 6),
+                           ("mixed bin, bilinear", ts.mixed_bin_scene(0), 7),
+                           ("mixed bin, nearest", ts.mixed_bin_scene(1, filt=abi.TEX_NEAREST), 8)):
+        got, st, o = render_route(gpu_renderer, cs, route, W, H, spp, seed, monkeypatch)
+        assert_oracle_frame(oracle, cs, got, st, o, W, H, spp, seed, f"{name}, {route}")
+
+
+def test_textured_tile_sharding(gpu_renderer, oracle):
+    """Each rank's share of a textured frame is the oracle's render of that rank's blocks, the shares sum to the 1-GPU frame
+    (to rounding on the block aprons, as tests/test_gpu_parity.py test_tile_sharding_sums_to_the_full_frame), and that frame
+    is the oracle's."""
+    cs = ts.random_textured_scene(3)
+    W, H, spp, seed = 288, 160, 3, 4
+    r = gpu_renderer
+    r.upload_scene(cs)
+    r.create_framebuffer(W, H)
+    st_full = r.render_frame(spp, seed)
+    full = r.read().copy()
+    assert_oracle_frame(oracle, cs, full, st_full, device.default_opts(), W, H, spp, seed, "full frame")
+    L = host.lib()
+    blocks = host.make_blocks(W, H, spp, seed)
+    per = host.blocks_per_pass(W, H)
+    world = 3
+    parts, paths = [], 0
+    for rank in range(world):
+        r.clear()
+        st = r.render_frame(spp, seed, rank=rank, world=world)
+        paths += st["paths"]
+        part = r.read().copy()
+        mine = [b for k, b in enumerate(blocks) if L.hj_block_owner(W, H, k // per, k % per, world) == rank]
+        assert_oracle_frame(oracle, cs, part, st, device.default_opts(), W, H, spp, seed, f"rank {rank} of {world}",
+                            blocks=(abi.ImageBlock * len(mine))(*mine))
+        parts.append(part.astype(np.float64))
+    assert paths == st_full["paths"]
+    np.testing.assert_allclose(np.sum(parts, axis=0), full, rtol=3e-6, atol=1e-6)
+
+
+def test_non_finite_texels(gpu_renderer, oracle):
+    """A texture holding NaN and +-Inf texels: the paths that meet them carry NaN / Inf, the reconstruction skips NaN taps -
+    the frame is still the oracle's, bit for bit, with both filters."""
+    for filt in (abi.TEX_NEAREST, abi.TEX_BILINEAR):
+        rng = np.random.default_rng(17)
+        t = ts.random_texels(rng, 6, 5)
+        t[1, 1, 0], t[2, 3, 1], t[4, 0, 2], t[5, 4, :3] = np.nan, np.inf, -np.inf, np.nan
+        s = host.Scene()
+        s.set_camera_cbox()
+        m = s.add_diffuse_textured(s.add_texture(t, filt))
+        s.add_quad((-1.2, 0, 1.2), (2.4, 0, 0), (0, 0, -2.4), m)
+        s.add_quad((-1.2, 0, -1.2), (2.4, 0, 0), (0, 2.0, 0), s.add_diffuse((0.5, 0.5, 0.5)))
+        s.add_quad((-0.4, 1.99, -0.4), (0.8, 0, 0), (0, 0, 0.8), s.add_emissive((12.0, 12.0, 12.0)))
+        s.add_sphere((0.0, 0.5, 0.0), 0.4, m)
+        cs = s.compile()
+        W, H, spp, seed = 96, 64, 2, 3
+        r = gpu_renderer
+        r.upload_scene(cs)
+        r.create_framebuffer(W, H)
+        st = r.render_frame(spp, seed)
+        got = r.read()
+        assert_oracle_frame(oracle, cs, got, st, device.default_opts(), W, H, spp, seed, f"non-finite texels, filter {filt}")
+        assert not np.isfinite(got).all()              # (the texels did reach the frame)

@@ -93,6 +93,116 @@ def textured_cbox(seed=1, W=16, H=8, extra=True, filt=abi.TEX_NEAREST):
     return scenes[0], scenes[1], tex
 
 
+# -------------------------------------------------------------------------------- scenes whose colour varies across surfaces
+
+TEXTURE_SHAPES = ((1, 1), (1, 9), (9, 1), (7, 5), (13, 9), (3, 2048))     # (H, W): 1 x 1, 1 x N, N x 1, odd sizes, 2048 x 3
+
+
+def random_texels(rng, H, W):
+    """Random colours, a few of them outside [0, 1] (negative ones included)."""
+    t = np.ones((H, W, 4), F)
+    t[..., :3] = rng.uniform(0.05, 0.95, (H, W, 3))
+    out = rng.random((H, W)) < 0.1
+    t[out, :3] = rng.uniform(-0.5, 1.6, (int(out.sum()), 3))
+    return t
+
+
+def _uv(rng, n, widths):
+    """n vertex uv in [-3, 3]: some at integers, some on texel edges k / W of the scene's textures."""
+    uv = rng.uniform(-3, 3, (n, 2))
+    kind = rng.integers(0, 4, (n, 2))
+    uv[kind == 1] = rng.integers(-3, 4, int((kind == 1).sum()))
+    edge = kind == 2
+    w = rng.choice(widths, int(edge.sum()))
+    uv[edge] = rng.integers(-3 * w, 3 * w + 1) / w
+    return uv.astype(F)
+
+
+def random_textured_scene(seed, big=True):
+    """tests/scenes.py random_scene with image textures: a 1024 x 1024 texture first (big=False: 64 x 48), so the small ones start
+    a million texels into the buffer, then 1 x 1, 1 x 9, 9 x 1, odd and 2048 x 3 ones, nearest and bilinear, some texels outside
+    [0, 1]; textured quads (walls among them), spheres (the lat-long seam) and triangles whose vertex uv lie in [-3, 3], on
+    integers and on texel edges; every other material kind alongside."""
+    rng = np.random.default_rng(3000 + seed)
+    s = host.Scene()
+    q = rng.normal(size=4)
+    q /= np.linalg.norm(q)
+    q = q * 0.15 + np.array([0, 0, 0, 1.0])
+    q /= np.linalg.norm(q)
+    s.set_camera((float(rng.uniform(-0.2, 0.2)), float(rng.uniform(0.7, 1.0)), float(rng.uniform(3.0, 3.6))),
+                 tuple(float(x) for x in q), float(rng.uniform(25, 45)))
+    shapes = [(1024, 1024) if big else (48, 64)] + list(TEXTURE_SHAPES)
+    filters = [abi.TEX_NEAREST, abi.TEX_BILINEAR] + [int(f) for f in rng.integers(0, 2, len(shapes) - 2)]
+    widths = []
+    textured = []
+    for (h, w), f in zip(shapes, filters):
+        textured.append(s.add_diffuse_textured(s.add_texture(random_texels(rng, h, w), f)))
+        widths.append(w)
+    plain = [s.add_diffuse(tuple(rng.uniform(0.1, 0.9, 3))) for _ in range(2)]
+    other = [s.add_diffuse_cboard(tuple(rng.uniform(0.2, 0.9, 3)), float(rng.uniform(0.05, 0.3)),
+                                  tuple(rng.uniform(0.1, 0.8, 3)), float(rng.uniform(0.05, 0.3))),
+             s.add_mirror(), s.add_dielectric(float(rng.uniform(1.2, 1.8))),
+             s.add_dielectric(1.5, extinction=tuple(rng.uniform(0.0, 2.0, 3)))]
+    lights = [s.add_emissive(tuple(rng.uniform(5, 25, 3))) for _ in range(2)]
+    mats = textured + textured + plain + other
+    walls = [int(rng.choice(textured)), int(rng.choice(textured)), other[0], plain[0]]
+    s.add_quad((-1.2, 0, 1.2), (2.4, 0, 0), (0, 0, -2.4), walls[0])
+    s.add_quad((-1.2, 0, -1.2), (2.4, 0, 0), (0, 2.0, 0), walls[1])
+    s.add_quad((-1.2, 0, 1.2), (0, 0, -2.4), (0, 2.0, 0), walls[2])
+    s.add_quad((1.2, 0, -1.2), (0, 0, 2.4), (0, 2.0, 0), walls[3])
+    s.add_quad((-0.4, 1.99, -0.4), (0.8, 0, 0), (0, 0, 0.8), lights[0])
+    for k in range(int(rng.integers(3, 7))):
+        m = textured[int(rng.integers(0, len(textured)))] if k < 2 else int(rng.choice(mats + lights[1:]))
+        s.add_sphere(tuple(rng.uniform([-0.8, 0.2, -0.8], [0.8, 1.2, 0.8])), float(rng.uniform(0.1, 0.35)), m)
+    s.add_quad(tuple(rng.uniform([-0.9, 0.1, -0.9], [0.3, 0.6, 0.3])), (0.5, 0.0, 0.1), (0.0, 0.5, 0.05), int(rng.choice(textured)))
+    nv = int(rng.integers(16, 40))
+    pos = rng.uniform([-0.9, 0.05, -0.9], [0.9, 1.5, 0.9], (nv, 3)).astype(F)
+    nrm = rng.normal(size=(nv, 3)).astype(F)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    base = s.add_vertices(pos, nrm, _uv(rng, nv, widths))
+    for _ in range(int(rng.integers(12, 36))):
+        a, b, c = (int(x) for x in rng.choice(nv, 3, replace=False))
+        s.add_triangle(base + a, base + b, base + c, int(rng.choice(mats + lights[1:])))
+    return s.compile()
+
+
+def mixed_bin_scene(seed=0, n=24, W=9, H=7, filt=abi.TEX_BILINEAR):
+    """The hit bin that textured hits share with the checkerboard (DESIGN.md "Image textures"): a floor and a back wall of n x n
+    cells, each two triangles, whose materials run checkerboard, textured, plain diffuse from one triangle to the next - the
+    waves of that bin hold lookups and checkerboards side by side.  uv follow the position, so both vary across the mesh."""
+    rng = np.random.default_rng(4000 + seed)
+    s = host.Scene()
+    s.set_camera_cbox()
+    tex = s.add_diffuse_textured(s.add_texture(random_texels(rng, H, W), filt))
+    cb = s.add_diffuse_cboard((0.9, 0.8, 0.2), 0.07, (0.1, 0.3, 0.8), 0.11)
+    plain = s.add_diffuse((0.6, 0.6, 0.6))
+    light = s.add_emissive((15.0, 14.0, 12.0))
+    s.add_quad((-0.4, 1.99, -0.4), (0.8, 0, 0), (0, 0, 0.8), light)
+    s.add_sphere((0.3, 0.35, 0.2), 0.3, tex)
+    cycle = (cb, tex, plain)
+    g = np.linspace(-1.2, 1.2, n + 1, dtype=F)
+    k = 0
+    for plane in ("floor", "back"):
+        if plane == "floor":
+            pos = np.array([[x, 0.0, z] for z in g for x in g], F)
+            nrm = np.tile(np.array([[0, 1, 0]], F), (len(pos), 1))
+            uv = np.stack([pos[:, 0] * 1.7, pos[:, 2] * 1.3], 1)
+        else:
+            pos = np.array([[x, (y + 1.2) / 1.2, -1.2] for y in g for x in g], F)
+            nrm = np.tile(np.array([[0, 0, 1]], F), (len(pos), 1))
+            uv = np.stack([pos[:, 0] * 2.1 + 0.3, pos[:, 1] * 1.9], 1)
+        b = s.add_vertices(pos, nrm, uv.astype(F))
+        for j in range(n):
+            for i in range(n):
+                v00 = b + j * (n + 1) + i
+                v01, v10, v11 = v00 + 1, v00 + n + 1, v00 + n + 2
+                tris = ((v00, v10, v01), (v01, v10, v11)) if plane == "floor" else ((v00, v01, v10), (v01, v11, v10))
+                for t in tris:
+                    s.add_triangle(*t, cycle[k % 3])
+                    k += 1
+    return s.compile()
+
+
 # -------------------------------------------------------------------------------- files of the textured OBJ loader
 
 OBJ = """mtllib tex.mtl
