@@ -89,8 +89,8 @@ void release_scene(hj_context* ctx) {
 }
 
 void release_slot(hj_context::BatchSlot& sl) {
-  sl.bufs.clear();                           // (DevBuf frees its memory)
-  sl.sample_bufs.clear();
+  sl.state.clear();
+  sl.samples.clear();
   sl.alloc_positions = 0;
   sl.st = hj::BatchState{};
 }
@@ -163,7 +163,7 @@ int hj_context_create(int device, hj_context** out) {
   hipDeviceProp_t prop;
   if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail(e, "hipGetDeviceProperties");
   ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
+  if ((e = hipStreamCreateWithFlags(ctx->stream.out(), hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
   // Tuning knobs (environment overrides exist only for sweeps; the defaults are the measured optima: DESIGN.md 4, profiles/NOTES.md).
   const Tuning tn = ctx->tuning = Tuning::from_env();
   ctx->num_wg = (uint32_t)ctx->num_cus * (uint32_t)tn.wg_per_cu;   // 8 x 4 waves = the 32-wave CU limit
@@ -179,20 +179,21 @@ int hj_context_create(int device, hj_context** out) {
   // of a workgroup's share of an 8192-block batch in flight at once: round 3's default, 24.7 GB of path state per slot) +6 %.
   // Frames back to back: 16384 ... 65536 are the same within a per cent (c2 3433-3441 / 3404-3412 / 3391-3411, c3 2769 / 2773-2791 /
   // 2779-2788, c4 1166-1171 / 1160-1172 / 1160 Mrays/s at 16384 / 32768 / 65536; 8192: -2.5 %): the tails that a large pool
-  // shortens are covered by the next frame there.  32768 = 12.4 GB per slot, 50 GB per context instead of 86.
+  // shortens are covered by the next frame there.  32768 = 12.1 GB per slot, 50 GB per context instead of 86.
   ctx->pool = (uint32_t)tn.pool / 64u * 64u;
   for (auto& sl : ctx->slots) {
-    if ((e = hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
-    if ((e = hipHostMalloc((void**)&sl.h_counts, sizeof(uint32_t) * 7 * ctx->num_wg, hipHostMallocDefault)) != hipSuccess) return fail(e, "hipHostMalloc");
-    for (hipEvent_t* ev : {&sl.ev_count[0], &sl.ev_count[1], &sl.ev_recon, &sl.ev_done, &sl.ev_path})
-      if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
+    sl.state.ctx = sl.samples.ctx = ctx;
+    if ((e = hipStreamCreateWithFlags(sl.stream.out(), hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
+    if ((e = sl.h_counts.reserve((size_t)(kSplitCounts + kStatWords) * ctx->num_wg)) != hipSuccess) return fail(e, "hipHostMalloc");
+    for (Event* ev : {&sl.ev_count[0], &sl.ev_count[1], &sl.ev_recon, &sl.ev_done, &sl.ev_path})
+      if ((e = hipEventCreateWithFlags(ev->out(), hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
   }
   // HJ_RECON_PRIORITY (default 1): the reconstructions run on one stream per slot of the device's highest priority.
   if (tn.recon_priority != 0) {
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
       for (auto& sl : ctx->slots)
-        if (hipStreamCreateWithPriority(&sl.rstream, hipStreamNonBlocking, greatest) != hipSuccess) sl.rstream = nullptr;
+        if (hipStreamCreateWithPriority(sl.rstream.out(), hipStreamNonBlocking, greatest) != hipSuccess) sl.rstream.h = nullptr;
   }
   *out = ctx;
   return HJ_OK;
@@ -215,29 +216,8 @@ void hj_context_destroy(hj_context* ctx) {
     if (sl.stream) (void)hipStreamSynchronize(sl.stream);
     if (sl.rstream) (void)hipStreamSynchronize(sl.rstream);
   }
-  release_scene(ctx);
-  ctx->resident.release();
-  release_batch(ctx);
-  for (auto& sl : ctx->slots) {
-    sl.d_blocks.release();
-    sl.d_tiles.release();
-    if (sl.h_tiles) (void)hipHostFree(sl.h_tiles);
-    if (sl.h_blocks) (void)hipHostFree(sl.h_blocks);
-    if (sl.h_counts) (void)hipHostFree(sl.h_counts);
-    for (hipEvent_t ev : {sl.ev_count[0], sl.ev_count[1], sl.ev_recon, sl.ev_done, sl.ev_path})
-      if (ev) (void)hipEventDestroy(ev);
-    if (sl.rstream) (void)hipStreamDestroy(sl.rstream);
-    if (sl.stream) (void)hipStreamDestroy(sl.stream);
-  }
   if (ctx->accum && ctx->accum_owned) (void)hipFree(ctx->accum);
-  for (hipEvent_t e : ctx->frame_events) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ctx->frame_event_pool) (void)hipEventDestroy(e);
-  for (auto& ep : ctx->events) {
-    (void)hipEventDestroy(ep.a);
-    (void)hipEventDestroy(ep.b);
-  }
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;                                // (the members free the rest: device buffers, pinned staging, events, streams)
 }
 
 int hj_framebuffer_create(hj_context* ctx, uint32_t width, uint32_t height, void* external) {
@@ -326,8 +306,6 @@ int hj_framebuffer_resolve(hj_context* ctx, float* host_rgb) {
   return HJ_OK;
 }
 
-// One render call = begin / submit ... / end, so that hj_render_frame can stream its block list through the batch
-// pipeline chunk by chunk without draining the slots between chunks (each drain exposes the tail of the last
 int hj_device_count(void) {
   int n = 0;
   return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
@@ -339,8 +317,6 @@ void hj_set_progress_callback(hj_context* ctx, hj_progress_fn fn, void* user, ui
   ctx->progress_user = user;
   ctx->progress_interval = interval_blocks ? interval_blocks : 1u;
 }
-
-// ---- RCCL through dlopen: the library itself has no link-time dependency on librccl.  A copy that the process has
 
 uint32_t hj_block_seed(uint64_t master, uint32_t pass, uint32_t j) { return hijiki::block_seed(master, pass, j); }
 uint32_t hj_block_owner(uint32_t width, uint32_t height, uint32_t pass, uint32_t j, uint32_t world) {

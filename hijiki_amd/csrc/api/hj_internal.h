@@ -4,7 +4,8 @@
 //   api/context.hip       context create / destroy, framebuffer, errors, environment switches            (no kernels)
 //   api/scene_upload.hip  hj_scene_upload: validation, host re-layout, emitter records, light grid; one commit at the end  (no kernels)
 //   api/scene_relayout.hip the same re-layout on the device (large trees, the tree hj_build_bvh_device left there)
-//   api/render.hip        batch slots, the launches of kernels/hj_kernels.h, render calls, probes
+//   api/render.hip        the launches of kernels/hj_kernels.h (the only unit that includes them), walk-statistics readers
+//   api/render_calls.hip  batch slots, render calls, hj_reserve, the pipeline, the worker thread, probes   (no kernels)
 //   api/comm.hip          RCCL (dlopen), hj_comm_*, hj_reduce_framebuffers
 //   api/lbvh_build.hip    hj_build_bvh_device: host half of kernels/hj_lbvh.h
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
@@ -82,7 +83,44 @@ struct DevBufs {
     for (auto& b : bufs) if (b.p) to.bufs.push_back(std::move(b));
     bufs.clear();
   }
+  void clear() { bufs.clear(); }
 };
+
+// Pinned host staging of `count` Ts: move-only, freed with the object; grow-only like dev_alloc.
+template <class T>
+struct PinnedBuf {
+  T* p = nullptr;
+  size_t count = 0;
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), count(o.count) { o.p = nullptr; o.count = 0; }
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(count, o.count); } return *this; }
+  ~PinnedBuf() { release(); }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; count = 0; }
+  // room for `need` Ts: a buffer that is too small is replaced by one of max(need, grow) Ts
+  hipError_t reserve(size_t need, size_t grow = 0) {
+    if (p && count >= need) return hipSuccess;
+    release();
+    const size_t n = std::max(need, grow);
+    const hipError_t e = hipHostMalloc((void**)&p, sizeof(T) * n, hipHostMallocDefault);
+    if (e == hipSuccess) count = n; else p = nullptr;
+    return e;
+  }
+};
+
+// One HIP stream or event and its owner: move-only, destroyed with the object.  Created through out(), used as the handle.
+template <class H, hipError_t (*destroy)(H)>
+struct HipHandle {
+  H h = nullptr;
+  HipHandle() = default;
+  HipHandle(HipHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+  HipHandle& operator=(HipHandle&& o) noexcept { if (this != &o) { reset(); std::swap(h, o.h); } return *this; }
+  ~HipHandle() { reset(); }
+  void reset() { if (h) (void)destroy(h); h = nullptr; }
+  H* out() { reset(); return &h; }                    // for hipStreamCreate* / hipEventCreate*
+  operator H() const { return h; }
+};
+using Stream = HipHandle<hipStream_t, hipStreamDestroy>;
+using Event = HipHandle<hipEvent_t, hipEventDestroy>;
 
 // HJ_*_TIMING: a call's stage times on stderr (fmt: a "%s" and a "%f"), each since the previous mark, after draining `sync` if set
 struct StageClock {
@@ -99,19 +137,27 @@ struct StageClock {
   }
 };
 
-struct EventPair { hipEvent_t a, b; int kind; };
+struct EventPair { Event a, b; int kind; };
+
+// A batch's statistics read-back: one array of num_wg words per statistic (BatchState::acc_closest and the four after it, one
+// allocation), behind the split path's two arrays of per-workgroup ray counts (one per round parity) in BatchSlot::h_counts.
+enum StatWord : uint32_t { kStatClosest, kStatShadow, kStatHits, kStatUnoccluded, kStatDirect, kStatWords };
+constexpr uint32_t kSplitCounts = 2;
 
 }  // namespace hjapi
 
 using hjapi::DevBuf;
 using hjapi::DevBufs;
 using hjapi::EventPair;
+using hjapi::Event;
+using hjapi::PinnedBuf;
+using hjapi::Stream;
 
 constexpr uint32_t kMaxSlots = 4;
 
 struct hj_context {
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;
   std::string error;
   int num_cus = 256;
 
@@ -130,19 +176,17 @@ struct hj_context {
   // one batch (a few long paths) overlaps the throughput phase of the next ones.
   struct BatchSlot {
     hj::BatchState st{};
-    std::vector<DevBuf> bufs, sample_bufs;   // path-state arrays + queues; per-sample buffers
+    DevBufs state, samples;               // path-state arrays + queues; per-sample buffers (api/render_calls.hip batch_arrays)
     DevBuf d_blocks, d_tiles;
-    uint32_t* h_tiles = nullptr;          // pinned staging of the per-tile block lists
-    size_t h_tiles_cap = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t rstream = nullptr;        // the reconstruction's stream (high priority: see hj_context_create)
-    hipEvent_t ev_path = nullptr;         // this slot's path kernel has finished (the reconstruction stream waits for it)
-    hj_image_block* h_blocks = nullptr;   // pinned staging of the block list
-    uint32_t h_blocks_cap = 0;
-    uint32_t* h_counts = nullptr;         // pinned read-back: 2 (split-path ray counts) + 5 (statistics) arrays of num_wg words
-    hipEvent_t ev_count[2] = {nullptr, nullptr};
-    hipEvent_t ev_recon = nullptr;        // this slot's reconstruction has run (orders framebuffer updates)
-    hipEvent_t ev_done = nullptr;         // batch complete, statistics copied back
+    PinnedBuf<uint32_t> h_tiles;          // pinned staging of the per-tile block lists
+    Stream stream;
+    Stream rstream;                       // the reconstruction's stream (high priority: see hj_context_create)
+    Event ev_path;                        // this slot's path kernel has finished (the reconstruction stream waits for it)
+    PinnedBuf<hj_image_block> h_blocks;   // pinned staging of the block list
+    PinnedBuf<uint32_t> h_counts;         // pinned read-back: kSplitCounts + kStatWords arrays of num_wg words
+    Event ev_count[2];
+    Event ev_recon;                       // this slot's reconstruction has run (orders framebuffer updates)
+    Event ev_done;                        // batch complete, statistics copied back
     bool pending = false, recon_recorded = false;
     uint32_t nb_in_flight = 0;            // ImageBlocks of the batch in flight (progress reporting)
     uint32_t g_in_flight = 0;             // workgroups of the batch in flight (statistics read-back)
@@ -182,8 +226,8 @@ struct hj_context {
   // Frames back to back WITHOUT draining the batch pipeline between them (HJ_RENDER_NO_DRAIN, hj_pipeline_wait): one event per
   // frame submitted (recorded behind its last batch), the statistics accumulated since the last full drain, the slot rotation
   // carried from frame to frame.
-  std::vector<hipEvent_t> frame_events;   // oldest first: frames submitted, not yet waited for
-  std::vector<hipEvent_t> frame_event_pool;
+  std::vector<Event> frame_events;        // oldest first: frames submitted, not yet waited for
+  std::vector<Event> frame_event_pool;
   bool pipe_active = false;               // something submitted with HJ_RENDER_NO_DRAIN has not been drained yet
   hj_render_stats pipe_stats{};
   size_t pipe_k = 0;
@@ -216,7 +260,7 @@ std::string get_error(hj_context* ctx);
 // stayed on the device against an upload of OTHER geometry with the same counts (an accident, not an adversary).
 uint64_t shape_arrays_hash(const hj_scene_desc* s);
 void put_error(hj_context* ctx, const std::string& text);
-std::mutex& alloc_mutex();                           // process-wide: a context sizing its batch slots (api/render.hip run_submit)
+std::mutex& alloc_mutex();                           // process-wide: a context sizing its batch slots (api/render_calls.hip run_submit)
 // api/scene_upload.hip: every invariant an upload checks; HJ_MAT_DIFFUSE_TEXTURED indices must be < num_textures
 int validate_scene(hj_context* ctx, const hj_scene_desc* s, size_t num_textures);
 int validate_textures(hj_context* ctx, const hj_texture_set* t);             // api/texture.hip
@@ -226,6 +270,17 @@ void release_slot(hj_context::BatchSlot& sl);
 void release_batch(hj_context* ctx);
 int sync_all(hj_context* ctx);                       // drains the context's streams (api/context.hip)
 void drop_cached_comms(hj_context* ctx);             // api/comm.hip: the communicators hj_reduce_framebuffers made for ctx
+
+// api/render.hip: the launches of kernels/hj_kernels.h, on `s` (a failed launch surfaces at the render call's hipGetLastError)
+void launch_path_wavefront(const hj::BatchState& st, const hj::DeviceScene& sc, const hj_render_opts& o, size_t lds_bytes, hipStream_t s);
+void launch_gen_camera(const hj::BatchState& st, const hj::DeviceScene& sc, hipStream_t s);
+void launch_trace_closest(const hj::BatchState& st, const hj::DeviceScene& sc, bool bvh, uint32_t parity, hipStream_t s);
+void launch_shade(const hj::BatchState& st, const hj::DeviceScene& sc, uint32_t parity, const hj_render_opts& o, hipStream_t s);
+void launch_trace_shadow(const hj::BatchState& st, const hj::DeviceScene& sc, bool bvh, hipStream_t s);
+// tiles: the per-tile block lists (CSR: tiles_x * tiles_y + 1 offsets, then the block indices)
+void launch_reconstruct(const hj::BatchState& st, float stddev, const uint32_t* tiles, uint32_t tiles_x, uint32_t tiles_y,
+                        float4* accum, uint32_t width, uint32_t height, hipStream_t s);
+void launch_debug_trace(const hj::DeviceScene& sc, const float* rays, uint32_t n, bool bvh, bool any_hit, float4* hits, hipStream_t s);
 
 }  // namespace hjapi
 

@@ -140,17 +140,17 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   // (on a stream of its own - a batch slot's, idle outside render calls -, so that the small copies the host needs for the top
   // do not queue behind it)
   hj_bvh_node* d_staged = nullptr;
-  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
+  Event ev_a, ev_b;
   hipStream_t side = ctx->slots[0].stream;
   if (sah_wave) {
     HJ_TRY(bufs.alloc(d_staged, 2 * (size_t)m));
-    HJ_HIP(ctx, hipEventCreateWithFlags(&ev.a, hipEventDisableTiming));
-    HJ_HIP(ctx, hipEventCreateWithFlags(&ev.b, hipEventDisableTiming));
-    HJ_HIP(ctx, hipEventRecord(ev.a, st));
-    HJ_HIP(ctx, hipStreamWaitEvent(side, ev.a, 0));
+    HJ_HIP(ctx, hipEventCreateWithFlags(ev_a.out(), hipEventDisableTiming));
+    HJ_HIP(ctx, hipEventCreateWithFlags(ev_b.out(), hipEventDisableTiming));
+    HJ_HIP(ctx, hipEventRecord(ev_a, st));
+    HJ_HIP(ctx, hipStreamWaitEvent(side, ev_a, 0));
     hipLaunchKernelGGL(hj::lbvh::k_emit_clusters_sah_wave, dim3(K), dim3(64), 0, side, t, K, cl, idx_mask, d_staged,
                        tn.bvh_child_order);
-    HJ_HIP(ctx, hipEventRecord(ev.b, side));
+    HJ_HIP(ctx, hipEventRecord(ev_b, side));
   }
   // ---- the top of the tree on the host: binned SAH over the K clusters and the nbig large shapes
   struct Item { float lo[3], hi[3]; uint32_t shape; uint32_t cluster; uint32_t records; float weight; uint32_t first; };
@@ -452,7 +452,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   HJ_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t*>(cl.base), cbase.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice, st));
   HJ_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t*>(cl.exit), cexit.data(), sizeof(uint32_t) * K, hipMemcpyHostToDevice, st));
   if (sah_wave) {
-    HJ_HIP(ctx, hipStreamWaitEvent(st, ev.b, 0));
+    HJ_HIP(ctx, hipStreamWaitEvent(st, ev_b, 0));
     hipLaunchKernelGGL(hj::lbvh::k_place_clusters, dim3(K), dim3(64), 0, st, K, cl, d_staged, d_out);
   }
   else if (sah_clusters)
