@@ -110,6 +110,12 @@ class TextureSet(C.Structure):
                 ("texels", C.POINTER(f32)), ("num_texels", C.c_size_t)]
 
 
+class Environment(C.Structure):
+    """hj_environment (ABI 0.5): texture `texture` of the scene's set lights every ray that leaves the scene (DESIGN.md
+    "Environment lighting")."""
+    _fields_ = [("texture", u32), ("scale", f32 * 3), ("select_prob", f32), ("_reserved", u32)]
+
+
 class ImageBlock(C.Structure):
     _fields_ = [("id", u32), ("seed", u32), ("origin", u32 * 2), ("dimension", u32 * 2),
                 ("original_dimension", u32 * 2), ("sample_offset", f32 * 2)]

@@ -92,6 +92,7 @@ void release_slot(hj_context::BatchSlot& sl) {
   sl.state.clear();
   sl.samples.clear();
   sl.alloc_positions = 0;
+  sl.env_bins = false;
   sl.st = hj::BatchState{};
 }
 void release_batch(hj_context* ctx) {
@@ -113,7 +114,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (4u << 8) | 0u; }   // 0.4.0: image textures (hj_scene_upload_textured, hj_debug_texture_lookup)
+uint32_t hj_version(void) { return (0u << 16) | (5u << 8) | 0u; }   // 0.5.0: environment lighting (hj_scene_upload_env, hj_debug_env_*)
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

@@ -10,6 +10,7 @@
 //   api/lbvh_build.hip    hj_build_bvh_device: host half of kernels/hj_lbvh.h
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
 //   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
+//   api/environment.hip   environment lighting: the checks and the alias table of hj_scene_upload_env, hj_debug_env_*
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -191,6 +192,7 @@ struct hj_context {
     uint32_t nb_in_flight = 0;            // ImageBlocks of the batch in flight (progress reporting)
     uint32_t g_in_flight = 0;             // workgroups of the batch in flight (statistics read-back)
     size_t alloc_positions = 0;           // record positions the path-state arrays hold (workgroups x pool)
+    bool env_bins = false;                // ... and the queues hold the miss bin of an environment (batch_arrays)
   } slots[kMaxSlots];
   uint32_t num_slots = 3;
   uint32_t slots_eff = 3;                // ... the current render call rotates through (1 when device memory is very short)
@@ -263,6 +265,11 @@ void put_error(hj_context* ctx, const std::string& text);
 std::mutex& alloc_mutex();                           // process-wide: a context sizing its batch slots (api/render_calls.hip run_submit)
 // api/scene_upload.hip: every invariant an upload checks; HJ_MAT_DIFFUSE_TEXTURED indices must be < num_textures
 int validate_scene(hj_context* ctx, const hj_scene_desc* s, size_t num_textures);
+// api/environment.hip: an environment's checks (hj_scene_upload_env) and its sampling distribution, built on the host before anything
+// is allocated; upload_environment copies the table and fills DeviceScene's env_* fields (env == NULL: nothing)
+struct EnvTable { std::vector<float4> rec; std::vector<double> prob, omega; double weight_sum = 0.0; };
+int validate_environment(hj_context* ctx, const hj_scene_desc* s, const hj_texture_set* t, const hj_environment* env, EnvTable& out);
+int upload_environment(DevBufs& bufs, const hj_texture_set* t, const hj_environment* env, const EnvTable& table, hj::DeviceScene& d);
 int validate_textures(hj_context* ctx, const hj_texture_set* t);             // api/texture.hip
 int upload_textures(DevBufs& bufs, const hj_texture_set* t, const float4** out);
 void release_scene(hj_context* ctx);

@@ -12,6 +12,14 @@ namespace hjapi {
 void launch_path_wavefront(const hj::BatchState& st, const hj::DeviceScene& sc, const hj_render_opts& o, size_t lds_bytes, hipStream_t s) {
   const dim3 blk(hj::kBlockThreads), grid(st.num_wg);
   const bool pairs = sc.has_pairs != 0, nt = sc.stream_state != 0;
+  if (sc.env_alias) {                        // a scene with an environment: the instantiations with the miss bin
+    if (!o.use_bvh) hipLaunchKernelGGL((hj::k_path_wavefront_env<false, false, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
+    else if (pairs && nt) hipLaunchKernelGGL((hj::k_path_wavefront_env<true, true, true>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
+    else if (pairs) hipLaunchKernelGGL((hj::k_path_wavefront_env<true, true, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
+    else if (nt) hipLaunchKernelGGL((hj::k_path_wavefront_env<true, false, true>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
+    else hipLaunchKernelGGL((hj::k_path_wavefront_env<true, false, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
+    return;
+  }
   if (!o.use_bvh) hipLaunchKernelGGL((hj::k_path_wavefront<false, false, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
   else if (pairs && nt) hipLaunchKernelGGL((hj::k_path_wavefront<true, true, true>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
   else if (pairs) hipLaunchKernelGGL((hj::k_path_wavefront<true, true, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
@@ -26,12 +34,15 @@ void launch_gen_camera(const hj::BatchState& st, const hj::DeviceScene& sc, hipS
 
 void launch_trace_closest(const hj::BatchState& st, const hj::DeviceScene& sc, bool bvh, uint32_t parity, hipStream_t s) {
   const dim3 blk(hj::kBlockThreads), grid(st.num_wg);
-  if (bvh) hipLaunchKernelGGL(hj::k_trace_closest<true>, grid, blk, 0, s, st, sc, parity);
+  if (sc.env_alias && bvh) hipLaunchKernelGGL(hj::k_trace_closest_env<true>, grid, blk, 0, s, st, sc, parity);
+  else if (sc.env_alias) hipLaunchKernelGGL(hj::k_trace_closest_env<false>, grid, blk, 0, s, st, sc, parity);
+  else if (bvh) hipLaunchKernelGGL(hj::k_trace_closest<true>, grid, blk, 0, s, st, sc, parity);
   else hipLaunchKernelGGL(hj::k_trace_closest<false>, grid, blk, 0, s, st, sc, parity);
 }
 
 void launch_shade(const hj::BatchState& st, const hj::DeviceScene& sc, uint32_t parity, const hj_render_opts& o, hipStream_t s) {
-  hipLaunchKernelGGL(hj::k_shade, dim3(st.num_wg), dim3(hj::kBlockThreads), 0, s, st, sc, parity, o.max_bounces, o.rr_start);
+  if (sc.env_alias) hipLaunchKernelGGL(hj::k_shade_env, dim3(st.num_wg), dim3(hj::kBlockThreads), 0, s, st, sc, parity, o.max_bounces, o.rr_start);
+  else hipLaunchKernelGGL(hj::k_shade, dim3(st.num_wg), dim3(hj::kBlockThreads), 0, s, st, sc, parity, o.max_bounces, o.rr_start);
 }
 
 void launch_trace_shadow(const hj::BatchState& st, const hj::DeviceScene& sc, bool bvh, hipStream_t s) {

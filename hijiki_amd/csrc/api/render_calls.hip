@@ -13,7 +13,7 @@ namespace {
 // parities where it has two) or per workgroup: f(pointer, Per, elements).  ensure_batch allocates them, run_begin sums them.
 enum class Per { Sample, Position, Workgroup };
 template <class F>
-void batch_arrays(hj::BatchState& st, bool extinction, F&& f) {
+void batch_arrays(hj::BatchState& st, bool extinction, bool env, F&& f) {
   f(st.smp_rgb, Per::Sample, 1);
   f(st.smp_nd, Per::Sample, 1);
   for (int par = 0; par < 2; par++) {
@@ -25,13 +25,13 @@ void batch_arrays(hj::BatchState& st, bool extinction, F&& f) {
   }
   f(st.hit, Per::Position, 1);
   f(st.hit_tag, Per::Position, 1);
-  f(st.q_hit, Per::Position, hj::kNumTags);
+  f(st.q_hit, Per::Position, hj::kNumTags + (env ? 1 : 0));   // (an environment: the miss bin, kernels/hj_stages.h kMissBin)
   f(st.sh_o, Per::Position, 1);
   f(st.sh_d, Per::Position, 1);
   f(st.sh_c, Per::Position, 1);
   f(st.cnt_ray[0], Per::Workgroup, 1);
   f(st.cnt_ray[1], Per::Workgroup, 1);
-  f(st.cnt_hit, Per::Workgroup, hj::kNumTags);
+  f(st.cnt_hit, Per::Workgroup, hj::kNumTags + (env ? 1 : 0));
   f(st.cnt_shadow, Per::Workgroup, 1);
   f(st.acc_closest, Per::Workgroup, kStatWords);   // acc_closest .. acc_direct (StatWord): one read-back
 }
@@ -45,12 +45,12 @@ int ensure_batch(hj_context* ctx, hj_context::BatchSlot& sl, uint32_t num_blocks
   const uint32_t per_wg = (((cap + 63u) / 64u + G - 1u) / G) * 64u;     // samples of the busiest workgroup
   const uint32_t pool = all_in_flight ? per_wg : std::min(per_wg, ctx->pool_eff);
   const size_t n = (size_t)G * pool;
-  const bool ext = ctx->scene.has_extinction;
+  const bool ext = ctx->scene.has_extinction, env = ctx->scene.env_alias != nullptr;
   hj::BatchState& st = sl.st;
   int rc = HJ_OK;
   // the arrays of the sample kind (or of the others) into `set`; per-workgroup arrays for the most workgroups a call may use
   auto alloc = [&](DevBufs& set, bool samples) {
-    batch_arrays(st, ext, [&](auto*& p, Per per, size_t k) {
+    batch_arrays(st, ext, env, [&](auto*& p, Per per, size_t k) {
       if (rc == HJ_OK && (per == Per::Sample) == samples)
         rc = set.alloc(p, k * (per == Per::Sample ? cap : per == Per::Position ? n : Gmax));
     });
@@ -64,11 +64,11 @@ int ensure_batch(hj_context* ctx, hj_context::BatchSlot& sl, uint32_t num_blocks
       rc = set_error(ctx, HJ_ERR_NOMEM, "pinned block staging allocation failed");
     if (rc == HJ_OK) st.capacity = cap;
   }
-  if (rc == HJ_OK && (sl.alloc_positions < n || (ext && !st.ext[0]))) {
+  if (rc == HJ_OK && (sl.alloc_positions < n || (ext && !st.ext[0]) || (env && !sl.env_bins))) {
     sl.state.clear();
     sl.alloc_positions = 0;
     alloc(sl.state, false);
-    if (rc == HJ_OK) sl.alloc_positions = n;
+    if (rc == HJ_OK) { sl.alloc_positions = n; sl.env_bins = env; }
   }
   if (rc == HJ_OK) {
     st.acc_shadow = st.acc_closest + (size_t)kStatShadow * G;
@@ -343,7 +343,7 @@ int run_begin(hj_context* ctx, RenderRun& run, const hj_render_opts* opts, hj_re
     run.batch = (uint32_t)std::min<size_t>(batch_cap, std::max<size_t>(256, (std::max<size_t>((n + 1) / 2, std::min<size_t>(n, 4096)) + 63) / 64 * 64));
   run.batch = std::min<uint32_t>(run.batch, run.split ? 2048u : 32768u);   // (a sample index has 31 bits: 131 072 blocks at most)   // the split path keeps every sample of a batch in flight
   // Footprint: per batch slot 512 KB of samples per ImageBlock of the batch + num_wg x pool positions of
-  // path state (batch_arrays: 181 B each, 213 B with tinted dielectrics).  DEFAULTS that do not fit the device's free memory
+  // path state (batch_arrays: 181 B each, 213 B with tinted dielectrics, 4 B more with an environment).  DEFAULTS that do not fit the device's free memory
   // (other contexts on the GPU, the host application) shrink until they do: first the pool (down to 8192 positions), then the
   // batch; an explicit hj_render_opts::batch_blocks is taken as given and fails with HJ_ERR_NOMEM if it does not fit.
   const size_t small_blocks = (size_t)ctx->tuning.wg_small_blocks;
@@ -362,7 +362,7 @@ int run_begin(hj_context* ctx, RenderRun& run, const hj_render_opts* opts, hj_re
           for (auto& b : set->bufs) held += b.bytes;
       size_t bytes[3] = {};                  // per sample, per position, per workgroup
       hj::BatchState shape{};
-      batch_arrays(shape, ctx->scene.has_extinction, [&](auto*& p, Per per, size_t k) { bytes[(int)per] += sizeof(*p) * k; });
+      batch_arrays(shape, ctx->scene.has_extinction, ctx->scene.env_alias != nullptr, [&](auto*& p, Per per, size_t k) { bytes[(int)per] += sizeof(*p) * k; });
       auto need = [&](uint32_t batch, uint32_t pool_cap) {
         const size_t slots_needed = std::max<size_t>(1, std::min<size_t>(ctx->num_slots, (n + batch - 1) / std::max<uint32_t>(batch, 1u)));
         const size_t per_wg = ((((size_t)batch * hj::kSlotsPerBlock + 63) / 64 + ctx->num_wg_eff - 1) / ctx->num_wg_eff) * 64;

@@ -531,7 +531,9 @@ extern "C" {
 
 int hj_scene_upload(hj_context* ctx, const hj_scene_desc* s) { return hj_scene_upload_textured(ctx, s, nullptr); }
 
-int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* s, const hj_texture_set* tex) {
+int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* s, const hj_texture_set* tex) { return hj_scene_upload_env(ctx, s, tex, nullptr); }
+
+int hj_scene_upload_env(hj_context* ctx, const hj_scene_desc* s, const hj_texture_set* tex, const hj_environment* env) {
   if (!ctx) return HJ_ERR_INVALID;
   HJ_NOT_BUSY(ctx);
   HJ_NOT_PIPELINED(ctx);
@@ -552,6 +554,8 @@ int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* s, const hj_t
   }
   HJ_TRY(validate_textures(ctx, tex));
   HJ_TRY(validate_scene(ctx, s, tex ? tex->num_textures : 0));
+  EnvTable env_table;                                        // (api/environment.hip: the checks, then the sampling distribution)
+  HJ_TRY(validate_environment(ctx, s, tex, env, env_table));
   hj_scene_desc with_tree;
   if (resident) { with_tree = *s; with_tree.num_bvh_nodes = rt.total; s = &with_tree; }   // (bvh stays NULL: nothing below reads it on this route)
   clock.mark("validation");
@@ -579,8 +583,8 @@ int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* s, const hj_t
   // HJ_UPLOAD_DEVICE_MIN (100 000) nodes on.  An array that is not a tree takes the host path.
   RelayoutOut ro;
   int rc = HJ_ERR_UNSUPPORTED;
-  const int env = tn.upload_device;
-  if ((resident || env == 1 || (env < 0 && s->num_bvh_nodes >= (size_t)tn.upload_device_min)) && s->num_bvh_nodes >= 3)
+  const int on_device = tn.upload_device;
+  if ((resident || on_device == 1 || (on_device < 0 && s->num_bvh_nodes >= (size_t)tn.upload_device_min)) && s->num_bvh_nodes >= 3)
     rc = relayout_device_route(ctx, s, tn, resident, clock, bufs, d, ro);
   if (rc == HJ_ERR_UNSUPPORTED && resident)                 // (no host array to fall back to)
     return set_error(ctx, rc, "the tree on the device cannot be re-laid out there (fewer than 3 or too many records)");
@@ -606,6 +610,7 @@ int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* s, const hj_t
   HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->dielectric), s->num_dielectric, &d.dielectric));
   HJ_TRY(upload(bufs, reinterpret_cast<const float4*>(s->emissive), s->num_emissive, &d.emissive));
   HJ_TRY(upload_textures(bufs, tex, &d.textures));
+  HJ_TRY(upload_environment(bufs, tex, env, env_table, d));
   clock.mark("other uploads");
   HJ_TRY(upload_light_grid(bufs, s, tn, resident ? static_cast<const hj_bvh_node*>(rt.nodes.p) : nullptr, d));
   clock.mark("light-shaft grid");

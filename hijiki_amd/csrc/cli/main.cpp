@@ -1,11 +1,12 @@
 // hijiki-hip — command line of the reference (`struct Opt` / `main`, src/main.rs:1426-1494) on the MI355X path:
 //
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
-//              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] <scene.obj | synthetic:KIND>
+//              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] [--env FILE [--env-scale S]]
+//              <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
 // no preview window, so --present-interval is accepted and ignored; --seed replaces the OS-seeded block RNG; --textures (not
-// upstream) renders the MTL's map_Kd images on diffuse materials.
+// upstream) renders the MTL's map_Kd images on diffuse materials; --env (not upstream) lights the scene with a lat-long HDR image.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +25,8 @@ struct Opt {
   bool put_cbox_spheres = false, use_bvh = false, device_bvh = false, textures = false;
   uint32_t width = 800, height = 600, present_interval = 128, sample_count = 64;
   uint64_t seed = 1;
-  std::string output_image = "/tmp/output.exr", scene;
+  std::string output_image = "/tmp/output.exr", scene, env;
+  float env_scale = 1.0f;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -35,6 +37,8 @@ struct Opt {
                "    --use-bvh             Use a BVH to optimize intersections\n"
                "    --device-bvh          (not upstream) build the tree on the GPU (LBVH, stays there: fast start) instead of on the host (SAH)\n"
                "    --textures            (not upstream) diffuse materials with map_Kd take their colour from that image (PFM or P6 PPM)\n\n"
+               "        --env <file>                             (not upstream) light the scene with this lat-long image (PFM or P6 PPM)\n"
+               "        --env-scale <scale>                      [default: 1] (not upstream) radiance scale of --env\n"
                "OPTIONS:\n    -h, --height <height>                        [default: 600]\n"
                "    -o, --output-image <output-image>            [default: /tmp/output.exr] (.exr, .pfm or .png)\n"
                "        --present-interval <present-interval>    [default: 128] (ignored: no preview window)\n"
@@ -63,12 +67,20 @@ Opt parse(int argc, char** argv) {
     else if (a == "-s" || a == "--sample-count") o.sample_count = (uint32_t)std::stoul(value(i));
     else if (a == "-o" || a == "--output-image") o.output_image = value(i);
     else if (a == "--seed") o.seed = std::stoull(value(i));
+    else if (a == "--env") o.env = value(i);
+    else if (a == "--env-scale") {
+      const std::string v = value(i);
+      char* end = nullptr;
+      o.env_scale = std::strtof(v.c_str(), &end);
+      if (end == v.c_str() || *end != '\0' || !(o.env_scale >= 0.0f) || o.env_scale > 3.0e38f) usage(("bad --env-scale " + v).c_str());
+    }
     else if (a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown flag " + a).c_str());
     else if (o.scene.empty()) o.scene = a;
     else usage("more than one scene given");
   }
   if (o.scene.empty()) usage("the <scene> argument is required");
+  if (o.env.empty() && o.env_scale != 1.0f) usage("--env-scale without --env");
   return o;
 }
 
@@ -90,6 +102,13 @@ int main(int argc, char** argv) {
       scene = hijiki::scene_from_obj(opt.scene, opt.textures);         // Scene::from_obj, src/main.rs:1462
     }
     if (opt.put_cbox_spheres) hijiki::put_cbox_spheres(scene);         // src/main.rs:1463-1483
+    uint32_t env_tex = 0;
+    if (!opt.env.empty()) {                                            // --env: the image joins the scene's textures, bilinear
+      uint32_t w = 0, h = 0;
+      std::vector<float> rgba;
+      hijiki::read_texture_image(opt.env, w, h, rgba);
+      env_tex = hijiki::add_texture(scene, w, h, rgba.data(), 4, HJ_TEX_BILINEAR);
+    }
     std::printf("Building BVH\n");                                     // src/main.rs:198
     // --device-bvh: the fast start - no tree on the host at all; hj_build_bvh_device leaves its tree on the device and
     // hj_scene_upload (scene->bvh == NULL) takes it over there: a 1 M-triangle scene is renderable 40 ms after its shapes exist
@@ -102,7 +121,16 @@ int main(int argc, char** argv) {
     std::printf("Built BVH with %zu nodes\n", num_nodes);              // src/main.rs:200
 
     const hj_texture_set tex = cs.texture_set();
-    check(ctx, opt.textures ? hj_scene_upload_textured(ctx, &desc, &tex) : hj_scene_upload(ctx, &desc), "scene upload");
+    if (!opt.env.empty()) {
+      // the environment's share of next-event samples: all of them without emitters, none for a black image, half otherwise
+      hj_environment env{env_tex, {opt.env_scale, opt.env_scale, opt.env_scale}, 1.0f, 0u};
+      double weight = 0.0;
+      check(nullptr, hj_debug_env_distribution(&tex, &env, nullptr, nullptr, nullptr, nullptr, &weight), "environment");
+      if (desc.num_emitters != 0) env.select_prob = weight > 0.0 ? 0.5f : 0.0f;
+      check(ctx, hj_scene_upload_env(ctx, &desc, &tex, &env), "scene upload");
+    } else {
+      check(ctx, opt.textures ? hj_scene_upload_textured(ctx, &desc, &tex) : hj_scene_upload(ctx, &desc), "scene upload");
+    }
     check(ctx, hj_framebuffer_create(ctx, opt.width, opt.height, nullptr), "framebuffer");
     hj_render_opts ro;
     hj_default_render_opts(&ro);

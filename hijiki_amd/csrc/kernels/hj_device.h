@@ -85,6 +85,14 @@ struct DeviceScene {
   const uint16_t* light_grid;   // lg_res^3 cells, x fastest; null: no grid
   uint32_t lg_res;              // cells per axis | kLightGridHasRecords
   float lg_lo[3], lg_inv[3];    // cell index along axis k = (int)((p[k] - lg_lo[k]) * lg_inv[k])
+  // Environment lighting (hj_env.h; DESIGN.md "Environment lighting"): read by the environment instantiations only.  Last, so that no
+  // field above moves.  env_alias: env_w x env_h records (alias threshold, alias cell bits, pdf of the cell, pdf of the alias cell)
+  // in texel order; null: no environment.
+  const float4* env_alias;
+  uint32_t env_tex;             // texture of `textures`
+  uint32_t env_w, env_h;
+  float env_scale[3];
+  float env_p;                  // probability that next-event estimation picks the environment
 };
 
 // One wavefront batch = the samples of up to 4096 ImageBlocks.  Two index spaces:

@@ -29,6 +29,7 @@
 // additions is the reference's (emission, then NEE, bounce by bounce) because a workgroup's stages are
 // separated by barriers (fused) or kernel boundaries (split).
 #pragma once
+#include <type_traits>
 #include "hj_stages.h"
 #include "hj_reconstruct.h"
 
@@ -55,99 +56,19 @@ namespace hj {
 #ifndef HJ_PATH_WAVES
 #define HJ_PATH_WAVES 7   // 72 VGPRs; measured on the compacted-record kernel: 6 waves (80 VGPRs) -6 %, 8 waves (64 VGPRs) -2 %, 5 waves -5 %
 #endif
-template <bool USE_BVH, bool PAIRS, bool NT>
-__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(HJ_PATH_WAVES, 8))) void k_path_wavefront(BatchState st, DeviceScene sc, uint32_t max_bounces,
-                                                                  uint32_t rr_start) {
-  // NT (large trees): the path state is streamed past the caches (ldp / stp)
-  __shared__ WgShared sh;
-  const uint32_t g = blockIdx.x;
-  // (the called stages read the batch and scene descriptions from this kernel's argument segment and reach `sh` through its LDS address)
-  const uint64_t ka_ = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-  const uint32_t ka_lo = (uint32_t)ka_, ka_hi = (uint32_t)(ka_ >> 32), sh_lds = (uint32_t)(uintptr_t)(WgSharedLds)&sh;
-  // Camera paths without records: kernels that have the packet stage (BVH walk over a tree with pair nodes)
-  constexpr bool IMPLICIT = USE_BVH && PAIRS;
-  RoundProbe rp;
-  uint32_t groups_left = wg_num_groups(st, g);
-  uint32_t total_closest = 0, total_shadow = 0, total_hits = 0, total_unocc = 0, total_direct = 0;   // (thread 0's copies are published)
-  if (groups_left != 0) {
-    uint32_t k_next = 0;                     // next group of this workgroup's sample sequence
-    if (threadIdx.x == 0) { sh.n_ray[0] = 0; sh.n_ray[1] = 0; sh.n_gen = 0; sh.n_shadow = 0; sh.n_unocc = 0; sh.n_direct = 0; sh.cam_first = 0xFFFFFFFFu; sh.cam_k0 = 0; sh.n_cam_dead = 0; }
-    if (USE_BVH) load_hot_nodes(sc, sh);
-    uint32_t waves = blockDim.x >> 6;
-    wg_sync(waves);
-    for (uint32_t parity = 0;; parity ^= 1u) {
-      // top-up: new camera paths behind the continuing ones, whole 64-sample groups while they fit.  IMPLICIT (kernels with
-      // the packet stage): nothing is written - positions [n0, n0 + 64 * ngen) simply ARE the samples of groups k0 ... of the
-      // workgroup's sequence; the packet stage builds their rays and shade rebuilds the paths that hit (camera_ray).
-      const uint32_t n0 = uni(sh.n_ray[parity]);
-      const uint32_t ngen = min(groups_left, (st.pool - n0) >> 6);
-      const uint32_t k0 = k_next;
-      if (ngen != 0) {
-        if (!IMPLICIT) {
-          rp.gen_begin();
-          stage_gen_camera_call<NT>(ka_lo, ka_hi, g, sh_lds, parity, n0, k_next, ngen, waves);
-          wg_sync(waves);
-          rp.gen_end(waves);
-        }
-        k_next += ngen;
-        groups_left -= ngen;
-      }
-      const uint32_t n = IMPLICIT ? n0 + 64u * ngen : n0 + uni(sh.n_gen), ns = uni(sh.n_shadow);
-      // next-event samples of the previous round's shade that the light-shaft grid answered (intersectScene(shadowRay) == false
-      // without a walk): shadow rays of the statistics all the same
-      { const uint32_t nd = uni(sh.n_direct); total_shadow += nd; total_unocc += nd; total_direct += nd; }
-      if (n + ns == 0) {
-        if (groups_left == 0) break;
-        // every sample of the new groups lay outside its block: next groups.  The other parity's path count is the one the
-        // round before last left behind (only a round that reaches the reset below clears it): it must not be found again.
-        if (threadIdx.x == 0) { sh.n_ray[parity ^ 1u] = 0; sh.n_direct = 0; }   // (n_direct: counted above, by thread 0, whose totals are the ones published)
-        wg_sync(waves);
-        continue;
-      }
-      // Tail of the workgroup: one wave can hold every ray of a round and the counts never grow again.
-      if (waves > 1u && groups_left == 0 && n + ns <= HJ_TAIL1) {
-        wg_sync(waves);                      // (everyone has read the counts)
-        if (threadIdx.x >= 64u) return;
-        waves = 1u;
-      }
-      rp.round_begin(n + ns);
-      wg_sync(waves);                        // everyone has read the counts before they are reset
-      if (threadIdx.x == 0) {
-        sh.head = 0; sh.head_cam = 0; sh.n_ray[parity ^ 1u] = 0; sh.n_gen = 0; sh.n_shadow = 0; sh.n_unocc = 0; sh.n_direct = 0;
-        sh.cam_first = (IMPLICIT && ngen != 0) ? n0 : 0xFFFFFFFFu; sh.cam_k0 = k0; sh.n_cam_dead = 0;
-      }
-      if (threadIdx.x < kNumTags) sh.cnt_hit[threadIdx.x] = 0;
-      wg_sync(waves);
-      rp.walk_begin();
-      // the round's new camera rays are the LAST entries of the closest-hit queue: they are walked as packets of 64
-      // (stage_camera_packets: one group of a block row each), the merged walk takes the continuing paths and the shadow rays
-      uint32_t cam = 0;
-      if (IMPLICIT && ngen != 0) {
-        cam = 64u * ngen;
-        stage_camera_packets_call<NT>(ka_lo, ka_hi, g, parity, n0, ngen, k0, sh_lds);
-      }
-      stage_trace_merged<USE_BVH, PAIRS, NT>(st, sc, g, parity, n - cam, ns, sh);
-      rp.walk_end(waves);
-      compact_hits_call<NT, 4u>(ka_lo, ka_hi, g, n, sh_lds, waves);
-      wg_sync(waves);
-      rp.compact_end();
-      if (n != 0) stage_shade_call<NT>(ka_lo, ka_hi, g, parity, max_bounces, rr_start, sh_lds, waves);
-      total_closest += n - uni(sh.n_cam_dead);   // (positions of ragged blocks' groups that hold no sample are not rays)
-      total_shadow += ns;
-      for (uint32_t k = 0; k < kNumTags; k++) total_hits += uni(sh.cnt_hit[k]);
-      total_unocc += uni(sh.n_unocc);
-      wg_sync(waves);
-      rp.round_end(waves);
-    }
-  }
-  if (threadIdx.x == 0) {
-    st.acc_closest[g] = total_closest;
-    st.acc_shadow[g] = total_shadow;
-    st.acc_hits[g] = total_hits;
-    st.acc_unoccluded[g] = total_unocc;
-    st.acc_direct[g] = total_direct;
-  }
-}
+// The kernel's text is hj_path_kernel.h, instantiated twice: k_path_wavefront, and k_path_wavefront_env for a scene with an
+// environment (ENV: a miss bin in the compaction, environment light in shade).  Two kernels of one text rather than a fourth template
+// flag, so that the first keeps its name and its code.
+#define HJ_PATH_KERNEL k_path_wavefront
+#define HJ_PATH_ENV false
+#include "hj_path_kernel.h"
+#undef HJ_PATH_KERNEL
+#undef HJ_PATH_ENV
+#define HJ_PATH_KERNEL k_path_wavefront_env
+#define HJ_PATH_ENV true
+#include "hj_path_kernel.h"
+#undef HJ_PATH_KERNEL
+#undef HJ_PATH_ENV
 
 // ---- split-kernel path (HJ_RENDER_SPLIT_KERNELS): the same stage functions, one launch per stage per bounce, for
 // per-stage timing and counters.  No regeneration: the pool holds every sample of the workgroup (api/render.hip sizes
@@ -171,9 +92,10 @@ __global__ __launch_bounds__(kBlockThreads) void k_gen_camera(BatchState st, Dev
   }
 }
 
-template <bool USE_BVH>
-__global__ __launch_bounds__(kBlockThreads) void k_trace_closest(BatchState st, DeviceScene sc, uint32_t parity) {
-  __shared__ WgShared sh;
+// ENV: st.cnt_hit holds kNumTags + 1 words per workgroup, the miss bin last.
+template <bool USE_BVH, bool ENV>
+HJ_DEV void trace_closest(const BatchState& st, const DeviceScene& sc, uint32_t parity) {
+  __shared__ std::conditional_t<ENV, WgSharedEnv, WgShared> sh;
   const uint32_t g = blockIdx.x;
   const uint32_t n = st.cnt_ray[parity][g];
   if (threadIdx.x == 0) { sh.head = 0; sh.n_unocc = 0; }
@@ -181,15 +103,26 @@ __global__ __launch_bounds__(kBlockThreads) void k_trace_closest(BatchState st, 
   if (USE_BVH && n != 0) load_hot_nodes(sc, sh);
   __syncthreads();
   stage_trace_merged<USE_BVH, true, false>(st, sc, g, parity, n, 0, sh);
-  compact_hits_by_tag<false, 4u>(st, sc, g, n, sh, blockDim.x >> 6);
+  compact_hits_by_tag<false, 4u, ENV>(st, sc, g, n, sh, blockDim.x >> 6);
   __syncthreads();
-  if (threadIdx.x < kNumTags) st.cnt_hit[g * kNumTags + threadIdx.x] = sh.cnt_hit[threadIdx.x];
+  constexpr uint32_t kBins = kNumTags + (ENV ? 1u : 0u);
+  if (threadIdx.x < kNumTags) st.cnt_hit[g * kBins + threadIdx.x] = sh.cnt_hit[threadIdx.x];
+  if (ENV && threadIdx.x == kMissBin) st.cnt_hit[g * kBins + kMissBin] = static_cast<WgSharedEnv&>(sh).cnt_miss;
   if (threadIdx.x == 0) {
     st.acc_closest[g] += n;
     uint32_t hits = 0;
     for (uint32_t k = 0; k < kNumTags; k++) hits += sh.cnt_hit[k];
     st.acc_hits[g] += hits;
   }
+}
+
+template <bool USE_BVH>
+__global__ __launch_bounds__(kBlockThreads) void k_trace_closest(BatchState st, DeviceScene sc, uint32_t parity) {
+  trace_closest<USE_BVH, false>(st, sc, parity);
+}
+template <bool USE_BVH>
+__global__ __launch_bounds__(kBlockThreads) void k_trace_closest_env(BatchState st, DeviceScene sc, uint32_t parity) {
+  trace_closest<USE_BVH, true>(st, sc, parity);
 }
 
 template <bool USE_BVH>
@@ -205,14 +138,16 @@ __global__ __launch_bounds__(kBlockThreads) void k_trace_shadow(BatchState st, D
   if (threadIdx.x == 0) st.acc_unoccluded[g] += sh.n_unocc;
 }
 
-__global__ __launch_bounds__(kBlockThreads) void k_shade(BatchState st, DeviceScene sc, uint32_t parity,
-                                                         uint32_t max_bounces, uint32_t rr_start) {
-  __shared__ WgShared sh;
+template <bool ENV>
+HJ_DEV void shade(const BatchState& st, const DeviceScene& sc, uint32_t parity, uint32_t max_bounces, uint32_t rr_start) {
+  __shared__ std::conditional_t<ENV, WgSharedEnv, WgShared> sh;
   const uint32_t g = blockIdx.x;
+  constexpr uint32_t kBins = kNumTags + (ENV ? 1u : 0u);
   if (threadIdx.x == 0) { sh.n_ray[parity ^ 1u] = 0; sh.n_shadow = 0; sh.n_direct = 0; sh.cam_first = 0xFFFFFFFFu; sh.cam_k0 = 0; }   // (every camera path has records here)
-  if (threadIdx.x < kNumTags) sh.cnt_hit[threadIdx.x] = st.cnt_hit[g * kNumTags + threadIdx.x];
+  if (threadIdx.x < kNumTags) sh.cnt_hit[threadIdx.x] = st.cnt_hit[g * kBins + threadIdx.x];
+  if (ENV && threadIdx.x == kMissBin) static_cast<WgSharedEnv&>(sh).cnt_miss = st.cnt_hit[g * kBins + kMissBin];
   __syncthreads();
-  stage_shade<false>(st, sc, g, parity, max_bounces, rr_start, sh, blockDim.x >> 6);
+  stage_shade<false, ENV>(st, sc, g, parity, max_bounces, rr_start, sh, blockDim.x >> 6);
   __syncthreads();
   if (threadIdx.x == 0) {
     st.cnt_ray[parity ^ 1u][g] = sh.n_ray[parity ^ 1u];
@@ -221,6 +156,15 @@ __global__ __launch_bounds__(kBlockThreads) void k_shade(BatchState st, DeviceSc
     st.acc_unoccluded[g] += sh.n_direct;
     st.acc_direct[g] += sh.n_direct;
   }
+}
+
+__global__ __launch_bounds__(kBlockThreads) void k_shade(BatchState st, DeviceScene sc, uint32_t parity,
+                                                         uint32_t max_bounces, uint32_t rr_start) {
+  shade<false>(st, sc, parity, max_bounces, rr_start);
+}
+__global__ __launch_bounds__(kBlockThreads) void k_shade_env(BatchState st, DeviceScene sc, uint32_t parity,
+                                                             uint32_t max_bounces, uint32_t rr_start) {
+  shade<true>(st, sc, parity, max_bounces, rr_start);
 }
 
 // Probe kernel behind hj_debug_trace: arbitrary rays -> raw hit records.

@@ -4,6 +4,7 @@
 #include "hj_intersect.h"
 #include "hj_light_grid_const.h"
 #include "hj_texture.h"
+#include "hj_env.h"
 
 #pragma clang fp contract(off)
 
@@ -52,10 +53,28 @@ struct SRec { v3 p, n; float pdf; };
 HJ_DEV v3 ld3(const float* p) { return V(p[0], p[1], p[2]); }
 
 // reference shader/scene.glsl:44-89 + shapes/*: sample*.  Always 3 draws.
-// `e` = the emitter that was sampled.
+// `e` = the emitter that was sampled.  ENV (environment instantiations): the first draw picks the environment with probability
+// env_p (kEnvEmitter, shadow ray to infinity: hj_env.h env_sample with the same two further draws); otherwise it is remapped to
+// [0, 1) and an area emitter is picked as upstream, its probability scaled by 1 - env_p (both exact no-ops for env_p == 0).
+template <bool ENV = false>
 HJ_DEV v3 sample_emitter(const DeviceScene& sc, v3 ref, uint32_t& rng, v3& sh_dir, float& sh_tmax, uint32_t& e) {
   float xi = rng_float(rng);
   e = 0;
+  float keep = 1.0f;
+  if (ENV) {
+    const float pe = sc.env_p;
+    if (pe == 1.0f || xi < pe) {
+      const uint32_t a = rng_uint(rng), b = rng_uint(rng);
+      float pdf;
+      uint32_t cell;
+      sh_dir = env_sample(sc, xi / pe, a, b, pdf, cell);
+      sh_tmax = kInf;
+      e = kEnvEmitter;
+      return divs(env_radiance(sc, sh_dir), pe * pdf);
+    }
+    xi = (xi - pe) / (1.0f - pe);
+    keep = 1.0f - pe;
+  }
   if (sc.num_emitters == 0) {   // reference reads emitters[0] out of bounds; defined here as "no light"
     rng_uint(rng); rng_uint(rng);
     sh_dir = V(0, 0, 0); sh_tmax = 0.0f;
@@ -69,7 +88,7 @@ HJ_DEV v3 sample_emitter(const DeviceScene& sc, v3 ref, uint32_t& rng, v3& sh_di
   // -> material: the values are the ones those arrays hold, the chain of dependent fetches is gone
   const float4* __restrict__ er = sc.emit_rec + (size_t)kEmitRecF4 * e;
   const float4 r0 = er[0], r1 = er[1], r2 = er[2], r3 = er[3];
-  const float em_pdf = r0.x;
+  const float em_pdf = ENV ? r0.x * keep : r0.x;
   const uint32_t kind = __float_as_uint(r0.y);
   const v3 power = V(r1.w, r2.w, r3.w);
   SRec sr;

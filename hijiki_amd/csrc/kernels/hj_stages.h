@@ -40,6 +40,11 @@ struct WgShared {                 // LDS of a path workgroup (16.5 KB)
   float4 rt[3 * kBlockThreads];
 #endif
 };
+// ... of an environment instantiation: the miss bin's counters behind (the other kernels keep their LDS size)
+struct WgSharedEnv : WgShared {
+  uint32_t cnt_miss;              // misses of this round's closest-hit rays
+  uint32_t wcnt_miss[kBlockThreads / 64];
+};
 
 HJ_DEV void load_hot_nodes(const DeviceScene& sc, WgShared& sh) {
   for (uint32_t i = threadIdx.x; i < 2 * sc.num_hot; i += blockDim.x) sh.nodes[i] = sc.nodes[i];
@@ -349,10 +354,15 @@ HJ_DEV void stage_camera_packets(const BatchState& st, const DeviceScene& sc, ui
 // The bin of a material tag: its own, except that textured diffuse hits share the checkerboard's (both are "diffuse with a colour
 // from (u, v)"; the bin count and the LDS counters stay as they were).  stage_shade tells the two apart by the material word.
 HJ_DEV uint32_t hit_bin(uint32_t tag) { return tag == HJ_MAT_DIFFUSE_TEXTURED && kNumTags == 5 ? (uint32_t)HJ_MAT_DIFFUSECBOARD : tag; }
+// ENV (environment instantiations): the misses are not over - they get a bin of their own behind the material bins (q_hit bin
+// kMissBin, counted in sh.cnt_miss), which stage_shade lights from the environment.
+constexpr uint32_t kMissBin = kNumTags;
 
-template <bool NT, uint32_t R>
+template <bool NT, uint32_t R, bool ENV = false>
 HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uint32_t g, uint32_t n, WgShared& sh,
                                 uint32_t waves) {
+  constexpr uint32_t kBins = kNumTags + (ENV ? 1u : 0u);
+  auto wcnt = [&](uint32_t w, uint32_t k) -> uint32_t& { return k < kNumTags ? sh.wcnt[w][k] : static_cast<WgSharedEnv&>(sh).wcnt_miss[w]; };
   const uint32_t G = st.num_wg;
   const uint32_t lane = threadIdx.x & 63u;
   const float4* __restrict__ hit = st.hit + g * st.pool;
@@ -372,7 +382,7 @@ HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uin
       id[j] = (row + j < r1 && i < n) ? __float_as_int(ldp<NT>(hit, i).y) : -1;
     }
 #pragma unroll
-    for (uint32_t j = 0; j < R; j++) tag[j] = id[j] >= 0 ? hit_bin(sc.materials[id[j]] >> HJ_MATERIAL_TAG_SHIFT) : 0xFFu;
+    for (uint32_t j = 0; j < R; j++) tag[j] = id[j] >= 0 ? hit_bin(sc.materials[id[j]] >> HJ_MATERIAL_TAG_SHIFT) : (ENV && (row + j < r1 && (row + j) * 64u + lane < n) ? kMissBin : 0xFFu);
   };
   // second pass: the tags the first pass left in hit_tag (a byte per ray: 64 B per row instead of 1 KB + the material gather)
   uint8_t* __restrict__ htag = st.hit_tag + g * st.pool;
@@ -383,9 +393,9 @@ HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uin
       tag[j] = (row + j < r1 && i < n) ? (uint32_t)htag[i] : 0xFFu;
     }
   };
-  uint32_t cnt[kNumTags];
+  uint32_t cnt[kBins];
 #pragma unroll
-  for (uint32_t k = 0; k < kNumTags; k++) cnt[k] = 0;
+  for (uint32_t k = 0; k < kBins; k++) cnt[k] = 0;
 #pragma unroll 1
   for (uint32_t row = r0; row < r1; row += R) {
     uint32_t tag[R];
@@ -395,19 +405,19 @@ HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uin
       const uint32_t i = (row + j) * 64u + lane;
       if (row + j < r1 && i < n) htag[i] = (uint8_t)tag[j];
 #pragma unroll
-      for (uint32_t k = 0; k < kNumTags; k++) cnt[k] += (uint32_t)__popcll(__ballot(tag[j] == k));
+      for (uint32_t k = 0; k < kBins; k++) cnt[k] += (uint32_t)__popcll(__ballot(tag[j] == k));
     }
   }
   if (lane == 0) {
 #pragma unroll
-    for (uint32_t k = 0; k < kNumTags; k++) sh.wcnt[wave][k] = cnt[k];
+    for (uint32_t k = 0; k < kBins; k++) wcnt(wave, k) = cnt[k];
   }
   wg_sync(waves);
-  uint32_t base[kNumTags];
+  uint32_t base[kBins];
 #pragma unroll
-  for (uint32_t k = 0; k < kNumTags; k++) {
+  for (uint32_t k = 0; k < kBins; k++) {
     base[k] = 0;
-    for (uint32_t w = 0; w < wave; w++) base[k] += uni(sh.wcnt[w][k]);
+    for (uint32_t w = 0; w < wave; w++) base[k] += uni(wcnt(w, k));
   }
 #pragma unroll 1
   for (uint32_t row = r0; row < r1; row += R) {
@@ -417,7 +427,7 @@ HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uin
     for (uint32_t j = 0; j < R; j++) {
       const uint32_t i = (row + j) * 64u + lane;
 #pragma unroll
-      for (uint32_t k = 0; k < kNumTags; k++) {
+      for (uint32_t k = 0; k < kBins; k++) {
         const unsigned long long mask = __ballot(tag[j] == k);
         if (tag[j] == k) st.q_hit[((size_t)k * G + g) * st.pool + base[k] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;
         base[k] += (uint32_t)__popcll(mask);
@@ -429,6 +439,12 @@ HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uin
     for (uint32_t w = 0; w < waves; w++) total += sh.wcnt[w][threadIdx.x];
     sh.cnt_hit[threadIdx.x] = total;
   }
+  if (ENV && threadIdx.x == kMissBin) {
+    WgSharedEnv& she = static_cast<WgSharedEnv&>(sh);
+    uint32_t total = 0;
+    for (uint32_t w = 0; w < waves; w++) total += she.wcnt_miss[w];
+    she.cnt_miss = total;
+  }
 }
 
 // reference shader/scene.glsl:160-175 (populate), render.glsl:102-144, material.glsl:18-91.
@@ -436,6 +452,9 @@ HJ_DEV void compact_hits_by_tag(const BatchState& st, const DeviceScene& sc, uin
 // next free position of the arrays of parity ^ 1 (sh.n_ray[parity ^ 1]), NEE shadow rays become shadow records
 // (sh.n_shadow).
 template <bool NT>
+HJ_DEV void shade_misses(const BatchState& st, const DeviceScene& sc, uint32_t g, uint32_t parity, WgShared& sh, uint32_t waves);
+
+template <bool NT, bool ENV = false>
 HJ_DEV void stage_shade(const BatchState& st, const DeviceScene& sc, uint32_t g, uint32_t parity, uint32_t max_bounces,
                         uint32_t rr_start, WgShared& sh, uint32_t waves) {
   const uint32_t G = st.num_wg;
@@ -517,7 +536,7 @@ HJ_DEV void stage_shade(const BatchState& st, const DeviceScene& sc, uint32_t g,
                            : (mat >> HJ_MATERIAL_TAG_SHIFT) == HJ_MAT_DIFFUSE_TEXTURED ? texture_rgb(sc.textures, midx, its.u, its.v)
                                                                                         : checkerboard(sc, midx, its.u, its.v);
           uint32_t em = 0;
-          const v3 imp = sample_emitter(sc, its.p, rng, sdir, stmax, em);                  // render.glsl:117-126
+          const v3 imp = sample_emitter<ENV>(sc, its.p, rng, sdir, stmax, em);                  // render.glsl:117-126
           if (len3(imp) > kEps && dot3(sdir, its.n) > 0.0f) {
             const float cs = dot3(its.n, sdir);
             const v3 f = (color * cs) * kInvPi;                                            // material.glsl:18-30
@@ -609,6 +628,52 @@ HJ_DEV void stage_shade(const BatchState& st, const DeviceScene& sc, uint32_t g,
     }
     }
   }
+  if (ENV) shade_misses<NT>(st, sc, g, parity, sh, waves);
+}
+
+// The miss bin of an environment instantiation (sh is a WgSharedEnv) (render.glsl:94-96 ends these paths): a path whose ray left the scene adds T * Le(d)
+// when wasDiscrete holds (a camera ray, or after a mirror or glass bounce: the rule of emissive hits, render.glsl:114), and 0 in
+// every channel where its current extinction is non-zero (the exp(-ext * inf) of a ray to infinity, without forming 0 * inf).  Then
+// the path is over.  No normal or depth feature is written.
+template <bool NT>
+HJ_DEV void shade_misses(const BatchState& st, const DeviceScene& sc, uint32_t g, uint32_t parity, WgShared& sh, uint32_t waves) {
+  const uint32_t G = st.num_wg;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t seg = g * st.pool;
+  const uint32_t cam_first = uni(sh.cam_first), cam_k0 = uni(sh.cam_k0);
+  const uint32_t n = uni(static_cast<WgSharedEnv&>(sh).cnt_miss);
+  const uint32_t* __restrict__ q = st.q_hit + ((size_t)kMissBin * G + g) * st.pool;
+  for (uint32_t i = wave * 64u + lane; i < n; i += waves * 64u) {
+    const uint32_t qpos = q[i];
+    const uint32_t slot = seg + qpos;
+    v3 rd, T, ext = V(0, 0, 0);
+    uint32_t smp, flags;
+    if (qpos >= cam_first) {                 // an IMPLICIT camera path (stage_shade)
+      const uint32_t c = qpos - cam_first;
+      smp = group_sample(wg_group(st, g, cam_k0 + (c >> 6)), c & 63u, sc.group_tile);
+      uint32_t rng = 0;
+      rd = V(0, 0, 0);
+      (void)camera_ray(st, sc, smp, rng, rd);
+      T = V(1.f, 1.f, 1.f);
+      flags = 1u;
+    } else {
+      const float4 ro4 = ldp<NT>(st.ray_o[parity], slot), rd4 = ldp<NT>(st.ray_d[parity], slot);
+      const float4 th4 = ldp<NT>(st.thr[parity], slot);
+      rd = xyz(rd4);
+      T = xyz(th4);
+      flags = __float_as_uint(th4.w);
+      smp = __float_as_uint(ro4.w) & ~kCameraFlag;
+      if (sc.has_extinction) ext = xyz(ldp<NT>(st.ext[parity], slot));
+    }
+    if ((flags & 1u) != 0u) {
+      const v3 le = env_radiance(sc, rd);
+      float4 s = ldp<NT>(st.smp_rgb, smp);
+      s.x += ext.x != 0.0f ? 0.0f : T.x * le.x;
+      s.y += ext.y != 0.0f ? 0.0f : T.y * le.y;
+      s.z += ext.z != 0.0f ? 0.0f : T.z * le.z;
+      stp<NT>(st.smp_rgb, smp, s);
+    }
+  }
 }
 
 // The stages as CALLED functions: shade needs about twice the registers of the walk, and inlined into
@@ -633,6 +698,18 @@ __device__ __attribute__((noinline)) void stage_shade_call(uint32_t ka_lo, uint3
   stage_shade<NT>(st, sc, uni(g), uni(parity), uni(max_bounces), uni(rr_start), sh, uni(waves));
 }
 
+// ... of an environment instantiation (the miss bin, environment next-event samples)
+template <bool NT>
+__device__ __attribute__((noinline)) void stage_shade_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t parity, uint32_t max_bounces,
+                                                                uint32_t rr_start, uint32_t sh_lds, uint32_t waves) {
+  typedef const __attribute__((address_space(4))) char* KArg;
+  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
+  const BatchState& st = *(const BatchState*)ka;
+  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
+  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
+  stage_shade<NT, true>(st, sc, uni(g), uni(parity), uni(max_bounces), uni(rr_start), sh, uni(waves));
+}
+
 template <bool NT>
 __device__ __attribute__((noinline)) void stage_gen_camera_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t sh_lds, uint32_t parity,
                                                                  uint32_t n0, uint32_t k0, uint32_t ngen, uint32_t waves) {
@@ -652,9 +729,40 @@ __device__ __attribute__((noinline)) void compact_hits_call(uint32_t ka_lo, uint
   WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
   compact_hits_by_tag<NT, R>(st, sc, uni(g), uni(n), sh, uni(waves));
 }
+template <bool NT, uint32_t R>
+__device__ __attribute__((noinline)) void compact_hits_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t n, uint32_t sh_lds, uint32_t waves) {
+  typedef const __attribute__((address_space(4))) char* KArg;
+  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
+  const BatchState& st = *(const BatchState*)ka;
+  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
+  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
+  compact_hits_by_tag<NT, R, true>(st, sc, uni(g), uni(n), sh, uni(waves));
+}
 
 template <bool NT>
 __device__ __attribute__((noinline)) void stage_camera_packets_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t parity, uint32_t first,
+                                                                     uint32_t chunks, uint32_t k0, uint32_t sh_lds) {
+  typedef const __attribute__((address_space(4))) char* KArg;
+  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
+  const BatchState& st = *(const BatchState*)ka;
+  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
+  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
+  stage_camera_packets<NT>(st, sc, uni(g), uni(parity), uni(first), uni(chunks), uni(k0), sh);
+}
+// Copies of the two wrappers above for the environment kernels: a called function shared by two kernels is compiled for what both of
+// them need, and the other kernels' code would change with it.
+template <bool NT>
+__device__ __attribute__((noinline)) void stage_gen_camera_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t sh_lds, uint32_t parity,
+                                                                 uint32_t n0, uint32_t k0, uint32_t ngen, uint32_t waves) {
+  typedef const __attribute__((address_space(4))) char* KArg;
+  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
+  const BatchState& st = *(const BatchState*)ka;
+  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
+  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
+  stage_gen_camera<NT>(st, sc, uni(g), sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves));
+}
+template <bool NT>
+__device__ __attribute__((noinline)) void stage_camera_packets_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t parity, uint32_t first,
                                                                      uint32_t chunks, uint32_t k0, uint32_t sh_lds) {
   typedef const __attribute__((address_space(4))) char* KArg;
   KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));

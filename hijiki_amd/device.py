@@ -23,7 +23,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_build_bvh_device", "hj_render_frame_async", "hj_sync", "hj_set_progress_callback", "hj_device_count",
            "hj_comm_create", "hj_comm_destroy", "hj_comm_reduce_framebuffers", "hj_reserve", "hj_framebuffer_bind",
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
-           "hj_scene_upload_textured", "hj_debug_texture_lookup")
+           "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
+           "hj_debug_env_distribution")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -47,6 +48,12 @@ def lib():
         L.hj_scene_upload.argtypes = [vp, C.POINTER(abi.SceneDesc)]
         L.hj_scene_upload_textured.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.TextureSet)]
         L.hj_debug_texture_lookup.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float)]
+        L.hj_scene_upload_env.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.TextureSet), C.POINTER(abi.Environment)]
+        L.hj_debug_env_lookup.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float)]
+        L.hj_debug_env_sample.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_float)]
+        L.hj_debug_env_distribution.argtypes = [C.POINTER(abi.TextureSet), C.POINTER(abi.Environment), C.POINTER(C.c_float),
+                                                C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                                C.POINTER(C.c_double)]
         L.hj_framebuffer_create.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
         L.hj_framebuffer_clear.argtypes = [vp]
         L.hj_framebuffer_device_ptr.argtypes = [vp]
@@ -92,6 +99,23 @@ def reduce_framebuffers(renderers, root=0):
     rc = lib().hj_reduce_framebuffers(arr, len(renderers), root)
     if rc != abi.HJ_OK:
         raise abi.HijikiError(rc, lib().hj_last_error(renderers[root]._h).decode())
+
+
+def env_distribution(textures, env):
+    """hj_debug_env_distribution (host code, no GPU): the environment's sampling distribution as hj_scene_upload_env builds it ->
+    dict of (H, W) arrays prob, pdf, alias_prob, alias and the float weight_sum (0: a black environment).  Raises on a refusal."""
+    t = textures.textures[env.texture]
+    shape = (t.height, t.width)
+    out = {k: np.zeros(shape, np.float32) for k in ("prob", "pdf", "alias_prob")}
+    out["alias"] = np.zeros(shape, np.uint32)
+    total = C.c_double()
+    f = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    rc = lib().hj_debug_env_distribution(C.byref(textures), C.byref(env), f(out["prob"]), f(out["pdf"]), f(out["alias_prob"]),
+                                         out["alias"].ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(total))
+    if rc != abi.HJ_OK:
+        raise abi.HijikiError(rc, "hj_debug_env_distribution refused the environment")
+    out["weight_sum"] = total.value
+    return out
 
 
 def device_count():
@@ -163,9 +187,13 @@ class Renderer:
         if rc != abi.HJ_OK:
             raise abi.HijikiError(rc, lib().hj_last_error(self._h).decode())
 
-    def upload_scene(self, compiled, device_tree=False, textures=None):
+    def upload_scene(self, compiled, device_tree=False, textures=None, environment=None):
         """hj_scene_upload.  device_tree: scene->bvh = NULL - the tree `build_bvh(compiled, keep_on_device=True)` left on the device.
-        A compiled scene with image textures goes up with them (hj_scene_upload_textured); `textures` (an abi.TextureSet) overrides."""
+        A compiled scene with image textures goes up with them (hj_scene_upload_textured); `textures` (an abi.TextureSet) overrides.
+        A compiled scene with an environment (host.Scene.set_environment) goes up with it (hj_scene_upload_env); `environment` (an
+        abi.Environment) overrides."""
+        if environment is None:
+            environment = getattr(compiled, "environment", None)
         desc = compiled.desc if hasattr(compiled, "desc") else compiled
         if textures is None and hasattr(compiled, "texture_set"):
             t = compiled.texture_set
@@ -176,10 +204,29 @@ class Renderer:
             d2.bvh = None
             d2.num_bvh_nodes = 0
             desc = d2
-        if textures is not None:
+        if environment is not None:
+            self._check(lib().hj_scene_upload_env(self._h, C.byref(desc), C.byref(textures) if textures is not None else None,
+                                                  C.byref(environment)))
+        elif textures is not None:
             self._check(lib().hj_scene_upload_textured(self._h, C.byref(desc), C.byref(textures)))
         else:
             self._check(lib().hj_scene_upload(self._h, C.byref(desc)))
+
+    def env_lookup(self, dirs):
+        """hj_debug_env_lookup: (n, 3) directions -> (n, 3) float32 radiance of the uploaded environment."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        rgb = np.zeros((len(d), 3), np.float32)
+        self._check(lib().hj_debug_env_lookup(self._h, d.ctypes.data_as(C.POINTER(C.c_float)), len(d),
+                                              rgb.ctypes.data_as(C.POINTER(C.c_float))))
+        return rgb
+
+    def env_sample(self, rng_states):
+        """hj_debug_env_sample: n uint32 RNG states -> (n, 8) float32: direction xyz, pdf, texel index, Le / pdf rgb."""
+        s = np.ascontiguousarray(rng_states, np.uint32).reshape(-1)
+        out = np.zeros((len(s), 8), np.float32)
+        self._check(lib().hj_debug_env_sample(self._h, s.ctypes.data_as(C.POINTER(C.c_uint32)), len(s),
+                                              out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
 
     def create_framebuffer(self, width, height, external_device_ptr=None):
         self._check(lib().hj_framebuffer_create(self._h, width, height, external_device_ptr))

@@ -102,6 +102,7 @@ class Scene:
 
     def __init__(self, _handle=None):
         self._h = C.c_void_p()
+        self._env = None                             # (texture, scale, select_prob): set_environment
         self._destroy = lib().hjh_scene_destroy      # bound now: module globals may be gone at interpreter exit
         if _handle is not None:
             self._h = _handle
@@ -169,6 +170,22 @@ class Scene:
     def add_diffuse_textured(self, texture):
         return _index(lib().hjh_scene_add_diffuse_textured(self._h, int(texture)))
 
+    # environment lighting (no counterpart upstream)
+    def set_environment(self, texture, scale=(1.0, 1.0, 1.0), select_prob=None):
+        """Light the scene with texture `texture` (add_texture / add_texture_file) as a lat-long environment, radiance scale * texel.
+        select_prob: probability that next-event estimation samples the environment; None: 1 without emitters, 0 for a black
+        environment, 0.5 otherwise (decided at compile)."""
+        sc = tuple(float(v) for v in (scale if np.ndim(scale) else (scale,) * 3))
+        if len(sc) != 3:
+            raise ValueError("scale: one value or three")
+        self._env = (int(texture), sc, None if select_prob is None else float(select_prob))
+
+    def set_environment_file(self, path, scale=(1.0, 1.0, 1.0), select_prob=None, filter=abi.TEX_BILINEAR):
+        """PFM (linear) or binary PPM P6 (sRGB-decoded) as the environment -> its texture index."""
+        t = self.add_texture_file(path, filter)
+        self.set_environment(t, scale, select_prob)
+        return t
+
     def add_vertices(self, pos, normal, uv=None):
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
         normal = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
@@ -204,7 +221,28 @@ class Scene:
         `device.Renderer.build_bvh` to build it on the device."""
         h = C.c_void_p()
         _check((lib().hjh_scene_compile if with_tree else lib().hjh_scene_compile_shapes)(self._h, C.byref(h)))
-        return CompiledScene(h)
+        cs = CompiledScene(h)
+        if self._env is not None:
+            cs.environment = environment(cs, *self._env)
+        return cs
+
+
+def environment(compiled, texture, scale=(1.0, 1.0, 1.0), select_prob=None):
+    """The abi.Environment hj_scene_upload_env takes for `compiled`; select_prob None: the default (Scene.set_environment)."""
+    env = abi.Environment()
+    env.texture = int(texture)
+    for k in range(3):
+        env.scale[k] = float(scale[k])
+    if select_prob is None:
+        if compiled.desc.num_emitters == 0:
+            select_prob = 1.0
+        else:
+            from . import device                  # (host code of the device library: no GPU needed)
+            if texture >= compiled.texture_set.num_textures:
+                raise ValueError(f"environment: texture {texture} of {compiled.texture_set.num_textures}")
+            select_prob = 0.5 if device.env_distribution(compiled.texture_set, env)["weight_sum"] > 0.0 else 0.0
+    env.select_prob = float(select_prob)
+    return env
 
 
 def _as_np(ptr, count, dtype, cols):
@@ -217,6 +255,8 @@ def _as_np(ptr, count, dtype, cols):
 
 class CompiledScene:
     """`struct CompiledScene` (src/main.rs:376-397); `.desc` is the hj_scene_desc the device library uploads."""
+
+    environment = None                               # abi.Environment, or None: no environment
 
     def __init__(self, handle):
         self._h = handle

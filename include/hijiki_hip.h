@@ -147,6 +147,12 @@ typedef struct hj_texture_set {
   const float*      texels;   size_t num_texels;
 } hj_texture_set;
 
+/* Environment lighting (no counterpart upstream; ABI 0.5): texture `texture` of the scene's hj_texture_set, read as a
+ * latitude-longitude map with +y up, lights every ray that leaves the scene.  Radiance from direction d = scale * the texture's
+ * colour at (u, v) of d (DESIGN.md "Environment lighting").  select_prob = the probability that next-event estimation at a diffuse
+ * hit samples the environment instead of an area emitter.  24 bytes. */
+typedef struct hj_environment { uint32_t texture; float scale[3]; float select_prob; uint32_t _reserved; } hj_environment;
+
 /* ImageBlock, src/main.rs:608-617 / shader/block.glsl:1-8.  40 bytes.
  * One per integrator+reconstruction dispatch pair in the reference
  * (src/main.rs:1322-1330). */
@@ -262,6 +268,12 @@ int hj_scene_upload(hj_context* ctx, const hj_scene_desc* scene);
  * before anything else happens, so a tree left by hj_build_bvh_device stays on the device); more than 2^32 texels, or a width or
  * height above 2^24: HJ_ERR_UNSUPPORTED.  The texels are copied to the device with the rest of the scene. */
 int hj_scene_upload_textured(hj_context* ctx, const hj_scene_desc* scene, const hj_texture_set* textures /* may be NULL */);
+/* hj_scene_upload_textured with an environment (ABI 0.5); env == NULL is hj_scene_upload_textured.  Checked before anything else
+ * happens, each HJ_ERR_INVALID: texture index out of range, a scale component negative or not finite, a non-finite texel of the
+ * environment, select_prob outside [0, 1], select_prob other than 1 with no emitters, select_prob > 0 when every cell of the
+ * sampling distribution weighs 0.  An environment of more than 2^28 texels: HJ_ERR_UNSUPPORTED.  The sampling distribution (an
+ * alias table over the texels) is built with the rest of the scene; an upload that fails keeps none of it. */
+int hj_scene_upload_env(hj_context* ctx, const hj_scene_desc* scene, const hj_texture_set* textures, const hj_environment* env);
 
 /* -------------------------------------------------------------- framebuffer */
 
@@ -435,6 +447,18 @@ int hj_debug_samples(hj_context* ctx, const hj_image_block* block, const hj_rend
  *   (uv = n x 2 floats, rgb = n x 3 floats), by the same device function.  No scene: HJ_ERR_STATE; texture out of range:
  *   HJ_ERR_INVALID. */
 int hj_debug_texture_lookup(hj_context* ctx, uint32_t texture, const float* uv, size_t n, float* rgb);
+/* hj_debug_env_lookup: the radiance the uploaded environment sends along n directions (dirs = n x 3 floats, any length; rgb =
+ *   n x 3 floats), by the device function misses and next-event samples use.  No environment: HJ_ERR_STATE.
+ * hj_debug_env_sample: one environment sample per RNG state (n uint32), drawn as next-event estimation draws it after picking the
+ *   environment (coin = rng_float, then two rng_uint): out = n x 8 floats = direction xyz (unit), pdf (solid angle, without the
+ *   selection probability), texel index (float), Le / pdf rgb.  No environment: HJ_ERR_STATE.
+ * hj_debug_env_distribution: the sampling distribution hj_scene_upload_env builds for `env` over `textures` (pure host code: no
+ *   context, no GPU), W x H entries in texel order (row 0 = top): cell probability P (may be NULL), pdf = P / solid angle (may be
+ *   NULL), alias-table threshold and alias cell (may be NULL).  weight_sum (may be NULL) = the sum of the cell weights; 0: black. */
+int hj_debug_env_lookup(hj_context* ctx, const float* dirs, size_t n, float* rgb);
+int hj_debug_env_sample(hj_context* ctx, const uint32_t* rng_states, size_t n, float* out);
+int hj_debug_env_distribution(const hj_texture_set* textures, const hj_environment* env, float* prob, float* pdf, float* alias_prob,
+                              uint32_t* alias, double* weight_sum);
 /* hj_debug_light_grid: the light-shaft visibility grid hj_scene_upload would build for `scene` (pure host code: no context,
  *   no GPU).  Returns the cells per axis (0: nothing can be proven for this scene).  bits (may be NULL) = res^3 bytes, x fastest:
  *   bit e of a cell set = every next-event shadow ray from a hit point in that cell to emitter e is unoccluded; the cell of a
