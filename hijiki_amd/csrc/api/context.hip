@@ -114,7 +114,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (5u << 8) | 0u; }   // 0.5.0: environment lighting (hj_scene_upload_env, hj_debug_env_*)
+uint32_t hj_version(void) { return (0u << 16) | (6u << 8) | 0u; }   // 0.6.0: hj_refit_bvh_device
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

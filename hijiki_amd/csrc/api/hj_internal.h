@@ -7,7 +7,7 @@
 //   api/render.hip        the launches of kernels/hj_kernels.h (the only unit that includes them), walk-statistics readers
 //   api/render_calls.hip  batch slots, render calls, hj_reserve, the pipeline, the worker thread, probes   (no kernels)
 //   api/comm.hip          RCCL (dlopen), hj_comm_*, hj_reduce_framebuffers
-//   api/lbvh_build.hip    hj_build_bvh_device: host half of kernels/hj_lbvh.h
+//   api/lbvh_build.hip    hj_build_bvh_device, hj_refit_bvh_device: host half of kernels/hj_lbvh.h
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
 //   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
 //   api/environment.hip   environment lighting: the checks and the alias table of hj_scene_upload_env, hj_debug_env_*
@@ -245,6 +245,17 @@ struct hj_context {
     bool valid = false;
     void release() { nodes.release(); spheres.release(); quads.release(); triangles.release(); vertices.release(); total = 0; valid = false; }
   } resident;
+
+  // hj_refit_bvh_device: the topology of the last refit that brought one - (shape_index, exit_index) per record, 8 bytes each -,
+  // kept for the refits that follow (scene->bvh == NULL).  Replaced by the next refit that brings a topology, freed with the context;
+  // builds and uploads neither read nor drop it.
+  struct KeptLinks {
+    hjapi::DevBuf links;
+    hjapi::DevBuf parent, arrived;               // derived from the links once: parent of every record, the climb's counters (all zero
+                                                 // between refits), 4 bytes per record each
+    size_t shapes = 0;                           // the links are 2 * shapes - 1 records
+    bool valid = false;
+  } refit_links;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment

@@ -51,6 +51,7 @@ struct Tuning {
   X(lbvh_sah, "HJ_LBVH_SAH", 1, 0, 1)                                                                                                   \
   X(lbvh_top_rotate, "HJ_LBVH_TOP_ROTATE", -1, -1, 64)     /* rotation passes over the host-built top: -1 by size */                    \
   X(lbvh_vote_paths, "HJ_LBVH_VOTE_PATHS", 60000, 0, 1 << 24) /* camera paths of the ray vote at the end of the build */                \
+  X(refit_tiled, "HJ_REFIT_TILED", 1, 0, 1)                /* hj_refit_bvh_device: 1 subtrees inside a run of records in LDS, 0 the plain climb */ \
   X(bvh_child_order, "HJ_BVH_CHILD_ORDER", 3, 0, 9)        /* static child order of the device build (3: fewer shapes first) */         \
   X(bvh_vote_shadow, "HJ_BVH_VOTE_SHADOW", kUnset, 0, 16)  /* a shadow ray's vote in quarters of a closest-hit ray's: 1 (4 on large trees) */
   // presence flags (debugging aids): set to anything = on

@@ -517,4 +517,136 @@ int hj_bvh_device_read(hj_context* ctx, hj_bvh_node* out_nodes, size_t capacity,
   return HJ_OK;
 }
 
+// The boxes of a tree recomputed for shapes that have moved (kernels/hj_lbvh.h, "REFIT"): the links stay, the leaves take the boxes
+// of their shapes as they are now, the inner nodes the union of their children's.  Stages, all on the context's stream with no
+// host synchronisation between them (one, for the verdict, when the links come from the host): links -> parents (+ validation),
+// the climb from the leaves, the cost's partial sums.
+int hj_refit_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* out_nodes, size_t capacity, size_t* out_num_nodes,
+                        double* out_cost) {
+  if (!ctx) return HJ_ERR_INVALID;
+  HJ_NOT_BUSY(ctx);
+  HJ_NOT_PIPELINED(ctx);
+  if (!s) return set_error(ctx, HJ_ERR_INVALID, "null argument");
+  const size_t n = s->num_spheres + s->num_quads + s->num_triangles;
+  if (n < 2) return set_error(ctx, HJ_ERR_INVALID, "scene needs at least 2 shapes (reference panics: root would be a leaf, src/main.rs:230)");
+  if (n >= hj::kInnerFlag / 4) return set_error(ctx, HJ_ERR_INVALID, "scene too large");
+  const size_t total = 2 * n - 1;
+  if (out_nodes && capacity < total) return set_error(ctx, HJ_ERR_INVALID, "node buffer holds %zu records, the tree has %zu", capacity, total);
+  if ((s->num_spheres && !s->spheres) || (s->num_quads && !s->quads) || (s->num_triangles && (!s->triangles || !s->vertices)))
+    return set_error(ctx, HJ_ERR_INVALID, "null shape array");
+  for (size_t i = 0; i < s->num_triangles; i++)
+    for (int k = 0; k < 3; k++)
+      if (s->triangles[i].v[k] >= s->num_vertices) return set_error(ctx, HJ_ERR_INVALID, "triangle %zu refers to unknown vertex", i);
+  hj_context::KeptLinks& kept = ctx->refit_links;
+  const bool from_host = s->bvh != nullptr;
+  if (from_host) {
+    if (s->num_bvh_nodes != total)
+      return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: the topology has %zu records, %zu shapes need %zu", s->num_bvh_nodes, n, total);
+  } else {
+    if (s->num_bvh_nodes != 0) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: scene->bvh is NULL but num_bvh_nodes is %zu", s->num_bvh_nodes);
+    if (!kept.valid) return set_error(ctx, HJ_ERR_STATE, "hj_refit_bvh_device: scene->bvh is NULL and no links are kept: the first refit brings a topology");
+    if (kept.shapes != n) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: the kept links are those of %zu shapes, the scene has %zu", kept.shapes, n);
+  }
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  const Tuning tn = ctx->tuning = Tuning::from_env();
+  StageClock clock{tn.lbvh_timing != 0, "hj_refit_bvh_device: %-28s %7.2f ms\n", ctx->stream};
+  clock.mark("argument checks");
+  DevBufs bufs(ctx);
+  hipStream_t st = ctx->stream;
+  const uint32_t N = (uint32_t)total;
+  const dim3 blk(256), grid((N + 255u) / 256u);
+  hj::lbvh::Refit r{};
+  r.N = N; r.n = (uint32_t)n;
+  if (from_host) {
+    // the links of the host's array (8 of its 32 bytes per record), checked on the device BEFORE anything of the context changes;
+    // the same kernel derives what the refits over these links reuse: parents, and counters that are zero between passes
+    std::vector<uint2> links(total);
+    for (size_t i = 0; i < total; i++) links[i] = make_uint2(s->bvh[i].shape_index, s->bvh[i].exit_index);
+    uint2* new_links = nullptr;
+    uint32_t* zeroed = nullptr;                              // nparents [N], seen [n], err [4]: one allocation
+    HJ_TRY(bufs.alloc(new_links, total));
+    HJ_TRY(bufs.alloc(r.parent, total));
+    HJ_TRY(bufs.alloc(r.arrived, total));
+    HJ_TRY(bufs.alloc(zeroed, total + n + 4));
+    r.links = new_links; r.nparents = zeroed; r.seen = zeroed + total; r.err = zeroed + total + n;
+    HJ_HIP(ctx, hipMemcpy(new_links, links.data(), sizeof(uint2) * total, hipMemcpyHostToDevice));
+    HJ_HIP(ctx, hipMemsetAsync(zeroed, 0, sizeof(uint32_t) * (total + n + 1), st));
+    HJ_HIP(ctx, hipMemsetAsync(r.err + 1, 0xFF, sizeof(uint32_t) * 3, st));
+    hipLaunchKernelGGL(hj::lbvh::k_rf_links<true>, grid, blk, 0, st, r);
+    hipLaunchKernelGGL(hj::lbvh::k_rf_check, grid, blk, 0, st, r);
+    HJ_HIP(ctx, hipStreamSynchronize(st));                   // (the verdict decides what follows)
+    HJ_HIP(ctx, hipGetLastError());
+    uint32_t err[4] = {0, 0, 0, 0};
+    HJ_HIP(ctx, hipMemcpy(err, r.err, sizeof err, hipMemcpyDeviceToHost));
+    if (err[0] & hj::lbvh::kRfNotATree) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: the links are not a pre-order skip-link tree");
+    if (err[0] & hj::lbvh::kRfShapeRange) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: a leaf holds shape %u, the scene has %zu", err[2], n);
+    if (err[0] & hj::lbvh::kRfShapeTwice) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: shape %u is in two leaves", err[3]);
+    if (err[0] & hj::lbvh::kRfShapeMissing) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: shape %u is in no leaf", err[1]);
+    clock.mark("links to the device, checks");
+    kept.links = bufs.take(new_links);                       // from here on these are the kept links, whatever happens below
+    kept.parent = bufs.take(r.parent); kept.arrived = bufs.take(r.arrived);
+    kept.shapes = n; kept.valid = kept.links.p != nullptr;
+  }
+  r.links = static_cast<const uint2*>(kept.links.p);
+  r.parent = static_cast<uint32_t*>(kept.parent.p); r.arrived = static_cast<uint32_t*>(kept.arrived.p);
+  ctx->resident.release();                                   // (a tree nobody took over: the refitted one replaces it)
+  void *keep_sp = nullptr, *keep_qd = nullptr, *keep_tr = nullptr, *keep_vx = nullptr;
+  hj::lbvh::Shapes sh{};
+  {
+    float4* sp = nullptr; float4* qd = nullptr; hj_triangle* tr = nullptr; hj_vertex* vx = nullptr;
+    HJ_TRY(bufs.alloc(sp, s->num_spheres));
+    HJ_TRY(bufs.alloc(qd, 3 * s->num_quads));
+    HJ_TRY(bufs.alloc(tr, s->num_triangles));
+    HJ_TRY(bufs.alloc(vx, s->num_vertices));
+    if (s->num_spheres) HJ_HIP(ctx, hipMemcpyAsync(sp, s->spheres, sizeof(float4) * s->num_spheres, hipMemcpyHostToDevice, st));
+    if (s->num_quads) HJ_HIP(ctx, hipMemcpyAsync(qd, s->quads, sizeof(float4) * 3 * s->num_quads, hipMemcpyHostToDevice, st));
+    if (s->num_triangles) HJ_HIP(ctx, hipMemcpyAsync(tr, s->triangles, sizeof(hj_triangle) * s->num_triangles, hipMemcpyHostToDevice, st));
+    if (s->num_vertices) HJ_HIP(ctx, hipMemcpyAsync(vx, s->vertices, sizeof(hj_vertex) * s->num_vertices, hipMemcpyHostToDevice, st));
+    sh.spheres = sp; sh.quads = qd; sh.triangles = tr; sh.vertices = vx;
+    keep_sp = sp; keep_qd = qd; keep_tr = tr; keep_vx = vx;
+    sh.ns = (uint32_t)s->num_spheres; sh.nq = (uint32_t)s->num_quads; sh.nt = (uint32_t)s->num_triangles;
+  }
+  hj_bvh_node* d_out = nullptr;
+  double* d_partial = nullptr;
+  HJ_TRY(bufs.alloc(d_out, total));
+  if (out_cost) HJ_TRY(bufs.alloc(d_partial, grid.x));
+  clock.mark("allocations + shape upload");
+  // ONE launch: leaf boxes, inner boxes, records (HJ_REFIT_TILED: which form - DESIGN.md 4, "Refit")
+  if (tn.refit_tiled != 0)
+    hipLaunchKernelGGL(hj::lbvh::k_rf_tiled, dim3((N + hj::lbvh::kRfTile - 1) / hj::lbvh::kRfTile), blk, 0, st, r, sh, reinterpret_cast<float4*>(d_out));
+  else
+    hipLaunchKernelGGL(hj::lbvh::k_rf_climb, grid, blk, 0, st, r, sh, reinterpret_cast<float4*>(d_out));
+  clock.mark(tn.refit_tiled != 0 ? "bottom-up pass (tiled)" : "bottom-up pass (plain climb)");
+  if (out_cost) hipLaunchKernelGGL(hj::lbvh::k_rf_cost, grid, blk, 0, st, reinterpret_cast<const float4*>(d_out), N, d_partial);
+  if (out_nodes) HJ_HIP(ctx, hipMemcpyAsync(out_nodes, d_out, sizeof(hj_bvh_node) * total, hipMemcpyDeviceToHost, st));
+  HJ_HIP(ctx, hipStreamSynchronize(st));
+  HJ_HIP(ctx, hipGetLastError());
+  std::vector<double> partial;
+  hj_bvh_node root{};
+  if (out_cost) {                                            // (synchronous copies: nothing is in flight into this frame's storage)
+    partial.resize(grid.x);
+    HJ_HIP(ctx, hipMemcpy(partial.data(), d_partial, sizeof(double) * grid.x, hipMemcpyDeviceToHost));
+    HJ_HIP(ctx, hipMemcpy(&root, d_out, sizeof root, hipMemcpyDeviceToHost));
+  }
+  clock.mark("cost, records to the host");
+  if (out_cost) {
+    double sum = 0.0;
+    for (double p : partial) sum += p;                       // index order: the same double for the same records
+    const double dx = (double)root.aabb_max[0] - (double)root.aabb_min[0], dy = (double)root.aabb_max[1] - (double)root.aabb_min[1],
+                 dz = (double)root.aabb_max[2] - (double)root.aabb_min[2];
+    const double area = (dx >= 0 && dy >= 0 && dz >= 0) ? dx * dy + dy * dz + dz * dx : 0.0;
+    *out_cost = area > 0.0 ? sum / area : 0.0;
+  }
+  {
+    hj_context::ResidentTree& rt = ctx->resident;
+    rt.nodes = bufs.take(d_out); rt.spheres = bufs.take(keep_sp); rt.quads = bufs.take(keep_qd);
+    rt.triangles = bufs.take(keep_tr); rt.vertices = bufs.take(keep_vx);
+    rt.total = total; rt.ns = s->num_spheres; rt.nq = s->num_quads; rt.nt = s->num_triangles; rt.nv = s->num_vertices;
+    rt.shapes_hash = shape_arrays_hash(s);
+    rt.valid = rt.nodes.p != nullptr;
+  }
+  if (out_num_nodes) *out_num_nodes = total;
+  return HJ_OK;
+}
+
 }  // extern "C"

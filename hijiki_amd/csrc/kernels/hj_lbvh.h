@@ -60,34 +60,40 @@ __global__ void k_init_bounds(int* bounds) {
   if (threadIdx.x < 12) bounds[threadIdx.x] = (threadIdx.x % 6u) < 3u ? 0x7FFFFFFF : (int)0x80000000;
 }
 
-// Shape bounds as the host computes them (src/shape.rs:13-20,46-54, src/main.rs:74-79) + bounds of the centroids.
+// The box of shape i (global shape index: spheres, quads, triangles) as the host computes it (src/shape.rs:13-20,46-54,
+// src/main.rs:74-79): ONE text for the build (k_shape_boxes) and the refit (k_rf_climb).
+HJ_DEV void shape_box(const Shapes& s, uint32_t i, float lo[3], float hi[3]) {
+  if (i < s.ns) {
+    const float4 sp = s.spheres[i];
+    const float c[3] = {sp.x, sp.y, sp.z};
+    for (int k = 0; k < 3; k++) { lo[k] = c[k] - sp.w; hi[k] = c[k] + sp.w; }
+    for (int k = 0; k < 3; k++) { const float a = f_min(lo[k], hi[k]), b = f_max(lo[k], hi[k]); lo[k] = a; hi[k] = b; }
+  } else if (i < s.ns + s.nq) {
+    const uint32_t q = i - s.ns;
+    const float4 o = s.quads[3 * q], e1 = s.quads[3 * q + 1], e2 = s.quads[3 * q + 2];
+    const float O[3] = {o.x, o.y, o.z}, A[3] = {e1.x, e1.y, e1.z}, B[3] = {e2.x, e2.y, e2.z};
+    for (int k = 0; k < 3; k++) {
+      const float p1 = O[k] + A[k], p2 = O[k] + B[k], p3 = (O[k] + A[k]) + B[k];
+      lo[k] = f_min(f_min(O[k], p1), f_min(p2, p3));
+      hi[k] = f_max(f_max(O[k], p1), f_max(p2, p3));
+    }
+  } else {
+    const hj_triangle tr = s.triangles[i - s.ns - s.nq];
+    const hj_vertex a = s.vertices[tr.v[0]], b = s.vertices[tr.v[1]], c = s.vertices[tr.v[2]];
+    for (int k = 0; k < 3; k++) {
+      lo[k] = f_min(f_min(a.pos[k], b.pos[k]), c.pos[k]);
+      hi[k] = f_max(f_max(a.pos[k], b.pos[k]), c.pos[k]);
+    }
+  }
+}
+
+// Shape bounds + bounds of the centroids.
 __global__ __launch_bounds__(256) void k_shape_boxes(Shapes s, Tree t, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
   const bool valid = i < n;
   if (valid) {
-    if (i < s.ns) {
-      const float4 sp = s.spheres[i];
-      const float c[3] = {sp.x, sp.y, sp.z};
-      for (int k = 0; k < 3; k++) { lo[k] = c[k] - sp.w; hi[k] = c[k] + sp.w; }
-      for (int k = 0; k < 3; k++) { const float a = f_min(lo[k], hi[k]), b = f_max(lo[k], hi[k]); lo[k] = a; hi[k] = b; }
-    } else if (i < s.ns + s.nq) {
-      const uint32_t q = i - s.ns;
-      const float4 o = s.quads[3 * q], e1 = s.quads[3 * q + 1], e2 = s.quads[3 * q + 2];
-      const float O[3] = {o.x, o.y, o.z}, A[3] = {e1.x, e1.y, e1.z}, B[3] = {e2.x, e2.y, e2.z};
-      for (int k = 0; k < 3; k++) {
-        const float p1 = O[k] + A[k], p2 = O[k] + B[k], p3 = (O[k] + A[k]) + B[k];
-        lo[k] = f_min(f_min(O[k], p1), f_min(p2, p3));
-        hi[k] = f_max(f_max(O[k], p1), f_max(p2, p3));
-      }
-    } else {
-      const hj_triangle tr = s.triangles[i - s.ns - s.nq];
-      const hj_vertex a = s.vertices[tr.v[0]], b = s.vertices[tr.v[1]], c = s.vertices[tr.v[2]];
-      for (int k = 0; k < 3; k++) {
-        lo[k] = f_min(f_min(a.pos[k], b.pos[k]), c.pos[k]);
-        hi[k] = f_max(f_max(a.pos[k], b.pos[k]), c.pos[k]);
-      }
-    }
+    shape_box(s, i, lo, hi);
     t.leaf_lo[i] = make_float4(lo[0], lo[1], lo[2], 0.f);
     t.leaf_hi[i] = make_float4(hi[0], hi[1], hi[2], 0.f);
   }
@@ -671,6 +677,194 @@ __global__ __launch_bounds__(256) void k_emit(Tree t, uint32_t n, uint32_t base,
   nd.aabb_max[0] = hi.x; nd.aabb_max[1] = hi.y; nd.aabb_max[2] = hi.z;
   nd.exit_index = end >= base + total ? end_exit : end;     // right spine: the exit of the subtree's root (src/main.rs:214-231)
   out[pos] = nd;
+}
+
+// ---- REFIT (hj_refit_bvh_device, api/lbvh_build.hip): the boxes of a flattened tree recomputed for shapes that have moved.  The
+// topology is the LINKS of the pre-order skip-link array, 8 bytes per record: x = shape_index (HJ_BVH_INNER: inner node), y =
+// exit_index.  Inner node i has the children l = i + 1 and r = exit[l].
+struct Refit {
+  const uint2* links;         // [N]
+  uint32_t N, n;              // records, shapes (N = 2n - 1)
+  uint32_t* parent;           // [N] parent of record i (record 0: kNoParent)
+  uint32_t* arrived;          // [N] arrival counters of the climb: k_rf_links zeroes them, every pass leaves them zero
+  uint32_t* nparents;         // [N] validation: how many inner nodes name record i as a child (zeroed)
+  uint32_t* seen;             // [n] validation: how many leaves hold shape k (zeroed)
+  uint32_t* err;              // [4] validation: [0] bit 0 not a tree, bit 1 a shape index out of range, bit 2 a shape in no leaf,
+                              //     bit 3 a shape in two leaves (zeroed); the lowest such shape: [1] in no leaf, [2] out of range,
+                              //     [3] in two leaves (set to 0xFFFFFFFF)
+};
+enum : uint32_t { kRfNotATree = 1u, kRfShapeRange = 2u, kRfShapeMissing = 4u, kRfShapeTwice = 8u };
+
+// links -> parents, one thread per record.  CHECK: the links come from the host - the conditions of a pre-order skip-link tree
+// (those of api/scene_relayout.hip k_rl_links / k_rl_check_tree: exits point forward, the right child's exit is its parent's,
+// every record but the root is the child of exactly one node) and the scatter leaf -> shape are verified on the way; nothing is
+// written outside [0, N) or [0, n) whatever the links hold.
+template <bool CHECK>
+__global__ __launch_bounds__(256) void k_rf_links(Refit r) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= r.N) return;
+  const uint2 me = r.links[i];
+  if (i == 0) r.parent[0] = kNoParent;
+  r.arrived[i] = 0;
+  if (CHECK) {
+    if (me.y <= i) { atomicOr(&r.err[0], kRfNotATree); return; }
+    if (i == 0 && me.x != HJ_BVH_INNER) atomicOr(&r.err[0], kRfNotATree);   // (2 shapes at least: the root is an inner node)
+  }
+  if (me.x != HJ_BVH_INNER) {
+    if (CHECK) {
+      if (me.x >= r.n) { atomicOr(&r.err[0], kRfShapeRange); atomicMin(&r.err[2], me.x); return; }
+      atomicAdd(&r.seen[me.x], 1u);
+    }
+    return;
+  }
+  const uint32_t l = i + 1;
+  if (CHECK && l >= r.N) { atomicOr(&r.err[0], kRfNotATree); return; }
+  const uint32_t rr = r.links[l].y;
+  if (CHECK) {
+    if (rr >= r.N || rr <= l || r.links[rr].y != me.y) { atomicOr(&r.err[0], kRfNotATree); return; }
+    atomicAdd(&r.nparents[l], 1u); atomicAdd(&r.nparents[rr], 1u);
+  }
+  r.parent[l] = i; r.parent[rr] = i;
+}
+// one thread per record: its parent count; threads [0, n) also: shape k sits in exactly one leaf
+__global__ __launch_bounds__(256) void k_rf_check(Refit r) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= r.N) return;
+  if (r.nparents[i] != (i == 0 ? 0u : 1u)) atomicOr(&r.err[0], kRfNotATree);
+  if (i < r.n && r.seen[i] != 1u) { atomicOr(&r.err[0], r.seen[i] == 0u ? kRfShapeMissing : kRfShapeTwice); atomicMin(r.seen[i] == 0u ? &r.err[1] : &r.err[3], i); }
+}
+
+HJ_DEV void rf_store(float4* out, uint32_t i, const float lo[3], const float hi[3], uint2 link) {
+  out[2 * (size_t)i] = make_float4(lo[0], lo[1], lo[2], __uint_as_float(link.x));
+  out[2 * (size_t)i + 1] = make_float4(hi[0], hi[1], hi[2], __uint_as_float(link.y));
+}
+
+// From record `child`, whose box (lo, hi) is written: up through the arrival counters.  At every inner node the first thread to
+// arrive leaves, the second one joins its box with the SIBLING's - which another CU may have written in this launch: read at agent
+// scope, ld_agent -, writes the node's record and goes on.
+HJ_DEV void rf_climb_from(const Refit& r, float4* out, uint32_t child, float lo[3], float hi[3]) {
+  uint32_t node = r.parent[child];
+  while (node != kNoParent) {
+    __threadfence();                                         // my child's record is visible before I count myself in
+    if (atomicAdd(&r.arrived[node], 1u) == 0u) return;
+    r.arrived[node] = 0;                                     // (nobody else comes: the counters are zero again when the pass ends)
+    __threadfence();
+    const uint32_t l = node + 1;
+    const uint32_t sib = child == l ? r.links[l].y : l;
+    const float4 slo = ld_agent(&out[2 * (size_t)sib]), shi = ld_agent(&out[2 * (size_t)sib + 1]);
+    lo[0] = f_min(lo[0], slo.x); lo[1] = f_min(lo[1], slo.y); lo[2] = f_min(lo[2], slo.z);
+    hi[0] = f_max(hi[0], shi.x); hi[1] = f_max(hi[1], shi.y); hi[2] = f_max(hi[2], shi.z);
+    rf_store(out, node, lo, hi, r.links[node]);
+    child = node;
+    node = r.parent[node];
+  }
+}
+
+// The bottom-up pass over the flattened array, k_refit's form: one thread per RECORD; the thread of a leaf computes the box of
+// its shape (shape_box), writes the leaf's record and climbs with that box in registers.  At every inner node the first thread to
+// arrive leaves, the second one joins its box with the SIBLING's - which another CU may have written in this launch: read at agent
+// scope, ld_agent -, writes the node's record and goes on.  f_min / f_max are exact and commutative: the result does not depend on
+// who arrives first.  No depth limit, no waiting.  `out`: the N 32-byte records as pairs of float4.
+__global__ __launch_bounds__(256) void k_rf_climb(Refit r, Shapes s, float4* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= r.N) return;
+  const uint2 me = r.links[i];
+  if (me.x == HJ_BVH_INNER) return;
+  float lo[3], hi[3];
+  shape_box(s, me.x, lo, hi);
+  rf_store(out, i, lo, hi, me);
+  rf_climb_from(r, out, i, lo, hi);
+}
+
+// The TILED form of the same pass.  A workgroup owns a run of kRfTile consecutive records; in pre-order a subtree is a contiguous
+// range, so most subtrees lie wholly inside one run.  Those are finished in LDS with workgroup barriers only: round after round an
+// inner node whose two children are in the run and done takes their union (no assumption about the links beyond "children follow
+// their parent": a node whose child lies outside the run, or is not done, simply stays open).  The records that are done go out
+// in one sweep; then only the LOCAL ROOTS - done nodes whose parent is not - climb through the arrival counters as k_rf_climb's
+// leaves do, and finish the nodes whose subtrees straddle runs.  The sweep's stores are another thread's than the one that
+// counts itself in at the parent, so every thread fences its own stores (agent scope) before the barrier that precedes the climb.
+constexpr uint32_t kRfTile = 1024, kRfPer = kRfTile / 256;
+__global__ __launch_bounds__(256) void k_rf_tiled(Refit r, Shapes s, float4* out) {
+  __shared__ float s_box[6][kRfTile];
+  __shared__ uint2 s_link[kRfTile];
+  __shared__ uint8_t s_done[kRfTile];
+  const uint32_t b = blockIdx.x * kRfTile, tid = threadIdx.x;
+  const uint32_t cnt = r.N - b < kRfTile ? r.N - b : kRfTile;
+  uint32_t open = 0;                                         // bit k: my record tid + 256 k is an inner node that is not done
+  for (uint32_t k = 0; k < kRfPer; k++) {
+    const uint32_t j = tid + 256u * k;
+    if (j >= cnt) break;
+    const uint2 me = r.links[b + j];
+    s_link[j] = me;
+    if (me.x != HJ_BVH_INNER) {
+      float lo[3], hi[3];
+      shape_box(s, me.x, lo, hi);
+      for (int d = 0; d < 3; d++) { s_box[d][j] = lo[d]; s_box[3 + d][j] = hi[d]; }
+      s_done[j] = 1;
+    } else {
+      s_done[j] = 0;
+      open |= 1u << k;
+    }
+  }
+  __syncthreads();
+  for (;;) {
+    uint32_t now = 0;
+    for (uint32_t k = 0; k < kRfPer; k++) {
+      if (!(open >> k & 1u)) continue;
+      const uint32_t j = tid + 256u * k, l = j + 1;
+      if (l >= cnt) continue;
+      const uint32_t rr = s_link[l].y - b;                   // (exits point forward: no wrap; a right-spine exit is far outside)
+      if (rr >= cnt || !s_done[l] || !s_done[rr]) continue;
+      for (int d = 0; d < 3; d++) {
+        s_box[d][j] = f_min(s_box[d][l], s_box[d][rr]);
+        s_box[3 + d][j] = f_max(s_box[3 + d][l], s_box[3 + d][rr]);
+      }
+      now |= 1u << k;
+    }
+    if (!__syncthreads_or((int)now)) break;                   // (nobody reads a box before its done flag, set behind this barrier)
+    for (uint32_t k = 0; k < kRfPer; k++) if (now >> k & 1u) s_done[tid + 256u * k] = 1;
+    open &= ~now;
+    __syncthreads();
+  }
+  for (uint32_t k = 0; k < kRfPer; k++) {
+    const uint32_t j = tid + 256u * k;
+    if (j >= cnt || !s_done[j]) continue;
+    const float lo[3] = {s_box[0][j], s_box[1][j], s_box[2][j]}, hi[3] = {s_box[3][j], s_box[4][j], s_box[5][j]};
+    rf_store(out, b + j, lo, hi, s_link[j]);
+  }
+  __threadfence();
+  __syncthreads();
+  for (uint32_t k = 0; k < kRfPer; k++) {
+    const uint32_t j = tid + 256u * k;
+    if (j >= cnt || !s_done[j]) continue;
+    const uint32_t p = r.parent[b + j];
+    if (p == kNoParent || (p >= b && s_done[p - b])) continue;
+    float lo[3] = {s_box[0][j], s_box[1][j], s_box[2][j]}, hi[3] = {s_box[3][j], s_box[4][j], s_box[5][j]};
+    rf_climb_from(r, out, b + j, lo, hi);
+  }
+}
+
+// The tree's surface-area cost: partial[b] = sum over the inner nodes of workgroup b's 256 records of area(node), in double, the
+// workgroup's sum taken in a fixed order (LDS tree); the host adds the partial sums in index order and divides by the root's area.
+HJ_DEV double rf_area(const float4 lo, const float4 hi) {
+  const double dx = (double)hi.x - (double)lo.x, dy = (double)hi.y - (double)lo.y, dz = (double)hi.z - (double)lo.z;
+  return (dx >= 0 && dy >= 0 && dz >= 0) ? dx * dy + dy * dz + dz * dx : 0.0;
+}
+__global__ __launch_bounds__(256) void k_rf_cost(const float4* __restrict__ rec, uint32_t N, double* __restrict__ partial) {
+  __shared__ double s_sum[256];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  double a = 0.0;
+  if (i < N) {
+    const float4 lo = rec[2 * (size_t)i], hi = rec[2 * (size_t)i + 1];
+    if (__float_as_uint(lo.w) == HJ_BVH_INNER) a = rf_area(lo, hi);
+  }
+  s_sum[threadIdx.x] = a;
+  __syncthreads();
+  for (uint32_t w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = s_sum[0];
 }
 
 }  // namespace lbvh

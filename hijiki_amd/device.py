@@ -24,7 +24,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_comm_create", "hj_comm_destroy", "hj_comm_reduce_framebuffers", "hj_reserve", "hj_framebuffer_bind",
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
-           "hj_debug_env_distribution")
+           "hj_debug_env_distribution", "hj_refit_bvh_device")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -83,6 +83,8 @@ def lib():
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
         L.hj_bvh_device_read.argtypes = [vp, C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
+        L.hj_refit_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_double)]
         L.hj_block_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.hj_block_seed.restype = C.c_uint32
         L.hj_pass_offset.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
@@ -307,6 +309,30 @@ class Renderer:
         self._check(lib().hj_build_bvh_device(self._h, C.byref(compiled.desc), nodes.ctypes.data_as(C.POINTER(abi.BvhNode)),
                                               len(nodes), C.byref(got)))
         return nodes[:got.value]
+
+    def refit_bvh(self, compiled, topology=None, keep_on_device=False, cost=False):
+        """hj_refit_bvh_device: the boxes of a tree recomputed for the shapes of `compiled` as they are now (`compiled.vertices`,
+        `.spheres`, `.quads` are writable views: an animation writes into them); the links stay.  `topology`: an (N, 8) uint32 array
+        whose shape and exit words are the tree (its boxes are ignored; the context keeps the links), None = the links the last
+        refit with a topology left.  Returns the (2 * shapes - 1, 8) uint32 records, or with keep_on_device=True their count
+        (`upload_scene(compiled, device_tree=True)` takes the tree over, `read_device_bvh()` copies it out); with cost=True a pair
+        (that, the tree's surface-area cost: sum over inner nodes of area(node) / area(root))."""
+        d = abi.SceneDesc()
+        C.memmove(C.byref(d), C.byref(compiled.desc), C.sizeof(abi.SceneDesc))
+        if topology is None:
+            d.bvh = None
+            d.num_bvh_nodes = 0
+        else:
+            topology = np.ascontiguousarray(topology, np.uint32).reshape(-1, 8)
+            d.bvh = topology.ctypes.data_as(C.POINTER(abi.BvhNode))
+            d.num_bvh_nodes = len(topology)
+        got = C.c_size_t(0)
+        sa = C.c_double(0.0)
+        nodes = None if keep_on_device else np.zeros((max(2 * compiled.num_shapes - 1, 1), 8), np.uint32)
+        self._check(lib().hj_refit_bvh_device(self._h, C.byref(d), None if nodes is None else nodes.ctypes.data_as(C.POINTER(abi.BvhNode)),
+                                              0 if nodes is None else len(nodes), C.byref(got), C.byref(sa) if cost else None))
+        out = got.value if keep_on_device else nodes[:got.value]
+        return (out, sa.value) if cost else out
 
     def read_device_bvh(self):
         """hj_bvh_device_read: the tree the last build left on the device, (nodes, 8) uint32."""

@@ -354,6 +354,31 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* scene, hj_bvh_node
  * tree handed over through the host, bit for bit. */
 int hj_bvh_device_read(hj_context* ctx, hj_bvh_node* out_nodes, size_t capacity, size_t* out_num_nodes /* may be NULL */);
 
+/* The boxes of a tree recomputed for shapes that have moved; the links stay (a REFIT, for deforming meshes and moving spheres:
+ * one pass over the tree instead of a new build).  `scene` carries the shape arrays as they are NOW (same counts as the
+ * topology's: the number of leaves is the number of shapes).  Topology:
+ *   scene->bvh != NULL   any valid pre-order skip-link tree with one shape per leaf (Scene::compile's, hj_build_bvh_device's,
+ *                        hj_tune_bvh_device's); only shape_index and exit_index are read, its boxes are ignored.  The context
+ *                        KEEPS a copy of the links on the device (8 bytes per record, and as much again for the parents and
+ *                        counters derived from them) until the context ends or another topology replaces it;
+ *   scene->bvh == NULL && scene->num_bvh_nodes == 0   the links kept by the last refit that brought some (none: HJ_ERR_STATE;
+ *                        those of another shape count: HJ_ERR_INVALID).
+ * Record i of the result keeps shape_index and exit_index; a leaf's box is its shape's (as hj_build_bvh_device computes it), an
+ * inner node's the union of its two children's (IEEE min / max: exact, the same whatever the order of evaluation).  So the refit
+ * of a tree hj_build_bvh_device built, with the shapes unmoved, is that tree bit for bit.
+ * The refitted tree stays on the device exactly as hj_build_bvh_device's does (it replaces such a tree): hj_scene_upload* with
+ * scene->bvh == NULL takes it over, hj_bvh_device_read copies it out; out_nodes (may be NULL) receives it as well.
+ * out_cost (may be NULL): sum over inner nodes of area(node) / area(root), accumulated in double - the tree's surface-area
+ * cost, for a caller who wants to decide when a deformation has gone far enough to rebuild.
+ * Refused with HJ_ERR_INVALID before the tree on the device or the kept links are touched: null arguments or shape arrays, fewer
+ * than 2 shapes, a triangle that names an unknown vertex, num_bvh_nodes != 2 * shapes - 1, links that are not a pre-order skip-link
+ * tree, a shape that is in no leaf or in two.  A failure after that (out of memory) leaves no tree on the device but keeps the
+ * links.  hj_build_bvh_device neither reads nor drops the kept links; an upload consumes the tree, not the links.
+ * Frame loop of an animation: move the shapes, hj_refit_bvh_device(ctx, scene with bvh = NULL, NULL, 0, NULL, NULL),
+ * hj_scene_upload(ctx, scene with bvh = NULL), render. */
+int hj_refit_bvh_device(hj_context* ctx, const hj_scene_desc* scene, hj_bvh_node* out_nodes /* may be NULL */, size_t capacity,
+                        size_t* out_num_nodes /* may be NULL */, double* out_cost /* may be NULL */);
+
 /* The child order of a flattened tree, voted by a sample of the scene's own rays - on the device (no counterpart upstream: the
  * reference walks the tree the `bvh` crate hands it, src/main.rs:199-231, children in array order, shader/scene.glsl:97-133; host
  * form of the same pass: hjh_compiled_tune_bvh).  `vote_paths` camera paths of `scene` (camera, materials, emitters) are traced
