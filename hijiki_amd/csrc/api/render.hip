@@ -8,23 +8,17 @@
 
 namespace hjapi {
 
-// Default path: ONE persistent launch per batch.
+// Default path: ONE persistent launch per batch.  A scene with an environment takes the instantiations with the miss bin.
+using PathKernel = void (*)(hj::BatchState, hj::DeviceScene, uint32_t, uint32_t);
+template <bool USE_BVH, bool PAIRS, bool NT>
+static PathKernel path_kernel(bool env) { return env ? hj::k_path_wavefront_env<USE_BVH, PAIRS, NT> : hj::k_path_wavefront<USE_BVH, PAIRS, NT>; }
+
 void launch_path_wavefront(const hj::BatchState& st, const hj::DeviceScene& sc, const hj_render_opts& o, size_t lds_bytes, hipStream_t s) {
-  const dim3 blk(hj::kBlockThreads), grid(st.num_wg);
-  const bool pairs = sc.has_pairs != 0, nt = sc.stream_state != 0;
-  if (sc.env_alias) {                        // a scene with an environment: the instantiations with the miss bin
-    if (!o.use_bvh) hipLaunchKernelGGL((hj::k_path_wavefront_env<false, false, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-    else if (pairs && nt) hipLaunchKernelGGL((hj::k_path_wavefront_env<true, true, true>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-    else if (pairs) hipLaunchKernelGGL((hj::k_path_wavefront_env<true, true, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-    else if (nt) hipLaunchKernelGGL((hj::k_path_wavefront_env<true, false, true>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-    else hipLaunchKernelGGL((hj::k_path_wavefront_env<true, false, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-    return;
-  }
-  if (!o.use_bvh) hipLaunchKernelGGL((hj::k_path_wavefront<false, false, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-  else if (pairs && nt) hipLaunchKernelGGL((hj::k_path_wavefront<true, true, true>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-  else if (pairs) hipLaunchKernelGGL((hj::k_path_wavefront<true, true, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-  else if (nt) hipLaunchKernelGGL((hj::k_path_wavefront<true, false, true>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
-  else hipLaunchKernelGGL((hj::k_path_wavefront<true, false, false>), grid, blk, lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
+  const bool pairs = sc.has_pairs != 0, nt = sc.stream_state != 0, env = sc.env_alias != nullptr;
+  const PathKernel k = !o.use_bvh ? path_kernel<false, false, false>(env)
+                       : pairs ? (nt ? path_kernel<true, true, true>(env) : path_kernel<true, true, false>(env))
+                               : (nt ? path_kernel<true, false, true>(env) : path_kernel<true, false, false>(env));
+  hipLaunchKernelGGL(k, dim3(st.num_wg), dim3(hj::kBlockThreads), lds_bytes, s, st, sc, o.max_bounces, o.rr_start);
 }
 
 // Diagnostic path (HJ_RENDER_SPLIT_KERNELS): one launch per stage per bounce.

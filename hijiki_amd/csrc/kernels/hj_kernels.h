@@ -20,8 +20,8 @@
 //
 // k_path_wavefront runs all stages of a batch in ONE persistent launch (workgroup barriers only): the kernel's own code
 // is the walk (trace_persistent: in-wave ray replacement, merged first step, bounded burst), the other stages are
-// CALLED device functions (stage_*_call: register-allocated on their own, so the walk stays free of spills; inlined they
-// made the walk spill - rounds 2-3, profiles/NOTES.md); `rp` = the round timing of the statistics build (hj_walk_probe.h);
+// CALLED device functions (stage_*_call<.., ENV>, compact_hits_call<.., ENV>: register-allocated on their own, so the walk
+// stays free of spills; inlined they made the walk spill - rounds 2-3, profiles/NOTES.md); `rp` = the round timing of the statistics build (hj_walk_probe.h);
 // k_gen_camera / k_trace_closest / k_shade / k_trace_shadow launch the stages one by one (diagnostic path).
 // No stage uses a global atomic: appends are wave ballot + one LDS atomic.
 //
@@ -58,7 +58,8 @@ namespace hj {
 #endif
 // The kernel's text is hj_path_kernel.h, instantiated twice: k_path_wavefront, and k_path_wavefront_env for a scene with an
 // environment (ENV: a miss bin in the compaction, environment light in shade).  Two kernels of one text rather than a fourth template
-// flag, so that the first keeps its name and its code.
+// flag, so that the first keeps its name and its code.  (One HJ_DEV body template with ENV as a fourth parameter, called from two thin
+// kernels, was tried: every path kernel comes out a few instructions different, profiles/NOTES.md "Environment twins folded".)
 #define HJ_PATH_KERNEL k_path_wavefront
 #define HJ_PATH_ENV false
 #include "hj_path_kernel.h"

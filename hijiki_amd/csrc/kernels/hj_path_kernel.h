@@ -31,8 +31,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(H
       if (ngen != 0) {
         if (!IMPLICIT) {
           rp.gen_begin();
-          if (ENV) stage_gen_camera_env_call<NT>(ka_lo, ka_hi, g, sh_lds, parity, n0, k_next, ngen, waves);
-          else stage_gen_camera_call<NT>(ka_lo, ka_hi, g, sh_lds, parity, n0, k_next, ngen, waves);
+          stage_gen_camera_call<NT, ENV>(ka_lo, ka_hi, g, sh_lds, parity, n0, k_next, ngen, waves);
           wg_sync(waves);
           rp.gen_end(waves);
         }
@@ -71,18 +70,15 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(H
       uint32_t cam = 0;
       if (IMPLICIT && ngen != 0) {
         cam = 64u * ngen;
-        if (ENV) stage_camera_packets_env_call<NT>(ka_lo, ka_hi, g, parity, n0, ngen, k0, sh_lds);
-        else stage_camera_packets_call<NT>(ka_lo, ka_hi, g, parity, n0, ngen, k0, sh_lds);
+        stage_camera_packets_call<NT, ENV>(ka_lo, ka_hi, g, parity, n0, ngen, k0, sh_lds);
       }
       stage_trace_merged<USE_BVH, PAIRS, NT>(st, sc, g, parity, n - cam, ns, sh);
       rp.walk_end(waves);
-      if (ENV) compact_hits_env_call<NT, 4u>(ka_lo, ka_hi, g, n, sh_lds, waves);
-      else compact_hits_call<NT, 4u>(ka_lo, ka_hi, g, n, sh_lds, waves);
+      compact_hits_call<NT, 4u, ENV>(ka_lo, ka_hi, g, n, sh_lds, waves);
       wg_sync(waves);
       rp.compact_end();
       if (n != 0) {
-        if (ENV) stage_shade_env_call<NT>(ka_lo, ka_hi, g, parity, max_bounces, rr_start, sh_lds, waves);
-        else stage_shade_call<NT>(ka_lo, ka_hi, g, parity, max_bounces, rr_start, sh_lds, waves);
+        stage_shade_call<NT, ENV>(ka_lo, ka_hi, g, parity, max_bounces, rr_start, sh_lds, waves);
       }
       total_closest += n - uni(sh.n_cam_dead);   // (positions of ragged blocks' groups that hold no sample are not rays)
       total_shadow += ns;

@@ -686,90 +686,40 @@ typedef __attribute__((address_space(3))) WgShared* WgSharedLds;
 constexpr size_t kSceneArgOffset = (sizeof(BatchState) + alignof(DeviceScene) - 1) / alignof(DeviceScene) * alignof(DeviceScene);
 struct KernelArgsHead { BatchState st; DeviceScene sc; };      // how the argument segment of those kernels starts
 static_assert(offsetof(KernelArgsHead, sc) == kSceneArgOffset, "DeviceScene's place in the kernel argument segment");
-template <bool NT>
+// What a called stage works on, from what the kernel passes it in registers: the two halves of its argument-segment pointer (the
+// intrinsic is null in a called function) and the LDS address of its WgShared.
+struct StageCtx { const BatchState& st; const DeviceScene& sc; WgShared& sh; };
+HJ_DEV StageCtx stage_ctx(uint32_t ka_lo, uint32_t ka_hi, uint32_t sh_lds) {
+  typedef const __attribute__((address_space(4))) char* KArg;
+  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
+  return {*(const BatchState*)ka, *(const DeviceScene*)(ka + kSceneArgOffset), *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds)};
+}
+
+// ENV: the wrappers of an environment instantiation (shade: the miss bin, environment next-event samples; compaction: the miss bin).
+template <bool NT, bool ENV>
 __device__ __attribute__((noinline)) void stage_shade_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t parity, uint32_t max_bounces,
                                                             uint32_t rr_start, uint32_t sh_lds, uint32_t waves) {
-  // (the argument-segment pointer comes from the kernel: the intrinsic is null in a called function)
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  stage_shade<NT>(st, sc, uni(g), uni(parity), uni(max_bounces), uni(rr_start), sh, uni(waves));
+  const StageCtx c = stage_ctx(ka_lo, ka_hi, sh_lds);
+  stage_shade<NT, ENV>(c.st, c.sc, uni(g), uni(parity), uni(max_bounces), uni(rr_start), c.sh, uni(waves));
 }
-
-// ... of an environment instantiation (the miss bin, environment next-event samples)
-template <bool NT>
-__device__ __attribute__((noinline)) void stage_shade_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t parity, uint32_t max_bounces,
-                                                                uint32_t rr_start, uint32_t sh_lds, uint32_t waves) {
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  stage_shade<NT, true>(st, sc, uni(g), uni(parity), uni(max_bounces), uni(rr_start), sh, uni(waves));
+template <bool NT, uint32_t R, bool ENV>
+__device__ __attribute__((noinline)) void compact_hits_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t n, uint32_t sh_lds, uint32_t waves) {
+  const StageCtx c = stage_ctx(ka_lo, ka_hi, sh_lds);
+  compact_hits_by_tag<NT, R, ENV>(c.st, c.sc, uni(g), uni(n), c.sh, uni(waves));
 }
-
-template <bool NT>
+// The bodies of the next two do not depend on ENV: the parameter only makes the environment kernels' instantiations functions of their
+// own (a called function shared by two kernels is compiled for what both of them need, and the other kernels' code would change with it).
+template <bool NT, bool ENV>
 __device__ __attribute__((noinline)) void stage_gen_camera_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t sh_lds, uint32_t parity,
                                                                  uint32_t n0, uint32_t k0, uint32_t ngen, uint32_t waves) {
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  stage_gen_camera<NT>(st, sc, uni(g), sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves));
+  const StageCtx c = stage_ctx(ka_lo, ka_hi, sh_lds);
+  stage_gen_camera<NT>(c.st, c.sc, uni(g), c.sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves));
 }
-template <bool NT, uint32_t R>
-__device__ __attribute__((noinline)) void compact_hits_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t n, uint32_t sh_lds, uint32_t waves) {
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  compact_hits_by_tag<NT, R>(st, sc, uni(g), uni(n), sh, uni(waves));
-}
-template <bool NT, uint32_t R>
-__device__ __attribute__((noinline)) void compact_hits_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t n, uint32_t sh_lds, uint32_t waves) {
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  compact_hits_by_tag<NT, R, true>(st, sc, uni(g), uni(n), sh, uni(waves));
-}
-
-template <bool NT>
+template <bool NT, bool ENV>
 __device__ __attribute__((noinline)) void stage_camera_packets_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t parity, uint32_t first,
                                                                      uint32_t chunks, uint32_t k0, uint32_t sh_lds) {
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  stage_camera_packets<NT>(st, sc, uni(g), uni(parity), uni(first), uni(chunks), uni(k0), sh);
-}
-// Copies of the two wrappers above for the environment kernels: a called function shared by two kernels is compiled for what both of
-// them need, and the other kernels' code would change with it.
-template <bool NT>
-__device__ __attribute__((noinline)) void stage_gen_camera_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t sh_lds, uint32_t parity,
-                                                                 uint32_t n0, uint32_t k0, uint32_t ngen, uint32_t waves) {
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  stage_gen_camera<NT>(st, sc, uni(g), sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves));
-}
-template <bool NT>
-__device__ __attribute__((noinline)) void stage_camera_packets_env_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t g, uint32_t parity, uint32_t first,
-                                                                     uint32_t chunks, uint32_t k0, uint32_t sh_lds) {
-  typedef const __attribute__((address_space(4))) char* KArg;
-  KArg ka = (KArg)(((uint64_t)uni(ka_hi) << 32) | (uint64_t)uni(ka_lo));
-  const BatchState& st = *(const BatchState*)ka;
-  const DeviceScene& sc = *(const DeviceScene*)(ka + kSceneArgOffset);
-  WgShared& sh = *(WgShared*)(WgSharedLds)(uintptr_t)uni(sh_lds);
-  stage_camera_packets<NT>(st, sc, uni(g), uni(parity), uni(first), uni(chunks), uni(k0), sh);
+  const StageCtx c = stage_ctx(ka_lo, ka_hi, sh_lds);
+  stage_camera_packets<NT>(c.st, c.sc, uni(g), uni(parity), uni(first), uni(chunks), uni(k0), c.sh);
 }
 
 }  // namespace hj

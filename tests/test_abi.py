@@ -117,7 +117,8 @@ def test_walk_of_the_fused_kernel_is_spill_free(tmp_path, monkeypatch):
     """The fused kernel's own code is the BVH walk (top-up, hit compaction, the camera-packet walk and shade are called
     functions with their own register allocation): no scratch (spill) instruction may sit inside the walk's loops, nor
     inside the node loop of the packet stage - one reload there is a dependent memory trip per iteration (DESIGN.md
-    section 4).  tools/spill_scan.py compiles the device code to gfx950 assembly and counts them."""
+    section 4).  tools/spill_scan.py compiles the device code to gfx950 assembly and counts them, for the plain kernels and
+    for the environment kernels (k_path_wavefront_env) alike."""
     import sys
     import tempfile
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -127,7 +128,9 @@ def test_walk_of_the_fused_kernel_is_spill_free(tmp_path, monkeypatch):
     res = spill_scan.scan()
     walks = [e for e in res if e["name"].startswith("k_path_wavefront<USE_BVH=1")]
     packets = [e for e in res if e["name"].startswith("stage_camera_packets_call")]
-    assert len(walks) == 4 and len(packets) == 2, [e["name"] for e in res]   # pair nodes x streamed path state; NT on / off
+    # walks: pair nodes x streamed path state x environment; packets: NT on / off x environment
+    assert len(walks) == 8 and len(packets) == 4, [e["name"] for e in res]
+    assert len({e["name"] for e in walks + packets}) == 12
     for e in walks + packets:
         assert e["max_loop_depth"] >= e["hot_depth"], e["name"]               # (the scan saw the loops it is meant to check)
         assert e["scratch_in_hot_loops"] == 0, (e["name"], e["hot_list"])

@@ -1,9 +1,14 @@
 """Is a change to the kernels' SOURCE a change to their machine code?  Compiles hijiki_amd/csrc/api/render.hip (the unit with the
 path kernels) to gfx950 assembly twice - at a git revision and in the working tree - and compares every function's instruction
-stream (labels, comments and debug directives dropped).  The hygiene work of round 6 (probe hooks instead of #ifdef blocks in
+stream (comments and debug directives dropped; a local label, .LBB<function>_<block>, loses the function's index in the unit, so
+the order in which the functions are emitted does not count).  The hygiene work of round 6 (probe hooks instead of #ifdef blocks in
 the walk, dead build alternatives removed, one text per shape test) was done under this check: 24 of 24 functions identical.
 
-    python tools/isa_diff.py [REV] [extra hipcc flags]        # REV defaults to HEAD; exit code 1 when a function differs
+    python tools/isa_diff.py [REV] [--rename REGEX=REPLACEMENT]... [extra hipcc flags]
+                                                             # REV defaults to HEAD; exit code 1 when a function differs
+
+Across a rename, functions are matched after every --rename (re.sub, in the order given) has been applied to REV's side: to its
+function names and to the symbols its instructions refer to.  A function that exists on one side only after that counts as differing.
 """
 import os, re, subprocess, sys, tempfile
 
@@ -12,9 +17,12 @@ FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-O3", "-ffp-contract=off", "-fn
          "-Wno-unused-function", "--cuda-device-only", "-S"]
 
 
-def functions(path):
+def functions(path, renames=()):
+    text = open(path).read()
+    for pat, repl in renames:
+        text = re.sub(pat, repl, text)
     out, cur = {}, None
-    for l in open(path).read().split("\n"):
+    for l in text.split("\n"):
         m = re.match(r"^(_Z\S+):\s*; @", l)
         if m:
             cur = m.group(1)
@@ -27,22 +35,27 @@ def functions(path):
             t = l.strip()
             if not t or t.startswith(";") or t.startswith(".loc") or t.startswith(".cfi"):
                 continue
-            out[cur].append(re.sub(r";.*$", "", t).rstrip())
+            out[cur].append(re.sub(r"(\.L[A-Za-z]+)\d+_", r"\1_", re.sub(r";.*$", "", t).rstrip()))
     return out
 
 
-def compile_tree(root, out, extra):
+def compile_tree(root, out, extra, renames=()):
     subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "-o", out, os.path.join(root, "hijiki_amd/csrc/api/render.hip")],
                    check=True, stderr=subprocess.DEVNULL)
-    return functions(out)
+    return functions(out, renames)
 
 
 def main():
     args = sys.argv[1:]
     rev = args.pop(0) if args and not args[0].startswith("-") else "HEAD"
+    renames = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
     with tempfile.TemporaryDirectory() as tmp:
         subprocess.run(f"git -C {ROOT} archive {rev} hijiki_amd/csrc include | tar -x -C {tmp}", shell=True, check=True)
-        old = compile_tree(tmp, os.path.join(tmp, "old.s"), args)
+        old = compile_tree(tmp, os.path.join(tmp, "old.s"), args, renames)
         new = compile_tree(ROOT, os.path.join(tmp, "new.s"), args)
     names = sorted(set(old) | set(new))
     differing = [n for n in names if old.get(n) != new.get(n)]

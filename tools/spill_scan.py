@@ -1,6 +1,6 @@
-"""Where the fused kernel's register spills landed: scratch instructions of each k_path_wavefront instantiation and of the
-stage functions it CALLS (stage_camera_packets_call, compact_hits_call, stage_shade_call, stage_gen_camera_call: each is
-register-allocated on its own), and the ones inside their hot loops.  A scratch reload inside the walk loop - or inside the
+"""Where the fused kernel's register spills landed: scratch instructions of each k_path_wavefront / k_path_wavefront_env instantiation
+(ENV=0 / ENV=1 in the labels) and of the stage functions it CALLS (stage_camera_packets_call<NT, ENV>, compact_hits_call<NT, R, ENV>,
+stage_shade_call<NT, ENV>, stage_gen_camera_call<NT, ENV>: each is register-allocated on its own), and the ones inside their hot loops.  A scratch reload inside the walk loop - or inside the
 node loop of the packet stage - is a memory round trip per iteration; cold-stage edits move them around (the allocator is
 global per function), so run this after touching any stage.
 
@@ -21,11 +21,12 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # function-name pattern -> (label, loop depth from which a scratch instruction counts as "hot")
 FUNCS = [
-    (r"_ZN2hj16k_path_wavefrontILb([01])ELb([01])ELb([01])E", "k_path_wavefront<USE_BVH={0}, PAIRS={1}, NT={2}>", 2),
-    (r"_ZN2hj25stage_camera_packets_callILb([01])E", "stage_camera_packets_call<NT={0}>", 2),
-    (r"_ZN2hj17compact_hits_callILb([01])ELj(\d+)E", "compact_hits_call<NT={0}, R={1}>", 1),
-    (r"_ZN2hj16stage_shade_callILb([01])E", "stage_shade_call<NT={0}>", 99),
-    (r"_ZN2hj21stage_gen_camera_callILb([01])E", "stage_gen_camera_call<NT={0}>", 99),
+    (r"_ZN2hj16k_path_wavefrontILb([01])ELb([01])ELb([01])E", "k_path_wavefront<USE_BVH={0}, PAIRS={1}, NT={2}, ENV=0>", 2),
+    (r"_ZN2hj20k_path_wavefront_envILb([01])ELb([01])ELb([01])E", "k_path_wavefront<USE_BVH={0}, PAIRS={1}, NT={2}, ENV=1>", 2),
+    (r"_ZN2hj25stage_camera_packets_callILb([01])ELb([01])E", "stage_camera_packets_call<NT={0}, ENV={1}>", 2),
+    (r"_ZN2hj17compact_hits_callILb([01])ELj(\d+)ELb([01])E", "compact_hits_call<NT={0}, R={1}, ENV={2}>", 1),
+    (r"_ZN2hj16stage_shade_callILb([01])ELb([01])E", "stage_shade_call<NT={0}, ENV={1}>", 99),
+    (r"_ZN2hj21stage_gen_camera_callILb([01])ELb([01])E", "stage_gen_camera_call<NT={0}, ENV={1}>", 99),
 ]
 
 
