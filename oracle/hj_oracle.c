@@ -240,6 +240,9 @@ typedef struct hjo_counters {
 typedef struct {
   const hj_scene_desc* sc;
   const hj_texture_set* tex;   /* image textures (NULL: none); checked by check_textures before any render */
+  const hj_environment* env;   /* environment lighting (NULL: none); checked by check_environment before any render */
+  const float* env_table;      /* its alias table: env_w * env_h records (threshold, alias cell as bits, pdf, pdf of the alias) */
+  uint32_t env_w, env_h;
   uint32_t ns, nq, nt;
   int use_bvh;
   hjo_counters* ctr;
@@ -296,6 +299,56 @@ static int check_textures(const hj_scene_desc* sc, const hj_texture_set* t) {
       return HJ_ERR_INVALID;
   return HJ_OK;
 }
+
+/* ENVIRONMENT LIGHTING (no counterpart upstream; DESIGN.md "Environment lighting"): the environment of the scenes rendered next
+ * and its sampling distribution, both borrowed until replaced; NULL = none.  The distribution arrives as DATA - `cells` records of
+ * four floats (alias-table threshold, alias cell as uint32 bits, pdf of the cell, pdf of the alias cell), what
+ * hj_debug_env_distribution returns - and is not rebuilt here.  Every entry point that shades checks both against the scene and
+ * the texture set first (check_environment) and refuses - renders nothing - what hj_scene_upload_env refuses. */
+static const hj_environment* g_env = NULL;
+static const float* g_env_table = NULL;
+static size_t g_env_cells = 0;
+HJO_EXPORT void hjo_set_environment(const hj_environment* env, const float* table, size_t cells) {
+  g_env = env; g_env_table = env ? table : NULL; g_env_cells = env ? cells : 0;
+}
+
+/* sc may be NULL (the probes have no scene: no emitter rule). */
+static int check_environment(const hj_scene_desc* sc, const hj_texture_set* t, const hj_environment* env, const float* table,
+                             size_t cells) {
+  if (!env) return HJ_OK;
+  const size_t nt = t ? t->num_textures : 0;
+  if (env->texture >= nt) return HJ_ERR_INVALID;
+  for (int c = 0; c < 3; c++)
+    if (!isfinite(env->scale[c]) || env->scale[c] < 0.0f) return HJ_ERR_INVALID;
+  if (!(env->select_prob >= 0.0f && env->select_prob <= 1.0f)) return HJ_ERR_INVALID;
+  if (sc && sc->num_emitters == 0 && env->select_prob != 1.0f) return HJ_ERR_INVALID;
+  const hj_texture* x = &t->textures[env->texture];
+  const size_t n = (size_t)x->width * x->height;
+  if (n > ((size_t)1 << 28)) return HJ_ERR_UNSUPPORTED;
+  const float* tx = t->texels + 4 * (size_t)x->first_texel;
+  for (size_t i = 0; i < n; i++)
+    if (!isfinite(tx[4 * i]) || !isfinite(tx[4 * i + 1]) || !isfinite(tx[4 * i + 2])) return HJ_ERR_INVALID;
+  if (!table || cells != n) return HJ_ERR_INVALID;
+  int any = 0;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t a; memcpy(&a, &table[4 * i + 1], 4);
+    if (a >= n) return HJ_ERR_INVALID;
+    if (table[4 * i + 2] > 0.0f) any = 1;
+  }
+  if (env->select_prob > 0.0f && !any) return HJ_ERR_INVALID;   /* sampled, but every cell weighs 0 */
+  return HJ_OK;
+}
+/* Textures, then the environment: the order of the upload's checks. */
+static int check_scene_inputs(const hj_scene_desc* sc) {
+  const int rc = check_textures(sc, g_textures);
+  if (rc != HJ_OK) return rc;
+  return check_environment(sc, g_textures, g_env, g_env_table, g_env_cells);
+}
+static void bind_environment(scene_t* S) {
+  S->env = g_env; S->env_table = g_env_table; S->env_w = S->env_h = 0;
+  if (g_env) { S->env_w = g_textures->textures[g_env->texture].width; S->env_h = g_textures->textures[g_env->texture].height; }
+}
+static void no_environment(scene_t* S) { S->env = NULL; S->env_table = NULL; S->env_w = S->env_h = 0; }
 
 static inline v3 ld3(const float* p) { return V(p[0], p[1], p[2]); }
 
@@ -528,13 +581,63 @@ static inline void sample_quad(const hj_quad* qd, uint32_t* rng, srec_t* sr) {
   sr->pdf = 1.0f / area;
 }
 
+/* Environment lighting (no counterpart upstream), DESIGN.md "Environment lighting" restated. */
+static v3 texture_rgb(const hj_texture_set* ts, uint32_t t, float u, float v);
+#define ENV_EMITTER 8   /* the emitter index an environment sample carries (the ray log's last column) */
+
+/* Le(d): the lat-long lookup with +y up (populate_sphere's convention for u); d of any length. */
+static v3 env_radiance(const scene_t* S, v3 d) {
+  float u = 0.5f + hj_atan2(d.z, d.x) * (1.0f / TWO_PIF);
+  float v = 0.5f + hj_atan2(d.y, sqrtf(d.x * d.x + d.z * d.z)) * INV_PIF;
+  if (u != u) u = 0.0f;
+  v3 c = texture_rgb(S->tex, S->env->texture, u, v);
+  return V(S->env->scale[0] * c.x, S->env->scale[1] * c.y, S->env->scale[2] * c.z);
+}
+
+/* One direction of the sampling distribution: draw a picks a column of the alias table, the coin keeps it or takes its alias,
+ * draw b places the direction in the cell - its high 16 bits in phi, its low 16 in sin(latitude), each (k + 1/2) / 65536. */
+static v3 env_direction(const scene_t* S, float coin, uint32_t a, uint32_t b, float* pdf, uint32_t* cell) {
+  const uint32_t W = S->env_w, H = S->env_h;
+  const uint32_t col = (uint32_t)(((uint64_t)a * (uint64_t)(W * H)) >> 32);
+  const float* rec = &S->env_table[4 * (size_t)col];
+  if (coin >= rec[0]) { *cell = f2bits(rec[1]); *pdf = rec[3]; }
+  else { *cell = col; *pdf = rec[2]; }
+  const uint32_t x = *cell % W, y = *cell / W;
+  const float fu = ((float)(b >> 16) + 0.5f) * (1.0f / 65536.0f);
+  const float fv = ((float)(b & 0xFFFFu) + 0.5f) * (1.0f / 65536.0f);
+  float sphi, cphi, s0, y0, s1, y1;
+  hj_sincos2pi(((float)x + fu) / (float)W - 0.5f, &sphi, &cphi);      /* phi = 2 pi ((x + fu) / W - 1/2) */
+  hj_sincos2pi((float)y / (float)(2u * H), &s0, &y0);                 /* y0 = cos(pi y / H) = cos(2 pi (y / 2H)) */
+  hj_sincos2pi((float)(y + 1u) / (float)(2u * H), &s1, &y1);
+  (void)s0; (void)s1;
+  const float ys = y1 + fv * (y0 - y1);
+  const float rr = sqrtf(f_max(0.0f, 1.0f - ys * ys));
+  return V(rr * cphi, ys, rr * sphi);
+}
+
 /* shader/scene.glsl:54-89.  Always consumes 3 random numbers.  With no
  * emitters the reference reads emitters[0] out of bounds (undefined); here
- * that case draws the 3 numbers and returns zero importance. */
+ * that case draws the 3 numbers and returns zero importance.
+ * With an environment the selection draw picks it with probability p_env (shadow ray to infinity, the same two further draws);
+ * otherwise the draw is remapped to [0, 1) and an area emitter's probability is scaled by 1 - p_env. */
 static _Thread_local int g_last_emitter = -1;     /* sample_emitter's choice: the last column of the diagnostic ray log below */
 static inline v3 sample_emitter(const scene_t* S, v3 ref, uint32_t* rng, ray_t* sh) {
   const hj_scene_desc* sc = S->sc;
   float xi = rng_float(rng);
+  float area_share = 1.0f;
+  if (S->env) {
+    const float pe = S->env->select_prob;
+    if (pe == 1.0f || xi < pe) {
+      const uint32_t a = rng_uint(rng), b = rng_uint(rng);
+      float pdf; uint32_t cell;
+      const v3 dir = env_direction(S, xi / pe, a, b, &pdf, &cell);
+      g_last_emitter = ENV_EMITTER;
+      sh->o = ref; sh->d = dir; sh->tmin = 2.0f * M_EPSF; sh->tmax = INFINITY;
+      return v_divs(env_radiance(S, dir), pe * pdf);
+    }
+    xi = (xi - pe) / (1.0f - pe);
+    area_share = 1.0f - pe;
+  }
   if (sc->num_emitters == 0) {
     rng_uint(rng); rng_uint(rng);
     sh->o = ref; sh->d = V(0, 0, 0); sh->tmin = 2.0f * M_EPSF; sh->tmax = 0.0f;
@@ -559,7 +662,8 @@ static inline v3 sample_emitter(const scene_t* S, v3 ref, uint32_t* rng, ray_t* 
   sh->o = ref; sh->d = dir; sh->tmin = 2.0f * M_EPSF; sh->tmax = dist - M_EPSF;
   float cosT = neg_of(dot3(dir, sr.n));
   if (cosT < 0.0f) return V(0, 0, 0);
-  float pdf = (((sc->emitters[e].pdf * sr.pdf) * dist) * dist) / cosT;
+  const float epdf = S->env ? sc->emitters[e].pdf * area_share : sc->emitters[e].pdf;
+  float pdf = (((epdf * sr.pdf) * dist) * dist) / cosT;
   return v_divs(power, pdf);
 }
 
@@ -726,7 +830,7 @@ typedef struct { float rgb[3]; float w; float n[3]; float depth; } sample_t;   /
 
 /* Diagnostic (tests and tools only): hjo_set_ray_log(path) makes every ray of the single-threaded entry points (hjo_integrate_block)
  * append a record of eleven floats - o, d, tMin, tMax, kind (0 closest, 1 shadow), hit id or -1, index of the emitter a shadow ray
- * aims at (-1 for a closest-hit ray) - to `path`; NULL closes the log. */
+ * aims at (8 = the environment; -1 for a closest-hit ray) - to `path`; NULL closes the log. */
 static FILE* g_ray_log = NULL;
 HJO_EXPORT void hjo_set_ray_log(const char* path) {
   if (g_ray_log) { fclose(g_ray_log); g_ray_log = NULL; }
@@ -752,7 +856,16 @@ static void integrate_ray(const scene_t* S, ray_t ray, uint32_t* rng, uint32_t m
     {
       const int hit_ = intersect_scene(S, ray, &its, closest_ctr(c));
       log_ray(&ray, 0, hit_ ? its.id : -1);
-      if (!hit_) break;
+      if (!hit_) {
+        /* The ray left the scene: the environment's radiance under the rule of emissive hits (camera ray, or after a mirror or
+         * glass bounce), nothing in a channel whose extinction is non-zero (exp(-ext * inf)), and the path ends. */
+        if (S->env && was_discrete) {
+          const v3 le = env_radiance(S, ray.d);
+          total = v_add(total, V(ext.x != 0.0f ? 0.0f : T.x * le.x, ext.y != 0.0f ? 0.0f : T.y * le.y,
+                                 ext.z != 0.0f ? 0.0f : T.z * le.z));
+        }
+        break;
+      }
     }
     c->hits++;
     if (bounce == 0) { out->depth = its.t; out->n[0] = its.n.x; out->n[1] = its.n.y; out->n[2] = its.n.z; }
@@ -879,6 +992,7 @@ static void* worker_main(void* arg) {
   hjo_counters local; memset(&local, 0, sizeof local);   /* on this thread's stack: no false sharing between workers */
   scene_t S; S.sc = J->sc; S.tex = J->tex; S.ns = (uint32_t)J->sc->num_spheres; S.nq = (uint32_t)J->sc->num_quads;
   S.nt = (uint32_t)J->sc->num_triangles; S.use_bvh = (int)J->opts->use_bvh; S.ctr = &local;
+  bind_environment(&S);
   const size_t chunks_per_block = (HJ_BLOCK_SIZE + ROW_CHUNK - 1) / ROW_CHUNK;
   for (;;) {
     pthread_barrier_wait(&J->bar);            /* batch start */
@@ -930,7 +1044,7 @@ HJO_EXPORT int hjo_render_blocks(const hj_scene_desc* sc, const hj_image_block* 
   if (opts->recon_radius != 2) return HJ_ERR_UNSUPPORTED;
   if (!validate_blocks(blocks, nblocks, W, H)) return HJ_ERR_INVALID;
   if (sc->num_materials != sc->num_spheres + sc->num_quads + sc->num_triangles) return HJ_ERR_INVALID;
-  const int trc = check_textures(sc, g_textures);
+  const int trc = check_scene_inputs(sc);
   if (trc != HJ_OK) return trc;
   if (nthreads < 1) nthreads = 1;
   job_t J; memset(&J, 0, sizeof J);
@@ -1047,6 +1161,7 @@ HJO_EXPORT int hjo_intersect(const hj_scene_desc* sc, int use_bvh, const float* 
   hjo_counters c; memset(&c, 0, sizeof c);
   scene_t S; S.sc = sc; S.ns = (uint32_t)sc->num_spheres; S.nq = (uint32_t)sc->num_quads;
   S.nt = (uint32_t)sc->num_triangles; S.use_bvh = use_bvh; S.ctr = &c; S.tex = NULL;
+  no_environment(&S);
   for (size_t i = 0; i < n; i++) {
     const float* r = &rays[i * 8];
     ray_t ray; ray.o = V(r[0], r[1], r[2]); ray.d = V(r[3], r[4], r[5]); ray.tmin = r[6]; ray.tmax = r[7];
@@ -1086,11 +1201,12 @@ HJO_EXPORT void hjo_camera_rays(const hj_camera* cam, uint32_t W, uint32_t H, co
  * (rgb, w, normal, depth) = layers 0 and 1 of the intermediate image. */
 HJO_EXPORT int hjo_integrate_block(const hj_scene_desc* sc, const hj_image_block* b, const hj_render_opts* opts,
                                    float* out, hjo_counters* ctr_out) {
-  const int trc = check_textures(sc, g_textures);
+  const int trc = check_scene_inputs(sc);
   if (trc != HJ_OK) return trc;
   hjo_counters c; memset(&c, 0, sizeof c);
   scene_t S; S.sc = sc; S.ns = (uint32_t)sc->num_spheres; S.nq = (uint32_t)sc->num_quads;
   S.nt = (uint32_t)sc->num_triangles; S.use_bvh = (int)opts->use_bvh; S.ctr = &c; S.tex = g_textures;
+  bind_environment(&S);
   integrate_block(&S, b, opts, tan_half_fov(sc->camera.fov), (sample_t*)out, 0, b->dimension[1]);
   if (ctr_out) *ctr_out = c;
   return HJ_OK;
@@ -1118,6 +1234,7 @@ HJO_EXPORT void hjo_dielectric_probe(float eta, const float* n3, const float* wi
   hj_scene_desc sc; memset(&sc, 0, sizeof sc); sc.dielectric = &m; sc.num_dielectric = 1;
   hjo_counters c; memset(&c, 0, sizeof c);
   scene_t S; S.sc = &sc; S.tex = NULL; S.ns = S.nq = S.nt = 0; S.use_bvh = 1; S.ctr = &c;
+  no_environment(&S);
   its_t its; memset(&its, 0, sizeof its); its.n = V(n3[0], n3[1], n3[2]);
   v3 wo, ext = V(0, 0, 0); int alive;
   sample_bsdf(&S, (HJ_MAT_DIELECTRIC << HJ_MATERIAL_TAG_SHIFT), V(wi3[0], wi3[1], wi3[2]), &its, rng, &wo, &ext, &alive);
@@ -1130,11 +1247,12 @@ HJO_EXPORT void hjo_dielectric_probe(float eta, const float* n3, const float* wi
  * the tests of render.glsl:121 reject it), [4..6] shadow direction, [7] shadow tMax, [8..10] wo, [11..13] sampleBSDF weight,
  * [14] alive, [15] RNG state bits after the step, [16..18] extinction after the step, [19] emitted radiance .r if emissive. */
 HJO_EXPORT int hjo_shade_probe(const hj_scene_desc* sc, const float* rays, const uint32_t* rng_in, size_t n, float* out) {
-  const int trc = check_textures(sc, g_textures);
+  const int trc = check_scene_inputs(sc);
   if (trc != HJ_OK) return trc;
   hjo_counters c; memset(&c, 0, sizeof c);
   scene_t S; S.sc = sc; S.ns = (uint32_t)sc->num_spheres; S.nq = (uint32_t)sc->num_quads;
   S.nt = (uint32_t)sc->num_triangles; S.use_bvh = 1; S.ctr = &c; S.tex = g_textures;
+  bind_environment(&S);
   for (size_t i = 0; i < n; i++) {
     const float* r = &rays[i * 8];
     float* o = &out[i * 20];
@@ -1178,6 +1296,47 @@ HJO_EXPORT int hjo_texture_lookup(const hj_texture_set* ts, uint32_t t, const fl
   for (size_t i = 0; i < n; i++) {
     const v3 c = texture_rgb(ts, t, uv[2 * i], uv[2 * i + 1]);
     rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+  }
+  return HJ_OK;
+}
+
+/* The probes of the environment set by hjo_set_environment over the textures set by hjo_set_textures, with the output layouts of
+ * hj_debug_env_lookup (rgb n x 3) and hj_debug_env_sample (n x 8: direction, pdf without the selection probability, cell, Le / pdf;
+ * coin = the state's first draw, then the two draws of next-event estimation).  No environment: HJ_ERR_STATE. */
+static int env_probe_scene(scene_t* S, hjo_counters* c) {
+  if (!g_env) return HJ_ERR_STATE;
+  int rc = check_texture_set(g_textures);
+  if (rc != HJ_OK) return rc;
+  rc = check_environment(NULL, g_textures, g_env, g_env_table, g_env_cells);
+  if (rc != HJ_OK) return rc;
+  memset(S, 0, sizeof *S); memset(c, 0, sizeof *c);
+  S->tex = g_textures; S->ctr = c;
+  bind_environment(S);
+  return HJ_OK;
+}
+HJO_EXPORT int hjo_env_lookup(const float* dirs, size_t n, float* rgb) {
+  scene_t S; hjo_counters c;
+  const int rc = env_probe_scene(&S, &c);
+  if (rc != HJ_OK) return rc;
+  for (size_t i = 0; i < n; i++) {
+    const v3 le = env_radiance(&S, ld3(&dirs[3 * i]));
+    rgb[3 * i] = le.x; rgb[3 * i + 1] = le.y; rgb[3 * i + 2] = le.z;
+  }
+  return HJ_OK;
+}
+HJO_EXPORT int hjo_env_sample(const uint32_t* rng_states, size_t n, float* out) {
+  scene_t S; hjo_counters c;
+  const int rc = env_probe_scene(&S, &c);
+  if (rc != HJ_OK) return rc;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t rng = rng_states[i];
+    const float coin = rng_float(&rng);
+    const uint32_t a = rng_uint(&rng), b = rng_uint(&rng);
+    float pdf; uint32_t cell;
+    const v3 d = env_direction(&S, coin, a, b, &pdf, &cell);
+    const v3 w = v_divs(env_radiance(&S, d), pdf);
+    float* o = &out[8 * i];
+    o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = pdf; o[4] = (float)cell; o[5] = w.x; o[6] = w.y; o[7] = w.z;
   }
   return HJ_OK;
 }

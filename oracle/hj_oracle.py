@@ -81,6 +81,10 @@ def lib():
         L.hjo_set_textures.argtypes = [C.POINTER(abi.TextureSet)]
         L.hjo_set_textures.restype = None
         L.hjo_texture_lookup.argtypes = [C.POINTER(abi.TextureSet), C.c_uint32, fp, C.c_size_t, fp]
+        L.hjo_set_environment.argtypes = [C.POINTER(abi.Environment), fp, C.c_size_t]
+        L.hjo_set_environment.restype = None
+        L.hjo_env_lookup.argtypes = [fp, C.c_size_t, fp]
+        L.hjo_env_sample.argtypes = [u32p, C.c_size_t, fp]
         L.hjo_sizeof_counters.restype = C.c_size_t
         assert L.hjo_sizeof_counters() == C.sizeof(Counters)
         _LIB = L
@@ -107,6 +111,54 @@ def textures(compiled, texture_set=None):
         L.hjo_set_textures(None)
 
 
+def env_table(texture_set, env):
+    """The alias table hjo_set_environment takes, from hj_debug_env_distribution (host code, no GPU): (W * H, 4) float32 records
+    (threshold, alias cell as uint32 bits, pdf of the cell, pdf of the alias cell).  None when the distribution is refused - the
+    oracle then refuses the environment itself."""
+    from hijiki_amd import abi, device
+    try:
+        d = device.env_distribution(texture_set, env)
+    except (abi.HijikiError, IndexError, ValueError):
+        return None
+    alias = d["alias"].ravel()
+    pdf = d["pdf"].ravel()
+    rec = np.zeros((alias.size, 4), np.float32)
+    rec[:, 0] = d["alias_prob"].ravel()
+    rec[:, 1] = alias.view(np.float32)
+    rec[:, 2] = pdf
+    rec[:, 3] = pdf[alias]
+    return rec
+
+
+@contextlib.contextmanager
+def environment(compiled, env=None, table=None):
+    """The environment of `compiled` (its `environment`, as device.Renderer.upload_scene takes it) - or `env`, an abi.Environment
+    that overrides it - and its sampling distribution (`table`, default env_table of the scene's texture set) for the oracle calls
+    inside the block (hjo_set_environment); none after it.  Use inside `textures(...)`: the environment is one of its textures."""
+    if env is None:
+        env = getattr(compiled, "environment", None)
+    L = lib()
+    if env is not None and table is None:
+        t = getattr(compiled, "texture_set", None)
+        if t is not None and env.texture < t.num_textures:
+            table = env_table(t, env)
+    if table is not None:
+        table = np.ascontiguousarray(table, np.float32).reshape(-1, 4)
+    L.hjo_set_environment(C.byref(env) if env is not None else None, _fp(table) if table is not None else None,
+                          len(table) if table is not None else 0)
+    try:
+        yield
+    finally:
+        L.hjo_set_environment(None, None, 0)
+
+
+@contextlib.contextmanager
+def scene_inputs(compiled, texture_set=None, env=None, table=None):
+    """textures(...) and environment(...) of one compiled scene."""
+    with textures(compiled, texture_set), environment(compiled, env, table):
+        yield
+
+
 def _status(name, rc):
     """A refusal as abi.HijikiError (a RuntimeError) carrying the status."""
     if rc != 0:
@@ -115,8 +167,8 @@ def _status(name, rc):
 
 
 def render_blocks(compiled, blocks, width, height, opts=None, nthreads=None, accum=None):
-    """Render `blocks` (ctypes array of ImageBlock) in order, with the compiled scene's image textures if it has any.  Returns
-    (accum[H,W,4], counters dict, seconds)."""
+    """Render `blocks` (ctypes array of ImageBlock) in order, with the compiled scene's image textures and environment if it has
+    any.  Returns (accum[H,W,4], counters dict, seconds)."""
     from hijiki_amd import abi
     L = lib()
     opts = opts or abi.RenderOpts.default()
@@ -124,7 +176,7 @@ def render_blocks(compiled, blocks, width, height, opts=None, nthreads=None, acc
     if accum is None:
         accum = np.zeros((height, width, 4), np.float32)
     ctr, secs = Counters(), C.c_double(0)
-    with textures(compiled):
+    with scene_inputs(compiled):
         rc = L.hjo_render_blocks(C.byref(compiled.desc), blocks, len(blocks), C.byref(opts), width, height, _fp(accum),
                                  nthreads, C.byref(ctr), C.byref(secs))
     _status("hjo_render_blocks", rc)
@@ -164,7 +216,7 @@ def shade_probe(compiled, rays, rng_states):
     rays = np.ascontiguousarray(rays, np.float32)
     rng = np.ascontiguousarray(rng_states, np.uint32)
     out = np.zeros((len(rays), 20), np.float32)
-    with textures(compiled):
+    with scene_inputs(compiled):
         _status("hjo_shade_probe", lib().hjo_shade_probe(C.byref(compiled.desc), _fp(rays), rng.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                          len(rays), _fp(out)))
     return out, out[:, 0].copy().view(np.int32), out[:, 15].copy().view(np.uint32)
@@ -176,6 +228,25 @@ def texture_lookup(texture_set, texture, uv):
     uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
     out = np.zeros((len(uv), 3), np.float32)
     _status("hjo_texture_lookup", lib().hjo_texture_lookup(C.byref(texture_set), int(texture), _fp(uv), len(uv), _fp(out)))
+    return out
+
+
+def env_lookup(compiled, dirs, env=None, table=None):
+    """hjo_env_lookup: the radiance the environment of `compiled` sends along (n, 3) directions -> (n, 3) float32."""
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    out = np.zeros((len(d), 3), np.float32)
+    with scene_inputs(compiled, env=env, table=table):
+        _status("hjo_env_lookup", lib().hjo_env_lookup(_fp(d), len(d), _fp(out)))
+    return out
+
+
+def env_sample(compiled, rng_states, env=None, table=None):
+    """hjo_env_sample: n uint32 RNG states -> (n, 8) float32: direction xyz, pdf, texel index, Le / pdf rgb (the layout of
+    hj_debug_env_sample)."""
+    s = np.ascontiguousarray(rng_states, np.uint32).reshape(-1)
+    out = np.zeros((len(s), 8), np.float32)
+    with scene_inputs(compiled, env=env, table=table):
+        _status("hjo_env_sample", lib().hjo_env_sample(s.ctypes.data_as(C.POINTER(C.c_uint32)), len(s), _fp(out)))
     return out
 
 
@@ -192,7 +263,7 @@ def integrate_block(compiled, block, opts=None):
     opts = opts or abi.RenderOpts.default()
     out = np.zeros((block.dimension[1], block.dimension[0], 8), np.float32)
     ctr = Counters()
-    with textures(compiled):
+    with scene_inputs(compiled):
         _status("hjo_integrate_block", lib().hjo_integrate_block(C.byref(compiled.desc), C.byref(block), C.byref(opts), _fp(out),
                                                                  C.byref(ctr)))
     return out, ctr.as_dict()
@@ -200,7 +271,8 @@ def integrate_block(compiled, block, opts=None):
 
 def logged_rays(compiled, blocks, opts=None):
     """Every ray the oracle traces for `blocks` (hjo_set_ray_log around hjo_integrate_block, single-threaded): (n, 11) float32 =
-    o, d, tMin, tMax, kind (0 closest-hit, 1 shadow), id of the shape hit or -1, index of the emitter a shadow ray aims at (else -1).  Directions are whatever the reference's
+    o, d, tMin, tMax, kind (0 closest-hit, 1 shadow), id of the shape hit or -1, index of the emitter a shadow ray aims at (8: the
+    environment; else -1).  Directions are whatever the reference's
     arithmetic made them - not always unit vectors."""
     import tempfile
     L = lib()

@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 
+import env_scenes
 import scenes
 import texture_scenes
 from hijiki_amd import abi, device, host
@@ -34,18 +35,39 @@ def source_seed():
     return int.from_bytes(h.digest()[:6], "little")
 
 
+def random_environment(s, rng, emitters=True):
+    """A random environment on the host.Scene `s`: random size (rows and columns of one among them), filter, scale (sometimes with
+    a zero channel) and select_prob (1 without emitters; None = the host's default)."""
+    H, W = [(1, 1), (1, 7), (5, 1), (9, 13), (16, 32), (33, 17)][int(rng.integers(0, 6))]
+    scale = [float(v) for v in rng.uniform(0.2, 3.0, 3)]
+    if rng.random() < 0.2 and H * W > 1:            # (never on one texel: the channel left might be its zero one)
+        scale[int(rng.integers(0, 3))] = 0.0
+    p = [None, 0.125, 0.5, 0.875, 1.0][int(rng.integers(0, 5))] if emitters else None
+    s.set_environment(s.add_texture(env_scenes.random_env(rng, H, W), int(rng.integers(0, 2))), tuple(scale), p)
+    return s
+
+
 def fuzz_scene(r, rng):
-    kind = int(rng.integers(0, 6))
+    kind = int(rng.integers(0, 7))
+    lit = rng.random() < 0.4                        # an environment (the upload and the oracle take the scene's own)
     if kind == 0:
-        cs = scenes.random_scene(int(rng.integers(0, 10000)))
+        s = scenes.random_scene_builder(int(rng.integers(0, 10000)))
+        cs = (random_environment(s, rng) if lit else s).compile()
     elif kind == 1:
         cs = scenes.random_cluster_scene(int(rng.integers(0, 10000)), scale=float(rng.choice([1.0, 1.0, 0.1, 7.0])))
     elif kind == 2:
-        cs = host.Scene.synthetic(host.SYNTH_CBOX_SPHERES, mesh_triangles=int(rng.choice([320, 1280]))).compile()
+        s = host.Scene.synthetic(host.SYNTH_CBOX_SPHERES, mesh_triangles=int(rng.choice([320, 1280])))
+        cs = (random_environment(s, rng) if lit else s).compile()
     elif kind == 3:
-        cs = host.Scene.synthetic(host.SYNTH_CBOX_MESH, mesh_triangles=int(rng.choice([2000, 20000]))).compile()
+        s = host.Scene.synthetic(host.SYNTH_CBOX_MESH, mesh_triangles=int(rng.choice([2000, 20000])))
+        cs = (random_environment(s, rng) if lit else s).compile()
     elif kind == 4:
         cs = scenes.nasty_scene(int(rng.integers(0, 10000)))
+    elif kind == 6:                                 # the open sky: no emitters (select_prob 1) or one quad light
+        H, W = [(1, 1), (4, 8), (9, 13)][int(rng.integers(0, 3))]
+        light = bool(rng.random() < 0.5)
+        cs = env_scenes.cluster_scene(env_scenes.random_env(rng, H, W), int(rng.integers(0, 2)), tuple(float(v) for v in rng.uniform(0.2, 3.0, 3)),
+                                      select_prob=float(rng.choice([0.125, 0.5, 0.875])) if light else None, light=light)
     elif rng.random() < 0.7:                        # image textures (the upload and the oracle take the scene's texture set)
         cs = texture_scenes.random_textured_scene(int(rng.integers(0, 10000)), big=rng.random() < 0.3)
     else:

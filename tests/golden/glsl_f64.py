@@ -33,7 +33,9 @@ def _view(ptr, count, dtype, cols):
 class Scene:
     """float64 copies of the scene buffers the shaders bind (scene.glsl:1-42, triangle.glsl:1-12, material.glsl:1-15)."""
 
-    def __init__(self, cs):
+    def __init__(self, cs, env_table=None):
+        """env_table: for a scene with an environment, its sampling distribution as (W * H, 4) float32 records (threshold, alias
+        cell as uint32 bits, pdf, pdf of the alias cell) - data, as the oracle takes it (DESIGN.md "Environment lighting")."""
         d = cs.desc
         f = lambda p, n, k: _view(p, n, np.float32, k).astype(np.float64)
         bu = _view(d.bvh, d.num_bvh_nodes, np.uint32, 8)
@@ -67,6 +69,14 @@ class Scene:
                 r = t.textures[i]
                 first, w, h = int(r.first_texel), int(r.width), int(r.height)
                 self.textures.append((texels[first:first + w * h].reshape(h, w, 4), int(r.filter)))
+        self.env = None                         # (texture index, scale rgb, select_prob)
+        e = getattr(cs, "environment", None)
+        if e is not None:
+            rec = np.ascontiguousarray(env_table, np.float32).reshape(-1, 4)
+            self.env = (int(e.texture), np.array(e.scale[:3], np.float64), float(e.select_prob))
+            self.env_thr = rec[:, 0].astype(np.float64)
+            self.env_alias = rec[:, 1].copy().view(np.uint32).astype(np.int64)
+            self.env_pdf, self.env_pdf_alias = rec[:, 2].astype(np.float64), rec[:, 3].astype(np.float64)
 
 
 # ------------------------------------------------------------------ rand.glsl
@@ -315,10 +325,64 @@ def sample_shape(sc, shape, rng, idx):
     return p, nn, pdf
 
 
+def env_radiance(sc, d):
+    """DESIGN.md "Environment lighting": Le(d) = scale * texture(env, u, v), lat-long with +y up; u = 0 where the longitude is
+    undefined (the definition's atan2(0, 0) is NaN)."""
+    t, scale, _ = sc.env
+    with np.errstate(invalid="ignore"):
+        u = 0.5 + np.arctan2(d[:, 2], d[:, 0]) / (2 * PI)
+        r = np.sqrt(d[:, 0] * d[:, 0] + d[:, 2] * d[:, 2])
+        v = 0.5 + np.arctan2(d[:, 1], r) / PI
+    pole = (d[:, 0] == 0) & (d[:, 2] == 0)
+    u = np.where(pole | np.isnan(u), 0.0, u)
+    v = np.where(pole & (d[:, 1] == 0), np.nan, v)
+    return texture(*sc.textures[t], u, v) * scale
+
+
+def sample_environment(sc, coin, a, b):
+    """One direction per path from the alias table: column from draw a, the coin keeps it or takes its alias, draw b places the
+    direction in the cell (high 16 bits: phi, low 16: sin(latitude), each (k + 1/2) / 65536) -> (direction, pdf, cell)."""
+    H, W = sc.textures[sc.env[0]][0].shape[:2]
+    col = ((a.astype(np.uint64) * np.uint64(W * H)) >> np.uint64(32)).astype(np.int64)
+    alias = coin >= sc.env_thr[col]
+    cell = np.where(alias, sc.env_alias[col], col)
+    pdf = np.where(alias, sc.env_pdf_alias[col], sc.env_pdf[col])
+    x, y = cell % W, cell // W
+    fu = ((b >> np.uint32(16)).astype(np.float64) + 0.5) / 65536.0
+    fv = ((b & np.uint32(0xFFFF)).astype(np.float64) + 0.5) / 65536.0
+    phi = 2 * PI * ((x + fu) / W - 0.5)
+    y0, y1 = np.cos(PI * y / H), np.cos(PI * (y + 1) / H)
+    ys = y1 + fv * (y0 - y1)
+    rr = np.sqrt(np.maximum(0.0, 1 - ys * ys))
+    return np.stack([rr * np.cos(phi), ys, rr * np.sin(phi)], 1), pdf, cell
+
+
 def sample_emitter(sc, ref, rng, idx):
-    """scene.glsl:54-89 -> (importance, shadow direction, shadow tMax); shadow tMin is 2 eps."""
+    """scene.glsl:54-89 -> (importance, shadow direction, shadow tMax); shadow tMin is 2 eps.  With an environment the selection
+    draw picks it with probability p_env (shadow ray to infinity); the others' draw is remapped and their emitter's probability
+    scaled by 1 - p_env."""
+    if sc.env is None:
+        return _sample_area_emitter(sc, ref, rng, idx, rng.uniform(idx), 1.0)
     n = len(idx)
     xi = rng.uniform(idx)
+    pe = sc.env[2]
+    imp, dirv, tmax = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
+    pick = np.ones(n, bool) if pe == 1.0 else xi < pe
+    if pick.any():
+        a, b = rng.uint(idx[pick]), rng.uint(idx[pick])
+        dd, pdf, _ = sample_environment(sc, xi[pick] / pe, a, b)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            imp[pick] = env_radiance(sc, dd) / (pe * pdf)[:, None]
+        dirv[pick], tmax[pick] = dd, np.inf
+    rest = ~pick
+    if rest.any():
+        imp[rest], dirv[rest], tmax[rest] = _sample_area_emitter(sc, ref[rest], rng, idx[rest], (xi[rest] - pe) / (1.0 - pe), 1.0 - pe)
+    return imp, dirv, tmax
+
+
+def _sample_area_emitter(sc, ref, rng, idx, xi, share):
+    """The area-emitter part of scene.glsl:54-89 for the selection draws xi; share = the probability left to the area emitters."""
+    n = len(idx)
     if len(sc.em_pdf) == 0:            # the reference reads emitters[0] out of bounds; defined as "no light" (DESIGN.md 2)
         rng.uint(idx); rng.uint(idx)
         return np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
@@ -337,7 +401,7 @@ def sample_emitter(sc, ref, rng, idx):
     with np.errstate(invalid="ignore", divide="ignore"):
         dirv = dirv / dist[:, None]
         cos_t = -_dot(dirv, nn)
-        pdf = sc.em_pdf[em] * spdf * dist * dist / cos_t                     # :86
+        pdf = sc.em_pdf[em] * share * spdf * dist * dist / cos_t             # :86
         imp = np.where((cos_t < 0)[:, None], 0.0, power / pdf[:, None])
     return imp, dirv, dist - EPS
 
@@ -475,6 +539,10 @@ def integrate(sc, o, d, rng_state, max_bounces=1000, rr_start=4, use_bvh=True):
         its = intersect_scene(sc, o[act], d[act], tmin[act], np.full(act.size, np.inf), use_bvh)
         hit = its.id >= 0
         a = act[hit]                                                         # :94-96
+        if sc.env is not None and not hit.all():                             # a ray that left the scene (no counterpart upstream)
+            m = act[~hit]
+            m = m[discrete[m]]
+            total[m] += np.where(ext[m] != 0, 0.0, T[m] * env_radiance(sc, d[m]))
         if a.size == 0:
             break
         iid, ip, inn = its.id[hit], its.p[hit], its.n[hit]

@@ -74,7 +74,12 @@ def furnace_masks(W, H):
 
 
 def random_scene(seed):
-    """Randomised scene through the whole Scene API: random mixes of triangles (a small random soup with random shading
+    return random_scene_builder(seed).compile()
+
+
+def random_scene_builder(seed):
+    """random_scene before compile() (a host.Scene: tests add textures or an environment to it).
+    Randomised scene through the whole Scene API: random mixes of triangles (a small random soup with random shading
     normals), spheres and quads, all five material kinds (dielectrics with and without extinction, several lights of
     different shape kinds), random camera."""
     rng = np.random.default_rng(1000 + seed)
@@ -109,7 +114,7 @@ def random_scene(seed):
     for _ in range(int(rng.integers(8, 30))):
         a, b, c = (int(x) for x in rng.choice(nv, 3, replace=False))
         s.add_triangle(base + a, base + b, base + c, int(rng.choice(mats + lights[1:])))
-    return s.compile()
+    return s
 
 
 def random_cluster_scene(seed, scale=1.0):
