@@ -84,6 +84,7 @@ int dev_alloc(hj_context* ctx, DevBuf& b, size_t bytes) {
 
 void release_scene(hj_context* ctx) {
   ctx->scene_bufs.bufs.clear();
+  ctx->update = hj_context::SceneUpdate{};
   ctx->num_textures = 0;
   ctx->have_scene = false;
 }
@@ -114,7 +115,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (6u << 8) | 0u; }   // 0.6.0: hj_refit_bvh_device
+uint32_t hj_version(void) { return (0u << 16) | (7u << 8) | 0u; }   // 0.7.0: hj_scene_update_shapes
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

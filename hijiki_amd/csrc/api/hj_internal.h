@@ -7,7 +7,9 @@
 //   api/render.hip        the launches of kernels/hj_kernels.h (the only unit that includes them), walk-statistics readers
 //   api/render_calls.hip  batch slots, render calls, hj_reserve, the pipeline, the worker thread, probes   (no kernels)
 //   api/comm.hip          RCCL (dlopen), hj_comm_*, hj_reduce_framebuffers
-//   api/lbvh_build.hip    hj_build_bvh_device, hj_refit_bvh_device: host half of kernels/hj_lbvh.h
+//   api/lbvh_build.hip    hj_build_bvh_device, hj_refit_bvh_device: host half of kernels/hj_lbvh.h (the only unit that includes it;
+//                         api/refit_pass.hpp: the refit's stages for a caller that brings its own link set)
+//   api/scene_update.hip  hj_scene_update_shapes: the uploaded scene's boxes, triangle and emitter records recomputed in place
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
 //   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
 //   api/environment.hip   environment lighting: the checks and the alias table of hj_scene_upload_env, hj_debug_env_*
@@ -167,6 +169,28 @@ struct hj_context {
   hj::DeviceScene scene{};
   DevBufs scene_bufs;
   uint32_t num_textures = 0;             // of the scene (scene.textures holds them: kernels/hj_texture.h)
+  // hj_scene_update_shapes (api/scene_update.hip).  What the upload keeps for it: per node i of the uploaded array where its record
+  // went in the re-laid-out copy (x) and where its guard record is (y), kNoRecord for none - a collapsed node, a pair's leaf, a leaf
+  // without a guard (record root2 + i of the second copy needs no map).  What the first update adds: its own link set (the uploaded
+  // topology's links, parents and counters - hj_context::refit_links is another caller's), the scratch records of the bottom-up pass,
+  // staging for shape arrays that come from the host.  Every pointer is a buffer of scene_bufs: release_scene forgets them.
+  struct SceneUpdate {
+    static constexpr uint32_t kNoRecord = 0xFFFFFFFFu;
+    const uint2* node_map = nullptr;     // [nodes0]
+    size_t nodes0 = 0;                   // records of the uploaded array
+    size_t num_vertices = 0, num_pairs = 0;
+    bool ready = false;                  // the fields below are allocated and the links verified
+    uint2* links = nullptr;              // [nodes0] (shape_index, exit_index)
+    uint32_t* parent = nullptr;          // [nodes0]
+    uint32_t* arrived = nullptr;         // [nodes0] zero between passes
+    float4* scratch = nullptr;           // [2 * nodes0] the refitted skip-link records
+    double* partial = nullptr;           // the cost's partial sums, one per 256 records
+    uint32_t* verdict = nullptr;         // [4] the check kernel's word
+    float4* in_spheres = nullptr;        // staging of host arrays
+    float4* in_quads = nullptr;
+    hj_vertex* in_vertices = nullptr;
+    hj_emitter* in_emitters = nullptr;
+  } update;
 
   // framebuffer
   float4* accum = nullptr;
@@ -284,6 +308,9 @@ int upload_environment(DevBufs& bufs, const hj_texture_set* t, const hj_environm
 int validate_textures(hj_context* ctx, const hj_texture_set* t);             // api/texture.hip
 int upload_textures(DevBufs& bufs, const hj_texture_set* t, const float4** out);
 void release_scene(hj_context* ctx);
+// api/scene_upload.hip: the light-shaft grid of `s` (all arrays on the host, or the tree at d_tree) into a new buffer of `bufs` and
+// d's lg_* fields; no grid (by size, by HJ_LIGHT_GRID, or because none could be proven) leaves d alone and returns HJ_OK
+int upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, const hj_bvh_node* d_tree, hj::DeviceScene& d);
 void release_slot(hj_context::BatchSlot& sl);
 void release_batch(hj_context* ctx);
 int sync_all(hj_context* ctx);                       // drains the context's streams (api/context.hip)

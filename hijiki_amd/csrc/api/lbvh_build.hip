@@ -1,6 +1,7 @@
 // hj_build_bvh_device: the host half of the device BVH build (kernels/hj_lbvh.h) - SURVEY.md 8(f) #2.
 #include "hj_internal.h"
 #include "tree_vote.hpp"
+#include "refit_pass.hpp"
 #include "../kernels/hj_lbvh.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -8,6 +9,55 @@
 #pragma clang fp contract(off)
 
 using namespace hjapi;
+
+namespace hjapi {
+
+int refit_check_links(hj_context* ctx, const RefitLinks& l, uint32_t* zeroed, const char* who) {
+  hipStream_t st = ctx->stream;
+  const dim3 blk(256), grid((l.N + 255u) / 256u);
+  hj::lbvh::Refit r{};
+  r.links = l.links; r.N = l.N; r.n = l.n; r.parent = l.parent; r.arrived = l.arrived;
+  r.nparents = zeroed; r.seen = zeroed + l.N; r.err = zeroed + l.N + l.n;
+  HJ_HIP(ctx, hipMemsetAsync(zeroed, 0, sizeof(uint32_t) * ((size_t)l.N + l.n + 1), st));
+  HJ_HIP(ctx, hipMemsetAsync(r.err + 1, 0xFF, sizeof(uint32_t) * 3, st));
+  hipLaunchKernelGGL(hj::lbvh::k_rf_links<true>, grid, blk, 0, st, r);
+  hipLaunchKernelGGL(hj::lbvh::k_rf_check, grid, blk, 0, st, r);
+  HJ_HIP(ctx, hipStreamSynchronize(st));                   // (the verdict decides what follows)
+  HJ_HIP(ctx, hipGetLastError());
+  uint32_t err[4] = {0, 0, 0, 0};
+  HJ_HIP(ctx, hipMemcpy(err, r.err, sizeof err, hipMemcpyDeviceToHost));
+  if (err[0] & hj::lbvh::kRfNotATree) return set_error(ctx, HJ_ERR_INVALID, "%s: the links are not a pre-order skip-link tree", who);
+  if (err[0] & hj::lbvh::kRfShapeRange) return set_error(ctx, HJ_ERR_INVALID, "%s: a leaf holds shape %u, the scene has %u", who, err[2], l.n);
+  if (err[0] & hj::lbvh::kRfShapeTwice) return set_error(ctx, HJ_ERR_INVALID, "%s: shape %u is in two leaves", who, err[3]);
+  if (err[0] & hj::lbvh::kRfShapeMissing) return set_error(ctx, HJ_ERR_INVALID, "%s: shape %u is in no leaf", who, err[1]);
+  return HJ_OK;
+}
+
+void refit_enqueue(hj_context* ctx, const RefitLinks& l, const RefitShapes& s, float4* out, bool tiled) {
+  hj::lbvh::Refit r{};
+  r.links = l.links; r.N = l.N; r.n = l.n; r.parent = l.parent; r.arrived = l.arrived;
+  const hj::lbvh::Shapes sh{s.spheres, s.quads, s.triangles, s.vertices, s.ns, s.nq, s.nt};
+  const dim3 blk(256);
+  if (tiled)
+    hipLaunchKernelGGL(hj::lbvh::k_rf_tiled, dim3((l.N + hj::lbvh::kRfTile - 1) / hj::lbvh::kRfTile), blk, 0, ctx->stream, r, sh, out);
+  else
+    hipLaunchKernelGGL(hj::lbvh::k_rf_climb, dim3((l.N + 255u) / 256u), blk, 0, ctx->stream, r, sh, out);
+}
+
+void refit_enqueue_cost(hj_context* ctx, const float4* records, uint32_t N, double* partial) {
+  hipLaunchKernelGGL(hj::lbvh::k_rf_cost, dim3((N + 255u) / 256u), dim3(256), 0, ctx->stream, records, N, partial);
+}
+
+double refit_cost(const std::vector<double>& partial, const hj_bvh_node& root) {
+  double sum = 0.0;
+  for (double p : partial) sum += p;                         // index order: the same double for the same records
+  const double dx = (double)root.aabb_max[0] - (double)root.aabb_min[0], dy = (double)root.aabb_max[1] - (double)root.aabb_min[1],
+               dz = (double)root.aabb_max[2] - (double)root.aabb_min[2];
+  const double area = (dx >= 0 && dy >= 0 && dz >= 0) ? dx * dy + dy * dz + dz * dx : 0.0;
+  return area > 0.0 ? sum / area : 0.0;
+}
+
+}  // namespace hjapi
 
 extern "C" {
 
@@ -554,9 +604,8 @@ int hj_refit_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   DevBufs bufs(ctx);
   hipStream_t st = ctx->stream;
   const uint32_t N = (uint32_t)total;
-  const dim3 blk(256), grid((N + 255u) / 256u);
-  hj::lbvh::Refit r{};
-  r.N = N; r.n = (uint32_t)n;
+  RefitLinks rl{};
+  rl.N = N; rl.n = (uint32_t)n;
   if (from_host) {
     // the links of the host's array (8 of its 32 bytes per record), checked on the device BEFORE anything of the context changes;
     // the same kernel derives what the refits over these links reuse: parents, and counters that are zero between passes
@@ -565,33 +614,22 @@ int hj_refit_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
     uint2* new_links = nullptr;
     uint32_t* zeroed = nullptr;                              // nparents [N], seen [n], err [4]: one allocation
     HJ_TRY(bufs.alloc(new_links, total));
-    HJ_TRY(bufs.alloc(r.parent, total));
-    HJ_TRY(bufs.alloc(r.arrived, total));
+    HJ_TRY(bufs.alloc(rl.parent, total));
+    HJ_TRY(bufs.alloc(rl.arrived, total));
     HJ_TRY(bufs.alloc(zeroed, total + n + 4));
-    r.links = new_links; r.nparents = zeroed; r.seen = zeroed + total; r.err = zeroed + total + n;
+    rl.links = new_links;
     HJ_HIP(ctx, hipMemcpy(new_links, links.data(), sizeof(uint2) * total, hipMemcpyHostToDevice));
-    HJ_HIP(ctx, hipMemsetAsync(zeroed, 0, sizeof(uint32_t) * (total + n + 1), st));
-    HJ_HIP(ctx, hipMemsetAsync(r.err + 1, 0xFF, sizeof(uint32_t) * 3, st));
-    hipLaunchKernelGGL(hj::lbvh::k_rf_links<true>, grid, blk, 0, st, r);
-    hipLaunchKernelGGL(hj::lbvh::k_rf_check, grid, blk, 0, st, r);
-    HJ_HIP(ctx, hipStreamSynchronize(st));                   // (the verdict decides what follows)
-    HJ_HIP(ctx, hipGetLastError());
-    uint32_t err[4] = {0, 0, 0, 0};
-    HJ_HIP(ctx, hipMemcpy(err, r.err, sizeof err, hipMemcpyDeviceToHost));
-    if (err[0] & hj::lbvh::kRfNotATree) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: the links are not a pre-order skip-link tree");
-    if (err[0] & hj::lbvh::kRfShapeRange) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: a leaf holds shape %u, the scene has %zu", err[2], n);
-    if (err[0] & hj::lbvh::kRfShapeTwice) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: shape %u is in two leaves", err[3]);
-    if (err[0] & hj::lbvh::kRfShapeMissing) return set_error(ctx, HJ_ERR_INVALID, "hj_refit_bvh_device: shape %u is in no leaf", err[1]);
+    HJ_TRY(refit_check_links(ctx, rl, zeroed, "hj_refit_bvh_device"));
     clock.mark("links to the device, checks");
     kept.links = bufs.take(new_links);                       // from here on these are the kept links, whatever happens below
-    kept.parent = bufs.take(r.parent); kept.arrived = bufs.take(r.arrived);
+    kept.parent = bufs.take(rl.parent); kept.arrived = bufs.take(rl.arrived);
     kept.shapes = n; kept.valid = kept.links.p != nullptr;
   }
-  r.links = static_cast<const uint2*>(kept.links.p);
-  r.parent = static_cast<uint32_t*>(kept.parent.p); r.arrived = static_cast<uint32_t*>(kept.arrived.p);
+  rl.links = static_cast<const uint2*>(kept.links.p);
+  rl.parent = static_cast<uint32_t*>(kept.parent.p); rl.arrived = static_cast<uint32_t*>(kept.arrived.p);
   ctx->resident.release();                                   // (a tree nobody took over: the refitted one replaces it)
   void *keep_sp = nullptr, *keep_qd = nullptr, *keep_tr = nullptr, *keep_vx = nullptr;
-  hj::lbvh::Shapes sh{};
+  RefitShapes sh{};
   {
     float4* sp = nullptr; float4* qd = nullptr; hj_triangle* tr = nullptr; hj_vertex* vx = nullptr;
     HJ_TRY(bufs.alloc(sp, s->num_spheres));
@@ -608,35 +646,26 @@ int hj_refit_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
   }
   hj_bvh_node* d_out = nullptr;
   double* d_partial = nullptr;
+  const size_t num_partial = refit_cost_partials(N);
   HJ_TRY(bufs.alloc(d_out, total));
-  if (out_cost) HJ_TRY(bufs.alloc(d_partial, grid.x));
+  if (out_cost) HJ_TRY(bufs.alloc(d_partial, num_partial));
   clock.mark("allocations + shape upload");
   // ONE launch: leaf boxes, inner boxes, records (HJ_REFIT_TILED: which form - DESIGN.md 4, "Refit")
-  if (tn.refit_tiled != 0)
-    hipLaunchKernelGGL(hj::lbvh::k_rf_tiled, dim3((N + hj::lbvh::kRfTile - 1) / hj::lbvh::kRfTile), blk, 0, st, r, sh, reinterpret_cast<float4*>(d_out));
-  else
-    hipLaunchKernelGGL(hj::lbvh::k_rf_climb, grid, blk, 0, st, r, sh, reinterpret_cast<float4*>(d_out));
+  refit_enqueue(ctx, rl, sh, reinterpret_cast<float4*>(d_out), tn.refit_tiled != 0);
   clock.mark(tn.refit_tiled != 0 ? "bottom-up pass (tiled)" : "bottom-up pass (plain climb)");
-  if (out_cost) hipLaunchKernelGGL(hj::lbvh::k_rf_cost, grid, blk, 0, st, reinterpret_cast<const float4*>(d_out), N, d_partial);
+  if (out_cost) refit_enqueue_cost(ctx, reinterpret_cast<const float4*>(d_out), N, d_partial);
   if (out_nodes) HJ_HIP(ctx, hipMemcpyAsync(out_nodes, d_out, sizeof(hj_bvh_node) * total, hipMemcpyDeviceToHost, st));
   HJ_HIP(ctx, hipStreamSynchronize(st));
   HJ_HIP(ctx, hipGetLastError());
   std::vector<double> partial;
   hj_bvh_node root{};
   if (out_cost) {                                            // (synchronous copies: nothing is in flight into this frame's storage)
-    partial.resize(grid.x);
-    HJ_HIP(ctx, hipMemcpy(partial.data(), d_partial, sizeof(double) * grid.x, hipMemcpyDeviceToHost));
+    partial.resize(num_partial);
+    HJ_HIP(ctx, hipMemcpy(partial.data(), d_partial, sizeof(double) * num_partial, hipMemcpyDeviceToHost));
     HJ_HIP(ctx, hipMemcpy(&root, d_out, sizeof root, hipMemcpyDeviceToHost));
   }
   clock.mark("cost, records to the host");
-  if (out_cost) {
-    double sum = 0.0;
-    for (double p : partial) sum += p;                       // index order: the same double for the same records
-    const double dx = (double)root.aabb_max[0] - (double)root.aabb_min[0], dy = (double)root.aabb_max[1] - (double)root.aabb_min[1],
-                 dz = (double)root.aabb_max[2] - (double)root.aabb_min[2];
-    const double area = (dx >= 0 && dy >= 0 && dz >= 0) ? dx * dy + dy * dz + dz * dx : 0.0;
-    *out_cost = area > 0.0 ? sum / area : 0.0;
-  }
+  if (out_cost) *out_cost = refit_cost(partial, root);
   {
     hj_context::ResidentTree& rt = ctx->resident;
     rt.nodes = bufs.take(d_out); rt.spheres = bufs.take(keep_sp); rt.quads = bufs.take(keep_qd);

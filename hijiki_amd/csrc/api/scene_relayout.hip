@@ -59,14 +59,7 @@ __global__ void k_rl_triangles(const hj_triangle* __restrict__ tris, const hj_ve
                                float4* __restrict__ isect, float4* __restrict__ shade) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nt) return;
-  const hj_vertex A = verts[tris[i].v[0]], B = verts[tris[i].v[1]], C = verts[tris[i].v[2]];
-  isect[3 * (size_t)i + 0] = make_float4(A.pos[0], A.pos[1], A.pos[2], 0.f);
-  isect[3 * (size_t)i + 1] = make_float4(B.pos[0] - A.pos[0], B.pos[1] - A.pos[1], B.pos[2] - A.pos[2], 0.f);
-  isect[3 * (size_t)i + 2] = make_float4(C.pos[0] - A.pos[0], C.pos[1] - A.pos[1], C.pos[2] - A.pos[2], 0.f);
-  shade[4 * (size_t)i + 0] = make_float4(A.normal[0], A.normal[1], A.normal[2], A.u);
-  shade[4 * (size_t)i + 1] = make_float4(B.normal[0], B.normal[1], B.normal[2], B.u);
-  shade[4 * (size_t)i + 2] = make_float4(C.normal[0], C.normal[1], C.normal[2], C.u);
-  shade[4 * (size_t)i + 3] = make_float4(A.v, B.v, C.v, 0.f);
+  tri_records(tris, verts, i, isect, shade);
 }
 
 __global__ void k_rl_init(RL r) {
@@ -266,6 +259,12 @@ __global__ void k_rl_records(RL r, float4* __restrict__ dev) {
   rec[1] = make_float4(nd.aabb_max[0], nd.aabb_max[1], nd.aabb_max[2], __uint_as_float(b));
 }
 
+// where every node of the uploaded array went (hj_scene_update_shapes); this route makes no guard records
+__global__ void k_rl_node_map(RL r, uint2* __restrict__ where) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < r.N) where[i] = make_uint2(r.del[i] ? kNone : r.map[i], kNone);
+}
+
 }  // namespace
 
 namespace hjapi {
@@ -442,6 +441,10 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
   hipLaunchKernelGGL(k_rl_records, grid, blk, 0, st, r, dev);
   hipLaunchKernelGGL(k_rl_records2, grid, blk, 0, st, r, dev, m_all);
   out.nodes = dev;
+  uint2* where = nullptr;
+  HJ_TRY(keep.alloc(where, N));
+  hipLaunchKernelGGL(k_rl_node_map, grid, blk, 0, st, r, where);
+  out.node_map = where;
   uint32_t root = 0;
   HJ_HIP(ctx, hipMemcpyAsync(&root, r.map, 4, hipMemcpyDeviceToHost, st));
   HJ_HIP(ctx, hipStreamSynchronize(st));

@@ -412,6 +412,17 @@ int relayout_on_host(hj_context* ctx, const hj_scene_desc* s, const Tuning& tn, 
       rec[1] = make_float4(nd.aabb_max[0], nd.aabb_max[1], nd.aabb_max[2], __builtin_bit_cast(float, b));
     }
     clock.mark("device records");
+    {   // where every node of the uploaded array went (hj_scene_update_shapes): its record, its guard's record
+      constexpr uint32_t none = hj_context::SceneUpdate::kNoRecord;
+      std::vector<uint2> where(N0);
+      for (size_t i = 0; i < N0; i++) {
+        const size_t g = gidx.empty() ? i : gidx[i];
+        // (a guard is the record in front of its leaf in `guarded`: an inner node over one child, which the collapse never drops)
+        const bool has_guard = !gidx.empty() && g != (i ? (size_t)gidx[i - 1] + 1 : 0);
+        where[i] = make_uint2(del[g] ? none : map[g], has_guard && !del[g - 1] ? map[g - 1] : none);
+      }
+      HJ_TRY(upload(keep, where.data(), where.size(), &out.node_map));
+    }
     HJ_TRY(upload(keep, pairs.data(), pairs.size(), &out.tri_pair));
     out.num_pairs = (uint32_t)(pairs.size() / 6);
     out.num_nodes = (uint32_t)(M_all + N0);
@@ -492,12 +503,14 @@ std::vector<float4> emitter_records(const hj_scene_desc* s) {
   return rec;
 }
 
+}  // namespace
+
 // Light-shaft visibility grid (api/light_grid.cpp): which next-event shadow rays are unoccluded whatever happens.  HJ_LIGHT_GRID =
 // cells per axis (0: none).  Default: 64 up to HJ_STREAM_MIN_NODES (300 000) tree nodes, none beyond - on the 1 M-triangle scene
 // a third of the shadow rays is proven free and the frame rate does not move (they are the cheap rays: a dozen steps on
 // LDS-resident nodes against the mesh rays' seventeen cold ones), while the build costs 50 ms of start-up there.
 // d_tree: the tree when it is on the device only (the grid is host code: the tree comes back for it).
-int upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, const hj_bvh_node* d_tree, hj::DeviceScene& d) {
+int hjapi::upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, const hj_bvh_node* d_tree, hj::DeviceScene& d) {
   const int res = Tuning::pick(tn.light_grid, s->num_bvh_nodes >= (size_t)tn.stream_min_nodes ? 0 : 64);
   if (res < 2) return HJ_OK;
   LightGrid lg;
@@ -524,8 +537,6 @@ int upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, c
                                      lg.res, lg.cells_surface, lg.cells_planar, lg.pairs_clear);
   return HJ_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -624,6 +635,11 @@ int hj_scene_upload_env(hj_context* ctx, const hj_scene_desc* s, const hj_textur
     rt.release();
   }
   ctx->scene = d;
+  ctx->update = hj_context::SceneUpdate{};
+  ctx->update.node_map = ro.node_map;
+  ctx->update.nodes0 = s->num_bvh_nodes;
+  ctx->update.num_vertices = s->num_vertices;
+  ctx->update.num_pairs = ro.num_pairs;
   ctx->num_textures = d.textures ? (uint32_t)tex->num_textures : 0u;
   ctx->have_scene = true;
   return HJ_OK;

@@ -24,7 +24,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_comm_create", "hj_comm_destroy", "hj_comm_reduce_framebuffers", "hj_reserve", "hj_framebuffer_bind",
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
-           "hj_debug_env_distribution", "hj_refit_bvh_device")
+           "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -85,6 +85,8 @@ def lib():
         L.hj_bvh_device_read.argtypes = [vp, C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_refit_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t),
                                           C.POINTER(C.c_double)]
+        L.hj_scene_update_shapes.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.POINTER(C.c_double)]
+        L.hj_debug_scene_tree.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.hj_block_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.hj_block_seed.restype = C.c_uint32
         L.hj_pass_offset.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
@@ -165,6 +167,7 @@ class Renderer:
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
+        self.device = int(device)
         self._destroy = lib().hj_context_destroy     # bound now: module globals may be gone at interpreter exit
         rc = lib().hj_context_create(device, C.byref(self._h))
         if rc != abi.HJ_OK:
@@ -333,6 +336,48 @@ class Renderer:
                                               0 if nodes is None else len(nodes), C.byref(got), C.byref(sa) if cost else None))
         out = got.value if keep_on_device else nodes[:got.value]
         return (out, sa.value) if cost else out
+
+    def update_shapes(self, compiled, device_arrays=None, light_grid=True, cost=False):
+        """hj_scene_update_shapes: the uploaded scene's shapes moved in place - spheres, quads, vertices, emitters and camera of
+        `compiled` as they are now; links, triangles, materials, textures and environment stay as uploaded.  device_arrays: a dict of
+        torch tensors on the renderer's device (`vertices` (V, 8), `spheres` (S, 4), `quads` (Q, 12); float32, contiguous) read in
+        place of the host arrays - ALL shape arrays then come from the device, so every kind the scene has must be there; torch's
+        current stream is synchronised first.  light_grid=False: a scene with a light-shaft grid loses it instead of getting a new
+        one.  cost=True: returns the refitted tree's surface-area cost (as `refit_bvh`)."""
+        d = abi.SceneDesc()
+        C.memmove(C.byref(d), C.byref(compiled.desc), C.sizeof(abi.SceneDesc))
+        flags = 0 if light_grid else abi.UPDATE_NO_LIGHT_GRID
+        if device_arrays is not None:
+            import torch
+            flags |= abi.UPDATE_DEVICE_ARRAYS
+            for name, field, count, words, rec in (("spheres", "spheres", d.num_spheres, 4, abi.Sphere), ("quads", "quads", d.num_quads, 12, abi.Quad),
+                                                   ("vertices", "vertices", d.num_vertices, 8, abi.Vertex)):
+                t = device_arrays.get(name)
+                if t is None:
+                    if count:
+                        raise ValueError(f"device_arrays lacks '{name}' ({count} records in the scene)")
+                    continue
+                if not (t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == count * words):
+                    raise ValueError(f"device_arrays['{name}']: a contiguous float32 tensor of {count} x {words} on GPU {self.device} is needed"
+                                     f" (got {tuple(t.shape)} {t.dtype} on {t.device})")
+                setattr(d, field, C.cast(C.c_void_p(t.data_ptr() if count else None), C.POINTER(rec)))
+            torch.cuda.current_stream().synchronize()
+        sa = C.c_double(0.0)
+        self._check(lib().hj_scene_update_shapes(self._h, C.byref(d), flags, C.byref(sa) if cost else None))
+        return sa.value if cost else None
+
+    def scene_tree(self):
+        """hj_debug_scene_tree: dict of `records` (num_nodes, 8) uint32 - the device node array, both copies of the tree -, `map`
+        (uploaded nodes, 2) uint32 - per uploaded node its record and its guard's record, 0xFFFFFFFF for none -, num_nodes, root,
+        root2, num_hot."""
+        info = (C.c_uint32 * 4)()
+        self._check(lib().hj_debug_scene_tree(self._h, None, 0, info, None))
+        records = np.zeros((max(info[0], 1), 8), np.uint32)
+        where = np.zeros((max(info[0] - info[2], 1), 2), np.uint32)
+        self._check(lib().hj_debug_scene_tree(self._h, records.ctypes.data_as(C.POINTER(C.c_float)), len(records), info,
+                                              where.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return {"records": records[:info[0]], "map": where[:info[0] - info[2]], "num_nodes": info[0], "root": info[1], "root2": info[2],
+                "num_hot": info[3]}
 
     def read_device_bvh(self):
         """hj_bvh_device_read: the tree the last build left on the device, (nodes, 8) uint32."""

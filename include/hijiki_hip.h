@@ -379,6 +379,36 @@ int hj_bvh_device_read(hj_context* ctx, hj_bvh_node* out_nodes, size_t capacity,
 int hj_refit_bvh_device(hj_context* ctx, const hj_scene_desc* scene, hj_bvh_node* out_nodes /* may be NULL */, size_t capacity,
                         size_t* out_num_nodes /* may be NULL */, double* out_cost /* may be NULL */);
 
+/* The uploaded scene's shapes moved IN PLACE (ABI 0.7): the frame loop of an animation becomes "move the shapes,
+ * hj_scene_update_shapes, render" - no refit + upload, no re-layout, no allocation after the first call.
+ * `scene` carries the shapes as they are NOW: spheres, quads, vertices, emitters (pdf and cdf change with area) and camera; every
+ * count equals the uploaded scene's.  bvh, triangles, materials and the material tables are NOT read: the uploaded scene's links,
+ * index triples, materials, textures and environment stay.  Afterwards the scene is what hj_scene_upload* would render from these
+ * shapes with the uploaded topology and refitted boxes: a leaf's box is its shape's, an inner node's the union of its two
+ * children's (hj_refit_bvh_device's pass), guard boxes follow the upload's formula from the moved shape and the new root box joined
+ * with the camera, the pre-gathered triangle, pair and emitter records are gathered again.  Which nodes the upload collapsed, paired
+ * or called hot, where the records lie, root, root2, num_hot and the tuning fields do not change ("Refit").
+ * flags: HJ_UPDATE_DEVICE_ARRAYS - scene->spheres / quads / vertices are DEVICE pointers on the context's device, read on the
+ * context's stream (the caller has finished writing them; no host copy is made unless a light-shaft grid is rebuilt);
+ * HJ_UPDATE_NO_LIGHT_GRID - a scene that has a light-shaft grid loses it instead of getting a new one (same image, no next-event
+ * sample proven free).  The old grid is never kept: its proofs are about the old geometry.
+ * out_cost (may be NULL): as hj_refit_bvh_device's.
+ * Refused before anything of the scene is written - the previous frame still renders bit for bit -: no scene (HJ_ERR_STATE); null
+ * arguments, other counts, unknown flag bits, a coordinate, radius or camera field that is not finite, an emitter whose shape is
+ * out of range or not emissive (HJ_ERR_INVALID); an uploaded tree that is not one leaf per shape - among them a scene uploaded
+ * without a tree (num_bvh_nodes == 0, rendered by linear scan) and a scene of a single shape, which have no boxes to refit: upload
+ * those again - (HJ_ERR_UNSUPPORTED); a frame in
+ * flight (HJ_ERR_STATE, as for an upload).  After those checks only a device error can fail; the context is then without a scene,
+ * as after a failed upload.  The call neither reads nor changes the tree hj_build_bvh_device / hj_refit_bvh_device left on the
+ * device, nor the refit's kept links: it owns the uploaded topology's link set, derived at the first update and kept with the scene. */
+#define HJ_UPDATE_DEVICE_ARRAYS 1u
+#define HJ_UPDATE_NO_LIGHT_GRID 2u
+int hj_scene_update_shapes(hj_context* ctx, const hj_scene_desc* scene, uint32_t flags, double* out_cost /* may be NULL */);
+/* Probe: the device node array (8 floats per record, capacity_records of room; NULL: only info), info = num_nodes, root, root2,
+ * num_hot, and (map != NULL) per node i of the uploaded array - num_nodes - root2 of them - two words: its record in the
+ * re-laid-out copy and its guard's record, 0xFFFFFFFF for none.  Record root2 + i is node i in the second copy. */
+int hj_debug_scene_tree(hj_context* ctx, float* records /* may be NULL */, size_t capacity_records, uint32_t info[4], uint32_t* map /* may be NULL */);
+
 /* The child order of a flattened tree, voted by a sample of the scene's own rays - on the device (no counterpart upstream: the
  * reference walks the tree the `bvh` crate hands it, src/main.rs:199-231, children in array order, shader/scene.glsl:97-133; host
  * form of the same pass: hjh_compiled_tune_bvh).  `vote_paths` camera paths of `scene` (camera, materials, emitters) are traced
