@@ -25,6 +25,10 @@ RENDER_NO_DRAIN = 8
 RENDER_NO_LIGHT_GRID = 16
 UPDATE_DEVICE_ARRAYS = 1          # hj_scene_update_shapes flags
 UPDATE_NO_LIGHT_GRID = 2
+# hj_debug_num: enum hj_num_op in its order, the record sizes and the cap
+NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "dot3", "cross3", "normalize3", "reflect3", "rng_seed",
+           "rng_uint", "rng_float", "rand_cos_hemisphere", "rand_uniform_sphere", "rand_barycentric")
+NUM_IN_WORDS, NUM_OUT_WORDS, NUM_MAX_RECORDS = 6, 4, 1 << 20
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
 

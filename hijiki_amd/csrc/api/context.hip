@@ -115,7 +115,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (7u << 8) | 0u; }   // 0.7.0: hj_scene_update_shapes
+uint32_t hj_version(void) { return (0u << 16) | (8u << 8) | 0u; }   // 0.8.0: hj_debug_num
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

@@ -24,7 +24,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_comm_create", "hj_comm_destroy", "hj_comm_reduce_framebuffers", "hj_reserve", "hj_framebuffer_bind",
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
-           "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree")
+           "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -87,6 +87,7 @@ def lib():
                                           C.POINTER(C.c_double)]
         L.hj_scene_update_shapes.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.POINTER(C.c_double)]
         L.hj_debug_scene_tree.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.hj_debug_num.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]
         L.hj_block_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.hj_block_seed.restype = C.c_uint32
         L.hj_pass_offset.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
@@ -410,6 +411,20 @@ class Renderer:
         out = np.zeros((len(uv), 3), np.float32)
         fp = C.POINTER(C.c_float)
         self._check(lib().hj_debug_texture_lookup(self._h, int(texture), uv.ctypes.data_as(fp), len(uv), out.ctypes.data_as(fp)))
+        return out
+
+    def num_probe(self, op, words):
+        """hj_debug_num: the device text of the numeric contract (kernels/hj_num.h) on caller-given inputs.  op: a name of
+        abi.NUM_OPS (or its index); words: (n, k <= 6) uint32 - the bits of the floats, or RNG states - padded with zeros to the
+        record's 6 words.  Returns (n, 4) uint32 (include/hijiki_hip.h says which words an op reads and writes)."""
+        w = np.asarray(words, np.uint32)
+        w = w.reshape(len(w), -1)
+        rec = np.zeros((len(w), abi.NUM_IN_WORDS), np.uint32)
+        rec[:, :w.shape[1]] = w
+        out = np.zeros((len(w), abi.NUM_OUT_WORDS), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        self._check(lib().hj_debug_num(self._h, abi.NUM_OPS.index(op) if isinstance(op, str) else int(op), rec.ctypes.data_as(up),
+                                       len(rec), out.ctypes.data_as(up)))
         return out
 
     def samples(self, block, opts=None):

@@ -529,6 +529,24 @@ int hj_debug_light_grid(const hj_scene_desc* scene, uint32_t res, uint8_t* bits,
  *   hj_debug_light_grid's bits = planar | mesh.  Any output may be NULL. */
 int hj_debug_light_grid_planes(const hj_scene_desc* scene, uint32_t res, uint8_t* planar, uint8_t* mesh, float* recs, float limits[2],
                                float lo[3], float inv[3], uint64_t stats[3]);
+/* hj_debug_num: the device text of the numeric contract (kernels/hj_num.h) on caller-given inputs - the
+ *   functions the path kernels call, one thread per record, no scene needed.  in = n x HJ_NUM_IN_WORDS words, out = n x
+ *   HJ_NUM_OUT_WORDS words; a word is the bits of a float, or a uint32 for the RNG; words an op does not read are ignored, words
+ *   it does not write come back 0.  With a = word 0, b = word 1, p = words 0-2, q = words 3-5, s = word 0 as an RNG state:
+ *     EXP exp(a); SINCOS2PI sin, cos of 2 pi a; ATAN2 atan2(y = a, x = b); ASIN asin(a); MIN / MAX min / max(a, b); DIV a / b;
+ *     SQRT sqrt(a); DOT3 p . q; CROSS3 p x q (3 words); NORMALIZE3 p / |p| (3 words); REFLECT3 reflect(I = p, N = q) (3 words);
+ *     RNG_SEED the hash of s; RNG_UINT / RNG_FLOAT the next draw, then the state after it; RAND_COS_HEMISPHERE /
+ *     RAND_UNIFORM_SPHERE / RAND_BARYCENTRIC the sample (3 words), then the state after it.
+ *   Refused with HJ_ERR_INVALID: a null argument, an op that is none of these, n == 0, n above HJ_NUM_MAX_RECORDS. */
+enum hj_num_op {
+  HJ_NUM_EXP = 0, HJ_NUM_SINCOS2PI, HJ_NUM_ATAN2, HJ_NUM_ASIN, HJ_NUM_MIN, HJ_NUM_MAX, HJ_NUM_DIV, HJ_NUM_SQRT, HJ_NUM_DOT3,
+  HJ_NUM_CROSS3, HJ_NUM_NORMALIZE3, HJ_NUM_REFLECT3, HJ_NUM_RNG_SEED, HJ_NUM_RNG_UINT, HJ_NUM_RNG_FLOAT,
+  HJ_NUM_RAND_COS_HEMISPHERE, HJ_NUM_RAND_UNIFORM_SPHERE, HJ_NUM_RAND_BARYCENTRIC, HJ_NUM_OPS
+};
+#define HJ_NUM_IN_WORDS 6
+#define HJ_NUM_OUT_WORDS 4
+#define HJ_NUM_MAX_RECORDS 1048576u   /* 2^20 */
+int hj_debug_num(hj_context* ctx, uint32_t op, const uint32_t* in, size_t n, uint32_t* out);
 
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host

@@ -64,15 +64,19 @@ static inline uint32_t f2bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u
  * start exactly in a quad's plane gave t = +0 here and -0 on the GPU.  The empty asm hides the producer from the fold. */
 static inline float neg_of(float x) { __asm__("" : "+x"(x)); return -x; }
 
-/* IEEE-754-2008 minNum / maxNum (a quiet NaN loses against a number). */
+/* IEEE-754-2008 minNum / maxNum (a quiet NaN loses against a number), with the one thing minNum leaves open settled as the
+ * kernels' v_min_f32 / v_max_f32 settle it: -0 is less than +0, whichever argument holds it.  Equal
+ * arguments differ in the sign bit at most, so OR-ing the words keeps a set sign (min) and AND-ing them clears it (max). */
 static inline float f_min(float a, float b) {
   float m = (a < b) ? a : b;
   if (b != b) m = a;
+  if (a == b) m = bits2f(f2bits(a) | f2bits(b));
   return m;
 }
 static inline float f_max(float a, float b) {
   float m = (a > b) ? a : b;
   if (b != b) m = a;
+  if (a == b) m = bits2f(f2bits(a) & f2bits(b));
   return m;
 }
 
@@ -114,8 +118,17 @@ static inline float hj_exp(float x) {
   return p * bits2f((uint32_t)(ni + 127) << 23);
 }
 
+/* float -> int as the kernels' (int)x converts (v_cvt_i32_f32): toward zero, saturating at INT32_MIN / INT32_MAX, a NaN to 0
+ * (DESIGN.md section 3).  C leaves a value outside int's range undefined, and x86's cvttss2si answers INT32_MIN for all of them. */
+static inline int f2i_sat(float x) {
+  if (x != x) return 0;
+  if (x >= 2147483648.0f) return INT32_MAX;
+  if (x <= -2147483648.0f) return INT32_MIN;
+  return (int)x;
+}
+
 /* (sin, cos)(2*pi*v) for v in [0,1]: quadrant by rint(4v), then polynomials
- * on [-pi/4, pi/4]. */
+ * on [-pi/4, pi/4].  Defined, if meaningless, for every other v: from |4v| >= 2^31 on the quadrant is the saturated k's. */
 static inline void hj_sincos2pi(float v, float* s_out, float* c_out) {
   float k = fmaf(v, 4.0f, 12582912.0f) - 12582912.0f;
   float r = fmaf(k, -0.25f, v);
@@ -129,7 +142,7 @@ static inline void hj_sincos2pi(float v, float* s_out, float* c_out) {
   cp = fmaf(cp, z, -1.388731625493765e-3f);
   cp = fmaf(cp, z, 4.166664568298827e-2f);
   float c = fmaf(cp, z * z, fmaf(-0.5f, z, 1.0f));
-  int q = ((int)k) & 3;
+  int q = f2i_sat(k) & 3;
   float S = s, C = c;
   if (q == 1) { S = c; C = neg_of(s); }
   else if (q == 2) { S = neg_of(s); C = neg_of(c); }
@@ -1149,6 +1162,43 @@ HJO_EXPORT void hjo_barycentric(uint32_t* state, float* out3) {
 }
 HJO_EXPORT void hjo_uniform_sphere(uint32_t* state, float* out3) {
   v3 r = rand_uniform_sphere(state); out3[0] = r.x; out3[1] = r.y; out3[2] = r.z;
+}
+
+/* The twin of hj_debug_num (include/hijiki_hip.h: same ops, same record layout) over the primitives above: in = n x
+ * HJ_NUM_IN_WORDS words, out = n x HJ_NUM_OUT_WORDS words.  Returns HJ_ERR_INVALID for an unknown op or a null argument. */
+static inline void put3(uint32_t* o, v3 a) { o[0] = f2bits(a.x); o[1] = f2bits(a.y); o[2] = f2bits(a.z); }
+HJO_EXPORT int hjo_num_batch(uint32_t op, const uint32_t* in, size_t n, uint32_t* out) {
+  if (op >= HJ_NUM_OPS || !in || !out) return HJ_ERR_INVALID;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t* w = in + HJ_NUM_IN_WORDS * i;
+    uint32_t* o = out + HJ_NUM_OUT_WORDS * i;
+    const float a = bits2f(w[0]), b = bits2f(w[1]);
+    const v3 p = V(bits2f(w[0]), bits2f(w[1]), bits2f(w[2])), q = V(bits2f(w[3]), bits2f(w[4]), bits2f(w[5]));
+    uint32_t s = w[0];
+    o[0] = o[1] = o[2] = o[3] = 0u;
+    switch (op) {
+      case HJ_NUM_EXP: o[0] = f2bits(hj_exp(a)); break;
+      case HJ_NUM_SINCOS2PI: { float sn, cs; hj_sincos2pi(a, &sn, &cs); o[0] = f2bits(sn); o[1] = f2bits(cs); break; }
+      case HJ_NUM_ATAN2: o[0] = f2bits(hj_atan2(a, b)); break;
+      case HJ_NUM_ASIN: o[0] = f2bits(hj_asin(a)); break;
+      case HJ_NUM_MIN: o[0] = f2bits(f_min(a, b)); break;
+      case HJ_NUM_MAX: o[0] = f2bits(f_max(a, b)); break;
+      case HJ_NUM_DIV: o[0] = f2bits(a / b); break;
+      case HJ_NUM_SQRT: o[0] = f2bits(sqrtf(a)); break;
+      case HJ_NUM_DOT3: o[0] = f2bits(dot3(p, q)); break;
+      case HJ_NUM_CROSS3: put3(o, cross3(p, q)); break;
+      case HJ_NUM_NORMALIZE3: put3(o, normalize3(p)); break;
+      case HJ_NUM_REFLECT3: put3(o, reflect3(p, q)); break;
+      case HJ_NUM_RNG_SEED: o[0] = rng_seed(s); break;
+      case HJ_NUM_RNG_UINT: o[0] = rng_uint(&s); o[1] = s; break;
+      case HJ_NUM_RNG_FLOAT: o[0] = f2bits(rng_float(&s)); o[1] = s; break;
+      case HJ_NUM_RAND_COS_HEMISPHERE: put3(o, rand_cos_hemisphere(&s)); o[3] = s; break;
+      case HJ_NUM_RAND_UNIFORM_SPHERE: put3(o, rand_uniform_sphere(&s)); o[3] = s; break;
+      case HJ_NUM_RAND_BARYCENTRIC: put3(o, rand_barycentric(&s)); o[3] = s; break;
+      default: break;
+    }
+  }
+  return HJ_OK;
 }
 
 /* rays: n x 8 floats (o.xyz, d.xyz, tmin, tmax).  hits: n x 4 (id as int bits, t, u, v of the

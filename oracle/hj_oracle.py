@@ -85,6 +85,7 @@ def lib():
         L.hjo_set_environment.restype = None
         L.hjo_env_lookup.argtypes = [fp, C.c_size_t, fp]
         L.hjo_env_sample.argtypes = [u32p, C.c_size_t, fp]
+        L.hjo_num_batch.argtypes = [C.c_uint32, u32p, C.c_size_t, u32p]
         L.hjo_sizeof_counters.restype = C.c_size_t
         assert L.hjo_sizeof_counters() == C.sizeof(Counters)
         _LIB = L
@@ -220,6 +221,21 @@ def shade_probe(compiled, rays, rng_states):
         _status("hjo_shade_probe", lib().hjo_shade_probe(C.byref(compiled.desc), _fp(rays), rng.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                          len(rays), _fp(out)))
     return out, out[:, 0].copy().view(np.int32), out[:, 15].copy().view(np.uint32)
+
+
+def num_batch(op, words):
+    """hjo_num_batch, the twin of hj_debug_num (device.Renderer.num_probe: same arguments, same (n, 4) uint32 result) over the
+    oracle's own primitives."""
+    from hijiki_amd import abi
+    w = np.asarray(words, np.uint32)
+    w = w.reshape(len(w), -1)
+    rec = np.zeros((len(w), abi.NUM_IN_WORDS), np.uint32)
+    rec[:, :w.shape[1]] = w
+    out = np.zeros((len(w), abi.NUM_OUT_WORDS), np.uint32)
+    up = C.POINTER(C.c_uint32)
+    _status("hjo_num_batch", lib().hjo_num_batch(abi.NUM_OPS.index(op) if isinstance(op, str) else int(op), rec.ctypes.data_as(up),
+                                                 len(rec), out.ctypes.data_as(up)))
+    return out
 
 
 def texture_lookup(texture_set, texture, uv):
