@@ -29,6 +29,8 @@ UPDATE_NO_LIGHT_GRID = 2
 NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "dot3", "cross3", "normalize3", "reflect3", "rng_seed",
            "rng_uint", "rng_float", "rand_cos_hemisphere", "rand_uniform_sphere", "rand_barycentric")
 NUM_IN_WORDS, NUM_OUT_WORDS, NUM_MAX_RECORDS = 6, 4, 1 << 20
+# hj_debug_shade_step: the record sizes and the cap
+STEP_IN_WORDS, STEP_OUT_WORDS, STEP_MAX_RECORDS = 18, 33, 1 << 16
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
 

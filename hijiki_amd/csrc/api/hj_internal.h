@@ -13,7 +13,8 @@
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
 //   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
 //   api/environment.hip   environment lighting: the checks and the alias table of hj_scene_upload_env, hj_debug_env_*
-//   api/step_probe.hip    hj_debug_num: the functions of kernels/hj_num.h on caller-given inputs (includes no other kernel header)
+//   api/step_probe.hip    hj_debug_num: the functions of kernels/hj_num.h on caller-given inputs (includes no other kernel header);
+//                         hj_debug_shade_step: one launch_shade over a fabricated batch                  (host code)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>

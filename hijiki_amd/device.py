@@ -24,7 +24,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_comm_create", "hj_comm_destroy", "hj_comm_reduce_framebuffers", "hj_reserve", "hj_framebuffer_bind",
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
-           "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num")
+           "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
+           "hj_debug_shade_step")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -88,6 +89,8 @@ def lib():
         L.hj_scene_update_shapes.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.POINTER(C.c_double)]
         L.hj_debug_scene_tree.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.hj_debug_num.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]
+        L.hj_debug_shade_step.argtypes = [vp, C.POINTER(abi.RenderOpts), C.POINTER(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.hj_block_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.hj_block_seed.restype = C.c_uint32
         L.hj_pass_offset.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
@@ -426,6 +429,19 @@ class Renderer:
         self._check(lib().hj_debug_num(self._h, abi.NUM_OPS.index(op) if isinstance(op, str) else int(op), rec.ctypes.data_as(up),
                                        len(rec), out.ctypes.data_as(up)))
         return out
+
+    def shade_step(self, records, opts=None, num_wg=1, parity=0):
+        """hj_debug_shade_step: one pass of the shade stage over (n, 18) uint32 records (path state and raw hit: include/hijiki_hip.h
+        lists the words) on the uploaded scene.  Returns ((n, 33) uint32 output records, (num_wg, 3) uint32 counters: continuing
+        paths, shadow records, next-event samples the light-shaft grid answered)."""
+        rec = np.ascontiguousarray(records, np.uint32).reshape(-1, abi.STEP_IN_WORDS)
+        out = np.zeros((len(rec), abi.STEP_OUT_WORDS), np.uint32)
+        ctr = np.zeros((max(int(num_wg), 1), 3), np.uint32)
+        up = C.POINTER(C.c_uint32)
+        o = opts if opts is not None else default_opts()
+        self._check(lib().hj_debug_shade_step(self._h, C.byref(o), rec.ctypes.data_as(up), len(rec), int(num_wg), int(parity),
+                                              out.ctypes.data_as(up), ctr.ctypes.data_as(up)))
+        return out, ctr
 
     def samples(self, block, opts=None):
         """Intermediate image of one block: (dim_y, dim_x, 8) = (rgb, 1, normal, depth)."""

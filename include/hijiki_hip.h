@@ -547,6 +547,33 @@ enum hj_num_op {
 #define HJ_NUM_OUT_WORDS 4
 #define HJ_NUM_MAX_RECORDS 1048576u   /* 2^20 */
 int hj_debug_num(hj_context* ctx, uint32_t op, const uint32_t* in, size_t n, uint32_t* out);
+/* hj_debug_shade_step: ONE pass of the shade stage over n caller-given path states and raw hits on the uploaded scene - the
+ *   stage's own kernel of the split path, launched once over a batch this call fabricates; nothing of its arithmetic is restated.
+ *   in = n x HJ_STEP_IN_WORDS words (the bits of a float unless said otherwise):
+ *      0-2 ray origin, 3-5 ray direction, 6 raw hit t, 7 object id (int32; negative: the ray left the scene), 8-9 raw hit u, v,
+ *      10-12 throughput, 13-15 extinction, 16 RNG state (uint32), 17 flags as the stage stores them (bit 0 wasDiscrete, bits 1..
+ *      the bounce index).
+ *   Record i is sample i and goes to the next position of workgroup i % num_wg's queue segment, in the path arrays of round parity
+ *   `parity` (0 or 1); hits are binned by material tag in queue order as the hit compaction bins them, misses go to the miss bin of
+ *   a scene with an environment and are dropped otherwise.  opts gives max_bounces, rr_start and HJ_RENDER_NO_LIGHT_GRID (use_bvh =
+ *   0 switches the light-shaft grid off as well), as in a render call.
+ *   out = n x HJ_STEP_OUT_WORDS words, matched to the records by the sample index the stage's appends carry; all zero but for:
+ *      0 alive (1: the path continues; words 1-14 are its next record), 1-3 next origin, 4-6 next direction, 7-9 throughput,
+ *      10 flags, 11 RNG state, 12-14 extinction (0 unless a dielectric of the scene has one: the stage then keeps none),
+ *      15 shadow record present (1), 16-18 its origin, 19-21 direction, 22 tMax, 23-25 the pending next-event contribution,
+ *      26-28 the sample's radiance (emission seen directly, the environment behind a miss, or a next-event contribution the
+ *      light-shaft grid proved unoccluded), 29-32 the sample's first-hit normal and t (written at bounce 0).
+ *   counters = num_wg x 3 words: continuing paths appended, shadow records appended, next-event samples the grid answered.
+ *   No scene: HJ_ERR_STATE.  HJ_ERR_INVALID: a null argument, n == 0, n above HJ_STEP_MAX_RECORDS, num_wg == 0 or above n (a
+ *   workgroup without a record), parity above 1, an object id that is no shape of the scene.
+ *   Reach: explicit path records through the stage's instantiation with ordinary loads and stores.  Implicit camera paths (no
+ *   record: state derived from the sample index), the streaming (non-temporal) instantiation of large trees and the fused kernel's
+ *   call wrapper are not reached from here; frames pin those. */
+#define HJ_STEP_IN_WORDS 18
+#define HJ_STEP_OUT_WORDS 33
+#define HJ_STEP_MAX_RECORDS 65536u
+int hj_debug_shade_step(hj_context* ctx, const hj_render_opts* opts, const uint32_t* in, size_t n, uint32_t num_wg, uint32_t parity,
+                        uint32_t* out, uint32_t* counters);
 
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host

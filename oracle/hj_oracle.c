@@ -856,6 +856,68 @@ static void log_ray(const ray_t* r, int kind, int id) {
   fwrite(rec, sizeof rec, 1, g_ray_log);
 }
 
+/* One step of render.glsl:94-144, from "hit known" to "next ray known": what integrate_ray's loop does with the raw hit (id, t, u, v;
+ * id < 0: the ray left the scene) of `ray` at bounce index `bounce`.  Hit point and frame as scene.glsl:160-175 makes them.  The
+ * visibility test is the caller's: the step hands back the shadow ray and the pending T * f * importance.  T, ext, was_discrete and
+ * rng are the path's state, updated in place; the return value says whether the path goes on (roulette and the bounce cap
+ * included), then o / wo are the next ray.  hjo_shade_step is this function over the records of hj_debug_shade_step. */
+typedef struct {
+  its_t its;            /* the populated hit (unset on a miss) */
+  int has_add; v3 add;  /* radiance the step itself adds: emission seen directly, the environment behind a miss */
+  int want_shadow;      /* the next-event sample passed render.glsl:121 ... */
+  ray_t sh; v3 scol;    /* ... its shadow ray, and T * evalBSDF * importance, added if the ray is unoccluded */
+  v3 wo;
+} step_t;
+
+static int shade_step(const scene_t* S, const ray_t* ray, int id, float t, float u, float v, uint32_t bounce, uint32_t max_bounces,
+                      uint32_t rr_start, v3* T, v3* ext, int* was_discrete, uint32_t* rng, step_t* o) {
+  memset(o, 0, sizeof *o);
+  if (id < 0) {
+    /* The ray left the scene: the environment's radiance under the rule of emissive hits (camera ray, or after a mirror or
+     * glass bounce), nothing in a channel whose extinction is non-zero (exp(-ext * inf)), and the path ends. */
+    if (S->env && *was_discrete) {
+      const v3 le = env_radiance(S, ray->d);
+      o->has_add = 1;
+      o->add = V(ext->x != 0.0f ? 0.0f : T->x * le.x, ext->y != 0.0f ? 0.0f : T->y * le.y, ext->z != 0.0f ? 0.0f : T->z * le.z);
+    }
+    return 0;
+  }
+  its_t* its = &o->its;
+  its->id = id; its->t = t; its->u = u; its->v = v; its->raw_u = u; its->raw_v = v;
+  its->p = V(fmaf(t, ray->d.x, ray->o.x), fmaf(t, ray->d.y, ray->o.y), fmaf(t, ray->d.z, ray->o.z));   /* scene.glsl:164 */
+  if ((uint32_t)id < S->ns) populate_sphere(&S->sc->spheres[id], its);
+  else if ((uint32_t)id < S->ns + S->nq) populate_quad(&S->sc->quads[(uint32_t)id - S->ns], its);
+  else populate_triangle(S, (uint32_t)id - S->ns - S->nq, its);
+  uint32_t mat = S->sc->materials[id];
+  uint32_t tag = mat >> HJ_MATERIAL_TAG_SHIFT, midx = mat & HJ_MATERIAL_INDEX_MASK;
+  float dist = len3(v_sub(ray->o, its->p));
+  *T = v_mul(*T, V(hj_exp(-ext->x * dist), hj_exp(-ext->y * dist), hj_exp(-ext->z * dist)));
+  if (tag == HJ_MAT_EMISSIVE && *was_discrete) {
+    o->has_add = 1;
+    o->add = v_mul(*T, ld3(S->sc->emissive[midx].power));
+  }
+  if (diffuse_tag(tag)) {
+    S->ctr->nee_evals++;
+    v3 imp = sample_emitter(S, its->p, rng, &o->sh);
+    if (len3(imp) > M_EPSF && dot3(o->sh.d, its->n) > 0.0f) {
+      v3 f = eval_bsdf(S, mat, o->sh.d, its);
+      o->want_shadow = 1;
+      o->scol = v_mul(v_mul(*T, f), imp);
+    }
+  }
+  int alive;
+  v3 wgt = sample_bsdf(S, mat, ray->d, its, rng, &o->wo, ext, &alive);
+  *T = v_mul(*T, wgt);
+  if (!alive) return 0;
+  *was_discrete = !diffuse_tag(tag);
+  if (bounce >= rr_start) { /* `bounce > 3` (render.glsl:137) for rr_start = 4 */
+    float q = f_min(0.99f, f_max(T->x, f_max(T->y, T->z)));
+    if (rng_float(rng) > q) return 0;
+    *T = v_divs(*T, q);
+  }
+  return bounce + 1u < max_bounces;   /* render.glsl:92 */
+}
+
 /* shader/render.glsl:81-147 */
 static void integrate_ray(const scene_t* S, ray_t ray, uint32_t* rng, uint32_t max_bounces, uint32_t rr_start,
                           sample_t* out) {
@@ -866,55 +928,25 @@ static void integrate_ray(const scene_t* S, ray_t ray, uint32_t* rng, uint32_t m
   its_t its; memset(&its, 0, sizeof its);
   for (uint32_t bounce = 0; bounce < max_bounces; bounce++) {
     c->closest_calls++;
-    {
-      const int hit_ = intersect_scene(S, ray, &its, closest_ctr(c));
-      log_ray(&ray, 0, hit_ ? its.id : -1);
-      if (!hit_) {
-        /* The ray left the scene: the environment's radiance under the rule of emissive hits (camera ray, or after a mirror or
-         * glass bounce), nothing in a channel whose extinction is non-zero (exp(-ext * inf)), and the path ends. */
-        if (S->env && was_discrete) {
-          const v3 le = env_radiance(S, ray.d);
-          total = v_add(total, V(ext.x != 0.0f ? 0.0f : T.x * le.x, ext.y != 0.0f ? 0.0f : T.y * le.y,
-                                 ext.z != 0.0f ? 0.0f : T.z * le.z));
-        }
-        break;
-      }
-    }
+    const int hit_ = intersect_scene(S, ray, &its, closest_ctr(c));
+    log_ray(&ray, 0, hit_ ? its.id : -1);
+    step_t st;
+    const int alive = shade_step(S, &ray, hit_ ? its.id : -1, its.t, its.raw_u, its.raw_v, bounce, max_bounces, rr_start, &T, &ext,
+                                 &was_discrete, rng, &st);
+    if (st.has_add) total = v_add(total, st.add);
+    if (!hit_) break;
     c->hits++;
-    if (bounce == 0) { out->depth = its.t; out->n[0] = its.n.x; out->n[1] = its.n.y; out->n[2] = its.n.z; }
-    uint32_t mat = S->sc->materials[its.id];
-    uint32_t tag = mat >> HJ_MATERIAL_TAG_SHIFT, midx = mat & HJ_MATERIAL_INDEX_MASK;
-    float dist = len3(v_sub(ray.o, its.p));
-    T = v_mul(T, V(hj_exp(-ext.x * dist), hj_exp(-ext.y * dist), hj_exp(-ext.z * dist)));
-    if (tag == HJ_MAT_EMISSIVE && was_discrete)
-      total = v_add(total, v_mul(T, ld3(S->sc->emissive[midx].power)));
-    if (diffuse_tag(tag)) {
-      ray_t sh;
-      c->nee_evals++;
-      v3 imp = sample_emitter(S, its.p, rng, &sh);
-      if (len3(imp) > M_EPSF && dot3(sh.d, its.n) > 0.0f) {
-        its_t dummy; memset(&dummy, 0, sizeof dummy);
-        c->shadow_calls++;
-        int occluded = intersect_scene(S, sh, &dummy, shadow_ctr(c));   /* scene.glsl:92-96: full closest hit */
-        log_ray(&sh, 1, occluded ? dummy.id : -1);
-        c->shadow_hits += (uint64_t)occluded;
-        if (!occluded) {
-          v3 f = eval_bsdf(S, mat, sh.d, &its);
-          total = v_add(total, v_mul(v_mul(T, f), imp));
-        }
-      }
+    if (bounce == 0) { out->depth = st.its.t; out->n[0] = st.its.n.x; out->n[1] = st.its.n.y; out->n[2] = st.its.n.z; }
+    if (st.want_shadow) {
+      its_t dummy; memset(&dummy, 0, sizeof dummy);
+      c->shadow_calls++;
+      int occluded = intersect_scene(S, st.sh, &dummy, shadow_ctr(c));   /* scene.glsl:92-96: full closest hit */
+      log_ray(&st.sh, 1, occluded ? dummy.id : -1);
+      c->shadow_hits += (uint64_t)occluded;
+      if (!occluded) total = v_add(total, st.scol);
     }
-    v3 wo; int alive;
-    v3 wgt = sample_bsdf(S, mat, ray.d, &its, rng, &wo, &ext, &alive);
-    T = v_mul(T, wgt);
     if (!alive) break;
-    ray.d = wo; ray.o = its.p; ray.tmin = 2.0f * M_EPSF; ray.tmax = INFINITY;
-    was_discrete = !diffuse_tag(tag);
-    if (bounce >= rr_start) { /* `bounce > 3` (render.glsl:137) for rr_start = 4 */
-      float q = f_min(0.99f, f_max(T.x, f_max(T.y, T.z)));
-      if (rng_float(rng) > q) break;
-      T = v_divs(T, q);
-    }
+    ray.d = st.wo; ray.o = st.its.p; ray.tmin = 2.0f * M_EPSF; ray.tmax = INFINITY;
   }
   out->rgb[0] = total.x; out->rgb[1] = total.y; out->rgb[2] = total.z; out->w = 1.0f;
 }
@@ -1332,6 +1364,55 @@ HJO_EXPORT int hjo_shade_probe(const hj_scene_desc* sc, const float* rays, const
     }
     memcpy(&o[0], &id, 4);
     memcpy(&o[15], &rng, 4);
+  }
+  return HJ_OK;
+}
+
+/* shade_step over the records of hj_debug_shade_step (include/hijiki_hip.h: HJ_STEP_IN_WORDS words in, HJ_STEP_OUT_WORDS words
+ * out, all zero where the step leaves nothing), on the scene with the textures and the environment set before.  As the stage does,
+ * a scene without a tinted dielectric carries no extinction (the words are ignored and come back 0), a miss without an environment
+ * leaves nothing, and the radiance words hold what the step adds by itself - never the next-event sample: the oracle has no light
+ * grid, so that one always comes back as a shadow record. */
+HJO_EXPORT int hjo_shade_step(const hj_scene_desc* sc, const hj_render_opts* opts, const uint32_t* in, size_t n, uint32_t* out) {
+  const int trc = check_scene_inputs(sc);
+  if (trc != HJ_OK) return trc;
+  hjo_counters c; memset(&c, 0, sizeof c);
+  scene_t S; S.sc = sc; S.ns = (uint32_t)sc->num_spheres; S.nq = (uint32_t)sc->num_quads;
+  S.nt = (uint32_t)sc->num_triangles; S.use_bvh = 1; S.ctr = &c; S.tex = g_textures;
+  bind_environment(&S);
+  int has_ext = 0;
+  for (size_t i = 0; i < sc->num_dielectric; i++)
+    if (sc->dielectric[i].extinction[0] != 0.f || sc->dielectric[i].extinction[1] != 0.f || sc->dielectric[i].extinction[2] != 0.f)
+      has_ext = 1;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t* w = &in[i * HJ_STEP_IN_WORDS];
+    uint32_t* o = &out[i * HJ_STEP_OUT_WORDS];
+    memset(o, 0, sizeof(uint32_t) * HJ_STEP_OUT_WORDS);
+    const int32_t id = (int32_t)w[7];
+    if (id >= (int32_t)(S.ns + S.nq + S.nt)) return HJ_ERR_INVALID;
+    ray_t ray; ray.o = V(bits2f(w[0]), bits2f(w[1]), bits2f(w[2])); ray.d = V(bits2f(w[3]), bits2f(w[4]), bits2f(w[5]));
+    ray.tmin = 0.0f; ray.tmax = INFINITY;
+    v3 T = V(bits2f(w[10]), bits2f(w[11]), bits2f(w[12]));
+    v3 ext = has_ext ? V(bits2f(w[13]), bits2f(w[14]), bits2f(w[15])) : V(0, 0, 0);
+    uint32_t rng = w[16];
+    int was_discrete = (int)(w[17] & 1u);
+    const uint32_t bounce = w[17] >> 1;
+    step_t st;
+    const int alive = shade_step(&S, &ray, id < 0 ? -1 : id, bits2f(w[6]), bits2f(w[8]), bits2f(w[9]), bounce, opts->max_bounces,
+                                 opts->rr_start, &T, &ext, &was_discrete, &rng, &st);
+    if (alive) {
+      o[0] = 1u;
+      put3(&o[1], st.its.p); put3(&o[4], st.wo); put3(&o[7], T);
+      o[10] = (uint32_t)was_discrete | ((bounce + 1u) << 1);
+      o[11] = rng;
+      if (has_ext) put3(&o[12], ext);
+    }
+    if (st.want_shadow) {
+      o[15] = 1u;
+      put3(&o[16], st.sh.o); put3(&o[19], st.sh.d); o[22] = f2bits(st.sh.tmax); put3(&o[23], st.scol);
+    }
+    if (st.has_add) { const v3 z = V(0, 0, 0); put3(&o[26], v_add(z, st.add)); }
+    if (id >= 0 && bounce == 0) { put3(&o[29], st.its.n); o[32] = f2bits(st.its.t); }
   }
   return HJ_OK;
 }

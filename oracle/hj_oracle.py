@@ -86,6 +86,7 @@ def lib():
         L.hjo_env_lookup.argtypes = [fp, C.c_size_t, fp]
         L.hjo_env_sample.argtypes = [u32p, C.c_size_t, fp]
         L.hjo_num_batch.argtypes = [C.c_uint32, u32p, C.c_size_t, u32p]
+        L.hjo_shade_step.argtypes = [C.POINTER(abi.SceneDesc), C.POINTER(abi.RenderOpts), u32p, C.c_size_t, u32p]
         L.hjo_sizeof_counters.restype = C.c_size_t
         assert L.hjo_sizeof_counters() == C.sizeof(Counters)
         _LIB = L
@@ -235,6 +236,21 @@ def num_batch(op, words):
     up = C.POINTER(C.c_uint32)
     _status("hjo_num_batch", lib().hjo_num_batch(abi.NUM_OPS.index(op) if isinstance(op, str) else int(op), rec.ctypes.data_as(up),
                                                  len(rec), out.ctypes.data_as(up)))
+    return out
+
+
+def shade_step(compiled, records, opts=None):
+    """hjo_shade_step, the twin of hj_debug_shade_step (device.Renderer.shade_step: same (n, 18) uint32 records, same (n, 33) uint32
+    result) over the step function integrate_ray itself calls.  Next-event samples always come back as shadow records: the oracle
+    has no light-shaft grid."""
+    from hijiki_amd import abi
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, abi.STEP_IN_WORDS)
+    out = np.zeros((len(rec), abi.STEP_OUT_WORDS), np.uint32)
+    opts = opts or abi.RenderOpts.default()
+    up = C.POINTER(C.c_uint32)
+    with scene_inputs(compiled):
+        _status("hjo_shade_step", lib().hjo_shade_step(C.byref(compiled.desc), C.byref(opts), rec.ctypes.data_as(up), len(rec),
+                                                       out.ctypes.data_as(up)))
     return out
 
 
