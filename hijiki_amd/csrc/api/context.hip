@@ -115,7 +115,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (9u << 8) | 0u; }   // 0.9.0: hj_debug_shade_step
+uint32_t hj_version(void) { return (0u << 16) | (10u << 8) | 0u; }   // 0.10.0: hj_trace_rays
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

@@ -15,6 +15,8 @@
 //   api/environment.hip   environment lighting: the checks and the alias table of hj_scene_upload_env, hj_debug_env_*
 //   api/step_probe.hip    hj_debug_num: the functions of kernels/hj_num.h on caller-given inputs (includes no other kernel header);
 //                         hj_debug_shade_step: one launch_shade over a fabricated batch                  (host code)
+//   api/ray_query.hip     hj_trace_rays: caller-given rays through the uploaded tree (includes the kernel headers up to hj_stages.h and
+//                         defines its own kernels beside the path kernels: the persistent walk with a fetch / finish of its own)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -282,6 +284,10 @@ struct hj_context {
     size_t shapes = 0;                           // the links are 2 * shapes - 1 records
     bool valid = false;
   } refit_links;
+
+  // hj_trace_rays (api/ray_query.hip): device staging of host arrays - one chunk of rays, their hit records and surface records.
+  // Grown on demand (dev_alloc keeps a buffer that is large enough), reused by every call, freed with the context.
+  struct RayQuery { hjapi::DevBuf rays, hits, surface; } query;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment

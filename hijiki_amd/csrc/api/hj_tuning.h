@@ -53,6 +53,10 @@ struct Tuning {
   X(lbvh_vote_paths, "HJ_LBVH_VOTE_PATHS", 60000, 0, 1 << 24) /* camera paths of the ray vote at the end of the build */                \
   X(refit_tiled, "HJ_REFIT_TILED", 1, 0, 1)                /* hj_refit_bvh_device: 1 subtrees inside a run of records in LDS, 0 the plain climb */ \
   X(bvh_child_order, "HJ_BVH_CHILD_ORDER", 3, 0, 9)        /* static child order of the device build (3: fewer shapes first) */         \
+  /* hj_trace_rays (read when the context is created and by every upload, render call and build: not per query) */                     \
+  X(trace_persistent, "HJ_TRACE_PERSISTENT", 1, 0, 1)      /* 1 the persistent walk with ray replacement (k_rq_walk), 0 one thread per ray (k_rq_plain) */ \
+  X(trace_wg_rays, "HJ_TRACE_WG_RAYS", 2048, 64, 1 << 24)  /* rays per workgroup segment of the persistent form */                      \
+  X(trace_chunk, "HJ_TRACE_CHUNK", 1 << 22, 64, 0x7FFFFFFF) /* rays per launch (and per staging buffer of host arrays) */               \
   X(bvh_vote_shadow, "HJ_BVH_VOTE_SHADOW", kUnset, 0, 16)  /* a shadow ray's vote in quarters of a closest-hit ray's: 1 (4 on large trees) */
   // presence flags (debugging aids): set to anything = on
 #define HJ_TUNING_FLAGS(X)                                                                                                              \

@@ -1,0 +1,187 @@
+// hj_trace_rays: caller-given rays through the uploaded tree - the public ray query ("Ray queries").
+//
+// The walk is the path kernel's own (kernels/hj_walk.h trace_persistent: in-wave ray replacement, merged first step, the LDS copy
+// of the hot nodes, pair nodes, the second tree for rays outside general position), instantiated here with a fetch that reads the
+// caller's ray array and a finish that writes one hit record per ray.  Nothing of the kernel headers is restated or edited: this
+// unit includes them (as api/render.hip does for the path kernels) and defines kernels of its own beside theirs.
+//   k_rq_walk<ANY, PAIRS>   persistent form: a workgroup owns a contiguous segment of the rays and walks it with ray replacement
+//   k_rq_plain<ANY>         plain form: one thread per ray through traverse() - the A/B partner (HJ_TRACE_PERSISTENT=0)
+//   k_rq_surface            second pass, one thread per ray: the populated intersection and the material word of every hit
+#include "hj_internal.h"
+#include "../kernels/hj_stages.h"
+
+#pragma clang fp contract(off)
+
+using namespace hjapi;
+
+namespace hj {
+
+// rays: two float4 per ray (origin.xyz, direction.x | direction.yz, tMin, tMax)
+HJ_DEV Ray rq_ray(float4 a, float4 b) {
+  Ray r; r.o = V(a.x, a.y, a.z); r.d = V(a.w, b.x, b.y); r.tmin = b.z; r.tmax = b.w;
+  return r;
+}
+// the record of a finished ray: (objectID bits, t, u, v); a miss: (-1, 0, 0, 0)
+HJ_DEV float4 rq_hit(const RawHit& h) {
+  const bool hit = h.id >= 0;
+  return make_float4(__int_as_float(hit ? h.id : -1), hit ? h.t : 0.f, hit ? h.u : 0.f, hit ? h.v : 0.f);
+}
+
+// Workgroup g walks rays [g * wg_rays, min(n, (g + 1) * wg_rays)): its waves pull them from the segment's head in LDS, a free lane
+// takes the next index (consecutive free lanes read consecutive rays), a finished ray's record goes to its own index - so which
+// lane or workgroup carried a ray shows in no result.
+template <bool ANY, bool PAIRS>
+__global__ __launch_bounds__(kBlockThreads) void k_rq_walk(DeviceScene sc, const float4* __restrict__ rays, uint32_t n, uint32_t wg_rays,
+                                                           float4* __restrict__ hits) {
+  __shared__ WgShared sh;
+  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(n / wg_rays): first < n)
+  const uint32_t cnt = n - first < wg_rays ? n - first : wg_rays;
+  if (threadIdx.x == 0) sh.head = 0;
+  load_hot_nodes(sc, sh);
+  __syncthreads();
+  const float4* __restrict__ seg_rays = rays + 2 * (size_t)first;
+  float4* __restrict__ seg_hits = hits + first;
+  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
+    slot = i;
+    any = ANY;
+    r = rq_ray(seg_rays[2 * i], seg_rays[2 * i + 1]);
+    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
+  };
+  auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
+    if (done) seg_hits[slot] = rq_hit(h);
+  };
+  trace_persistent<ANY ? 1 : 0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+}
+
+template <bool ANY>
+__global__ __launch_bounds__(kBlockThreads) void k_rq_plain(DeviceScene sc, const float4* __restrict__ rays, uint32_t n,
+                                                            float4* __restrict__ hits) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  RawHit h; h.t = 0.f; h.u = 0.f; h.v = 0.f;
+  traverse<true, ANY>(sc, rq_ray(rays[2 * (size_t)i], rays[2 * (size_t)i + 1]), h);
+  hits[i] = rq_hit(h);
+}
+
+// surface: four float4 per ray = p.xyz, n.xyz, u, v, ft.xyz, fb.xyz, material word, 0.  The hit point and populate* are the shade
+// stage's (kernels/hj_stages.h stage_shade: fma(t, d, o), scene.glsl:164).  A pass of its own: inside the walk's finish it would
+// take the walk's registers.
+__global__ __launch_bounds__(kBlockThreads) void k_rq_surface(DeviceScene sc, const float4* __restrict__ rays, const float4* __restrict__ hits,
+                                                              uint32_t n, float4* __restrict__ surface) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 hr = hits[i];
+  const uint32_t id = (uint32_t)__float_as_int(hr.x);
+  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
+  if (id < sc.ns + sc.nq + sc.nt) {                                // (a miss is 0xFFFFFFFF)
+    const Ray r = rq_ray(rays[2 * (size_t)i], rays[2 * (size_t)i + 1]);
+    Its its;
+    its.p = V(fmaf(hr.y, r.d.x, r.o.x), fmaf(hr.y, r.d.y, r.o.y), fmaf(hr.y, r.d.z, r.o.z));
+    if (id < sc.ns) populate_sphere(sc.spheres[id], its);
+    else if (id < sc.ns + sc.nq) populate_quad(sc, id - sc.ns, hr.z, hr.w, its);
+    else populate_triangle(sc, id - sc.ns - sc.nq, hr.z, hr.w, its);
+    s0 = make_float4(its.p.x, its.p.y, its.p.z, its.n.x);
+    s1 = make_float4(its.n.y, its.n.z, its.u, its.v);
+    s2 = make_float4(its.ft.x, its.ft.y, its.ft.z, its.fb.x);
+    s3 = make_float4(its.fb.y, its.fb.z, __uint_as_float(sc.materials[id]), 0.f);
+  }
+  float4* __restrict__ out = surface + 4 * (size_t)i;
+  out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3;
+}
+
+}  // namespace hj
+
+namespace {
+
+// one launch: rays [0, n) at `rays` -> `hits` (and `surface` unless null), all on the device
+void launch_query(hj_context* ctx, const float4* rays, uint32_t n, bool any, float4* hits, float4* surface) {
+  const hj::DeviceScene& sc = ctx->scene;
+  const Tuning& tn = ctx->tuning;
+  hipStream_t s = ctx->stream;
+  const dim3 blk(hj::kBlockThreads);
+  if (tn.trace_persistent != 0) {
+    // rays per workgroup: HJ_TRACE_WG_RAYS, fewer when the launch would otherwise leave CUs without a workgroup (never below one
+    // ray per thread)
+    const uint32_t per_cu = ((n + (uint32_t)ctx->num_cus - 1u) / (uint32_t)ctx->num_cus + 63u) / 64u * 64u;
+    const uint32_t wg_rays = std::min<uint32_t>((uint32_t)tn.trace_wg_rays, std::max<uint32_t>(per_cu, (uint32_t)hj::kBlockThreads));
+    const dim3 grid((n + wg_rays - 1u) / wg_rays);
+    const bool pairs = sc.has_pairs != 0;
+    if (any && pairs) hipLaunchKernelGGL((hj::k_rq_walk<true, true>), grid, blk, 0, s, sc, rays, n, wg_rays, hits);
+    else if (any) hipLaunchKernelGGL((hj::k_rq_walk<true, false>), grid, blk, 0, s, sc, rays, n, wg_rays, hits);
+    else if (pairs) hipLaunchKernelGGL((hj::k_rq_walk<false, true>), grid, blk, 0, s, sc, rays, n, wg_rays, hits);
+    else hipLaunchKernelGGL((hj::k_rq_walk<false, false>), grid, blk, 0, s, sc, rays, n, wg_rays, hits);
+  } else {
+    const dim3 grid((n + hj::kBlockThreads - 1u) / hj::kBlockThreads);
+    if (any) hipLaunchKernelGGL(hj::k_rq_plain<true>, grid, blk, 0, s, sc, rays, n, hits);
+    else hipLaunchKernelGGL(hj::k_rq_plain<false>, grid, blk, 0, s, sc, rays, n, hits);
+  }
+  if (surface) {
+    const dim3 grid((n + hj::kBlockThreads - 1u) / hj::kBlockThreads);
+    hipLaunchKernelGGL(hj::k_rq_surface, grid, blk, 0, s, sc, rays, static_cast<const float4*>(hits), n, surface);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The argument checks come first and need neither a device nor a context's state (a refusal without a context leaves its text in
+// hj_last_error(NULL), as hj_context_create's do).  A process without a HIP device cannot hold a context: a call that is otherwise
+// valid gets HJ_ERR_DEVICE there, like every entry point that computes.
+int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, float* hits, float* surface) {
+  if (flags & ~(uint32_t)(HJ_TRACE_ANY_HIT | HJ_TRACE_DEVICE_ARRAYS)) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: unknown flag bits 0x%x", flags);
+  const bool any = (flags & HJ_TRACE_ANY_HIT) != 0, on_device = (flags & HJ_TRACE_DEVICE_ARRAYS) != 0;
+  if (n != 0) {
+    if (!rays || !hits) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: null %s", !rays ? "rays" : "hits");
+    if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: %zu rays, at most 2^31 - 1 a call", n);
+    if (surface && any) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: an any-hit record is no closest hit: no surface with HJ_TRACE_ANY_HIT");
+    if (on_device && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surface)) & 15u) != 0)
+      return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: device arrays must be 16-byte aligned");
+  }
+  if (!ctx) {
+    if (hj_device_count() == 0) return set_error(nullptr, HJ_ERR_DEVICE, "hj_trace_rays: no HIP device available; this library has no CPU fallback");
+    return set_error(nullptr, HJ_ERR_INVALID, "hj_trace_rays: null context");
+  }
+  HJ_NOT_BUSY(ctx);
+  HJ_NOT_PIPELINED(ctx);
+  if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "hj_trace_rays: no scene has been uploaded");
+  if (n == 0) return HJ_OK;
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  // rays of one launch (HJ_TRACE_CHUNK): bounds the staging buffers of host arrays; device arrays take the same loop
+  const size_t chunk = (size_t)ctx->tuning.trace_chunk;
+  const size_t f4 = sizeof(float4);
+  float4 *d_rays = nullptr, *d_hits = nullptr, *d_surface = nullptr;
+  if (!on_device) {
+    hj_context::RayQuery& q = ctx->query;
+    const size_t most = std::min(n, chunk);
+    HJ_TRY(dev_alloc(ctx, q.rays, most * 2 * f4));
+    HJ_TRY(dev_alloc(ctx, q.hits, most * f4));
+    if (surface) HJ_TRY(dev_alloc(ctx, q.surface, most * 4 * f4));
+    d_rays = static_cast<float4*>(q.rays.p); d_hits = static_cast<float4*>(q.hits.p);
+    d_surface = surface ? static_cast<float4*>(q.surface.p) : nullptr;
+  }
+  hipError_t e = hipSuccess;
+  for (size_t at = 0; at < n && e == hipSuccess; at += chunk) {
+    const uint32_t cnt = (uint32_t)std::min(chunk, n - at);
+    if (on_device) {
+      d_rays = reinterpret_cast<float4*>(const_cast<float*>(rays)) + 2 * at;
+      d_hits = reinterpret_cast<float4*>(hits) + at;
+      d_surface = surface ? reinterpret_cast<float4*>(surface) + 4 * at : nullptr;
+    } else {
+      e = hipMemcpyAsync(d_rays, rays + 8 * at, cnt * 2 * f4, hipMemcpyHostToDevice, ctx->stream);
+      if (e != hipSuccess) break;
+    }
+    launch_query(ctx, d_rays, cnt, any, d_hits, d_surface);
+    e = hipGetLastError();
+    if (!on_device) {
+      if (e == hipSuccess) e = hipMemcpyAsync(hits + 4 * at, d_hits, cnt * f4, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && surface) e = hipMemcpyAsync(surface + 16 * at, d_surface, cnt * 4 * f4, hipMemcpyDeviceToHost, ctx->stream);
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "hj_trace_rays: %s", hipGetErrorString(e));
+  return HJ_OK;
+}
+
+}  // extern "C"

@@ -25,7 +25,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
-           "hj_debug_shade_step")
+           "hj_debug_shade_step", "hj_trace_rays")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -80,6 +80,7 @@ def lib():
         L.hj_comm_destroy.restype = None
         L.hj_comm_reduce_framebuffers.argtypes = [vp, C.c_int]
         L.hj_debug_trace.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        L.hj_trace_rays.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp]      # (host or device pointers)
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -407,6 +408,41 @@ class Renderer:
         self._check(lib().hj_debug_trace(self._h, rays.ctypes.data_as(fp), len(rays), int(use_bvh), int(any_hit),
                                          hits.ctypes.data_as(fp)))
         return hits[:, 0].copy().view(np.int32), hits[:, 1], hits[:, 2], hits[:, 3]
+
+    def trace_rays(self, rays, any_hit=False, surface=False):
+        """hj_trace_rays: (n, 8) rays (origin, direction of any length, tMin, tMax) through the uploaded tree -> ids (n,) int32 (-1: a
+        miss), t, u, v (n,) float32 of the raw hit [, surface (n, 16) float32: p, n, u, v, ft, fb of the populated intersection, the
+        hit shape's material word as float bits, 0; zeros for a miss].  any_hit: the walk stops at the first accepted hit - `ids >= 0`
+        is the answer; no surface with it.  A float32 numpy array gives numpy arrays.  A contiguous float32 torch tensor on the
+        renderer's GPU is read in place and gives tensors on that GPU (ids: an int32 view of the hit records' first column); torch's
+        current stream is synchronised first."""
+        if any_hit and surface:
+            raise ValueError("trace_rays: no surface with any_hit (the record is not the closest hit)")
+        flags = abi.TRACE_ANY_HIT if any_hit else 0
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not (rays.is_cuda and rays.device.index == self.device and rays.dtype == torch.float32 and rays.is_contiguous()
+                    and rays.dim() == 2 and rays.shape[1] == 8):
+                raise ValueError(f"trace_rays: a contiguous float32 tensor of (n, 8) on GPU {self.device} is needed"
+                                 f" (got {tuple(rays.shape)} {rays.dtype} on {rays.device})")
+            n = rays.shape[0]
+            hits = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            surf = torch.empty((n, 16), dtype=torch.float32, device=rays.device) if surface else None
+            torch.cuda.current_stream(rays.device).synchronize()      # (the allocations and whatever wrote `rays`)
+            self._check(lib().hj_trace_rays(self._h, rays.data_ptr() if n else None, n, flags | abi.TRACE_DEVICE_ARRAYS,
+                                            hits.data_ptr() if n else None, surf.data_ptr() if surface and n else None))
+            out = (hits[:, 0].view(torch.int32), hits[:, 1], hits[:, 2], hits[:, 3])
+            return out + ((surf,) if surface else ())
+        rays = np.asarray(rays)
+        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace_rays: a float32 array of (n, 8) is needed (got {rays.shape} {rays.dtype})")
+        rays = np.ascontiguousarray(rays)
+        hits = np.zeros((len(rays), 4), np.float32)
+        surf = np.zeros((len(rays), 16), np.float32) if surface else None
+        self._check(lib().hj_trace_rays(self._h, rays.ctypes.data, len(rays), flags, hits.ctypes.data,
+                                        surf.ctypes.data if surface else None))
+        out = (hits[:, 0].copy().view(np.int32), hits[:, 1], hits[:, 2], hits[:, 3])
+        return out + ((surf,) if surface else ())
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

@@ -483,6 +483,30 @@ int hj_comm_reduce_framebuffers(hj_comm* comm, int root);
  * kept until one of the contexts is destroyed. */
 int hj_reduce_framebuffers(hj_context* const* ctxs, int n, int root);
 
+/* -------------------------------------------------------------- ray queries */
+
+/* hj_trace_rays (ABI 0.10): caller-given rays through the uploaded scene's tree, by the path kernel's own walk (no counterpart in
+ * the reference; intersectScene, shader/scene.glsl:92-175, per ray).
+ *   rays: n x 8 floats (origin.xyz, direction.xyz, tMin, tMax) - hj_debug_trace's layout; directions of any length.
+ *   hits: n x 4 floats (objectID as int32 bits or -1, t, u, v of the raw hit; a miss: -1, 0, 0, 0).
+ *   surface (may be NULL): n x 16 floats per ray - p.xyz, n.xyz, u, v, ft.xyz, fb.xyz (the populated intersection: hit point
+ *     fma(t, d, o), shading normal, texture coordinates, tangent frame), [14] = the hit shape's material word (tag << 24 | index)
+ *     as uploaded, [15] = 0; all 16 words 0 for a miss.
+ *   HJ_TRACE_ANY_HIT: the walk stops at the first accepted hit in its visiting order (the shadow-ray form): only `objectID >= 0`
+ *     is the reference's answer; the record is still a function of ray and tree alone.  No surface with it.
+ *   HJ_TRACE_DEVICE_ARRAYS: rays / hits / surface are device pointers on the context's GPU, 16-byte aligned, read and written in
+ *     place (the caller orders its own streams before the call).  Without it they are host arrays, staged through buffers the
+ *     context keeps.
+ * The tree is always walked (there is no linear-scan form).  Runs on the context's stream and returns when the results are complete;
+ * record i depends on ray i and the scene alone.  n == 0: HJ_OK, nothing touched.
+ * HJ_ERR_INVALID: null rays or hits, unknown flag bits, n above 2^31 - 1, surface together with HJ_TRACE_ANY_HIT, misaligned
+ *   device arrays - checked before anything else, without a device; with a null context the text is in hj_last_error(NULL).
+ * A null context: HJ_ERR_DEVICE in a process without a HIP device (which cannot hold a context), HJ_ERR_INVALID otherwise.
+ * HJ_ERR_STATE: no scene, an asynchronous frame in flight, frames submitted with HJ_RENDER_NO_DRAIN not yet drained. */
+#define HJ_TRACE_ANY_HIT 1u
+#define HJ_TRACE_DEVICE_ARRAYS 2u
+int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, float* hits, float* surface);
+
 /* ------------------------------------------------------------------- probes */
 
 /* Function-level probes used by the parity tests (no counterpart in the
