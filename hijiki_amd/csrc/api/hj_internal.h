@@ -5,7 +5,8 @@
 //   api/scene_upload.hip  hj_scene_upload: validation, host re-layout, emitter records, light grid; one commit at the end  (no kernels)
 //   api/scene_relayout.hip the same re-layout on the device (large trees, the tree hj_build_bvh_device left there)
 //   api/render.hip        the launches of kernels/hj_kernels.h (the only unit that includes them), walk-statistics readers
-//   api/render_calls.hip  batch slots, render calls, hj_reserve, the pipeline, the worker thread, probes   (no kernels)
+//   api/render_calls.hip  batch slots, render calls, hj_reserve, the pipeline, the worker thread, probes (hj_debug_trace,
+//                         hj_debug_samples, hj_debug_reconstruct)                                        (no kernels)
 //   api/comm.hip          RCCL (dlopen), hj_comm_*, hj_reduce_framebuffers
 //   api/lbvh_build.hip    hj_build_bvh_device, hj_refit_bvh_device: host half of kernels/hj_lbvh.h (the only unit that includes it;
 //                         api/refit_pass.hpp: the refit's stages for a caller that brings its own link set)

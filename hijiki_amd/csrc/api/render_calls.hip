@@ -757,4 +757,62 @@ int hj_debug_samples(hj_context* ctx, const hj_image_block* block, const hj_rend
   return HJ_OK;
 }
 
+// One reconstruction over caller-given samples (include/hijiki_hip.h): the blocks are staged in slot 0 as a batch's are, their
+// sample images placed at the kernel's pitch, and the tile lists and the launch are enqueue_reconstruct's.  Every sample slot
+// outside a block's dimension holds kReconPoison in all its words - finite on purpose: the kernel skips a NaN tap, so a stray
+// read of a NaN would change nothing, a stray read of this changes every bit.
+int hj_debug_reconstruct(hj_context* ctx, const hj_image_block* blocks, size_t nb, const hj_render_opts* opts, const float* samples) {
+  if (!ctx) return HJ_ERR_INVALID;
+  HJ_NOT_BUSY(ctx);
+  HJ_NOT_PIPELINED(ctx);
+  if (!ctx->accum) return set_error(ctx, HJ_ERR_STATE, "hj_debug_reconstruct before hj_framebuffer_create");
+  if (!blocks || !samples) return set_error(ctx, HJ_ERR_INVALID, "hj_debug_reconstruct: null argument");
+  if (nb == 0) return set_error(ctx, HJ_ERR_INVALID, "hj_debug_reconstruct: no blocks");
+  if (nb > HJ_RECON_MAX_BLOCKS) return set_error(ctx, HJ_ERR_INVALID, "hj_debug_reconstruct: %zu blocks, at most %u a call", nb, (unsigned)HJ_RECON_MAX_BLOCKS);
+  for (size_t i = 0; i < nb; i++) {            // (as run_submit)
+    const hj_image_block& b = blocks[i];
+    if (b.dimension[0] == 0 || b.dimension[1] == 0 || b.dimension[0] > HJ_BLOCK_SIZE || b.dimension[1] > HJ_BLOCK_SIZE)
+      return set_error(ctx, HJ_ERR_INVALID, "block %zu: dimension %ux%u outside (0,128]", i, b.dimension[0], b.dimension[1]);
+    if (b.original_dimension[0] != ctx->width || b.original_dimension[1] != ctx->height)
+      return set_error(ctx, HJ_ERR_INVALID, "block %zu: original_dimension %ux%u != framebuffer %ux%u", i,
+                       b.original_dimension[0], b.original_dimension[1], ctx->width, ctx->height);
+  }
+  hj_render_opts o;
+  if (opts) o = *opts;
+  else hj_default_render_opts(&o);
+  HJ_TRY(check_opts(ctx, o));
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->events_used = 0;
+  Timer tm{ctx, false};
+  HJ_TRY(sync_all(ctx));
+  hj_context::BatchSlot& sl = ctx->slots[0];
+  hj::BatchState st;
+  HJ_TRY(stage_blocks(ctx, sl, blocks, (uint32_t)nb, st, false));
+  constexpr float kReconPoison = 1e30f;
+  const size_t slots = nb * hj::kSlotsPerBlock;
+  const float4 poison = make_float4(kReconPoison, kReconPoison, kReconPoison, kReconPoison);
+  std::vector<float4> rgb(slots, poison), nd(slots, poison);
+  const float* in = samples;
+  for (size_t i = 0; i < nb; i++)
+    for (uint32_t y = 0; y < blocks[i].dimension[1]; y++)
+      for (uint32_t x = 0; x < blocks[i].dimension[0]; x++, in += 8) {
+        const size_t sp = i * hj::kSlotsPerBlock + (size_t)y * HJ_BLOCK_SIZE + x;
+        rgb[sp] = make_float4(in[0], in[1], in[2], in[3]);
+        nd[sp] = make_float4(in[4], in[5], in[6], in[7]);
+      }
+  // (rgb and nd are read until the streams are drained: no return between the copies and sync_all)
+  int rc = HJ_OK;
+  for (auto [dst, src] : {std::pair<float4*, const float4*>{st.smp_rgb, rgb.data()}, {st.smp_nd, nd.data()}}) {
+    const hipError_t e = hipMemcpyAsync(dst, src, sizeof(float4) * slots, hipMemcpyHostToDevice, sl.stream);
+    if (e != hipSuccess && rc == HJ_OK) rc = set_error(ctx, HJ_ERR_DEVICE, "hj_debug_reconstruct: %s", hipGetErrorString(e));
+  }
+  if (rc == HJ_OK) rc = enqueue_reconstruct(ctx, sl, ctx->slots[1], st, (uint32_t)nb, o, tm);
+  const int rc2 = sync_all(ctx);               // (after an error too: nothing may still be writing to the framebuffer)
+  if (rc == HJ_OK) rc = rc2;
+  if (rc != HJ_OK) return rc;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "hj_debug_reconstruct: %s", hipGetErrorString(e));
+  return HJ_OK;
+}
+
 }  // extern "C"

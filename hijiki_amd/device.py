@@ -25,7 +25,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
-           "hj_debug_shade_step", "hj_trace_rays")
+           "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -92,6 +92,7 @@ def lib():
         L.hj_debug_num.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]
         L.hj_debug_shade_step.argtypes = [vp, C.POINTER(abi.RenderOpts), C.POINTER(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.hj_debug_reconstruct.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_block_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.hj_block_seed.restype = C.c_uint32
         L.hj_pass_offset.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
@@ -478,6 +479,21 @@ class Renderer:
         self._check(lib().hj_debug_shade_step(self._h, C.byref(o), rec.ctypes.data_as(up), len(rec), int(num_wg), int(parity),
                                               out.ctypes.data_as(up), ctr.ctypes.data_as(up)))
         return out, ctr
+
+    def reconstruct(self, blocks, samples, opts=None):
+        """hj_debug_reconstruct: one reconstruction pass over caller-given samples into the framebuffer.  blocks: a ctypes array (or
+        list) of at most abi.RECON_MAX_BLOCKS abi.ImageBlock; samples: per block a (dim_y, dim_x, 8) float32 array in the layout of
+        `samples` (or all of them concatenated)."""
+        if not isinstance(blocks, C.Array):
+            blocks = (abi.ImageBlock * len(blocks))(*blocks)
+        if not isinstance(samples, np.ndarray):
+            samples = np.concatenate([np.ascontiguousarray(s, np.float32).ravel() for s in samples]) if len(samples) else np.zeros(0, np.float32)
+        smp = np.ascontiguousarray(samples, np.float32).ravel()
+        need = sum(8 * b.dimension[0] * b.dimension[1] for b in blocks)
+        if smp.size != need:
+            raise ValueError(f"reconstruct: {smp.size} sample floats for blocks that hold {need}")
+        self._check(lib().hj_debug_reconstruct(self._h, blocks, len(blocks), C.byref(opts) if opts is not None else None,
+                                               smp.ctypes.data_as(C.POINTER(C.c_float))))
 
     def samples(self, block, opts=None):
         """Intermediate image of one block: (dim_y, dim_x, 8) = (rgb, 1, normal, depth)."""

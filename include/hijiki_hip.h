@@ -598,6 +598,21 @@ int hj_debug_num(hj_context* ctx, uint32_t op, const uint32_t* in, size_t n, uin
 #define HJ_STEP_MAX_RECORDS 65536u
 int hj_debug_shade_step(hj_context* ctx, const hj_render_opts* opts, const uint32_t* in, size_t n, uint32_t num_wg, uint32_t parity,
                         uint32_t* out, uint32_t* counters);
+/* hj_debug_reconstruct: ONE reconstruction pass (shader/reconstruction.glsl:22-66) over caller-given samples, accumulated into the
+ *   context's framebuffer (created or bound) exactly as a batch's reconstruction is: the nb blocks are staged in a batch slot, the
+ *   per-tile block lists and the launch are the render calls' own; nothing of the kernel or of the lists is restated.
+ *   samples = the blocks' sample images in hj_debug_samples' layout, one after the other in list order: dimension.y x dimension.x
+ *   x 8 floats per block (rgb, weight, normal xyz, depth), of any value.  Of a block only origin, dimension, original_dimension and
+ *   sample_offset are read; of opts (NULL: the defaults) only recon_stddev, and the checks every render call makes.  Every sample
+ *   slot of the batch outside a block's dimension holds 1e30 in every word before the launch - finite, because the kernel skips a
+ *   tap whose product is a NaN and would so hide a stray read of one.
+ *   No scene is needed.  No framebuffer: HJ_ERR_STATE.  HJ_ERR_INVALID: a null argument, nb == 0, nb above HJ_RECON_MAX_BLOCKS, a
+ *   dimension outside (0, HJ_BLOCK_SIZE], an original_dimension that is not the framebuffer's, recon_stddev not > 0, max_bounces
+ *   == 0; HJ_ERR_UNSUPPORTED: recon_radius != 2.  A block none of whose extended rectangle lies in the image is no error.
+ *   Reach: one batch in slot 0.  The order between batches of different slots (the reconstruction event chain) is not reached
+ *   from here; frames pin it. */
+#define HJ_RECON_MAX_BLOCKS 64u
+int hj_debug_reconstruct(hj_context* ctx, const hj_image_block* blocks, size_t nb, const hj_render_opts* opts, const float* samples);
 
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host

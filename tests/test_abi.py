@@ -48,7 +48,7 @@ def test_hip_library_exports_every_declared_symbol():
     assert set(names) == set(device.EXPORTS), set(names) ^ set(device.EXPORTS)
     for n in names:
         assert hasattr(L, n), n
-    assert L.hj_version() >= 0x000100
+    assert L.hj_version() >= 0x000B00                           # ABI 0.11: hj_debug_reconstruct
 
 
 def test_hip_library_has_gfx950_code_object():
@@ -102,6 +102,7 @@ def test_argument_checks_need_no_gpu():
     assert L.hj_sync(None, None) == abi.HJ_ERR_INVALID
     assert L.hj_render_frame_async(None, 1, 1, 0, 1, 0, 1, None) == abi.HJ_ERR_INVALID
     assert L.hj_reserve(None, 1, None) == abi.HJ_ERR_INVALID
+    assert L.hj_debug_reconstruct(None, None, 1, None, None) == abi.HJ_ERR_INVALID
     out = C.c_void_p()
     assert L.hj_comm_create(None, 1, C.byref(out)) == abi.HJ_ERR_INVALID and not out.value
     arr = (C.c_void_p * 1)(None)
