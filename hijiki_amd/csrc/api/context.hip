@@ -115,7 +115,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (11u << 8) | 0u; }   // 0.11.0: hj_debug_reconstruct
+uint32_t hj_version(void) { return (0u << 16) | (12u << 8) | 0u; }   // 0.12.0: hj_trace_paths
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

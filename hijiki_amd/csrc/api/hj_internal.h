@@ -18,6 +18,8 @@
 //                         hj_debug_shade_step: one launch_shade over a fabricated batch                  (host code)
 //   api/ray_query.hip     hj_trace_rays: caller-given rays through the uploaded tree (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the persistent walk with a fetch / finish of its own)
+//   api/path_query.hip    hj_trace_paths: path-traced radiance along caller-given rays (includes the kernel headers up to hj_stages.h and
+//                         defines its own kernels beside the path kernels: the fused kernel's round loop with a top-up from a ray array)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -289,6 +291,16 @@ struct hj_context {
   // hj_trace_rays (api/ray_query.hip): device staging of host arrays - one chunk of rays, their hit records and surface records.
   // Grown on demand (dev_alloc keeps a buffer that is large enough), reused by every call, freed with the context.
   struct RayQuery { hjapi::DevBuf rays, hits, surface; } query;
+
+  // hj_trace_paths (api/path_query.hip): its own path state - the path arrays and queues of num_wg x pool positions, the per-workgroup
+  // statistics, one chunk of samples - and the device staging of host arrays.  Never the batch slots': a query between two frames
+  // leaves them and the framebuffer alone.  Grown on demand, reused by every call, freed with the context.
+  struct PathQuery {
+    hjapi::DevBuf ray_o[2], ray_d[2], thr[2], ext[2], hit, hit_tag, q_hit, sh_o, sh_d, sh_c;
+    hjapi::DevBuf acc;                    // kStatWords words per workgroup
+    hjapi::DevBuf smp_rgb, smp_nd;
+    hjapi::DevBuf rays, samples;          // staging: one chunk of rays, their sample records
+  } paths;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment

@@ -25,7 +25,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
-           "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct")
+           "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -81,6 +81,8 @@ def lib():
         L.hj_comm_reduce_framebuffers.argtypes = [vp, C.c_int]
         L.hj_debug_trace.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         L.hj_trace_rays.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp]      # (host or device pointers)
+        L.hj_trace_paths.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(abi.RenderOpts), C.c_uint32, vp,
+                                     C.POINTER(abi.RenderStats)]               # (host or device pointers)
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -444,6 +446,51 @@ class Renderer:
                                         surf.ctypes.data if surface else None))
         out = (hits[:, 0].copy().view(np.int32), hits[:, 1], hits[:, 2], hits[:, 3])
         return out + ((surf,) if surface else ())
+
+    def trace_paths(self, rays, seeds=None, spp=1, opts=None, stats=False):
+        """hj_trace_paths: the path-traced radiance along (n, 8) rays (origin, direction of any length, a uint32 seed as the bits of
+        word 6, a reserved word) -> (n, 8) float32 in the layout of `samples`: the float32 sum of the ray's `spp` samples' radiance,
+        (float)spp, the first hit's shading normal and t (zeros for a miss).  Sample k of ray i draws from seedRng(seed_i + k).
+        seeds: an (n,) uint32 array (int32 tensor) written into column 6 of a COPY of `rays`; the caller's array is never modified.
+        opts: max_bounces, rr_start and RENDER_NO_LIGHT_GRID as in a render call.  A float32 numpy array gives a numpy array.  A
+        contiguous float32 torch tensor on the renderer's GPU is read in place and gives a tensor on that GPU; torch's current stream
+        is synchronised first.  stats=True: returns (samples, statistics dict)."""
+        spp = int(spp)
+        if not 1 <= spp <= 65536:
+            raise ValueError(f"trace_paths: spp {spp} outside [1, 65536]")
+        st = abi.RenderStats()
+        o = C.byref(opts) if opts is not None else None
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not (rays.is_cuda and rays.device.index == self.device and rays.dtype == torch.float32 and rays.is_contiguous()
+                    and rays.dim() == 2 and rays.shape[1] == 8):
+                raise ValueError(f"trace_paths: a contiguous float32 tensor of (n, 8) on GPU {self.device} is needed"
+                                 f" (got {tuple(rays.shape)} {rays.dtype} on {rays.device})")
+            n = rays.shape[0]
+            if seeds is not None:
+                if not (type(seeds).__module__.split(".")[0] == "torch" and seeds.device == rays.device and seeds.dtype == torch.int32
+                        and tuple(seeds.shape) == (n,)):
+                    raise ValueError(f"trace_paths: seeds must be an int32 tensor of ({n},) on GPU {self.device}")
+                rays = rays.clone()
+                rays.view(torch.int32)[:, 6] = seeds
+            out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+            torch.cuda.current_stream(rays.device).synchronize()      # (the allocations and whatever wrote `rays`)
+            self._check(lib().hj_trace_paths(self._h, rays.data_ptr() if n else None, n, spp, o, abi.PATHS_DEVICE_ARRAYS,
+                                             out.data_ptr() if n else None, C.byref(st)))
+            return (out, stats_dict(st)) if stats else out
+        rays = np.asarray(rays)
+        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace_paths: a float32 array of (n, 8) is needed (got {rays.shape} {rays.dtype})")
+        if seeds is not None:
+            seeds = np.asarray(seeds)
+            if seeds.dtype != np.uint32 or seeds.shape != (len(rays),):
+                raise ValueError(f"trace_paths: seeds must be a uint32 array of ({len(rays)},) (got {seeds.shape} {seeds.dtype})")
+            rays = np.array(rays, np.float32, order="C")              # (a copy)
+            rays.view(np.uint32)[:, 6] = seeds
+        rays = np.ascontiguousarray(rays)
+        out = np.zeros((len(rays), 8), np.float32)
+        self._check(lib().hj_trace_paths(self._h, rays.ctypes.data, len(rays), spp, o, 0, out.ctypes.data, C.byref(st)))
+        return (out, stats_dict(st)) if stats else out
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

@@ -499,6 +499,7 @@ int hj_reduce_framebuffers(hj_context* const* ctxs, int n, int root);
  *     context keeps.
  * The tree is always walked (there is no linear-scan form).  Runs on the context's stream and returns when the results are complete;
  * record i depends on ray i and the scene alone.  n == 0: HJ_OK, nothing touched.
+ * Origin domain: agreement with the reference bit for bit is claimed for origins within the scene's extent of it - hj_trace_paths below says why.
  * HJ_ERR_INVALID: null rays or hits, unknown flag bits, n above 2^31 - 1, surface together with HJ_TRACE_ANY_HIT, misaligned
  *   device arrays - checked before anything else, without a device; with a null context the text is in hj_last_error(NULL).
  * A null context: HJ_ERR_DEVICE in a process without a HIP device (which cannot hold a context), HJ_ERR_INVALID otherwise.
@@ -506,6 +507,46 @@ int hj_reduce_framebuffers(hj_context* const* ctxs, int n, int root);
 #define HJ_TRACE_ANY_HIT 1u
 #define HJ_TRACE_DEVICE_ARRAYS 2u
 int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, float* hits, float* surface);
+
+/* ------------------------------------------------------------- path queries */
+
+/* hj_trace_paths (ABI 0.12): the path-traced radiance that arrives along caller-given rays - integrateRay (shader/render.glsl:81-147)
+ * per ray instead of per camera pixel; no counterpart in the reference.  For light-map and probe baking, radiance caches, sensors
+ * that are no pinhole camera.
+ *   rays: n x 8 words per ray - words 0-2 the origin, 3-5 the direction (used as given, never normalised, as the reference uses a
+ *     ray's), word 6 a uint32 seed stored as bits, word 7 reserved and ignored.  The first six words are hj_trace_rays' layout.
+ *   spp: samples per ray, 1 ... 65536.  Sample k of ray i starts exactly as a camera path does (render.glsl:86-90,156): RNG state
+ *     seedRng(seed_i + k) with uint32 wrap-around, throughput 1, extinction 0, wasDiscrete, bounce 0, first segment tMin = eps and
+ *     tMax = inf; later segments as integrateRay continues them.  So a block's camera rays with seed = block.seed + lx + ly *
+ *     dimension.x give hj_debug_samples' records.
+ *   samples: n x 8 floats per ray in hj_debug_samples' layout - rgb = the float32 sum over k = 0, 1, ... in that order of the samples'
+ *     radiance, starting from +0; [3] = (float)spp; [4..7] = the first hit's shading normal and t (the same for every k; all zero
+ *     for a miss).  Record i depends on ray i, spp, opts and the scene alone: not on the workgroup count, the pool or chunk size
+ *     (HJ_PATHS_WGS, HJ_PATHS_POOL, HJ_PATHS_CHUNK, read when the context is created), nor on which lane carried the path.
+ *   opts (NULL: the defaults): max_bounces, rr_start and HJ_RENDER_NO_LIGHT_GRID mean what they mean in a render call; use_bvh == 0 is
+ *     HJ_ERR_UNSUPPORTED (the tree is always walked, as in hj_trace_rays); any other HJ_RENDER_* bit is HJ_ERR_INVALID; the
+ *     reconstruction fields and batch_blocks are ignored.
+ *   stats (may be NULL): paths (= n * spp), closest_rays, shadow_rays, hits, unoccluded_shadow_rays, shadow_rays_proven_free, batches
+ *     (= launches of the path kernel) and total_ms; every other field 0.
+ *   HJ_PATHS_DEVICE_ARRAYS: rays and samples are device pointers on the context's GPU, 16-byte aligned, read and written in place on the
+ *     context's stream (the caller orders its own streams before the call).  Without it they are host arrays, staged through buffers
+ *     the context keeps.
+ * The query owns its path state (about 250 bytes per position in flight, at most HJ_PATHS_WGS x HJ_PATHS_POOL = 2048 x 2048 positions =
+ * 1 GB at the defaults, plus 32 bytes per sample of a launch, at most 2^22), kept with the context; it borrows nothing of the batch
+ * slots: a query between two frames leaves them and the framebuffer alone.  Returns when the results are complete.  n == 0: HJ_OK,
+ * nothing touched.
+ * Origin domain: the uploaded tree's leaf guards are padded for ray origins inside the scene's root box joined with the camera (2e-4
+ *   for scenes up to 50 units, 4e-6 of the extent beyond).  Agreement with the reference bit for bit is claimed for origins within
+ *   that extent of the scene; a caller whose rays start farther away uploads under HJ_LEAF_GUARDS=0 (no guards: the reference's own
+ *   leaf tests, slower).  hj_trace_rays has the same limit.
+ * HJ_ERR_INVALID, checked before anything else and without a device (with a null context the text is in hj_last_error(NULL)): null
+ *   rays or samples with n > 0, unknown flag bits, spp == 0 or above 65536, n above 2^31 - 1, misaligned device arrays, max_bounces
+ *   == 0 (and the refusals of opts above).  A null context: HJ_ERR_DEVICE in a process without a HIP device, HJ_ERR_INVALID otherwise.
+ * HJ_ERR_STATE: an asynchronous frame in flight, frames submitted with HJ_RENDER_NO_DRAIN not yet drained, no scene.  A refused call
+ *   writes nothing. */
+#define HJ_PATHS_DEVICE_ARRAYS 1u
+int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
+                   uint32_t flags, float* samples, hj_render_stats* stats /* may be NULL */);
 
 /* ------------------------------------------------------------------- probes */
 
