@@ -89,15 +89,44 @@ void release_scene(hj_context* ctx) {
   ctx->have_scene = false;
 }
 
-void release_slot(hj_context::BatchSlot& sl) {
-  sl.state.clear();
-  sl.samples.clear();
-  sl.alloc_positions = 0;
-  sl.env_bins = false;
-  sl.st = hj::BatchState{};
+int ensure_path_state(hj_context* ctx, PathState& ps, size_t samples, uint32_t G, uint32_t Gmax, uint32_t pool, bool extinction, bool env) {
+  const size_t n = (size_t)G * pool;
+  hj::BatchState& st = ps.st;
+  ps.state.ctx = ps.samples.ctx = ctx;
+  int rc = HJ_OK;
+  auto alloc = [&](DevBufs& set, bool sample_kind) {   // the arrays of the sample kind (or of the others) into `set`
+    batch_arrays(st, extinction, env, [&](auto*& p, Per per, size_t k) {
+      if (rc == HJ_OK && (per == Per::Sample) == sample_kind)
+        rc = set.alloc(p, k * (per == Per::Sample ? samples : per == Per::Position ? n : Gmax));
+    });
+  };
+  if (st.capacity < samples) {
+    ps.samples.clear();
+    st.capacity = 0;
+    alloc(ps.samples, true);
+    if (rc == HJ_OK) st.capacity = (uint32_t)samples;
+  }
+  if (rc == HJ_OK && (ps.alloc_positions < n || ps.alloc_wgs < Gmax || (extinction && !st.ext[0]) || (env && !ps.env_bins))) {
+    ps.state.clear();
+    ps.alloc_positions = ps.alloc_wgs = 0;
+    alloc(ps.state, false);
+    if (rc == HJ_OK) { ps.alloc_positions = n; ps.alloc_wgs = Gmax; ps.env_bins = env; }
+  }
+  if (rc != HJ_OK) return rc;
+  st.pool = pool;
+  set_num_wg(st, G);
+  return HJ_OK;
+}
+
+void release_path_state(PathState& ps) {
+  ps.state.clear();
+  ps.samples.clear();
+  ps.alloc_positions = ps.alloc_wgs = 0;
+  ps.env_bins = false;
+  ps.st = hj::BatchState{};
 }
 void release_batch(hj_context* ctx) {
-  for (auto& sl : ctx->slots) release_slot(sl);
+  for (auto& sl : ctx->slots) release_path_state(sl);
 }
 
 int sync_all(hj_context* ctx) {
@@ -184,7 +213,6 @@ int hj_context_create(int device, hj_context** out) {
   // shortens are covered by the next frame there.  32768 = 12.1 GB per slot, 50 GB per context instead of 86.
   ctx->pool = (uint32_t)tn.pool / 64u * 64u;
   for (auto& sl : ctx->slots) {
-    sl.state.ctx = sl.samples.ctx = ctx;
     if ((e = hipStreamCreateWithFlags(sl.stream.out(), hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
     if ((e = sl.h_counts.reserve((size_t)(kSplitCounts + kStatWords) * ctx->num_wg)) != hipSuccess) return fail(e, "hipHostMalloc");
     for (Event* ev : {&sl.ev_count[0], &sl.ev_count[1], &sl.ev_recon, &sl.ev_done, &sl.ev_path})

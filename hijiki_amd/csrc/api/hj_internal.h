@@ -1,7 +1,8 @@
 // Internals shared by the translation units of libhijiki_hip.so (api/*.hip): the context object, device buffers and the
 // small helpers every entry point uses.  Nothing here is part of the C ABI (include/hijiki_hip.h).
 //
-//   api/context.hip       context create / destroy, framebuffer, errors, environment switches            (no kernels)
+//   api/context.hip       context create / destroy, framebuffer, errors, environment switches, ensure_path_state: the arrays of a
+//                         batch's path state (PathState, batch_arrays below) for the slots, the path query and the shade probe  (no kernels)
 //   api/scene_upload.hip  hj_scene_upload: validation, host re-layout, emitter records, light grid; one commit at the end  (no kernels)
 //   api/scene_relayout.hip the same re-layout on the device (large trees, the tree hj_build_bvh_device left there)
 //   api/render.hip        the launches of kernels/hj_kernels.h (the only unit that includes them), walk-statistics readers
@@ -15,11 +16,12 @@
 //   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
 //   api/environment.hip   environment lighting: the checks and the alias table of hj_scene_upload_env, hj_debug_env_*
 //   api/step_probe.hip    hj_debug_num: the functions of kernels/hj_num.h on caller-given inputs (includes no other kernel header);
-//                         hj_debug_shade_step: one launch_shade over a fabricated batch                  (host code)
+//                         hj_debug_shade_step: one launch_shade over a fabricated batch in a PathState of its own  (host code)
 //   api/ray_query.hip     hj_trace_rays: caller-given rays through the uploaded tree (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the persistent walk with a fetch / finish of its own)
 //   api/path_query.hip    hj_trace_paths: path-traced radiance along caller-given rays (includes the kernel headers up to hj_stages.h and
-//                         defines its own kernels beside the path kernels: the fused kernel's round loop with a top-up from a ray array)
+//                         defines its own kernels beside the path kernels: the fused kernel's round loop with a top-up from a ray array);
+//                         its path state is hj_context::PathQuery, a PathState
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -154,6 +156,65 @@ struct EventPair { Event a, b; int kind; };
 enum StatWord : uint32_t { kStatClosest, kStatShadow, kStatHits, kStatUnoccluded, kStatDirect, kStatWords };
 constexpr uint32_t kSplitCounts = 2;
 
+// BatchState's arrays (kernels/hj_device.h), each with its number of elements per sample, per path-state position (both round
+// parities where it has two) or per workgroup: f(pointer, Per, elements).  ensure_path_state allocates them, run_begin sums them.
+// extinction: the scene has tinted dielectrics, or the caller writes ext[] whatever the scene (hj_debug_shade_step).
+enum class Per { Sample, Position, Workgroup };
+inline uint32_t hit_bins(bool env) { return hj::kNumTags + (env ? 1u : 0u); }   // (an environment: the miss bin, kernels/hj_stages.h kMissBin)
+template <class F>
+void batch_arrays(hj::BatchState& st, bool extinction, bool env, F&& f) {
+  f(st.smp_rgb, Per::Sample, 1);
+  f(st.smp_nd, Per::Sample, 1);
+  for (int par = 0; par < 2; par++) {
+    f(st.ray_o[par], Per::Position, 1);
+    f(st.ray_d[par], Per::Position, 1);
+    f(st.thr[par], Per::Position, 1);
+    if (extinction) f(st.ext[par], Per::Position, 1);   // (only tinted dielectrics read it)
+    else st.ext[par] = nullptr;
+  }
+  f(st.hit, Per::Position, 1);
+  f(st.hit_tag, Per::Position, 1);
+  f(st.q_hit, Per::Position, hit_bins(env));
+  f(st.sh_o, Per::Position, 1);
+  f(st.sh_d, Per::Position, 1);
+  f(st.sh_c, Per::Position, 1);
+  f(st.cnt_ray[0], Per::Workgroup, 1);
+  f(st.cnt_ray[1], Per::Workgroup, 1);
+  f(st.cnt_hit, Per::Workgroup, hit_bins(env));
+  f(st.cnt_shadow, Per::Workgroup, 1);
+  f(st.acc_closest, Per::Workgroup, kStatWords);   // acc_closest .. acc_direct (StatWord): one read-back
+}
+
+// A batch's path state and its owner: what a batch slot, the path query (hj_context::PathQuery) and hj_debug_shade_step's
+// fabricated batch hand to the kernels, sized by ensure_path_state and freed with the object.
+struct PathState {
+  hj::BatchState st{};
+  DevBufs state, samples;               // path-state arrays + queues + per-workgroup arrays; per-sample buffers (batch_arrays)
+  size_t alloc_positions = 0;           // record positions the path-state arrays hold (workgroups x pool)
+  uint32_t alloc_wgs = 0;               // workgroups the per-workgroup arrays hold
+  bool env_bins = false;                // ... and the queues hold the miss bin of an environment (hit_bins)
+};
+
+// Launches of `G` workgroups: num_wg, and acc_shadow .. acc_direct at stride G behind acc_closest (as the read-back expects them).
+inline void set_num_wg(hj::BatchState& st, uint32_t G) {
+  st.num_wg = G;
+  st.acc_shadow = st.acc_closest + (size_t)kStatShadow * G;
+  st.acc_hits = st.acc_closest + (size_t)kStatHits * G;
+  st.acc_unoccluded = st.acc_closest + (size_t)kStatUnoccluded * G;
+  st.acc_direct = st.acc_closest + (size_t)kStatDirect * G;
+}
+
+// ... and that read-back (kStatWords arrays of G words), folded into a call's statistics
+inline void add_stat_words(hj_render_stats& stats, const uint32_t* h_acc, size_t G) {
+  for (size_t i = 0; i < G; i++) {
+    stats.closest_rays += h_acc[kStatClosest * G + i];
+    stats.shadow_rays += h_acc[kStatShadow * G + i];
+    stats.hits += h_acc[kStatHits * G + i];
+    stats.unoccluded_shadow_rays += h_acc[kStatUnoccluded * G + i];
+    stats.shadow_rays_proven_free += h_acc[kStatDirect * G + i];
+  }
+}
+
 }  // namespace hjapi
 
 using hjapi::DevBuf;
@@ -206,9 +267,7 @@ struct hj_context {
 
   // Batch slots: batch k runs on slot k mod num_slots (own state arrays, own stream), so the latency-bound tail of
   // one batch (a few long paths) overlaps the throughput phase of the next ones.
-  struct BatchSlot {
-    hj::BatchState st{};
-    DevBufs state, samples;               // path-state arrays + queues; per-sample buffers (api/render_calls.hip batch_arrays)
+  struct BatchSlot : hjapi::PathState {
     DevBuf d_blocks, d_tiles;
     PinnedBuf<uint32_t> h_tiles;          // pinned staging of the per-tile block lists
     Stream stream;
@@ -222,8 +281,6 @@ struct hj_context {
     bool pending = false, recon_recorded = false;
     uint32_t nb_in_flight = 0;            // ImageBlocks of the batch in flight (progress reporting)
     uint32_t g_in_flight = 0;             // workgroups of the batch in flight (statistics read-back)
-    size_t alloc_positions = 0;           // record positions the path-state arrays hold (workgroups x pool)
-    bool env_bins = false;                // ... and the queues hold the miss bin of an environment (batch_arrays)
   } slots[kMaxSlots];
   uint32_t num_slots = 3;
   uint32_t slots_eff = 3;                // ... the current render call rotates through (1 when device memory is very short)
@@ -292,14 +349,12 @@ struct hj_context {
   // Grown on demand (dev_alloc keeps a buffer that is large enough), reused by every call, freed with the context.
   struct RayQuery { hjapi::DevBuf rays, hits, surface; } query;
 
-  // hj_trace_paths (api/path_query.hip): its own path state - the path arrays and queues of num_wg x pool positions, the per-workgroup
-  // statistics, one chunk of samples - and the device staging of host arrays.  Never the batch slots': a query between two frames
-  // leaves them and the framebuffer alone.  Grown on demand, reused by every call, freed with the context.
-  struct PathQuery {
-    hjapi::DevBuf ray_o[2], ray_d[2], thr[2], ext[2], hit, hit_tag, q_hit, sh_o, sh_d, sh_c;
-    hjapi::DevBuf acc;                    // kStatWords words per workgroup
-    hjapi::DevBuf smp_rgb, smp_nd;
-    hjapi::DevBuf rays, samples;          // staging: one chunk of rays, their sample records
+  // hj_trace_paths (api/path_query.hip): its own path state - num_wg x pool positions, per-workgroup arrays for HJ_PATHS_WGS
+  // workgroups, one chunk of samples (ensure_path_state: a set that is too short is freed and allocated again, whole) - and the
+  // device staging of host arrays (grown on demand).  Never the batch slots': a query between two frames leaves them and the
+  // framebuffer alone.  Reused by every call, freed with the context.
+  struct PathQuery : hjapi::PathState {
+    hjapi::DevBuf in_rays, out_samples;   // staging: one chunk of rays, their sample records
   } paths;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
@@ -332,7 +387,11 @@ void release_scene(hj_context* ctx);
 // api/scene_upload.hip: the light-shaft grid of `s` (all arrays on the host, or the tree at d_tree) into a new buffer of `bufs` and
 // d's lg_* fields; no grid (by size, by HJ_LIGHT_GRID, or because none could be proven) leaves d alone and returns HJ_OK
 int upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, const hj_bvh_node* d_tree, hj::DeviceScene& d);
-void release_slot(hj_context::BatchSlot& sl);
+// Room for `samples` samples and G x pool positions (per-workgroup arrays for Gmax >= G workgroups) in ps, and ps.st's pointers,
+// pool and num_wg set for a launch of G workgroups.  A set that is too short - or lacks ext[] / the miss bin the scene now
+// needs - is freed first, then allocated whole; on failure the caller releases ps (or lets it go).  (api/context.hip)
+int ensure_path_state(hj_context* ctx, PathState& ps, size_t samples, uint32_t G, uint32_t Gmax, uint32_t pool, bool extinction, bool env);
+void release_path_state(PathState& ps);
 void release_batch(hj_context* ctx);
 int sync_all(hj_context* ctx);                       // drains the context's streams (api/context.hip)
 void drop_cached_comms(hj_context* ctx);             // api/comm.hip: the communicators hj_reduce_framebuffers made for ctx
@@ -347,6 +406,15 @@ void launch_trace_shadow(const hj::BatchState& st, const hj::DeviceScene& sc, bo
 void launch_reconstruct(const hj::BatchState& st, float stddev, const uint32_t* tiles, uint32_t tiles_x, uint32_t tiles_y,
                         float4* accum, uint32_t width, uint32_t height, hipStream_t s);
 void launch_debug_trace(const hj::DeviceScene& sc, const float* rays, uint32_t n, bool bvh, bool any_hit, float4* hits, hipStream_t s);
+
+// The scene as a render call's kernels see it: the light-shaft grid (api/light_grid.cpp) answers "no shape of the TREE lies
+// between this cell and that emitter", so it is taken away from a linear-scan render (scene.glsl:134-158 tests every shape of
+// the arrays, in the tree or not) and from a call that asks for every shadow ray to be walked (HJ_RENDER_NO_LIGHT_GRID).
+inline hj::DeviceScene scene_for(const hj_context* ctx, const hj_render_opts& o) {
+  hj::DeviceScene sc = ctx->scene;
+  if (!o.use_bvh || (o.flags & HJ_RENDER_NO_LIGHT_GRID)) sc.light_grid = nullptr;
+  return sc;
+}
 
 }  // namespace hjapi
 

@@ -228,41 +228,23 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
   const uint32_t G = (uint32_t)std::min<size_t>((size_t)tn.paths_wgs, most_groups);
   const uint32_t per_wg = (uint32_t)((most_groups + G - 1) / G) * 64u;                  // samples of the busiest workgroup
   const uint32_t pool = std::min(per_wg, (uint32_t)tn.paths_pool / 64u * 64u);
-  const size_t positions = (size_t)G * pool, f4 = sizeof(float4);                      // (<= 4096 * 2^19: a position is a uint32)
-  hj::DeviceScene sc = ctx->scene;
-  if (o.flags & HJ_RENDER_NO_LIGHT_GRID) sc.light_grid = nullptr;                       // (every shadow ray is walked: api/render_calls.hip scene_for)
-  const bool ext = sc.has_extinction != 0, env = sc.env_alias != nullptr;
+  const size_t f4 = sizeof(float4);                                                     // (G x pool <= 4096 * 2^19: a position is a uint32)
+  const hj::DeviceScene sc = scene_for(ctx, o);
 
+  // Per-workgroup arrays for HJ_PATHS_WGS workgroups, the most a call uses: two calls can need the same number of positions with
+  // different workgroup counts.  st.capacity: the samples allocated, not this call's.
   hj_context::PathQuery& pq = ctx->paths;
-  hj::BatchState st{};
-  auto f4buf = [&](DevBuf& b, size_t count, float4*& out) {
-    const int rc = dev_alloc(ctx, b, count * f4);
-    out = static_cast<float4*>(b.p);
+  if (const int rc = ensure_path_state(ctx, pq, most_samples, G, (uint32_t)tn.paths_wgs, pool, sc.has_extinction != 0, sc.env_alias != nullptr)) {
+    release_path_state(pq);
     return rc;
-  };
-  for (int par = 0; par < 2; par++) {
-    HJ_TRY(f4buf(pq.ray_o[par], positions, st.ray_o[par]));
-    HJ_TRY(f4buf(pq.ray_d[par], positions, st.ray_d[par]));
-    HJ_TRY(f4buf(pq.thr[par], positions, st.thr[par]));
-    if (ext) HJ_TRY(f4buf(pq.ext[par], positions, st.ext[par]));                        // (only tinted dielectrics read it)
   }
-  HJ_TRY(f4buf(pq.hit, positions, st.hit));
-  HJ_TRY(f4buf(pq.sh_o, positions, st.sh_o));
-  HJ_TRY(f4buf(pq.sh_d, positions, st.sh_d));
-  HJ_TRY(f4buf(pq.sh_c, positions, st.sh_c));
-  HJ_TRY(dev_alloc(ctx, pq.hit_tag, std::max<size_t>(positions, 16)));
-  HJ_TRY(dev_alloc(ctx, pq.q_hit, positions * sizeof(uint32_t) * (hj::kNumTags + (env ? 1 : 0))));   // (an environment: the miss bin)
-  HJ_TRY(dev_alloc(ctx, pq.acc, sizeof(uint32_t) * kStatWords * G));
-  HJ_TRY(f4buf(pq.smp_rgb, most_samples, st.smp_rgb));
-  HJ_TRY(f4buf(pq.smp_nd, most_samples, st.smp_nd));
-  st.hit_tag = static_cast<uint8_t*>(pq.hit_tag.p);
-  st.q_hit = static_cast<uint32_t*>(pq.q_hit.p);
-  st.capacity = (uint32_t)most_samples;
-  st.pool = pool;
+  hj::BatchState st = pq.st;
   float4 *d_rays = nullptr, *d_out = nullptr;
   if (!on_device) {
-    HJ_TRY(f4buf(pq.rays, most_rays * 2, d_rays));
-    HJ_TRY(f4buf(pq.samples, most_rays * 2, d_out));
+    HJ_TRY(dev_alloc(ctx, pq.in_rays, most_rays * 2 * f4));
+    HJ_TRY(dev_alloc(ctx, pq.out_samples, most_rays * 2 * f4));
+    d_rays = static_cast<float4*>(pq.in_rays.p);
+    d_out = static_cast<float4*>(pq.out_samples.p);
   }
   const size_t launches = (n + chunk_rays - 1) / chunk_rays;
   std::vector<uint32_t> h_acc;
@@ -285,13 +267,7 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
       if (e != hipSuccess) break;
     }
     // fewer workgroups when the chunk has fewer 64-sample groups (the last chunk); the segments stay `pool` positions long
-    st.num_wg = std::min<uint32_t>(G, (num_samples + 63u) / 64u);
-    uint32_t* acc = static_cast<uint32_t*>(pq.acc.p);
-    st.acc_closest = acc + (size_t)kStatClosest * st.num_wg;
-    st.acc_shadow = acc + (size_t)kStatShadow * st.num_wg;
-    st.acc_hits = acc + (size_t)kStatHits * st.num_wg;
-    st.acc_unoccluded = acc + (size_t)kStatUnoccluded * st.num_wg;
-    st.acc_direct = acc + (size_t)kStatDirect * st.num_wg;
+    set_num_wg(st, std::min<uint32_t>(G, (num_samples + 63u) / 64u));
     hj::PathQueryArgs q{d_rays, spp, num_samples, o.max_bounces, o.rr_start};
     launch_paths(st, sc, q, ctx->stream);
     hipLaunchKernelGGL(hj::k_pq_resolve, dim3((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads), dim3(hj::kBlockThreads), 0, ctx->stream,
@@ -299,7 +275,7 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
     e = hipGetLastError();
     if (e == hipSuccess && !on_device) e = hipMemcpyAsync(samples + 8 * at, d_out, cnt * 2 * f4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && stats)
-      e = hipMemcpyAsync(h_acc.data() + launch * kStatWords * G, acc, sizeof(uint32_t) * kStatWords * st.num_wg, hipMemcpyDeviceToHost, ctx->stream);
+      e = hipMemcpyAsync(h_acc.data() + launch * kStatWords * G, st.acc_closest, sizeof(uint32_t) * kStatWords * st.num_wg, hipMemcpyDeviceToHost, ctx->stream);
   }
   const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
   if (e == hipSuccess) e = es;
@@ -309,15 +285,7 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
     size_t at = 0;
     for (size_t l = 0; l < launches; l++, at += chunk_rays) {
       const size_t cnt = std::min(chunk_rays, n - at);
-      const size_t g_used = std::min<size_t>(G, (cnt * spp + 63) / 64);
-      const uint32_t* a = h_acc.data() + l * kStatWords * G;
-      for (size_t i = 0; i < g_used; i++) {
-        stats->closest_rays += a[kStatClosest * g_used + i];
-        stats->shadow_rays += a[kStatShadow * g_used + i];
-        stats->hits += a[kStatHits * g_used + i];
-        stats->unoccluded_shadow_rays += a[kStatUnoccluded * g_used + i];
-        stats->shadow_rays_proven_free += a[kStatDirect * g_used + i];
-      }
+      add_stat_words(*stats, h_acc.data() + l * kStatWords * G, std::min<size_t>(G, (cnt * spp + 63) / 64));
     }
     stats->paths = (uint64_t)n * spp;
     stats->batches = launches;

@@ -9,86 +9,21 @@ using namespace hjapi;
 
 namespace {
 
-// BatchState's arrays (kernels/hj_device.h), each with its number of elements per sample, per path-state position (both round
-// parities where it has two) or per workgroup: f(pointer, Per, elements).  ensure_batch allocates them, run_begin sums them.
-enum class Per { Sample, Position, Workgroup };
-template <class F>
-void batch_arrays(hj::BatchState& st, bool extinction, bool env, F&& f) {
-  f(st.smp_rgb, Per::Sample, 1);
-  f(st.smp_nd, Per::Sample, 1);
-  for (int par = 0; par < 2; par++) {
-    f(st.ray_o[par], Per::Position, 1);
-    f(st.ray_d[par], Per::Position, 1);
-    f(st.thr[par], Per::Position, 1);
-    if (extinction) f(st.ext[par], Per::Position, 1);   // (only tinted dielectrics read it)
-    else st.ext[par] = nullptr;
-  }
-  f(st.hit, Per::Position, 1);
-  f(st.hit_tag, Per::Position, 1);
-  f(st.q_hit, Per::Position, hj::kNumTags + (env ? 1 : 0));   // (an environment: the miss bin, kernels/hj_stages.h kMissBin)
-  f(st.sh_o, Per::Position, 1);
-  f(st.sh_d, Per::Position, 1);
-  f(st.sh_c, Per::Position, 1);
-  f(st.cnt_ray[0], Per::Workgroup, 1);
-  f(st.cnt_ray[1], Per::Workgroup, 1);
-  f(st.cnt_hit, Per::Workgroup, hj::kNumTags + (env ? 1 : 0));
-  f(st.cnt_shadow, Per::Workgroup, 1);
-  f(st.acc_closest, Per::Workgroup, kStatWords);   // acc_closest .. acc_direct (StatWord): one read-back
-}
-
 // Sample buffers for `num_blocks` ImageBlocks and path-state arrays + queues of `pool` slots per workgroup.
 // pool: the fused kernel regenerates paths, so a few thousand slots per workgroup keep it busy whatever the batch
 // size (ctx->pool, HJ_POOL); the split-kernel path starts every sample of the batch at once and needs them all.
 int ensure_batch(hj_context* ctx, hj_context::BatchSlot& sl, uint32_t num_blocks, bool all_in_flight) {
   const uint32_t cap = num_blocks * hj::kSlotsPerBlock;
-  const uint32_t G = ctx->num_wg_eff, Gmax = ctx->num_wg;
+  const uint32_t G = ctx->num_wg_eff;
   const uint32_t per_wg = (((cap + 63u) / 64u + G - 1u) / G) * 64u;     // samples of the busiest workgroup
   const uint32_t pool = all_in_flight ? per_wg : std::min(per_wg, ctx->pool_eff);
-  const size_t n = (size_t)G * pool;
-  const bool ext = ctx->scene.has_extinction, env = ctx->scene.env_alias != nullptr;
-  hj::BatchState& st = sl.st;
-  int rc = HJ_OK;
-  // the arrays of the sample kind (or of the others) into `set`; per-workgroup arrays for the most workgroups a call may use
-  auto alloc = [&](DevBufs& set, bool samples) {
-    batch_arrays(st, ext, env, [&](auto*& p, Per per, size_t k) {
-      if (rc == HJ_OK && (per == Per::Sample) == samples)
-        rc = set.alloc(p, k * (per == Per::Sample ? cap : per == Per::Position ? n : Gmax));
-    });
-  };
-  if (st.capacity < cap) {
-    sl.samples.clear();
-    st.capacity = 0;
-    alloc(sl.samples, true);
-    if (rc == HJ_OK) rc = dev_alloc(ctx, sl.d_blocks, sizeof(hj_image_block) * num_blocks);
-    if (rc == HJ_OK && sl.h_blocks.reserve(num_blocks) != hipSuccess)
-      rc = set_error(ctx, HJ_ERR_NOMEM, "pinned block staging allocation failed");
-    if (rc == HJ_OK) st.capacity = cap;
-  }
-  if (rc == HJ_OK && (sl.alloc_positions < n || (ext && !st.ext[0]) || (env && !sl.env_bins))) {
-    sl.state.clear();
-    sl.alloc_positions = 0;
-    alloc(sl.state, false);
-    if (rc == HJ_OK) { sl.alloc_positions = n; sl.env_bins = env; }
-  }
-  if (rc == HJ_OK) {
-    st.acc_shadow = st.acc_closest + (size_t)kStatShadow * G;
-    st.acc_hits = st.acc_closest + (size_t)kStatHits * G;
-    st.acc_unoccluded = st.acc_closest + (size_t)kStatUnoccluded * G;
-    st.acc_direct = st.acc_closest + (size_t)kStatDirect * G;
-    st.pool = pool;
-  }
-  st.num_wg = G;
-  if (rc != HJ_OK) release_slot(sl);
+  // (per-workgroup arrays for the most workgroups a call may use)
+  int rc = ensure_path_state(ctx, sl, cap, G, ctx->num_wg, pool, ctx->scene.has_extinction, ctx->scene.env_alias != nullptr);
+  if (rc == HJ_OK) rc = dev_alloc(ctx, sl.d_blocks, sizeof(hj_image_block) * num_blocks);
+  if (rc == HJ_OK && sl.h_blocks.reserve(num_blocks) != hipSuccess)
+    rc = set_error(ctx, HJ_ERR_NOMEM, "pinned block staging allocation failed");
+  if (rc != HJ_OK) release_path_state(sl);
   return rc;
-}
-
-// The scene as a render call's kernels see it: the light-shaft grid (api/light_grid.cpp) answers "no shape of the TREE lies
-// between this cell and that emitter", so it is taken away from a linear-scan render (scene.glsl:134-158 tests every shape of
-// the arrays, in the tree or not) and from a call that asks for every shadow ray to be walked (HJ_RENDER_NO_LIGHT_GRID).
-hj::DeviceScene scene_for(const hj_context* ctx, const hj_render_opts& o) {
-  hj::DeviceScene sc = ctx->scene;
-  if (!o.use_bvh || (o.flags & HJ_RENDER_NO_LIGHT_GRID)) sc.light_grid = nullptr;
-  return sc;
 }
 
 enum { EV_CLOSEST = 0, EV_SHADOW = 1, EV_SHADE = 2, EV_RECON = 3, EV_PATH = 4 };
@@ -177,15 +112,7 @@ int harvest(hj_context* ctx, hj_context::BatchSlot& sl, hj_render_stats* stats, 
     ctx->progress(ctx->progress_user, ctx->blocks_done, std::max(ctx->blocks_total, ctx->blocks_done));
   }
   if (stats) {
-    const size_t G = sl.g_in_flight;
-    const uint32_t* h_acc = sl.h_counts.p + kSplitCounts * G;
-    for (size_t i = 0; i < G; i++) {
-      stats->closest_rays += h_acc[kStatClosest * G + i];
-      stats->shadow_rays += h_acc[kStatShadow * G + i];
-      stats->hits += h_acc[kStatHits * G + i];
-      stats->unoccluded_shadow_rays += h_acc[kStatUnoccluded * G + i];
-      stats->shadow_rays_proven_free += h_acc[kStatDirect * G + i];
-    }
+    add_stat_words(*stats, sl.h_counts.p + (size_t)kSplitCounts * sl.g_in_flight, sl.g_in_flight);
     stats->batches += 1;
   }
   return HJ_OK;

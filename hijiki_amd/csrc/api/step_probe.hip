@@ -98,8 +98,7 @@ int hj_debug_shade_step(hj_context* ctx, const hj_render_opts* opts, const uint3
   if (n > HJ_STEP_MAX_RECORDS) return set_error(ctx, HJ_ERR_INVALID, "hj_debug_shade_step: %zu records, at most %u a call", n, (unsigned)HJ_STEP_MAX_RECORDS);
   if (num_wg == 0 || num_wg > n) return set_error(ctx, HJ_ERR_INVALID, "hj_debug_shade_step: %u workgroups for %zu records", num_wg, n);
   if (parity > 1u) return set_error(ctx, HJ_ERR_INVALID, "hj_debug_shade_step: parity %u", parity);
-  hj::DeviceScene sc = ctx->scene;
-  if (!opts->use_bvh || (opts->flags & HJ_RENDER_NO_LIGHT_GRID)) sc.light_grid = nullptr;   // (as a render call: render_calls.hip scene_for)
+  const hj::DeviceScene sc = scene_for(ctx, *opts);
   const uint32_t shapes = sc.ns + sc.nq + sc.nt;
   const uint32_t cnt = (uint32_t)n;
   for (uint32_t i = 0; i < cnt; i++) {
@@ -111,7 +110,7 @@ int hj_debug_shade_step(hj_context* ctx, const hj_render_opts* opts, const uint3
   if (shapes) HJ_HIP(ctx, hipMemcpy(materials.data(), sc.materials, sizeof(uint32_t) * shapes, hipMemcpyDeviceToHost));
 
   const bool env = sc.env_alias != nullptr, has_ext = sc.has_extinction != 0;
-  const uint32_t G = num_wg, bins = hj::kNumTags + (env ? 1u : 0u), miss_bin = hj::kNumTags;
+  const uint32_t G = num_wg, bins = hit_bins(env), miss_bin = hj::kNumTags;
   const uint32_t pool = ((cnt + G - 1u) / G + 63u) / 64u * 64u;
   const size_t P = (size_t)G * pool;
   const uint32_t np = parity ^ 1u;
@@ -144,38 +143,16 @@ int hj_debug_shade_step(hj_context* ctx, const hj_render_opts* opts, const uint3
     c++;
   }
 
-  DevBufs bufs(ctx);
-  hj::BatchState st{};
-  st.num_wg = G; st.pool = pool; st.capacity = cnt;
-  HJ_TRY(bufs.alloc(st.smp_rgb, cnt));
-  HJ_TRY(bufs.alloc(st.smp_nd, cnt));
-  for (int k = 0; k < 2; k++) {
-    HJ_TRY(bufs.alloc(st.ray_o[k], P));
-    HJ_TRY(bufs.alloc(st.ray_d[k], P));
-    HJ_TRY(bufs.alloc(st.thr[k], P));
-    HJ_TRY(bufs.alloc(st.ext[k], P));
-    HJ_TRY(bufs.alloc(st.cnt_ray[k], G));
-  }
-  HJ_TRY(bufs.alloc(st.hit, P));
-  HJ_TRY(bufs.alloc(st.hit_tag, P));
-  HJ_TRY(bufs.alloc(st.q_hit, (size_t)bins * P));
-  HJ_TRY(bufs.alloc(st.sh_o, P));
-  HJ_TRY(bufs.alloc(st.sh_d, P));
-  HJ_TRY(bufs.alloc(st.sh_c, P));
-  HJ_TRY(bufs.alloc(st.cnt_hit, (size_t)G * bins));
-  HJ_TRY(bufs.alloc(st.cnt_shadow, G));
-  HJ_TRY(bufs.alloc(st.acc_closest, G));
-  HJ_TRY(bufs.alloc(st.acc_shadow, G));
-  HJ_TRY(bufs.alloc(st.acc_hits, G));
-  HJ_TRY(bufs.alloc(st.acc_unoccluded, G));
-  HJ_TRY(bufs.alloc(st.acc_direct, G));
+  PathState ps;                                            // (freed on return)
+  HJ_TRY(ensure_path_state(ctx, ps, cnt, G, G, pool, /*extinction=*/true, env));   // ext[] whatever the scene: set and read back below
+  const hj::BatchState& st = ps.st;
   hipStream_t s = ctx->stream;
   const size_t f4 = sizeof(float4), w4 = sizeof(uint32_t);
   HJ_HIP(ctx, hipMemsetAsync(st.smp_rgb, 0, f4 * cnt, s));
   HJ_HIP(ctx, hipMemsetAsync(st.smp_nd, 0, f4 * cnt, s));
   for (float4* a : {st.ray_o[np], st.ray_d[np], st.thr[np], st.ext[np], st.sh_o, st.sh_d, st.sh_c}) HJ_HIP(ctx, hipMemsetAsync(a, 0, f4 * P, s));
-  for (uint32_t* a : {st.cnt_ray[0], st.cnt_ray[1], st.cnt_shadow, st.acc_closest, st.acc_shadow, st.acc_hits, st.acc_unoccluded, st.acc_direct})
-    HJ_HIP(ctx, hipMemsetAsync(a, 0, w4 * G, s));
+  for (uint32_t* a : {st.cnt_ray[0], st.cnt_ray[1], st.cnt_shadow}) HJ_HIP(ctx, hipMemsetAsync(a, 0, w4 * G, s));
+  HJ_HIP(ctx, hipMemsetAsync(st.acc_closest, 0, w4 * kStatWords * G, s));   // acc_closest .. acc_direct: one allocation
   HJ_HIP(ctx, hipMemcpyAsync(st.ray_o[parity], h_o.data(), f4 * P, hipMemcpyHostToDevice, s));
   HJ_HIP(ctx, hipMemcpyAsync(st.ray_d[parity], h_d.data(), f4 * P, hipMemcpyHostToDevice, s));
   HJ_HIP(ctx, hipMemcpyAsync(st.thr[parity], h_t.data(), f4 * P, hipMemcpyHostToDevice, s));

@@ -103,6 +103,33 @@ def test_prefixes(pq, n):
     assert_samples(got, want[:n], f"n = {n}")
 
 
+def test_state_regrows_on_a_live_context(monkeypatch):
+    """One context, six queries whose path state differs in what it must hold; every result is the reference's prefix word for word
+    (record k depends on ray k alone: its own seed).  cbox, all rays: the positions, no miss bin, no ext[].  env (environment and
+    tinted glass), 64 rays: fewer positions, but the miss bin and ext[] - "positions suffice" must still reallocate.  cbox, 65 rays:
+    the larger layout is kept.  One workgroup of 128 positions, then two of 64: the same positions, another workgroup count.  env, all
+    rays, with the counts.  Last, beyond HJ_PATHS_WGS of every earlier step: the per-workgroup arrays regrow."""
+    want = {name: R.expected(name, 40)[0] for name in ("cbox", "env")}
+    o = R.options(40)
+    with device.Renderer(0) as r:
+        def query(name, n, what, switches=""):
+            for kv in switches.split():
+                monkeypatch.setenv(*kv.split("="))
+            r.upload_scene(R.scene(name))                                                  # (an upload re-reads the switches)
+            got, stats = r.trace_paths(R.ray_set(name)[:n], opts=o, stats=True)
+            assert_samples(got, want[name][:n], what)
+            return stats
+        stats = query("cbox", R.N_RAYS, "cbox, all rays")
+        assert_counts(stats, R.expected("cbox", 40)[1], "cbox, all rays")
+        query("env", 64, "env[:64] after cbox: miss bin and ext[] on fewer positions")
+        query("cbox", 65, "cbox[:65] in the larger layout")
+        query("cbox", 200, "one workgroup of 128 positions", "HJ_PATHS_WGS=1 HJ_PATHS_POOL=128")
+        query("cbox", 200, "two workgroups of 64 positions", "HJ_PATHS_WGS=2 HJ_PATHS_POOL=64")
+        stats = query("env", R.N_RAYS, "env, all rays")
+        assert_counts(stats, R.expected("env", 40)[1], "env, all rays")
+        query("cbox", 200, "more workgroups allowed than ever allocated for", "HJ_PATHS_WGS=4096 HJ_PATHS_POOL=64")
+
+
 def test_samples_per_ray(pq):
     """500 rays at spp = 4: the reference's sum, and the in-order float32 sum of four spp = 1 calls with seeds + k (the ray seeded
     0xFFFFFFFE wraps); word 3 is 4.0."""
