@@ -159,6 +159,11 @@ class RenderOpts(C.Structure):
         return RenderOpts(use_bvh=1, recon_radius=2, recon_stddev=0.5, max_bounces=1000, rr_start=4, batch_blocks=0)
 
 
+class AdaptiveOpts(C.Structure):
+    """hj_adaptive_opts (ABI 0.13): the rounds and the stop rule of hj_trace_paths_adaptive."""
+    _fields_ = [("spp_min", u32), ("spp_step", u32), ("spp_max", u32), ("rel_error", f32), ("floor", f32)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [("paths", u64), ("closest_rays", u64), ("shadow_rays", u64), ("batches", u64),
                 ("bounce_rounds", u64), ("trace_closest_ms", C.c_double), ("trace_shadow_ms", C.c_double),

@@ -22,6 +22,8 @@
 //   api/path_query.hip    hj_trace_paths: path-traced radiance along caller-given rays (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the fused kernel's round loop with a top-up from a ray array);
 //                         its path state is hj_context::PathQuery, a PathState
+//   api/path_adaptive.hip hj_trace_paths_adaptive: rounds of that path kernel (path_query_pass) over the rays still active, with the
+//                         k_pa_* kernels between them (running sums and stop rule, order-preserving compaction); includes hj_num.h only
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -353,8 +355,17 @@ struct hj_context {
   // workgroups, one chunk of samples (ensure_path_state: a set that is too short is freed and allocated again, whole) - and the
   // device staging of host arrays (grown on demand).  Never the batch slots': a query between two frames leaves them and the
   // framebuffer alone.  Reused by every call, freed with the context.
+  // hj_trace_paths_adaptive (api/path_adaptive.hip) runs its rounds in the same path state and adds, per ray of a call: the running
+  // sums, the active flags, two index lists and one compacted ray array (ping-pong of the compaction), and the moments' staging.
   struct PathQuery : hjapi::PathState {
-    hjapi::DevBuf in_rays, out_samples;   // staging: one chunk of rays, their sample records
+    hjapi::DevBuf in_rays, out_samples;   // staging: one chunk of rays (adaptive: all rays of the call), their sample records
+    hjapi::DevBuf pa_sums, pa_s2;         // adaptive: float4 (R, G, B, S1) and float S2 per ray
+    hjapi::DevBuf pa_flags;               // ... uint32 per entry of a round's list: the ray is still active
+    hjapi::DevBuf pa_src[2];              // ... uint32 per entry: the list's ray indices, this round's and the next's
+    hjapi::DevBuf pa_rays;                // ... the next round's rays: the active rays in order, seeds advanced
+    hjapi::DevBuf pa_counts;              // ... per workgroup of the compaction its active count / offset, then the total
+    hjapi::DevBuf pa_moments;             // ... staging of host moments
+    hjapi::PinnedBuf<uint32_t> pa_active; // ... the total as the host reads it after a round
   } paths;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
@@ -393,6 +404,13 @@ int upload_light_grid(DevBufs& bufs, const hj_scene_desc* s, const Tuning& tn, c
 int ensure_path_state(hj_context* ctx, PathState& ps, size_t samples, uint32_t G, uint32_t Gmax, uint32_t pool, bool extinction, bool env);
 void release_path_state(PathState& ps);
 void release_batch(hj_context* ctx);
+// api/path_query.hip: the shape of a fixed-spp pass over at most n rays as hj_trace_paths lays it out - rays and samples of the
+// largest launch, its workgroups and positions per workgroup - and one launch of the path kernel over cnt device rays into st's
+// sample arrays (smp_rgb / smp_nd of sample ray * spp + k; the statistics per workgroup behind st.acc_closest, st.num_wg of them)
+struct PathQueryPlan { size_t chunk_rays, most_rays, most_samples; uint32_t G, pool; };
+PathQueryPlan path_query_plan(const Tuning& tn, size_t n, uint32_t spp);
+void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_rays, uint32_t cnt, uint32_t spp,
+                     const hj_render_opts& o, hipStream_t s);
 int sync_all(hj_context* ctx);                       // drains the context's streams (api/context.hip)
 void drop_cached_comms(hj_context* ctx);             // api/comm.hip: the communicators hj_reduce_framebuffers made for ctx
 

@@ -1,0 +1,338 @@
+// hj_trace_paths_adaptive: path queries whose sample count is decided per ray on the device ("Adaptive path queries").
+//
+// Sample k of a ray starts from rng_seed(seed + k), so "ray i after d samples" is the same ray with seed_i + d: a later round is a
+// compacted ray array with advanced seeds, and it goes through api/path_query.hip's path kernel unchanged (path_query_pass).  This
+// unit holds what runs between two rounds and includes hj_num.h only, so the path kernels' machine code does not depend on it:
+//   k_pa_accumulate  one thread per ray of a launch: continues the ray's float32 running sums R, G, B, S1, S2 over the launch's
+//                    smp_rgb records in ascending k, evaluates the stop rule (pa_stops), writes the active flag and, when the ray
+//                    stops, its output record
+//   k_pa_count       per workgroup of 256 list entries the number of active ones (wave ballot + popcount)
+//   k_pa_scan        ONE workgroup: the counts become exclusive offsets, the total goes to the word the host reads
+//   k_pa_scatter     the active entries, in list order, to the next round's index list and ray array (word 6 = seed_i + n_i)
+// Ordinary loads and stores, no inline assembly, no global atomic, and no workgroup ever waits for another: the three compaction
+// steps are three launches.
+#include "hj_internal.h"
+#include "../kernels/hj_num.h"
+
+#pragma clang fp contract(off)
+
+using namespace hjapi;
+
+namespace hj {
+
+constexpr uint32_t kPaThreads = 256u;   // threads of a k_pa_* workgroup = list entries of a compaction workgroup (4 waves)
+
+// The stop rule, after a round that brought the ray to m samples (2 <= spp_min <= m <= spp_max).  S1, S2: the float32 running sums
+// of the samples' luminance Y and of Y * Y.  Every operation is float32, in this order, uncontracted; the divisions are correctly
+// rounded; f_max is maxNum.
+//   mean = S1 / (float)m
+//   var  = max(0, S2 - S1 * mean) / (float)(m - 1)
+//   sem2 = var / (float)m                                  (the squared standard error of the mean luminance)
+//   thr  = rel_error * max(mean, floor)
+//   stop = sem2 <= thr * thr  ||  m == spp_max             (a NaN sem2 compares false: such a ray stops only at spp_max)
+HJ_DEV bool pa_stops(float S1, float S2, uint32_t m, uint32_t spp_max, float rel_error, float floor, float& sem2) {
+  const float mean = S1 / (float)m;
+  const float var = f_max(0.f, S2 - S1 * mean) / (float)(m - 1u);
+  sem2 = var / (float)m;
+  const float thr = rel_error * f_max(mean, floor);
+  return sem2 <= thr * thr || m == spp_max;
+}
+
+struct AdaptiveArgs {
+  uint32_t spp_max;
+  float rel_error, floor;
+};
+
+// One launch of the path kernel has written smp_rgb / smp_nd for cnt rays at c samples each (sample j * c + k).  Entry j of the
+// launch is entry j of the round's list behind its first `at` entries (the pointers come offset): ray src[j], or ray first + j in
+// round 0, whose list is every ray (src == NULL) and whose sums start from +0.  n_before: the samples every ray of the list has
+// already (they all have the same number: a ray that is still active has been in every round).
+//   sums[i] = (R, G, B, S1), s2[i] = S2: read unless round 0, written unless the ray stops
+//   samples[2 i] = (R, G, B, (float)n_i) when ray i stops; samples[2 i + 1] = first-hit normal and t, in round 0
+//   moments[i] (may be NULL) = (S1, S2, sem2, n_i as bits) when ray i stops
+__global__ __launch_bounds__(kPaThreads) void k_pa_accumulate(const float4* __restrict__ smp_rgb, const float4* __restrict__ smp_nd, const uint32_t* __restrict__ src,
+                                                              uint32_t first, uint32_t cnt, uint32_t c, uint32_t n_before, AdaptiveArgs a,
+                                                              float4* __restrict__ sums, float* __restrict__ s2, uint32_t* __restrict__ flags,
+                                                              float4* __restrict__ samples, float4* __restrict__ moments) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cnt) return;
+  const uint32_t i = src ? src[j] : first + j;
+  const uint32_t s0 = j * c;                 // (below the launch's sample count: no wrap)
+  float R = 0.f, G = 0.f, B = 0.f, S1 = 0.f, S2 = 0.f;
+  if (n_before != 0u) {
+    const float4 v = sums[i];
+    R = v.x; G = v.y; B = v.z; S1 = v.w; S2 = s2[i];
+  } else {
+    samples[2 * (size_t)i + 1] = smp_nd[s0];
+  }
+  for (uint32_t k = 0; k < c; k++) {
+    const float4 v = smp_rgb[s0 + k];
+    R += v.x; G += v.y; B += v.z;
+    const float Y = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z;
+    S1 += Y;
+    S2 += Y * Y;
+  }
+  const uint32_t m = n_before + c;
+  float sem2;
+  const bool stop = pa_stops(S1, S2, m, a.spp_max, a.rel_error, a.floor, sem2);
+  flags[j] = stop ? 0u : 1u;
+  if (stop) {
+    samples[2 * (size_t)i] = make_float4(R, G, B, (float)m);
+    if (moments) moments[i] = make_float4(S1, S2, sem2, __uint_as_float(m));
+  } else {
+    sums[i] = make_float4(R, G, B, S1);
+    s2[i] = S2;
+  }
+}
+
+// The active entries of a workgroup's 256 list entries: per wave a ballot and its popcount, summed over the four waves
+HJ_DEV uint32_t pa_wave_counts(const uint32_t* __restrict__ flags, uint32_t len, uint32_t* wave_cnt, bool& active, unsigned long long& mask) {
+  const uint32_t j = blockIdx.x * kPaThreads + threadIdx.x;
+  active = j < len && flags[j] != 0u;
+  mask = __ballot(active);
+  if ((threadIdx.x & 63u) == 0u) wave_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
+  __syncthreads();
+  return j;
+}
+
+__global__ __launch_bounds__(kPaThreads) void k_pa_count(const uint32_t* __restrict__ flags, uint32_t len, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t wave_cnt[kPaThreads / 64u];
+  bool active;
+  unsigned long long mask;
+  pa_wave_counts(flags, len, wave_cnt, active, mask);
+  if (threadIdx.x == 0) counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// counts[0, nb) -> their exclusive prefix sums in place, counts[nb] = the total.  One workgroup: thread t owns the `per` consecutive
+// counts from t * per, sums them, the 256 partial sums are scanned in LDS (Hillis-Steele, workgroup barriers only), and every
+// thread walks its counts again.  (A total is at most the list's length, below 2^31.)
+__global__ __launch_bounds__(kPaThreads) void k_pa_scan(uint32_t* __restrict__ counts, uint32_t nb) {
+  __shared__ uint32_t part[2][kPaThreads];
+  const uint32_t t = threadIdx.x;
+  const uint32_t per = (nb + kPaThreads - 1u) / kPaThreads;
+  const uint32_t lo = min(t * per, nb), hi = min(lo + per, nb);
+  uint32_t sum = 0;
+  for (uint32_t b = lo; b < hi; b++) sum += counts[b];
+  uint32_t cur = 0;
+  part[0][t] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < kPaThreads; d <<= 1) {
+    part[cur ^ 1u][t] = part[cur][t] + (t >= d ? part[cur][t - d] : 0u);
+    cur ^= 1u;
+    __syncthreads();
+  }
+  uint32_t run = part[cur][t] - sum;          // (exclusive)
+  for (uint32_t b = lo; b < hi; b++) {
+    const uint32_t v = counts[b];
+    counts[b] = run;
+    run += v;
+  }
+  if (t == kPaThreads - 1u) counts[nb] = part[cur][t];
+}
+
+// Entry j of the list, if active, becomes entry offsets[workgroup] + (active entries of the workgroup before it) of the next list:
+// its ray index, and the caller's ray with word 6 = seed + n_after (uint32 wrap-around).  src == NULL: the list is every ray.
+__global__ __launch_bounds__(kPaThreads) void k_pa_scatter(const uint32_t* __restrict__ flags, const uint32_t* __restrict__ src, uint32_t len,
+                                                           const uint32_t* __restrict__ offsets, const float4* __restrict__ rays, uint32_t n_after,
+                                                           uint32_t* __restrict__ src_out, float4* __restrict__ rays_out) {
+  __shared__ uint32_t wave_cnt[kPaThreads / 64u];
+  bool active;
+  unsigned long long mask;
+  const uint32_t j = pa_wave_counts(flags, len, wave_cnt, active, mask);
+  if (!active) return;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  uint32_t pos = offsets[blockIdx.x] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+  for (uint32_t w = 0; w < wave; w++) pos += wave_cnt[w];
+  const uint32_t i = src ? src[j] : j;
+  const float4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
+  src_out[pos] = i;
+  rays_out[2 * (size_t)pos] = a;
+  rays_out[2 * (size_t)pos + 1] = make_float4(b.x, b.y, __uint_as_float(__float_as_uint(b.z) + n_after), b.w);
+}
+
+}  // namespace hj
+
+extern "C" {
+
+// The argument checks come first and need neither a device nor a context's state (hj_trace_paths' order and style).
+int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const hj_adaptive_opts* aopts, const hj_render_opts* opts, uint32_t flags,
+                            float* samples, float* moments, hj_render_stats* stats) {
+  if (n != 0 && (!rays || !samples)) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: null %s", !rays ? "rays" : "samples");
+  if (flags & ~(uint32_t)HJ_PATHS_DEVICE_ARRAYS) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: unknown flag bits 0x%x", flags);
+  const bool on_device = (flags & HJ_PATHS_DEVICE_ARRAYS) != 0;
+  if (!aopts) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: null adaptive opts");
+  const hj_adaptive_opts a = *aopts;
+  if (a.spp_min < 2u) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: spp_min %u below 2 (a variance needs two samples)", a.spp_min);
+  if (a.spp_step == 0u) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: spp_step must be >= 1");
+  if (a.spp_max < a.spp_min) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: spp_max %u below spp_min %u", a.spp_max, a.spp_min);
+  if (a.spp_max > 65536u) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: spp_max %u above 65536", a.spp_max);
+  if (!(a.rel_error >= 0.f) || std::isinf(a.rel_error) || !(a.floor >= 0.f) || std::isinf(a.floor))
+    return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: rel_error %g and floor %g must be finite and >= 0", (double)a.rel_error, (double)a.floor);
+  const uint32_t max_rounds = 1u + (a.spp_max - a.spp_min + a.spp_step - 1u) / a.spp_step;
+  if (max_rounds > 64u)
+    return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: %u rounds from spp_min %u to spp_max %u in steps of %u, at most 64", max_rounds, a.spp_min,
+                     a.spp_max, a.spp_step);
+  if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: %zu rays, at most 2^31 - 1 a call", n);
+  if (n != 0 && on_device &&
+      ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(moments)) & 15u) != 0)
+    return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: device arrays must be 16-byte aligned");
+  hj_render_opts o;
+  if (opts) o = *opts;
+  else hj_default_render_opts(&o);
+  if (o.max_bounces == 0) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: max_bounces must be >= 1");
+  if (o.use_bvh == 0)
+    return set_error(ctx, HJ_ERR_UNSUPPORTED, "hj_trace_paths_adaptive: the tree is always walked (use_bvh == 0: there is no linear-scan form)");
+  if (o.flags & ~(uint32_t)HJ_RENDER_NO_LIGHT_GRID)
+    return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: of the HJ_RENDER_* bits only HJ_RENDER_NO_LIGHT_GRID applies (flags 0x%x)", o.flags);
+  if (!ctx) {
+    if (hj_device_count() == 0)
+      return set_error(nullptr, HJ_ERR_DEVICE, "hj_trace_paths_adaptive: no HIP device available; this library has no CPU fallback");
+    return set_error(nullptr, HJ_ERR_INVALID, "hj_trace_paths_adaptive: null context");
+  }
+  HJ_NOT_BUSY(ctx);
+  HJ_NOT_PIPELINED(ctx);
+  if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "hj_trace_paths_adaptive: no scene has been uploaded");
+  if (n == 0) return HJ_OK;
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  const auto wall0 = std::chrono::steady_clock::now();
+
+  // The path state for the largest round there can be: no ray stops, and a round has spp_min, spp_step or the last short round's
+  // samples per ray.  A round lays its launches out as hj_trace_paths lays out a query of its rays and samples (path_query_plan);
+  // that layout grows with the number of rays, so a round of fewer rays fits into what is allocated here.
+  const Tuning& tn = ctx->tuning;
+  const uint32_t n32 = (uint32_t)n;
+  const uint32_t later = a.spp_max - a.spp_min;
+  const uint32_t shapes[3] = {a.spp_min, std::min(a.spp_step, later), later % a.spp_step};
+  size_t need_samples = 0;
+  PathQueryPlan big{};
+  for (const uint32_t c : shapes) {
+    if (c == 0) continue;
+    const PathQueryPlan p = path_query_plan(tn, n, c);
+    need_samples = std::max(need_samples, p.most_samples);
+    if ((size_t)p.G * p.pool > (size_t)big.G * big.pool) big = p;
+  }
+  const hj::DeviceScene sc = scene_for(ctx, o);
+  hj_context::PathQuery& pq = ctx->paths;
+  if (const int rc = ensure_path_state(ctx, pq, need_samples, big.G, (uint32_t)tn.paths_wgs, big.pool, sc.has_extinction != 0, sc.env_alias != nullptr)) {
+    release_path_state(pq);
+    return rc;
+  }
+  hj::BatchState st = pq.st;
+
+  // Per ray of the call: 20 B of running sums, 4 B of flags; with a second round 8 B of index lists and 32 B of rays; a count per
+  // 256 rays; host arrays are staged whole, once (32 B of rays, 32 B of samples, 16 B of moments).
+  const size_t f4 = sizeof(float4), u4 = sizeof(uint32_t);
+  const uint32_t blocks_most = (n32 + hj::kPaThreads - 1u) / hj::kPaThreads;
+  HJ_TRY(dev_alloc(ctx, pq.pa_sums, n * f4));
+  HJ_TRY(dev_alloc(ctx, pq.pa_s2, n * sizeof(float)));
+  HJ_TRY(dev_alloc(ctx, pq.pa_flags, n * u4));
+  if (later != 0) {
+    HJ_TRY(dev_alloc(ctx, pq.pa_src[0], n * u4));
+    HJ_TRY(dev_alloc(ctx, pq.pa_src[1], n * u4));
+    HJ_TRY(dev_alloc(ctx, pq.pa_rays, n * 2 * f4));
+    HJ_TRY(dev_alloc(ctx, pq.pa_counts, ((size_t)blocks_most + 1) * u4));
+    HJ_HIP(ctx, pq.pa_active.reserve(1));
+  }
+  const float4* d_rays = reinterpret_cast<const float4*>(rays);
+  float4 *d_out = reinterpret_cast<float4*>(samples), *d_mom = reinterpret_cast<float4*>(moments);
+  if (!on_device) {
+    HJ_TRY(dev_alloc(ctx, pq.in_rays, n * 2 * f4));
+    HJ_TRY(dev_alloc(ctx, pq.out_samples, n * 2 * f4));
+    if (moments) HJ_TRY(dev_alloc(ctx, pq.pa_moments, n * f4));
+    d_rays = static_cast<const float4*>(pq.in_rays.p);
+    d_out = static_cast<float4*>(pq.out_samples.p);
+    d_mom = moments ? static_cast<float4*>(pq.pa_moments.p) : nullptr;
+  }
+  float4* sums = static_cast<float4*>(pq.pa_sums.p);
+  float* s2 = static_cast<float*>(pq.pa_s2.p);
+  uint32_t* d_flags = static_cast<uint32_t*>(pq.pa_flags.p);
+  uint32_t* d_counts = static_cast<uint32_t*>(pq.pa_counts.p);
+  const hj::AdaptiveArgs args{a.spp_max, a.rel_error, a.floor};
+  std::vector<uint32_t> h_acc;
+  hj_render_stats total{};
+
+  hipError_t e = hipSuccess;
+  if (!on_device) e = hipMemcpyAsync(pq.in_rays.p, rays, n * 2 * f4, hipMemcpyHostToDevice, ctx->stream);
+  // A round: the path launches over the list's rays, chunked as hj_trace_paths chunks, each followed by its accumulate; the
+  // compaction of the list; the 4-byte active count; ONE hipStreamSynchronize.  Every ray of a list has n_before samples.
+  const float4* list_rays = d_rays;          // round 0 reads the caller's rays in place
+  const uint32_t* list_src = nullptr;        // ... and its list is every ray
+  uint32_t active = n32, n_before = 0, side = 0;
+  while (active != 0 && e == hipSuccess) {
+    const uint32_t c = n_before == 0 ? a.spp_min : std::min(a.spp_step, a.spp_max - n_before);
+    const uint32_t n_after = n_before + c;
+    const PathQueryPlan plan = path_query_plan(tn, active, c);
+    st.pool = plan.pool;
+    const size_t launches = (active + plan.chunk_rays - 1) / plan.chunk_rays;
+    if (stats) {
+      try {
+        h_acc.assign(launches * kStatWords * plan.G, 0u);
+      } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return set_error(ctx, HJ_ERR_NOMEM, "hj_trace_paths_adaptive: out of host memory");
+      }
+    }
+    size_t launch = 0;
+    for (size_t at = 0; at < active && e == hipSuccess; at += plan.chunk_rays, launch++) {
+      const uint32_t cnt = (uint32_t)std::min<size_t>(plan.chunk_rays, active - at);
+      path_query_pass(st, sc, plan.G, list_rays + 2 * at, cnt, c, o, ctx->stream);
+      hipLaunchKernelGGL(hj::k_pa_accumulate, dim3((cnt + hj::kPaThreads - 1u) / hj::kPaThreads), dim3(hj::kPaThreads), 0, ctx->stream,
+                         static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd), list_src ? list_src + at : nullptr, (uint32_t)at,
+                         cnt, c, n_before, args, sums, s2, d_flags + at, d_out, d_mom);
+      e = hipGetLastError();
+      if (e == hipSuccess && stats)
+        e = hipMemcpyAsync(h_acc.data() + launch * kStatWords * plan.G, st.acc_closest, sizeof(uint32_t) * kStatWords * st.num_wg, hipMemcpyDeviceToHost,
+                           ctx->stream);
+    }
+    const bool last = n_after == a.spp_max;  // every ray of the list stops: nothing to compact, the count is 0
+    if (e == hipSuccess && !last) {
+      const uint32_t nb = (active + hj::kPaThreads - 1u) / hj::kPaThreads;
+      uint32_t* next_src = static_cast<uint32_t*>(pq.pa_src[side].p);
+      hipLaunchKernelGGL(hj::k_pa_count, dim3(nb), dim3(hj::kPaThreads), 0, ctx->stream, d_flags, active, d_counts);
+      hipLaunchKernelGGL(hj::k_pa_scan, dim3(1), dim3(hj::kPaThreads), 0, ctx->stream, d_counts, nb);
+      hipLaunchKernelGGL(hj::k_pa_scatter, dim3(nb), dim3(hj::kPaThreads), 0, ctx->stream, d_flags, list_src, active, d_counts, d_rays, n_after, next_src,
+                         static_cast<float4*>(pq.pa_rays.p));
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(pq.pa_active.p, d_counts + nb, u4, hipMemcpyDeviceToHost, ctx->stream);
+      list_src = next_src;
+      list_rays = static_cast<const float4*>(pq.pa_rays.p);
+      side ^= 1u;
+    }
+    if (e == hipSuccess && last && !on_device) {      // the results of host arrays ride on the last possible round's synchronisation
+      e = hipMemcpyAsync(samples, d_out, n * 2 * f4, hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && moments) e = hipMemcpyAsync(moments, d_mom, n * f4, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) break;
+    if (stats) {
+      size_t at = 0;
+      for (size_t l = 0; l < launches; l++, at += plan.chunk_rays) {
+        const size_t cnt = std::min<size_t>(plan.chunk_rays, active - at);
+        add_stat_words(total, h_acc.data() + l * kStatWords * plan.G, std::min<size_t>(plan.G, (cnt * c + 63) / 64));
+      }
+    }
+    total.paths += (uint64_t)active * c;
+    total.batches += launches;
+    total.bounce_rounds += 1;
+    const uint32_t next = last ? 0u : *pq.pa_active.p;
+    if (next > active) return set_error(ctx, HJ_ERR_DEVICE, "hj_trace_paths_adaptive: %u active rays out of a list of %u", next, active);
+    if (next == 0 && !last && !on_device) {           // the rays ran out before spp_max: one more, synchronous, copy back
+      e = hipMemcpy(samples, d_out, n * 2 * f4, hipMemcpyDeviceToHost);
+      if (e == hipSuccess && moments) e = hipMemcpy(moments, d_mom, n * f4, hipMemcpyDeviceToHost);
+    }
+    active = next;
+    n_before = n_after;
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return set_error(ctx, HJ_ERR_DEVICE, "hj_trace_paths_adaptive: %s", hipGetErrorString(e));
+  }
+  if (stats) {
+    total.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    *stats = total;
+  }
+  return HJ_OK;
+}
+
+}  // extern "C"

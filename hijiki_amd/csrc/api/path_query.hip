@@ -175,9 +175,31 @@ __global__ __launch_bounds__(kBlockThreads) void k_pq_resolve(const float4* __re
 
 }  // namespace hj
 
-namespace {
+namespace hjapi {
 
-void launch_paths(const hj::BatchState& st, const hj::DeviceScene& sc, const hj::PathQueryArgs& q, hipStream_t s) {
+// The shape of a fixed-spp pass over at most n rays.  A launch takes whole rays: at most HJ_PATHS_CHUNK samples (one ray when spp
+// alone exceeds it: spp <= 65536), dealt in 64-sample groups over at most HJ_PATHS_WGS workgroups of at most HJ_PATHS_POOL positions
+// each - fewer positions when the busiest workgroup has fewer samples than that.  (G x pool <= 4096 * 2^19: a position is a uint32.)
+PathQueryPlan path_query_plan(const Tuning& tn, size_t n, uint32_t spp) {
+  PathQueryPlan p;
+  p.chunk_rays = std::max<size_t>(1, (size_t)tn.paths_chunk / spp);
+  p.most_rays = std::min(n, p.chunk_rays);
+  p.most_samples = p.most_rays * spp;
+  const size_t most_groups = (p.most_samples + 63) / 64;
+  p.G = (uint32_t)std::min<size_t>((size_t)tn.paths_wgs, most_groups);
+  const uint32_t per_wg = (uint32_t)((most_groups + p.G - 1) / p.G) * 64u;              // samples of the busiest workgroup
+  p.pool = std::min(per_wg, (uint32_t)tn.paths_pool / 64u * 64u);
+  return p;
+}
+
+// One launch of the path kernel: cnt rays at d_rays, spp samples each, into the sample arrays of st (num_samples = cnt * spp <=
+// 2^31 - 1: HJ_PATHS_CHUNK's upper bound).  Fewer workgroups when the chunk has fewer 64-sample groups (the last chunk); the
+// segments stay st.pool positions long.  st: num_wg and the statistics pointers are set for this launch (set_num_wg).
+void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_rays, uint32_t cnt, uint32_t spp,
+                     const hj_render_opts& o, hipStream_t s) {
+  const uint32_t num_samples = cnt * spp;
+  set_num_wg(st, std::min<uint32_t>(G, (num_samples + 63u) / 64u));
+  hj::PathQueryArgs q{d_rays, spp, num_samples, o.max_bounces, o.rr_start};
   const dim3 grid(st.num_wg), blk(hj::kBlockThreads);
   const bool pairs = sc.has_pairs != 0, env = sc.env_alias != nullptr;
   if (pairs && env) hipLaunchKernelGGL((hj::k_pq_paths<true, true>), grid, blk, 0, s, st, sc, q);
@@ -186,7 +208,7 @@ void launch_paths(const hj::BatchState& st, const hj::DeviceScene& sc, const hj:
   else hipLaunchKernelGGL((hj::k_pq_paths<false, false>), grid, blk, 0, s, st, sc, q);
 }
 
-}  // namespace
+}  // namespace hjapi
 
 extern "C" {
 
@@ -218,17 +240,12 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
   HJ_HIP(ctx, hipSetDevice(ctx->device));
   const auto wall0 = std::chrono::steady_clock::now();
 
-  // Sizes.  A launch takes whole rays: at most HJ_PATHS_CHUNK samples (one ray when spp alone exceeds it: spp <= 65536), dealt in
-  // 64-sample groups over at most HJ_PATHS_WGS workgroups of at most HJ_PATHS_POOL positions each - fewer positions when the busiest
-  // workgroup has fewer samples than that.
+  // Sizes (path_query_plan above).
   const Tuning& tn = ctx->tuning;
-  const size_t chunk_rays = std::max<size_t>(1, (size_t)tn.paths_chunk / spp);
-  const size_t most_rays = std::min(n, chunk_rays), most_samples = most_rays * spp;
-  const size_t most_groups = (most_samples + 63) / 64;
-  const uint32_t G = (uint32_t)std::min<size_t>((size_t)tn.paths_wgs, most_groups);
-  const uint32_t per_wg = (uint32_t)((most_groups + G - 1) / G) * 64u;                  // samples of the busiest workgroup
-  const uint32_t pool = std::min(per_wg, (uint32_t)tn.paths_pool / 64u * 64u);
-  const size_t f4 = sizeof(float4);                                                     // (G x pool <= 4096 * 2^19: a position is a uint32)
+  const PathQueryPlan plan = path_query_plan(tn, n, spp);
+  const size_t chunk_rays = plan.chunk_rays, most_rays = plan.most_rays, most_samples = plan.most_samples;
+  const uint32_t G = plan.G, pool = plan.pool;
+  const size_t f4 = sizeof(float4);
   const hj::DeviceScene sc = scene_for(ctx, o);
 
   // Per-workgroup arrays for HJ_PATHS_WGS workgroups, the most a call uses: two calls can need the same number of positions with
@@ -258,7 +275,6 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
   size_t launch = 0;
   for (size_t at = 0; at < n && e == hipSuccess; at += chunk_rays, launch++) {
     const uint32_t cnt = (uint32_t)std::min(chunk_rays, n - at);
-    const uint32_t num_samples = cnt * spp;                                             // (<= 2^31 - 1: HJ_PATHS_CHUNK's upper bound)
     if (on_device) {
       d_rays = reinterpret_cast<float4*>(const_cast<float*>(rays)) + 2 * at;
       d_out = reinterpret_cast<float4*>(samples) + 2 * at;
@@ -266,10 +282,7 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
       e = hipMemcpyAsync(d_rays, rays + 8 * at, cnt * 2 * f4, hipMemcpyHostToDevice, ctx->stream);
       if (e != hipSuccess) break;
     }
-    // fewer workgroups when the chunk has fewer 64-sample groups (the last chunk); the segments stay `pool` positions long
-    set_num_wg(st, std::min<uint32_t>(G, (num_samples + 63u) / 64u));
-    hj::PathQueryArgs q{d_rays, spp, num_samples, o.max_bounces, o.rr_start};
-    launch_paths(st, sc, q, ctx->stream);
+    path_query_pass(st, sc, G, d_rays, cnt, spp, o, ctx->stream);
     hipLaunchKernelGGL(hj::k_pq_resolve, dim3((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads), dim3(hj::kBlockThreads), 0, ctx->stream,
                        static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd), spp, cnt, d_out);
     e = hipGetLastError();

@@ -25,7 +25,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
-           "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths")
+           "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -83,6 +83,8 @@ def lib():
         L.hj_trace_rays.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp]      # (host or device pointers)
         L.hj_trace_paths.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(abi.RenderOpts), C.c_uint32, vp,
                                      C.POINTER(abi.RenderStats)]               # (host or device pointers)
+        L.hj_trace_paths_adaptive.argtypes = [vp, vp, C.c_size_t, C.POINTER(abi.AdaptiveOpts), C.POINTER(abi.RenderOpts), C.c_uint32, vp, vp,
+                                              C.POINTER(abi.RenderStats)]      # (host or device pointers)
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -460,37 +462,82 @@ class Renderer:
             raise ValueError(f"trace_paths: spp {spp} outside [1, 65536]")
         st = abi.RenderStats()
         o = C.byref(opts) if opts is not None else None
-        if type(rays).__module__.split(".")[0] == "torch":
+        rays, on_gpu = self._path_rays("trace_paths", rays, seeds)
+        n = len(rays)
+        if on_gpu:
             import torch
-            if not (rays.is_cuda and rays.device.index == self.device and rays.dtype == torch.float32 and rays.is_contiguous()
-                    and rays.dim() == 2 and rays.shape[1] == 8):
-                raise ValueError(f"trace_paths: a contiguous float32 tensor of (n, 8) on GPU {self.device} is needed"
-                                 f" (got {tuple(rays.shape)} {rays.dtype} on {rays.device})")
-            n = rays.shape[0]
-            if seeds is not None:
-                if not (type(seeds).__module__.split(".")[0] == "torch" and seeds.device == rays.device and seeds.dtype == torch.int32
-                        and tuple(seeds.shape) == (n,)):
-                    raise ValueError(f"trace_paths: seeds must be an int32 tensor of ({n},) on GPU {self.device}")
-                rays = rays.clone()
-                rays.view(torch.int32)[:, 6] = seeds
             out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
             torch.cuda.current_stream(rays.device).synchronize()      # (the allocations and whatever wrote `rays`)
             self._check(lib().hj_trace_paths(self._h, rays.data_ptr() if n else None, n, spp, o, abi.PATHS_DEVICE_ARRAYS,
                                              out.data_ptr() if n else None, C.byref(st)))
             return (out, stats_dict(st)) if stats else out
+        out = np.zeros((n, 8), np.float32)
+        self._check(lib().hj_trace_paths(self._h, rays.ctypes.data, n, spp, o, 0, out.ctypes.data, C.byref(st)))
+        return (out, stats_dict(st)) if stats else out
+
+    def _path_rays(self, what, rays, seeds):
+        """The ray argument of the path queries, checked before any call -> (rays, on_gpu): a contiguous float32 (n, 8) torch tensor
+        on the renderer's GPU as it is, or a contiguous float32 numpy array; with `seeds` a copy whose column 6 holds them."""
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not (rays.is_cuda and rays.device.index == self.device and rays.dtype == torch.float32 and rays.is_contiguous()
+                    and rays.dim() == 2 and rays.shape[1] == 8):
+                raise ValueError(f"{what}: a contiguous float32 tensor of (n, 8) on GPU {self.device} is needed"
+                                 f" (got {tuple(rays.shape)} {rays.dtype} on {rays.device})")
+            n = rays.shape[0]
+            if seeds is not None:
+                if not (type(seeds).__module__.split(".")[0] == "torch" and seeds.device == rays.device and seeds.dtype == torch.int32
+                        and tuple(seeds.shape) == (n,)):
+                    raise ValueError(f"{what}: seeds must be an int32 tensor of ({n},) on GPU {self.device}")
+                rays = rays.clone()
+                rays.view(torch.int32)[:, 6] = seeds
+            return rays, True
         rays = np.asarray(rays)
         if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError(f"trace_paths: a float32 array of (n, 8) is needed (got {rays.shape} {rays.dtype})")
+            raise ValueError(f"{what}: a float32 array of (n, 8) is needed (got {rays.shape} {rays.dtype})")
         if seeds is not None:
             seeds = np.asarray(seeds)
             if seeds.dtype != np.uint32 or seeds.shape != (len(rays),):
-                raise ValueError(f"trace_paths: seeds must be a uint32 array of ({len(rays)},) (got {seeds.shape} {seeds.dtype})")
+                raise ValueError(f"{what}: seeds must be a uint32 array of ({len(rays)},) (got {seeds.shape} {seeds.dtype})")
             rays = np.array(rays, np.float32, order="C")              # (a copy)
             rays.view(np.uint32)[:, 6] = seeds
-        rays = np.ascontiguousarray(rays)
-        out = np.zeros((len(rays), 8), np.float32)
-        self._check(lib().hj_trace_paths(self._h, rays.ctypes.data, len(rays), spp, o, 0, out.ctypes.data, C.byref(st)))
-        return (out, stats_dict(st)) if stats else out
+        return np.ascontiguousarray(rays), False
+
+    def trace_paths_adaptive(self, rays, seeds=None, spp_min=4, spp_step=4, spp_max=64, rel_error=0.05, floor=0.01, opts=None, stats=False,
+                             moments=False):
+        """hj_trace_paths_adaptive: `trace_paths` with the number of samples decided per ray on the device.  Every ray gets spp_min
+        samples, then spp_step more a round (never more than spp_max in all) until the standard error of its mean luminance is at
+        most rel_error * max(mean luminance, floor) - include/hijiki_hip.h spells the rule out.  -> (n, 8) float32 records as
+        `trace_paths` gives them, word 3 = the samples the ray received: record i is what `trace_paths` returns for ray i with that
+        spp.  rays, seeds, opts and the array / tensor handling are `trace_paths`'.  moments=True: also an (n, 4) float32 array
+        (tensor) of S1, S2 (the sums of the samples' luminance and of its square), the last sem2 and the sample count as uint32 bits.
+        stats=True: also the statistics dict (bounce_rounds = rounds run).  Returns samples [, moments] [, statistics]."""
+        spp_min, spp_step, spp_max, rel_error, floor = int(spp_min), int(spp_step), int(spp_max), float(rel_error), float(floor)
+        if not (2 <= spp_min <= spp_max <= 65536 and spp_step >= 1):
+            raise ValueError(f"trace_paths_adaptive: 2 <= spp_min <= spp_max <= 65536 and spp_step >= 1 are needed (got {spp_min}, {spp_max}, {spp_step})")
+        if 1 + -(-(spp_max - spp_min) // spp_step) > 64:
+            raise ValueError(f"trace_paths_adaptive: more than 64 rounds from {spp_min} to {spp_max} in steps of {spp_step}")
+        if not (0.0 <= rel_error < float("inf") and 0.0 <= floor < float("inf")):
+            raise ValueError(f"trace_paths_adaptive: rel_error and floor must be finite and >= 0 (got {rel_error}, {floor})")
+        a = abi.AdaptiveOpts(spp_min, spp_step, spp_max, rel_error, floor)
+        st = abi.RenderStats()
+        o = C.byref(opts) if opts is not None else None
+        rays, on_gpu = self._path_rays("trace_paths_adaptive", rays, seeds)
+        n = len(rays)
+        if on_gpu:
+            import torch
+            out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+            mom = torch.empty((n, 4), dtype=torch.float32, device=rays.device) if moments else None
+            torch.cuda.current_stream(rays.device).synchronize()      # (the allocations and whatever wrote `rays`)
+            self._check(lib().hj_trace_paths_adaptive(self._h, rays.data_ptr() if n else None, n, C.byref(a), o, abi.PATHS_DEVICE_ARRAYS,
+                                                      out.data_ptr() if n else None, mom.data_ptr() if moments and n else None, C.byref(st)))
+        else:
+            out = np.zeros((n, 8), np.float32)
+            mom = np.zeros((n, 4), np.float32) if moments else None
+            self._check(lib().hj_trace_paths_adaptive(self._h, rays.ctypes.data, n, C.byref(a), o, 0, out.ctypes.data,
+                                                      mom.ctypes.data if moments else None, C.byref(st)))
+        res = (out,) + ((mom,) if moments else ()) + ((stats_dict(st),) if stats else ())
+        return res if len(res) > 1 else out
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

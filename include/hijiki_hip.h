@@ -548,6 +548,41 @@ int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, 
 int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
                    uint32_t flags, float* samples, hj_render_stats* stats /* may be NULL */);
 
+/* hj_trace_paths_adaptive (ABI 0.13): hj_trace_paths with the number of samples decided per ray, on the device - for baking, where most
+ * rays converge in a handful of samples and a minority needs many.  rays, samples, flags (HJ_PATHS_DEVICE_ARRAYS), opts and the origin
+ * domain are exactly hj_trace_paths'; no counterpart in the reference.
+ *   Rounds.  Round 0 gives every ray spp_min samples; round r >= 1 gives every ray that is still active min(spp_step, spp_max - n_i)
+ *     samples, n_i being the samples ray i has had, with the sample index k continuing at n_i (sample k starts from seedRng(seed_i + k),
+ *     as in hj_trace_paths).  1 + ceil((spp_max - spp_min) / spp_step) rounds at most, and at most 64.
+ *   Running sums per ray, all float32, from +0, in ascending k, uncontracted, continued from round to round (never re-associated as
+ *     per-round partial sums):  R += r; G += g; B += b;  Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b;  S1 += Y;  S2 += Y * Y.
+ *   Stop rule, evaluated after each round with m = n_i (float32, in this order, divisions correctly rounded, max = fmaxf):
+ *       mean = S1 / (float)m;   var = max(0, S2 - S1 * mean) / (float)(m - 1);   sem2 = var / (float)m;
+ *       thr = rel_error * max(mean, floor);   ray i stops when sem2 <= thr * thr or n_i == spp_max
+ *     - the standard error of the mean luminance is at most rel_error * max(mean luminance, floor).  A NaN sem2 compares false: such a
+ *     ray stops only at spp_max.  Stopping on a ray's own samples biases its estimate (rays stop more readily while their samples
+ *     happen to be dark and alike); spp_min and floor bound that, rel_error = 0 removes it (every ray gets spp_max).
+ *   samples: n x 8 floats, hj_trace_paths' record with [3] = (float)n_i.  Record i is bit for bit what hj_trace_paths returns for ray i
+ *     with spp = n_i; it depends on ray i, the adaptive opts, opts and the scene alone.
+ *   moments (may be NULL): n x 4 floats - S1, S2, the sem2 of the last evaluation, n_i as uint32 bits.
+ *   stats (may be NULL): paths = the sum of n_i; closest_rays, shadow_rays, hits, unoccluded_shadow_rays, shadow_rays_proven_free summed
+ *     over all launches; batches = launches of the path kernel; bounce_rounds = adaptive rounds run; total_ms; every other field 0.
+ * Beside hj_trace_paths' path state the context keeps, per ray of the largest call, 64 bytes (running sums, flags, two index lists,
+ * the next round's rays); host arrays are staged whole, once per call (80 bytes per ray more).  The call synchronises once per round.
+ * HJ_ERR_INVALID, checked before anything else and without a device, in hj_trace_paths' order: what hj_trace_paths refuses of rays,
+ *   samples, flags, n and opts; null adaptive opts, spp_min < 2, spp_step == 0, spp_max < spp_min, spp_max > 65536, a rel_error or
+ *   floor that is NaN, negative or infinite, more than 64 rounds, misaligned moments with device arrays.  The null context,
+ *   HJ_ERR_STATE and n == 0 as in hj_trace_paths.  A refused call writes nothing. */
+typedef struct hj_adaptive_opts {
+  uint32_t spp_min;    /* samples of the first round, >= 2                                   */
+  uint32_t spp_step;   /* samples of every later round, >= 1                                 */
+  uint32_t spp_max;    /* a ray never gets more; spp_min <= spp_max <= 65536                 */
+  float    rel_error;  /* stop when the standard error of the mean luminance is at most      */
+  float    floor;      /*   rel_error * max(mean luminance, floor); both finite, >= 0        */
+} hj_adaptive_opts;
+int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const hj_adaptive_opts* adaptive, const hj_render_opts* opts /* NULL = defaults */,
+                            uint32_t flags, float* samples, float* moments /* may be NULL */, hj_render_stats* stats /* may be NULL */);
+
 /* ------------------------------------------------------------------- probes */
 
 /* Function-level probes used by the parity tests (no counterpart in the
