@@ -16,7 +16,7 @@ HOST_HDR = hijiki_amd/csrc/host/scene.hpp hijiki_amd/csrc/host/blockgen.hpp incl
 # scene_update.hip, lbvh_build.hip, tree_vote.hip, texture.hip, environment.hip, step_probe.hip, ray_query.hip, path_query.hip and path_adaptive.hip hold device code.  The register / scratch / LDS report of the path kernels: hijiki_amd/lib/resource_usage.txt.
 HIP_UNITS = context scene_upload scene_relayout scene_update render render_calls comm lbvh_build tree_vote texture environment step_probe ray_query path_query path_adaptive
 HIP_OBJ = $(HIP_UNITS:%=build/obj/%.o) build/obj/blockgen.o build/obj/light_grid.o
-HIP_HDR = $(wildcard hijiki_amd/csrc/kernels/*.h) hijiki_amd/csrc/api/hj_internal.h hijiki_amd/csrc/api/hj_tuning.h hijiki_amd/csrc/api/light_grid.hpp hijiki_amd/csrc/api/scene_relayout.hpp hijiki_amd/csrc/api/refit_pass.hpp hijiki_amd/csrc/api/tree_vote.hpp include/hijiki_hip.h hijiki_amd/csrc/host/blockgen.hpp
+HIP_HDR = $(wildcard hijiki_amd/csrc/kernels/*.h) hijiki_amd/csrc/api/hj_internal.h hijiki_amd/csrc/api/hj_tuning.h hijiki_amd/csrc/api/light_grid.hpp hijiki_amd/csrc/api/scene_relayout.hpp hijiki_amd/csrc/api/refit_pass.hpp hijiki_amd/csrc/api/guard_box.hpp hijiki_amd/csrc/api/tree_vote.hpp include/hijiki_hip.h hijiki_amd/csrc/host/blockgen.hpp
 HIP_FLAGS = --offload-arch=$(ARCH) -std=c++17 -O3 -fPIC $(FP_STRICT) -fhip-fp32-correctly-rounded-divide-sqrt -fvisibility=hidden \
             -Wall -Wno-unused-function $(HIP_EXTRA)
 

@@ -4,6 +4,8 @@
 // scene_upload.hip (which stays for small trees, where it takes a millisecond, and for arrays that are not trees), step by step:
 //
 //   k_rl_triangles                 tri_isect / tri_shade, one thread per triangle
+//   k_rl_guard_want, _unpair, scan, k_rl_guard_build    leaf guards (HJ_LEAF_GUARDS): the uploaded array with a one-child inner node in
+//                                  front of every guarded leaf - what the steps below work on, as the host's do
 //   k_rl_init, k_rl_links          area, parent and parent count of every node: the device path wants a TREE (every node but
 //                                  the root has exactly one parent, children lie behind their parent); anything else -> host path
 //   k_rl_collapse_level  x depth   the collapse (an inner node over two inner nodes dropped when its area is > thr x its nearest
@@ -19,6 +21,7 @@
 //
 // The image does not depend on the layout; tests render every scene kind through both paths (HJ_UPLOAD_DEVICE = 0 / 1).
 #include "hj_internal.h"
+#include "guard_box.hpp"
 #include "scene_relayout.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -34,8 +37,9 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr int kMaxKids = 64;            // children of a kept node after the collapse (a collapsed binary tree: 2^levels); more -> host path
 
 struct RL {
-  const hj_bvh_node* bvh;
+  const hj_bvh_node* bvh;              // the array the steps work on: the uploaded one, or the guarded one
   uint32_t N, first_tri, nshapes;
+  uint32_t guarded;                     // bvh holds guard nodes: inner nodes over one leaf, which share their exit
   float thr;                            // collapse threshold
   float* sa;
   float* anc;
@@ -62,6 +66,46 @@ __global__ void k_rl_triangles(const hj_triangle* __restrict__ tris, const hj_ve
   tri_records(tris, verts, i, isect, shade);
 }
 
+// Leaf guards (scene_upload.hip "Guard nodes for single leaves"): which leaves of the uploaded array get one ...
+__global__ void k_rl_guard_want(const hj_bvh_node* __restrict__ bvh, uint32_t n0, uint32_t ns, uint32_t guard_spheres, uint32_t guard_flat,
+                                uint32_t* __restrict__ want) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n0) return;
+  const uint32_t sh = bvh[i].shape_index;
+  want[i] = sh == HJ_BVH_INNER ? 0u : (sh < ns ? guard_spheres : guard_flat);
+}
+// ... but the two triangle leaves of a future pair node, which keep their parent's box as their guard (a launch of its own: it
+// clears what k_rl_guard_want set)
+__global__ void k_rl_guard_unpair(const hj_bvh_node* __restrict__ bvh, uint32_t n0, uint32_t first_tri, uint32_t* __restrict__ want) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n0 || i + 2 >= n0 || bvh[i].shape_index != HJ_BVH_INNER) return;
+  const uint32_t l = i + 1, rr = bvh[l].exit_index;
+  if (rr != l + 1) return;                                    // (rr = i + 2 < n0 from here on)
+  const uint32_t sl = bvh[l].shape_index, sr = bvh[rr].shape_index;
+  if (sl == HJ_BVH_INNER || sr == HJ_BVH_INNER) return;
+  if (sl >= first_tri && sr >= first_tri) { want[l] = 0; want[rr] = 0; }
+}
+// The guarded array: node i at gidx[i] = i + before[i] + want[i], its guard - the shape's own padded bounds, the leaf's exit - in
+// front of it; exits move with the nodes they name (an exit beyond the array stays beyond it).  before = exclusive scan of want.
+__global__ void k_rl_guard_build(const hj_bvh_node* __restrict__ bvh, uint32_t n0, RefitShapes shapes, float pad_abs,
+                                 const uint32_t* __restrict__ want, const uint32_t* __restrict__ before, uint32_t guards,
+                                 hj_bvh_node* __restrict__ out, uint32_t* __restrict__ gidx) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n0) return;
+  hj_bvh_node nd = bvh[i];
+  const uint32_t e = nd.exit_index;
+  nd.exit_index = e < n0 ? e + before[e] : e + guards;
+  uint32_t at = i + before[i];
+  if (want[i]) {
+    hj_bvh_node g = nd;
+    g.shape_index = HJ_BVH_INNER;
+    su_guard_box(shapes, nd.shape_index, pad_abs, g.aabb_min, g.aabb_max);
+    out[at++] = g;
+  }
+  out[at] = nd;
+  gidx[i] = at;
+}
+
 __global__ void k_rl_init(RL r) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= r.N) return;
@@ -83,6 +127,11 @@ __global__ void k_rl_links(RL r) {
   const uint32_t l = i + 1;
   if (l >= r.N) { atomicOr(&r.err[0], 1u); return; }
   const uint32_t rr = r.bvh[l].exit_index;
+  if (r.guarded && !rl_inner(r, l) && rr == r.bvh[i].exit_index) {   // a guard: its only child is its leaf
+    r.parent[l] = i;
+    atomicAdd(&r.nparents[l], 1u);
+    return;
+  }
   if (rr >= r.N || rr <= l || r.bvh[rr].exit_index != r.bvh[i].exit_index) { atomicOr(&r.err[0], 1u); return; }   // (the right child's exit is its parent's)
   r.parent[l] = i; r.parent[rr] = i;
   atomicAdd(&r.nparents[l], 1u); atomicAdd(&r.nparents[rr], 1u);
@@ -102,7 +151,10 @@ __global__ void k_rl_collapse_level(RL r, uint32_t L) {
   // in a register it re-used for a load inside a narrower exec mask - lanes whose left child is a leaf then formed a wild address)
   const size_t l = (size_t)i + 1;
   const hj_bvh_node ni = r.bvh[i], nl = r.bvh[l];
-  const size_t rr = nl.exit_index;
+  // (a guard's only child is its leaf, and their common exit may lie beyond the array: the leaf stands in for the sibling, which
+  // keeps the guard - a leaf child - and hands the leaf the guard's area and depth L + 1, as the host does)
+  const bool single = (r.guarded != 0) & (nl.shape_index != HJ_BVH_INNER) & (nl.exit_index == ni.exit_index);
+  const size_t rr = single ? l : (size_t)nl.exit_index;
   const hj_bvh_node nr = r.bvh[rr];
   bool in = true;
   for (int k = 0; k < 3; k++)
@@ -227,15 +279,18 @@ __global__ void k_rl_group_offsets(RL r, uint32_t L) {
 
 // the second copy of the tree (api/scene_upload.hip, kernels/hj_intersect.h general_position): the reference's own array, record i
 // at base + i - nothing collapsed; pair nodes keep their mark, their two leaves' records are never reached
-__global__ void k_rl_records2(RL r, float4* __restrict__ dev, uint32_t base) {
+// (bvh0, n0: the uploaded array; gidx: where its nodes are in r.bvh, NULL without guards)
+__global__ void k_rl_records2(RL r, const hj_bvh_node* __restrict__ bvh0, uint32_t n0, const uint32_t* __restrict__ gidx,
+                              float4* __restrict__ dev, uint32_t base) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= r.N) return;
-  const hj_bvh_node nd = r.bvh[i];
+  if (i >= n0) return;
+  const hj_bvh_node nd = bvh0[i];
+  const uint32_t g = gidx ? gidx[i] : i;
   uint32_t a;
   if (nd.shape_index != HJ_BVH_INNER) a = nd.shape_index;
-  else if (r.pair_flag[i]) a = hj::kInnerFlag | hj::kPairFlag | r.pair_idx[i];
-  else a = hj::kInnerFlag | (i + 1 < r.N ? base + i + 1 : hj::kEndOfWalk);
-  const uint32_t b = nd.exit_index < r.N ? base + nd.exit_index : hj::kEndOfWalk;
+  else if (r.pair_flag[g]) a = hj::kInnerFlag | hj::kPairFlag | r.pair_idx[g];
+  else a = hj::kInnerFlag | (i + 1 < n0 ? base + i + 1 : hj::kEndOfWalk);
+  const uint32_t b = nd.exit_index < n0 ? base + nd.exit_index : hj::kEndOfWalk;
   float4* rec = dev + 2 * ((size_t)base + i);
   rec[0] = make_float4(nd.aabb_min[0], nd.aabb_min[1], nd.aabb_min[2], __uint_as_float(a));
   rec[1] = make_float4(nd.aabb_max[0], nd.aabb_max[1], nd.aabb_max[2], __uint_as_float(b));
@@ -259,10 +314,14 @@ __global__ void k_rl_records(RL r, float4* __restrict__ dev) {
   rec[1] = make_float4(nd.aabb_max[0], nd.aabb_max[1], nd.aabb_max[2], __uint_as_float(b));
 }
 
-// where every node of the uploaded array went (hj_scene_update_shapes); this route makes no guard records
-__global__ void k_rl_node_map(RL r, uint2* __restrict__ where) {
+// where every node of the uploaded array went (hj_scene_update_shapes): its record, its guard's record (a guard is the record in
+// front of its leaf in the guarded array: an inner node over one child, which the collapse never drops)
+__global__ void k_rl_node_map(RL r, uint32_t n0, const uint32_t* __restrict__ gidx, uint2* __restrict__ where) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < r.N) where[i] = make_uint2(r.del[i] ? kNone : r.map[i], kNone);
+  if (i >= n0) return;
+  const uint32_t g = gidx ? gidx[i] : i;
+  const bool has_guard = gidx && g != (i ? gidx[i - 1] + 1u : 0u);
+  where[i] = make_uint2(r.del[g] ? kNone : r.map[g], has_guard && !r.del[g - 1] ? r.map[g - 1] : kNone);
 }
 
 }  // namespace
@@ -291,14 +350,15 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
                        int node_order, float collapse_thr, bool timing, DevBufs& keep, RelayoutOut& out, const hj_bvh_node* d_tree) {
   // d_tree: the skip-link array is on the device already (hj_build_bvh_device's tree: hj_context::resident); s->bvh is not read then
   out = RelayoutOut{};
-  const size_t N = s->num_bvh_nodes;
-  if (N < 3 || N >= 0x3FFFFFFFu) return HJ_ERR_UNSUPPORTED;
+  const size_t N0 = s->num_bvh_nodes;                       // the uploaded array; N: the array the steps work on (with the guards)
+  if (N0 < 3 || N0 >= 0x3FFFFFFFu) return HJ_ERR_UNSUPPORTED;
+  size_t N = N0;
   hipStream_t st = ctx->stream;
   StageClock clock{timing, "hj_scene_upload (device): %-24s %8.2f ms\n", st};
   DevBufs tmp(ctx);                                         // scratch: released on return
   int rc = HJ_OK;
-  const uint32_t n32 = (uint32_t)N, nt = (uint32_t)s->num_triangles;
-  const dim3 blk(256), grid((n32 + 255) / 256);
+  const uint32_t n0 = (uint32_t)N0, nt = (uint32_t)s->num_triangles;
+  const dim3 blk(256), grid0((n0 + 255) / 256);
 
   // triangle records
   float4 *isect = nullptr, *shade = nullptr;
@@ -310,11 +370,57 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
   // the skip-link array as it is
   hj_bvh_node* d_bvh = const_cast<hj_bvh_node*>(d_tree);      // (the kernels only read it)
   if (!d_bvh) {
-    HJ_TRY(tmp.alloc(d_bvh, N));
-    HJ_HIP(ctx, hipMemcpyAsync(d_bvh, s->bvh, sizeof(hj_bvh_node) * N, hipMemcpyHostToDevice, st));
+    HJ_TRY(tmp.alloc(d_bvh, N0));
+    HJ_HIP(ctx, hipMemcpyAsync(d_bvh, s->bvh, sizeof(hj_bvh_node) * N0, hipMemcpyHostToDevice, st));
   }
+  const hj_bvh_node* d_bvh0 = d_bvh;
+
+  // leaf guards (HJ_LEAF_GUARDS, scene_upload.hip): 2 (default) every triangle or quad leaf that does not become half of a pair
+  // node; 1 sphere leaves only, 3 all leaves (not exact).  The steps below then work on the guarded array.
+  uint32_t* gidx = nullptr;
+  {
+    const int mode = ctx->tuning.leaf_guards;
+    const bool guard_spheres = mode == 1 || mode == 3, guard_flat = mode >= 2;
+    if ((guard_spheres && s->num_spheres != 0) || (guard_flat && s->num_quads + s->num_triangles != 0)) {
+      uint32_t *want = nullptr, *before = nullptr;
+      HJ_TRY(tmp.alloc(want, N0)); HJ_TRY(tmp.alloc(before, N0 + 1));
+      hipLaunchKernelGGL(k_rl_guard_want, grid0, blk, 0, st, d_bvh0, n0, (uint32_t)s->num_spheres, guard_spheres ? 1u : 0u, guard_flat ? 1u : 0u, want);
+      if (guard_flat) hipLaunchKernelGGL(k_rl_guard_unpair, grid0, blk, 0, st, d_bvh0, n0, (uint32_t)(s->num_spheres + s->num_quads), want);
+      size_t bytes = 0;
+      HJ_HIP(ctx, rocprim::exclusive_scan(nullptr, bytes, want, before, 0u, N0, rocprim::plus<uint32_t>(), st));
+      uint8_t* scan_tmp = nullptr;
+      HJ_TRY(tmp.alloc(scan_tmp, std::max<size_t>(bytes, 16)));
+      HJ_HIP(ctx, rocprim::exclusive_scan(scan_tmp, bytes, want, before, 0u, N0, rocprim::plus<uint32_t>(), st));
+      uint32_t last[2] = {0, 0};
+      hj_bvh_node root{};
+      HJ_HIP(ctx, hipMemcpyAsync(&last[0], before + (N0 - 1), 4, hipMemcpyDeviceToHost, st));
+      HJ_HIP(ctx, hipMemcpyAsync(&last[1], want + (N0 - 1), 4, hipMemcpyDeviceToHost, st));
+      HJ_HIP(ctx, hipMemcpyAsync(&root, d_bvh0, sizeof root, hipMemcpyDeviceToHost, st));
+      HJ_HIP(ctx, hipStreamSynchronize(st));
+      const uint32_t guards = last[0] + last[1];
+      if (guards != 0 && N0 + guards < 0x3FFFFFFFu) {
+        RefitShapes shapes{};
+        shapes.ns = (uint32_t)s->num_spheres; shapes.nq = (uint32_t)s->num_quads; shapes.nt = nt;
+        shapes.triangles = d_tris; shapes.vertices = d_verts;
+        float4 *d_spheres = nullptr, *d_quads = nullptr;
+        HJ_TRY(tmp.alloc(d_spheres, std::max<size_t>(s->num_spheres, 1))); HJ_TRY(tmp.alloc(d_quads, std::max<size_t>(3 * s->num_quads, 1)));
+        if (s->num_spheres) HJ_HIP(ctx, hipMemcpyAsync(d_spheres, s->spheres, sizeof(float4) * s->num_spheres, hipMemcpyHostToDevice, st));
+        if (s->num_quads) HJ_HIP(ctx, hipMemcpyAsync(d_quads, s->quads, sizeof(float4) * 3 * s->num_quads, hipMemcpyHostToDevice, st));
+        shapes.spheres = d_spheres; shapes.quads = d_quads;
+        hj_bvh_node* guarded = nullptr;
+        N = N0 + guards;
+        HJ_TRY(tmp.alloc(guarded, N)); HJ_TRY(tmp.alloc(gidx, N0));
+        hipLaunchKernelGGL(k_rl_guard_build, grid0, blk, 0, st, d_bvh0, n0, shapes, guard_pad_abs(root.aabb_min, root.aabb_max, s->camera.position),
+                           want, before, guards, guarded, gidx);
+        d_bvh = guarded;
+      }
+    }
+  }
+  clock.mark("leaf guards");
+  const uint32_t n32 = (uint32_t)N;
+  const dim3 grid((n32 + 255) / 256);
   RL r{};
-  r.bvh = d_bvh; r.N = n32; r.first_tri = (uint32_t)(s->num_spheres + s->num_quads);
+  r.bvh = d_bvh; r.N = n32; r.guarded = gidx ? 1u : 0u; r.first_tri = (uint32_t)(s->num_spheres + s->num_quads);
   r.nshapes = (uint32_t)(s->num_spheres + s->num_quads + s->num_triangles);
   r.thr = collapse_thr;
   HJ_TRY(tmp.alloc(r.sa, N)); HJ_TRY(tmp.alloc(r.anc, N)); HJ_TRY(tmp.alloc(r.parent, N)); HJ_TRY(tmp.alloc(r.nparents, N));
@@ -433,17 +539,17 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
   clock.mark("node order");
 
   // device records (zero-filled padding), placed so that the array does not cross a 4 GiB boundary (kernels/hj_walk.h)
-  if ((size_t)m_all + N >= hj::kEndOfWalk) return set_error(ctx, HJ_ERR_UNSUPPORTED, "BVH of %zu records: too large", (size_t)m_all + N);
-  const size_t rec_bytes = sizeof(float4) * 2 * ((size_t)m_all + N);      // the two copies of the tree
+  if ((size_t)m_all + N0 >= hj::kEndOfWalk) return set_error(ctx, HJ_ERR_UNSUPPORTED, "BVH of %zu records: too large", (size_t)m_all + N0);
+  const size_t rec_bytes = sizeof(float4) * 2 * ((size_t)m_all + N0);     // the two copies of the tree
   float4* dev = nullptr;
   HJ_TRY(place_node_array(keep, rec_bytes, M, &dev));
   HJ_HIP(ctx, hipMemsetAsync(dev, 0, rec_bytes, st));
   hipLaunchKernelGGL(k_rl_records, grid, blk, 0, st, r, dev);
-  hipLaunchKernelGGL(k_rl_records2, grid, blk, 0, st, r, dev, m_all);
+  hipLaunchKernelGGL(k_rl_records2, grid0, blk, 0, st, r, d_bvh0, n0, gidx, dev, m_all);
   out.nodes = dev;
   uint2* where = nullptr;
-  HJ_TRY(keep.alloc(where, N));
-  hipLaunchKernelGGL(k_rl_node_map, grid, blk, 0, st, r, where);
+  HJ_TRY(keep.alloc(where, N0));
+  hipLaunchKernelGGL(k_rl_node_map, grid0, blk, 0, st, r, n0, gidx, where);
   out.node_map = where;
   uint32_t root = 0;
   HJ_HIP(ctx, hipMemcpyAsync(&root, r.map, 4, hipMemcpyDeviceToHost, st));
@@ -451,7 +557,7 @@ int relayout_on_device(hj_context* ctx, const hj_scene_desc* s, const hj_triangl
   HJ_HIP(ctx, hipGetLastError());
   clock.mark("device records");
   out.tri_isect = isect; out.tri_shade = shade; out.tri_pair = pairs;
-  out.num_nodes = m_all + n32; out.root = root; out.root2 = m_all; out.num_hot = hot; out.num_pairs = num_pairs; out.kept = M;
+  out.num_nodes = m_all + n0; out.root = root; out.root2 = m_all; out.num_hot = hot; out.num_pairs = num_pairs; out.kept = M;
   return HJ_OK;
 }
 

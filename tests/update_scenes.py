@@ -54,6 +54,24 @@ def parents_of(nodes):
     return parent
 
 
+def expected_guards(where, cs, want):
+    """(guarded, lo, hi, widened, parent): the uploaded nodes that have a guard, the box each guard must hold - the formula's, or,
+    where the leaf's parent has no record and the padded box is not inside the parent's box, the parent's box -, which of them hold
+    their parent's box, and the parents.  `want` = the uploaded (or refitted) tree, `where` = Renderer.scene_tree()["map"]."""
+    guarded = np.nonzero(where[:, 1] != NONE)[0]
+    f = want.view(F)
+    gmin, gmax = guard_boxes(cs, f[0, 0:3], f[0, 4:7])
+    shape = want[guarded, 3]
+    assert (shape != NONE).all(), "a guard in front of an inner node"
+    lo, hi = gmin[shape], gmax[shape]
+    p = parents_of(want)[guarded]
+    assert (p >= 0).all()
+    plo, phi = f[p, 0:3], f[p, 4:7]
+    widened = (where[p, 0] == NONE) & ~((lo >= plo).all(axis=1) & (hi <= phi).all(axis=1))
+    lo, hi = np.where(widened[:, None], plo, lo), np.where(widened[:, None], phi, hi)
+    return guarded, lo, hi, widened, p
+
+
 def check_records(tree, cs, want):
     """Every assertion of 'Records': `tree` = Renderer.scene_tree() after an update, `want` = the numpy refit of the uploaded topology.
     A guard holds the formula's box - or, where the upload collapsed the leaf's parent and the padded box is no longer inside the
@@ -65,18 +83,9 @@ def check_records(tree, cs, want):
     assert (boxes_of(rec[root2:root2 + n0]) == boxes_of(want)).all(), "second copy"
     mapped = np.nonzero(where[:, 0] != NONE)[0]
     assert (boxes_of(rec[where[mapped, 0]]) == boxes_of(want[mapped])).all(), "mapped records"
-    guarded = np.nonzero(where[:, 1] != NONE)[0]
-    if len(guarded):
+    if (where[:, 1] != NONE).any():
         f = want.view(F)
-        gmin, gmax = guard_boxes(cs, f[0, 0:3], f[0, 4:7])
-        shape = want[guarded, 3]
-        assert (shape != NONE).all()
-        lo, hi = gmin[shape], gmax[shape]
-        p = parents_of(want)[guarded]
-        assert (p >= 0).all()
-        plo, phi = f[p, 0:3], f[p, 4:7]
-        widened = (where[p, 0] == NONE) & ~((lo >= plo).all(axis=1) & (hi <= phi).all(axis=1))
-        lo, hi = np.where(widened[:, None], plo, lo), np.where(widened[:, None], phi, hi)
+        guarded, lo, hi, widened, p = expected_guards(where, cs, want)
         g = rec[where[guarded, 1]].view(F)
         assert (g[:, 0:3].view(np.uint32) == lo.view(np.uint32)).all() and (g[:, 4:7].view(np.uint32) == hi.view(np.uint32)).all(), "guard records"
         # what the collapse needs: every record under a collapsed node lies inside that node's box
@@ -86,7 +95,7 @@ def check_records(tree, cs, want):
             mine = p == c
             assert (g[mine, 0:3] >= f[c, 0:3]).all() and (g[mine, 4:7] <= f[c, 4:7]).all(), "a guard sticks out of its collapsed parent"
         return len(mapped), len(guarded), int(widened.sum())
-    return len(mapped), len(guarded), 0
+    return len(mapped), 0, 0
 
 
 
