@@ -28,6 +28,9 @@ UPDATE_NO_LIGHT_GRID = 2
 TRACE_ANY_HIT = 1                 # hj_trace_rays flags
 TRACE_DEVICE_ARRAYS = 2
 PATHS_DEVICE_ARRAYS = 1           # hj_trace_paths flag
+GATHER_DEVICE_ARRAYS = 1          # hj_trace_irradiance flags
+GATHER_SPHERE = 2
+GATHER_SH9 = 4                    # (only together with GATHER_SPHERE)
 # hj_debug_num: enum hj_num_op in its order, the record sizes and the cap
 NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "dot3", "cross3", "normalize3", "reflect3", "rng_seed",
            "rng_uint", "rng_float", "rand_cos_hemisphere", "rand_uniform_sphere", "rand_barycentric")

@@ -24,6 +24,10 @@
 //                         its path state is hj_context::PathQuery, a PathState
 //   api/path_adaptive.hip hj_trace_paths_adaptive: rounds of that path kernel (path_query_pass) over the rays still active, with the
 //                         k_pa_* kernels between them (running sums and stop rule, order-preserving compaction); includes hj_num.h only
+//   api/gather_query.hip  hj_trace_irradiance: gather queries at caller-given points (includes the kernel headers up to hj_stages.h and
+//                         defines its own kernels beside the path kernels: the round loop of api/path_query.hip restated with a top-up
+//                         that draws a direction at a point, and the per-point reduction); plans with path_query_plan and runs in
+//                         hj_context::PathQuery's path state and staging
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -357,6 +361,8 @@ struct hj_context {
   // framebuffer alone.  Reused by every call, freed with the context.
   // hj_trace_paths_adaptive (api/path_adaptive.hip) runs its rounds in the same path state and adds, per ray of a call: the running
   // sums, the active flags, two index lists and one compacted ray array (ping-pong of the compaction), and the moments' staging.
+  // hj_trace_irradiance (api/gather_query.hip) runs in the same path state and stages host arrays in in_rays (a chunk of points) and
+  // out_samples (their records: 32 bytes a point, 144 with HJ_GATHER_SH9).
   struct PathQuery : hjapi::PathState {
     hjapi::DevBuf in_rays, out_samples;   // staging: one chunk of rays (adaptive: all rays of the call), their sample records
     hjapi::DevBuf pa_sums, pa_s2;         // adaptive: float4 (R, G, B, S1) and float S2 per ray

@@ -25,7 +25,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_pipeline_wait", "hj_debug_light_grid", "hj_debug_light_grid_planes", "hj_tune_bvh_device", "hj_bvh_device_read",
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
-           "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive")
+           "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
+           "hj_trace_irradiance")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -85,6 +86,8 @@ def lib():
                                      C.POINTER(abi.RenderStats)]               # (host or device pointers)
         L.hj_trace_paths_adaptive.argtypes = [vp, vp, C.c_size_t, C.POINTER(abi.AdaptiveOpts), C.POINTER(abi.RenderOpts), C.c_uint32, vp, vp,
                                               C.POINTER(abi.RenderStats)]      # (host or device pointers)
+        L.hj_trace_irradiance.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(abi.RenderOpts), C.c_uint32, vp,
+                                          C.POINTER(abi.RenderStats)]          # (host or device pointers)
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -538,6 +541,46 @@ class Renderer:
                                                       mom.ctypes.data if moments else None, C.byref(st)))
         res = (out,) + ((mom,) if moments else ()) + ((stats_dict(st),) if stats else ())
         return res if len(res) > 1 else out
+
+    def trace_irradiance(self, points, seeds=None, spp=1, sphere=False, sh9=False, opts=None, stats=None):
+        """hj_trace_irradiance: the radiance gathered at (n, 8) points (position, normal of any length - used as given -, a uint32
+        seed as the bits of word 6, a reserved word).  Sample k of point i draws its direction on the device from seedRng(seed_i + k):
+        cosine-weighted about the normal, or with sphere=True uniform over the sphere (the normal is ignored), and the path goes on
+        from there as a sample of `trace_paths` does.  -> (n, 8) float32: the float32 sum of the `spp` samples' radiance, (float)spp,
+        the number of samples whose first segment hit something, the nearest such hit's t (+inf if none), two zeros - irradiance is
+        pi / spp x words 0..2, ambient occlusion word 4 / spp.  sh9=True (only with sphere=True): (n, 36), behind those eight words the
+        sums of Y_j(direction) * radiance for the nine real spherical harmonics of bands 0..2 (word 8 + 3 j + c), word 35 zero.
+        seeds, opts and the array / tensor handling are `trace_paths'`: a numpy array gives a numpy array; a contiguous float32 torch
+        tensor on the renderer's GPU is read in place and gives a tensor on that GPU, torch's current stream synchronised first.
+        With host arrays in hemisphere mode a normal that is not finite or all zero is refused; with tensors that is the caller's
+        contract.  stats: true returns (records, statistics dict)."""
+        spp = int(spp)
+        if not 1 <= spp <= 65536:
+            raise ValueError(f"trace_irradiance: spp {spp} outside [1, 65536]")
+        if sh9 and not sphere:
+            raise ValueError("trace_irradiance: sh9 needs sphere=True (the basis is integrated over the whole sphere)")
+        flags = (abi.GATHER_SPHERE if sphere else 0) | (abi.GATHER_SH9 if sh9 else 0)
+        words = 36 if sh9 else 8
+        st = abi.RenderStats()
+        o = C.byref(opts) if opts is not None else None
+        points, on_gpu = self._path_rays("trace_irradiance", points, seeds)
+        n = len(points)
+        if on_gpu:
+            import torch
+            out = torch.empty((n, words), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()    # (the allocations and whatever wrote `points`)
+            self._check(lib().hj_trace_irradiance(self._h, points.data_ptr() if n else None, n, spp, o, flags | abi.GATHER_DEVICE_ARRAYS,
+                                                  out.data_ptr() if n else None, C.byref(st)))
+            return (out, stats_dict(st)) if stats else out
+        if not sphere:
+            nm = points[:, 3:6]
+            bad = ~np.isfinite(nm).all(axis=1) | (nm == 0).all(axis=1)
+            if bad.any():
+                i = int(np.argmax(bad))
+                raise ValueError(f"trace_irradiance: point {i} has the normal {nm[i].tolist()}: finite and not all zero is needed")
+        out = np.zeros((n, words), np.float32)
+        self._check(lib().hj_trace_irradiance(self._h, points.ctypes.data, n, spp, o, flags, out.ctypes.data, C.byref(st)))
+        return (out, stats_dict(st)) if stats else out
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

@@ -583,6 +583,57 @@ typedef struct hj_adaptive_opts {
 int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const hj_adaptive_opts* adaptive, const hj_render_opts* opts /* NULL = defaults */,
                             uint32_t flags, float* samples, float* moments /* may be NULL */, hj_render_stats* stats /* may be NULL */);
 
+/* hj_trace_irradiance (ABI 0.14): the radiance gathered at caller-given points, over the hemisphere about a normal or over the
+ * sphere - the query of a light-map texel or a probe.  The directions are drawn on the device from the call's own RNG, so a record is
+ * reproducible; no counterpart in the reference.  opts, stats and the path state are exactly hj_trace_paths'.
+ *   points: n x 8 words per point - words 0-2 the position, 3-5 the normal (used as given, never normalised, as hj_trace_paths uses
+ *     its directions), word 6 a uint32 seed stored as bits, word 7 reserved and ignored.  Words 0-2 and word 6 sit where
+ *     hj_trace_rays and hj_trace_paths have origin and seed.
+ *   spp: samples per point, 1 ... 65536.  Sample k of point i: RNG state s = seedRng(seed_i + k) with uint32 wrap-around; two draws
+ *     give the direction d_k,
+ *       default (hemisphere): l = randCosHemisphere(s) in populateTriangle's frame about the normal n (shader/shapes/triangle.glsl):
+ *           bt = |n.x| > |n.y| ? (0,1,0) : (1,0,0);  t = normalize(cross(n, bt));  b = cross(n, t);  d = (t * l.x + b * l.y) + n * l.z
+ *         - the expression of a diffuse bounce (material.glsl:37-46), in the numeric contract's cross and normalize;
+ *       HJ_GATHER_SPHERE: d = randUniformSphere(s); the normal is ignored.
+ *     A path then starts at (position_i, d_k) exactly as a sample of hj_trace_paths does, with the RNG state CONTINUED behind the two
+ *     draws and not reseeded: throughput 1, extinction 0, wasDiscrete, bounce 0, first segment tMin = eps and tMax = inf.  No
+ *     next-event sample is taken at the gather point; a light the gather ray hits counts through wasDiscrete.  L_k: its radiance.
+ *   out: n x 8 floats per point, n x 36 with HJ_GATHER_SH9 -
+ *     [0..2] the float32 sum of L_k over k = 0, 1, ... in that order, starting from +0;  [3] (float)spp;
+ *     [4] the number of samples whose first segment hit something (first-hit t > 0), as a float;
+ *     [5] the smallest first-hit t among those samples, +inf if there is none;  [6], [7] zero.
+ *     Irradiance is pi / spp x [0..2] (hemisphere), ambient occlusion [4] / spp.
+ *     HJ_GATHER_SH9 (only together with HJ_GATHER_SPHERE): [8 + 3 j + c] is the running float32 sum over ascending k, from +0, of
+ *     Y_j(d_k) * L_k[c] - one multiply, then one add, no contraction; [35] zero.  d_k = (x, y, z) as drawn, not renormalised.  The
+ *     real spherical-harmonic basis of bands 0..2, float32, in this order and operation order:
+ *         Y_0 = c0            Y_1 = c1 * y                          Y_2 = c1 * z            Y_3 = c1 * x
+ *         Y_4 = c2 * (x * y)  Y_5 = c2 * (y * z)                    Y_6 = c3 * ((3.0f * z) * z - 1.0f)
+ *         Y_7 = c2 * (x * z)  Y_8 = c4 * (x * x - y * y)
+ *         c0 = 0x1.20dd76p-2f  c1 = 0x1.f45438p-2f  c2 = 0x1.17b142p+0f  c3 = 0x1.42f602p-2f  c4 = 0x1.17b142p-1f
+ *         (0.28209479, 0.48860252, 1.0925485, 0.31539157, 0.54627424)
+ *     Record i depends on point i, spp, flags, opts and the scene alone: not on HJ_PATHS_WGS, HJ_PATHS_POOL or HJ_PATHS_CHUNK, nor on
+ *     which lane carried a path.
+ *   HJ_GATHER_DEVICE_ARRAYS: points and out are device pointers on the context's GPU, 16-byte aligned, read and written in place on
+ *     the context's stream (the caller orders its own streams before the call).  Without it they are host arrays, staged through
+ *     buffers the context keeps.
+ * A launch takes whole points (at most HJ_PATHS_CHUNK samples; one point when spp alone exceeds it); the path state is
+ * hj_trace_paths' own, kept with the context.  Returns when the results are complete (one synchronisation).  n == 0: HJ_OK, nothing
+ * touched.
+ * Origin domain: hj_trace_paths' - agreement with the reference's arithmetic bit for bit is claimed for positions inside the scene's
+ *   root box joined with the camera (the leaf guards' padding; HJ_LEAF_GUARDS=0 beyond).
+ * Normals: in hemisphere mode a normal must be finite and not all zero (the frame normalises cross(n, bt)).  With host arrays the call
+ *   checks every point before anything is written; with HJ_GATHER_DEVICE_ARRAYS that is the caller's contract, as the directions of
+ *   hj_trace_paths are.
+ * HJ_ERR_INVALID, checked before anything else and without a device, in hj_trace_paths' order: null points or out with n > 0, unknown
+ *   flag bits, HJ_GATHER_SH9 without HJ_GATHER_SPHERE, spp == 0 or above 65536, n above 2^31 - 1, misaligned device arrays, the
+ *   refusals of opts, a bad normal in host arrays.  The null context, HJ_ERR_STATE and n == 0 as in hj_trace_paths.  A refused call
+ *   writes nothing. */
+#define HJ_GATHER_DEVICE_ARRAYS 1u
+#define HJ_GATHER_SPHERE 2u
+#define HJ_GATHER_SH9 4u   /* only together with HJ_GATHER_SPHERE */
+int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
+                        uint32_t flags, float* out, hj_render_stats* stats /* may be NULL */);
+
 /* ------------------------------------------------------------------- probes */
 
 /* Function-level probes used by the parity tests (no counterpart in the
