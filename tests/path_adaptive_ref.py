@@ -31,24 +31,30 @@ def stops(S1, S2, m, a):
     return stop, sem2
 
 
-def expected(cs, rays, a, opts):
+def expected(cs, rays, a, opts, sample=None):
     """-> dict: samples (n, 8) float32, moments (n, 4) uint32 (the bits of S1, S2, the last sem2; n_i), n (n,) int64, counts (COUNTS),
-    rounds (adaptive rounds run)"""
+    rounds (adaptive rounds run), lists (the length of every round's list of rays).  sample(active, k) -> (the spp = 1 records of
+    sample k of the rays `active`, their counts): where a sample comes from - by default the oracle, compose() with seeds + k."""
     rays = np.ascontiguousarray(rays, F).reshape(-1, 8)
     n = len(rays)
     seeds = rays.view(U)[:, 6].copy()
+
+    def composed(active, k):
+        sub = rays[active].copy()
+        sub.view(U)[:, 6] = seeds[active] + U(k)                                           # (uint32 wrap-around)
+        return R.compose(cs, sub, 1, opts)
+    sample = sample or composed
     rgb, S1, S2, sem2 = np.zeros((n, 3), F), np.zeros(n, F), np.zeros(n, F), np.zeros(n, F)
     nd = np.zeros((n, 4), F)
     n_i = np.zeros(n, np.int64)
     counts = dict.fromkeys(COUNTS, 0)
     active = np.arange(n)
-    done, rounds = 0, 0
+    done, rounds, lists = 0, 0, []
     while len(active):
         c = a["spp_min"] if done == 0 else min(a["spp_step"], a["spp_max"] - done)
+        lists.append(len(active))
         for k in range(done, done + c):
-            sub = rays[active].copy()
-            sub.view(U)[:, 6] = seeds[active] + U(k)                                       # (uint32 wrap-around)
-            smp, cnt = R.compose(cs, sub, 1, opts)
+            smp, cnt = sample(active, k)
             for key in COUNTS:
                 counts[key] += cnt[key]
             r, g, b = smp[:, 0], smp[:, 1], smp[:, 2]
@@ -66,7 +72,7 @@ def expected(cs, rays, a, opts):
         active = active[~stop]
     samples = np.concatenate([rgb, n_i.astype(F)[:, None], nd], 1)
     moments = np.stack([S1.view(U), S2.view(U), sem2.view(U), n_i.astype(U)], 1)
-    return dict(samples=samples, moments=moments, n=n_i, counts=counts, rounds=rounds)
+    return dict(samples=samples, moments=moments, n=n_i, counts=counts, rounds=rounds, lists=lists)
 
 
 @functools.lru_cache(maxsize=None)
