@@ -258,8 +258,20 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
         const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
         return (dx >= 0 && dy >= 0 && dz >= 0) ? dx * dy + dy * dz + dz * dx : 0.f;
       }
+      // The boxes this builder WRITES take their minimum and maximum with the zeros ordered, -0 < +0, as the device's f_min / f_max
+      // do (v_min_f32 / v_max_f32 order them) and as ordered() does: std::fmin / std::fmax leave the sign of a zero to the order of
+      // their arguments, and the host's top then held +0 where the refit of the same links gives -0 ("Build level").
+      // Equal operands differ in the sign of a zero at most: OR keeps the minus for a minimum, AND drops it for a maximum.
+      static float zmin(float a, float b) {
+        if (a == b) return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, a) | __builtin_bit_cast(uint32_t, b));
+        return std::fmin(a, b);
+      }
+      static float zmax(float a, float b) {
+        if (a == b) return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, a) & __builtin_bit_cast(uint32_t, b));
+        return std::fmax(a, b);
+      }
       static void grow(float* lo, float* hi, const float* alo, const float* ahi) {
-        for (int k = 0; k < 3; k++) { lo[k] = std::fmin(lo[k], alo[k]); hi[k] = std::fmax(hi[k], ahi[k]); }
+        for (int k = 0; k < 3; k++) { lo[k] = zmin(lo[k], alo[k]); hi[k] = zmax(hi[k], ahi[k]); }
       }
       void bounds(size_t a, size_t b, float* lo, float* hi) const {
         for (int k = 0; k < 3; k++) { lo[k] = INFINITY; hi[k] = -INFINITY; }
@@ -357,7 +369,7 @@ int hj_build_bvh_device(hj_context* ctx, const hj_scene_desc* s, hj_bvh_node* ou
         n.weight = t.n[n.left].weight + t.n[n.right].weight;
       }
       static void set_box(TNode& n, int c, const TNode& child) {     // n's box for child c = union of that child's two boxes
-        for (int k = 0; k < 3; k++) { n.lo[c][k] = std::fmin(child.lo[0][k], child.lo[1][k]); n.hi[c][k] = std::fmax(child.hi[0][k], child.hi[1][k]); }
+        for (int k = 0; k < 3; k++) { n.lo[c][k] = zmin(child.lo[0][k], child.lo[1][k]); n.hi[c][k] = zmax(child.hi[0][k], child.hi[1][k]); }
       }
       double rotate(Tree& t, int32_t root) {
         double gain = 0;

@@ -763,8 +763,9 @@ HJ_DEV void rf_climb_from(const Refit& r, float4* out, uint32_t child, float lo[
 // The bottom-up pass over the flattened array, k_refit's form: one thread per RECORD; the thread of a leaf computes the box of
 // its shape (shape_box), writes the leaf's record and climbs with that box in registers.  At every inner node the first thread to
 // arrive leaves, the second one joins its box with the SIBLING's - which another CU may have written in this launch: read at agent
-// scope, ld_agent -, writes the node's record and goes on.  f_min / f_max are exact and commutative: the result does not depend on
-// who arrives first.  No depth limit, no waiting.  `out`: the N 32-byte records as pairs of float4.
+// scope, ld_agent -, writes the node's record and goes on.  f_min / f_max are exact and commutative, the zeros included: v_min_f32 and
+// v_max_f32 order them, -0 < +0, as ordered() does, so the result does not depend on who arrives first (pinned on scenes with both
+// zeros on one coordinate: tests/test_lbvh_edges_gpu.py::test_refit_orders_the_zeros_on_given_topologies).  No depth limit, no waiting.  `out`: the N 32-byte records as pairs of float4.
 __global__ __launch_bounds__(256) void k_rf_climb(Refit r, Shapes s, float4* out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= r.N) return;
