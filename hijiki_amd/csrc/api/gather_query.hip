@@ -8,13 +8,12 @@
 //   k_gq_paths<PAIRS, ENV, SPHERE>  one persistent launch per chunk of samples: workgroup g owns the 64-sample groups g, g + num_wg, ...
 //   k_gq_resolve<SH9>               one thread per point: the float32 sums over its spp samples in ascending order, the first
 //                                   segments' hit count and nearest hit, the nine SH-weighted sums
-// The round loop of k_gq_paths is the TWIN of k_pq_paths' (api/path_query.hip): the same text with the top-up exchanged.  It is
-// restated and not shared: as a device function template inlined into both kernels it moved k_pq_paths' machine code (the
-// workgroup size is read with the kernel's bound only in a kernel's own body), and hj_trace_paths must not move.  A change to one
-// loop is a change to the other.
+// The round loop of k_gq_paths is k_pq_paths' (api/path_query.hip): ONE text, api/query_round_loop.h, included into both kernel
+// bodies with the top-up named by a macro.  The host half behind the entry point's checks is fixed_spp_query (api/path_query.hip).
 #include "hj_internal.h"
 #include <type_traits>
 #include "../kernels/hj_stages.h"
+#include "query_round.h"
 
 #pragma clang fp contract(off)
 
@@ -22,24 +21,15 @@ using namespace hjapi;
 
 namespace hj {
 
-constexpr uint32_t kGqTail = 128u;   // rays of a round at which the workgroup shrinks to one wave (kPqTail of api/path_query.hip)
-#define HJ_GQ_WAVES 7                // the path kernel's register budget (HJ_PATH_WAVES): the called stages are compiled for it
-
 // What the kernel's argument segment holds behind (BatchState, DeviceScene).  A sample is s = point * spp + k, k < spp; the chunk's
 // samples are [0, num_samples), num_samples <= 2^31 - 1 (the sample index shares its word with kCameraFlag).
 struct GatherArgs {
-  const float4* points;   // two float4 per point: position.xyz, normal.x | normal.yz, seed bits, reserved
+  const float4* src;      // two float4 per point: position.xyz, normal.x | normal.yz, seed bits, reserved
   uint32_t spp;
   uint32_t num_samples;
   uint32_t max_bounces;
   uint32_t rr_start;
 };
-
-// 64-sample groups of workgroup g: group k of its sequence is global group g + k * num_wg (the path kernel's round-robin deal)
-HJ_DEV uint32_t gq_num_groups(uint32_t num_samples, uint32_t num_wg, uint32_t g) {
-  const uint32_t groups = (num_samples + 63u) / 64u;
-  return groups > g ? (groups - g + num_wg - 1u) / num_wg : 0u;
-}
 
 // The direction of sample k of the point (a, b) - the ONE text of it: the top-up draws it, the SH reduction draws it again.
 // rng: rng_seed(seed + k) with uint32 wrap-around, advanced by the two draws (the state the path goes on with).
@@ -102,84 +92,13 @@ __device__ __attribute__((noinline)) void stage_gen_points_call(uint32_t ka_lo, 
   stage_gen_points<SPHERE>(c.st, c.sc, points, uni(spp), uni(num_samples), uni(g), c.sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves));
 }
 
-// The whole life of a chunk of samples in ONE launch: the round loop of k_pq_paths (api/path_query.hip; kernels/hj_path_kernel.h's
-// loop for explicit records), with the top-up above.  Path regeneration keeps about `pool` paths in flight per workgroup until its
-// samples run out.  sh.cam_first stays 0xFFFFFFFF in every round: no path is implicit, so no stage reads st.blocks (null here).
-// Exit condition every wave reaches, exactly as in the path kernel: the counts a round's decisions depend on (n_ray, n_gen,
-// n_shadow in LDS, groups_left in every thread alike) are read by all waves between two workgroup barriers, so all waves take the
-// same branch; the loop ends when there are no rays, no shadow rays and no groups left, and every path ends - a bounce ends it with
-// probability >= 1 % from bounce rr_start on, and max_bounces caps it.  A wave that leaves at the one-wave tail leaves for good: the
-// counts never grow again once groups_left is 0.
-// No global atomic, no inline assembly; ordinary loads and stores (NT = false).  The statistics are per workgroup, summed on the host.
+// One persistent launch per chunk of samples: the round loop of api/query_round_loop.h with the top-up above.
 template <bool PAIRS, bool ENV, bool SPHERE>
-__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(HJ_GQ_WAVES, 8))) void k_gq_paths(BatchState st, DeviceScene sc, GatherArgs q) {
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(HJ_QUERY_WAVES, 8))) void k_gq_paths(BatchState st, DeviceScene sc, GatherArgs q) {
   __shared__ std::conditional_t<ENV, WgSharedEnv, WgShared> sh;
-  const uint32_t g = blockIdx.x;
-  // (the called stages read the batch and scene descriptions from this kernel's argument segment and reach `sh` through its LDS address)
-  const uint64_t ka_ = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-  const uint32_t ka_lo = (uint32_t)ka_, ka_hi = (uint32_t)(ka_ >> 32), sh_lds = (uint32_t)(uintptr_t)(WgSharedLds)&sh;
-  const uint32_t pts_lo = (uint32_t)(uintptr_t)q.points, pts_hi = (uint32_t)((uint64_t)(uintptr_t)q.points >> 32);
-  uint32_t groups_left = gq_num_groups(q.num_samples, st.num_wg, g);
-  uint32_t total_closest = 0, total_shadow = 0, total_hits = 0, total_unocc = 0, total_direct = 0;   // (thread 0's copies are published)
-  if (groups_left != 0) {
-    uint32_t k_next = 0;                     // next group of this workgroup's sample sequence
-    if (threadIdx.x == 0) { sh.n_ray[0] = 0; sh.n_ray[1] = 0; sh.n_gen = 0; sh.n_shadow = 0; sh.n_unocc = 0; sh.n_direct = 0; sh.cam_first = 0xFFFFFFFFu; sh.cam_k0 = 0; sh.n_cam_dead = 0; }
-    load_hot_nodes(sc, sh);
-    uint32_t waves = blockDim.x >> 6;
-    wg_sync(waves);
-    for (uint32_t parity = 0;; parity ^= 1u) {
-      // top-up: new paths behind the continuing ones, whole 64-sample groups while they fit
-      const uint32_t n0 = uni(sh.n_ray[parity]);
-      const uint32_t ngen = min(groups_left, (st.pool - n0) >> 6);
-      if (ngen != 0) {
-        stage_gen_points_call<ENV, SPHERE>(ka_lo, ka_hi, pts_lo, pts_hi, q.spp, q.num_samples, g, sh_lds, parity, n0, k_next, ngen, waves);
-        wg_sync(waves);
-        k_next += ngen;
-        groups_left -= ngen;
-      }
-      const uint32_t n = n0 + uni(sh.n_gen), ns = uni(sh.n_shadow);
-      // next-event samples of the previous round's shade that the light-shaft grid answered: shadow rays of the statistics all the same
-      { const uint32_t nd = uni(sh.n_direct); total_shadow += nd; total_unocc += nd; total_direct += nd; }
-      if (n + ns == 0) {
-        if (groups_left == 0) break;
-        // (not reached with points - every group below the chunk's count holds a sample -, kept as the path kernel has it)
-        if (threadIdx.x == 0) { sh.n_ray[parity ^ 1u] = 0; sh.n_direct = 0; }
-        wg_sync(waves);
-        continue;
-      }
-      // Tail of the workgroup: one wave can hold every ray of a round and the counts never grow again.
-      if (waves > 1u && groups_left == 0 && n + ns <= kGqTail) {
-        wg_sync(waves);                      // (everyone has read the counts)
-        if (threadIdx.x >= 64u) return;
-        waves = 1u;
-      }
-      wg_sync(waves);                        // everyone has read the counts before they are reset
-      if (threadIdx.x == 0) {
-        sh.head = 0; sh.head_cam = 0; sh.n_ray[parity ^ 1u] = 0; sh.n_gen = 0; sh.n_shadow = 0; sh.n_unocc = 0; sh.n_direct = 0;
-        sh.cam_first = 0xFFFFFFFFu; sh.cam_k0 = 0; sh.n_cam_dead = 0;
-      }
-      if (threadIdx.x < kNumTags) sh.cnt_hit[threadIdx.x] = 0;
-      wg_sync(waves);
-      stage_trace_merged<true, PAIRS, false>(st, sc, g, parity, n, ns, sh);
-      compact_hits_call<false, 4u, ENV>(ka_lo, ka_hi, g, n, sh_lds, waves);
-      wg_sync(waves);
-      if (n != 0) {
-        stage_shade_call<false, ENV>(ka_lo, ka_hi, g, parity, q.max_bounces, q.rr_start, sh_lds, waves);
-      }
-      total_closest += n;
-      total_shadow += ns;
-      for (uint32_t k = 0; k < kNumTags; k++) total_hits += uni(sh.cnt_hit[k]);
-      total_unocc += uni(sh.n_unocc);
-      wg_sync(waves);
-    }
-  }
-  if (threadIdx.x == 0) {
-    st.acc_closest[g] = total_closest;
-    st.acc_shadow[g] = total_shadow;
-    st.acc_hits[g] = total_hits;
-    st.acc_unoccluded[g] = total_unocc;
-    st.acc_direct[g] = total_direct;
-  }
+#define HJ_QUERY_TOP_UP stage_gen_points_call<ENV, SPHERE>
+#include "query_round_loop.h"
+#undef HJ_QUERY_TOP_UP
 }
 
 // The real spherical-harmonic basis of bands 0..2 at d (not renormalised), in the order and with the constants and operation
@@ -253,9 +172,32 @@ static void launch_gq_paths(bool sphere, dim3 grid, dim3 blk, hipStream_t s, con
 
 }  // namespace hj
 
+// the path launch and the resolve of one chunk (FixedSppQuery::chunk): path_query_pass's launch shape, a point in the place of a ray
+static void gather_chunk(const FixedSppQuery& fq, hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_pts, uint32_t cnt,
+                         float4* d_out, hipStream_t s) {
+  const bool sphere = (fq.flags & HJ_GATHER_SPHERE) != 0, sh9 = (fq.flags & HJ_GATHER_SH9) != 0;
+  const bool pairs = sc.has_pairs != 0, env = sc.env_alias != nullptr;
+  const uint32_t spp = fq.spp, num_samples = cnt * spp;    // (<= 2^31 - 1: HJ_PATHS_CHUNK's upper bound, or one point's spp)
+  set_num_wg(st, std::min<uint32_t>(G, (num_samples + 63u) / 64u));
+  const hj::GatherArgs q{d_pts, spp, num_samples, fq.o.max_bounces, fq.o.rr_start};
+  const dim3 grid(st.num_wg), blk(hj::kBlockThreads);
+  if (pairs && env) hj::launch_gq_paths<true, true>(sphere, grid, blk, s, st, sc, q);
+  else if (pairs) hj::launch_gq_paths<true, false>(sphere, grid, blk, s, st, sc, q);
+  else if (env) hj::launch_gq_paths<false, true>(sphere, grid, blk, s, st, sc, q);
+  else hj::launch_gq_paths<false, false>(sphere, grid, blk, s, st, sc, q);
+  const dim3 rgrid((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads);
+  if (sh9)
+    hipLaunchKernelGGL(hj::k_gq_resolve<true>, rgrid, blk, 0, s, static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd),
+                       d_pts, spp, cnt, d_out);
+  else
+    hipLaunchKernelGGL(hj::k_gq_resolve<false>, rgrid, blk, 0, s, static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd),
+                       d_pts, spp, cnt, d_out);
+}
+
 extern "C" {
 
-// The argument checks come first and need neither a device nor a context's state (hj_trace_paths' order and style).
+// The argument checks come first and need neither a device nor a context's state (hj_trace_paths' order and style).  Sizes, path
+// state, staging, chunking by whole points, the ONE hipStreamSynchronize and the statistics are fixed_spp_query's (api/path_query.hip).
 int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t spp, const hj_render_opts* opts, uint32_t flags, float* out,
                         hj_render_stats* stats) {
   if (n != 0 && (!points || !out)) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: null %s", !points ? "points" : "out");
@@ -267,14 +209,8 @@ int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t
   if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: %zu points, at most 2^31 - 1 a call", n);
   if (n != 0 && on_device && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: device arrays must be 16-byte aligned");
-  hj_render_opts o;
-  if (opts) o = *opts;
-  else hj_default_render_opts(&o);
-  if (o.max_bounces == 0) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: max_bounces must be >= 1");
-  if (o.use_bvh == 0)
-    return set_error(ctx, HJ_ERR_UNSUPPORTED, "hj_trace_irradiance: the tree is always walked (use_bvh == 0: there is no linear-scan form)");
-  if (o.flags & ~(uint32_t)HJ_RENDER_NO_LIGHT_GRID)
-    return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: of the HJ_RENDER_* bits only HJ_RENDER_NO_LIGHT_GRID applies (flags 0x%x)", o.flags);
+  FixedSppQuery q{__func__, points, n, spp, sh9 ? 9u : 2u, on_device, out, stats, {}, gather_chunk, flags};
+  HJ_TRY(query_render_opts(ctx, __func__, opts, q.o));
   if (!sphere && !on_device) {               // (device arrays: the caller's contract)
     for (size_t i = 0; i < n; i++) {
       const float* nm = points + 8 * i + 3;
@@ -283,95 +219,9 @@ int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t
                          (double)nm[0], (double)nm[1], (double)nm[2]);
     }
   }
-  if (!ctx) {
-    if (hj_device_count() == 0)
-      return set_error(nullptr, HJ_ERR_DEVICE, "hj_trace_irradiance: no HIP device available; this library has no CPU fallback");
-    return set_error(nullptr, HJ_ERR_INVALID, "hj_trace_irradiance: null context");
-  }
-  HJ_NOT_BUSY(ctx);
-  HJ_NOT_PIPELINED(ctx);
-  if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "hj_trace_irradiance: no scene has been uploaded");
+  HJ_TRY(query_gate(ctx, __func__));
   if (n == 0) return HJ_OK;
-  HJ_HIP(ctx, hipSetDevice(ctx->device));
-  const auto wall0 = std::chrono::steady_clock::now();
-
-  // Sizes: hj_trace_paths' (path_query_plan), a point in the place of a ray.  A launch takes whole points.
-  const Tuning& tn = ctx->tuning;
-  const PathQueryPlan plan = path_query_plan(tn, n, spp);
-  const size_t chunk_pts = plan.chunk_rays, most_pts = plan.most_rays;
-  const uint32_t G = plan.G;
-  const size_t f4 = sizeof(float4), rec = sh9 ? 9 : 2;                  // float4 of an output record
-  const hj::DeviceScene sc = scene_for(ctx, o);
-
-  // The path state is hj_trace_paths' (hj_context::paths), and so is the staging of host arrays.
-  hj_context::PathQuery& pq = ctx->paths;
-  if (const int rc = ensure_path_state(ctx, pq, plan.most_samples, G, (uint32_t)tn.paths_wgs, plan.pool, sc.has_extinction != 0, sc.env_alias != nullptr)) {
-    release_path_state(pq);
-    return rc;
-  }
-  hj::BatchState st = pq.st;
-  float4 *d_pts = nullptr, *d_out = nullptr;
-  if (!on_device) {
-    HJ_TRY(dev_alloc(ctx, pq.in_rays, most_pts * 2 * f4));
-    HJ_TRY(dev_alloc(ctx, pq.out_samples, most_pts * rec * f4));
-    d_pts = static_cast<float4*>(pq.in_rays.p);
-    d_out = static_cast<float4*>(pq.out_samples.p);
-  }
-  const size_t launches = (n + chunk_pts - 1) / chunk_pts;
-  std::vector<uint32_t> h_acc;
-  try {
-    if (stats) h_acc.assign(launches * kStatWords * G, 0u);
-  } catch (const std::bad_alloc&) {
-    return set_error(ctx, HJ_ERR_NOMEM, "hj_trace_irradiance: out of host memory");
-  }
-
-  const bool pairs = sc.has_pairs != 0, env = sc.env_alias != nullptr;
-  hipError_t e = hipSuccess;
-  size_t launch = 0;
-  for (size_t at = 0; at < n && e == hipSuccess; at += chunk_pts, launch++) {
-    const uint32_t cnt = (uint32_t)std::min(chunk_pts, n - at);
-    if (on_device) {
-      d_pts = reinterpret_cast<float4*>(const_cast<float*>(points)) + 2 * at;
-      d_out = reinterpret_cast<float4*>(out) + rec * at;
-    } else {
-      e = hipMemcpyAsync(d_pts, points + 8 * at, cnt * 2 * f4, hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) break;
-    }
-    const uint32_t num_samples = cnt * spp;    // (<= 2^31 - 1: HJ_PATHS_CHUNK's upper bound, or one point's spp)
-    set_num_wg(st, std::min<uint32_t>(G, (num_samples + 63u) / 64u));
-    const hj::GatherArgs q{d_pts, spp, num_samples, o.max_bounces, o.rr_start};
-    const dim3 grid(st.num_wg), blk(hj::kBlockThreads);
-    if (pairs && env) hj::launch_gq_paths<true, true>(sphere, grid, blk, ctx->stream, st, sc, q);
-    else if (pairs) hj::launch_gq_paths<true, false>(sphere, grid, blk, ctx->stream, st, sc, q);
-    else if (env) hj::launch_gq_paths<false, true>(sphere, grid, blk, ctx->stream, st, sc, q);
-    else hj::launch_gq_paths<false, false>(sphere, grid, blk, ctx->stream, st, sc, q);
-    const dim3 rgrid((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads);
-    if (sh9)
-      hipLaunchKernelGGL(hj::k_gq_resolve<true>, rgrid, blk, 0, ctx->stream, static_cast<const float4*>(st.smp_rgb),
-                         static_cast<const float4*>(st.smp_nd), static_cast<const float4*>(d_pts), spp, cnt, d_out);
-    else
-      hipLaunchKernelGGL(hj::k_gq_resolve<false>, rgrid, blk, 0, ctx->stream, static_cast<const float4*>(st.smp_rgb),
-                         static_cast<const float4*>(st.smp_nd), static_cast<const float4*>(d_pts), spp, cnt, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out + 4 * rec * at, d_out, cnt * rec * f4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && stats)
-      e = hipMemcpyAsync(h_acc.data() + launch * kStatWords * G, st.acc_closest, sizeof(uint32_t) * kStatWords * st.num_wg, hipMemcpyDeviceToHost, ctx->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "hj_trace_irradiance: %s", hipGetErrorString(e));
-  if (stats) {
-    std::memset(stats, 0, sizeof *stats);
-    size_t at = 0;
-    for (size_t l = 0; l < launches; l++, at += chunk_pts) {
-      const size_t cnt = std::min(chunk_pts, n - at);
-      add_stat_words(*stats, h_acc.data() + l * kStatWords * G, std::min<size_t>(G, (cnt * spp + 63) / 64));
-    }
-    stats->paths = (uint64_t)n * spp;
-    stats->batches = launches;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-  }
-  return HJ_OK;
+  return fixed_spp_query(ctx, q);
 }
 
 }  // extern "C"

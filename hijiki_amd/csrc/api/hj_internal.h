@@ -20,14 +20,16 @@
 //   api/ray_query.hip     hj_trace_rays: caller-given rays through the uploaded tree (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the persistent walk with a fetch / finish of its own)
 //   api/path_query.hip    hj_trace_paths: path-traced radiance along caller-given rays (includes the kernel headers up to hj_stages.h and
-//                         defines its own kernels beside the path kernels: the fused kernel's round loop with a top-up from a ray array);
-//                         its path state is hj_context::PathQuery, a PathState
+//                         defines its own kernels beside the path kernels: the round loop of api/query_round_loop.h with a top-up from a
+//                         ray array); its path state is hj_context::PathQuery, a PathState.  Also the host code the queries share:
+//                         path_query_plan / path_query_pass, query_render_opts, query_gate, QueryStats, fixed_spp_query (below)
+//   api/query_round.h     the tail threshold, register budget and group deal of the queries' path kernels
+//   api/query_round_loop.h the text of their round loop: no include guard, included inside the bodies of k_pq_paths and k_gq_paths
 //   api/path_adaptive.hip hj_trace_paths_adaptive: rounds of that path kernel (path_query_pass) over the rays still active, with the
 //                         k_pa_* kernels between them (running sums and stop rule, order-preserving compaction); includes hj_num.h only
 //   api/gather_query.hip  hj_trace_irradiance: gather queries at caller-given points (includes the kernel headers up to hj_stages.h and
-//                         defines its own kernels beside the path kernels: the round loop of api/path_query.hip restated with a top-up
-//                         that draws a direction at a point, and the per-point reduction); plans with path_query_plan and runs in
-//                         hj_context::PathQuery's path state and staging
+//                         defines its own kernels beside the path kernels: the same round loop with a top-up that draws a direction
+//                         at a point, and the per-point reduction); its host half behind the checks is fixed_spp_query
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -417,6 +419,42 @@ struct PathQueryPlan { size_t chunk_rays, most_rays, most_samples; uint32_t G, p
 PathQueryPlan path_query_plan(const Tuning& tn, size_t n, uint32_t spp);
 void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_rays, uint32_t cnt, uint32_t spp,
                      const hj_render_opts& o, hipStream_t s);
+// api/path_query.hip: what the query entry points share; `fn` is the entry point's name, for the messages.
+//   query_render_opts  opts (NULL: the defaults) into o and the refusals of the path-type queries: max_bounces, use_bvh, HJ_RENDER_* bits
+//   query_gate         every query, behind its argument checks: a null context (HJ_ERR_DEVICE without a HIP device, HJ_ERR_INVALID
+//                      otherwise), an asynchronous frame in flight, frames in the pipeline, no scene
+int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opts, hj_render_opts& o);
+int query_gate(hj_context* ctx, const char* fn);
+// The statistics read-back of a pass's launches (kStatWords x G words each), summed on the host once the stream has drained.
+// on == false (the caller wants no statistics): every member does nothing.
+struct QueryStats {
+  bool on;
+  uint32_t G = 0;
+  std::vector<uint32_t> h_acc;
+  explicit QueryStats(bool on_) : on(on_) {}
+  int reserve(hj_context* ctx, const char* fn, size_t launches, uint32_t G);   // HJ_ERR_NOMEM: behind a synchronise of ctx->stream
+  hipError_t enqueue(size_t launch, const hj::BatchState& st, hipStream_t s);  // the copy of the launch st was just set up for
+  // ... of a pass over `len` rays in launches of chunk_rays at spp samples each, added to `to`
+  void add(hj_render_stats& to, size_t chunk_rays, size_t len, uint32_t spp) const;
+};
+// A fixed-spp query behind its entry point's checks (n > 0): hj_trace_paths and hj_trace_irradiance.  fixed_spp_query owns the plan,
+// the path state (hj_context::paths) and the staging of host arrays, the chunk loop - H2D, `chunk`, D2H, statistics copy -, the ONE
+// hipStreamSynchronize and the statistics; `chunk` enqueues the path launch and the resolve of cnt records at d_in into d_out.
+struct FixedSppQuery {
+  const char* name;                      // the entry point
+  const float* in;                       // n records of two float4: rays or points
+  size_t n;
+  uint32_t spp;
+  size_t rec;                            // float4 of an output record
+  bool on_device;                        // in / out are device arrays, used in place
+  float* out;
+  hj_render_stats* stats;                // may be NULL
+  hj_render_opts o;
+  void (*chunk)(const FixedSppQuery& q, hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_in, uint32_t cnt, float4* d_out,
+                hipStream_t s);
+  uint32_t flags;                        // the entry point's own, for `chunk`
+};
+int fixed_spp_query(hj_context* ctx, const FixedSppQuery& q);
 int sync_all(hj_context* ctx);                       // drains the context's streams (api/context.hip)
 void drop_cached_comms(hj_context* ctx);             // api/comm.hip: the communicators hj_reduce_framebuffers made for ctx
 
@@ -444,18 +482,21 @@ inline hj::DeviceScene scene_for(const hj_context* ctx, const hj_render_opts& o)
 
 // Entry points that touch the context's device state refuse to run while an asynchronous frame is in flight on it
 // (the worker thread owns the slots, the streams and the framebuffer until hj_sync).
-#define HJ_NOT_BUSY(ctx)                                                                                          \
+// (fn: the entry point's name where a helper checks on its behalf)
+#define HJ_NOT_BUSY_IN(ctx, fn)                                                                                   \
   do {                                                                                                            \
     if ((ctx)->busy.load(std::memory_order_acquire))                                                              \
-      return set_error(ctx, HJ_ERR_STATE, "%s: an asynchronous frame is in flight on this context: call hj_sync first", __func__); \
+      return set_error(ctx, HJ_ERR_STATE, "%s: an asynchronous frame is in flight on this context: call hj_sync first", fn); \
   } while (0)
+#define HJ_NOT_BUSY(ctx) HJ_NOT_BUSY_IN(ctx, __func__)
 
 // ... and while frames submitted with HJ_RENDER_NO_DRAIN are still in flight (hj_pipeline_wait(ctx, 0, ...) drains them).
-#define HJ_NOT_PIPELINED(ctx)                                                                                     \
+#define HJ_NOT_PIPELINED_IN(ctx, fn)                                                                              \
   do {                                                                                                            \
     if ((ctx)->pipe_active)                                                                                       \
-      return set_error(ctx, HJ_ERR_STATE, "%s: frames submitted with HJ_RENDER_NO_DRAIN are in flight: call hj_pipeline_wait(ctx, 0, ...) first", __func__); \
+      return set_error(ctx, HJ_ERR_STATE, "%s: frames submitted with HJ_RENDER_NO_DRAIN are in flight: call hj_pipeline_wait(ctx, 0, ...) first", fn); \
   } while (0)
+#define HJ_NOT_PIPELINED(ctx) HJ_NOT_PIPELINED_IN(ctx, __func__)
 
 #define HJ_HIP(ctx, call)                                                                         \
   do {                                                                                            \

@@ -11,6 +11,8 @@
 //   k_pa_scatter     the active entries, in list order, to the next round's index list and ray array (word 6 = seed_i + n_i)
 // Ordinary loads and stores, no inline assembly, no global atomic, and no workgroup ever waits for another: the three compaction
 // steps are three launches.
+// The render-opts check, the context gate and the statistics read-back are the queries' (api/path_query.hip); the round loop below
+// is this entry point's own.
 #include "hj_internal.h"
 #include "../kernels/hj_num.h"
 
@@ -177,21 +179,8 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
       ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(moments)) & 15u) != 0)
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: device arrays must be 16-byte aligned");
   hj_render_opts o;
-  if (opts) o = *opts;
-  else hj_default_render_opts(&o);
-  if (o.max_bounces == 0) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: max_bounces must be >= 1");
-  if (o.use_bvh == 0)
-    return set_error(ctx, HJ_ERR_UNSUPPORTED, "hj_trace_paths_adaptive: the tree is always walked (use_bvh == 0: there is no linear-scan form)");
-  if (o.flags & ~(uint32_t)HJ_RENDER_NO_LIGHT_GRID)
-    return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: of the HJ_RENDER_* bits only HJ_RENDER_NO_LIGHT_GRID applies (flags 0x%x)", o.flags);
-  if (!ctx) {
-    if (hj_device_count() == 0)
-      return set_error(nullptr, HJ_ERR_DEVICE, "hj_trace_paths_adaptive: no HIP device available; this library has no CPU fallback");
-    return set_error(nullptr, HJ_ERR_INVALID, "hj_trace_paths_adaptive: null context");
-  }
-  HJ_NOT_BUSY(ctx);
-  HJ_NOT_PIPELINED(ctx);
-  if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "hj_trace_paths_adaptive: no scene has been uploaded");
+  HJ_TRY(query_render_opts(ctx, __func__, opts, o));
+  HJ_TRY(query_gate(ctx, __func__));
   if (n == 0) return HJ_OK;
   HJ_HIP(ctx, hipSetDevice(ctx->device));
   const auto wall0 = std::chrono::steady_clock::now();
@@ -248,7 +237,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
   uint32_t* d_flags = static_cast<uint32_t*>(pq.pa_flags.p);
   uint32_t* d_counts = static_cast<uint32_t*>(pq.pa_counts.p);
   const hj::AdaptiveArgs args{a.spp_max, a.rel_error, a.floor};
-  std::vector<uint32_t> h_acc;
+  QueryStats acc(stats != nullptr);
   hj_render_stats total{};
 
   hipError_t e = hipSuccess;
@@ -264,14 +253,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
     const PathQueryPlan plan = path_query_plan(tn, active, c);
     st.pool = plan.pool;
     const size_t launches = (active + plan.chunk_rays - 1) / plan.chunk_rays;
-    if (stats) {
-      try {
-        h_acc.assign(launches * kStatWords * plan.G, 0u);
-      } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return set_error(ctx, HJ_ERR_NOMEM, "hj_trace_paths_adaptive: out of host memory");
-      }
-    }
+    HJ_TRY(acc.reserve(ctx, __func__, launches, plan.G));
     size_t launch = 0;
     for (size_t at = 0; at < active && e == hipSuccess; at += plan.chunk_rays, launch++) {
       const uint32_t cnt = (uint32_t)std::min<size_t>(plan.chunk_rays, active - at);
@@ -280,9 +262,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
                          static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd), list_src ? list_src + at : nullptr, (uint32_t)at,
                          cnt, c, n_before, args, sums, s2, d_flags + at, d_out, d_mom);
       e = hipGetLastError();
-      if (e == hipSuccess && stats)
-        e = hipMemcpyAsync(h_acc.data() + launch * kStatWords * plan.G, st.acc_closest, sizeof(uint32_t) * kStatWords * st.num_wg, hipMemcpyDeviceToHost,
-                           ctx->stream);
+      if (e == hipSuccess) e = acc.enqueue(launch, st, ctx->stream);
     }
     const bool last = n_after == a.spp_max;  // every ray of the list stops: nothing to compact, the count is 0
     if (e == hipSuccess && !last) {
@@ -305,13 +285,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
     const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) break;
-    if (stats) {
-      size_t at = 0;
-      for (size_t l = 0; l < launches; l++, at += plan.chunk_rays) {
-        const size_t cnt = std::min<size_t>(plan.chunk_rays, active - at);
-        add_stat_words(total, h_acc.data() + l * kStatWords * plan.G, std::min<size_t>(plan.G, (cnt * c + 63) / 64));
-      }
-    }
+    acc.add(total, plan.chunk_rays, active, c);
     total.paths += (uint64_t)active * c;
     total.batches += launches;
     total.bounce_rounds += 1;

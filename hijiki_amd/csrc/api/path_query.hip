@@ -3,14 +3,18 @@
 // The rounds are the fused path kernel's (kernels/hj_path_kernel.h, its loop over EXPLICIT path records): top-up, the merged walk of
 // closest-hit and shadow rays, hit compaction by material tag, shade - the stages of kernels/hj_stages.h, called as that kernel calls
 // them.  Nothing of the kernel headers is restated or edited: this unit includes them (as api/ray_query.hip does) and defines kernels
-// of its own beside the path kernels.  The one new text is the top-up, which takes its paths from the caller's ray array instead of
-// the camera.
+// of its own beside the path kernels.  The round loop is api/query_round_loop.h, the text k_gq_paths (api/gather_query.hip) includes
+// too; this unit's own text is the top-up, which takes its paths from the caller's ray array instead of the camera.
 //   k_pq_paths<PAIRS, ENV>  one persistent launch per chunk of samples: workgroup g owns the 64-sample groups g, g + num_wg, ...
 //   k_pq_resolve            one thread per ray: the float32 sum of its spp samples in ascending order, first-hit normal and t
-// The one-wave tail of the path kernel (HJ_TAIL1 there, kPqTail here) is KEPT: a query's last long paths are as few as a batch's.
+// The one-wave tail of the path kernel (HJ_TAIL1 there, kQueryTail here) is KEPT: a query's last long paths are as few as a batch's.
+// Host code the queries share lives here too (namespace hjapi, declared in hj_internal.h): path_query_plan and path_query_pass, the
+// render-opts check and the context gate of the entry points, the statistics read-back (QueryStats), and fixed_spp_query, the
+// driver of hj_trace_paths and hj_trace_irradiance.
 #include "hj_internal.h"
 #include <type_traits>
 #include "../kernels/hj_stages.h"
+#include "query_round.h"
 
 #pragma clang fp contract(off)
 
@@ -18,24 +22,15 @@ using namespace hjapi;
 
 namespace hj {
 
-constexpr uint32_t kPqTail = 128u;   // rays of a round at which the workgroup shrinks to one wave (the path kernel's HJ_TAIL1)
-#define HJ_PQ_WAVES 7                // the path kernel's register budget (HJ_PATH_WAVES): the called stages are compiled for it
-
 // What the kernel's argument segment holds behind (BatchState, DeviceScene).  A sample is s = ray * spp + k, k < spp; the chunk's
 // samples are [0, num_samples), num_samples <= 2^31 - 1 (the sample index shares its word with kCameraFlag).
 struct PathQueryArgs {
-  const float4* rays;     // two float4 per ray: origin.xyz, direction.x | direction.yz, seed bits, reserved
+  const float4* src;      // two float4 per ray: origin.xyz, direction.x | direction.yz, seed bits, reserved
   uint32_t spp;
   uint32_t num_samples;
   uint32_t max_bounces;
   uint32_t rr_start;
 };
-
-// 64-sample groups of workgroup g: group k of its sequence is global group g + k * num_wg (the path kernel's round-robin deal)
-HJ_DEV uint32_t pq_num_groups(uint32_t num_samples, uint32_t num_wg, uint32_t g) {
-  const uint32_t groups = (num_samples + 63u) / 64u;
-  return groups > g ? (groups - g + num_wg - 1u) / num_wg : 0u;
-}
 
 // Top-up from the caller's rays: paths for groups [k0, k0 + ngen) of this workgroup's sample sequence, written to the path arrays of
 // `parity` behind the n0 continuing paths (positions n0 + sh.n_gen...; the caller guarantees n0 + 64 * ngen <= pool).  A path starts
@@ -77,84 +72,13 @@ __device__ __attribute__((noinline)) void stage_gen_rays_call(uint32_t ka_lo, ui
   stage_gen_rays(c.st, c.sc, rays, uni(spp), uni(num_samples), uni(g), c.sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves));
 }
 
-// The whole life of a chunk of samples in ONE launch: the round loop of kernels/hj_path_kernel.h for explicit records (its
-// non-IMPLICIT form), with the top-up above.  Path regeneration keeps about `pool` paths in flight per workgroup until its samples
-// run out.  sh.cam_first stays 0xFFFFFFFF in every round: no path is implicit, so no stage reads st.blocks (null here).
-// Exit condition every wave reaches, exactly as in the path kernel: the counts a round's decisions depend on (n_ray, n_gen,
-// n_shadow in LDS, groups_left in every thread alike) are read by all waves between two workgroup barriers, so all waves take the
-// same branch; the loop ends when there are no rays, no shadow rays and no groups left, and every path ends - a bounce ends it with
-// probability >= 1 % from bounce rr_start on, and max_bounces caps it.  A wave that leaves at the one-wave tail leaves for good: the
-// counts never grow again once groups_left is 0.
-// No global atomic, no inline assembly; ordinary loads and stores (NT = false).  The statistics are per workgroup, summed on the host.
+// One persistent launch per chunk of samples: the round loop of api/query_round_loop.h with the top-up above.
 template <bool PAIRS, bool ENV>
-__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(HJ_PQ_WAVES, 8))) void k_pq_paths(BatchState st, DeviceScene sc, PathQueryArgs q) {
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(HJ_QUERY_WAVES, 8))) void k_pq_paths(BatchState st, DeviceScene sc, PathQueryArgs q) {
   __shared__ std::conditional_t<ENV, WgSharedEnv, WgShared> sh;
-  const uint32_t g = blockIdx.x;
-  // (the called stages read the batch and scene descriptions from this kernel's argument segment and reach `sh` through its LDS address)
-  const uint64_t ka_ = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
-  const uint32_t ka_lo = (uint32_t)ka_, ka_hi = (uint32_t)(ka_ >> 32), sh_lds = (uint32_t)(uintptr_t)(WgSharedLds)&sh;
-  const uint32_t rays_lo = (uint32_t)(uintptr_t)q.rays, rays_hi = (uint32_t)((uint64_t)(uintptr_t)q.rays >> 32);
-  uint32_t groups_left = pq_num_groups(q.num_samples, st.num_wg, g);
-  uint32_t total_closest = 0, total_shadow = 0, total_hits = 0, total_unocc = 0, total_direct = 0;   // (thread 0's copies are published)
-  if (groups_left != 0) {
-    uint32_t k_next = 0;                     // next group of this workgroup's sample sequence
-    if (threadIdx.x == 0) { sh.n_ray[0] = 0; sh.n_ray[1] = 0; sh.n_gen = 0; sh.n_shadow = 0; sh.n_unocc = 0; sh.n_direct = 0; sh.cam_first = 0xFFFFFFFFu; sh.cam_k0 = 0; sh.n_cam_dead = 0; }
-    load_hot_nodes(sc, sh);
-    uint32_t waves = blockDim.x >> 6;
-    wg_sync(waves);
-    for (uint32_t parity = 0;; parity ^= 1u) {
-      // top-up: new paths behind the continuing ones, whole 64-sample groups while they fit
-      const uint32_t n0 = uni(sh.n_ray[parity]);
-      const uint32_t ngen = min(groups_left, (st.pool - n0) >> 6);
-      if (ngen != 0) {
-        stage_gen_rays_call<ENV>(ka_lo, ka_hi, rays_lo, rays_hi, q.spp, q.num_samples, g, sh_lds, parity, n0, k_next, ngen, waves);
-        wg_sync(waves);
-        k_next += ngen;
-        groups_left -= ngen;
-      }
-      const uint32_t n = n0 + uni(sh.n_gen), ns = uni(sh.n_shadow);
-      // next-event samples of the previous round's shade that the light-shaft grid answered: shadow rays of the statistics all the same
-      { const uint32_t nd = uni(sh.n_direct); total_shadow += nd; total_unocc += nd; total_direct += nd; }
-      if (n + ns == 0) {
-        if (groups_left == 0) break;
-        // (not reached with rays - every group below the chunk's count holds a sample -, kept as the path kernel has it)
-        if (threadIdx.x == 0) { sh.n_ray[parity ^ 1u] = 0; sh.n_direct = 0; }
-        wg_sync(waves);
-        continue;
-      }
-      // Tail of the workgroup: one wave can hold every ray of a round and the counts never grow again.
-      if (waves > 1u && groups_left == 0 && n + ns <= kPqTail) {
-        wg_sync(waves);                      // (everyone has read the counts)
-        if (threadIdx.x >= 64u) return;
-        waves = 1u;
-      }
-      wg_sync(waves);                        // everyone has read the counts before they are reset
-      if (threadIdx.x == 0) {
-        sh.head = 0; sh.head_cam = 0; sh.n_ray[parity ^ 1u] = 0; sh.n_gen = 0; sh.n_shadow = 0; sh.n_unocc = 0; sh.n_direct = 0;
-        sh.cam_first = 0xFFFFFFFFu; sh.cam_k0 = 0; sh.n_cam_dead = 0;
-      }
-      if (threadIdx.x < kNumTags) sh.cnt_hit[threadIdx.x] = 0;
-      wg_sync(waves);
-      stage_trace_merged<true, PAIRS, false>(st, sc, g, parity, n, ns, sh);
-      compact_hits_call<false, 4u, ENV>(ka_lo, ka_hi, g, n, sh_lds, waves);
-      wg_sync(waves);
-      if (n != 0) {
-        stage_shade_call<false, ENV>(ka_lo, ka_hi, g, parity, q.max_bounces, q.rr_start, sh_lds, waves);
-      }
-      total_closest += n;
-      total_shadow += ns;
-      for (uint32_t k = 0; k < kNumTags; k++) total_hits += uni(sh.cnt_hit[k]);
-      total_unocc += uni(sh.n_unocc);
-      wg_sync(waves);
-    }
-  }
-  if (threadIdx.x == 0) {
-    st.acc_closest[g] = total_closest;
-    st.acc_shadow[g] = total_shadow;
-    st.acc_hits[g] = total_hits;
-    st.acc_unoccluded[g] = total_unocc;
-    st.acc_direct[g] = total_direct;
-  }
+#define HJ_QUERY_TOP_UP stage_gen_rays_call<ENV>
+#include "query_round_loop.h"
+#undef HJ_QUERY_TOP_UP
 }
 
 // samples: two float4 per ray = (sum of the ray's spp sample radiances in ascending k, starting from +0, in float32; (float)spp),
@@ -208,7 +132,128 @@ void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, 
   else hipLaunchKernelGGL((hj::k_pq_paths<false, false>), grid, blk, 0, s, st, sc, q);
 }
 
+// ---- what the query entry points share (declared in hj_internal.h; host code only) ----
+
+// opts (NULL: the defaults) into o, and the refusals every path-type query has for them
+int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opts, hj_render_opts& o) {
+  if (opts) o = *opts;
+  else hj_default_render_opts(&o);
+  if (o.max_bounces == 0) return set_error(ctx, HJ_ERR_INVALID, "%s: max_bounces must be >= 1", fn);
+  if (o.use_bvh == 0) return set_error(ctx, HJ_ERR_UNSUPPORTED, "%s: the tree is always walked (use_bvh == 0: there is no linear-scan form)", fn);
+  if (o.flags & ~(uint32_t)HJ_RENDER_NO_LIGHT_GRID)
+    return set_error(ctx, HJ_ERR_INVALID, "%s: of the HJ_RENDER_* bits only HJ_RENDER_NO_LIGHT_GRID applies (flags 0x%x)", fn, o.flags);
+  return HJ_OK;
+}
+
+// A process without a HIP device cannot hold a context: a call that is otherwise valid gets HJ_ERR_DEVICE there, like every entry
+// point that computes.
+int query_gate(hj_context* ctx, const char* fn) {
+  if (!ctx) {
+    if (hj_device_count() == 0) return set_error(nullptr, HJ_ERR_DEVICE, "%s: no HIP device available; this library has no CPU fallback", fn);
+    return set_error(nullptr, HJ_ERR_INVALID, "%s: null context", fn);
+  }
+  HJ_NOT_BUSY_IN(ctx, fn);
+  HJ_NOT_PIPELINED_IN(ctx, fn);
+  if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "%s: no scene has been uploaded", fn);
+  return HJ_OK;
+}
+
+int QueryStats::reserve(hj_context* ctx, const char* fn, size_t launches, uint32_t G_) {
+  G = G_;
+  try {
+    if (on) h_acc.assign(launches * kStatWords * G, 0u);
+  } catch (const std::bad_alloc&) {
+    (void)hipStreamSynchronize(ctx->stream);                      // (nothing of this call stays in flight)
+    return set_error(ctx, HJ_ERR_NOMEM, "%s: out of host memory", fn);
+  }
+  return HJ_OK;
+}
+
+hipError_t QueryStats::enqueue(size_t launch, const hj::BatchState& st, hipStream_t s) {
+  if (!on) return hipSuccess;
+  return hipMemcpyAsync(h_acc.data() + launch * kStatWords * G, st.acc_closest, sizeof(uint32_t) * kStatWords * st.num_wg, hipMemcpyDeviceToHost, s);
+}
+
+void QueryStats::add(hj_render_stats& to, size_t chunk_rays, size_t len, uint32_t spp) const {
+  if (!on) return;
+  size_t launch = 0;
+  for (size_t at = 0; at < len; at += chunk_rays, launch++) {
+    const size_t cnt = std::min(chunk_rays, len - at);
+    add_stat_words(to, h_acc.data() + launch * kStatWords * G, std::min<size_t>(G, (cnt * spp + 63) / 64));
+  }
+}
+
+int fixed_spp_query(hj_context* ctx, const FixedSppQuery& q) {
+  const size_t n = q.n, rec = q.rec;
+  const uint32_t spp = q.spp;
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  const auto wall0 = std::chrono::steady_clock::now();
+
+  // Sizes (path_query_plan above).  A launch takes whole rays.
+  const Tuning& tn = ctx->tuning;
+  const PathQueryPlan plan = path_query_plan(tn, n, spp);
+  const size_t chunk_rays = plan.chunk_rays, most_rays = plan.most_rays;
+  const uint32_t G = plan.G;
+  const size_t f4 = sizeof(float4);
+  const hj::DeviceScene sc = scene_for(ctx, q.o);
+
+  // Per-workgroup arrays for HJ_PATHS_WGS workgroups, the most a call uses: two calls can need the same number of positions with
+  // different workgroup counts.  st.capacity: the samples allocated, not this call's.
+  hj_context::PathQuery& pq = ctx->paths;
+  if (const int rc = ensure_path_state(ctx, pq, plan.most_samples, G, (uint32_t)tn.paths_wgs, plan.pool, sc.has_extinction != 0, sc.env_alias != nullptr)) {
+    release_path_state(pq);
+    return rc;
+  }
+  hj::BatchState st = pq.st;
+  float4 *d_in = nullptr, *d_out = nullptr;
+  if (!q.on_device) {
+    HJ_TRY(dev_alloc(ctx, pq.in_rays, most_rays * 2 * f4));
+    HJ_TRY(dev_alloc(ctx, pq.out_samples, most_rays * rec * f4));
+    d_in = static_cast<float4*>(pq.in_rays.p);
+    d_out = static_cast<float4*>(pq.out_samples.p);
+  }
+  const size_t launches = (n + chunk_rays - 1) / chunk_rays;
+  QueryStats acc(q.stats != nullptr);
+  HJ_TRY(acc.reserve(ctx, q.name, launches, G));
+
+  hipError_t e = hipSuccess;
+  size_t launch = 0;
+  for (size_t at = 0; at < n && e == hipSuccess; at += chunk_rays, launch++) {
+    const uint32_t cnt = (uint32_t)std::min(chunk_rays, n - at);
+    if (q.on_device) {
+      d_in = reinterpret_cast<float4*>(const_cast<float*>(q.in)) + 2 * at;
+      d_out = reinterpret_cast<float4*>(q.out) + rec * at;
+    } else {
+      e = hipMemcpyAsync(d_in, q.in + 8 * at, cnt * 2 * f4, hipMemcpyHostToDevice, ctx->stream);
+      if (e != hipSuccess) break;
+    }
+    q.chunk(q, st, sc, G, d_in, cnt, d_out, ctx->stream);
+    e = hipGetLastError();
+    if (e == hipSuccess && !q.on_device) e = hipMemcpyAsync(q.out + 4 * rec * at, d_out, cnt * rec * f4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = acc.enqueue(launch, st, ctx->stream);
+  }
+  const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "%s: %s", q.name, hipGetErrorString(e));
+  if (q.stats) {
+    std::memset(q.stats, 0, sizeof *q.stats);
+    acc.add(*q.stats, chunk_rays, n, spp);
+    q.stats->paths = (uint64_t)n * spp;
+    q.stats->batches = launches;
+    q.stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  }
+  return HJ_OK;
+}
+
 }  // namespace hjapi
+
+// the path launch and the resolve of one chunk (FixedSppQuery::chunk)
+static void paths_chunk(const FixedSppQuery& q, hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_rays, uint32_t cnt,
+                        float4* d_out, hipStream_t s) {
+  path_query_pass(st, sc, G, d_rays, cnt, q.spp, q.o, s);
+  hipLaunchKernelGGL(hj::k_pq_resolve, dim3((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads), dim3(hj::kBlockThreads), 0, s,
+                     static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd), q.spp, cnt, d_out);
+}
 
 extern "C" {
 
@@ -222,89 +267,11 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
   if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths: %zu rays, at most 2^31 - 1 a call", n);
   if (n != 0 && on_device && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(samples)) & 15u) != 0)
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths: device arrays must be 16-byte aligned");
-  hj_render_opts o;
-  if (opts) o = *opts;
-  else hj_default_render_opts(&o);
-  if (o.max_bounces == 0) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths: max_bounces must be >= 1");
-  if (o.use_bvh == 0) return set_error(ctx, HJ_ERR_UNSUPPORTED, "hj_trace_paths: the tree is always walked (use_bvh == 0: there is no linear-scan form)");
-  if (o.flags & ~(uint32_t)HJ_RENDER_NO_LIGHT_GRID)
-    return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths: of the HJ_RENDER_* bits only HJ_RENDER_NO_LIGHT_GRID applies (flags 0x%x)", o.flags);
-  if (!ctx) {
-    if (hj_device_count() == 0) return set_error(nullptr, HJ_ERR_DEVICE, "hj_trace_paths: no HIP device available; this library has no CPU fallback");
-    return set_error(nullptr, HJ_ERR_INVALID, "hj_trace_paths: null context");
-  }
-  HJ_NOT_BUSY(ctx);
-  HJ_NOT_PIPELINED(ctx);
-  if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "hj_trace_paths: no scene has been uploaded");
+  FixedSppQuery q{__func__, rays, n, spp, 2, on_device, samples, stats, {}, paths_chunk, flags};
+  HJ_TRY(query_render_opts(ctx, __func__, opts, q.o));
+  HJ_TRY(query_gate(ctx, __func__));
   if (n == 0) return HJ_OK;
-  HJ_HIP(ctx, hipSetDevice(ctx->device));
-  const auto wall0 = std::chrono::steady_clock::now();
-
-  // Sizes (path_query_plan above).
-  const Tuning& tn = ctx->tuning;
-  const PathQueryPlan plan = path_query_plan(tn, n, spp);
-  const size_t chunk_rays = plan.chunk_rays, most_rays = plan.most_rays, most_samples = plan.most_samples;
-  const uint32_t G = plan.G, pool = plan.pool;
-  const size_t f4 = sizeof(float4);
-  const hj::DeviceScene sc = scene_for(ctx, o);
-
-  // Per-workgroup arrays for HJ_PATHS_WGS workgroups, the most a call uses: two calls can need the same number of positions with
-  // different workgroup counts.  st.capacity: the samples allocated, not this call's.
-  hj_context::PathQuery& pq = ctx->paths;
-  if (const int rc = ensure_path_state(ctx, pq, most_samples, G, (uint32_t)tn.paths_wgs, pool, sc.has_extinction != 0, sc.env_alias != nullptr)) {
-    release_path_state(pq);
-    return rc;
-  }
-  hj::BatchState st = pq.st;
-  float4 *d_rays = nullptr, *d_out = nullptr;
-  if (!on_device) {
-    HJ_TRY(dev_alloc(ctx, pq.in_rays, most_rays * 2 * f4));
-    HJ_TRY(dev_alloc(ctx, pq.out_samples, most_rays * 2 * f4));
-    d_rays = static_cast<float4*>(pq.in_rays.p);
-    d_out = static_cast<float4*>(pq.out_samples.p);
-  }
-  const size_t launches = (n + chunk_rays - 1) / chunk_rays;
-  std::vector<uint32_t> h_acc;
-  try {
-    if (stats) h_acc.assign(launches * kStatWords * G, 0u);
-  } catch (const std::bad_alloc&) {
-    return set_error(ctx, HJ_ERR_NOMEM, "hj_trace_paths: out of host memory");
-  }
-
-  hipError_t e = hipSuccess;
-  size_t launch = 0;
-  for (size_t at = 0; at < n && e == hipSuccess; at += chunk_rays, launch++) {
-    const uint32_t cnt = (uint32_t)std::min(chunk_rays, n - at);
-    if (on_device) {
-      d_rays = reinterpret_cast<float4*>(const_cast<float*>(rays)) + 2 * at;
-      d_out = reinterpret_cast<float4*>(samples) + 2 * at;
-    } else {
-      e = hipMemcpyAsync(d_rays, rays + 8 * at, cnt * 2 * f4, hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) break;
-    }
-    path_query_pass(st, sc, G, d_rays, cnt, spp, o, ctx->stream);
-    hipLaunchKernelGGL(hj::k_pq_resolve, dim3((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads), dim3(hj::kBlockThreads), 0, ctx->stream,
-                       static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd), spp, cnt, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(samples + 8 * at, d_out, cnt * 2 * f4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && stats)
-      e = hipMemcpyAsync(h_acc.data() + launch * kStatWords * G, st.acc_closest, sizeof(uint32_t) * kStatWords * st.num_wg, hipMemcpyDeviceToHost, ctx->stream);
-  }
-  const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "hj_trace_paths: %s", hipGetErrorString(e));
-  if (stats) {
-    std::memset(stats, 0, sizeof *stats);
-    size_t at = 0;
-    for (size_t l = 0; l < launches; l++, at += chunk_rays) {
-      const size_t cnt = std::min(chunk_rays, n - at);
-      add_stat_words(*stats, h_acc.data() + l * kStatWords * G, std::min<size_t>(G, (cnt * spp + 63) / 64));
-    }
-    stats->paths = (uint64_t)n * spp;
-    stats->batches = launches;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-  }
-  return HJ_OK;
+  return fixed_spp_query(ctx, q);
 }
 
 }  // extern "C"

@@ -126,8 +126,8 @@ void launch_query(hj_context* ctx, const float4* rays, uint32_t n, bool any, flo
 extern "C" {
 
 // The argument checks come first and need neither a device nor a context's state (a refusal without a context leaves its text in
-// hj_last_error(NULL), as hj_context_create's do).  A process without a HIP device cannot hold a context: a call that is otherwise
-// valid gets HJ_ERR_DEVICE there, like every entry point that computes.
+// hj_last_error(NULL), as hj_context_create's do).  Then the queries' gate (query_gate, api/path_query.hip): a null context, a frame
+// in flight, frames in the pipeline, no scene.
 int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, float* hits, float* surface) {
   if (flags & ~(uint32_t)(HJ_TRACE_ANY_HIT | HJ_TRACE_DEVICE_ARRAYS)) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: unknown flag bits 0x%x", flags);
   const bool any = (flags & HJ_TRACE_ANY_HIT) != 0, on_device = (flags & HJ_TRACE_DEVICE_ARRAYS) != 0;
@@ -138,13 +138,7 @@ int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, 
     if (on_device && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surface)) & 15u) != 0)
       return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: device arrays must be 16-byte aligned");
   }
-  if (!ctx) {
-    if (hj_device_count() == 0) return set_error(nullptr, HJ_ERR_DEVICE, "hj_trace_rays: no HIP device available; this library has no CPU fallback");
-    return set_error(nullptr, HJ_ERR_INVALID, "hj_trace_rays: null context");
-  }
-  HJ_NOT_BUSY(ctx);
-  HJ_NOT_PIPELINED(ctx);
-  if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "hj_trace_rays: no scene has been uploaded");
+  HJ_TRY(query_gate(ctx, __func__));
   if (n == 0) return HJ_OK;
   HJ_HIP(ctx, hipSetDevice(ctx->device));
   // rays of one launch (HJ_TRACE_CHUNK): bounds the staging buffers of host arrays; device arrays take the same loop
