@@ -37,6 +37,7 @@ NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "do
 NUM_IN_WORDS, NUM_OUT_WORDS, NUM_MAX_RECORDS = 6, 4, 1 << 20
 # hj_debug_shade_step: the record sizes and the cap
 STEP_IN_WORDS, STEP_OUT_WORDS, STEP_MAX_RECORDS = 18, 33, 1 << 16
+REINSERT_MAX_PASSES = 64         # hj_optimize_bvh_device: passes a call
 RECON_MAX_BLOCKS = 64            # hj_debug_reconstruct: blocks a call
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64

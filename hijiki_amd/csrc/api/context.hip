@@ -144,7 +144,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (14u << 8) | 0u; }   // 0.14.0: hj_trace_irradiance
+uint32_t hj_version(void) { return (0u << 16) | (15u << 8) | 0u; }   // 0.15.0: hj_optimize_bvh_device
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

@@ -13,6 +13,8 @@
 //                         api/refit_pass.hpp: the refit's stages for a caller that brings its own link set)
 //   api/scene_update.hip  hj_scene_update_shapes: the uploaded scene's boxes, triangle and emitter records recomputed in place
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
+//   api/tree_reinsert.hip hj_optimize_bvh_device: the tree left on the device optimised by parallel reinsertion (its kernels, around the
+//                         per-node steps of api/tree_reinsert.h; includes no kernel header but hj_num.h's)
 //   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
 //   api/environment.hip   environment lighting: the checks and the alias table of hj_scene_upload_env, hj_debug_env_*
 //   api/step_probe.hip    hj_debug_num: the functions of kernels/hj_num.h on caller-given inputs (includes no other kernel header);

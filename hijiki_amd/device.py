@@ -26,7 +26,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
            "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
-           "hj_trace_irradiance")
+           "hj_trace_irradiance", "hj_optimize_bvh_device")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -94,6 +94,8 @@ def lib():
         L.hj_bvh_device_read.argtypes = [vp, C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_refit_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t),
                                           C.POINTER(C.c_double)]
+        L.hj_optimize_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.POINTER(abi.BvhNode), C.c_size_t,
+                                             C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
         L.hj_scene_update_shapes.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.POINTER(C.c_double)]
         L.hj_debug_scene_tree.argtypes = [vp, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.hj_debug_num.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]
@@ -349,6 +351,27 @@ class Renderer:
                                               0 if nodes is None else len(nodes), C.byref(got), C.byref(sa) if cost else None))
         out = got.value if keep_on_device else nodes[:got.value]
         return (out, sa.value) if cost else out
+
+    def optimize_bvh_device(self, compiled=None, passes=8, keep_on_device=True):
+        """hj_optimize_bvh_device: the tree `build_bvh` / `refit_bvh` left on the device (keep_on_device=True there), optimised by at
+        most `passes` passes of parallel reinsertion; it replaces that tree.  compiled: the scene whose rays vote the child order of
+        the new tree (None: no vote).  Returns a dict: `nodes` (the record count, or with keep_on_device=False the (N, 8) uint32
+        records), `cost_before`, `cost_after` (surface-area cost, as `refit_bvh`'s), `moves` (subtrees moved)."""
+        passes = int(passes)
+        if not 0 <= passes <= abi.REINSERT_MAX_PASSES:
+            raise ValueError(f"passes must be 0 ... {abi.REINSERT_MAX_PASSES}")
+        got, moves = C.c_size_t(0), C.c_uint32(0)
+        before, after = C.c_double(0.0), C.c_double(0.0)
+        nodes = None
+        if not keep_on_device:
+            self._check(lib().hj_bvh_device_read(self._h, None, 0, C.byref(got)))
+            nodes = np.zeros((max(got.value, 1), 8), np.uint32)
+        self._check(lib().hj_optimize_bvh_device(self._h, None if compiled is None else C.byref(compiled.desc), passes,
+                                                 None if nodes is None else nodes.ctypes.data_as(C.POINTER(abi.BvhNode)),
+                                                 0 if nodes is None else len(nodes), C.byref(got), C.byref(before), C.byref(after),
+                                                 C.byref(moves)))
+        return {"nodes": got.value if keep_on_device else nodes[:got.value], "cost_before": before.value, "cost_after": after.value,
+                "moves": moves.value}
 
     def update_shapes(self, compiled, device_arrays=None, light_grid=True, cost=False):
         """hj_scene_update_shapes: the uploaded scene's shapes moved in place - spheres, quads, vertices, emitters and camera of

@@ -379,6 +379,30 @@ int hj_bvh_device_read(hj_context* ctx, hj_bvh_node* out_nodes, size_t capacity,
 int hj_refit_bvh_device(hj_context* ctx, const hj_scene_desc* scene, hj_bvh_node* out_nodes /* may be NULL */, size_t capacity,
                         size_t* out_num_nodes /* may be NULL */, double* out_cost /* may be NULL */);
 
+/* hj_optimize_bvh_device (ABI 0.15): the tree hj_build_bvh_device or hj_refit_bvh_device left on the device, optimised there by
+ * parallel reinsertion (Meister & Bittner 2018; objective and bound of the host's insertion-based pass): at most `passes` (<= 64)
+ * passes, each of which lets every node but the root and its children look for the node whose sibling it should become, resolves
+ * the conflicts (a move locks the nodes whose links it rewrites; the larger gain, then the larger node index wins; a pass that
+ * does not lower the cost is taken back and repeated with every node on a move's path locked, which makes the gains independent)
+ * and applies the winners; a pass without a move ends the call, and the cost never rises.  The result is a function of the input records and
+ * `passes` alone.  It replaces the tree on the device (hj_scene_upload* with scene->bvh == NULL takes it over, hj_bvh_device_read
+ * copies it out; the shape arrays kept with the tree stay): a valid pre-order skip-link array of the same records, record 0 the
+ * root, every leaf's box bit for bit what it was, every inner box the union of its two children's, the root's exit by
+ * hj_build_bvh_device's rule.  scene != NULL (its shape counts must be the tree's): the call ends with the ray-voted child order
+ * over the new tree, as the build does (camera, materials and emitters of `scene`, HJ_LBVH_VOTE_PATHS paths; a moved parent holds
+ * its children in the order (new sibling, moved node)); scene == NULL: no vote.  out_cost_before / out_cost_after: the surface-area
+ * cost (hj_refit_bvh_device's out_cost) of the input and of the final records; out_moves: subtrees moved, summed over the passes.
+ * passes == 0, a tree of fewer than 7 records, or a first pass without a move: HJ_OK, the tree untouched, both costs equal.
+ * Refused, the tree on the device left as it was: passes > 64 or a node buffer that is too small (HJ_ERR_INVALID), a null context,
+ * a frame in flight, no tree on the device (HJ_ERR_STATE), a scene with other shape counts (HJ_ERR_INVALID).  A device failure
+ * midway leaves no tree on the device, as a failed refit does.  A call that moved something also drops the links
+ * hj_refit_bvh_device kept: they are the old topology's, so the next refit must bring one (scene->bvh = the optimised records;
+ * with scene->bvh == NULL it is refused with HJ_ERR_STATE). */
+int hj_optimize_bvh_device(hj_context* ctx, const hj_scene_desc* scene /* may be NULL */, uint32_t passes,
+                           hj_bvh_node* out_nodes /* may be NULL */, size_t capacity, size_t* out_num_nodes /* may be NULL */,
+                           double* out_cost_before /* may be NULL */, double* out_cost_after /* may be NULL */,
+                           uint32_t* out_moves /* may be NULL: subtrees moved, summed over the passes */);
+
 /* The uploaded scene's shapes moved IN PLACE (ABI 0.7): the frame loop of an animation becomes "move the shapes,
  * hj_scene_update_shapes, render" - no refit + upload, no re-layout, no allocation after the first call.
  * `scene` carries the shapes as they are NOW: spheres, quads, vertices, emitters (pdf and cdf change with area) and camera; every
