@@ -31,6 +31,9 @@ PATHS_DEVICE_ARRAYS = 1           # hj_trace_paths flag
 GATHER_DEVICE_ARRAYS = 1          # hj_trace_irradiance flags
 GATHER_SPHERE = 2
 GATHER_SH9 = 4                    # (only together with GATHER_SPHERE)
+LIGHTMAP_DEVICE_ARRAYS = 1        # hj_lightmap_desc flag
+LIGHTMAP_MAX_GUTTER = 64          # hj_bake_lightmap: dilation passes a call
+LIGHTMAP_NONE = 0xFFFFFFFF        # owner word of a texel nobody owns
 # hj_debug_num: enum hj_num_op in its order, the record sizes and the cap
 NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "dot3", "cross3", "normalize3", "reflect3", "rng_seed",
            "rng_uint", "rng_float", "rand_cos_hemisphere", "rand_uniform_sphere", "rand_barycentric")
@@ -166,6 +169,12 @@ class RenderOpts(C.Structure):
 class AdaptiveOpts(C.Structure):
     """hj_adaptive_opts (ABI 0.13): the rounds and the stop rule of hj_trace_paths_adaptive."""
     _fields_ = [("spp_min", u32), ("spp_step", u32), ("spp_max", u32), ("rel_error", f32), ("floor", f32)]
+
+
+class LightmapDesc(C.Structure):
+    """hj_lightmap_desc (ABI 0.16): the atlas, the triangle range, the seeds and the offset of hj_lightmap_texels / hj_bake_lightmap."""
+    _fields_ = [("width", u32), ("height", u32), ("first_triangle", u32), ("num_triangles", u32), ("seed", u32), ("seed_stride", u32),
+                ("offset", f32), ("flags", u32)]
 
 
 class RenderStats(C.Structure):

@@ -32,6 +32,10 @@
 //   api/gather_query.hip  hj_trace_irradiance: gather queries at caller-given points (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the same round loop with a top-up that draws a direction
 //                         at a point, and the per-point reduction); its host half behind the checks is fixed_spp_query
+//   api/lightmap.hip      hj_lightmap_texels, hj_bake_lightmap: the uploaded triangles' UVs rasterised into gather points, the gather's
+//                         records scattered into an atlas and dilated (the only unit that includes kernels/hj_lightmap.h; beside it
+//                         hj_num.h alone: the path kernels' machine code does not depend on it).  The gather itself is
+//                         hj_trace_irradiance's, entered through that entry point with device arrays
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -377,6 +381,12 @@ struct hj_context {
     hjapi::DevBuf pa_moments;             // ... staging of host moments
     hjapi::PinnedBuf<uint32_t> pa_active; // ... the total as the host reads it after a round
   } paths;
+
+  // hj_lightmap_texels / hj_bake_lightmap (api/lightmap.hip): the owner map (a word per texel), per 64 triangles the mask of those
+  // whose texel box is left to whole waves, the scan's tile counts and their
+  // total, staging of host-side points; the bake's points, gather records and its two ping-pong images.  Grown on demand
+  // (dev_alloc keeps a buffer that is large enough), reused by every call, freed with the context.
+  struct Lightmap { hjapi::DevBuf owner, masks, counts, points, records, image[2]; } lightmap;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment

@@ -64,7 +64,11 @@ struct Tuning {
   X(paths_pool, "HJ_PATHS_POOL", 2048, 64, 1 << 19)        /* positions per workgroup (rounded down to a multiple of 64) */             \
   X(paths_wgs, "HJ_PATHS_WGS", 2048, 1, 4096)              /* most workgroups per launch (fewer when the chunk has fewer 64-sample groups) */ \
   X(paths_chunk, "HJ_PATHS_CHUNK", 1 << 22, 64, 0x7FFFFFFF) /* samples per launch (the sample index shares its word with kCameraFlag) */  \
-  X(bvh_vote_shadow, "HJ_BVH_VOTE_SHADOW", kUnset, 0, 16)  /* a shadow ray's vote in quarters of a closest-hit ray's: 1 (4 on large trees) */
+  X(bvh_vote_shadow, "HJ_BVH_VOTE_SHADOW", kUnset, 0, 16)  /* a shadow ray's vote in quarters of a closest-hit ray's: 1 (4 on large trees) */ \
+  /* hj_lightmap_texels / hj_bake_lightmap (read like hj_trace_rays' rows: as the context's creation or its last upload, render     \
+     call or build found them - the light-map calls themselves do not refresh the table) */                                          \
+  X(lightmap_lane_texels, "HJ_LIGHTMAP_LANE_TEXELS", 64, 0, 1 << 28) /* k_lm_owner: a texel box up to this size is one lane's, a larger one k_lm_owner_wide's */ \
+  X(lightmap_slices, "HJ_LIGHTMAP_SLICES", kUnset, 1, 256) /* grid rows of k_lm_owner_wide that share a box: as many as fill the device, at most 256 */
   // presence flags (debugging aids): set to anything = on
 #define HJ_TUNING_FLAGS(X)                                                                                                              \
   X(trace_bounces, "HJ_TRACE_BOUNCES")                     /* per-bounce table of the split-kernel path on stderr */                    \

@@ -2,11 +2,14 @@
 //
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
 //              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] [--env FILE [--env-scale S]]
+//              [--bake-lightmap WxH [--gutter 2]]
 //              <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
 // no preview window, so --present-interval is accepted and ignored; --seed replaces the OS-seeded block RNG; --textures (not
-// upstream) renders the MTL's map_Kd images on diffuse materials; --env (not upstream) lights the scene with a lat-long HDR image.
+// upstream) renders the MTL's map_Kd images on diffuse materials; --env (not upstream) lights the scene with a lat-long HDR image;
+// --bake-lightmap WxH (not upstream) writes no camera frame but the scene's light-map atlas: hj_bake_lightmap over all triangles at
+// -s samples a texel, seed --seed, stride 1, offset 1e-3, --gutter dilation passes; the atlas's rgb goes to -o, row v = 0 on top.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +30,8 @@ struct Opt {
   uint64_t seed = 1;
   std::string output_image = "/tmp/output.exr", scene, env;
   float env_scale = 1.0f;
+  uint32_t bake_w = 0, bake_h = 0, gutter = 2;             // --bake-lightmap WxH (0: render a frame), --gutter
+  bool gutter_given = false;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -39,6 +44,8 @@ struct Opt {
                "    --textures            (not upstream) diffuse materials with map_Kd take their colour from that image (PFM or P6 PPM)\n\n"
                "        --env <file>                             (not upstream) light the scene with this lat-long image (PFM or P6 PPM)\n"
                "        --env-scale <scale>                      [default: 1] (not upstream) radiance scale of --env\n"
+               "        --bake-lightmap <W>x<H>                  (not upstream) bake the light-map atlas of the scene's UVs instead of a frame\n"
+               "        --gutter <passes>                        [default: 2] (not upstream) dilation passes of --bake-lightmap, 0 ... 64\n"
                "OPTIONS:\n    -h, --height <height>                        [default: 600]\n"
                "    -o, --output-image <output-image>            [default: /tmp/output.exr] (.exr, .pfm or .png)\n"
                "        --present-interval <present-interval>    [default: 128] (ignored: no preview window)\n"
@@ -74,6 +81,20 @@ Opt parse(int argc, char** argv) {
       o.env_scale = std::strtof(v.c_str(), &end);
       if (end == v.c_str() || *end != '\0' || !(o.env_scale >= 0.0f) || o.env_scale > 3.0e38f) usage(("bad --env-scale " + v).c_str());
     }
+    else if (a == "--bake-lightmap") {
+      const std::string v = value(i);
+      unsigned w = 0, h = 0;
+      char tail = 0;
+      if (std::sscanf(v.c_str(), "%ux%u%c", &w, &h, &tail) != 2 || w == 0 || h == 0 || w > 16384u || h > 16384u || (uint64_t)w * h > (1ull << 26))
+        usage(("bad --bake-lightmap " + v + " (WxH, 1 ... 16384 each, at most 2^26 texels)").c_str());
+      o.bake_w = w; o.bake_h = h;
+    }
+    else if (a == "--gutter") {
+      const unsigned long g = std::stoul(value(i));
+      if (g > HJ_LIGHTMAP_MAX_GUTTER) usage("--gutter above 64");
+      o.gutter = (uint32_t)g;
+      o.gutter_given = true;
+    }
     else if (a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown flag " + a).c_str());
     else if (o.scene.empty()) o.scene = a;
@@ -81,6 +102,7 @@ Opt parse(int argc, char** argv) {
   }
   if (o.scene.empty()) usage("the <scene> argument is required");
   if (o.env.empty() && o.env_scale != 1.0f) usage("--env-scale without --env");
+  if (o.gutter_given && o.bake_w == 0) usage("--gutter without --bake-lightmap");
   return o;
 }
 
@@ -131,6 +153,26 @@ int main(int argc, char** argv) {
     } else {
       check(ctx, opt.textures ? hj_scene_upload_textured(ctx, &desc, &tex) : hj_scene_upload(ctx, &desc), "scene upload");
     }
+    const auto save = [&](uint32_t w, uint32_t h, const float* rgb) {
+      const std::string ext = opt.output_image.size() > 4 ? opt.output_image.substr(opt.output_image.size() - 4) : "";
+      if (ext == ".pfm") hijiki::write_pfm(opt.output_image, w, h, rgb);
+      else if (ext == ".png") hijiki::write_png(opt.output_image, w, h, rgb);   // the preview image
+      else hijiki::write_exr(opt.output_image, w, h, rgb);
+    };
+    if (opt.bake_w != 0) {                                             // --bake-lightmap: the atlas instead of a frame
+      const hj_lightmap_desc lm{opt.bake_w, opt.bake_h, 0u, 0u, (uint32_t)opt.seed, 1u, 1e-3f, 0u};
+      std::vector<float> rgba((size_t)opt.bake_w * opt.bake_h * 4), rgb((size_t)opt.bake_w * opt.bake_h * 3);
+      size_t texels = 0;
+      hj_render_stats bst;
+      std::printf("Baking %u x %u texels...\n", opt.bake_w, opt.bake_h);
+      check(ctx, hj_bake_lightmap(ctx, &lm, opt.sample_count, opt.gutter, nullptr, rgba.data(), &texels, &bst), "bake");
+      std::printf("Gathered %llu paths at %zu texels in %.6fs\n", (unsigned long long)bst.paths, texels, bst.total_ms * 1e-3);
+      for (size_t t = 0; t < (size_t)opt.bake_w * opt.bake_h; t++)
+        for (int c = 0; c < 3; c++) rgb[3 * t + c] = rgba[4 * t + c];
+      save(opt.bake_w, opt.bake_h, rgb.data());
+      hj_context_destroy(ctx);
+      return 0;
+    }
     check(ctx, hj_framebuffer_create(ctx, opt.width, opt.height, nullptr), "framebuffer");
     hj_render_opts ro;
     hj_default_render_opts(&ro);
@@ -155,10 +197,7 @@ int main(int argc, char** argv) {
 
     std::vector<float> rgb((size_t)opt.width * opt.height * 3);
     check(ctx, hj_framebuffer_resolve(ctx, rgb.data()), "read-back");  // Renderer::save_image, src/main.rs:1493
-    const std::string ext = opt.output_image.size() > 4 ? opt.output_image.substr(opt.output_image.size() - 4) : "";
-    if (ext == ".pfm") hijiki::write_pfm(opt.output_image, opt.width, opt.height, rgb.data());
-    else if (ext == ".png") hijiki::write_png(opt.output_image, opt.width, opt.height, rgb.data());   // the preview image
-    else hijiki::write_exr(opt.output_image, opt.width, opt.height, rgb.data());
+    save(opt.width, opt.height, rgb.data());
     hj_context_destroy(ctx);
     return 0;
   } catch (const std::exception& e) {

@@ -26,7 +26,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
            "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
-           "hj_trace_irradiance", "hj_optimize_bvh_device")
+           "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -88,6 +88,9 @@ def lib():
                                               C.POINTER(abi.RenderStats)]      # (host or device pointers)
         L.hj_trace_irradiance.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(abi.RenderOpts), C.c_uint32, vp,
                                           C.POINTER(abi.RenderStats)]          # (host or device pointers)
+        L.hj_lightmap_texels.argtypes = [vp, C.POINTER(abi.LightmapDesc), vp, C.c_size_t, vp, C.POINTER(C.c_size_t)]   # (host or device pointers)
+        L.hj_bake_lightmap.argtypes = [vp, C.POINTER(abi.LightmapDesc), C.c_uint32, C.c_uint32, C.POINTER(abi.RenderOpts), vp,
+                                       C.POINTER(C.c_size_t), C.POINTER(abi.RenderStats)]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -604,6 +607,74 @@ class Renderer:
         out = np.zeros((n, words), np.float32)
         self._check(lib().hj_trace_irradiance(self._h, points.ctypes.data, n, spp, o, flags, out.ctypes.data, C.byref(st)))
         return (out, stats_dict(st)) if stats else out
+
+    @staticmethod
+    def _lightmap_desc(what, width, height, first_triangle, num_triangles, seed, seed_stride, offset, device):
+        """The desc of the light-map calls, checked before any call."""
+        width, height = int(width), int(height)
+        if not (1 <= width <= 16384 and 1 <= height <= 16384 and width * height <= 1 << 26):
+            raise ValueError(f"{what}: atlas {width} x {height}: 1 ... 16384 each and at most 2^26 texels")
+        offset = float(offset)
+        if not np.isfinite(np.float32(offset)):
+            raise ValueError(f"{what}: offset {offset} is not finite")
+        for name, v in (("first_triangle", first_triangle), ("num_triangles", num_triangles), ("seed", seed), ("seed_stride", seed_stride)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{what}: {name} {v} is no uint32")
+        return abi.LightmapDesc(width, height, int(first_triangle), int(num_triangles), int(seed), int(seed_stride), offset,
+                                abi.LIGHTMAP_DEVICE_ARRAYS if device else 0)
+
+    def lightmap_texels(self, width, height, first_triangle=0, num_triangles=0, seed=0, seed_stride=1, offset=0.0, owner=False, device=False):
+        """hj_lightmap_texels: the uploaded scene's triangle UVs rasterised into a width x height atlas -> (count, 8) float32 points, one
+        per texel that a triangle of [first_triangle, first_triangle + num_triangles) owns (0: all from first_triangle on), in ascending
+        texel index t = y * width + x: position (moved by normal * offset), normal, the seed seed + t * seed_stride as the bits of
+        word 6, t as the bits of word 7 - a `points` argument of `trace_irradiance` as it stands.  include/hijiki_hip.h spells the
+        coverage rule out.  owner=True: also the (height, width) uint32 owner map (abi.LIGHTMAP_NONE: no owner).  device=True: torch
+        tensors on the renderer's GPU, written in place on the device; torch's current stream is synchronised first."""
+        d = self._lightmap_desc("lightmap_texels", width, height, first_triangle, num_triangles, seed, seed_stride, offset, device)
+        count = C.c_size_t(0)
+        self._check(lib().hj_lightmap_texels(self._h, C.byref(d), None, 0, None, C.byref(count)))
+        n = count.value
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            pts = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            own = torch.empty((d.height, d.width), dtype=torch.int32, device=dev) if owner else None
+            torch.cuda.current_stream(dev).synchronize()              # (the allocations)
+            self._check(lib().hj_lightmap_texels(self._h, C.byref(d), pts.data_ptr() if n else None, n, own.data_ptr() if owner else None,
+                                                 C.byref(count)))
+            return (pts, own) if owner else pts
+        pts = np.zeros((n, 8), np.float32)
+        own = np.zeros((d.height, d.width), np.uint32) if owner else None
+        if n or owner:
+            self._check(lib().hj_lightmap_texels(self._h, C.byref(d), pts.ctypes.data if n else None, n, own.ctypes.data if owner else None,
+                                                 C.byref(count)))
+        return (pts, own) if owner else pts
+
+    def bake_lightmap(self, width, height, spp, gutter=2, first_triangle=0, num_triangles=0, seed=0, seed_stride=1, offset=0.0, opts=None,
+                      stats=False, device=False):
+        """hj_bake_lightmap: `lightmap_texels`, the hemisphere gather of `trace_irradiance` at `spp` samples over its points, and the
+        records scattered into the atlas, all on the device -> (height, width, 4) float32: a texel with a record holds its irradiance
+        (pi / spp x the gathered sum) and alpha 1; `gutter` dilation passes give texels next to covered ones the mean of their covered
+        neighbours and alpha 0.5; everything else is zero.  opts as in `trace_irradiance`.  device=True: a torch tensor on the
+        renderer's GPU.  stats=True: returns (image, the gather's statistics dict with `texels` = the texels that had a record)."""
+        spp, gutter = int(spp), int(gutter)
+        if not 1 <= spp <= 65536:
+            raise ValueError(f"bake_lightmap: spp {spp} outside [1, 65536]")
+        if not 0 <= gutter <= abi.LIGHTMAP_MAX_GUTTER:
+            raise ValueError(f"bake_lightmap: gutter {gutter} outside [0, {abi.LIGHTMAP_MAX_GUTTER}]")
+        d = self._lightmap_desc("bake_lightmap", width, height, first_triangle, num_triangles, seed, seed_stride, offset, device)
+        st, count = abi.RenderStats(), C.c_size_t(0)
+        o = C.byref(opts) if opts is not None else None
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            img = torch.empty((d.height, d.width, 4), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            self._check(lib().hj_bake_lightmap(self._h, C.byref(d), spp, gutter, o, img.data_ptr(), C.byref(count), C.byref(st)))
+        else:
+            img = np.zeros((d.height, d.width, 4), np.float32)
+            self._check(lib().hj_bake_lightmap(self._h, C.byref(d), spp, gutter, o, img.ctypes.data, C.byref(count), C.byref(st)))
+        return (img, dict(stats_dict(st), texels=count.value)) if stats else img
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

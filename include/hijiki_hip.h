@@ -658,6 +658,74 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
 int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
                         uint32_t flags, float* out, hj_render_stats* stats /* may be NULL */);
 
+/* hj_lightmap_texels (ABI 0.16): the uploaded scene's triangle UVs rasterised into gather points, on the device - from "uploaded
+ * scene" to the `points` of hj_trace_irradiance without a trip through the host.  Reads the triangles and the hj_vertex records the
+ * scene was uploaded with (u, v, pos, normal; hj_scene_update_shapes rewrites them).  No counterpart in the reference.
+ * Every arithmetic operation below is float32, one rounding per operation, no contraction; vector operations are the numeric
+ * contract's (cross, normalize, v * s, v + v of kernels/hj_num.h: DESIGN.md 3); division is IEEE `/`.
+ *   Texel t = y * width + x has its centre at p = (((float)x + 0.5f) / (float)width, ((float)y + 0.5f) / (float)height).
+ *   Triangle i has vertex uv a, b, c (hj_vertex::u / v of its three vertices, not wrapped).  With
+ *       edge(s, t, p) = (t.u - s.u) * (p.v - s.v) - (t.v - s.v) * (p.u - s.u)
+ *       e0 = edge(b, c, p)   e1 = edge(c, a, p)   e2 = edge(a, b, p)   s = (e0 + e1) + e2
+ *   triangle i COVERS the texel when all six uv are finite; min(a.u, b.u, c.u) <= p.u <= max(a.u, b.u, c.u) and the same in v (exact
+ *   comparisons: the closed box); (e0 >= 0 && e1 >= 0 && e2 >= 0) || (e0 <= 0 && e1 <= 0 && e2 <= 0) - both windings count -; and
+ *   s != 0 - a zero-area footprint covers nothing.
+ *   The OWNER of a texel is the lowest covering triangle index in [first_triangle, first_triangle + num_triangles).  For the owner:
+ *       hu = e1 / s   hv = e2 / s   l0 = (1.0f - hu) - hv
+ *       P = (A.pos * l0 + B.pos * hu) + C.pos * hv
+ *       n = normalize((A.normal * l0 + B.normal * hu) + C.normal * hv)              (populateTriangle's expressions)
+ *   A texel whose n has a non-finite component, or is all zero, has NO owner: the call never emits a normal that the hemisphere
+ *   gather could not build its frame about.  The emitted position is P + n * offset.
+ *   points (may be NULL: the call only counts): the owned texels in ascending t, 8 words each - 0-2 the position, 3-5 the normal,
+ *     6 the seed seed + t * seed_stride (uint32 wrap-around) as bits, 7 t as uint32 bits.  Word 7 is the word hj_trace_irradiance
+ *     ignores: the array is a valid `points` argument as it stands and carries its own scatter address.
+ *   owner (may be NULL): width * height words, the owning triangle index or 0xFFFFFFFF.
+ *   *out_count: the number of owned texels, written whenever the call returns HJ_OK - and when capacity_points is below it: the call
+ *     then returns HJ_ERR_INVALID and writes nothing else.
+ *   HJ_LIGHTMAP_DEVICE_ARRAYS: points and owner are device pointers on the context's GPU, 16-byte aligned, written on the context's
+ *     stream; the call returns after one synchronisation.  Without it they are host arrays.
+ *   The result depends on the scene and the desc alone: not on HJ_LIGHTMAP_LANE_TEXELS or HJ_LIGHTMAP_SLICES, nor on any launch shape.
+ * The owner map (4 bytes a texel) and the scan's counts are kept with the context, grown on demand.
+ * HJ_ERR_INVALID, checked before anything else and without a device (with a null context the text is in hj_last_error(NULL)): a null
+ *   desc or out_count, unknown flag bits, width or height outside [1, 16384] or width * height above 2^26, a non-finite offset,
+ *   misaligned device arrays; then, with the scene at hand, a triangle range beyond the scene's triangles.  A null context:
+ *   HJ_ERR_DEVICE in a process without a HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: an asynchronous frame in flight, frames
+ *   submitted with HJ_RENDER_NO_DRAIN not yet drained, no scene.  No triangle in range: HJ_OK and a count of 0.  A refused call
+ *   writes nothing. */
+#define HJ_LIGHTMAP_DEVICE_ARRAYS 1u
+typedef struct hj_lightmap_desc {
+  uint32_t width, height;      /* the atlas: 1 ... 16384 each, width * height <= 2^26                      */
+  uint32_t first_triangle;     /* index into the scene's triangle array                                    */
+  uint32_t num_triangles;      /* 0 = all from first_triangle to the end                                   */
+  uint32_t seed, seed_stride;  /* texel t gets seed + t * seed_stride (uint32 wrap-around)                 */
+  float    offset;             /* the position is moved by normal * offset; finite                         */
+  uint32_t flags;              /* HJ_LIGHTMAP_DEVICE_ARRAYS                                                */
+} hj_lightmap_desc;
+int hj_lightmap_texels(hj_context* ctx, const hj_lightmap_desc* desc, float* points /* may be NULL */, size_t capacity_points,
+                       uint32_t* owner /* may be NULL */, size_t* out_count);
+
+/* hj_bake_lightmap (ABI 0.16): from the uploaded scene to the atlas image - hj_lightmap_texels, the hemisphere gather of
+ * hj_trace_irradiance over its points, and the records scattered into an image - without the points leaving the device.
+ *   1. The texels of desc, as hj_lightmap_texels emits them, into a buffer the context keeps.
+ *   2. hj_trace_irradiance over them (hemisphere mode, device arrays), spp samples each, with opts.
+ *   3. scale = 3.14159274f / (float)spp.  A texel with a record is (sum.r * scale, sum.g * scale, sum.b * scale, 1.0f) - its
+ *      irradiance, alpha 1 -, every other texel (0, 0, 0, 0).
+ *   4. `gutter` dilation passes (0 ... 64), each from one image into another: a texel with alpha == 0 in the pass's input and at
+ *      least one 8-neighbour with alpha > 0 becomes (sum / (float)k, 0.5f): sum the float32 sum from +0 of those neighbours' rgb
+ *      in the order dy = -1, 0, 1 outer, dx = -1, 0, 1 inner, k their number, one division per channel; neighbours outside the
+ *      atlas do not exist; every other texel is copied.
+ *   image: width * height * 4 floats, row y = 0 first - a host array, or with HJ_LIGHTMAP_DEVICE_ARRAYS a 16-byte-aligned device
+ *     pointer.  *out_count (may be NULL): the texels that had a record.  stats (may be NULL): the gather's (all zero when there is
+ *     no texel to gather at).
+ * spp and opts have hj_trace_irradiance's domain and refusals.  The context keeps, beside hj_lightmap_texels' buffers, 64 bytes per
+ * owned texel (points and records) and up to two images.
+ * HJ_ERR_INVALID, before anything else and without a device: what hj_lightmap_texels refuses of desc, a null image, spp == 0 or
+ *   above 65536, gutter above 64, a misaligned device image, the refusals of opts.  Context, state and the triangle range as in
+ *   hj_lightmap_texels.  A refused call writes nothing. */
+#define HJ_LIGHTMAP_MAX_GUTTER 64u
+int hj_bake_lightmap(hj_context* ctx, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_render_opts* opts /* NULL = defaults */,
+                     float* image, size_t* out_count /* may be NULL */, hj_render_stats* stats /* may be NULL */);
+
 /* ------------------------------------------------------------------- probes */
 
 /* Function-level probes used by the parity tests (no counterpart in the
