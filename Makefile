@@ -13,9 +13,9 @@ HOST_SRC = hijiki_amd/csrc/host/scene.cpp hijiki_amd/csrc/host/tree_opt.cpp hiji
            hijiki_amd/csrc/host/obj_loader.cpp hijiki_amd/csrc/host/image_io.cpp hijiki_amd/csrc/host/host_api.cpp
 HOST_HDR = hijiki_amd/csrc/host/scene.hpp hijiki_amd/csrc/host/blockgen.hpp include/hijiki_hip.h include/hijiki_host.h
 # libhijiki_hip.so: its translation units (hijiki_amd/csrc/api/hj_internal.h lists them); render.hip, scene_relayout.hip,
-# scene_update.hip, lbvh_build.hip, tree_vote.hip, texture.hip, environment.hip, step_probe.hip, ray_query.hip, path_query.hip, path_adaptive.hip, gather_query.hip, lightmap.hip and tree_reinsert.hip hold device code.  The register / scratch / LDS report of the path kernels: hijiki_amd/lib/resource_usage.txt
-# (render.hip's kernels, then behind the line '# gather_query.hip' the gather query's, then behind '# lightmap.hip' the light-map kernels').
-HIP_UNITS = context scene_upload scene_relayout scene_update render render_calls comm lbvh_build tree_vote texture environment step_probe ray_query path_query path_adaptive gather_query lightmap tree_reinsert
+# scene_update.hip, lbvh_build.hip, tree_vote.hip, texture.hip, environment.hip, step_probe.hip, ray_query.hip, path_query.hip, path_adaptive.hip, gather_query.hip, lightmap_filter.hip, lightmap.hip and tree_reinsert.hip hold device code.  The register / scratch / LDS report of the path kernels: hijiki_amd/lib/resource_usage.txt
+# (render.hip's kernels, then behind the line '# gather_query.hip' the gather query's, behind '# lightmap_filter.hip' the light-map filter's, then behind '# lightmap.hip' the light-map kernels').
+HIP_UNITS = context scene_upload scene_relayout scene_update render render_calls comm lbvh_build tree_vote texture environment step_probe ray_query path_query path_adaptive gather_query lightmap_filter lightmap tree_reinsert
 HIP_OBJ = $(HIP_UNITS:%=build/obj/%.o) build/obj/blockgen.o build/obj/light_grid.o
 HIP_HDR = $(wildcard hijiki_amd/csrc/kernels/*.h) hijiki_amd/csrc/api/hj_internal.h hijiki_amd/csrc/api/hj_tuning.h hijiki_amd/csrc/api/light_grid.hpp hijiki_amd/csrc/api/scene_relayout.hpp hijiki_amd/csrc/api/refit_pass.hpp hijiki_amd/csrc/api/guard_box.hpp hijiki_amd/csrc/api/tree_vote.hpp hijiki_amd/csrc/api/tree_reinsert.h hijiki_amd/csrc/api/query_round.h hijiki_amd/csrc/api/query_round_loop.h include/hijiki_hip.h hijiki_amd/csrc/host/blockgen.hpp
 HIP_FLAGS = --offload-arch=$(ARCH) -std=c++17 -O3 -fPIC $(FP_STRICT) -fhip-fp32-correctly-rounded-divide-sqrt -fvisibility=hidden \
@@ -46,7 +46,15 @@ build/obj/gather_query.o: hijiki_amd/csrc/api/gather_query.hip $(HIP_HDR) build/
 	  > build/obj/resource_usage.tmp && mv build/obj/resource_usage.tmp hijiki_amd/lib/resource_usage.txt
 
 # (behind gather_query.o, whose rule cuts the report from its own line on: a rebuild of that unit rebuilds this one)
-build/obj/lightmap.o: hijiki_amd/csrc/api/lightmap.hip $(HIP_HDR) build/obj/gather_query.o
+build/obj/lightmap_filter.o: hijiki_amd/csrc/api/lightmap_filter.hip $(HIP_HDR) build/obj/gather_query.o
+	@mkdir -p build/obj hijiki_amd/lib
+	$(HIPCC) $(HIP_FLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/obj/lightmap_filter.report \
+	  || (cat build/obj/lightmap_filter.report; false)
+	@(sed '/^# lightmap_filter.hip$$/,$$d' hijiki_amd/lib/resource_usage.txt; echo '# lightmap_filter.hip'; cat build/obj/lightmap_filter.report) \
+	  > build/obj/resource_usage.lf.tmp && mv build/obj/resource_usage.lf.tmp hijiki_amd/lib/resource_usage.txt
+
+# (behind lightmap_filter.o in the same way; its section is the report's last)
+build/obj/lightmap.o: hijiki_amd/csrc/api/lightmap.hip $(HIP_HDR) build/obj/lightmap_filter.o
 	@mkdir -p build/obj hijiki_amd/lib
 	$(HIPCC) $(HIP_FLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/obj/lightmap.report \
 	  || (cat build/obj/lightmap.report; false)

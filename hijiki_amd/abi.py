@@ -34,6 +34,7 @@ GATHER_SH9 = 4                    # (only together with GATHER_SPHERE)
 LIGHTMAP_DEVICE_ARRAYS = 1        # hj_lightmap_desc flag
 LIGHTMAP_MAX_GUTTER = 64          # hj_bake_lightmap: dilation passes a call
 LIGHTMAP_NONE = 0xFFFFFFFF        # owner word of a texel nobody owns
+LIGHTMAP_FILTER_MAX_ITERATIONS = 8  # hj_lightmap_filter: iteration i uses the step 1 << i
 # hj_debug_num: enum hj_num_op in its order, the record sizes and the cap
 NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "dot3", "cross3", "normalize3", "reflect3", "rng_seed",
            "rng_uint", "rng_float", "rand_cos_hemisphere", "rand_uniform_sphere", "rand_barycentric")
@@ -175,6 +176,11 @@ class LightmapDesc(C.Structure):
     """hj_lightmap_desc (ABI 0.16): the atlas, the triangle range, the seeds and the offset of hj_lightmap_texels / hj_bake_lightmap."""
     _fields_ = [("width", u32), ("height", u32), ("first_triangle", u32), ("num_triangles", u32), ("seed", u32), ("seed_stride", u32),
                 ("offset", f32), ("flags", u32)]
+
+
+class LightmapFilter(C.Structure):
+    """hj_lightmap_filter (ABI 0.17): the iterations and the edge stops of hj_filter_lightmap / hj_bake_lightmap_filtered."""
+    _fields_ = [("iterations", u32), ("sigma_position", f32), ("sigma_normal", f32), ("sigma_color", f32), ("flags", u32)]
 
 
 class RenderStats(C.Structure):

@@ -144,7 +144,7 @@ int sync_all(hj_context* ctx) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (16u << 8) | 0u; }   // 0.16.0: hj_lightmap_texels, hj_bake_lightmap
+uint32_t hj_version(void) { return (0u << 16) | (17u << 8) | 0u; }   // 0.17.0: hj_filter_lightmap, hj_bake_lightmap_filtered
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

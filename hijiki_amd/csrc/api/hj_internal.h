@@ -33,9 +33,12 @@
 //                         defines its own kernels beside the path kernels: the same round loop with a top-up that draws a direction
 //                         at a point, and the per-point reduction); its host half behind the checks is fixed_spp_query
 //   api/lightmap.hip      hj_lightmap_texels, hj_bake_lightmap: the uploaded triangles' UVs rasterised into gather points, the gather's
-//                         records scattered into an atlas and dilated (the only unit that includes kernels/hj_lightmap.h; beside it
+//                         records scattered into an atlas and dilated (includes kernels/hj_lightmap.h but for its filter section; beside it
 //                         hj_num.h alone: the path kernels' machine code does not depend on it).  The gather itself is
-//                         hj_trace_irradiance's, entered through that entry point with device arrays
+//                         hj_trace_irradiance's, entered through that entry point with device arrays.  hj_bake_lightmap_filtered: the same
+//                         host routine with the filter between scatter and dilation
+//   api/lightmap_filter.hip hj_filter_lightmap: the edge-avoiding a-trous filter over an atlas, and lightmap_filter_check /
+//                         lightmap_filter_enqueue (below) for the bake (includes the filter section of kernels/hj_lightmap.h and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -386,7 +389,9 @@ struct hj_context {
   // whose texel box is left to whole waves, the scan's tile counts and their
   // total, staging of host-side points; the bake's points, gather records and its two ping-pong images.  Grown on demand
   // (dev_alloc keeps a buffer that is large enough), reused by every call, freed with the context.
-  struct Lightmap { hjapi::DevBuf owner, masks, counts, points, records, image[2]; } lightmap;
+  // hj_filter_lightmap (api/lightmap_filter.hip): guide, 32 bytes per texel (position, valid word, normal); it shares points (staging
+  // of host arrays) and the two images
+  struct Lightmap { hjapi::DevBuf owner, masks, counts, points, records, image[2], guide; } lightmap;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
@@ -437,6 +442,13 @@ void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, 
 //                      otherwise), an asynchronous frame in flight, frames in the pipeline, no scene
 int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opts, hj_render_opts& o);
 int query_gate(hj_context* ctx, const char* fn);
+// The light-map filter for both of its entry points (api/lightmap_filter.hip):
+//   lightmap_filter_check    what both refuse of a filter, without a device: unknown flag bits, iterations, sigmas
+//   lightmap_filter_enqueue  guide from the `count` device points, then f.iterations iterations from img[cur] into img[cur ^ 1], cur
+//                            flipped by each: the result is in img[cur] on return.  Enqueues on the context's stream only.
+int lightmap_filter_check(hj_context* ctx, const char* fn, const hj_lightmap_filter* f);
+int lightmap_filter_enqueue(hj_context* ctx, const hj_lightmap_filter& f, uint32_t W, uint32_t H, const float4* d_points, uint32_t count, float4* const img[2],
+                            uint32_t& cur);
 // The statistics read-back of a pass's launches (kStatWords x G words each), summed on the host once the stream has drained.
 // on == false (the caller wants no statistics): every member does nothing.
 struct QueryStats {

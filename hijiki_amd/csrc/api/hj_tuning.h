@@ -68,7 +68,9 @@ struct Tuning {
   /* hj_lightmap_texels / hj_bake_lightmap (read like hj_trace_rays' rows: as the context's creation or its last upload, render     \
      call or build found them - the light-map calls themselves do not refresh the table) */                                          \
   X(lightmap_lane_texels, "HJ_LIGHTMAP_LANE_TEXELS", 64, 0, 1 << 28) /* k_lm_owner: a texel box up to this size is one lane's, a larger one k_lm_owner_wide's */ \
-  X(lightmap_slices, "HJ_LIGHTMAP_SLICES", kUnset, 1, 256) /* grid rows of k_lm_owner_wide that share a box: as many as fill the device, at most 256 */
+  X(lightmap_slices, "HJ_LIGHTMAP_SLICES", kUnset, 1, 256) /* grid rows of k_lm_owner_wide that share a box: as many as fill the device, at most 256 */ \
+  /* hj_filter_lightmap / hj_bake_lightmap_filtered (read like the rows above) */                                                        \
+  X(lightmap_filter_lds_step, "HJ_LIGHTMAP_FILTER_LDS_STEP", 128, 0, 128) /* steps up to this take k_lm_filter_lds, larger ones k_lm_filter_direct: 0 never, 128 always (measured faster at every step) */
   // presence flags (debugging aids): set to anything = on
 #define HJ_TUNING_FLAGS(X)                                                                                                              \
   X(trace_bounces, "HJ_TRACE_BOUNCES")                     /* per-bounce table of the split-kernel path on stderr */                    \

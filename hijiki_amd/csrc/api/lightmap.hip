@@ -1,12 +1,12 @@
-// hj_lightmap_texels, hj_bake_lightmap: the uploaded scene's triangle UVs rasterised into gather points, and the gather's records
+// hj_lightmap_texels, hj_bake_lightmap, hj_bake_lightmap_filtered: the uploaded scene's triangle UVs rasterised into gather points, and the gather's records
 // scattered into an atlas image ("Light-map baking").
 //
-// The kernels are kernels/hj_lightmap.h's (this is the only unit that includes it; beside it hj_num.h alone, so the path kernels'
+// The kernels are kernels/hj_lightmap.h's (its filter section belongs to api/lightmap_filter.hip; beside it hj_num.h alone, so the path kernels'
 // machine code does not depend on this unit).  The gather of the bake is hj_trace_irradiance itself, called with device arrays: it
 // enters fixed_spp_query with the gather's own chunk function, and nothing of its plan or its round loop is restated here.
 //   texels:  owner map = 0xFFFFFFFF  ->  k_lm_owner  ->  k_lm_owner_wide  ->  k_lm_count  ->  k_lm_scan  ->  k_lm_emit
 //   bake:    texels (a synchronisation: the count sizes the buffers)  ->  hj_trace_irradiance  ->  image = 0  ->  k_lm_scatter  ->
-//            gutter x k_lm_dilate between two images
+//            [the filter's iterations: api/lightmap_filter.hip]  ->  gutter x k_lm_dilate between two images
 #include "hj_internal.h"
 #include "../kernels/hj_lightmap.h"
 
@@ -92,6 +92,82 @@ int drain(hj_context* ctx, const char* fn, int rc) {
   return HJ_OK;
 }
 
+// Both bakes (fn: the entry point's name).  filter == NULL or no iterations: hj_bake_lightmap, launch for launch.
+int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_lightmap_filter* filter,
+         const hj_render_opts* opts, float* image, size_t* out_count, hj_render_stats* stats) {
+  if (!desc || !image) return set_error(ctx, HJ_ERR_INVALID, "%s: null %s", fn, !desc ? "desc" : "image");
+  HJ_TRY(check_desc(ctx, fn, desc));
+  const bool on_device = (desc->flags & HJ_LIGHTMAP_DEVICE_ARRAYS) != 0;
+  if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "%s: spp %u outside [1, 65536]", fn, spp);
+  if (gutter > HJ_LIGHTMAP_MAX_GUTTER) return set_error(ctx, HJ_ERR_INVALID, "%s: gutter %u above %u passes", fn, gutter, HJ_LIGHTMAP_MAX_GUTTER);
+  if (on_device && (reinterpret_cast<uintptr_t>(image) & 15u) != 0)
+    return set_error(ctx, HJ_ERR_INVALID, "%s: a device image must be 16-byte aligned", fn);
+  if (filter) HJ_TRY(lightmap_filter_check(ctx, fn, filter));
+  const uint32_t iterations = filter ? filter->iterations : 0u;
+  hj_render_opts o;
+  HJ_TRY(query_render_opts(ctx, fn, opts, o));
+  HJ_TRY(query_gate(ctx, fn));
+  hj::LmArgs a{};
+  HJ_TRY(check_range(ctx, fn, desc, a));
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  const uint32_t n = a.W * a.H;
+  hj_context::Lightmap& lm = ctx->lightmap;
+
+  // 1. the texels: the count comes to the host, because it sizes the points, the records and the gather
+  uint32_t *d_owner = nullptr, *d_counts = nullptr, nb = 0, total = 0;
+  int rc = enqueue_owner_and_scan(ctx, a, d_owner, d_counts, nb);
+  if (rc == HJ_OK && hipMemcpyAsync(&total, d_counts + nb, sizeof total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    rc = set_error(ctx, HJ_ERR_DEVICE, "%s: the count's copy failed", fn);
+  HJ_TRY(drain(ctx, fn, rc));
+  // the images: with f filter iterations and g gutter passes the scatter starts where f + g swaps end in the caller's device image (or in image[0])
+  float4* img[2] = {nullptr, nullptr};
+  if (on_device) img[0] = reinterpret_cast<float4*>(image);
+  else {
+    HJ_TRY(dev_alloc(ctx, lm.image[0], sizeof(float4) * (size_t)n));
+    img[0] = static_cast<float4*>(lm.image[0].p);
+  }
+  if (gutter + iterations != 0) {
+    HJ_TRY(dev_alloc(ctx, lm.image[1], sizeof(float4) * (size_t)n));
+    img[1] = static_cast<float4*>(lm.image[1].p);
+  }
+  uint32_t cur = (gutter + iterations) & 1u;     // (after that many swaps: 0)
+  float4 *d_points = nullptr, *d_records = nullptr;
+  if (total != 0) {
+    HJ_TRY(dev_alloc(ctx, lm.points, sizeof(float4) * 2 * (size_t)total));
+    HJ_TRY(dev_alloc(ctx, lm.records, sizeof(float4) * 2 * (size_t)total));
+    d_points = static_cast<float4*>(lm.points.p);
+    d_records = static_cast<float4*>(lm.records.p);
+    enqueue_emit(ctx, a, d_owner, d_counts, nb, total, d_points, nullptr);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, fn, set_error(ctx, HJ_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e)));
+    // 2. the gather: the same stream, so it runs behind the emit; it returns with its records complete
+    HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), total, spp, &o, HJ_GATHER_DEVICE_ARRAYS, reinterpret_cast<float*>(d_records), stats));
+  } else if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+  }
+  // 3. scatter, the filter's iterations, 4. dilate
+  hipStream_t s = ctx->stream;
+  hipError_t e = hipMemsetAsync(img[cur], 0, sizeof(float4) * (size_t)n, s);
+  if (e == hipSuccess && total != 0) {
+    const float scale = 3.14159274f / (float)spp;
+    hipLaunchKernelGGL(hj::k_lm_scatter, dim3((total + hj::kLmThreads - 1u) / hj::kLmThreads), dim3(hj::kLmThreads), 0, s, d_points, d_records, total, scale,
+                       img[cur]);
+  }
+  if (e == hipSuccess && iterations != 0) {
+    if (const int frc = lightmap_filter_enqueue(ctx, *filter, a.W, a.H, d_points, total, img, cur); frc != HJ_OK) return drain(ctx, fn, frc);
+  }
+  for (uint32_t g = 0; g < gutter && e == hipSuccess; g++) {
+    hipLaunchKernelGGL(hj::k_lm_dilate, dim3(nb), dim3(hj::kLmThreads), 0, s, static_cast<const float4*>(img[cur]), img[cur ^ 1u], a.W, a.H);
+    cur ^= 1u;
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  // 5. to the host
+  if (e == hipSuccess && !on_device) e = hipMemcpyAsync(image, img[cur], sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, s);
+  if (e != hipSuccess) rc = set_error(ctx, HJ_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+  HJ_TRY(drain(ctx, fn, rc));
+  if (out_count) *out_count = total;
+  return HJ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -144,72 +220,12 @@ int hj_lightmap_texels(hj_context* ctx, const hj_lightmap_desc* desc, float* poi
 
 int hj_bake_lightmap(hj_context* ctx, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_render_opts* opts, float* image,
                      size_t* out_count, hj_render_stats* stats) {
-  if (!desc || !image) return set_error(ctx, HJ_ERR_INVALID, "hj_bake_lightmap: null %s", !desc ? "desc" : "image");
-  HJ_TRY(check_desc(ctx, __func__, desc));
-  const bool on_device = (desc->flags & HJ_LIGHTMAP_DEVICE_ARRAYS) != 0;
-  if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "hj_bake_lightmap: spp %u outside [1, 65536]", spp);
-  if (gutter > HJ_LIGHTMAP_MAX_GUTTER) return set_error(ctx, HJ_ERR_INVALID, "hj_bake_lightmap: gutter %u above %u passes", gutter, HJ_LIGHTMAP_MAX_GUTTER);
-  if (on_device && (reinterpret_cast<uintptr_t>(image) & 15u) != 0)
-    return set_error(ctx, HJ_ERR_INVALID, "hj_bake_lightmap: a device image must be 16-byte aligned");
-  hj_render_opts o;
-  HJ_TRY(query_render_opts(ctx, __func__, opts, o));
-  HJ_TRY(query_gate(ctx, __func__));
-  hj::LmArgs a{};
-  HJ_TRY(check_range(ctx, __func__, desc, a));
-  HJ_HIP(ctx, hipSetDevice(ctx->device));
-  const uint32_t n = a.W * a.H;
-  hj_context::Lightmap& lm = ctx->lightmap;
+  return bake(ctx, __func__, desc, spp, gutter, nullptr, opts, image, out_count, stats);
+}
 
-  // 1. the texels: the count comes to the host, because it sizes the points, the records and the gather
-  uint32_t *d_owner = nullptr, *d_counts = nullptr, nb = 0, total = 0;
-  int rc = enqueue_owner_and_scan(ctx, a, d_owner, d_counts, nb);
-  if (rc == HJ_OK && hipMemcpyAsync(&total, d_counts + nb, sizeof total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-    rc = set_error(ctx, HJ_ERR_DEVICE, "hj_bake_lightmap: the count's copy failed");
-  HJ_TRY(drain(ctx, __func__, rc));
-  // the images: with gutter passes g the scatter starts where g passes end in the caller's device image (or in image[0])
-  float4* img[2] = {nullptr, nullptr};
-  if (on_device) img[0] = reinterpret_cast<float4*>(image);
-  else {
-    HJ_TRY(dev_alloc(ctx, lm.image[0], sizeof(float4) * (size_t)n));
-    img[0] = static_cast<float4*>(lm.image[0].p);
-  }
-  if (gutter != 0) {
-    HJ_TRY(dev_alloc(ctx, lm.image[1], sizeof(float4) * (size_t)n));
-    img[1] = static_cast<float4*>(lm.image[1].p);
-  }
-  uint32_t cur = gutter & 1u;                    // (after `gutter` swaps: 0)
-  float4 *d_points = nullptr, *d_records = nullptr;
-  if (total != 0) {
-    HJ_TRY(dev_alloc(ctx, lm.points, sizeof(float4) * 2 * (size_t)total));
-    HJ_TRY(dev_alloc(ctx, lm.records, sizeof(float4) * 2 * (size_t)total));
-    d_points = static_cast<float4*>(lm.points.p);
-    d_records = static_cast<float4*>(lm.records.p);
-    enqueue_emit(ctx, a, d_owner, d_counts, nb, total, d_points, nullptr);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, __func__, set_error(ctx, HJ_ERR_DEVICE, "hj_bake_lightmap: %s", hipGetErrorString(e)));
-    // 2. the gather: the same stream, so it runs behind the emit; it returns with its records complete
-    HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), total, spp, &o, HJ_GATHER_DEVICE_ARRAYS, reinterpret_cast<float*>(d_records), stats));
-  } else if (stats) {
-    std::memset(stats, 0, sizeof *stats);
-  }
-  // 3. scatter, 4. dilate
-  hipStream_t s = ctx->stream;
-  hipError_t e = hipMemsetAsync(img[cur], 0, sizeof(float4) * (size_t)n, s);
-  if (e == hipSuccess && total != 0) {
-    const float scale = 3.14159274f / (float)spp;
-    hipLaunchKernelGGL(hj::k_lm_scatter, dim3((total + hj::kLmThreads - 1u) / hj::kLmThreads), dim3(hj::kLmThreads), 0, s, d_points, d_records, total, scale,
-                       img[cur]);
-  }
-  for (uint32_t g = 0; g < gutter && e == hipSuccess; g++) {
-    hipLaunchKernelGGL(hj::k_lm_dilate, dim3(nb), dim3(hj::kLmThreads), 0, s, static_cast<const float4*>(img[cur]), img[cur ^ 1u], a.W, a.H);
-    cur ^= 1u;
-  }
-  if (e == hipSuccess) e = hipGetLastError();
-  // 5. to the host
-  if (e == hipSuccess && !on_device) e = hipMemcpyAsync(image, img[cur], sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) rc = set_error(ctx, HJ_ERR_DEVICE, "hj_bake_lightmap: %s", hipGetErrorString(e));
-  HJ_TRY(drain(ctx, __func__, rc));
-  if (out_count) *out_count = total;
-  return HJ_OK;
+int hj_bake_lightmap_filtered(hj_context* ctx, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_lightmap_filter* filter,
+                              const hj_render_opts* opts, float* image, size_t* out_count, hj_render_stats* stats) {
+  return bake(ctx, __func__, desc, spp, gutter, filter, opts, image, out_count, stats);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 //
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
 //              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] [--env FILE [--env-scale S]]
-//              [--bake-lightmap WxH [--gutter 2]]
+//              [--bake-lightmap WxH [--gutter 2] [--filter N[,sp[,sn[,sc]]]]]
 //              <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
@@ -10,7 +10,11 @@
 // upstream) renders the MTL's map_Kd images on diffuse materials; --env (not upstream) lights the scene with a lat-long HDR image;
 // --bake-lightmap WxH (not upstream) writes no camera frame but the scene's light-map atlas: hj_bake_lightmap over all triangles at
 // -s samples a texel, seed --seed, stride 1, offset 1e-3, --gutter dilation passes; the atlas's rgb goes to -o, row v = 0 on top.
+// --filter N[,sp[,sn[,sc]]] (not upstream) runs N iterations of hj_filter_lightmap's edge-avoiding a-trous filter between the bake's
+// scatter and its dilation (hj_bake_lightmap_filtered): sp, sn, sc are sigma_position (default: 1 % of the root box's diagonal),
+// sigma_normal (0.5) and sigma_color (0: off) - a starting point, not a tuned optimum.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +36,9 @@ struct Opt {
   float env_scale = 1.0f;
   uint32_t bake_w = 0, bake_h = 0, gutter = 2;             // --bake-lightmap WxH (0: render a frame), --gutter
   bool gutter_given = false;
+  uint32_t filter_n = 0;                                   // --filter N[,sp[,sn[,sc]]]: iterations (0: none)
+  float filter_sp = -1.0f, filter_sn = 0.5f, filter_sc = 0.0f;   // (sp < 0: 1 % of the root box's diagonal)
+  bool filter_given = false;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -46,6 +53,9 @@ struct Opt {
                "        --env-scale <scale>                      [default: 1] (not upstream) radiance scale of --env\n"
                "        --bake-lightmap <W>x<H>                  (not upstream) bake the light-map atlas of the scene's UVs instead of a frame\n"
                "        --gutter <passes>                        [default: 2] (not upstream) dilation passes of --bake-lightmap, 0 ... 64\n"
+               "        --filter <N>[,<sp>[,<sn>[,<sc>]]]        (not upstream) N = 0 ... 8 iterations of the edge-avoiding a-trous filter over the baked\n"
+               "                                                 atlas; sigmas of position [default: 1 %% of the scene box's diagonal], normal [0.5]\n"
+               "                                                 and colour [0 = off]: a starting point, not a tuned optimum\n"
                "OPTIONS:\n    -h, --height <height>                        [default: 600]\n"
                "    -o, --output-image <output-image>            [default: /tmp/output.exr] (.exr, .pfm or .png)\n"
                "        --present-interval <present-interval>    [default: 128] (ignored: no preview window)\n"
@@ -95,6 +105,18 @@ Opt parse(int argc, char** argv) {
       o.gutter = (uint32_t)g;
       o.gutter_given = true;
     }
+    else if (a == "--filter") {
+      const std::string v = value(i);
+      unsigned n = 0;
+      float sg[3] = {-1.0f, 0.5f, 0.0f};
+      char tail = 0;
+      const int got = std::sscanf(v.c_str(), "%u,%f,%f,%f%c", &n, &sg[0], &sg[1], &sg[2], &tail);
+      bool ok = got >= 1 && got <= 4 && n <= HJ_LIGHTMAP_FILTER_MAX_ITERATIONS && v.find_first_not_of("0123456789.,eE+-") == std::string::npos && v.back() != ',';
+      for (int k = 0; ok && k < got - 1; k++) ok = sg[k] >= 0.0f && sg[k] <= 3.0e38f;
+      if (!ok) usage(("bad --filter " + v + " (N[,sp[,sn[,sc]]]: N = 0 ... 8, sigmas finite and >= 0)").c_str());
+      o.filter_n = n; o.filter_sp = sg[0]; o.filter_sn = sg[1]; o.filter_sc = sg[2];
+      o.filter_given = true;
+    }
     else if (a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown flag " + a).c_str());
     else if (o.scene.empty()) o.scene = a;
@@ -103,6 +125,8 @@ Opt parse(int argc, char** argv) {
   if (o.scene.empty()) usage("the <scene> argument is required");
   if (o.env.empty() && o.env_scale != 1.0f) usage("--env-scale without --env");
   if (o.gutter_given && o.bake_w == 0) usage("--gutter without --bake-lightmap");
+  if (o.filter_given && o.bake_w == 0) usage("--filter without --bake-lightmap");
+  if (o.filter_given && o.filter_sp < 0.0f && o.device_bvh) usage("--filter with --device-bvh needs its sigma_position (no root box on the host)");
   return o;
 }
 
@@ -165,7 +189,20 @@ int main(int argc, char** argv) {
       size_t texels = 0;
       hj_render_stats bst;
       std::printf("Baking %u x %u texels...\n", opt.bake_w, opt.bake_h);
-      check(ctx, hj_bake_lightmap(ctx, &lm, opt.sample_count, opt.gutter, nullptr, rgba.data(), &texels, &bst), "bake");
+      if (opt.filter_given) {
+        float sp = opt.filter_sp;
+        if (sp < 0.0f) {                                                 // 1 % of the root box's diagonal
+          const hj_bvh_node& root = cs.bvh.at(0);
+          const float dx = root.aabb_max[0] - root.aabb_min[0], dy = root.aabb_max[1] - root.aabb_min[1], dz = root.aabb_max[2] - root.aabb_min[2];
+          sp = 0.01f * std::sqrt((dx * dx + dy * dy) + dz * dz);
+        }
+        const hj_lightmap_filter flt{opt.filter_n, sp, opt.filter_sn, opt.filter_sc, 0u};
+        std::printf("Filter: %u iterations, sigmas %g (position), %g (normal), %g (colour)\n", flt.iterations, (double)sp, (double)flt.sigma_normal,
+                    (double)flt.sigma_color);
+        check(ctx, hj_bake_lightmap_filtered(ctx, &lm, opt.sample_count, opt.gutter, &flt, nullptr, rgba.data(), &texels, &bst), "bake");
+      } else {
+        check(ctx, hj_bake_lightmap(ctx, &lm, opt.sample_count, opt.gutter, nullptr, rgba.data(), &texels, &bst), "bake");
+      }
       std::printf("Gathered %llu paths at %zu texels in %.6fs\n", (unsigned long long)bst.paths, texels, bst.total_ms * 1e-3);
       for (size_t t = 0; t < (size_t)opt.bake_w * opt.bake_h; t++)
         for (int c = 0; c < 3; c++) rgb[3 * t + c] = rgba[4 * t + c];

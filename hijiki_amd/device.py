@@ -26,7 +26,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_scene_upload_textured", "hj_debug_texture_lookup", "hj_scene_upload_env", "hj_debug_env_lookup", "hj_debug_env_sample",
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
            "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
-           "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap")
+           "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap", "hj_filter_lightmap",
+           "hj_bake_lightmap_filtered")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -91,6 +92,9 @@ def lib():
         L.hj_lightmap_texels.argtypes = [vp, C.POINTER(abi.LightmapDesc), vp, C.c_size_t, vp, C.POINTER(C.c_size_t)]   # (host or device pointers)
         L.hj_bake_lightmap.argtypes = [vp, C.POINTER(abi.LightmapDesc), C.c_uint32, C.c_uint32, C.POINTER(abi.RenderOpts), vp,
                                        C.POINTER(C.c_size_t), C.POINTER(abi.RenderStats)]
+        L.hj_filter_lightmap.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(abi.LightmapFilter), vp]   # (host or device pointers)
+        L.hj_bake_lightmap_filtered.argtypes = [vp, C.POINTER(abi.LightmapDesc), C.c_uint32, C.c_uint32, C.POINTER(abi.LightmapFilter),
+                                                C.POINTER(abi.RenderOpts), vp, C.POINTER(C.c_size_t), C.POINTER(abi.RenderStats)]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -174,6 +178,14 @@ def default_opts():
     o = abi.RenderOpts()
     lib().hj_default_render_opts(C.byref(o))
     return o
+
+
+def default_filter_sigmas(compiled):
+    """(sigma_position, sigma_normal, sigma_color) the command line's `--filter N` uses for a compiled scene with a host tree: 1 % of
+    the root box's diagonal, 0.5, 0 (float32 arithmetic, as the CLI computes it).  A starting point, not a tuned optimum."""
+    root = compiled.bvh_f32[0]
+    d = root[4:7] - root[0:3]
+    return float(np.float32(0.01) * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])), 0.5, 0.0
 
 
 def stats_dict(st):
@@ -650,13 +662,56 @@ class Renderer:
                                                  C.byref(count)))
         return (pts, own) if owner else pts
 
+    @staticmethod
+    def _lightmap_filter(what, iterations, sigma_position, sigma_normal, sigma_color, device):
+        """The filter of the light-map calls, checked before any call."""
+        iterations = int(iterations)
+        if not 0 <= iterations <= abi.LIGHTMAP_FILTER_MAX_ITERATIONS:
+            raise ValueError(f"{what}: {iterations} filter iterations outside [0, {abi.LIGHTMAP_FILTER_MAX_ITERATIONS}]")
+        for name, v in (("sigma_position", sigma_position), ("sigma_normal", sigma_normal), ("sigma_color", sigma_color)):
+            v = np.float32(v)
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"{what}: {name} {v}: finite and >= 0 is needed")
+        return abi.LightmapFilter(iterations, float(sigma_position), float(sigma_normal), float(sigma_color), abi.LIGHTMAP_DEVICE_ARRAYS if device else 0)
+
+    def filter_lightmap(self, image, points, iterations, sigma_position, sigma_normal, sigma_color=0.0, device=False):
+        """hj_filter_lightmap: `iterations` (0 ... 8) iterations of an edge-avoiding a-trous filter over the (height, width, 4) float32
+        atlas `image`, guided by the (count, 8) `points` of `lightmap_texels` over the same atlas (position, normal, the texel index
+        in word 7, strictly ascending): a 5 x 5 B3-spline kernel at the steps 1, 2, 4, ..., each tap weighted down by its distance in
+        world position (`sigma_position`, world units), normal (`sigma_normal`) and colour (`sigma_color`, halved every
+        iteration); a sigma of 0 switches its stop off.  Texels no point names are left as they are; alpha is kept.  -> a new
+        (height, width, 4) array.  device=True: `image` and `points` are contiguous float32 torch tensors on the renderer's GPU, the
+        points' indices the caller's contract (a point that names no texel is skipped); `image` is filtered IN PLACE and returned;
+        torch's current stream is synchronised first."""
+        f = self._lightmap_filter("filter_lightmap", iterations, sigma_position, sigma_normal, sigma_color, device)
+        if device:
+            import torch
+            for name, t in (("image", image), ("points", points)):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"filter_lightmap: {name} must be a contiguous float32 tensor on cuda:{self.device}")
+            if image.dim() != 3 or image.shape[2] != 4 or points.dim() != 2 or points.shape[1] != 8:
+                raise ValueError("filter_lightmap: image (height, width, 4) and points (count, 8) are needed")
+            h, w, n = int(image.shape[0]), int(image.shape[1]), int(points.shape[0])
+            torch.cuda.current_stream(image.device).synchronize()     # (whatever wrote the tensors)
+            self._check(lib().hj_filter_lightmap(self._h, w, h, points.data_ptr() if n else None, n, C.byref(f), image.data_ptr()))
+            return image
+        img = np.array(image, np.float32, order="C")                     # (a copy: the caller's array is left alone)
+        pts = np.ascontiguousarray(points, np.float32)
+        if img.ndim != 3 or img.shape[2] != 4 or pts.ndim != 2 or pts.shape[1] != 8:
+            raise ValueError("filter_lightmap: image (height, width, 4) and points (count, 8) are needed")
+        self._check(lib().hj_filter_lightmap(self._h, img.shape[1], img.shape[0], pts.ctypes.data if len(pts) else None, len(pts), C.byref(f),
+                                             img.ctypes.data))
+        return img
+
     def bake_lightmap(self, width, height, spp, gutter=2, first_triangle=0, num_triangles=0, seed=0, seed_stride=1, offset=0.0, opts=None,
-                      stats=False, device=False):
+                      stats=False, device=False, filter=None):
         """hj_bake_lightmap: `lightmap_texels`, the hemisphere gather of `trace_irradiance` at `spp` samples over its points, and the
         records scattered into the atlas, all on the device -> (height, width, 4) float32: a texel with a record holds its irradiance
         (pi / spp x the gathered sum) and alpha 1; `gutter` dilation passes give texels next to covered ones the mean of their covered
         neighbours and alpha 0.5; everything else is zero.  opts as in `trace_irradiance`.  device=True: a torch tensor on the
-        renderer's GPU.  stats=True: returns (image, the gather's statistics dict with `texels` = the texels that had a record)."""
+        renderer's GPU.  stats=True: returns (image, the gather's statistics dict with `texels` = the texels that had a record).
+        filter: None, or (iterations, sigma_position, sigma_normal[, sigma_color]) - `filter_lightmap` over the scattered image with the
+        bake's own points as guides, before the dilation (hj_bake_lightmap_filtered); `default_filter_sigmas` gives a starting point."""
         spp, gutter = int(spp), int(gutter)
         if not 1 <= spp <= 65536:
             raise ValueError(f"bake_lightmap: spp {spp} outside [1, 65536]")
@@ -665,15 +720,22 @@ class Renderer:
         d = self._lightmap_desc("bake_lightmap", width, height, first_triangle, num_triangles, seed, seed_stride, offset, device)
         st, count = abi.RenderStats(), C.c_size_t(0)
         o = C.byref(opts) if opts is not None else None
+        if filter is None:
+            call = lambda p: lib().hj_bake_lightmap(self._h, C.byref(d), spp, gutter, o, p, C.byref(count), C.byref(st))  # noqa: E731
+        else:
+            if not 2 <= len(filter) - 1 <= 3:
+                raise ValueError("bake_lightmap: filter is (iterations, sigma_position, sigma_normal[, sigma_color])")
+            f = self._lightmap_filter("bake_lightmap", filter[0], filter[1], filter[2], filter[3] if len(filter) > 3 else 0.0, False)
+            call = lambda p: lib().hj_bake_lightmap_filtered(self._h, C.byref(d), spp, gutter, C.byref(f), o, p, C.byref(count), C.byref(st))  # noqa: E731
         if device:
             import torch
             dev = torch.device("cuda", self.device)
             img = torch.empty((d.height, d.width, 4), dtype=torch.float32, device=dev)
             torch.cuda.current_stream(dev).synchronize()              # (the allocation)
-            self._check(lib().hj_bake_lightmap(self._h, C.byref(d), spp, gutter, o, img.data_ptr(), C.byref(count), C.byref(st)))
+            self._check(call(img.data_ptr()))
         else:
             img = np.zeros((d.height, d.width, 4), np.float32)
-            self._check(lib().hj_bake_lightmap(self._h, C.byref(d), spp, gutter, o, img.ctypes.data, C.byref(count), C.byref(st)))
+            self._check(call(img.ctypes.data))
         return (img, dict(stats_dict(st), texels=count.value)) if stats else img
 
     def texture_lookup(self, texture, uv):

@@ -726,6 +726,61 @@ int hj_lightmap_texels(hj_context* ctx, const hj_lightmap_desc* desc, float* poi
 int hj_bake_lightmap(hj_context* ctx, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_render_opts* opts /* NULL = defaults */,
                      float* image, size_t* out_count /* may be NULL */, hj_render_stats* stats /* may be NULL */);
 
+/* hj_filter_lightmap (ABI 0.17): an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a light-map atlas on the device -
+ * the stage between hj_bake_lightmap's raw Monte-Carlo estimate and a usable light map.  A 5 x 5 B3-spline kernel whose taps move
+ * apart by powers of two, with edge stops on world position, normal and, optionally, colour, which keep charts that sit side by
+ * side in the atlas, and walls that meet in a corner, from bleeding into each other.  No counterpart in the reference.
+ *   points: `count` records of 8 words, exactly as hj_lightmap_texels emits them - position in words 0-2, normal in words 3-5, word 7
+ *     the texel index t = y * width + x, strictly ascending (word 6 is ignored).  A texel is GUIDED when a point names it; the
+ *     image's alpha plays no part in that.
+ *   image: width * height * 4 floats, row y = 0 first, read and written.
+ *   Every operation is float32 with one rounding and no contraction: no fused multiply-add outside hj_exp.
+ *       sq(v) = (v.x * v.x + v.y * v.y) + v.z * v.z                                     (deliberately not the contract's dot3)
+ *   Computed on the host, once: ip = sigma_position > 0 ? 1.0f / (sigma_position * sigma_position) : 0.0f; in_ the same of
+ *   sigma_normal; ic_0 the same of sigma_color; ic_i = ic_{i-1} * 4.0f (the colour stop halves every iteration).
+ *   Iteration i = 0 ... iterations - 1 reads image I, writes image O and uses the step s = 1 << i.  A texel that is not guided is
+ *   copied, all four words.  For a guided texel at (x, y) with rgb c in I, position P and normal n: sum = (+0, +0, +0), wsum = +0,
+ *   then for dy = -2 ... 2 (outer), dx = -2 ... 2 (inner):
+ *     1. the tap is q = (x + dx * s, y + dy * s); it is skipped when it lies outside the atlas or is not guided;
+ *     2. h = k[|dx|] * k[|dy|] with k = {0.375f, 0.25f, 0.0625f} (the products are exact);
+ *     3. a = (sq(P_q - P) * ip + sq(n_q - n) * in_) + sq(c_q - c) * ic_i;
+ *     4. w = h * hj_exp(-a) - the numeric contract's exp (kernels/hj_num.h; HJ_NUM_EXP of hj_debug_num);
+ *     5. sum.r = sum.r + c_q.r * w, likewise g and b;   6. wsum = wsum + w.
+ *   O.rgb = sum / wsum, one IEEE division per channel; O.a = I.a.  For finite data the centre tap alone gives wsum >= 0.140625.
+ *   Agreement bit for bit with that text is claimed for finite images and guides; non-finite values just propagate.
+ *   After the last iteration the result is in `image`.  iterations == 0: HJ_OK, nothing touched.  The result depends on (width,
+ *   height, points, filter, image) alone: not on HJ_LIGHTMAP_FILTER_LDS_STEP, nor on any launch shape.
+ *   HJ_LIGHTMAP_DEVICE_ARRAYS (filter->flags): points and image are device pointers on the context's GPU, 16-byte aligned, read and
+ *     written on the context's stream; the call returns after one synchronisation.  The texel indices are then the caller's
+ *     contract; a word 7 that is not below width * height names no texel and its point is skipped - it cannot fault.  Without the
+ *     flag they are host arrays, checked before anything is written and staged through buffers the context keeps.
+ * The context keeps 32 bytes per texel of guide data and one more image, grown on demand, freed with the context.
+ * HJ_ERR_INVALID, before anything else and without a device, in this order: a null filter or image, null points with count > 0;
+ *   unknown flag bits; iterations above 8; a negative or non-finite sigma; width or height outside hj_lightmap_texels' limits;
+ *   count above width * height; misaligned device arrays; with host arrays a texel index that is not strictly ascending or not
+ *   below width * height, or a non-finite position or normal.  The null context and HJ_ERR_STATE as in hj_lightmap_texels.  A
+ *   refused call writes nothing. */
+#define HJ_LIGHTMAP_FILTER_MAX_ITERATIONS 8u
+typedef struct hj_lightmap_filter {
+  uint32_t iterations;      /* 0 ... 8; iteration i uses the step s = 1 << i                                          */
+  float    sigma_position;  /* world units; 0 = this stop is off                                                      */
+  float    sigma_normal;    /* on |n_q - n|; 0 = off                                                                  */
+  float    sigma_color;     /* on |c_q - c| of the iteration's input; halves every iteration; 0 = off                 */
+  uint32_t flags;           /* HJ_LIGHTMAP_DEVICE_ARRAYS                                                              */
+} hj_lightmap_filter;
+int hj_filter_lightmap(hj_context* ctx, uint32_t width, uint32_t height, const float* points, size_t count, const hj_lightmap_filter* filter,
+                       float* image /* width * height * 4, read and written */);
+
+/* hj_bake_lightmap_filtered (ABI 0.17): steps 1-3 of hj_bake_lightmap, then hj_filter_lightmap's iterations over the scattered image
+ * with the bake's own points as guides - they never leave the device -, then step 4, the gutter dilation.  With filter == NULL or
+ * iterations == 0 it IS hj_bake_lightmap, bit for bit, statistics included (one host routine serves both).  The filter's
+ * HJ_LIGHTMAP_DEVICE_ARRAYS bit is ignored: desc->flags says where the image lives.
+ * HJ_ERR_INVALID: hj_bake_lightmap's refusals in its order, with the filter's (unknown flag bits, iterations above 8, a negative or
+ *   non-finite sigma) between the misaligned device image and the refusals of opts. */
+int hj_bake_lightmap_filtered(hj_context* ctx, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_lightmap_filter* filter /* NULL = none */,
+                              const hj_render_opts* opts /* NULL = defaults */, float* image, size_t* out_count /* may be NULL */,
+                              hj_render_stats* stats /* may be NULL */);
+
 /* ------------------------------------------------------------------- probes */
 
 /* Function-level probes used by the parity tests (no counterpart in the

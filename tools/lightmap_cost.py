@@ -12,6 +12,14 @@ tree of that scene is built on the device.
     check    on the mesh: the texel stage at --bake-size against trace_irradiance at spp = 16 over its own output (DESIGN.md 4,
              "Light-map baking": a texel stage that takes longer than that gather has the wrong work split)
 
+    filter   (--filter: this section alone, on the cbox scene and the mesh) Renderer.filter_lightmap(device=True) at 1024 x 1024 and
+             4096 x 4096 over the texel stage's points, 1 ... 5 iterations, in three contexts: every step in the LDS form
+             (HJ_LIGHTMAP_FILTER_LDS_STEP=128), every step in the direct form (0), the default; beside trace_irradiance at spp = 16
+             over the same points.  A call of N iterations is the guide (32 B a texel zeroed, then the scatter), the steps
+             1 ... 2^(N-1) and, for odd N, one copy of the image; a step's time is the difference of two calls' best times.  Beside it
+             the bytes an iteration must move - 48 B read and 16 B written per guided texel - and the multiple of their time at
+             6.3 TB/s that the step takes.
+
 --pairs interleaved runs after a warm-up of each; a run's time is a host clock between two device synchronisations; ms, lowest ...
 highest.  No threshold is set: the table belongs in DESIGN.md ("Light-map baking"), the raw output in profiles/ (--out).  Run under
 its own time limit:
@@ -37,6 +45,7 @@ ap.add_argument("--bake-size", type=int, default=1024)
 ap.add_argument("--spp", type=int, default=16)
 ap.add_argument("--gutter", type=int, default=2)
 ap.add_argument("--pairs", type=int, default=5)
+ap.add_argument("--filter", action="store_true", help="the filter section alone")
 ap.add_argument("--out", default="", help="append the run to this file")
 a = ap.parse_args()
 
@@ -108,6 +117,34 @@ def upload(cs):
         r.upload_scene(cs)
 
 
+def filter_section(name, cs, forms):
+    """forms: {"lds": renderer, "direct": renderer, "default": renderer} (contexts created under their switch; the filter reads no scene)"""
+    pos = cs.vertices[:, 0:3]
+    d = pos.max(0) - pos.min(0)
+    sig = (float(np.float32(0.01) * np.sqrt((d * d).sum(dtype=np.float32))), 0.5, 0.0)
+    say(f"{name}: filter, sigmas {sig[0]:.4g} / {sig[1]} / {sig[2]} (1 % of the mesh's diagonal, the command line's defaults)")
+    for S in (1024, 4096):
+        pts = r.lightmap_texels(S, S, offset=1e-3, device=True)
+        img = torch.rand((S, S, 4), device=dev)
+        runs = {"gather 16 spp": lambda: r.trace_irradiance(pts, spp=16)}
+        for form, rr in forms.items():
+            for n in range(1, 6):
+                runs[f"{form} {n}"] = (lambda rr=rr, n=n: rr.filter_lightmap(img, pts, n, *sig, device=True))
+        all_secs = interleaved(runs)
+        secs = {k: min(v) for k, v in all_secs.items()}
+        need = 64.0 * len(pts)
+        floor = need / 6.3e12
+        say(f"  {S} x {S}, {len(pts)} guided texels of {S * S}: {a.pairs} interleaved runs, lowest ... highest; an iteration must move "
+            f"{need / 1e6:.1f} MB = {floor * 1e3:.4f} ms at 6.3 TB/s")
+        for k, v in all_secs.items():
+            say(f"    {k}: {spread(v)}")
+        for form in forms:
+            steps = ", ".join(f"s = {1 << (n - 1)}: {(secs[f'{form} {n}'] - secs[f'{form} {n - 1}']) * 1e3:.3f} ms "
+                              f"({(secs[f'{form} {n}'] - secs[f'{form} {n - 1}']) / floor:.1f} x)" for n in range(2, 6))
+            say(f"    {form}, a step as the difference of two calls' best (odd N carry one image copy more): {steps}")
+        say(f"    5 iterations (default) / gather at 16 spp, best of each: {secs['default 5'] / secs['gather 16 spp']:.3f}")
+
+
 import lightmap_scenes  # noqa: E402
 
 scenes = {"cbox": lightmap_scenes.bake_scene()}
@@ -119,8 +156,22 @@ if len(r.lightmap_texels(1024, 1024, device=True)) < len(synth.triangles) // 100
     mesh, side = with_grid_atlas(synth)
     note = f"a grid atlas of {side} x {side} cells"
 scenes[f"mesh ({len(mesh.triangles)} triangles, {note})"] = mesh
-mixed, _ = with_grid_atlas(synth, chart=True)
-scenes[f"mesh + one chart ({len(mixed.triangles)} triangles: the grid atlas, then a pair over the whole atlas)"] = mixed
+forms = {}
+if a.filter:
+    for form, step in (("lds", "128"), ("direct", "0"), ("default", None)):
+        if step is None:
+            os.environ.pop("HJ_LIGHTMAP_FILTER_LDS_STEP", None)
+        else:
+            os.environ["HJ_LIGHTMAP_FILTER_LDS_STEP"] = step
+        forms[form] = device.Renderer(0)
+        forms[form].upload_scene(scenes["cbox"])                        # (a query needs a scene; the filter reads none of it)
+    for name, cs in scenes.items():
+        upload(cs)
+        filter_section(name, cs, forms)
+    scenes = {}
+else:
+    mixed, _ = with_grid_atlas(synth, chart=True)
+    scenes[f"mesh + one chart ({len(mixed.triangles)} triangles: the grid atlas, then a pair over the whole atlas)"] = mixed
 
 for name, cs in scenes.items():
     upload(cs)
@@ -143,4 +194,6 @@ for name, cs in scenes.items():
 if a.out:
     with open(a.out, "a") as f:
         f.write("\n".join(LINES) + "\n")
+for rr in forms.values():
+    rr.close()
 r.close()
