@@ -14,7 +14,8 @@ HOST_SRC = hijiki_amd/csrc/host/scene.cpp hijiki_amd/csrc/host/tree_opt.cpp hiji
 HOST_HDR = hijiki_amd/csrc/host/scene.hpp hijiki_amd/csrc/host/blockgen.hpp include/hijiki_hip.h include/hijiki_host.h
 # libhijiki_hip.so: its translation units (hijiki_amd/csrc/api/hj_internal.h lists them); render.hip, scene_relayout.hip,
 # scene_update.hip, lbvh_build.hip, tree_vote.hip, texture.hip, environment.hip, step_probe.hip, ray_query.hip, path_query.hip, path_adaptive.hip, gather_query.hip, lightmap_filter.hip, lightmap.hip and tree_reinsert.hip hold device code.  The register / scratch / LDS report of the path kernels: hijiki_amd/lib/resource_usage.txt
-# (render.hip's kernels, then behind the line '# gather_query.hip' the gather query's, behind '# lightmap_filter.hip' the light-map filter's, then behind '# lightmap.hip' the light-map kernels').
+# (render.hip's kernels, then behind the line '# gather_query.hip' the gather query's, behind '# lightmap_filter.hip' the light-map filter's, then behind '# lightmap.hip' the light-map kernels': report_unit below).
+# HIP_HDR: every unit is rebuilt when a header changes; kernels/*.h by wildcard, so a new kernel header (hj_compact.h, hj_lightmap_filter.h) needs no line here.
 HIP_UNITS = context scene_upload scene_relayout scene_update render render_calls comm lbvh_build tree_vote texture environment step_probe ray_query path_query path_adaptive gather_query lightmap_filter lightmap tree_reinsert
 HIP_OBJ = $(HIP_UNITS:%=build/obj/%.o) build/obj/blockgen.o build/obj/light_grid.o
 HIP_HDR = $(wildcard hijiki_amd/csrc/kernels/*.h) hijiki_amd/csrc/api/hj_internal.h hijiki_amd/csrc/api/hj_tuning.h hijiki_amd/csrc/api/light_grid.hpp hijiki_amd/csrc/api/scene_relayout.hpp hijiki_amd/csrc/api/refit_pass.hpp hijiki_amd/csrc/api/guard_box.hpp hijiki_amd/csrc/api/tree_vote.hpp hijiki_amd/csrc/api/tree_reinsert.h hijiki_amd/csrc/api/query_round.h hijiki_amd/csrc/api/query_round_loop.h include/hijiki_hip.h hijiki_amd/csrc/host/blockgen.hpp
@@ -32,34 +33,23 @@ hijiki_amd/lib/libhijiki_host.so: $(HOST_SRC) $(HOST_HDR)
 	$(CXX) -std=c++17 -O2 -g0 -fPIC -shared -Wall -Wextra $(FP_STRICT) -fvisibility=hidden \
 	  -DHJ_BUILDING -pthread -o $@ $(HOST_SRC)
 
-build/obj/render.o: hijiki_amd/csrc/api/render.hip $(HIP_HDR)
+# $(call report_unit,UNIT,PREDECESSOR): UNIT.o compiled with the compiler's resource report, which replaces resource_usage.txt from the
+# line '# UNIT.hip' on.  It stands behind PREDECESSOR.o, whose rule cuts the report from its own line on, so a rebuild of a unit
+# rebuilds the sections behind it and a rebuild of the last unit alone replaces its section.  No predecessor: the unit starts the
+# report, without a marker line.
+define report_unit
+build/obj/$(1).o: hijiki_amd/csrc/api/$(1).hip $$(HIP_HDR) $(2:%=build/obj/%.o)
 	@mkdir -p build/obj hijiki_amd/lib
-	$(HIPCC) $(HIP_FLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> hijiki_amd/lib/resource_usage.txt \
-	  || (cat hijiki_amd/lib/resource_usage.txt; false)
-
-# (behind render.o, which starts the report; a rebuild of this unit alone replaces its section)
-build/obj/gather_query.o: hijiki_amd/csrc/api/gather_query.hip $(HIP_HDR) build/obj/render.o
-	@mkdir -p build/obj hijiki_amd/lib
-	$(HIPCC) $(HIP_FLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/obj/gather_query.report \
-	  || (cat build/obj/gather_query.report; false)
-	@(sed '/^# gather_query.hip$$/,$$d' hijiki_amd/lib/resource_usage.txt; echo '# gather_query.hip'; cat build/obj/gather_query.report) \
+	$$(HIPCC) $$(HIP_FLAGS) -c $$< -o $$@ -Rpass-analysis=kernel-resource-usage 2> build/obj/$(1).report \
+	  || (cat build/obj/$(1).report; false)
+	@($(if $(2),sed '/^# $(1).hip$$$$/$(comma)$$$$d' hijiki_amd/lib/resource_usage.txt; echo '# $(1).hip';) cat build/obj/$(1).report) \
 	  > build/obj/resource_usage.tmp && mv build/obj/resource_usage.tmp hijiki_amd/lib/resource_usage.txt
-
-# (behind gather_query.o, whose rule cuts the report from its own line on: a rebuild of that unit rebuilds this one)
-build/obj/lightmap_filter.o: hijiki_amd/csrc/api/lightmap_filter.hip $(HIP_HDR) build/obj/gather_query.o
-	@mkdir -p build/obj hijiki_amd/lib
-	$(HIPCC) $(HIP_FLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/obj/lightmap_filter.report \
-	  || (cat build/obj/lightmap_filter.report; false)
-	@(sed '/^# lightmap_filter.hip$$/,$$d' hijiki_amd/lib/resource_usage.txt; echo '# lightmap_filter.hip'; cat build/obj/lightmap_filter.report) \
-	  > build/obj/resource_usage.lf.tmp && mv build/obj/resource_usage.lf.tmp hijiki_amd/lib/resource_usage.txt
-
-# (behind lightmap_filter.o in the same way; its section is the report's last)
-build/obj/lightmap.o: hijiki_amd/csrc/api/lightmap.hip $(HIP_HDR) build/obj/lightmap_filter.o
-	@mkdir -p build/obj hijiki_amd/lib
-	$(HIPCC) $(HIP_FLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/obj/lightmap.report \
-	  || (cat build/obj/lightmap.report; false)
-	@(sed '/^# lightmap.hip$$/,$$d' hijiki_amd/lib/resource_usage.txt; echo '# lightmap.hip'; cat build/obj/lightmap.report) \
-	  > build/obj/resource_usage.lm.tmp && mv build/obj/resource_usage.lm.tmp hijiki_amd/lib/resource_usage.txt
+endef
+comma := ,
+$(eval $(call report_unit,render,))
+$(eval $(call report_unit,gather_query,render))
+$(eval $(call report_unit,lightmap_filter,gather_query))
+$(eval $(call report_unit,lightmap,lightmap_filter))
 
 build/obj/%.o: hijiki_amd/csrc/api/%.hip $(HIP_HDR)
 	@mkdir -p build/obj

@@ -140,6 +140,17 @@ int sync_all(hj_context* ctx) {
   return HJ_OK;
 }
 
+int drain(hj_context* ctx, const char* fn, int rc) {
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc != HJ_OK) return rc;
+  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+  return HJ_OK;
+}
+
+int drain(hj_context* ctx, const char* fn, hipError_t e) {
+  return drain(ctx, fn, e == hipSuccess ? (int)HJ_OK : set_error(ctx, HJ_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e)));
+}
+
 }  // namespace hjapi
 
 extern "C" {

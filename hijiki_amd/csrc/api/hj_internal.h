@@ -28,17 +28,18 @@
 //   api/query_round.h     the tail threshold, register budget and group deal of the queries' path kernels
 //   api/query_round_loop.h the text of their round loop: no include guard, included inside the bodies of k_pq_paths and k_gq_paths
 //   api/path_adaptive.hip hj_trace_paths_adaptive: rounds of that path kernel (path_query_pass) over the rays still active, with the
-//                         k_pa_* kernels between them (running sums and stop rule, order-preserving compaction); includes hj_num.h only
+//                         k_pa_* kernels between them (running sums and stop rule; the order-preserving compaction is
+//                         kernels/hj_compact.h's text); includes that header and hj_num.h only
 //   api/gather_query.hip  hj_trace_irradiance: gather queries at caller-given points (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the same round loop with a top-up that draws a direction
 //                         at a point, and the per-point reduction); its host half behind the checks is fixed_spp_query
 //   api/lightmap.hip      hj_lightmap_texels, hj_bake_lightmap: the uploaded triangles' UVs rasterised into gather points, the gather's
-//                         records scattered into an atlas and dilated (includes kernels/hj_lightmap.h but for its filter section; beside it
+//                         records scattered into an atlas and dilated (includes kernels/hj_lightmap.h; beside it hj_compact.h and
 //                         hj_num.h alone: the path kernels' machine code does not depend on it).  The gather itself is
 //                         hj_trace_irradiance's, entered through that entry point with device arrays.  hj_bake_lightmap_filtered: the same
 //                         host routine with the filter between scatter and dilation
 //   api/lightmap_filter.hip hj_filter_lightmap: the edge-avoiding a-trous filter over an atlas, and lightmap_filter_check /
-//                         lightmap_filter_enqueue (below) for the bake (includes the filter section of kernels/hj_lightmap.h and hj_num.h alone)
+//                         lightmap_filter_enqueue (below) for the bake (includes kernels/hj_lightmap_filter.h and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -446,6 +447,14 @@ int query_gate(hj_context* ctx, const char* fn);
 //   lightmap_filter_check    what both refuse of a filter, without a device: unknown flag bits, iterations, sigmas
 //   lightmap_filter_enqueue  guide from the `count` device points, then f.iterations iterations from img[cur] into img[cur ^ 1], cur
 //                            flipped by each: the result is in img[cur] on return.  Enqueues on the context's stream only.
+//   lightmap_atlas_check     the atlas every light-map entry point accepts (the limits are here alone)
+constexpr uint32_t kLightmapMaxSide = 16384u;
+constexpr uint64_t kLightmapMaxTexels = 1ull << 26;
+inline int lightmap_atlas_check(hj_context* ctx, const char* fn, uint32_t w, uint32_t h) {
+  if (w == 0 || h == 0 || w > kLightmapMaxSide || h > kLightmapMaxSide || (uint64_t)w * h > kLightmapMaxTexels)
+    return set_error(ctx, HJ_ERR_INVALID, "%s: atlas %u x %u: 1 ... 16384 each and at most 2^26 texels", fn, w, h);
+  return HJ_OK;
+}
 int lightmap_filter_check(hj_context* ctx, const char* fn, const hj_lightmap_filter* f);
 int lightmap_filter_enqueue(hj_context* ctx, const hj_lightmap_filter& f, uint32_t W, uint32_t H, const float4* d_points, uint32_t count, float4* const img[2],
                             uint32_t& cur);
@@ -480,6 +489,11 @@ struct FixedSppQuery {
 };
 int fixed_spp_query(hj_context* ctx, const FixedSppQuery& q);
 int sync_all(hj_context* ctx);                       // drains the context's streams (api/context.hip)
+// The closing tail of an entry point that enqueued on the context's stream (fn: its name): the stream is synchronised whatever was
+// enqueued and whatever failed - nothing of the call stays in flight - and the first error is the call's.  rc: the status so far, or
+// e: the first hipError_t of the enqueue chain, refused as "fn: text".  (api/context.hip)
+int drain(hj_context* ctx, const char* fn, int rc);
+int drain(hj_context* ctx, const char* fn, hipError_t e);
 void drop_cached_comms(hj_context* ctx);             // api/comm.hip: the communicators hj_reduce_framebuffers made for ctx
 
 // api/render.hip: the launches of kernels/hj_kernels.h, on `s` (a failed launch surfaces at the render call's hipGetLastError)

@@ -1,8 +1,8 @@
 // hj_lightmap_texels, hj_bake_lightmap, hj_bake_lightmap_filtered: the uploaded scene's triangle UVs rasterised into gather points, and the gather's records
 // scattered into an atlas image ("Light-map baking").
 //
-// The kernels are kernels/hj_lightmap.h's (its filter section belongs to api/lightmap_filter.hip; beside it hj_num.h alone, so the path kernels'
-// machine code does not depend on this unit).  The gather of the bake is hj_trace_irradiance itself, called with device arrays: it
+// The kernels are kernels/hj_lightmap.h's (beside it hj_compact.h and hj_num.h alone, so the path kernels' machine code does not
+// depend on this unit).  The gather of the bake is hj_trace_irradiance itself, called with device arrays: it
 // enters fixed_spp_query with the gather's own chunk function, and nothing of its plan or its round loop is restated here.
 //   texels:  owner map = 0xFFFFFFFF  ->  k_lm_owner  ->  k_lm_owner_wide  ->  k_lm_count  ->  k_lm_scan  ->  k_lm_emit
 //   bake:    texels (a synchronisation: the count sizes the buffers)  ->  hj_trace_irradiance  ->  image = 0  ->  k_lm_scatter  ->
@@ -16,14 +16,10 @@ using namespace hjapi;
 
 namespace {
 
-constexpr uint32_t kMaxSide = 16384u;
-constexpr uint64_t kMaxTexels = 1ull << 26;
-
 // What both entry points refuse of a desc, without a device (fn: the entry point's name)
 int check_desc(hj_context* ctx, const char* fn, const hj_lightmap_desc* d) {
   if (d->flags & ~(uint32_t)HJ_LIGHTMAP_DEVICE_ARRAYS) return set_error(ctx, HJ_ERR_INVALID, "%s: unknown flag bits 0x%x", fn, d->flags);
-  if (d->width == 0 || d->height == 0 || d->width > kMaxSide || d->height > kMaxSide || (uint64_t)d->width * d->height > kMaxTexels)
-    return set_error(ctx, HJ_ERR_INVALID, "%s: atlas %u x %u: 1 ... 16384 each and at most 2^26 texels", fn, d->width, d->height);
+  HJ_TRY(lightmap_atlas_check(ctx, fn, d->width, d->height));
   if (!std::isfinite(d->offset)) return set_error(ctx, HJ_ERR_INVALID, "%s: offset %g is not finite", fn, (double)d->offset);
   return HJ_OK;
 }
@@ -84,14 +80,6 @@ void enqueue_emit(hj_context* ctx, const hj::LmArgs& a, const uint32_t* d_owner,
   hipLaunchKernelGGL(hj::k_lm_emit, dim3(nb), dim3(hj::kLmThreads), 0, ctx->stream, a, a.W * a.H, d_owner, d_counts, nb, capacity, d_points, d_owner_out);
 }
 
-// (also after a failed enqueue: nothing of the call stays in flight)
-int drain(hj_context* ctx, const char* fn, int rc) {
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc != HJ_OK) return rc;
-  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
-  return HJ_OK;
-}
-
 // Both bakes (fn: the entry point's name).  filter == NULL or no iterations: hj_bake_lightmap, launch for launch.
 int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_lightmap_filter* filter,
          const hj_render_opts* opts, float* image, size_t* out_count, hj_render_stats* stats) {
@@ -138,7 +126,7 @@ int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t
     d_points = static_cast<float4*>(lm.points.p);
     d_records = static_cast<float4*>(lm.records.p);
     enqueue_emit(ctx, a, d_owner, d_counts, nb, total, d_points, nullptr);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, fn, set_error(ctx, HJ_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e)));
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, fn, e);
     // 2. the gather: the same stream, so it runs behind the emit; it returns with its records complete
     HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), total, spp, &o, HJ_GATHER_DEVICE_ARRAYS, reinterpret_cast<float*>(d_records), stats));
   } else if (stats) {
@@ -162,8 +150,7 @@ int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t
   if (e == hipSuccess) e = hipGetLastError();
   // 5. to the host
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(image, img[cur], sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) rc = set_error(ctx, HJ_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
-  HJ_TRY(drain(ctx, fn, rc));
+  HJ_TRY(drain(ctx, fn, e));
   if (out_count) *out_count = total;
   return HJ_OK;
 }
@@ -192,8 +179,7 @@ int hj_lightmap_texels(hj_context* ctx, const hj_lightmap_desc* desc, float* poi
     if (points || owner) enqueue_emit(ctx, a, d_owner, d_counts, nb, capacity, reinterpret_cast<float4*>(points), owner);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&total, d_counts + nb, sizeof total, hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) rc = set_error(ctx, HJ_ERR_DEVICE, "hj_lightmap_texels: %s", hipGetErrorString(e));
-    HJ_TRY(drain(ctx, __func__, rc));
+    HJ_TRY(drain(ctx, __func__, e));
   } else {
     // host arrays: the count first - it sizes the staging -, then the records
     if (rc == HJ_OK && hipMemcpyAsync(&total, d_counts + nb, sizeof total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)

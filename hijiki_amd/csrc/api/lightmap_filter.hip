@@ -1,12 +1,11 @@
 // hj_filter_lightmap: the edge-avoiding a-trous filter over a light-map atlas ("Light-map filter"), and the host half of
 // the filter that hj_bake_lightmap_filtered (api/lightmap.hip) enters between its scatter and its dilation.
 //
-// The kernels are the filter section of kernels/hj_lightmap.h (HJ_LIGHTMAP_FILTER_KERNELS: this unit gets those alone, api/lightmap.hip
-// the others; beside it hj_num.h alone, so the path kernels' machine code does not depend on this unit).
+// The kernels are kernels/hj_lightmap_filter.h's (beside it hj_num.h and the light-map constants alone, so the path kernels' machine
+// code does not depend on this unit).
 //   guide = 0  ->  k_lm_guide  ->  iterations x (k_lm_filter_lds | k_lm_filter_direct) between two images
 #include "hj_internal.h"
-#define HJ_LIGHTMAP_FILTER_KERNELS
-#include "../kernels/hj_lightmap.h"
+#include "../kernels/hj_lightmap_filter.h"
 
 #pragma clang fp contract(off)
 
@@ -60,21 +59,6 @@ int lightmap_filter_enqueue(hj_context* ctx, const hj_lightmap_filter& f, uint32
 
 }  // namespace hjapi
 
-namespace {
-
-constexpr uint32_t kMaxSide = 16384u;          // (hj_lightmap_texels' limits: api/lightmap.hip)
-constexpr uint64_t kMaxTexels = 1ull << 26;
-
-// (also after a failed enqueue: nothing of the call stays in flight)
-int drain(hj_context* ctx, int rc) {
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc != HJ_OK) return rc;
-  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "hj_filter_lightmap: %s", hipGetErrorString(e));
-  return HJ_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 // The argument checks come first and need neither a device nor a context's state (hj_lightmap_texels' order and style).
@@ -82,8 +66,7 @@ int hj_filter_lightmap(hj_context* ctx, uint32_t width, uint32_t height, const f
   if (!filter || !image || (count != 0 && !points))
     return set_error(ctx, HJ_ERR_INVALID, "hj_filter_lightmap: null %s", !filter ? "filter" : !image ? "image" : "points");
   HJ_TRY(lightmap_filter_check(ctx, __func__, filter));
-  if (width == 0 || height == 0 || width > kMaxSide || height > kMaxSide || (uint64_t)width * height > kMaxTexels)
-    return set_error(ctx, HJ_ERR_INVALID, "hj_filter_lightmap: atlas %u x %u: 1 ... 16384 each and at most 2^26 texels", width, height);
+  HJ_TRY(lightmap_atlas_check(ctx, __func__, width, height));
   const size_t n = (size_t)width * height;
   if (count > n) return set_error(ctx, HJ_ERR_INVALID, "hj_filter_lightmap: %zu points for %zu texels", count, n);
   const bool on_device = (filter->flags & HJ_LIGHTMAP_DEVICE_ARRAYS) != 0;
@@ -116,9 +99,9 @@ int hj_filter_lightmap(hj_context* ctx, uint32_t width, uint32_t height, const f
     img[0] = static_cast<float4*>(lm.image[0].p);
     HJ_HIP(ctx, hipMemcpyAsync(img[0], image, sizeof(float4) * n, hipMemcpyHostToDevice, s));
     if (count != 0) {
-      HJ_TRY(drain(ctx, dev_alloc(ctx, lm.points, sizeof(float4) * 2 * count)));
+      HJ_TRY(drain(ctx, __func__, dev_alloc(ctx, lm.points, sizeof(float4) * 2 * count)));
       if (hipMemcpyAsync(lm.points.p, points, sizeof(float4) * 2 * count, hipMemcpyHostToDevice, s) != hipSuccess)
-        return drain(ctx, set_error(ctx, HJ_ERR_DEVICE, "hj_filter_lightmap: the points' copy failed"));
+        return drain(ctx, __func__, set_error(ctx, HJ_ERR_DEVICE, "hj_filter_lightmap: the points' copy failed"));
       d_points = static_cast<const float4*>(lm.points.p);
     }
   }
@@ -128,7 +111,7 @@ int hj_filter_lightmap(hj_context* ctx, uint32_t width, uint32_t height, const f
   if (rc == HJ_OK && (!on_device || cur != 0u) &&
       hipMemcpyAsync(image, img[cur], sizeof(float4) * n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s) != hipSuccess)
     rc = set_error(ctx, HJ_ERR_DEVICE, "hj_filter_lightmap: the image's copy failed");
-  return drain(ctx, rc);
+  return drain(ctx, __func__, rc);
 }
 
 }  // extern "C"

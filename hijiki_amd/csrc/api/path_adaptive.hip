@@ -14,7 +14,7 @@
 // The render-opts check, the context gate and the statistics read-back are the queries' (api/path_query.hip); the round loop below
 // is this entry point's own.
 #include "hj_internal.h"
-#include "../kernels/hj_num.h"
+#include "../kernels/hj_compact.h"
 
 #pragma clang fp contract(off)
 
@@ -87,50 +87,16 @@ __global__ __launch_bounds__(kPaThreads) void k_pa_accumulate(const float4* __re
   }
 }
 
-// The active entries of a workgroup's 256 list entries: per wave a ballot and its popcount, summed over the four waves
-HJ_DEV uint32_t pa_wave_counts(const uint32_t* __restrict__ flags, uint32_t len, uint32_t* wave_cnt, bool& active, unsigned long long& mask) {
-  const uint32_t j = blockIdx.x * kPaThreads + threadIdx.x;
-  active = j < len && flags[j] != 0u;
-  mask = __ballot(active);
-  if ((threadIdx.x & 63u) == 0u) wave_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
-  __syncthreads();
-  return j;
-}
-
+// The compaction is kernels/hj_compact.h's text; here: what is active (flag != 0 of an entry below len) and what an active entry becomes.
 __global__ __launch_bounds__(kPaThreads) void k_pa_count(const uint32_t* __restrict__ flags, uint32_t len, uint32_t* __restrict__ counts) {
   __shared__ uint32_t wave_cnt[kPaThreads / 64u];
-  bool active;
-  unsigned long long mask;
-  pa_wave_counts(flags, len, wave_cnt, active, mask);
-  if (threadIdx.x == 0) counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  const uint32_t j = blockIdx.x * kPaThreads + threadIdx.x;
+  (void)compact_wave_counts(j < len && flags[j] != 0u, wave_cnt);
+  if (threadIdx.x == 0) counts[blockIdx.x] = compact_tile_count<kPaThreads>(wave_cnt);
 }
 
-// counts[0, nb) -> their exclusive prefix sums in place, counts[nb] = the total.  One workgroup: thread t owns the `per` consecutive
-// counts from t * per, sums them, the 256 partial sums are scanned in LDS (Hillis-Steele, workgroup barriers only), and every
-// thread walks its counts again.  (A total is at most the list's length, below 2^31.)
-__global__ __launch_bounds__(kPaThreads) void k_pa_scan(uint32_t* __restrict__ counts, uint32_t nb) {
-  __shared__ uint32_t part[2][kPaThreads];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (nb + kPaThreads - 1u) / kPaThreads;
-  const uint32_t lo = min(t * per, nb), hi = min(lo + per, nb);
-  uint32_t sum = 0;
-  for (uint32_t b = lo; b < hi; b++) sum += counts[b];
-  uint32_t cur = 0;
-  part[0][t] = sum;
-  __syncthreads();
-  for (uint32_t d = 1; d < kPaThreads; d <<= 1) {
-    part[cur ^ 1u][t] = part[cur][t] + (t >= d ? part[cur][t - d] : 0u);
-    cur ^= 1u;
-    __syncthreads();
-  }
-  uint32_t run = part[cur][t] - sum;          // (exclusive)
-  for (uint32_t b = lo; b < hi; b++) {
-    const uint32_t v = counts[b];
-    counts[b] = run;
-    run += v;
-  }
-  if (t == kPaThreads - 1u) counts[nb] = part[cur][t];
-}
+// (A total is at most the list's length, below 2^31.)
+__global__ __launch_bounds__(kPaThreads) void k_pa_scan(uint32_t* __restrict__ counts, uint32_t nb) { compact_scan_tiles<kPaThreads>(counts, nb); }
 
 // Entry j of the list, if active, becomes entry offsets[workgroup] + (active entries of the workgroup before it) of the next list:
 // its ray index, and the caller's ray with word 6 = seed + n_after (uint32 wrap-around).  src == NULL: the list is every ray.
@@ -138,13 +104,11 @@ __global__ __launch_bounds__(kPaThreads) void k_pa_scatter(const uint32_t* __res
                                                            const uint32_t* __restrict__ offsets, const float4* __restrict__ rays, uint32_t n_after,
                                                            uint32_t* __restrict__ src_out, float4* __restrict__ rays_out) {
   __shared__ uint32_t wave_cnt[kPaThreads / 64u];
-  bool active;
-  unsigned long long mask;
-  const uint32_t j = pa_wave_counts(flags, len, wave_cnt, active, mask);
+  const uint32_t j = blockIdx.x * kPaThreads + threadIdx.x;
+  const bool active = j < len && flags[j] != 0u;
+  const unsigned long long mask = compact_wave_counts(active, wave_cnt);
   if (!active) return;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  uint32_t pos = offsets[blockIdx.x] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-  for (uint32_t w = 0; w < wave; w++) pos += wave_cnt[w];
+  HJ_COMPACT_RANK(pos, offsets[blockIdx.x], wave_cnt, mask);
   const uint32_t i = src ? src[j] : j;
   const float4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
   src_out[pos] = i;
@@ -282,9 +246,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
       e = hipMemcpyAsync(samples, d_out, n * 2 * f4, hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess && moments) e = hipMemcpyAsync(moments, d_mom, n * f4, hipMemcpyDeviceToHost, ctx->stream);
     }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) break;
+    HJ_TRY(drain(ctx, __func__, e));                              // (the round's ONE synchronisation)
     acc.add(total, plan.chunk_rays, active, c);
     total.paths += (uint64_t)active * c;
     total.batches += launches;
@@ -298,10 +260,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
     active = next;
     n_before = n_after;
   }
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return set_error(ctx, HJ_ERR_DEVICE, "hj_trace_paths_adaptive: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return drain(ctx, __func__, e);          // (the rays' copy in, or the synchronous copy back)
   if (stats) {
     total.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     *stats = total;

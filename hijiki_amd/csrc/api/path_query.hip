@@ -232,9 +232,7 @@ int fixed_spp_query(hj_context* ctx, const FixedSppQuery& q) {
     if (e == hipSuccess && !q.on_device) e = hipMemcpyAsync(q.out + 4 * rec * at, d_out, cnt * rec * f4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = acc.enqueue(launch, st, ctx->stream);
   }
-  const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "%s: %s", q.name, hipGetErrorString(e));
+  HJ_TRY(drain(ctx, q.name, e));
   if (q.stats) {
     std::memset(q.stats, 0, sizeof *q.stats);
     acc.add(*q.stats, chunk_rays, n, spp);

@@ -172,10 +172,7 @@ int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, 
       if (e == hipSuccess && surface) e = hipMemcpyAsync(surface + 16 * at, d_surface, cnt * 4 * f4, hipMemcpyDeviceToHost, ctx->stream);
     }
   }
-  const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also after a failed enqueue: nothing of this call stays in flight)
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return set_error(ctx, HJ_ERR_DEVICE, "hj_trace_rays: %s", hipGetErrorString(e));
-  return HJ_OK;
+  return drain(ctx, __func__, e);
 }
 
 }  // extern "C"

@@ -11,26 +11,15 @@
 //   k_lm_emit       one thread per owned texel: its record at its rank, the owner map to the caller
 //   k_lm_scatter    one thread per gather record: the scaled sum to the texel word 7 of its point names
 //   k_lm_dilate     one gutter pass from one image into another
-// Ordinary loads and stores and no inline assembly; the atomicMin of the two owner kernels is the one global atomic.
-//
-// The light-map filter ("Light-map filter"; include/hijiki_hip.h: hj_filter_lightmap) lives here too, for the unit
-// api/lightmap_filter.hip, which defines HJ_LIGHTMAP_FILTER_KERNELS before it includes this file and gets those kernels alone:
-//   k_lm_guide          one thread per point: position, normal and a valid word to the dense per-texel guide (zeroed before)
-//   k_lm_filter_direct  one a-trous iteration, one thread per texel, every tap loaded from memory
-//   k_lm_filter_lds     the same iteration on the lattice of one residue class modulo the step: tile and apron staged in LDS
-// Both forms call lm_tap, THE text of a tap, in the same order, so which one ran never shows in a bit.
+// Ordinary loads and stores and no inline assembly; the atomicMin of the two owner kernels is the one global atomic.  The compaction
+// of count, scan and emit is kernels/hj_compact.h's text.
 #pragma once
-#include "../../../include/hijiki_hip.h"
-#include "hj_num.h"
+#include "hj_lightmap_const.h"
+#include "hj_compact.h"
 
 #pragma clang fp contract(off)
 
 namespace hj {
-
-constexpr uint32_t kLmThreads = 256u;          // threads of a k_lm_* workgroup = texels of a scan tile (4 waves)
-constexpr uint32_t kLmNone = 0xFFFFFFFFu;      // owner word of a texel nobody owns
-
-#ifndef HJ_LIGHTMAP_FILTER_KERNELS
 
 struct LmUv { float au, av, bu, bv, cu, cv; };
 struct LmEdges { float e0, e1, e2, s; };
@@ -174,13 +163,6 @@ HJ_DEV bool lm_record(const LmArgs& a, uint32_t tri, uint32_t t, float4& r0, flo
   return true;
 }
 
-// The owned texels of a workgroup's 256: per wave a ballot and its popcount (the compaction of api/path_adaptive.hip)
-HJ_DEV void lm_wave_counts(bool owned, uint32_t* wave_cnt, unsigned long long& mask) {
-  mask = __ballot(owned);
-  if ((threadIdx.x & 63u) == 0u) wave_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
-  __syncthreads();
-}
-
 // One thread per texel (n = W * H): a texel whose record fails for its normal gets its owner word reset; counts[workgroup] = the
 // texels of the tile that keep an owner.
 __global__ __launch_bounds__(kLmThreads) void k_lm_count(LmArgs a, uint32_t n, uint32_t* __restrict__ owner, uint32_t* __restrict__ counts) {
@@ -195,37 +177,12 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_count(LmArgs a, uint32_t n, u
       if (!owned) owner[t] = kLmNone;
     }
   }
-  unsigned long long mask;
-  lm_wave_counts(owned, wave_cnt, mask);
-  if (threadIdx.x == 0) counts[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+  (void)compact_wave_counts(owned, wave_cnt);
+  if (threadIdx.x == 0) counts[blockIdx.x] = compact_tile_count<kLmThreads>(wave_cnt);
 }
 
-// counts[0, nb) -> their exclusive prefix sums in place, counts[nb] = the total.  One workgroup: thread t owns the `per` consecutive
-// counts from t * per, sums them, the 256 partial sums are scanned in LDS (Hillis-Steele, workgroup barriers only), and every
-// thread walks its counts again.  (A total is at most W * H <= 2^26.)
-__global__ __launch_bounds__(kLmThreads) void k_lm_scan(uint32_t* __restrict__ counts, uint32_t nb) {
-  __shared__ uint32_t part[2][kLmThreads];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (nb + kLmThreads - 1u) / kLmThreads;
-  const uint32_t lo = min(t * per, nb), hi = min(lo + per, nb);
-  uint32_t sum = 0;
-  for (uint32_t b = lo; b < hi; b++) sum += counts[b];
-  uint32_t cur = 0;
-  part[0][t] = sum;
-  __syncthreads();
-  for (uint32_t d = 1; d < kLmThreads; d <<= 1) {
-    part[cur ^ 1u][t] = part[cur][t] + (t >= d ? part[cur][t - d] : 0u);
-    cur ^= 1u;
-    __syncthreads();
-  }
-  uint32_t run = part[cur][t] - sum;          // (exclusive)
-  for (uint32_t b = lo; b < hi; b++) {
-    const uint32_t v = counts[b];
-    counts[b] = run;
-    run += v;
-  }
-  if (t == kLmThreads - 1u) counts[nb] = part[cur][t];
-}
+// The tiles' counts -> their exclusive offsets, the total behind them.  (A total is at most W * H <= 2^26.)
+__global__ __launch_bounds__(kLmThreads) void k_lm_scan(uint32_t* __restrict__ counts, uint32_t nb) { compact_scan_tiles<kLmThreads>(counts, nb); }
 
 // One thread per texel: an owned texel writes its record at rank offsets[tile] + the owned texels of the tile before it, so the
 // records stand in ascending texel order.  Nothing is written when the total (offsets[nb]) exceeds `capacity`: the caller learns
@@ -236,14 +193,11 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_emit(LmArgs a, uint32_t n, co
   const uint32_t t = blockIdx.x * kLmThreads + threadIdx.x;
   const uint32_t o = t < n ? owner[t] : kLmNone;
   const bool owned = o != kLmNone;
-  unsigned long long mask;
-  lm_wave_counts(owned, wave_cnt, mask);
+  const unsigned long long mask = compact_wave_counts(owned, wave_cnt);
   if (points && (uint64_t)offsets[nb] > capacity) return;
   if (owner_out && t < n) owner_out[t] = o;
   if (!owned || !points) return;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  uint32_t pos = offsets[blockIdx.x] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-  for (uint32_t w = 0; w < wave; w++) pos += wave_cnt[w];
+  HJ_COMPACT_RANK(pos, offsets[blockIdx.x], wave_cnt, mask);
   float4 r0, r1;
   (void)lm_record(a, o, t, r0, r1);
   points[2 * (size_t)pos] = r0;
@@ -282,138 +236,5 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_dilate(const float4* __restri
   }
   out[t] = c;
 }
-
-#else  // HJ_LIGHTMAP_FILTER_KERNELS
-
-// The guide: two float4 per texel t - [2 t] = (P, valid word: 0 = not guided), [2 t + 1] = (n, 0) - so a tap is one aligned 32-byte
-// read beside its 16 bytes of colour, and a texel that is not guided costs the valid word alone.
-struct LmFilterArgs {
-  const float4* guide;
-  const float4* in;             // the iteration's input image I ...
-  float4* out;                  // ... and its output O (never the same buffer)
-  uint32_t W, H, s;             // s: the step, 1 << i
-  float ip, in_, ic;            // 1 / sigma^2 of position, normal and this iteration's colour stop; 0 = off
-};
-
-constexpr uint32_t kLfTX = 32u, kLfTY = 8u;                   // texels of a workgroup's tile: 256 threads, a wave is two rows
-constexpr uint32_t kLfCX = kLfTX + 4u, kLfCY = kLfTY + 4u;    // ... with its apron of two taps on every side (k_lm_filter_lds)
-
-struct LmAcc { float r, g, b, w; };
-
-HJ_DEV float lm_sq(v3 v) { return (v.x * v.x + v.y * v.y) + v.z * v.z; }
-HJ_DEV float lm_k(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
-
-// One tap q of the texel (P, n, c), spline weight h: include/hijiki_hip.h's steps 3 - 6
-HJ_DEV void lm_tap(LmAcc& acc, v3 P, v3 n, v3 c, v3 Pq, v3 nq, v3 cq, float h, const LmFilterArgs& a) {
-  const float e = (lm_sq(Pq - P) * a.ip + lm_sq(nq - n) * a.in_) + lm_sq(cq - c) * a.ic;
-  const float w = h * hj_exp(-e);
-  acc.r = acc.r + cq.x * w;
-  acc.g = acc.g + cq.y * w;
-  acc.b = acc.b + cq.z * w;
-  acc.w = acc.w + w;
-}
-
-HJ_DEV bool lm_guided(const float4* guide, uint32_t t) { return reinterpret_cast<const uint32_t*>(guide)[8u * (size_t)t + 3u] != 0u; }
-
-// One thread per point; the guide holds zeros before.  A word 7 that names no texel of the atlas is skipped.
-__global__ __launch_bounds__(kLmThreads) void k_lm_guide(const float4* __restrict__ points, uint32_t count, uint32_t n, float4* __restrict__ guide) {
-  const uint32_t i = blockIdx.x * kLmThreads + threadIdx.x;
-  if (i >= count) return;
-  const float4 r0 = points[2 * (size_t)i], r1 = points[2 * (size_t)i + 1];
-  const uint32_t t = __float_as_uint(r1.w);
-  if (t >= n) return;
-  guide[2 * (size_t)t] = make_float4(r0.x, r0.y, r0.z, __uint_as_float(1u));
-  guide[2 * (size_t)t + 1] = make_float4(r0.w, r1.x, r1.y, 0.0f);
-}
-
-// Grid (ceil(W / 32), ceil(H / 8)): thread (i, j) of a workgroup is texel (32 bx + i, 8 by + j).  Every tap is loaded from memory:
-// the valid word first, guide and colour only behind it; the lanes of a row read contiguous segments at every step.
-__global__ __launch_bounds__(kLfTX * kLfTY) void k_lm_filter_direct(LmFilterArgs a) {
-  const uint32_t x = blockIdx.x * kLfTX + (threadIdx.x & (kLfTX - 1u)), y = blockIdx.y * kLfTY + threadIdx.x / kLfTX;
-  if (x >= a.W || y >= a.H) return;
-  const uint32_t t = y * a.W + x;
-  const float4 ci = a.in[t];
-  if (!lm_guided(a.guide, t)) {
-    a.out[t] = ci;
-    return;
-  }
-  const float4 g0 = a.guide[2 * (size_t)t], g1 = a.guide[2 * (size_t)t + 1];
-  const v3 P = xyz(g0), n = xyz(g1), c = xyz(ci);
-  LmAcc acc{0.f, 0.f, 0.f, 0.f};
-  const int s = (int)a.s;
-  for (int dy = -2; dy <= 2; dy++) {
-    const int yy = (int)y + dy * s;
-    if (yy < 0 || yy >= (int)a.H) continue;
-#pragma unroll
-    for (int dx = -2; dx <= 2; dx++) {
-      const int xx = (int)x + dx * s;
-      if (xx < 0 || xx >= (int)a.W) continue;
-      const uint32_t q = (uint32_t)yy * a.W + (uint32_t)xx;
-      if (!lm_guided(a.guide, q)) continue;
-      const float4 q0 = a.guide[2 * (size_t)q], q1 = a.guide[2 * (size_t)q + 1], cq = a.in[q];
-      lm_tap(acc, P, n, c, xyz(q0), xyz(q1), xyz(cq), lm_k(dx) * lm_k(dy), a);
-    }
-  }
-  a.out[t] = make_float4(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, ci.w);
-}
-
-// The texels with x = rx, y = ry modulo s form a lattice on which the taps of step s are the taps of step 1: a workgroup takes a
-// 32 x 8 tile of ONE lattice and stages the tile and its apron of two - guide and rgb, 40 bytes a cell, 17 280 bytes a workgroup at
-// every step - in LDS.  Grid (s * tiles_x, s * tiles_y), tiles_x = ceil(ceil(W / s) / 32), tiles_y = ceil(ceil(H / s) / 8): block
-// (rx * tiles_x + tx, ry * tiles_y + ty).  A cell outside the atlas or not guided holds a zero valid word (and read nothing more).
-__global__ __launch_bounds__(kLfTX * kLfTY) void k_lm_filter_lds(LmFilterArgs a, uint32_t tiles_x, uint32_t tiles_y) {
-  __shared__ float4 s_p[kLfCX * kLfCY];       // (P, valid word)
-  __shared__ float4 s_n[kLfCX * kLfCY];       // (n, c.r)
-  __shared__ float2 s_c[kLfCX * kLfCY];       // (c.g, c.b)
-  const uint32_t rx = blockIdx.x / tiles_x, ry = blockIdx.y / tiles_y;
-  const int s = (int)a.s;
-  const int lx0 = (int)((blockIdx.x - rx * tiles_x) * kLfTX), ly0 = (int)((blockIdx.y - ry * tiles_y) * kLfTY);   // lattice coordinates
-  for (uint32_t k = threadIdx.x; k < kLfCX * kLfCY; k += kLfTX * kLfTY) {
-    const uint32_t cj = k / kLfCX, ci = k - cj * kLfCX;
-    const int xx = (int)rx + s * (lx0 + (int)ci - 2), yy = (int)ry + s * (ly0 + (int)cj - 2);   // (|.| < 2^15 + 34 * 128)
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), nn = p;
-    float2 cc = make_float2(0.f, 0.f);
-    if (xx >= 0 && yy >= 0 && xx < (int)a.W && yy < (int)a.H) {
-      const uint32_t q = (uint32_t)yy * a.W + (uint32_t)xx;
-      if (lm_guided(a.guide, q)) {
-        const float4 q1 = a.guide[2 * (size_t)q + 1], cq = a.in[q];
-        p = a.guide[2 * (size_t)q];
-        nn = make_float4(q1.x, q1.y, q1.z, cq.x);
-        cc = make_float2(cq.y, cq.z);
-      }
-    }
-    s_p[k] = p;
-    s_n[k] = nn;
-    s_c[k] = cc;
-  }
-  __syncthreads();
-  const uint32_t i = threadIdx.x & (kLfTX - 1u), j = threadIdx.x / kLfTX;
-  const uint32_t x = rx + a.s * ((uint32_t)lx0 + i), y = ry + a.s * ((uint32_t)ly0 + j);
-  if (x >= a.W || y >= a.H) return;
-  const uint32_t t = y * a.W + x;
-  const float4 ci = a.in[t];
-  const uint32_t home = (j + 2u) * kLfCX + (i + 2u);
-  const float4 g0 = s_p[home];
-  if (__float_as_uint(g0.w) == 0u) {
-    a.out[t] = ci;
-    return;
-  }
-  const v3 P = xyz(g0), n = xyz(s_n[home]), c = xyz(ci);
-  LmAcc acc{0.f, 0.f, 0.f, 0.f};
-  for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-    for (int dx = -2; dx <= 2; dx++) {
-      const uint32_t k = (uint32_t)((int)home + dy * (int)kLfCX + dx);
-      const float4 q0 = s_p[k];
-      if (__float_as_uint(q0.w) == 0u) continue;
-      const float4 q1 = s_n[k];
-      const float2 q2 = s_c[k];
-      lm_tap(acc, P, n, c, xyz(q0), xyz(q1), V(q1.w, q2.x, q2.y), lm_k(dx) * lm_k(dy), a);
-    }
-  }
-  a.out[t] = make_float4(acc.r / acc.w, acc.g / acc.w, acc.b / acc.w, ci.w);
-}
-
-#endif  // HJ_LIGHTMAP_FILTER_KERNELS
 
 }  // namespace hj

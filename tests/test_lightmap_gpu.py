@@ -59,8 +59,9 @@ def edge_reference(W, H):
     return _edge[W, H]
 
 
-@pytest.mark.parametrize("W,H", [(1, 1), (7, 5), (64, 64), (257, 131)])
+@pytest.mark.parametrize("W,H", [(1, 1), (7, 5), (64, 64), (257, 131), (256, 256), (256, 257)])
 def test_edge_cases_at_four_atlas_sizes(lm, W, H):
+    """(the last two: 256 and 257 scan tiles - k_lm_scan's threads own one count each, then two, the last threads' runs empty)"""
     cs, case = LS.edge_scene()
     lm.upload_scene(cs)
     want = edge_reference(W, H)
