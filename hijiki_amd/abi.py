@@ -168,7 +168,8 @@ class RenderOpts(C.Structure):
 
 
 class AdaptiveOpts(C.Structure):
-    """hj_adaptive_opts (ABI 0.13): the rounds and the stop rule of hj_trace_paths_adaptive."""
+    """hj_adaptive_opts (ABI 0.13): the rounds and the stop rule of hj_trace_paths_adaptive, hj_trace_irradiance_adaptive and
+    hj_bake_lightmap_adaptive."""
     _fields_ = [("spp_min", u32), ("spp_step", u32), ("spp_max", u32), ("rel_error", f32), ("floor", f32)]
 
 

@@ -172,19 +172,43 @@ static void launch_gq_paths(bool sphere, dim3 grid, dim3 blk, hipStream_t s, con
 
 }  // namespace hj
 
-// the path launch and the resolve of one chunk (FixedSppQuery::chunk): path_query_pass's launch shape, a point in the place of a ray
-static void gather_chunk(const FixedSppQuery& fq, hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_pts, uint32_t cnt,
-                         float4* d_out, hipStream_t s) {
-  const bool sphere = (fq.flags & HJ_GATHER_SPHERE) != 0, sh9 = (fq.flags & HJ_GATHER_SH9) != 0;
+namespace hjapi {
+
+// the path launch of one chunk: path_query_pass's launch shape, a point in the place of a ray (declared in hj_internal.h)
+void gather_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_pts, uint32_t cnt, uint32_t spp, const hj_render_opts& o,
+                       uint32_t flags, hipStream_t s) {
+  const bool sphere = (flags & HJ_GATHER_SPHERE) != 0;
   const bool pairs = sc.has_pairs != 0, env = sc.env_alias != nullptr;
-  const uint32_t spp = fq.spp, num_samples = cnt * spp;    // (<= 2^31 - 1: HJ_PATHS_CHUNK's upper bound, or one point's spp)
+  const uint32_t num_samples = cnt * spp;                  // (<= 2^31 - 1: HJ_PATHS_CHUNK's upper bound, or one point's spp)
   set_num_wg(st, std::min<uint32_t>(G, (num_samples + 63u) / 64u));
-  const hj::GatherArgs q{d_pts, spp, num_samples, fq.o.max_bounces, fq.o.rr_start};
+  const hj::GatherArgs q{d_pts, spp, num_samples, o.max_bounces, o.rr_start};
   const dim3 grid(st.num_wg), blk(hj::kBlockThreads);
   if (pairs && env) hj::launch_gq_paths<true, true>(sphere, grid, blk, s, st, sc, q);
   else if (pairs) hj::launch_gq_paths<true, false>(sphere, grid, blk, s, st, sc, q);
   else if (env) hj::launch_gq_paths<false, true>(sphere, grid, blk, s, st, sc, q);
   else hj::launch_gq_paths<false, false>(sphere, grid, blk, s, st, sc, q);
+}
+
+// hemisphere mode, host arrays: every normal finite and not all zero, before anything is written
+int gather_normals_check(hj_context* ctx, const char* fn, const float* points, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    const float* nm = points + 8 * i + 3;
+    if (!std::isfinite(nm[0]) || !std::isfinite(nm[1]) || !std::isfinite(nm[2]) || (nm[0] == 0.f && nm[1] == 0.f && nm[2] == 0.f))
+      return set_error(ctx, HJ_ERR_INVALID, "%s: point %zu has the normal (%g, %g, %g): finite and not all zero is needed", fn, i, (double)nm[0],
+                       (double)nm[1], (double)nm[2]);
+  }
+  return HJ_OK;
+}
+
+}  // namespace hjapi
+
+// the path launch and the resolve of one chunk (FixedSppQuery::chunk)
+static void gather_chunk(const FixedSppQuery& fq, hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_pts, uint32_t cnt,
+                         float4* d_out, hipStream_t s) {
+  const bool sh9 = (fq.flags & HJ_GATHER_SH9) != 0;
+  const uint32_t spp = fq.spp;
+  gather_query_pass(st, sc, G, d_pts, cnt, spp, fq.o, fq.flags, s);
+  const dim3 blk(hj::kBlockThreads);
   const dim3 rgrid((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads);
   if (sh9)
     hipLaunchKernelGGL(hj::k_gq_resolve<true>, rgrid, blk, 0, s, static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd),
@@ -211,14 +235,7 @@ int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: device arrays must be 16-byte aligned");
   FixedSppQuery q{__func__, points, n, spp, sh9 ? 9u : 2u, on_device, out, stats, {}, gather_chunk, flags};
   HJ_TRY(query_render_opts(ctx, __func__, opts, q.o));
-  if (!sphere && !on_device) {               // (device arrays: the caller's contract)
-    for (size_t i = 0; i < n; i++) {
-      const float* nm = points + 8 * i + 3;
-      if (!std::isfinite(nm[0]) || !std::isfinite(nm[1]) || !std::isfinite(nm[2]) || (nm[0] == 0.f && nm[1] == 0.f && nm[2] == 0.f))
-        return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: point %zu has the normal (%g, %g, %g): finite and not all zero is needed", i,
-                         (double)nm[0], (double)nm[1], (double)nm[2]);
-    }
-  }
+  if (!sphere && !on_device) HJ_TRY(gather_normals_check(ctx, __func__, points, n));   // (device arrays: the caller's contract)
   HJ_TRY(query_gate(ctx, __func__));
   if (n == 0) return HJ_OK;
   return fixed_spp_query(ctx, q);

@@ -29,15 +29,22 @@
 //   api/query_round_loop.h the text of their round loop: no include guard, included inside the bodies of k_pq_paths and k_gq_paths
 //   api/path_adaptive.hip hj_trace_paths_adaptive: rounds of that path kernel (path_query_pass) over the rays still active, with the
 //                         k_pa_* kernels between them (running sums and stop rule; the order-preserving compaction is
-//                         kernels/hj_compact.h's text); includes that header and hj_num.h only
+//                         kernels/hj_compact.h's text); includes that header and hj_num.h only.  Also adaptive_query (below), the
+//                         round loop both adaptive queries enter
+//   api/adaptive_stop.h   the stop rule of the adaptive queries (pa_stops): one text for k_pa_accumulate and k_ga_accumulate
 //   api/gather_query.hip  hj_trace_irradiance: gather queries at caller-given points (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the same round loop with a top-up that draws a direction
 //                         at a point, and the per-point reduction); its host half behind the checks is fixed_spp_query
+//   api/gather_adaptive.hip hj_trace_irradiance_adaptive: adaptive_query over gather points (gather_query_pass for a round's launches,
+//                         k_ga_accumulate between them: the running sums with the first segments' hit count and nearest hit), and
+//                         k_ga_scatter, the scatter of hj_bake_lightmap_adaptive with its per-texel scale and sample map (includes
+//                         adaptive_stop.h and hj_num.h only)
 //   api/lightmap.hip      hj_lightmap_texels, hj_bake_lightmap: the uploaded triangles' UVs rasterised into gather points, the gather's
 //                         records scattered into an atlas and dilated (includes kernels/hj_lightmap.h; beside it hj_compact.h and
 //                         hj_num.h alone: the path kernels' machine code does not depend on it).  The gather itself is
 //                         hj_trace_irradiance's, entered through that entry point with device arrays.  hj_bake_lightmap_filtered: the same
-//                         host routine with the filter between scatter and dilation
+//                         host routine with the filter between scatter and dilation; hj_bake_lightmap_adaptive: the same routine
+//                         with hj_trace_irradiance_adaptive as its gather and api/gather_adaptive.hip's scatter
 //   api/lightmap_filter.hip hj_filter_lightmap: the edge-avoiding a-trous filter over an atlas, and lightmap_filter_check /
 //                         lightmap_filter_enqueue (below) for the bake (includes kernels/hj_lightmap_filter.h and hj_num.h alone)
 #pragma once
@@ -375,6 +382,7 @@ struct hj_context {
   // sums, the active flags, two index lists and one compacted ray array (ping-pong of the compaction), and the moments' staging.
   // hj_trace_irradiance (api/gather_query.hip) runs in the same path state and stages host arrays in in_rays (a chunk of points) and
   // out_samples (their records: 32 bytes a point, 144 with HJ_GATHER_SH9).
+  // hj_trace_irradiance_adaptive (api/gather_adaptive.hip) is the adaptive query over points: the same buffers, and 8 bytes a point more.
   struct PathQuery : hjapi::PathState {
     hjapi::DevBuf in_rays, out_samples;   // staging: one chunk of rays (adaptive: all rays of the call), their sample records
     hjapi::DevBuf pa_sums, pa_s2;         // adaptive: float4 (R, G, B, S1) and float S2 per ray
@@ -383,6 +391,7 @@ struct hj_context {
     hjapi::DevBuf pa_rays;                // ... the next round's rays: the active rays in order, seeds advanced
     hjapi::DevBuf pa_counts;              // ... per workgroup of the compaction its active count / offset, then the total
     hjapi::DevBuf pa_moments;             // ... staging of host moments
+    hjapi::DevBuf pa_state;               // ... the query's own running state per record (the adaptive gather: hit count, nearest hit)
     hjapi::PinnedBuf<uint32_t> pa_active; // ... the total as the host reads it after a round
   } paths;
 
@@ -392,7 +401,8 @@ struct hj_context {
   // (dev_alloc keeps a buffer that is large enough), reused by every call, freed with the context.
   // hj_filter_lightmap (api/lightmap_filter.hip): guide, 32 bytes per texel (position, valid word, normal); it shares points (staging
   // of host arrays) and the two images
-  struct Lightmap { hjapi::DevBuf owner, masks, counts, points, records, image[2], guide; } lightmap;
+  // hj_bake_lightmap_adaptive: sample_map, the staging of a host-side sample map (a word per texel)
+  struct Lightmap { hjapi::DevBuf owner, masks, counts, points, records, image[2], guide, sample_map; } lightmap;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
@@ -488,6 +498,51 @@ struct FixedSppQuery {
   uint32_t flags;                        // the entry point's own, for `chunk`
 };
 int fixed_spp_query(hj_context* ctx, const FixedSppQuery& q);
+// api/gather_query.hip: the gather's counterpart of path_query_pass - one launch of k_gq_paths over cnt device points at spp samples
+// each into st's sample arrays, without the resolve (flags: HJ_GATHER_SPHERE) - and the check of host points' normals in
+// hemisphere mode (finite, not all zero), for both gather entry points
+void gather_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_pts, uint32_t cnt, uint32_t spp, const hj_render_opts& o,
+                       uint32_t flags, hipStream_t s);
+int gather_normals_check(hj_context* ctx, const char* fn, const float* points, size_t n);
+// An adaptive query behind its entry point's checks (n > 0): hj_trace_paths_adaptive and hj_trace_irradiance_adaptive
+// (api/path_adaptive.hip).  adaptive_query owns the plans, the path state, the per-record buffers (hj_context::PathQuery pa_*), the
+// round loop - per chunk `pass` and `accumulate`, then the compaction of the list (k_pa_count / k_pa_scan / k_pa_scatter) -, the ONE
+// hipStreamSynchronize per round, the staging of host arrays and the statistics.  `pass` enqueues the path launch of cnt records at
+// d_in with c samples each; `accumulate` enqueues the kernel that continues the running sums over that launch's samples, evaluates
+// the stop rule, writes the active flags and a stopping record's output (AdaptiveLaunch says where everything is).
+struct AdaptiveLaunch {
+  const uint32_t* src;                   // the launch's entries of the round's list (NULL in round 0: record first + j)
+  uint32_t first, cnt, c, n_before;      // its place in the list, its records, samples a record this round and before it
+  uint32_t spp_max;                      // the stop rule's constants
+  float rel_error, floor;
+  float4* sums;                          // per record of the call: (R, G, B, S1)
+  float* s2;                             // ... S2
+  void* state;                           // ... state_bytes of the query's own running state (NULL: none)
+  uint32_t* flags;                       // per entry of the launch: still active
+  float4* out;                           // two float4 per record of the call
+  float4* moments;                       // may be NULL
+};
+struct AdaptiveQuery {
+  const char* name;                      // the entry point
+  const char* what;                      // "rays" / "points", for a message
+  const float* in;                       // n records of two float4, the seed in word 6
+  size_t n;
+  hj_adaptive_opts a;                    // checked (adaptive_opts_check)
+  bool on_device;                        // in / out / moments are device arrays, used in place
+  float* out;
+  float* moments;                        // may be NULL
+  hj_render_stats* stats;                // may be NULL
+  hj_render_opts o;
+  void (*pass)(const AdaptiveQuery& q, hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_in, uint32_t cnt, uint32_t c, hipStream_t s);
+  void (*accumulate)(const AdaptiveQuery& q, const hj::BatchState& st, const AdaptiveLaunch& l, hipStream_t s);
+  uint32_t flags;                        // the entry point's own, for the callbacks
+  size_t state_bytes;                    // running state per record beside the sums (0: none)
+};
+int adaptive_opts_check(hj_context* ctx, const char* fn, const hj_adaptive_opts* aopts, hj_adaptive_opts& a);
+int adaptive_query(hj_context* ctx, const AdaptiveQuery& q);
+// api/gather_adaptive.hip: the adaptive bake's scatter - `n` gather records whose word 3 is (float)n_i, into the zeroed image at the
+// texel word 7 of the point names, scaled by 3.14159274f / (float)n_i; sample_map (may be NULL) gets n_i at that texel
+void lightmap_scatter_adaptive(const float4* d_points, const float4* d_records, uint32_t n, float4* d_image, uint32_t* d_sample_map, hipStream_t s);
 int sync_all(hj_context* ctx);                       // drains the context's streams (api/context.hip)
 // The closing tail of an entry point that enqueued on the context's stream (fn: its name): the stream is synchronised whatever was
 // enqueued and whatever failed - nothing of the call stays in flight - and the first error is the call's.  rc: the status so far, or

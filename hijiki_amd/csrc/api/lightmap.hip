@@ -1,4 +1,4 @@
-// hj_lightmap_texels, hj_bake_lightmap, hj_bake_lightmap_filtered: the uploaded scene's triangle UVs rasterised into gather points, and the gather's records
+// hj_lightmap_texels, hj_bake_lightmap, hj_bake_lightmap_filtered, hj_bake_lightmap_adaptive: the uploaded scene's triangle UVs rasterised into gather points, and the gather's records
 // scattered into an atlas image ("Light-map baking").
 //
 // The kernels are kernels/hj_lightmap.h's (beside it hj_compact.h and hj_num.h alone, so the path kernels' machine code does not
@@ -7,6 +7,8 @@
 //   texels:  owner map = 0xFFFFFFFF  ->  k_lm_owner  ->  k_lm_owner_wide  ->  k_lm_count  ->  k_lm_scan  ->  k_lm_emit
 //   bake:    texels (a synchronisation: the count sizes the buffers)  ->  hj_trace_irradiance  ->  image = 0  ->  k_lm_scatter  ->
 //            [the filter's iterations: api/lightmap_filter.hip]  ->  gutter x k_lm_dilate between two images
+//   adaptive bake:  the same with hj_trace_irradiance_adaptive as the gather and, for k_lm_scatter, api/gather_adaptive.hip's scatter
+//            (lightmap_scatter_adaptive: the scale per texel from the record's own sample count, and the sample map)
 #include "hj_internal.h"
 #include "../kernels/hj_lightmap.h"
 
@@ -80,16 +82,22 @@ void enqueue_emit(hj_context* ctx, const hj::LmArgs& a, const uint32_t* d_owner,
   hipLaunchKernelGGL(hj::k_lm_emit, dim3(nb), dim3(hj::kLmThreads), 0, ctx->stream, a, a.W * a.H, d_owner, d_counts, nb, capacity, d_points, d_owner_out);
 }
 
-// Both bakes (fn: the entry point's name).  filter == NULL or no iterations: hj_bake_lightmap, launch for launch.
-int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_lightmap_filter* filter,
-         const hj_render_opts* opts, float* image, size_t* out_count, hj_render_stats* stats) {
+// The three bakes (fn: the entry point's name).  filter == NULL or no iterations: hj_bake_lightmap, launch for launch.  adaptive:
+// hj_bake_lightmap_adaptive - spp is not read, the gather is hj_trace_irradiance_adaptive and the scatter api/gather_adaptive.hip's,
+// which also fills sample_map (may be NULL; only read with adaptive).
+int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t spp, bool adaptive, const hj_adaptive_opts* aopts, uint32_t gutter,
+         const hj_lightmap_filter* filter, const hj_render_opts* opts, float* image, uint32_t* sample_map, size_t* out_count, hj_render_stats* stats) {
   if (!desc || !image) return set_error(ctx, HJ_ERR_INVALID, "%s: null %s", fn, !desc ? "desc" : "image");
   HJ_TRY(check_desc(ctx, fn, desc));
   const bool on_device = (desc->flags & HJ_LIGHTMAP_DEVICE_ARRAYS) != 0;
-  if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "%s: spp %u outside [1, 65536]", fn, spp);
+  hj_adaptive_opts ad{};
+  if (adaptive) HJ_TRY(adaptive_opts_check(ctx, fn, aopts, ad));
+  else if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "%s: spp %u outside [1, 65536]", fn, spp);
   if (gutter > HJ_LIGHTMAP_MAX_GUTTER) return set_error(ctx, HJ_ERR_INVALID, "%s: gutter %u above %u passes", fn, gutter, HJ_LIGHTMAP_MAX_GUTTER);
   if (on_device && (reinterpret_cast<uintptr_t>(image) & 15u) != 0)
     return set_error(ctx, HJ_ERR_INVALID, "%s: a device image must be 16-byte aligned", fn);
+  if (on_device && adaptive && (reinterpret_cast<uintptr_t>(sample_map) & 15u) != 0)
+    return set_error(ctx, HJ_ERR_INVALID, "%s: a device sample map must be 16-byte aligned", fn);
   if (filter) HJ_TRY(lightmap_filter_check(ctx, fn, filter));
   const uint32_t iterations = filter ? filter->iterations : 0u;
   hj_render_opts o;
@@ -119,6 +127,14 @@ int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t
     img[1] = static_cast<float4*>(lm.image[1].p);
   }
   uint32_t cur = (gutter + iterations) & 1u;     // (after that many swaps: 0)
+  uint32_t* d_map = nullptr;                     // the adaptive bake's sample map: the caller's device array, or staging of a host array
+  if (adaptive && sample_map) {
+    d_map = sample_map;
+    if (!on_device) {
+      HJ_TRY(dev_alloc(ctx, lm.sample_map, sizeof(uint32_t) * (size_t)n));
+      d_map = static_cast<uint32_t*>(lm.sample_map.p);
+    }
+  }
   float4 *d_points = nullptr, *d_records = nullptr;
   if (total != 0) {
     HJ_TRY(dev_alloc(ctx, lm.points, sizeof(float4) * 2 * (size_t)total));
@@ -128,14 +144,21 @@ int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t
     enqueue_emit(ctx, a, d_owner, d_counts, nb, total, d_points, nullptr);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, fn, e);
     // 2. the gather: the same stream, so it runs behind the emit; it returns with its records complete
-    HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), total, spp, &o, HJ_GATHER_DEVICE_ARRAYS, reinterpret_cast<float*>(d_records), stats));
+    if (adaptive)
+      HJ_TRY(hj_trace_irradiance_adaptive(ctx, reinterpret_cast<const float*>(d_points), total, &ad, &o, HJ_GATHER_DEVICE_ARRAYS,
+                                          reinterpret_cast<float*>(d_records), nullptr, stats));
+    else
+      HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), total, spp, &o, HJ_GATHER_DEVICE_ARRAYS, reinterpret_cast<float*>(d_records), stats));
   } else if (stats) {
     std::memset(stats, 0, sizeof *stats);
   }
   // 3. scatter, the filter's iterations, 4. dilate
   hipStream_t s = ctx->stream;
   hipError_t e = hipMemsetAsync(img[cur], 0, sizeof(float4) * (size_t)n, s);
-  if (e == hipSuccess && total != 0) {
+  if (e == hipSuccess && d_map) e = hipMemsetAsync(d_map, 0, sizeof(uint32_t) * (size_t)n, s);
+  if (e == hipSuccess && total != 0 && adaptive) {
+    lightmap_scatter_adaptive(d_points, d_records, total, img[cur], d_map, s);
+  } else if (e == hipSuccess && total != 0) {
     const float scale = 3.14159274f / (float)spp;
     hipLaunchKernelGGL(hj::k_lm_scatter, dim3((total + hj::kLmThreads - 1u) / hj::kLmThreads), dim3(hj::kLmThreads), 0, s, d_points, d_records, total, scale,
                        img[cur]);
@@ -150,6 +173,7 @@ int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t
   if (e == hipSuccess) e = hipGetLastError();
   // 5. to the host
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(image, img[cur], sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && !on_device && d_map) e = hipMemcpyAsync(sample_map, d_map, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s);
   HJ_TRY(drain(ctx, fn, e));
   if (out_count) *out_count = total;
   return HJ_OK;
@@ -206,12 +230,17 @@ int hj_lightmap_texels(hj_context* ctx, const hj_lightmap_desc* desc, float* poi
 
 int hj_bake_lightmap(hj_context* ctx, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_render_opts* opts, float* image,
                      size_t* out_count, hj_render_stats* stats) {
-  return bake(ctx, __func__, desc, spp, gutter, nullptr, opts, image, out_count, stats);
+  return bake(ctx, __func__, desc, spp, false, nullptr, gutter, nullptr, opts, image, nullptr, out_count, stats);
 }
 
 int hj_bake_lightmap_filtered(hj_context* ctx, const hj_lightmap_desc* desc, uint32_t spp, uint32_t gutter, const hj_lightmap_filter* filter,
                               const hj_render_opts* opts, float* image, size_t* out_count, hj_render_stats* stats) {
-  return bake(ctx, __func__, desc, spp, gutter, filter, opts, image, out_count, stats);
+  return bake(ctx, __func__, desc, spp, false, nullptr, gutter, filter, opts, image, nullptr, out_count, stats);
+}
+
+int hj_bake_lightmap_adaptive(hj_context* ctx, const hj_lightmap_desc* desc, const hj_adaptive_opts* adaptive, uint32_t gutter, const hj_lightmap_filter* filter,
+                              const hj_render_opts* opts, float* image, uint32_t* sample_map, size_t* out_count, hj_render_stats* stats) {
+  return bake(ctx, __func__, desc, 0, true, adaptive, gutter, filter, opts, image, sample_map, out_count, stats);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 //
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
 //              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] [--env FILE [--env-scale S]]
-//              [--bake-lightmap WxH [--gutter 2] [--filter N[,sp[,sn[,sc]]]]]
+//              [--bake-lightmap WxH [--gutter 2] [--filter N[,sp[,sn[,sc]]]] [--adaptive min,step,max,rel[,floor]] [--sample-map FILE]]
 //              <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
@@ -13,6 +13,9 @@
 // --filter N[,sp[,sn[,sc]]] (not upstream) runs N iterations of hj_filter_lightmap's edge-avoiding a-trous filter between the bake's
 // scatter and its dilation (hj_bake_lightmap_filtered): sp, sn, sc are sigma_position (default: 1 % of the root box's diagonal),
 // sigma_normal (0.5) and sigma_color (0: off) - a starting point, not a tuned optimum.
+// --adaptive min,step,max,rel[,floor] (not upstream) bakes with hj_bake_lightmap_adaptive: every texel gets `min` samples, then `step`
+// more a round up to `max`, until the standard error of its mean luminance is at most rel * max(mean, floor) (floor: 0.01 unless
+// given); -s is then ignored, with a note on stderr.  --sample-map FILE writes the samples each texel received as a one-channel PFM.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -39,6 +42,9 @@ struct Opt {
   uint32_t filter_n = 0;                                   // --filter N[,sp[,sn[,sc]]]: iterations (0: none)
   float filter_sp = -1.0f, filter_sn = 0.5f, filter_sc = 0.0f;   // (sp < 0: 1 % of the root box's diagonal)
   bool filter_given = false;
+  hj_adaptive_opts adaptive{0u, 0u, 0u, 0.0f, 0.01f};      // --adaptive min,step,max,rel[,floor]
+  bool adaptive_given = false, samples_given = false;      // (samples_given: -s was on the command line)
+  std::string sample_map;                                  // --sample-map FILE
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -56,6 +62,10 @@ struct Opt {
                "        --filter <N>[,<sp>[,<sn>[,<sc>]]]        (not upstream) N = 0 ... 8 iterations of the edge-avoiding a-trous filter over the baked\n"
                "                                                 atlas; sigmas of position [default: 1 %% of the scene box's diagonal], normal [0.5]\n"
                "                                                 and colour [0 = off]: a starting point, not a tuned optimum\n"
+               "        --adaptive <min>,<step>,<max>,<rel>[,<floor>]  (not upstream) --bake-lightmap with the sample count decided per texel:\n"
+               "                                                 min samples, then step more a round up to max, until the standard error of the\n"
+               "                                                 mean luminance is at most rel * max(mean, floor [0.01]); -s is ignored\n"
+               "        --sample-map <file>                      (not upstream) with --adaptive: the samples per texel as a one-channel PFM\n"
                "OPTIONS:\n    -h, --height <height>                        [default: 600]\n"
                "    -o, --output-image <output-image>            [default: /tmp/output.exr] (.exr, .pfm or .png)\n"
                "        --present-interval <present-interval>    [default: 128] (ignored: no preview window)\n"
@@ -81,7 +91,7 @@ Opt parse(int argc, char** argv) {
     else if (a == "-w" || a == "--width") o.width = (uint32_t)std::stoul(value(i));
     else if (a == "-h" || a == "--height") o.height = (uint32_t)std::stoul(value(i));
     else if (a == "--present-interval") o.present_interval = (uint32_t)std::stoul(value(i));
-    else if (a == "-s" || a == "--sample-count") o.sample_count = (uint32_t)std::stoul(value(i));
+    else if (a == "-s" || a == "--sample-count") { o.sample_count = (uint32_t)std::stoul(value(i)); o.samples_given = true; }
     else if (a == "-o" || a == "--output-image") o.output_image = value(i);
     else if (a == "--seed") o.seed = std::stoull(value(i));
     else if (a == "--env") o.env = value(i);
@@ -117,6 +127,20 @@ Opt parse(int argc, char** argv) {
       o.filter_n = n; o.filter_sp = sg[0]; o.filter_sn = sg[1]; o.filter_sc = sg[2];
       o.filter_given = true;
     }
+    else if (a == "--adaptive") {
+      const std::string v = value(i);
+      unsigned mn = 0, stp = 0, mx = 0;
+      float rel = 0.0f, fl = 0.01f;
+      char tail = 0;
+      const int got = std::sscanf(v.c_str(), "%u,%u,%u,%f,%f%c", &mn, &stp, &mx, &rel, &fl, &tail);
+      const bool ok = (got == 4 || got == 5) && v.find_first_not_of("0123456789.,eE+-") == std::string::npos && v.back() != ',' && mn >= 2 && stp >= 1 &&
+                      mx >= mn && mx <= 65536u && 1u + (mx - mn + stp - 1u) / stp <= 64u && rel >= 0.0f && rel <= 3.0e38f && fl >= 0.0f && fl <= 3.0e38f;
+      if (!ok)
+        usage(("bad --adaptive " + v + " (min,step,max,rel[,floor]: 2 <= min <= max <= 65536, step >= 1, at most 64 rounds, rel and floor finite and >= 0)").c_str());
+      o.adaptive = hj_adaptive_opts{mn, stp, mx, rel, fl};
+      o.adaptive_given = true;
+    }
+    else if (a == "--sample-map") o.sample_map = value(i);
     else if (a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown flag " + a).c_str());
     else if (o.scene.empty()) o.scene = a;
@@ -126,8 +150,24 @@ Opt parse(int argc, char** argv) {
   if (o.env.empty() && o.env_scale != 1.0f) usage("--env-scale without --env");
   if (o.gutter_given && o.bake_w == 0) usage("--gutter without --bake-lightmap");
   if (o.filter_given && o.bake_w == 0) usage("--filter without --bake-lightmap");
+  if (o.adaptive_given && o.bake_w == 0) usage("--adaptive without --bake-lightmap");
+  if (!o.sample_map.empty() && !o.adaptive_given) usage("--sample-map without --adaptive");
+  if (o.adaptive_given && o.samples_given) std::fprintf(stderr, "note: --adaptive decides the samples per texel; -s %u is ignored\n", o.sample_count);
   if (o.filter_given && o.filter_sp < 0.0f && o.device_bvh) usage("--filter with --device-bvh needs its sigma_position (no root box on the host)");
   return o;
+}
+
+// the sample map as a one-channel PFM ("Pf"): the counts as floats (exact: at most 65536), bottom row first on disk
+void write_grey_pfm(const std::string& path, uint32_t w, uint32_t h, const std::vector<uint32_t>& words) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot create " + path);
+  std::fprintf(f, "Pf\n%u %u\n-1.0\n", w, h);
+  std::vector<float> row(w);
+  for (uint32_t y = 0; y < h; y++) {
+    for (uint32_t x = 0; x < w; x++) row[x] = (float)words[(size_t)(h - 1 - y) * w + x];
+    std::fwrite(row.data(), sizeof(float), w, f);
+  }
+  if (std::fclose(f) != 0) throw std::runtime_error("write failed: " + path);
 }
 
 void check(hj_context* ctx, int rc, const char* what) {
@@ -189,6 +229,7 @@ int main(int argc, char** argv) {
       size_t texels = 0;
       hj_render_stats bst;
       std::printf("Baking %u x %u texels...\n", opt.bake_w, opt.bake_h);
+      hj_lightmap_filter flt{0u, 0.0f, 0.0f, 0.0f, 0u};
       if (opt.filter_given) {
         float sp = opt.filter_sp;
         if (sp < 0.0f) {                                                 // 1 % of the root box's diagonal
@@ -196,9 +237,19 @@ int main(int argc, char** argv) {
           const float dx = root.aabb_max[0] - root.aabb_min[0], dy = root.aabb_max[1] - root.aabb_min[1], dz = root.aabb_max[2] - root.aabb_min[2];
           sp = 0.01f * std::sqrt((dx * dx + dy * dy) + dz * dz);
         }
-        const hj_lightmap_filter flt{opt.filter_n, sp, opt.filter_sn, opt.filter_sc, 0u};
+        flt = hj_lightmap_filter{opt.filter_n, sp, opt.filter_sn, opt.filter_sc, 0u};
         std::printf("Filter: %u iterations, sigmas %g (position), %g (normal), %g (colour)\n", flt.iterations, (double)sp, (double)flt.sigma_normal,
                     (double)flt.sigma_color);
+      }
+      if (opt.adaptive_given) {
+        std::vector<uint32_t> smap(opt.sample_map.empty() ? 0 : (size_t)opt.bake_w * opt.bake_h);
+        std::printf("Adaptive: %u samples, then %u a round up to %u; rel_error %g, floor %g\n", opt.adaptive.spp_min, opt.adaptive.spp_step, opt.adaptive.spp_max,
+                    (double)opt.adaptive.rel_error, (double)opt.adaptive.floor);
+        check(ctx, hj_bake_lightmap_adaptive(ctx, &lm, &opt.adaptive, opt.gutter, opt.filter_given ? &flt : nullptr, nullptr, rgba.data(),
+                                             smap.empty() ? nullptr : smap.data(), &texels, &bst), "bake");
+        std::printf("Adaptive rounds: %llu\n", (unsigned long long)bst.bounce_rounds);
+        if (!smap.empty()) write_grey_pfm(opt.sample_map, opt.bake_w, opt.bake_h, smap);
+      } else if (opt.filter_given) {
         check(ctx, hj_bake_lightmap_filtered(ctx, &lm, opt.sample_count, opt.gutter, &flt, nullptr, rgba.data(), &texels, &bst), "bake");
       } else {
         check(ctx, hj_bake_lightmap(ctx, &lm, opt.sample_count, opt.gutter, nullptr, rgba.data(), &texels, &bst), "bake");

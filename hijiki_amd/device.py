@@ -27,7 +27,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
            "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
            "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap", "hj_filter_lightmap",
-           "hj_bake_lightmap_filtered")
+           "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -95,6 +95,10 @@ def lib():
         L.hj_filter_lightmap.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(abi.LightmapFilter), vp]   # (host or device pointers)
         L.hj_bake_lightmap_filtered.argtypes = [vp, C.POINTER(abi.LightmapDesc), C.c_uint32, C.c_uint32, C.POINTER(abi.LightmapFilter),
                                                 C.POINTER(abi.RenderOpts), vp, C.POINTER(C.c_size_t), C.POINTER(abi.RenderStats)]
+        L.hj_trace_irradiance_adaptive.argtypes = [vp, vp, C.c_size_t, C.POINTER(abi.AdaptiveOpts), C.POINTER(abi.RenderOpts), C.c_uint32, vp, vp,
+                                                   C.POINTER(abi.RenderStats)]  # (host or device pointers)
+        L.hj_bake_lightmap_adaptive.argtypes = [vp, C.POINTER(abi.LightmapDesc), C.POINTER(abi.AdaptiveOpts), C.c_uint32, C.POINTER(abi.LightmapFilter),
+                                                C.POINTER(abi.RenderOpts), vp, vp, C.POINTER(C.c_size_t), C.POINTER(abi.RenderStats)]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -544,6 +548,18 @@ class Renderer:
             rays.view(np.uint32)[:, 6] = seeds
         return np.ascontiguousarray(rays), False
 
+    @staticmethod
+    def _adaptive_opts(what, spp_min, spp_step, spp_max, rel_error, floor):
+        """The adaptive opts of the adaptive calls, checked before any call."""
+        spp_min, spp_step, spp_max, rel_error, floor = int(spp_min), int(spp_step), int(spp_max), float(rel_error), float(floor)
+        if not (2 <= spp_min <= spp_max <= 65536 and spp_step >= 1):
+            raise ValueError(f"{what}: 2 <= spp_min <= spp_max <= 65536 and spp_step >= 1 are needed (got {spp_min}, {spp_max}, {spp_step})")
+        if 1 + -(-(spp_max - spp_min) // spp_step) > 64:
+            raise ValueError(f"{what}: more than 64 rounds from {spp_min} to {spp_max} in steps of {spp_step}")
+        if not (0.0 <= rel_error < float("inf") and 0.0 <= floor < float("inf")):
+            raise ValueError(f"{what}: rel_error and floor must be finite and >= 0 (got {rel_error}, {floor})")
+        return abi.AdaptiveOpts(spp_min, spp_step, spp_max, rel_error, floor)
+
     def trace_paths_adaptive(self, rays, seeds=None, spp_min=4, spp_step=4, spp_max=64, rel_error=0.05, floor=0.01, opts=None, stats=False,
                              moments=False):
         """hj_trace_paths_adaptive: `trace_paths` with the number of samples decided per ray on the device.  Every ray gets spp_min
@@ -553,14 +569,7 @@ class Renderer:
         spp.  rays, seeds, opts and the array / tensor handling are `trace_paths`'.  moments=True: also an (n, 4) float32 array
         (tensor) of S1, S2 (the sums of the samples' luminance and of its square), the last sem2 and the sample count as uint32 bits.
         stats=True: also the statistics dict (bounce_rounds = rounds run).  Returns samples [, moments] [, statistics]."""
-        spp_min, spp_step, spp_max, rel_error, floor = int(spp_min), int(spp_step), int(spp_max), float(rel_error), float(floor)
-        if not (2 <= spp_min <= spp_max <= 65536 and spp_step >= 1):
-            raise ValueError(f"trace_paths_adaptive: 2 <= spp_min <= spp_max <= 65536 and spp_step >= 1 are needed (got {spp_min}, {spp_max}, {spp_step})")
-        if 1 + -(-(spp_max - spp_min) // spp_step) > 64:
-            raise ValueError(f"trace_paths_adaptive: more than 64 rounds from {spp_min} to {spp_max} in steps of {spp_step}")
-        if not (0.0 <= rel_error < float("inf") and 0.0 <= floor < float("inf")):
-            raise ValueError(f"trace_paths_adaptive: rel_error and floor must be finite and >= 0 (got {rel_error}, {floor})")
-        a = abi.AdaptiveOpts(spp_min, spp_step, spp_max, rel_error, floor)
+        a = self._adaptive_opts("trace_paths_adaptive", spp_min, spp_step, spp_max, rel_error, floor)
         st = abi.RenderStats()
         o = C.byref(opts) if opts is not None else None
         rays, on_gpu = self._path_rays("trace_paths_adaptive", rays, seeds)
@@ -619,6 +628,41 @@ class Renderer:
         out = np.zeros((n, words), np.float32)
         self._check(lib().hj_trace_irradiance(self._h, points.ctypes.data, n, spp, o, flags, out.ctypes.data, C.byref(st)))
         return (out, stats_dict(st)) if stats else out
+
+    def trace_irradiance_adaptive(self, points, seeds=None, spp_min=4, spp_step=4, spp_max=64, rel_error=0.05, floor=0.01, sphere=False, opts=None,
+                                  stats=False, moments=False):
+        """hj_trace_irradiance_adaptive: `trace_irradiance` with the number of samples decided per point on the device, by the rounds
+        and the stop rule of `trace_paths_adaptive` (spp_min samples, then spp_step more a round up to spp_max, until the standard
+        error of the mean luminance is at most rel_error * max(mean luminance, floor)).  -> (n, 8) float32 records as
+        `trace_irradiance` gives them, word 3 = the samples the point received: record i is what `trace_irradiance` returns for point
+        i with that spp.  There is no sh9.  points, seeds, sphere, opts, the normal check of host arrays and the array / tensor
+        handling are `trace_irradiance`'s; moments and stats are `trace_paths_adaptive`'s.  Returns records [, moments] [, statistics]."""
+        a = self._adaptive_opts("trace_irradiance_adaptive", spp_min, spp_step, spp_max, rel_error, floor)
+        flags = abi.GATHER_SPHERE if sphere else 0
+        st = abi.RenderStats()
+        o = C.byref(opts) if opts is not None else None
+        points, on_gpu = self._path_rays("trace_irradiance_adaptive", points, seeds)
+        n = len(points)
+        if on_gpu:
+            import torch
+            out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+            mom = torch.empty((n, 4), dtype=torch.float32, device=points.device) if moments else None
+            torch.cuda.current_stream(points.device).synchronize()    # (the allocations and whatever wrote `points`)
+            self._check(lib().hj_trace_irradiance_adaptive(self._h, points.data_ptr() if n else None, n, C.byref(a), o, flags | abi.GATHER_DEVICE_ARRAYS,
+                                                           out.data_ptr() if n else None, mom.data_ptr() if moments and n else None, C.byref(st)))
+        else:
+            if not sphere:
+                nm = points[:, 3:6]
+                bad = ~np.isfinite(nm).all(axis=1) | (nm == 0).all(axis=1)
+                if bad.any():
+                    i = int(np.argmax(bad))
+                    raise ValueError(f"trace_irradiance_adaptive: point {i} has the normal {nm[i].tolist()}: finite and not all zero is needed")
+            out = np.zeros((n, 8), np.float32)
+            mom = np.zeros((n, 4), np.float32) if moments else None
+            self._check(lib().hj_trace_irradiance_adaptive(self._h, points.ctypes.data, n, C.byref(a), o, flags, out.ctypes.data,
+                                                           mom.ctypes.data if moments else None, C.byref(st)))
+        res = (out,) + ((mom,) if moments else ()) + ((stats_dict(st),) if stats else ())
+        return res if len(res) > 1 else out
 
     @staticmethod
     def _lightmap_desc(what, width, height, first_triangle, num_triangles, seed, seed_stride, offset, device):
@@ -704,14 +748,24 @@ class Renderer:
         return img
 
     def bake_lightmap(self, width, height, spp, gutter=2, first_triangle=0, num_triangles=0, seed=0, seed_stride=1, offset=0.0, opts=None,
-                      stats=False, device=False, filter=None):
+                      stats=False, device=False, filter=None, adaptive=None, sample_map=False):
         """hj_bake_lightmap: `lightmap_texels`, the hemisphere gather of `trace_irradiance` at `spp` samples over its points, and the
         records scattered into the atlas, all on the device -> (height, width, 4) float32: a texel with a record holds its irradiance
         (pi / spp x the gathered sum) and alpha 1; `gutter` dilation passes give texels next to covered ones the mean of their covered
         neighbours and alpha 0.5; everything else is zero.  opts as in `trace_irradiance`.  device=True: a torch tensor on the
         renderer's GPU.  stats=True: returns (image, the gather's statistics dict with `texels` = the texels that had a record).
         filter: None, or (iterations, sigma_position, sigma_normal[, sigma_color]) - `filter_lightmap` over the scattered image with the
-        bake's own points as guides, before the dilation (hj_bake_lightmap_filtered); `default_filter_sigmas` gives a starting point."""
+        bake's own points as guides, before the dilation (hj_bake_lightmap_filtered); `default_filter_sigmas` gives a starting point.
+        adaptive: None, or a dict with the keywords of `trace_irradiance_adaptive` (spp_min, spp_step, spp_max, rel_error, floor; its
+        defaults for those left out) - hj_bake_lightmap_adaptive: the gather decides each texel's sample count, `spp` is not used (pass
+        None), a texel's scale is pi / its own count, and `bounce_rounds` of the statistics is the rounds run.  sample_map=True (only
+        with adaptive): also the (height, width) uint32 map (an int32 tensor with device=True) of the samples each texel with a record
+        received, 0 elsewhere.  Returns image [, sample map] [, statistics]."""
+        if adaptive is not None:
+            return self._bake_lightmap_adaptive(width, height, adaptive, int(gutter), first_triangle, num_triangles, seed, seed_stride, offset, opts,
+                                                stats, device, filter, sample_map)
+        if sample_map:
+            raise ValueError("bake_lightmap: sample_map needs adaptive (a fixed-spp bake gives every texel spp samples)")
         spp, gutter = int(spp), int(gutter)
         if not 1 <= spp <= 65536:
             raise ValueError(f"bake_lightmap: spp {spp} outside [1, 65536]")
@@ -737,6 +791,40 @@ class Renderer:
             img = np.zeros((d.height, d.width, 4), np.float32)
             self._check(call(img.ctypes.data))
         return (img, dict(stats_dict(st), texels=count.value)) if stats else img
+
+    def _bake_lightmap_adaptive(self, width, height, adaptive, gutter, first_triangle, num_triangles, seed, seed_stride, offset, opts, stats, device,
+                                filter, sample_map):
+        """`bake_lightmap` with adaptive=dict: hj_bake_lightmap_adaptive."""
+        unknown = set(adaptive) - {"spp_min", "spp_step", "spp_max", "rel_error", "floor"}
+        if unknown:
+            raise ValueError(f"bake_lightmap: adaptive has the unknown keys {sorted(unknown)}")
+        kw = dict(dict(spp_min=4, spp_step=4, spp_max=64, rel_error=0.05, floor=0.01), **adaptive)
+        a = self._adaptive_opts("bake_lightmap", kw["spp_min"], kw["spp_step"], kw["spp_max"], kw["rel_error"], kw["floor"])
+        if not 0 <= gutter <= abi.LIGHTMAP_MAX_GUTTER:
+            raise ValueError(f"bake_lightmap: gutter {gutter} outside [0, {abi.LIGHTMAP_MAX_GUTTER}]")
+        d = self._lightmap_desc("bake_lightmap", width, height, first_triangle, num_triangles, seed, seed_stride, offset, device)
+        st, count = abi.RenderStats(), C.c_size_t(0)
+        o = C.byref(opts) if opts is not None else None
+        f = None
+        if filter is not None:
+            if not 2 <= len(filter) - 1 <= 3:
+                raise ValueError("bake_lightmap: filter is (iterations, sigma_position, sigma_normal[, sigma_color])")
+            f = C.byref(self._lightmap_filter("bake_lightmap", filter[0], filter[1], filter[2], filter[3] if len(filter) > 3 else 0.0, False))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            img = torch.empty((d.height, d.width, 4), dtype=torch.float32, device=dev)
+            smap = torch.empty((d.height, d.width), dtype=torch.int32, device=dev) if sample_map else None
+            torch.cuda.current_stream(dev).synchronize()              # (the allocations)
+            self._check(lib().hj_bake_lightmap_adaptive(self._h, C.byref(d), C.byref(a), gutter, f, o, img.data_ptr(),
+                                                        smap.data_ptr() if sample_map else None, C.byref(count), C.byref(st)))
+        else:
+            img = np.zeros((d.height, d.width, 4), np.float32)
+            smap = np.zeros((d.height, d.width), np.uint32) if sample_map else None
+            self._check(lib().hj_bake_lightmap_adaptive(self._h, C.byref(d), C.byref(a), gutter, f, o, img.ctypes.data,
+                                                        smap.ctypes.data if sample_map else None, C.byref(count), C.byref(st)))
+        res = (img,) + ((smap,) if sample_map else ()) + ((dict(stats_dict(st), texels=count.value),) if stats else ())
+        return res if len(res) > 1 else img
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

@@ -781,6 +781,50 @@ int hj_bake_lightmap_filtered(hj_context* ctx, const hj_lightmap_desc* desc, uin
                               const hj_render_opts* opts /* NULL = defaults */, float* image, size_t* out_count /* may be NULL */,
                               hj_render_stats* stats /* may be NULL */);
 
+/* hj_trace_irradiance_adaptive (ABI 0.18): hj_trace_irradiance with the number of samples decided per point, on the device - the gather
+ * of a bake whose texels mostly converge in a handful of samples while penumbrae and corners need many.  points, opts, the origin
+ * domain and the normal rules are exactly hj_trace_irradiance's; adaptive is hj_trace_paths_adaptive's hj_adaptive_opts with its
+ * domain; no counterpart in the reference.
+ *   flags: HJ_GATHER_DEVICE_ARRAYS, HJ_GATHER_SPHERE.  HJ_GATHER_SH9 is refused.
+ *   Rounds.  As in hj_trace_paths_adaptive: round 0 gives every point spp_min samples; round r >= 1 gives every point that is still
+ *     active min(spp_step, spp_max - n_i) samples, the sample index k continuing at n_i (sample k of point i starts from
+ *     seedRng(seed_i + k) and draws its direction as in hj_trace_irradiance).  At most 64 rounds.
+ *   Running state per point, float32, from +0, in ascending k, uncontracted, continued from round to round and never re-associated:
+ *     R, G, B, S1, S2 exactly as hj_trace_paths_adaptive gives them (Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b); the number of
+ *     samples whose first segment hit something (first-hit t > 0); the minimum (fminf) of those t, starting from +inf.
+ *   Stop rule: hj_trace_paths_adaptive's, evaluated after each round with m = n_i - one text serves both queries.  The note on its
+ *     bias holds here as there: a point stops more readily while its samples happen to be dark and alike, so a texel in a penumbra
+ *     that has seen no light yet may stop dark; spp_min and floor bound that, rel_error = 0 removes it.
+ *   out: n x 8 floats in hj_trace_irradiance's layout with [3] = (float)n_i.  Record i is bit for bit what hj_trace_irradiance returns
+ *     for point i alone with spp = n_i and the same flags.  It depends on point i, adaptive, flags, opts and the scene alone: not on
+ *     HJ_PATHS_WGS, HJ_PATHS_POOL or HJ_PATHS_CHUNK, nor on the other points of the call.
+ *   moments (may be NULL): n x 4 words - S1, S2, the sem2 of the last evaluation, n_i as uint32 bits.
+ *   stats (may be NULL): as hj_trace_paths_adaptive's - paths = the sum of n_i, bounce_rounds = adaptive rounds run, batches =
+ *     launches of the path kernel, the walk's counts summed over all launches, total_ms; every other field 0.
+ * Beside hj_trace_paths_adaptive's buffers the context keeps 8 bytes per point (hit count, nearest hit).  One synchronisation per round.
+ * HJ_ERR_INVALID, checked before anything else and without a device, in hj_trace_irradiance's order: null points or out with n > 0,
+ *   unknown flag bits, HJ_GATHER_SH9; then, where hj_trace_irradiance checks spp, the adaptive refusals of hj_trace_paths_adaptive in
+ *   its order (null adaptive opts ... more than 64 rounds); n above 2^31 - 1; misaligned device arrays (moments included); the
+ *   refusals of opts; a bad normal in host arrays.  The null context, HJ_ERR_STATE and n == 0 (HJ_OK) as in hj_trace_irradiance.  A
+ *   refused call writes nothing. */
+int hj_trace_irradiance_adaptive(hj_context* ctx, const float* points, size_t n, const hj_adaptive_opts* adaptive, const hj_render_opts* opts /* NULL = defaults */,
+                                 uint32_t flags, float* out, float* moments /* may be NULL */, hj_render_stats* stats /* may be NULL */);
+
+/* hj_bake_lightmap_adaptive (ABI 0.18): hj_bake_lightmap_filtered with step 2 replaced by hj_trace_irradiance_adaptive (hemisphere
+ * mode, device arrays) over the context's own point buffer, so that a texel gets the samples its own variance asks for.
+ *   3. scale is per texel: a texel with a record is (sum.r * s, sum.g * s, sum.b * s, 1.0f) with s = 3.14159274f / (float)n_i, one
+ *      correctly rounded float32 division - the value hj_bake_lightmap computes when n_i == spp.
+ *   sample_map (may be NULL): width * height uint32 words, n_i for a texel with a record and 0 elsewhere (the gutter included) - a
+ *     host array, or with HJ_LIGHTMAP_DEVICE_ARRAYS a 16-byte-aligned device pointer, as image is.
+ *   The filter and the dilation are hj_bake_lightmap_filtered's, unchanged.  stats (may be NULL): the adaptive gather's.
+ * With spp_min == spp_max == spp (>= 2) the image, *out_count and every statistic but total_ms and bounce_rounds (1 here: the rounds
+ * run) are bit for bit hj_bake_lightmap_filtered's at that spp.
+ * HJ_ERR_INVALID: hj_bake_lightmap_filtered's refusals in its order, with the adaptive refusals of hj_trace_paths_adaptive in the
+ *   place of spp's and a misaligned device sample map behind the misaligned device image.  A refused call writes nothing. */
+int hj_bake_lightmap_adaptive(hj_context* ctx, const hj_lightmap_desc* desc, const hj_adaptive_opts* adaptive, uint32_t gutter,
+                              const hj_lightmap_filter* filter /* NULL = none */, const hj_render_opts* opts /* NULL = defaults */, float* image,
+                              uint32_t* sample_map /* may be NULL */, size_t* out_count /* may be NULL */, hj_render_stats* stats /* may be NULL */);
+
 /* ------------------------------------------------------------------- probes */
 
 /* Function-level probes used by the parity tests (no counterpart in the

@@ -20,6 +20,12 @@ tree of that scene is built on the device.
              the bytes an iteration must move - 48 B read and 16 B written per guided texel - and the multiple of their time at
              6.3 TB/s that the step takes.
 
+    adaptive (--adaptive: this section alone, on the cbox scene and the mesh) Renderer.bake_lightmap(device=True) at --bake-size:
+             the fixed bake at 16 and 64 spp beside the adaptive bake at 4 / +4 / 64 (--rel-error, floor 0.01), and beside the fixed
+             bake at the adaptive bake's own mean sample count (rounded): the same total samples without the between-round work
+             (accumulate + compaction + one synchronisation a round).  Beside the times the samples taken, the rounds run and the
+             RMSE over the owned texels against a bake at --truth-spp.
+
 --pairs interleaved runs after a warm-up of each; a run's time is a host clock between two device synchronisations; ms, lowest ...
 highest.  No threshold is set: the table belongs in DESIGN.md ("Light-map baking"), the raw output in profiles/ (--out).  Run under
 its own time limit:
@@ -46,6 +52,9 @@ ap.add_argument("--spp", type=int, default=16)
 ap.add_argument("--gutter", type=int, default=2)
 ap.add_argument("--pairs", type=int, default=5)
 ap.add_argument("--filter", action="store_true", help="the filter section alone")
+ap.add_argument("--adaptive", action="store_true", help="the adaptive section alone")
+ap.add_argument("--rel-error", type=float, default=0.05)
+ap.add_argument("--truth-spp", type=int, default=4096)
 ap.add_argument("--out", default="", help="append the run to this file")
 a = ap.parse_args()
 
@@ -145,6 +154,32 @@ def filter_section(name, cs, forms):
         say(f"    5 iterations (default) / gather at 16 spp, best of each: {secs['default 5'] / secs['gather 16 spp']:.3f}")
 
 
+def adaptive_section(name):
+    S, kw = a.bake_size, dict(gutter=0, offset=1e-3, device=True)
+    ad = dict(spp_min=4, spp_step=4, spp_max=64, rel_error=a.rel_error, floor=0.01)
+    _, smap, st = r.bake_lightmap(S, S, None, adaptive=ad, sample_map=True, stats=True, seed=1 << 30, seed_stride=64, **kw)
+    count, total, rounds = st["texels"], st["paths"], st["bounce_rounds"]
+    mean = max(1, int(round(total / max(count, 1))))
+    runs = {"fixed 16 spp": lambda: r.bake_lightmap(S, S, 16, seed=1 << 30, seed_stride=64, **kw),
+            "fixed 64 spp": lambda: r.bake_lightmap(S, S, 64, seed=1 << 30, seed_stride=64, **kw),
+            "adaptive 4 / +4 / 64": lambda: r.bake_lightmap(S, S, None, adaptive=ad, seed=1 << 30, seed_stride=64, **kw),
+            f"fixed {mean} spp (the adaptive bake's mean)": lambda: r.bake_lightmap(S, S, mean, seed=1 << 30, seed_stride=64, **kw)}
+    secs = interleaved(runs)
+    truth = r.bake_lightmap(S, S, a.truth_spp, seed=1, seed_stride=a.truth_spp, **kw)
+    owned = truth[:, :, 3] == 1
+    say(f"{name}: {S} x {S}, {count} texels, rel_error {a.rel_error}: {a.pairs} interleaved runs, lowest ... highest; RMSE over the owned texels against {a.truth_spp} spp")
+    for k, f in runs.items():
+        img = f()
+        rmse = float(torch.sqrt(torch.mean((img[owned][:, 0:3].double() - truth[owned][:, 0:3].double()) ** 2)))
+        spp = {"fixed 16 spp": 16 * count, "fixed 64 spp": 64 * count, "adaptive 4 / +4 / 64": total}.get(k, mean * count)
+        say(f"    {k}: {spread(secs[k])}; {spp} samples; rounds {rounds if k.startswith('adaptive') else 1}; RMSE {rmse:.5f}")
+    hist = torch.bincount(smap.reshape(-1).long(), minlength=65)[4::4].tolist()
+    say(f"    adaptive: samples a texel 4, 8, ... 64: {hist}")
+    ka, km = "adaptive 4 / +4 / 64", f"fixed {mean} spp (the adaptive bake's mean)"
+    say(f"    between-round work: adaptive - fixed at the mean, best of each: {(min(secs[ka]) - min(secs[km])) * 1e3:.2f} ms = "
+        f"{(min(secs[ka]) - min(secs[km])) / min(secs[ka]):.3f} of the adaptive call ({total} against {mean * count} samples)")
+
+
 import lightmap_scenes  # noqa: E402
 
 scenes = {"cbox": lightmap_scenes.bake_scene()}
@@ -168,6 +203,11 @@ if a.filter:
     for name, cs in scenes.items():
         upload(cs)
         filter_section(name, cs, forms)
+    scenes = {}
+elif a.adaptive:
+    for name, cs in scenes.items():
+        upload(cs)
+        adaptive_section(name)
     scenes = {}
 else:
     mixed, _ = with_grid_atlas(synth, chart=True)
