@@ -2,7 +2,10 @@
 float32 - vectorised over texels, one triangle at a time in ascending index, every operation on np.float32 arrays in the written
 order.  normalize is the oracle's (oracle.num_batch, the numeric contract's: test_num_gpu.py pins the device's to it).  Shares no
 text with the kernels: the closed box of the predicate is evaluated first, on the texel centres themselves, so no integer bounding
-box exists here."""
+box exists here.  coverage_owner_batched is the same predicate for meshes of 10^5 to 10^6 triangles: the centres are strictly
+increasing, so np.searchsorted finds the centres inside a closed interval exactly, by the same comparisons; the (triangle, texel)
+pairs of all small triangles are evaluated in one batch, and the owner is the minimum index (np.minimum.at).
+test_lightmap_scale_host.py pins it to coverage_owner word for word."""
 import numpy as np
 
 U, F = np.uint32, np.float32
@@ -59,6 +62,43 @@ def coverage_owner(triangles, vertices, W, H, first=0, num=0):
     return owner
 
 
+def coverage_owner_batched(triangles, vertices, W, H, first=0, num=0, small=64, chunk=1 << 16):
+    """coverage_owner vectorised over triangles.  A triangle's candidates are the centres pu[x0:x1] x pv[y0:y1] inside its closed
+    box (searchsorted: 'left' is the first centre >= min, 'right' one past the last centre <= max).  Triangles with at most `small`
+    candidates: every (triangle, texel) pair at once, `chunk` triangles at a time, in edges' expressions; the others one by one
+    through covers.  The minimum commutes, so the order of the two parts does not show."""
+    tri = np.asarray(triangles, np.int64).reshape(-1, 3)
+    vt = np.asarray(vertices, F).reshape(-1, 8)
+    last = len(tri) if num == 0 else first + num
+    uv = vt[tri[first:last]][:, :, [3, 7]]                               # (m, 3, 2)
+    finite = np.isfinite(uv).all(axis=(1, 2))
+    uv = np.where(finite[:, None, None], uv, F(0))
+    pu, pv = centres(W), centres(H)
+    x0, x1 = np.searchsorted(pu, uv[:, :, 0].min(axis=1), "left"), np.searchsorted(pu, uv[:, :, 0].max(axis=1), "right")
+    y0, y1 = np.searchsorted(pv, uv[:, :, 1].min(axis=1), "left"), np.searchsorted(pv, uv[:, :, 1].max(axis=1), "right")
+    nx, ny = np.where(finite, x1 - x0, 0), np.where(finite, y1 - y0, 0)
+    cand = nx * ny
+    owner = np.full(H * W, NONE, U)
+    few = np.flatnonzero((cand > 0) & (cand <= small))
+    for c0 in range(0, len(few), chunk):
+        j = few[c0:c0 + chunk]
+        rep = np.repeat(j, cand[j])                                      # the triangle of each pair
+        k = np.arange(len(rep)) - np.repeat(np.cumsum(cand[j]) - cand[j], cand[j])
+        ry = k // nx[rep]
+        xs, ys = x0[rep] + (k - ry * nx[rep]), y0[rep] + ry
+        a, b, c = ((uv[rep, v, 0], uv[rep, v, 1]) for v in range(3))
+        with np.errstate(all="ignore"):
+            e0, e1, e2, s = edges(a, b, c, pu[xs], pv[ys])
+            mask = (((e0 >= 0) & (e1 >= 0) & (e2 >= 0)) | ((e0 <= 0) & (e1 <= 0) & (e2 <= 0))) & (s != 0)
+        np.minimum.at(owner, (ys * W + xs)[mask], (first + rep[mask]).astype(U))
+    owner = owner.reshape(H, W)
+    for j in np.flatnonzero(cand > small):
+        ys, xs, mask = covers(uv[j], W, H)
+        sub = owner[np.ix_(ys, xs)]
+        owner[np.ix_(ys, xs)] = np.where(mask, np.minimum(sub, U(first + j)), sub)
+    return owner
+
+
 def normalize3(v):
     from oracle import hj_oracle as oracle
     if not len(v):
@@ -66,11 +106,11 @@ def normalize3(v):
     return oracle.num_batch("normalize3", np.ascontiguousarray(v, F).view(U))[:, 0:3].copy().view(F)
 
 
-def texels(triangles, vertices, W, H, first=0, num=0, seed=0, seed_stride=1, offset=0.0):
-    """-> (points (count, 8) float32 in ascending texel index, owner (H, W) uint32)"""
+def texels(triangles, vertices, W, H, first=0, num=0, seed=0, seed_stride=1, offset=0.0, batched=False):
+    """-> (points (count, 8) float32 in ascending texel index, owner (H, W) uint32); batched: coverage by coverage_owner_batched"""
     tri = np.asarray(triangles, np.int64).reshape(-1, 3)
     vt = np.asarray(vertices, F).reshape(-1, 8)
-    owner = coverage_owner(tri, vt, W, H, first, num)
+    owner = (coverage_owner_batched if batched else coverage_owner)(tri, vt, W, H, first, num)
     t = np.flatnonzero(owner.ravel() != NONE)
     o = owner.ravel()[t].astype(np.int64)
     A, B, C = (vt[tri[o, k]] if len(o) else np.zeros((0, 8), F) for k in range(3))
