@@ -35,6 +35,9 @@ LIGHTMAP_DEVICE_ARRAYS = 1        # hj_lightmap_desc flag
 LIGHTMAP_MAX_GUTTER = 64          # hj_bake_lightmap: dilation passes a call
 LIGHTMAP_NONE = 0xFFFFFFFF        # owner word of a texel nobody owns
 LIGHTMAP_FILTER_MAX_ITERATIONS = 8  # hj_lightmap_filter: iteration i uses the step 1 << i
+PROBES_DEVICE_ARRAYS = 1          # hj_probe_desc flag
+PROBE_WORDS = 28                  # words of a probe record: 27 SH coefficients of the irradiance, the validity weight
+PROBE_MAX_COUNT, PROBE_MAX_PROBES = 1024, 1 << 22   # probes along an axis, probes of a volume
 # hj_debug_num: enum hj_num_op in its order, the record sizes and the cap
 NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "dot3", "cross3", "normalize3", "reflect3", "rng_seed",
            "rng_uint", "rng_float", "rand_cos_hemisphere", "rand_uniform_sphere", "rand_barycentric")
@@ -182,6 +185,12 @@ class LightmapDesc(C.Structure):
 class LightmapFilter(C.Structure):
     """hj_lightmap_filter (ABI 0.17): the iterations and the edge stops of hj_filter_lightmap / hj_bake_lightmap_filtered."""
     _fields_ = [("iterations", u32), ("sigma_position", f32), ("sigma_normal", f32), ("sigma_color", f32), ("flags", u32)]
+
+
+class ProbeDesc(C.Structure):
+    """hj_probe_desc (ABI 0.19): the grid, the seeds and the validity rule of hj_probe_points / hj_bake_probes / hj_sample_probes."""
+    _fields_ = [("origin", f32 * 3), ("spacing", f32 * 3), ("count", u32 * 3), ("seed", u32), ("seed_stride", u32), ("min_distance", f32),
+                ("flags", u32)]
 
 
 class RenderStats(C.Structure):

@@ -13,6 +13,7 @@
 #include "hj_internal.h"
 #include <type_traits>
 #include "../kernels/hj_stages.h"
+#include "../kernels/hj_sh9.h"
 #include "query_round.h"
 
 #pragma clang fp contract(off)
@@ -101,24 +102,10 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(H
 #undef HJ_QUERY_TOP_UP
 }
 
-// The real spherical-harmonic basis of bands 0..2 at d (not renormalised), in the order and with the constants and operation
-// order of include/hijiki_hip.h: 1, y, z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2
-HJ_DEV void gq_sh9(v3 d, float (&Y)[9]) {
-  constexpr float c0 = 0x1.20dd76p-2f, c1 = 0x1.f45438p-2f, c2 = 0x1.17b142p+0f, c3 = 0x1.42f602p-2f, c4 = 0x1.17b142p-1f;
-  Y[0] = c0;
-  Y[1] = c1 * d.y;
-  Y[2] = c1 * d.z;
-  Y[3] = c1 * d.x;
-  Y[4] = c2 * (d.x * d.y);
-  Y[5] = c2 * (d.y * d.z);
-  Y[6] = c3 * ((3.0f * d.z) * d.z - 1.0f);
-  Y[7] = c2 * (d.x * d.z);
-  Y[8] = c4 * (d.x * d.x - d.y * d.y);
-}
-
 // out: 2 float4 per point, 9 with SH9 - (the float32 sum of the point's spp sample radiances in ascending k, starting from +0;
 // (float)spp), (the samples whose first segment hit: first-hit t > 0; the smallest such t or +inf; 0; 0), then with SH9 the 27 sums
-// over ascending k of Y_j(d_k) * L_k[c] at word 8 + 3 j + c - one multiply, then one add - and a zero.  d_k: gq_direction<true> again.
+// over ascending k of Y_j(d_k) * L_k[c] at word 8 + 3 j + c - one multiply, then one add - and a zero.  d_k: gq_direction<true> again;
+// Y_j: kernels/hj_sh9.h's basis, which the probe look-up shares.
 template <bool SH9>
 __global__ __launch_bounds__(kBlockThreads) void k_gq_resolve(const float4* __restrict__ smp_rgb, const float4* __restrict__ smp_nd,
                                                               const float4* __restrict__ points, uint32_t spp, uint32_t n, float4* __restrict__ out) {
@@ -146,7 +133,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_gq_resolve(const float4* __re
     if (SH9) {
       uint32_t rng;
       float Y[9];
-      gq_sh9(gq_direction<true>(pa, pb, k, rng), Y);
+      sh9_basis(gq_direction<true>(pa, pb, k, rng), Y);
 #pragma unroll
       for (uint32_t j = 0; j < 9u; j++) {
         sh[3 * j] += Y[j] * v.x;

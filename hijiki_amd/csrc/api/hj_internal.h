@@ -47,6 +47,11 @@
 //                         with hj_trace_irradiance_adaptive as its gather and api/gather_adaptive.hip's scatter
 //   api/lightmap_filter.hip hj_filter_lightmap: the edge-avoiding a-trous filter over an atlas, and lightmap_filter_check /
 //                         lightmap_filter_enqueue (below) for the bake (includes kernels/hj_lightmap_filter.h and hj_num.h alone)
+//   api/probe_volume.hip  hj_probe_points, hj_bake_probes, hj_sample_probes: a grid of probes as gather points, the sphere gather's SH
+//                         sums resolved to irradiance coefficients with a validity weight (k_pv_points, k_pv_resolve; the gather is
+//                         hj_trace_irradiance's, entered through that entry point with device arrays), and the trilinear look-up of a
+//                         volume at caller-given points (includes kernels/hj_probes.h; beside it hj_sh9.h - the SH basis, which
+//                         api/gather_query.hip includes too - and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -404,6 +409,11 @@ struct hj_context {
   // hj_bake_lightmap_adaptive: sample_map, the staging of a host-side sample map (a word per texel)
   struct Lightmap { hjapi::DevBuf owner, masks, counts, points, records, image[2], guide, sample_map; } lightmap;
 
+  // hj_probe_points / hj_bake_probes / hj_sample_probes (api/probe_volume.hip): the bake's gather points (32 bytes a probe) and the
+  // gather's SH records (144 bytes a probe); staging of a host-side volume (112 bytes a probe), of host-side sample points (32 bytes
+  // a point) and of their results (16 bytes a point).  Grown on demand, reused by every call, freed with the context.
+  struct Probes { hjapi::DevBuf points, records, volume, in_points, out; } probes;
+
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
   hjapi::Tuning tuning;
@@ -451,8 +461,10 @@ void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, 
 //   query_render_opts  opts (NULL: the defaults) into o and the refusals of the path-type queries: max_bounces, use_bvh, HJ_RENDER_* bits
 //   query_gate         every query, behind its argument checks: a null context (HJ_ERR_DEVICE without a HIP device, HJ_ERR_INVALID
 //                      otherwise), an asynchronous frame in flight, frames in the pipeline, no scene
+//   context_gate       query_gate without its last check, for the calls that need a context but no scene
 int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opts, hj_render_opts& o);
 int query_gate(hj_context* ctx, const char* fn);
+int context_gate(hj_context* ctx, const char* fn);
 // The light-map filter for both of its entry points (api/lightmap_filter.hip):
 //   lightmap_filter_check    what both refuse of a filter, without a device: unknown flag bits, iterations, sigmas
 //   lightmap_filter_enqueue  guide from the `count` device points, then f.iterations iterations from img[cur] into img[cur ^ 1], cur

@@ -147,13 +147,18 @@ int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opt
 
 // A process without a HIP device cannot hold a context: a call that is otherwise valid gets HJ_ERR_DEVICE there, like every entry
 // point that computes.
-int query_gate(hj_context* ctx, const char* fn) {
+int context_gate(hj_context* ctx, const char* fn) {
   if (!ctx) {
     if (hj_device_count() == 0) return set_error(nullptr, HJ_ERR_DEVICE, "%s: no HIP device available; this library has no CPU fallback", fn);
     return set_error(nullptr, HJ_ERR_INVALID, "%s: null context", fn);
   }
   HJ_NOT_BUSY_IN(ctx, fn);
   HJ_NOT_PIPELINED_IN(ctx, fn);
+  return HJ_OK;
+}
+
+int query_gate(hj_context* ctx, const char* fn) {
+  HJ_TRY(context_gate(ctx, fn));
   if (!ctx->have_scene) return set_error(ctx, HJ_ERR_STATE, "%s: no scene has been uploaded", fn);
   return HJ_OK;
 }

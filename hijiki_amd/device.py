@@ -27,7 +27,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_debug_env_distribution", "hj_refit_bvh_device", "hj_scene_update_shapes", "hj_debug_scene_tree", "hj_debug_num",
            "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
            "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap", "hj_filter_lightmap",
-           "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive")
+           "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive", "hj_probe_points", "hj_bake_probes",
+           "hj_sample_probes")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -99,6 +100,9 @@ def lib():
                                                    C.POINTER(abi.RenderStats)]  # (host or device pointers)
         L.hj_bake_lightmap_adaptive.argtypes = [vp, C.POINTER(abi.LightmapDesc), C.POINTER(abi.AdaptiveOpts), C.c_uint32, C.POINTER(abi.LightmapFilter),
                                                 C.POINTER(abi.RenderOpts), vp, vp, C.POINTER(C.c_size_t), C.POINTER(abi.RenderStats)]
+        L.hj_probe_points.argtypes = [vp, C.POINTER(abi.ProbeDesc), vp]      # (host or device pointers)
+        L.hj_bake_probes.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.c_uint32, C.POINTER(abi.RenderOpts), vp, C.POINTER(abi.RenderStats)]
+        L.hj_sample_probes.argtypes = [vp, C.POINTER(abi.ProbeDesc), vp, vp, C.c_size_t, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -825,6 +829,118 @@ class Renderer:
                                                         smap.ctypes.data if sample_map else None, C.byref(count), C.byref(st)))
         res = (img,) + ((smap,) if sample_map else ()) + ((dict(stats_dict(st), texels=count.value),) if stats else ())
         return res if len(res) > 1 else img
+
+    @staticmethod
+    def _probe_desc(what, origin, spacing, count, seed=0, seed_stride=1, min_distance=0.0, device=False):
+        """The desc of the probe calls, checked before any call.  count is (nx, ny, nz), as origin and spacing are (x, y, z)."""
+        origin, spacing = np.asarray(origin, np.float32).reshape(-1), np.asarray(spacing, np.float32).reshape(-1)
+        count = [int(c) for c in count]
+        if len(origin) != 3 or len(spacing) != 3 or len(count) != 3:
+            raise ValueError(f"{what}: origin, spacing and count have three components each")
+        if not (all(1 <= c <= abi.PROBE_MAX_COUNT for c in count) and count[0] * count[1] * count[2] <= abi.PROBE_MAX_PROBES):
+            raise ValueError(f"{what}: count {count}: 1 ... {abi.PROBE_MAX_COUNT} each and at most 2^22 probes")
+        if not np.isfinite(origin).all():
+            raise ValueError(f"{what}: origin {origin.tolist()} is not finite")
+        if not (np.isfinite(spacing).all() and (spacing > 0).all()):
+            raise ValueError(f"{what}: spacing {spacing.tolist()}: finite and > 0 is needed")
+        min_distance = np.float32(min_distance)
+        if not (np.isfinite(min_distance) and min_distance >= 0):
+            raise ValueError(f"{what}: min_distance {min_distance}: finite and >= 0 is needed")
+        for name, v in (("seed", seed), ("seed_stride", seed_stride)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{what}: {name} {v} is no uint32")
+        f3, u3 = C.c_float * 3, C.c_uint32 * 3
+        return abi.ProbeDesc(f3(*origin.tolist()), f3(*spacing.tolist()), u3(*count), int(seed), int(seed_stride), float(min_distance),
+                             abi.PROBES_DEVICE_ARRAYS if device else 0)
+
+    def probe_points(self, origin, spacing, count, seed=0, seed_stride=1, device=False):
+        """hj_probe_points: the gather points of a grid of count = (nx, ny, nz) probes, probe (x, y, z) at origin + (x, y, z) * spacing
+        -> (nx * ny * nz, 8) float32 in ascending p = (z * ny + y) * nx + x: position, a zero normal, the seed seed + p * seed_stride
+        as the bits of word 6, p as the bits of word 7 - a `points` argument of `trace_irradiance(sphere=True)` as it stands.  No
+        scene is needed.  device=True: a torch tensor on the renderer's GPU, written in place on the device; torch's current stream is
+        synchronised first."""
+        d = self._probe_desc("probe_points", origin, spacing, count, seed, seed_stride, 0.0, device)
+        n = d.count[0] * d.count[1] * d.count[2]
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            pts = torch.empty((n, 8), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            self._check(lib().hj_probe_points(self._h, C.byref(d), pts.data_ptr()))
+            return pts
+        pts = np.zeros((n, 8), np.float32)
+        self._check(lib().hj_probe_points(self._h, C.byref(d), pts.ctypes.data))
+        return pts
+
+    def bake_probes(self, origin, spacing, count, spp, min_distance=0.0, seed=0, seed_stride=1, opts=None, stats=False, device=False):
+        """hj_bake_probes: an irradiance probe volume of the uploaded scene, baked on the device - `probe_points`, the sphere gather of
+        `trace_irradiance(sphere=True, sh9=True)` at `spp` samples over them, and the SH sums resolved to irradiance coefficients
+        -> (nz, ny, nx, 28) float32: word 3 j + c of a probe is the coefficient of the j-th real spherical harmonic (bands 0..2, the
+        gather's order) of the irradiance as a function of the surface normal, channel c; word 27 is 1 when no gather ray hit
+        anything nearer than `min_distance`, else 0 (a probe inside or against a wall).  opts as in `trace_irradiance`.  device=True: a
+        torch tensor on the renderer's GPU.  stats=True: returns (volume, the gather's statistics dict).  `sample_probes` reads it."""
+        spp = int(spp)
+        if not 1 <= spp <= 65536:
+            raise ValueError(f"bake_probes: spp {spp} outside [1, 65536]")
+        d = self._probe_desc("bake_probes", origin, spacing, count, seed, seed_stride, min_distance, device)
+        shape = (d.count[2], d.count[1], d.count[0], abi.PROBE_WORDS)
+        st = abi.RenderStats()
+        o = C.byref(opts) if opts is not None else None
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            vol = torch.empty(shape, dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            self._check(lib().hj_bake_probes(self._h, C.byref(d), spp, o, vol.data_ptr(), C.byref(st)))
+        else:
+            vol = np.zeros(shape, np.float32)
+            self._check(lib().hj_bake_probes(self._h, C.byref(d), spp, o, vol.ctypes.data, C.byref(st)))
+        return (vol, stats_dict(st)) if stats else vol
+
+    def sample_probes(self, volume, origin, spacing, points, normals=None, device=None):
+        """hj_sample_probes: the irradiance at points from a (nz, ny, nx, 28) probe volume (`bake_probes`; count comes from its shape)
+        whose probe (0, 0, 0) sits at `origin`, `spacing` apart -> (n, 4) float32: the irradiance (r, g, b) on a surface with the
+        point's normal, trilinearly interpolated between the eight probes around the position with each probe's validity as a further
+        weight, and that weight sum (0, and a black result, where no valid probe stands near).  Positions outside the volume take the
+        nearest face's value.  points: (n, 8) in the gather's layout (position, normal of any length but zero, two ignored words), or
+        (n, 3) positions with `normals` (n, 3).  numpy arrays give a numpy array: positions and normals must be finite.  Contiguous
+        float32 torch tensors on the renderer's GPU (volume and points alike; device=None decides by the volume's type) are read in
+        place and give a tensor on that GPU - there nothing in `points` can make the call fault, a NaN just propagates; torch's
+        current stream is synchronised first.  No scene is needed."""
+        on_gpu = type(volume).__module__.split(".")[0] == "torch" if device is None else bool(device)
+        if volume.ndim != 4 or volume.shape[3] != abi.PROBE_WORDS:
+            raise ValueError(f"sample_probes: a volume of (nz, ny, nx, {abi.PROBE_WORDS}) is needed (got {tuple(volume.shape)})")
+        count = (int(volume.shape[2]), int(volume.shape[1]), int(volume.shape[0]))
+        d = self._probe_desc("sample_probes", origin, spacing, count, device=on_gpu)
+        if normals is not None:
+            if points.ndim != 2 or points.shape[1] != 3 or tuple(normals.shape) != tuple(points.shape):
+                raise ValueError("sample_probes: with normals, points and normals are (n, 3) each")
+        elif points.ndim != 2 or points.shape[1] != 8:
+            raise ValueError(f"sample_probes: points of (n, 8), or (n, 3) with normals, are needed (got {tuple(points.shape)})")
+        if on_gpu:
+            import torch
+            for name, t in (("volume", volume), ("points", points)) + ((("normals", normals),) if normals is not None else ()):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"sample_probes: {name} must be a contiguous float32 tensor on cuda:{self.device}")
+            if normals is not None:
+                points = torch.cat([points, normals, torch.zeros((points.shape[0], 2), dtype=torch.float32, device=points.device)], 1)
+            n = int(points.shape[0])
+            out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()    # (the allocations and whatever wrote the tensors)
+            self._check(lib().hj_sample_probes(self._h, C.byref(d), volume.data_ptr(), points.data_ptr() if n else None, n,
+                                               out.data_ptr() if n else None))
+            return out
+        vol = np.ascontiguousarray(volume, np.float32)
+        if normals is not None:
+            points = np.concatenate([np.asarray(points, np.float32), np.asarray(normals, np.float32), np.zeros((len(points), 2), np.float32)], 1)
+        pts = np.ascontiguousarray(points, np.float32)
+        bad = ~np.isfinite(pts[:, 0:6]).all(axis=1) | (pts[:, 3:6] == 0).all(axis=1)
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"sample_probes: point {i} ({pts[i, 0:6].tolist()}): finite positions and finite normals that are not all zero are needed")
+        out = np.zeros((len(pts), 4), np.float32)
+        self._check(lib().hj_sample_probes(self._h, C.byref(d), vol.ctypes.data, pts.ctypes.data, len(pts), out.ctypes.data))
+        return out
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

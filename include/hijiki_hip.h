@@ -825,6 +825,75 @@ int hj_bake_lightmap_adaptive(hj_context* ctx, const hj_lightmap_desc* desc, con
                               const hj_lightmap_filter* filter /* NULL = none */, const hj_render_opts* opts /* NULL = defaults */, float* image,
                               uint32_t* sample_map /* may be NULL */, size_t* out_count /* may be NULL */, hj_render_stats* stats /* may be NULL */);
 
+/* Irradiance probe volumes (ABI 0.19): a regular grid of probes, each the order-2 spherical-harmonic coefficients of the irradiance at
+ * its position as a function of the surface normal, baked from the uploaded scene on the device, and the look-up of such a volume at
+ * caller-given points - lighting for what a light map cannot cover: moving objects, meshes without UVs, volumetric effects.  No
+ * counterpart in the reference.  Every arithmetic operation below is float32, one rounding per operation, no contraction; vector
+ * operations are the numeric contract's (normalize of kernels/hj_num.h: DESIGN.md 3); division is IEEE `/`.
+ *   A volume has n = count[0] * count[1] * count[2] probes.  Probe (x, y, z) has the index p = (z * count[1] + y) * count[0] + x and
+ *   sits at origin[a] + (float)i_a * spacing[a] in axis a (one product, then one sum).  A probe record is HJ_PROBE_WORDS = 28 words:
+ *   [3 j + c] the coefficient of Y_j (hj_trace_irradiance's basis, in its order) for channel c, [27] the validity weight.
+ *
+ * hj_probe_points: the n gather points of desc in ascending p, 8 words each - 0-2 the position, 3-5 +0 (sphere mode never reads the
+ *   normal), 6 the seed seed + p * seed_stride (uint32 wrap-around) as bits, 7 p as uint32 bits: a valid `points` argument of
+ *   hj_trace_irradiance as it stands, as hj_lightmap_texels' output is.  Needs a context but no scene.
+ *
+ * hj_bake_probes: from the uploaded scene to the volume without the points or the gather's records leaving the device.
+ *   1. The points of desc, as hj_probe_points emits them, into a buffer the context keeps.
+ *   2. hj_trace_irradiance over them with HJ_GATHER_SPHERE | HJ_GATHER_SH9 (device arrays), spp samples each, with opts.
+ *   3. s = 12.5663706f / (float)spp - the Monte-Carlo weight of a uniform sphere sample, 4 pi / spp.  Word 3 j + c of probe p is
+ *      (sum[8 + 3 j + c] * s) * A_band(j) with A_0 = 3.14159274f (j = 0), A_1 = 2.09439516f (j = 1 ... 3), A_2 = 0.785398185f
+ *      (j = 4 ... 8): pi, 2 pi / 3, pi / 4, the convolution with the clamped cosine lobe (Ramamoorthi and Hanrahan 2001).  Word 27 is
+ *      1.0f when word 5 of the gather's record - the nearest first hit, +inf if there is none - is >= min_distance, else 0.0f: a probe
+ *      that close to a surface most likely sits inside or behind it.
+ *   probes: n x 28 floats.  stats (may be NULL): the gather's.  spp and opts have hj_trace_irradiance's domain and refusals, and the
+ *   origin domain is the gather's: the bit-for-bit claim holds for probes inside the scene's root box joined with the camera.  The
+ *   result depends on the scene, desc, spp and opts alone.  The context keeps 176 bytes per probe (points and records).
+ *
+ * hj_sample_probes: irradiance at n points from the eight probes around each.  points: n x 8 words in the gather's layout - words 0-2
+ *   the position, 3-5 the normal (any length but zero; normalised here), 6-7 ignored.  Needs a context but no scene.
+ *   Per axis a, with m = count[a] - 1:
+ *       g = (pos[a] - origin[a]) / spacing[a];   g = (g >= 0.0f) ? g : 0.0f  (a NaN becomes 0);   g = (g <= (float)m) ? g : (float)m;
+ *       i0 = min((uint32_t)g, m > 0 ? m - 1 : 0);   f = g - (float)i0;   i1 = min(i0 + 1, m);   the weights are 1.0f - f of i0 and f of i1.
+ *   The eight corners in the order dz outer, dy, dx inner (d = 0: i0, d = 1: i1), probe q each:
+ *       w = ((wx * wy) * wz) * probes[q][27];   a corner with w == 0 is skipped - an invalid probe, the far plane at f == 0 and a
+ *       single-plane axis contribute nothing, and a NaN coefficient behind a zero weight cannot leak;
+ *       otherwise acc[k] = acc[k] + probes[q][k] * w for k = 0 ... 26, from +0, and wsum = wsum + w, from +0.
+ *   wsum == 0: out = (0, 0, 0, 0).  Otherwise c[k] = acc[k] / wsum, nn = normalize(normal), Y_j(nn) hj_trace_irradiance's basis with
+ *   its constants and operation order, E[c] = the sum over j = 0 ... 8, ascending, from +0, of c[3 j + c] * Y_j, and
+ *   out = (E[0], E[1], E[2], wsum): the irradiance on a surface with that normal, and how much valid weight stood behind it.
+ *   No index is formed from a value that has not been clamped: with device arrays nothing in `points` can make the call fault.  The
+ *   result depends on (desc, probes, points) alone, not on any launch shape.  Of desc the seeds and min_distance are not used.
+ *
+ * HJ_PROBES_DEVICE_ARRAYS (desc->flags): every array argument is a device pointer on the context's GPU, 16-byte aligned, read and
+ *   written in place on the context's stream; hj_probe_points and hj_sample_probes return after one synchronisation, hj_bake_probes
+ *   after the gather's and one more.  Without it they are host arrays, staged through buffers the context keeps (a volume whole, and
+ *   48 bytes per sample point); hj_sample_probes then checks before anything is written that every position and normal is finite
+ *   and that no normal is all zero - with device arrays that is the caller's contract, and a bad normal gives a NaN, not a fault.
+ * HJ_ERR_INVALID, checked before anything else and without a device (with a null context the text is in hj_last_error(NULL)), in
+ *   this order: a null desc or array argument (hj_sample_probes: only with n > 0); unknown flag bits; a count outside [1, 1024] or
+ *   a product above 2^22; a non-finite origin; a spacing that is not finite or not > 0; a min_distance that is negative or not
+ *   finite; then spp == 0 or above 65536; misaligned device arrays; the refusals of opts; n above 2^31 - 1; a bad position or normal
+ *   in host arrays.  A null context: HJ_ERR_DEVICE in a process without a HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: an
+ *   asynchronous frame in flight, frames submitted with HJ_RENDER_NO_DRAIN not yet drained, and for hj_bake_probes no scene.
+ *   hj_sample_probes with n == 0: HJ_OK, nothing touched.  A refused call writes nothing.
+ * Not here: no back-face or visibility (Chebyshev) weighting against light leaks - validity is the min_distance rule alone; no adaptive
+ *   probe bake (hj_trace_irradiance_adaptive refuses HJ_GATHER_SH9). */
+#define HJ_PROBES_DEVICE_ARRAYS 1u
+#define HJ_PROBE_WORDS 28u
+typedef struct hj_probe_desc {
+  float    origin[3];          /* probe (0,0,0); finite                                              */
+  float    spacing[3];         /* finite, > 0                                                        */
+  uint32_t count[3];           /* 1 ... 1024 each, product <= 2^22                                   */
+  uint32_t seed, seed_stride;  /* probe p gets seed + p * seed_stride (uint32 wrap-around)           */
+  float    min_distance;       /* finite, >= 0: a probe with a first hit nearer than this is invalid */
+  uint32_t flags;              /* HJ_PROBES_DEVICE_ARRAYS                                            */
+} hj_probe_desc;
+int hj_probe_points(hj_context* ctx, const hj_probe_desc* desc, float* points /* n x 8 */);
+int hj_bake_probes(hj_context* ctx, const hj_probe_desc* desc, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
+                   float* probes /* n x 28 */, hj_render_stats* stats /* may be NULL */);
+int hj_sample_probes(hj_context* ctx, const hj_probe_desc* desc, const float* probes, const float* points, size_t n, float* out /* n x 4 */);
+
 /* ------------------------------------------------------------------- probes */
 
 /* Function-level probes used by the parity tests (no counterpart in the
