@@ -36,8 +36,9 @@ def points(d):
     p = np.arange(nx * ny * nz, dtype=np.int64)
     idx = (p % nx, (p // nx) % ny, p // (nx * ny))
     out = np.zeros((len(p), 8), F)
-    for a in range(3):
-        out[:, a] = d["origin"][a] + idx[a].astype(F) * d["spacing"][a]
+    with np.errstate(over="ignore", invalid="ignore"):   # (a grid whose positions overflow: +-inf, as float32 gives them)
+        for a in range(3):
+            out[:, a] = d["origin"][a] + idx[a].astype(F) * d["spacing"][a]
     out.view(U)[:, 6] = ((d["seed"] + p * d["seed_stride"]) & 0xFFFFFFFF).astype(U)
     out.view(U)[:, 7] = p.astype(U)
     return out
@@ -68,21 +69,30 @@ def axis(pos, origin, spacing, count):
     return i0, i1, (F(1) - f).astype(F), f
 
 
-def sample(d, volume, pts):
-    """volume (nz, ny, nx, 28) or (n, 28), pts (n, 8) -> (n, 4) float32 as hj_sample_probes defines it"""
+def sample(d, volume, pts, detail=False):
+    """volume (nz, ny, nx, 28) or (n, 28), pts (n, 8) -> (n, 4) float32 as hj_sample_probes defines it.  volume may also be a
+    callable that maps probe indices q (an int64 array) to their records (len(q), 28): a volume that does not exist on the host.
+    detail: -> (out, w (n, 8): the corners' weights in the order dz, dy, dx, the wsum before the zero rule, q (n, 8) int64)"""
     nx, ny, nz = d["count"]
-    vol = np.ascontiguousarray(volume, F).reshape(nx * ny * nz, WORDS)
+    if callable(volume):
+        fetch = lambda q: np.ascontiguousarray(volume(q), F).reshape(len(q), WORDS)      # noqa: E731
+    else:
+        vol = np.ascontiguousarray(volume, F).reshape(nx * ny * nz, WORDS)
+        fetch = lambda q: vol[q]                                                         # noqa: E731
     pts = np.ascontiguousarray(pts, F).reshape(-1, 8)
     n = len(pts)
     ax = [axis(pts[:, a], d["origin"][a], d["spacing"][a], d["count"][a]) for a in range(3)]
     acc, wsum = np.zeros((n, 27), F), np.zeros(n, F)
+    ws, qs = [], []
     with np.errstate(invalid="ignore", over="ignore"):
         for dz in range(2):
             for dy in range(2):
                 for dx in range(2):
                     q = (ax[2][dz] * ny + ax[1][dy]) * nx + ax[0][dx]
-                    rec = vol[q]
+                    rec = fetch(q)
                     w = ((ax[0][2 + dx] * ax[1][2 + dy]) * ax[2][2 + dz]) * rec[:, 27]
+                    ws.append(w)
+                    qs.append(q)
                     on = w != 0                       # (a NaN weight counts: it is not zero)
                     acc = np.where(on[:, None], acc + rec[:, 0:27] * w[:, None], acc).astype(F)
                     wsum = np.where(on, wsum + w, wsum).astype(F)
@@ -99,6 +109,8 @@ def sample(d, volume, pts):
             out[:, ch] = e
         out[:, 3] = wsum
     out[zero] = 0
+    if detail:
+        return out, np.stack(ws, 1).astype(F).reshape(n, 8), wsum, np.stack(qs, 1).reshape(n, 8)
     return out
 
 
@@ -200,3 +212,53 @@ def sample_points(d, n, seed, nonfinite=False):
     pts[:, 3:6] = v
     pts.view(U)[:, 6:8] = rng.integers(0, 1 << 32, (n, 2), dtype=np.uint64).astype(U)      # (ignored words: anything)
     return pts
+
+
+# --------------------------------------------------------------------------------------------- a volume that is a function of (p, k)
+
+M32 = 0xFFFFFFFF
+HASH_VALID = (1.0, 1.0, 0.0, 0.25)                   # the validity of a probe by the low two bits of its word 27's hash
+
+
+def _mix(x):
+    """An integer hash of uint32 values in uint32 arithmetic, written for int64 carriers (numpy arrays and torch tensors alike): both
+    multipliers are below 2^31, so no product reaches 2^63, and every step is masked back to 32 bits."""
+    x = ((x ^ (x >> 16)) * 0x7FEB352D) & M32
+    x = ((x ^ (x >> 15)) * 0x2C1B3C6D) & M32
+    return x ^ (x >> 16)
+
+
+def hashed_records(q):
+    """probe indices q (int64) -> (len(q), 28) float32, the records of hashed_volume: word k of probe p from h = _mix(p * 28 + k).
+    Coefficients (float)(h >> 8) * 2^-23 - 1 in [-1, 1) - 24 bits, a power of two, a difference of multiples of 2^-23 below 2: every
+    step exact in float32.  Validity HASH_VALID[h(p, 27) & 3]; behind a zero validity word k is NaN, +inf, -inf by k % 3."""
+    q = np.asarray(q, np.int64).reshape(-1)
+    h = _mix(q[:, None] * WORDS + np.arange(WORDS, dtype=np.int64)[None, :])
+    out = ((h >> 8).astype(F) * F(2.0 ** -23) - F(1)).astype(F)
+    valid = np.array(HASH_VALID, F)[h[:, 27] & 3]
+    bad = np.array([np.nan, np.inf, -np.inf], F)[np.arange(27) % 3]
+    out[:, 0:27] = np.where((valid == 0)[:, None], bad[None, :], out[:, 0:27])
+    out[:, 27] = valid
+    return out
+
+
+def hashed_volume(count, device="cpu", slab=1 << 16):
+    """the whole volume of hashed_records as a torch tensor (nz, ny, nx, 28) on `device`, built `slab` probes at a time (the int64
+    temporaries of a slab: 28 * 8 * slab bytes each)"""
+    import torch
+    nx, ny, nz = count
+    n = nx * ny * nz
+    dev = torch.device(device)
+    vol = torch.empty((n, WORDS), dtype=torch.float32, device=dev)
+    k = torch.arange(WORDS, dtype=torch.int64, device=dev)[None, :]
+    table = torch.tensor(HASH_VALID, dtype=torch.float32, device=dev)
+    bad = torch.tensor([float("nan"), float("inf"), float("-inf")], dtype=torch.float32, device=dev)[torch.arange(27, device=dev) % 3]
+    for a in range(0, n, slab):
+        p = torch.arange(a, min(a + slab, n), dtype=torch.int64, device=dev)
+        h = _mix(p[:, None] * WORDS + k)
+        out = (h >> 8).to(torch.float32) * (2.0 ** -23) - 1.0
+        valid = table[h[:, 27] & 3]
+        out[:, 0:27] = torch.where((valid == 0)[:, None], bad[None, :], out[:, 0:27])
+        out[:, 27] = valid
+        vol[a:a + len(p)] = out
+    return vol.reshape(nz, ny, nx, WORDS)
