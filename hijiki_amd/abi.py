@@ -46,6 +46,10 @@ NUM_IN_WORDS, NUM_OUT_WORDS, NUM_MAX_RECORDS = 6, 4, 1 << 20
 STEP_IN_WORDS, STEP_OUT_WORDS, STEP_MAX_RECORDS = 18, 33, 1 << 16
 REINSERT_MAX_PASSES = 64         # hj_optimize_bvh_device: passes a call
 RECON_MAX_BLOCKS = 64            # hj_debug_reconstruct: blocks a call
+VOTE_MAX_LEVELS = 8192           # hj_debug_vote_*: levels of inner nodes the exchange accepts and a ray votes at
+VOTE_MAX_RAYS = 1 << 20          # hj_debug_vote_cast: rays a call
+VOTE_MAX_SHADOW = 16             # ... and the largest w_shadow (HJ_BVH_VOTE_SHADOW's range)
+VOTE_MISS = 0xFFFFFFFF           # ... the leaf position of a ray that hit nothing
 
 f32, u32, u64 = C.c_float, C.c_uint32, C.c_uint64
 

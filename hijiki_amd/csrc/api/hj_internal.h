@@ -13,6 +13,7 @@
 //                         api/refit_pass.hpp: the refit's stages for a caller that brings its own link set)
 //   api/scene_update.hip  hj_scene_update_shapes: the uploaded scene's boxes, triangle and emitter records recomputed in place
 //   api/tree_vote.hip     hj_tune_bvh_device: host half of kernels/hj_vote.h (child order voted by sampled rays)
+//                         and its probes hj_debug_vote_cast / _exchange / _gains (k_debug_cast: the vote's closest and cast on given rays)
 //   api/tree_reinsert.hip hj_optimize_bvh_device: the tree left on the device optimised by parallel reinsertion (its kernels, around the
 //                         per-node steps of api/tree_reinsert.h; includes no kernel header but hj_num.h's)
 //   api/texture.hip       image textures: the checks and the device buffer of hj_scene_upload_textured, hj_debug_texture_lookup
@@ -433,6 +434,8 @@ void put_error(hj_context* ctx, const std::string& text);
 std::mutex& alloc_mutex();                           // process-wide: a context sizing its batch slots (api/render_calls.hip run_submit)
 // api/scene_upload.hip: every invariant an upload checks; HJ_MAT_DIFFUSE_TEXTURED indices must be < num_textures
 int validate_scene(hj_context* ctx, const hj_scene_desc* s, size_t num_textures);
+// ... and its check of the links alone: bvh[N] is a pre-order skip-link tree (shape words are not read but for HJ_BVH_INNER)
+int validate_tree_links(hj_context* ctx, const hj_bvh_node* bvh, size_t N);
 // api/environment.hip: an environment's checks (hj_scene_upload_env) and its sampling distribution, built on the host before anything
 // is allocated; upload_environment copies the table and fills DeviceScene's env_* fields (env == NULL: nothing)
 struct EnvTable { std::vector<float4> rec; std::vector<double> prob, omega; double weight_sum = 0.0; };

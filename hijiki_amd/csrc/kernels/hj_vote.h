@@ -28,6 +28,7 @@ namespace hj {
 namespace vote {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kMaxLevels = HJ_VOTE_MAX_LEVELS;  // levels of inner nodes the exchange walks (api/tree_vote.hip) and a ray votes at (cast)
 
 struct Scene {
   const float4* spheres;            // hj_sphere
@@ -139,12 +140,12 @@ HJ_DEV Hit closest(const Scene& s, const Ray& r) {
   return h;
 }
 
-// One ray's votes: down the ancestors of the leaf it hit
+// One ray's votes: down the ancestors of the leaf it hit (all of them: a tree the exchange accepts has at most kMaxLevels)
 HJ_DEV void cast(const Scene& s, const Ray& r, const Hit& h, bool any) {
   if (h.shape < 0) return;
   const Prep p = prep(r);
   uint32_t i = 0, end_i = s.N;
-  for (int guard = 0; guard < 4096 && i != h.pos; guard++) {
+  for (uint32_t guard = 0; guard < kMaxLevels && i != h.pos; guard++) {
     const uint32_t l = i + 1;
     if (l >= s.N) return;
     const uint32_t rr = __float_as_uint(s.nodes[2 * (size_t)l + 1].w);          // the left child's exit = the right child

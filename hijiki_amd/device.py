@@ -28,7 +28,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
            "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap", "hj_filter_lightmap",
            "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive", "hj_probe_points", "hj_bake_probes",
-           "hj_sample_probes")
+           "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -117,6 +117,12 @@ def lib():
         L.hj_debug_shade_step.argtypes = [vp, C.POINTER(abi.RenderOpts), C.POINTER(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.hj_debug_reconstruct.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
+        u64p = C.POINTER(C.c_uint64)
+        L.hj_debug_vote_cast.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(C.c_float), C.c_size_t, C.c_uint32, C.c_uint32,
+                                         C.POINTER(C.c_uint32), u64p, u64p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.hj_debug_vote_exchange.argtypes = [vp, C.POINTER(abi.BvhNode), C.c_size_t, u64p, u64p, C.POINTER(abi.BvhNode), C.c_size_t,
+                                             C.POINTER(C.c_uint32)]
+        L.hj_debug_vote_gains.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_size_t, u64p, u64p, C.c_size_t]
         L.hj_block_seed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         L.hj_block_seed.restype = C.c_uint32
         L.hj_pass_offset.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_float)]
@@ -453,6 +459,45 @@ class Renderer:
         self._check(lib().hj_tune_bvh_device(self._h, C.byref(compiled.desc), nodes.ctypes.data_as(C.POINTER(abi.BvhNode)),
                                              len(nodes), int(vote_paths)))
         return nodes[:len(compiled.bvh)]
+
+    def debug_vote_cast(self, compiled, rays, any_hit=False, w_shadow=1, hits=None):
+        """hj_debug_vote_cast: what the (n, 8) float32 `rays` add to the vote's gains in the tree of `compiled`.  hits: None (the
+        vote's own closest hit), or (leaf positions (n,) - abi.VOTE_MISS for a miss -, t (n,) float32).  Returns gain_l, gain_r
+        (N,) uint64 and found (n, 4) uint32: leaf position, shape, t bits, 0."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n, N = len(rays), len(compiled.bvh)
+        given = None
+        if hits is not None:
+            given = np.zeros((n, 2), np.uint32)
+            given[:, 0] = np.asarray(hits[0], np.uint32)
+            given[:, 1] = np.ascontiguousarray(hits[1], np.float32).view(np.uint32)
+        gl, gr, found = np.zeros(max(N, 1), np.uint64), np.zeros(max(N, 1), np.uint64), np.zeros((max(n, 1), 4), np.uint32)
+        u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        self._check(lib().hj_debug_vote_cast(self._h, C.byref(compiled.desc), rays.ctypes.data_as(C.POINTER(C.c_float)), n, int(bool(any_hit)),
+                                             int(w_shadow), None if given is None else given.ctypes.data_as(u32p), gl.ctypes.data_as(u64p),
+                                             gr.ctypes.data_as(u64p), len(gl), found.ctypes.data_as(u32p)))
+        return gl[:N], gr[:N], found[:n]
+
+    def debug_vote_exchange(self, nodes, gain_l, gain_r):
+        """hj_debug_vote_exchange: the (N, 8) uint32 records re-ordered by the (N,) uint64 gains -> (records, exchanged, levels)."""
+        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+        gl, gr = np.ascontiguousarray(gain_l, np.uint64), np.ascontiguousarray(gain_r, np.uint64)
+        if gl.shape != (len(nodes),) or gr.shape != (len(nodes),):
+            raise ValueError("debug_vote_exchange: one gain of each side per record")
+        out = np.zeros((max(len(nodes), 1), 8), np.uint32)
+        info = (C.c_uint32 * 4)()
+        u64p, bp = C.POINTER(C.c_uint64), C.POINTER(abi.BvhNode)
+        self._check(lib().hj_debug_vote_exchange(self._h, nodes.ctypes.data_as(bp), len(nodes), gl.ctypes.data_as(u64p), gr.ctypes.data_as(u64p),
+                                                 out.ctypes.data_as(bp), len(out), info))
+        return out[:len(nodes)], int(info[1]), int(info[0])
+
+    def debug_vote_gains(self, compiled, paths):
+        """hj_debug_vote_gains: gain_l, gain_r (N,) uint64 as `paths` sampled camera paths of `compiled` leave them."""
+        N = len(compiled.bvh)
+        gl, gr = np.zeros(max(N, 1), np.uint64), np.zeros(max(N, 1), np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        self._check(lib().hj_debug_vote_gains(self._h, C.byref(compiled.desc), int(paths), gl.ctypes.data_as(u64p), gr.ctypes.data_as(u64p), len(gl)))
+        return gl[:N], gr[:N]
 
     def trace(self, rays, use_bvh=True, any_hit=False):
         """intersectScene for (n,8) rays -> ids (n,) int32, t, u, v (n,) float32 (raw hit, before populate)."""

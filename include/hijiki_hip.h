@@ -1000,6 +1000,36 @@ int hj_debug_shade_step(hj_context* ctx, const hj_render_opts* opts, const uint3
  *   from here; frames pin it. */
 #define HJ_RECON_MAX_BLOCKS 64u
 int hj_debug_reconstruct(hj_context* ctx, const hj_image_block* blocks, size_t nb, const hj_render_opts* opts, const float* samples);
+/* The two stages of the device ray vote (hj_tune_bvh_device, kernels/hj_vote.h) apart, on caller-given inputs (ABI 0.20): the same
+ *   device functions and kernels, the same host routines as the vote's; nothing of them is restated.  All arrays on the host.
+ * hj_debug_vote_cast: what n caller-given rays add to the gains of scene->bvh (scene->num_bvh_nodes = N records).  rays = n x 8
+ *   floats in hj_trace_rays' layout, the direction used as it is (the sampler's are unit vectors; the sphere test assumes one, the slab
+ *   test does not).  any_hit != 0: every ray votes as a shadow ray (all of ci, times w_shadow); 0: as a closest-hit ray
+ *   ((ci - ct) * 4).  w_shadow: explicit, 0 ... 16 (HJ_BVH_VOTE_SHADOW's range).  given_hits (may be NULL) = n x 2 words: the array
+ *   position of the leaf the ray hit (0xFFFFFFFF: the ray missed) and t (float bits): hj::vote::closest is then skipped and
+ *   hj::vote::cast runs on that hit - the counts become a function of the boxes, the ray and t alone.  NULL: cast runs on what
+ *   closest finds.  gain_l, gain_r = `capacity` (>= N) 64-bit words each, of which N are written; found = n x 4 words: leaf position
+ *   (0xFFFFFFFF: none), shape (int32, -1: none), t (float bits), 0 - of closest, or the given hit echoed.
+ *   A ray votes at every ancestor of its leaf down to level HJ_VOTE_MAX_LEVELS, the depth the exchange accepts.
+ * hj_debug_vote_exchange: the exchange on caller-given gains.  nodes = N records of a pre-order skip-link tree (boxes and shape
+ *   words are carried, not read; the root's exit may be N or HJ_BVH_ROOT_EXIT or anything >= N); gain_l, gain_r = N words.  The
+ *   children of node i change places where gain_r[i] > gain_l[i] (ties stay).  out_nodes (capacity >= N) = the re-ordered records,
+ *   info = levels that held an inner node, nodes exchanged, the kernels' error bits, 0.  Statuses as the vote's: links that are not a
+ *   tree's HJ_ERR_INVALID (checked on the host, before the device: the exchange sizes its writes by them), more than
+ *   HJ_VOTE_MAX_LEVELS levels HJ_ERR_UNSUPPORTED.
+ * hj_debug_vote_gains: gain_l, gain_r (capacity >= N words each) exactly as the sampler leaves them after `paths` camera paths of
+ *   `scene` through scene->bvh - what hj_tune_bvh_device(scene, ..., paths) hands to its exchange; w_shadow from HJ_BVH_VOTE_SHADOW /
+ *   the tree's size, as there.  paths == 0 or N < 3: all zero.
+ * Refused with HJ_ERR_INVALID before the device is touched: a null argument, a scene without a tree or one hj_scene_upload would
+ *   refuse, capacity < N, n == 0 or above HJ_VOTE_MAX_RAYS, w_shadow > 16, a given position that is neither 0xFFFFFFFF nor a leaf
+ *   of the tree, N == 0.  Then the gates of hj_tune_bvh_device: a frame in flight, frames in the pipeline (HJ_ERR_STATE). */
+#define HJ_VOTE_MAX_LEVELS 8192u
+#define HJ_VOTE_MAX_RAYS 1048576u   /* 2^20 */
+int hj_debug_vote_cast(hj_context* ctx, const hj_scene_desc* scene, const float* rays, size_t n, uint32_t any_hit, uint32_t w_shadow,
+                       const uint32_t* given_hits /* may be NULL */, uint64_t* gain_l, uint64_t* gain_r, size_t capacity, uint32_t* found);
+int hj_debug_vote_exchange(hj_context* ctx, const hj_bvh_node* nodes, size_t N, const uint64_t* gain_l, const uint64_t* gain_r,
+                           hj_bvh_node* out_nodes, size_t capacity, uint32_t info[4]);
+int hj_debug_vote_gains(hj_context* ctx, const hj_scene_desc* scene, size_t paths, uint64_t* gain_l, uint64_t* gain_r, size_t capacity);
 
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host
