@@ -38,6 +38,18 @@ LIGHTMAP_FILTER_MAX_ITERATIONS = 8  # hj_lightmap_filter: iteration i uses the s
 PROBES_DEVICE_ARRAYS = 1          # hj_probe_desc flag
 PROBE_WORDS = 28                  # words of a probe record: 27 SH coefficients of the irradiance, the validity weight
 PROBE_MAX_COUNT, PROBE_MAX_PROBES = 1024, 1 << 22   # probes along an axis, probes of a volume
+PROBE_VIS_DEVICE_ARRAYS, PROBE_VIS_NO_BACKFACE, PROBE_VIS_NO_CHEBYSHEV = 1, 2, 4   # hj_probe_vis_desc flags
+PROBE_VIS_RES = (4, 8, 16)        # interior texels per side of a probe's octahedral map
+PROBE_VIS_MAX_RAYS_PER_TEXEL = 64
+PROBE_VIS_MAX_DISTANCE = 1e18
+PROBE_VIS_SLAB_RAYS = 1 << 19     # the most rays of one slab of hj_bake_probe_visibility
+
+
+def probe_vis_words(res):
+    """HJ_PROBE_VIS_WORDS: the words of one probe's atlas, (res + 2)^2 texels of two moments"""
+    return 2 * (res + 2) * (res + 2)
+
+
 # hj_debug_num: enum hj_num_op in its order, the record sizes and the cap
 NUM_OPS = ("exp", "sincos2pi", "atan2", "asin", "min", "max", "div", "sqrt", "dot3", "cross3", "normalize3", "reflect3", "rng_seed",
            "rng_uint", "rng_float", "rand_cos_hemisphere", "rand_uniform_sphere", "rand_barycentric")
@@ -195,6 +207,12 @@ class ProbeDesc(C.Structure):
     """hj_probe_desc (ABI 0.19): the grid, the seeds and the validity rule of hj_probe_points / hj_bake_probes / hj_sample_probes."""
     _fields_ = [("origin", f32 * 3), ("spacing", f32 * 3), ("count", u32 * 3), ("seed", u32), ("seed_stride", u32), ("min_distance", f32),
                 ("flags", u32)]
+
+
+class ProbeVisDesc(C.Structure):
+    """hj_probe_vis_desc (ABI 0.21): the octahedral map, the bake's rays and the look-up's bias and switches of
+    hj_probe_visibility_rays / hj_bake_probe_visibility / hj_sample_probes_visible."""
+    _fields_ = [("res", u32), ("rays_per_texel", u32), ("max_distance", f32), ("normal_bias", f32), ("flags", u32)]
 
 
 class RenderStats(C.Structure):

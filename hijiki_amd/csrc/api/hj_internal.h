@@ -52,7 +52,11 @@
 //                         sums resolved to irradiance coefficients with a validity weight (k_pv_points, k_pv_resolve; the gather is
 //                         hj_trace_irradiance's, entered through that entry point with device arrays), and the trilinear look-up of a
 //                         volume at caller-given points (includes kernels/hj_probes.h; beside it hj_sh9.h - the SH basis, which
-//                         api/gather_query.hip includes too - and hj_num.h alone)
+//                         api/gather_query.hip includes too - and hj_num.h alone); probe_desc_check (below) for the unit behind it
+//   api/probe_visibility.hip hj_probe_visibility_rays, hj_bake_probe_visibility, hj_sample_probes_visible: per probe an octahedral
+//                         atlas of distance moments - in slabs: k_pvv_rays, hj_trace_rays through that entry point with device arrays,
+//                         k_pvv_reduce - and the look-up with back-face and Chebyshev weights (includes kernels/hj_probe_vis.h; beside
+//                         it hj_probes.h, hj_sh9.h and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -415,6 +419,11 @@ struct hj_context {
   // a point) and of their results (16 bytes a point).  Grown on demand, reused by every call, freed with the context.
   struct Probes { hjapi::DevBuf points, records, volume, in_points, out; } probes;
 
+  // hj_probe_visibility_rays / hj_bake_probe_visibility / hj_sample_probes_visible (api/probe_visibility.hip): one slab's rays (32
+  // bytes a ray) and hits (16 bytes a ray), at most HJ_PROBE_VIS_SLAB_RAYS of them; staging of a host-side atlas (the bake: one
+  // slab's part, the look-up: whole), volume, sample points and results.  Grown on demand, reused by every call, freed with the context.
+  struct ProbeVis { hjapi::DevBuf rays, hits, atlas, volume, in_points, out; } probe_vis;
+
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
   hjapi::Tuning tuning;
@@ -468,6 +477,11 @@ void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, 
 int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opts, hj_render_opts& o);
 int query_gate(hj_context* ctx, const char* fn);
 int context_gate(hj_context* ctx, const char* fn);
+}  // namespace hjapi
+namespace hj { struct PvGrid; }   // kernels/hj_probes.h
+namespace hjapi {
+// api/probe_volume.hip: what every probe entry point refuses of a desc, without a device, in the header's order -> g, n = the probes
+int probe_desc_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGrid& g, uint32_t& n);
 // The light-map filter for both of its entry points (api/lightmap_filter.hip):
 //   lightmap_filter_check    what both refuse of a filter, without a device: unknown flag bits, iterations, sigmas
 //   lightmap_filter_enqueue  guide from the `count` device points, then f.iterations iterations from img[cur] into img[cur ^ 1], cur

@@ -93,6 +93,10 @@ void enqueue_points(hj_context* ctx, const hj::PvGrid& g, const hj_probe_desc* d
 
 }  // namespace
 
+namespace hjapi {
+int probe_desc_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGrid& g, uint32_t& n) { return check_desc(ctx, fn, d, g, n); }
+}  // namespace hjapi
+
 extern "C" {
 
 // The argument checks come first and need neither a device nor a context's state (hj_lightmap_texels' order and style).

@@ -3,6 +3,7 @@
 // each, uncontracted, in that order.  The SH basis is kernels/hj_sh9.h's, the gather's own.
 //   pv_axis       THE text of one axis' clamp: the two probe planes about a coordinate and their weights
 //   k_pv_sample   a grid-stride loop over the points: eight 112-byte records per point as float4 loads, 27 sums in registers
+//                 (left out under HJ_PROBES_NO_SAMPLE_KERNEL: a unit that wants pv_axis and PvGrid alone)
 // Ordinary loads and stores, no LDS, no atomics and no inline assembly.  No index is formed from a value that has not been clamped:
 // whatever the points hold - NaN, infinities - every load stays inside the volume.
 #pragma once
@@ -32,6 +33,7 @@ HJ_DEV void pv_axis(float p, float origin, float spacing, uint32_t count, uint32
   i1 = min(i0 + 1u, m);
 }
 
+#ifndef HJ_PROBES_NO_SAMPLE_KERNEL   // (hj_probe_vis.h takes the clamp and the grid above and leaves the kernel to api/probe_volume.hip)
 // probes: count[0] * count[1] * count[2] records of kPvVec float4 (at most 2^22: a float4 index stays below 2^25); points: n records of two
 // float4 (position.xyz, normal.x | normal.yz, ignored, ignored); out: n float4.  The eight corners' validity weights come first - a
 // corner's weight decides whether it counts -, then the records one float4 column at a time: the eight loads of a column are
@@ -93,5 +95,6 @@ __global__ __launch_bounds__(kPvThreads) void k_pv_sample(PvGrid g, const float4
     out[i] = o;
   }
 }
+#endif  // HJ_PROBES_NO_SAMPLE_KERNEL
 
 }  // namespace hj

@@ -28,7 +28,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_debug_shade_step", "hj_trace_rays", "hj_debug_reconstruct", "hj_trace_paths", "hj_trace_paths_adaptive",
            "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap", "hj_filter_lightmap",
            "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive", "hj_probe_points", "hj_bake_probes",
-           "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains")
+           "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains", "hj_probe_visibility_rays",
+           "hj_bake_probe_visibility", "hj_sample_probes_visible")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -103,6 +104,9 @@ def lib():
         L.hj_probe_points.argtypes = [vp, C.POINTER(abi.ProbeDesc), vp]      # (host or device pointers)
         L.hj_bake_probes.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.c_uint32, C.POINTER(abi.RenderOpts), vp, C.POINTER(abi.RenderStats)]
         L.hj_sample_probes.argtypes = [vp, C.POINTER(abi.ProbeDesc), vp, vp, C.c_size_t, vp]
+        L.hj_probe_visibility_rays.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), C.c_uint32, C.c_uint32, vp]
+        L.hj_bake_probe_visibility.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), vp]   # (host or device pointers)
+        L.hj_sample_probes_visible.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), vp, vp, vp, C.c_size_t, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -985,6 +989,126 @@ class Renderer:
             raise ValueError(f"sample_probes: point {i} ({pts[i, 0:6].tolist()}): finite positions and finite normals that are not all zero are needed")
         out = np.zeros((len(pts), 4), np.float32)
         self._check(lib().hj_sample_probes(self._h, C.byref(d), vol.ctypes.data, pts.ctypes.data, len(pts), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _probe_vis_desc(what, res, rays_per_texel=1, max_distance=1.0, normal_bias=0.0, backface=True, chebyshev=True, device=False):
+        """The hj_probe_vis_desc of the visibility calls, checked before any call."""
+        res, rays_per_texel = int(res), int(rays_per_texel)
+        if res not in abi.PROBE_VIS_RES:
+            raise ValueError(f"{what}: res {res}: one of {abi.PROBE_VIS_RES} is needed")
+        if not 1 <= rays_per_texel <= abi.PROBE_VIS_MAX_RAYS_PER_TEXEL:
+            raise ValueError(f"{what}: rays_per_texel {rays_per_texel} outside [1, {abi.PROBE_VIS_MAX_RAYS_PER_TEXEL}]")
+        max_distance, normal_bias = np.float32(max_distance), np.float32(normal_bias)
+        if not (np.isfinite(max_distance) and 0 < max_distance <= np.float32(abi.PROBE_VIS_MAX_DISTANCE)):
+            raise ValueError(f"{what}: max_distance {max_distance}: finite, > 0 and at most 1e18 is needed")
+        if not (np.isfinite(normal_bias) and normal_bias >= 0):
+            raise ValueError(f"{what}: normal_bias {normal_bias}: finite and >= 0 is needed")
+        flags = ((abi.PROBE_VIS_DEVICE_ARRAYS if device else 0) | (0 if backface else abi.PROBE_VIS_NO_BACKFACE)
+                 | (0 if chebyshev else abi.PROBE_VIS_NO_CHEBYSHEV))
+        return abi.ProbeVisDesc(res, rays_per_texel, float(max_distance), float(normal_bias), flags)
+
+    def probe_visibility_rays(self, origin, spacing, count, res=8, rays_per_texel=4, max_distance=1e18, seed=0, seed_stride=1, first_probe=0,
+                              num_probes=None, device=False):
+        """hj_probe_visibility_rays: the rays `bake_probe_visibility` traces for the probes first_probe ... first_probe + num_probes - 1
+        (None: to the last) of a grid -> (num_probes * res * res * rays_per_texel, 8) float32, probe-major: `trace_rays` records -
+        the probe's position, a unit direction drawn inside texel (r // rays_per_texel) % res, (r // rays_per_texel) // res of the
+        probe's octahedral map from seedRng(seed + p * seed_stride + r), tMin 0, tMax max_distance.  No scene is needed.
+        device=True: a torch tensor on the renderer's GPU, written in place on the device."""
+        d = self._probe_desc("probe_visibility_rays", origin, spacing, count, seed, seed_stride, 0.0, device)
+        v = self._probe_vis_desc("probe_visibility_rays", res, rays_per_texel, max_distance, device=device)
+        n = d.count[0] * d.count[1] * d.count[2]
+        first_probe = int(first_probe)
+        num_probes = n - first_probe if num_probes is None else int(num_probes)
+        if not (0 <= first_probe and 0 <= num_probes and first_probe + num_probes <= n):
+            raise ValueError(f"probe_visibility_rays: probes {first_probe} ... {first_probe + num_probes} of {n}")
+        rows = num_probes * v.res * v.res * v.rays_per_texel
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            rays = torch.empty((rows, 8), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            self._check(lib().hj_probe_visibility_rays(self._h, C.byref(d), C.byref(v), first_probe, num_probes, rays.data_ptr() if rows else None))
+            return rays
+        rays = np.zeros((rows, 8), np.float32)
+        self._check(lib().hj_probe_visibility_rays(self._h, C.byref(d), C.byref(v), first_probe, num_probes, rays.ctypes.data if rows else None))
+        return rays
+
+    def bake_probe_visibility(self, origin, spacing, count, res=8, rays_per_texel=4, max_distance=1e18, seed=0, seed_stride=1, device=False):
+        """hj_bake_probe_visibility: the visibility atlas of a grid of probes in the uploaded scene -> (nz, ny, nx, res + 2, res + 2, 2)
+        float32: per probe an octahedral map of res x res texels (rows: the map's y) with a one-texel border that holds the map's
+        wrap-around, per texel the mean and the mean squared distance to the nearest surface over `rays_per_texel` rays drawn inside
+        the texel; a ray that hits nothing within `max_distance` counts as max_distance.  `sample_probes_visible` reads it beside
+        the volume of `bake_probes` on the same grid.  device=True: a torch tensor on the renderer's GPU."""
+        d = self._probe_desc("bake_probe_visibility", origin, spacing, count, seed, seed_stride, 0.0, device)
+        v = self._probe_vis_desc("bake_probe_visibility", res, rays_per_texel, max_distance, device=device)
+        shape = (d.count[2], d.count[1], d.count[0], v.res + 2, v.res + 2, 2)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            atlas = torch.empty(shape, dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            self._check(lib().hj_bake_probe_visibility(self._h, C.byref(d), C.byref(v), atlas.data_ptr()))
+            return atlas
+        atlas = np.zeros(shape, np.float32)
+        self._check(lib().hj_bake_probe_visibility(self._h, C.byref(d), C.byref(v), atlas.ctypes.data))
+        return atlas
+
+    def sample_probes_visible(self, volume, atlas, origin, spacing, points, normal_bias=0.0, backface=True, chebyshev=True, normals=None,
+                              device=None):
+        """hj_sample_probes_visible: `sample_probes` with the weights against light leaks -> (n, 4) float32.  Each of the eight probes
+        about a point is weighted further by a back-face factor (((dot(direction to the probe, normal) + 1) / 2)^2 + 0.2: probes
+        behind the surface count less) and by Chebyshev's bound, cubed and at least 0.05, on the share of the probe's rays that reach
+        as far as the point moved `normal_bias` along its normal, from the two moments `atlas` (`bake_probe_visibility` on the same
+        grid: (nz, ny, nx, res + 2, res + 2, 2); res comes from its shape) holds in the point's direction.  backface=False /
+        chebyshev=False switch a factor off; with both off atlas may be None and the result is `sample_probes`'.  volume, points,
+        normals and the numpy / torch rules as in `sample_probes`."""
+        on_gpu = type(volume).__module__.split(".")[0] == "torch" if device is None else bool(device)
+        if volume.ndim != 4 or volume.shape[3] != abi.PROBE_WORDS:
+            raise ValueError(f"sample_probes_visible: a volume of (nz, ny, nx, {abi.PROBE_WORDS}) is needed (got {tuple(volume.shape)})")
+        count = (int(volume.shape[2]), int(volume.shape[1]), int(volume.shape[0]))
+        if atlas is None:
+            if backface or chebyshev:
+                raise ValueError("sample_probes_visible: an atlas is needed unless backface and chebyshev are both off")
+            res = abi.PROBE_VIS_RES[0]
+        else:
+            if atlas.ndim != 6 or tuple(atlas.shape[0:3]) != tuple(volume.shape[0:3]) or atlas.shape[3] != atlas.shape[4] or atlas.shape[5] != 2:
+                raise ValueError(f"sample_probes_visible: an atlas of (nz, ny, nx, res + 2, res + 2, 2) on the volume's grid is needed"
+                                 f" (got {tuple(atlas.shape)} beside {tuple(volume.shape)})")
+            res = int(atlas.shape[3]) - 2
+        d = self._probe_desc("sample_probes_visible", origin, spacing, count, device=on_gpu)
+        v = self._probe_vis_desc("sample_probes_visible", res, normal_bias=normal_bias, backface=backface, chebyshev=chebyshev, device=on_gpu)
+        if normals is not None:
+            if points.ndim != 2 or points.shape[1] != 3 or tuple(normals.shape) != tuple(points.shape):
+                raise ValueError("sample_probes_visible: with normals, points and normals are (n, 3) each")
+        elif points.ndim != 2 or points.shape[1] != 8:
+            raise ValueError(f"sample_probes_visible: points of (n, 8), or (n, 3) with normals, are needed (got {tuple(points.shape)})")
+        if on_gpu:
+            import torch
+            for name, t in ((("volume", volume), ("points", points)) + ((("atlas", atlas),) if atlas is not None else ())
+                            + ((("normals", normals),) if normals is not None else ())):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"sample_probes_visible: {name} must be a contiguous float32 tensor on cuda:{self.device}")
+            if normals is not None:
+                points = torch.cat([points, normals, torch.zeros((points.shape[0], 2), dtype=torch.float32, device=points.device)], 1)
+            n = int(points.shape[0])
+            out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()    # (the allocations and whatever wrote the tensors)
+            self._check(lib().hj_sample_probes_visible(self._h, C.byref(d), C.byref(v), volume.data_ptr(), atlas.data_ptr() if atlas is not None else None,
+                                                       points.data_ptr() if n else None, n, out.data_ptr() if n else None))
+            return out
+        vol = np.ascontiguousarray(volume, np.float32)
+        atl = np.ascontiguousarray(atlas, np.float32) if atlas is not None else None
+        if normals is not None:
+            points = np.concatenate([np.asarray(points, np.float32), np.asarray(normals, np.float32), np.zeros((len(points), 2), np.float32)], 1)
+        pts = np.ascontiguousarray(points, np.float32)
+        bad = ~np.isfinite(pts[:, 0:6]).all(axis=1) | (pts[:, 3:6] == 0).all(axis=1)
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"sample_probes_visible: point {i} ({pts[i, 0:6].tolist()}): finite positions and finite normals that are not all zero are needed")
+        out = np.zeros((len(pts), 4), np.float32)
+        self._check(lib().hj_sample_probes_visible(self._h, C.byref(d), C.byref(v), vol.ctypes.data, atl.ctypes.data if atl is not None else None,
+                                                   pts.ctypes.data, len(pts), out.ctypes.data))
         return out
 
     def texture_lookup(self, texture, uv):

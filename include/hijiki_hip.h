@@ -877,8 +877,8 @@ int hj_bake_lightmap_adaptive(hj_context* ctx, const hj_lightmap_desc* desc, con
  *   in host arrays.  A null context: HJ_ERR_DEVICE in a process without a HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: an
  *   asynchronous frame in flight, frames submitted with HJ_RENDER_NO_DRAIN not yet drained, and for hj_bake_probes no scene.
  *   hj_sample_probes with n == 0: HJ_OK, nothing touched.  A refused call writes nothing.
- * Not here: no back-face or visibility (Chebyshev) weighting against light leaks - validity is the min_distance rule alone; no adaptive
- *   probe bake (hj_trace_irradiance_adaptive refuses HJ_GATHER_SH9). */
+ * Not here: no adaptive probe bake (hj_trace_irradiance_adaptive refuses HJ_GATHER_SH9).  The weights against light leaks - back face and
+ *   visibility (Chebyshev) - are hj_sample_probes_visible's, below; hj_sample_probes itself knows the min_distance rule alone. */
 #define HJ_PROBES_DEVICE_ARRAYS 1u
 #define HJ_PROBE_WORDS 28u
 typedef struct hj_probe_desc {
@@ -893,6 +893,93 @@ int hj_probe_points(hj_context* ctx, const hj_probe_desc* desc, float* points /*
 int hj_bake_probes(hj_context* ctx, const hj_probe_desc* desc, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
                    float* probes /* n x 28 */, hj_render_stats* stats /* may be NULL */);
 int hj_sample_probes(hj_context* ctx, const hj_probe_desc* desc, const float* probes, const float* points, size_t n, float* out /* n x 4 */);
+
+/* Probe visibility (ABI 0.21): per probe an octahedral map of the mean and the mean squared distance to the nearest surface, baked
+ * from the uploaded scene on the device, and a look-up of a probe volume that weights each of the eight probes about a point by a
+ * back-face factor and by Chebyshev's bound on the share of the probe's rays that reach the point - the weights against light leaks
+ * of Majercik et al. 2019, "Dynamic Diffuse Global Illumination with Ray-Traced Irradiance Fields" (their constants 0.2, 0.05 and
+ * the cube).  Without them trilinear interpolation pulls light through every wall thinner than one spacing.  No counterpart in the
+ * reference.  The numeric rules are the probe volumes' above: float32, one rounding per operation, no contraction; normalize, dot,
+ * length and the RNG are the numeric contract's (kernels/hj_num.h: dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)), length =
+ * sqrt(dot(a, a)), normalize(a) = a * (1.0f / length(a))); min and max are minNum and maxNum; sg(x) = x >= 0.0f ? 1.0f : -1.0f.
+ *   Of hj_probe_desc these calls use origin, spacing, count, seed and seed_stride; its flags must be 0 or HJ_PROBES_DEVICE_ARRAYS and
+ *   must agree with HJ_PROBE_VIS_DEVICE_ARRAYS of hj_probe_vis_desc; min_distance is checked and not used.  T = res + 2.
+ *
+ * The atlas.  Probe p owns T * T texels of two floats, HJ_PROBE_VIS_WORDS(res) words behind word p * HJ_PROBE_VIS_WORDS(res): texel
+ *   (bx, by) at index by * T + bx holds m1, the mean distance, and m2, the mean squared distance.  The interior is 1 ... res in both;
+ *   interior texel (tx, ty), 0-based, is (tx + 1, ty + 1) and covers the square [tx, tx + 1] x [ty, ty + 1] * (2 / res) - 1 of the
+ *   octahedral map.  The one-texel border holds the octahedral wrap: border (i + 1, 0) is interior (res - 1 - i, 0), border
+ *   (i + 1, res + 1) is interior (res - 1 - i, res - 1), border (0, j + 1) is interior (0, res - 1 - j), border (res + 1, j + 1) is
+ *   interior (res - 1, res - 1 - j), and each of the four corners is the diagonally opposite interior corner - so that the look-up
+ *   is a plain bilinear fetch.
+ *
+ * hj_probe_visibility_rays: the rays of the bake for the probes first_probe ... first_probe + num_probes - 1, probe-major, res * res
+ *   * rays_per_texel each in ascending r, as hj_trace_rays' records (8 words).  With s = rays_per_texel, ray r = (ty * res + tx) * s + k
+ *   of probe p is sample k < s of interior texel (tx, ty):
+ *       state = seedRng(seed + p * seed_stride + r)  (uint32 wrap-around);   u = rng_float(state);   v = rng_float(state);
+ *       ex = ((float)tx + u) * (2.0f / (float)res) - 1.0f;   ey = ((float)ty + v) * (2.0f / (float)res) - 1.0f;
+ *       az = (1.0f - |ex|) - |ey|;   d = az >= 0.0f ? (ex, ey, az) : ((1.0f - |ey|) * sg(ex), (1.0f - |ex|) * sg(ey), az);
+ *       words 0-2 the probe's position (above), 3-5 normalize(d), 6 tMin = 0.0f, 7 tMax = max_distance.
+ *   Needs a context but no scene.  num_probes == 0: HJ_OK, nothing touched.
+ *
+ * hj_bake_probe_visibility: from the uploaded scene to the atlas, in slabs of whole probes of at most HJ_PROBE_VIS_SLAB_RAYS rays (at
+ *   least 32 probes).  Per slab: 1. its rays, as hj_probe_visibility_rays emits them; 2. hj_trace_rays over them with
+ *   HJ_TRACE_DEVICE_ARRAYS, closest hit, no surface; 3. per atlas texel of the slab's probes, border included (a border texel takes
+ *   the rays of the interior texel it copies), from a1 = a2 = +0, for k = 0 ... s - 1 ascending:
+ *       dist = hit ? min(t, max_distance) : max_distance;   a1 = a1 + dist;   a2 = a2 + dist * dist;
+ *   then m1 = a1 / (float)s and m2 = a2 / (float)s.  The atlas depends on the scene and the two descs alone, not on the slab size or a
+ *   launch shape.  The context keeps one slab's rays and hits (48 bytes a ray, 24 MB at most) and, for a host-side atlas, one slab's
+ *   part of it: nothing that grows with the volume.  The origin domain is hj_trace_rays'.
+ *
+ * hj_sample_probes_visible: hj_sample_probes with the two factors in each corner's weight.  probes, points, m (hj_sample_probes' n)
+ *   and out as there.  Per point: x = words 0-2, nn = normalize(words 3-5), xb[a] = x[a] + nn[a] * normal_bias.  Axes, corners and
+ *   q exactly as in hj_sample_probes (from x, not xb).  Per corner, P the probe's position from the corner's indices:
+ *     back face:  wb = 1.0f if P == x in every component or with HJ_PROBE_VIS_NO_BACKFACE; otherwise
+ *         t = normalize(P - x);   h = (dot(t, nn) + 1.0f) * 0.5f;   wb = h * h + 0.2f.
+ *     Chebyshev:  e = xb - P;  wv = 1.0f if every component of e is zero or with HJ_PROBE_VIS_NO_CHEBYSHEV; otherwise rr = length(e),
+ *         l1 = (|e.x| + |e.y|) + |e.z|;   px = e.x / l1;   py = e.y / l1;
+ *         if e.z < 0.0f: (px, py) = ((1.0f - |py|) * sg(px), (1.0f - |px|) * sg(py)), both from the old values;
+ *         cx = (px * 0.5f + 0.5f) * (float)res + 0.5f;   cy likewise;   per axis hj_sample_probes' clamp with origin 0, spacing 1 and
+ *         count T gives i0, i1 and f (a NaN becomes 0);   with t00 = texel (ix0, iy0), t10 = (ix1, iy0), t01 = (ix0, iy1), t11 = (ix1, iy1),
+ *         per moment  m = (t00 * (1.0f - fx) + t10 * fx) * (1.0f - fy) + (t01 * (1.0f - fx) + t11 * fx) * fy;
+ *         if rr > m1:  var = |m1 * m1 - m2|;   dl = rr - m1;   c = var / (var + dl * dl);   wv = max((c * c) * c, 0.05f);   else wv = 1.0f.
+ *     w = ((((wx * wy) * wz) * probes[q][27]) * wb) * wv;  from here on hj_sample_probes word for word: the w == 0 skip, acc, wsum,
+ *     the basis at nn, out = (E[0], E[1], E[2], wsum).
+ *   No index is formed from a value that has not been clamped: with device arrays nothing in points, probes or atlas can make the
+ *   call fault; a NaN moment gives wv = 0.05f or 1.0f; a non-finite position gives NaN factors and a NaN result (a NaN, of no defined sign
+ *   or payload), unless both factors are off.  With both NO_ flags atlas may be NULL and is not read, and the result is bit
+ *   for bit hj_sample_probes'.  Needs a context but no scene.  m == 0: HJ_OK, nothing touched.
+ *
+ * HJ_PROBE_VIS_DEVICE_ARRAYS: as HJ_PROBES_DEVICE_ARRAYS - every array argument is a device pointer on the context's GPU, 16-byte aligned.
+ *   Without it they are host arrays, staged through buffers the context keeps (hj_sample_probes_visible: volume and atlas whole, 48
+ *   bytes per point); hj_sample_probes_visible then refuses non-finite positions and normals and all-zero normals as hj_sample_probes does.
+ * HJ_ERR_INVALID, checked before anything else and without a device (with a null context the text is in hj_last_error(NULL)), in
+ *   this order: a null desc, vis or array argument (hj_probe_visibility_rays: rays only with num_probes > 0; hj_sample_probes_visible:
+ *   arrays only with m > 0, atlas only unless both NO_ flags are set); the refusals of hj_probe_desc in their order above; unknown bits
+ *   in vis->flags; device-array flags that disagree; res other than 4, 8, 16; rays_per_texel outside [1, 64] and a max_distance that
+ *   is not finite, not > 0 or above 1e18f (the rays and the bake; the look-up ignores both); a normal_bias that is negative or not
+ *   finite (the look-up; the others ignore it, and the NO_ flags); first_probe + num_probes above the volume's probes; misaligned
+ *   device arrays; m above 2^31 - 1; a bad position or normal in host arrays.  A null context: HJ_ERR_DEVICE in a process without a
+ *   HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: hj_trace_rays' - an asynchronous frame in flight, frames submitted with
+ *   HJ_RENDER_NO_DRAIN not yet drained, and for hj_bake_probe_visibility no scene.  A refused call writes nothing.
+ * Not here: no adaptive bake, no blending of an atlas over time (the paper's hysteresis), no multi-GPU split, no CLI. */
+#define HJ_PROBE_VIS_DEVICE_ARRAYS 1u
+#define HJ_PROBE_VIS_NO_BACKFACE 2u    /* look-up only */
+#define HJ_PROBE_VIS_NO_CHEBYSHEV 4u   /* look-up only */
+#define HJ_PROBE_VIS_SLAB_RAYS 524288u /* 2^19: the most rays of one slab of hj_bake_probe_visibility */
+typedef struct hj_probe_vis_desc {
+  uint32_t res;             /* octahedral map, res x res interior texels: 4, 8 or 16               */
+  uint32_t rays_per_texel;  /* s, 1 ... 64 (rays and bake)                                         */
+  float    max_distance;    /* finite, > 0, <= 1e18f: rays end here, a miss counts as this         */
+  float    normal_bias;     /* finite, >= 0 (look-up)                                              */
+  uint32_t flags;           /* HJ_PROBE_VIS_*                                                      */
+} hj_probe_vis_desc;
+#define HJ_PROBE_VIS_WORDS(res) (2u * ((res) + 2u) * ((res) + 2u))   /* 72, 200, 648: a probe's atlas is a multiple of 16 bytes */
+int hj_probe_visibility_rays(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, uint32_t first_probe, uint32_t num_probes,
+                             float* rays /* num_probes * res * res * rays_per_texel x 8 */);
+int hj_bake_probe_visibility(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, float* atlas /* n x HJ_PROBE_VIS_WORDS(res) */);
+int hj_sample_probes_visible(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes /* n x 28 */,
+                             const float* atlas, const float* points /* m x 8 */, size_t m, float* out /* m x 4 */);
 
 /* ------------------------------------------------------------------- probes */
 
