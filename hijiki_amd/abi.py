@@ -43,6 +43,10 @@ PROBE_VIS_RES = (4, 8, 16)        # interior texels per side of a probe's octahe
 PROBE_VIS_MAX_RAYS_PER_TEXEL = 64
 PROBE_VIS_MAX_DISTANCE = 1e18
 PROBE_VIS_SLAB_RAYS = 1 << 19     # the most rays of one slab of hj_bake_probe_visibility
+PROBE_UPDATE_WORDS = 8            # words of hj_probe_update
+PROBE_UPDATE_SOFT_STEP = 0.15     # what a change beyond change_soft takes off the hysteresis (Majercik et al. 2019)
+PROBE_UPDATE_CHANGE = (0.25, 0.8)  # the wrapper's defaults for change_soft, change_hard: the paper's starting point, not tuned
+PROBE_UPDATE_FRAME_STRIDE = 0x9E3779B1   # the wrapper's default frame_stride: odd, so that 2^32 frames have 2^32 seeds
 
 
 def probe_vis_words(res):
@@ -213,6 +217,13 @@ class ProbeVisDesc(C.Structure):
     """hj_probe_vis_desc (ABI 0.21): the octahedral map, the bake's rays and the look-up's bias and switches of
     hj_probe_visibility_rays / hj_bake_probe_visibility / hj_sample_probes_visible."""
     _fields_ = [("res", u32), ("rays_per_texel", u32), ("max_distance", f32), ("normal_bias", f32), ("flags", u32)]
+
+
+class ProbeUpdate(C.Structure):
+    """hj_probe_update (ABI 0.22): the probe window, the frame's seeds, the hysteresis and the change thresholds of hj_update_probes /
+    hj_update_probe_visibility."""
+    _fields_ = [("first_probe", u32), ("num_probes", u32), ("frame", u32), ("frame_stride", u32), ("hysteresis", f32), ("change_soft", f32),
+                ("change_hard", f32), ("flags", u32)]
 
 
 class RenderStats(C.Structure):

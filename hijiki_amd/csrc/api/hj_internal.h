@@ -56,7 +56,12 @@
 //   api/probe_visibility.hip hj_probe_visibility_rays, hj_bake_probe_visibility, hj_sample_probes_visible: per probe an octahedral
 //                         atlas of distance moments - in slabs: k_pvv_rays, hj_trace_rays through that entry point with device arrays,
 //                         k_pvv_reduce - and the look-up with back-face and Chebyshev weights (includes kernels/hj_probe_vis.h; beside
-//                         it hj_probes.h, hj_sh9.h and hj_num.h alone)
+//                         it hj_probes.h, hj_sh9.h and hj_num.h alone); probe_vis_bake_check, probe_vis_rays_enqueue (below)
+//   api/probe_update.hip  hj_update_probes, hj_update_probe_visibility: a window of probes re-baked under a frame's seeds and folded
+//                         into what the caller holds - k_pv_points and hj_trace_irradiance, then k_pu_resolve (resolve and blend in
+//                         one pass); per slab k_pvv_rays and hj_trace_rays, then k_pu_reduce (moments, blend and border in one pass)
+//                         (includes kernels/hj_probe_update.h; beside it the functions of hj_probes.h and hj_probe_vis.h, without
+//                         their kernels, and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -417,11 +422,13 @@ struct hj_context {
   // hj_probe_points / hj_bake_probes / hj_sample_probes (api/probe_volume.hip): the bake's gather points (32 bytes a probe) and the
   // gather's SH records (144 bytes a probe); staging of a host-side volume (112 bytes a probe), of host-side sample points (32 bytes
   // a point) and of their results (16 bytes a point).  Grown on demand, reused by every call, freed with the context.
+  // hj_update_probes (api/probe_update.hip) uses points, records and - for host arrays - volume, each for the probes of its window alone.
   struct Probes { hjapi::DevBuf points, records, volume, in_points, out; } probes;
 
   // hj_probe_visibility_rays / hj_bake_probe_visibility / hj_sample_probes_visible (api/probe_visibility.hip): one slab's rays (32
   // bytes a ray) and hits (16 bytes a ray), at most HJ_PROBE_VIS_SLAB_RAYS of them; staging of a host-side atlas (the bake: one
   // slab's part, the look-up: whole), volume, sample points and results.  Grown on demand, reused by every call, freed with the context.
+  // hj_update_probe_visibility (api/probe_update.hip) uses rays, hits and - for host arrays - atlas, each for one slab of its window.
   struct ProbeVis { hjapi::DevBuf rays, hits, atlas, volume, in_points, out; } probe_vis;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
@@ -478,10 +485,17 @@ int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opt
 int query_gate(hj_context* ctx, const char* fn);
 int context_gate(hj_context* ctx, const char* fn);
 }  // namespace hjapi
-namespace hj { struct PvGrid; }   // kernels/hj_probes.h
+namespace hj { struct PvGrid; struct PvvMap; }   // kernels/hj_probes.h, kernels/hj_probe_vis.h
 namespace hjapi {
-// api/probe_volume.hip: what every probe entry point refuses of a desc, without a device, in the header's order -> g, n = the probes
+// api/probe_volume.hip: what every probe entry point refuses of a desc, without a device, in the header's order -> g, n = the probes;
+// and the enqueue, on the context's stream, of the gather points of the probes first ... first + n - 1 (n > 0) under `seed`
 int probe_desc_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGrid& g, uint32_t& n);
+void probe_points_enqueue(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t n, float4* d_points);
+// api/probe_visibility.hip: what hj_bake_probe_visibility refuses of the two descs, in the header's order -> g, n, v; and the enqueue
+// of the bake's rays for the probes first ... first + probes - 1 (at most a slab's) under `seed`
+int probe_vis_bake_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, const hj_probe_vis_desc* vis, hj::PvGrid& g, uint32_t& n, hj::PvvMap& v);
+void probe_vis_rays_enqueue(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t probes,
+                            float4* d_rays);
 // The light-map filter for both of its entry points (api/lightmap_filter.hip):
 //   lightmap_filter_check    what both refuse of a filter, without a device: unknown flag bits, iterations, sigmas
 //   lightmap_filter_enqueue  guide from the `count` device points, then f.iterations iterations from img[cur] into img[cur ^ 1], cur

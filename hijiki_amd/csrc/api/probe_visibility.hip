@@ -52,12 +52,23 @@ dim3 per_item(uint32_t n) { return dim3((n + hj::kPvvThreads - 1u) / hj::kPvvThr
 // whole probes of a slab: at most kPvvSlabRays rays (res^2 s <= 16384: at least 32 probes)
 uint32_t slab_probes(const hj::PvvMap& v) { return hj::kPvvSlabRays / (v.res * v.res * v.s); }
 
-void enqueue_rays(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, const hj_probe_desc* d, uint32_t first, uint32_t probes, float4* d_rays) {
+// the rays of the probes first ... first + probes - 1 (at most a slab's) under `seed`, on the context's stream
+void enqueue_rays(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t probes, float4* d_rays) {
   const uint32_t count = probes * (v.res * v.res * v.s);
-  hipLaunchKernelGGL(hj::k_pvv_rays, per_item(count), dim3(hj::kPvvThreads), 0, ctx->stream, g, v, d->seed, d->seed_stride, first, count, d_rays);
+  hipLaunchKernelGGL(hj::k_pvv_rays, per_item(count), dim3(hj::kPvvThreads), 0, ctx->stream, g, v, seed, seed_stride, first, count, d_rays);
 }
 
 }  // namespace
+
+namespace hjapi {   // for api/probe_update.hip (hj_internal.h)
+int probe_vis_bake_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, const hj_probe_vis_desc* vis, hj::PvGrid& g, uint32_t& n, hj::PvvMap& v) {
+  return check_descs(ctx, fn, Call::kBake, d, vis, g, n, v);
+}
+void probe_vis_rays_enqueue(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t probes,
+                            float4* d_rays) {
+  enqueue_rays(ctx, g, v, seed, seed_stride, first, probes, d_rays);
+}
+}  // namespace hjapi
 
 extern "C" {
 
@@ -83,7 +94,7 @@ int hj_probe_visibility_rays(hj_context* ctx, const hj_probe_desc* desc, const h
     const uint32_t cnt = std::min(slab, num_probes - at);
     float* here = rays + 8 * (size_t)at * per;
     float4* d_rays = on_device ? reinterpret_cast<float4*>(here) : static_cast<float4*>(ctx->probe_vis.rays.p);
-    enqueue_rays(ctx, g, v, desc, first_probe + at, cnt, d_rays);
+    enqueue_rays(ctx, g, v, desc->seed, desc->seed_stride, first_probe + at, cnt, d_rays);
     e = hipGetLastError();
     if (e == hipSuccess && !on_device) e = hipMemcpyAsync(here, d_rays, sizeof(float4) * 2 * (size_t)cnt * per, hipMemcpyDeviceToHost, ctx->stream);
   }
@@ -109,7 +120,7 @@ int hj_bake_probe_visibility(hj_context* ctx, const hj_probe_desc* desc, const h
   for (uint32_t at = 0; at < n; at += slab) {
     const uint32_t cnt = std::min(slab, n - at);
     // 1. the rays, 2. the trace: the same stream, so it runs behind the rays; it returns with its hits complete
-    enqueue_rays(ctx, g, v, desc, at, cnt, d_rays);
+    enqueue_rays(ctx, g, v, desc->seed, desc->seed_stride, at, cnt, d_rays);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, __func__, e);
     HJ_TRY(hj_trace_rays(ctx, reinterpret_cast<const float*>(d_rays), (size_t)cnt * per, HJ_TRACE_DEVICE_ARRAYS, reinterpret_cast<float*>(d_hits), nullptr));
     // 3. the moments, border included (a host-side atlas: through one slab's staging, which the copy leaves before the next slab writes it)

@@ -7,8 +7,9 @@
 //   points:  k_pv_points
 //   bake:    k_pv_points  ->  hj_trace_irradiance (sphere, SH9; it returns with its records complete)  ->  k_pv_resolve
 //   sample:  k_pv_sample
-//   k_pv_points   one thread per probe: its gather point
+//   k_pv_points   one thread per probe of a window: its gather point
 //   k_pv_resolve  one thread per probe: the gather's 27 SH sums scaled to irradiance coefficients, and the validity weight
+// For api/probe_update.hip: probe_desc_check and probe_points_enqueue (hj_internal.h).
 #include "hj_internal.h"
 #include "../kernels/hj_probes.h"
 
@@ -18,35 +19,24 @@ using namespace hjapi;
 
 namespace hj {
 
-// Probe p = (z * count[1] + y) * count[0] + x: position origin + (float)i * spacing per axis (a product, then a sum), normal +0, the seed
-// seed + p * seed_stride (uint32 wrap-around), p.
-__global__ __launch_bounds__(kPvThreads) void k_pv_points(PvGrid g, uint32_t seed, uint32_t seed_stride, uint32_t n, float4* __restrict__ points) {
-  const uint32_t p = blockIdx.x * kPvThreads + threadIdx.x;
-  if (p >= n) return;
+// Probe p = first + i of thread i, p = (z * count[1] + y) * count[0] + x: position origin + (float)i * spacing per axis (a product, then a
+// sum), normal +0, the seed seed + p * seed_stride (uint32 wrap-around), p.  points: the n records of the window first ... first + n - 1.
+__global__ __launch_bounds__(kPvThreads) void k_pv_points(PvGrid g, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t n, float4* __restrict__ points) {
+  const uint32_t i = blockIdx.x * kPvThreads + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = first + i;
   const uint32_t x = p % g.count[0], yz = p / g.count[0], y = yz % g.count[1], z = yz / g.count[1];
   const float px = g.origin[0] + (float)x * g.spacing[0], py = g.origin[1] + (float)y * g.spacing[1], pz = g.origin[2] + (float)z * g.spacing[2];
-  points[2 * (size_t)p] = make_float4(px, py, pz, 0.0f);
-  points[2 * (size_t)p + 1] = make_float4(0.0f, 0.0f, __uint_as_float(seed + p * seed_stride), __uint_as_float(p));
+  points[2 * (size_t)i] = make_float4(px, py, pz, 0.0f);
+  points[2 * (size_t)i + 1] = make_float4(0.0f, 0.0f, __uint_as_float(seed + p * seed_stride), __uint_as_float(p));
 }
 
-// records: 9 float4 per probe, hj_trace_irradiance's with HJ_GATHER_SH9.  Word 3 j + c of a probe is (sum[8 + 3 j + c] * s) * A_band(j),
-// s = 12.5663706f / (float)spp; the bands' clamped-cosine factors are pi, 2 pi / 3, pi / 4.  Word 27: 1.0f when the nearest first hit
-// (record word 5, +inf without one) is >= min_distance, else 0.0f.
+// records: 9 float4 per probe, hj_trace_irradiance's with HJ_GATHER_SH9; the arithmetic is pv_resolve_record's (kernels/hj_probes.h).
 __global__ __launch_bounds__(kPvThreads) void k_pv_resolve(const float4* __restrict__ records, uint32_t n, float s, float min_distance, float4* __restrict__ probes) {
   const uint32_t p = blockIdx.x * kPvThreads + threadIdx.x;
   if (p >= n) return;
-  constexpr float A0 = 3.14159274f, A1 = 2.09439516f, A2 = 0.785398185f;
-  const float4* __restrict__ r = records + 9 * (size_t)p;
-  const float nearest = r[1].y;
   float v[28];
-#pragma unroll
-  for (uint32_t m = 0; m < kPvVec; m++) {
-    const float4 t = r[2 + m];
-    v[4 * m] = t.x; v[4 * m + 1] = t.y; v[4 * m + 2] = t.z; v[4 * m + 3] = t.w;
-  }
-#pragma unroll
-  for (uint32_t k = 0; k < 27u; k++) v[k] = (v[k] * s) * (k < 3u ? A0 : k < 12u ? A1 : A2);
-  v[27] = (nearest >= min_distance) ? 1.0f : 0.0f;
+  pv_resolve_record(records + 9 * (size_t)p, s, min_distance, v);
 #pragma unroll
   for (uint32_t m = 0; m < kPvVec; m++) probes[kPvVec * (size_t)p + m] = make_float4(v[4 * m], v[4 * m + 1], v[4 * m + 2], v[4 * m + 3]);
 }
@@ -87,14 +77,18 @@ bool misaligned(const void* a, const void* b = nullptr, const void* c = nullptr)
 
 dim3 per_probe(uint32_t n) { return dim3((n + hj::kPvThreads - 1u) / hj::kPvThreads); }
 
-void enqueue_points(hj_context* ctx, const hj::PvGrid& g, const hj_probe_desc* d, uint32_t n, float4* d_points) {
-  hipLaunchKernelGGL(hj::k_pv_points, per_probe(n), dim3(hj::kPvThreads), 0, ctx->stream, g, d->seed, d->seed_stride, n, d_points);
+// the gather points of the probes first ... first + n - 1 (n > 0) under `seed`, on the context's stream
+void enqueue_points(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t n, float4* d_points) {
+  hipLaunchKernelGGL(hj::k_pv_points, per_probe(n), dim3(hj::kPvThreads), 0, ctx->stream, g, seed, seed_stride, first, n, d_points);
 }
 
 }  // namespace
 
 namespace hjapi {
 int probe_desc_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGrid& g, uint32_t& n) { return check_desc(ctx, fn, d, g, n); }
+void probe_points_enqueue(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t n, float4* d_points) {
+  enqueue_points(ctx, g, seed, seed_stride, first, n, d_points);
+}
 }  // namespace hjapi
 
 extern "C" {
@@ -114,7 +108,7 @@ int hj_probe_points(hj_context* ctx, const hj_probe_desc* desc, float* points) {
     HJ_TRY(dev_alloc(ctx, ctx->probes.points, sizeof(float4) * 2 * (size_t)n));
     d_points = static_cast<float4*>(ctx->probes.points.p);
   }
-  enqueue_points(ctx, g, desc, n, d_points);
+  enqueue_points(ctx, g, desc->seed, desc->seed_stride, 0u, n, d_points);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(points, d_points, sizeof(float4) * 2 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
   return drain(ctx, __func__, e);
@@ -142,7 +136,7 @@ int hj_bake_probes(hj_context* ctx, const hj_probe_desc* desc, uint32_t spp, con
     d_probes = static_cast<float4*>(pv.volume.p);
   }
   float4 *d_points = static_cast<float4*>(pv.points.p), *d_records = static_cast<float4*>(pv.records.p);
-  enqueue_points(ctx, g, desc, n, d_points);
+  enqueue_points(ctx, g, desc->seed, desc->seed_stride, 0u, n, d_points);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, __func__, e);
   HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), n, spp, &o, HJ_GATHER_SPHERE | HJ_GATHER_SH9 | HJ_GATHER_DEVICE_ARRAYS,
                              reinterpret_cast<float*>(d_records), stats));

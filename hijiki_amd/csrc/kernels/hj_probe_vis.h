@@ -6,6 +6,8 @@
 // the clamp), hj_sh9.h and hj_num.h alone: the path kernels' machine code does not depend on this unit.
 //   pvv_position    a probe's position from its index: k_pv_points' expression
 //   pvv_oct_decode  a point of the octahedral square [-1, 1]^2 to its (unnormalised) direction;  pvv_oct_encode: the way back
+//   pvv_border_source  THE text of the border: the interior texel an atlas texel copies;  pvv_moments: THE text of a texel's two moments
+//   (the kernels are left out under HJ_PROBE_VIS_NO_KERNELS: a unit that wants the functions above alone)
 //   k_pvv_rays      one thread per ray: hj_trace_rays' record of sample k of a texel of a probe
 //   k_pvv_reduce    one thread per atlas texel, border included: the two moments of its s distances, summed in ascending k
 //   k_pvv_sample    a grid-stride loop over the points: hj_probes.h's k_pv_sample with the two factors in each corner's weight
@@ -56,6 +58,39 @@ HJ_DEV void pvv_oct_encode(v3 e, float& px, float& py) {
   }
 }
 
+// THE text of the border: atlas texel (bx, by) of a map of T = res + 2 texels a side -> the interior texel (tx, ty), 0-based, it
+// copies (an interior texel: itself) - the octahedral wrap, so that the look-up's bilinear fetch has no special case at the edges.
+HJ_DEV void pvv_border_source(uint32_t res, uint32_t bx, uint32_t by, uint32_t& tx, uint32_t& ty) {
+  const uint32_t T = res + 2u, last = res - 1u;
+  const bool ex = bx == 0u || bx == T - 1u, ey = by == 0u || by == T - 1u;
+  if (ex && ey) {                      // a corner: the diagonally opposite interior corner
+    tx = bx == 0u ? last : 0u;
+    ty = by == 0u ? last : 0u;
+  } else if (ey) {                     // top and bottom rows: mirrored in x
+    tx = res - bx;
+    ty = by == 0u ? 0u : last;
+  } else if (ex) {                     // left and right columns: mirrored in y
+    tx = bx == 0u ? 0u : last;
+    ty = res - by;
+  } else {
+    tx = bx - 1u;
+    ty = by - 1u;
+  }
+}
+
+// THE text of the moments: h, the v.s hit records (hj_trace_rays') of one interior texel's rays -> (m1, m2), summed in ascending k.
+HJ_DEV float2 pvv_moments(const PvvMap& v, const float4* __restrict__ h) {
+  float a1 = 0.0f, a2 = 0.0f;
+  for (uint32_t k = 0; k < v.s; k++) {
+    const float4 r = h[k];
+    const float dist = (__float_as_int(r.x) >= 0) ? f_min(r.y, v.max_distance) : v.max_distance;
+    a1 = a1 + dist;
+    a2 = a2 + dist * dist;
+  }
+  return make_float2(a1 / (float)v.s, a2 / (float)v.s);
+}
+
+#ifndef HJ_PROBE_VIS_NO_KERNELS   // (hj_probe_update.h takes the functions above and leaves the kernels to api/probe_visibility.hip)
 // rays: count records of two float4 (origin.xyz, dir.x | dir.yz, tMin = 0, tMax = max_distance); ray i of the launch is ray
 // r = i % (res^2 s) of probe first + i / (res^2 s).  (count <= kPvvSlabRays or a caller's window, below 2^32 either way.)
 __global__ __launch_bounds__(kPvvThreads) void k_pvv_rays(PvGrid g, PvvMap v, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t count,
@@ -82,31 +117,10 @@ __global__ __launch_bounds__(kPvvThreads) void k_pvv_reduce(PvvMap v, const floa
   const uint32_t T = v.res + 2u, texels = T * T;
   const uint32_t i = blockIdx.x * kPvvThreads + threadIdx.x;
   if (i >= probes * texels) return;
-  const uint32_t p = i / texels, b = i % texels, bx = b % T, by = b / T, last = v.res - 1u;
-  const bool ex = bx == 0u || bx == T - 1u, ey = by == 0u || by == T - 1u;
+  const uint32_t p = i / texels, b = i % texels;
   uint32_t tx, ty;
-  if (ex && ey) {                      // a corner: the diagonally opposite interior corner
-    tx = bx == 0u ? last : 0u;
-    ty = by == 0u ? last : 0u;
-  } else if (ey) {                     // top and bottom rows: mirrored in x
-    tx = v.res - bx;
-    ty = by == 0u ? 0u : last;
-  } else if (ex) {                     // left and right columns: mirrored in y
-    tx = bx == 0u ? 0u : last;
-    ty = v.res - by;
-  } else {
-    tx = bx - 1u;
-    ty = by - 1u;
-  }
-  const float4* __restrict__ h = hits + ((size_t)p * (v.res * v.res) + (ty * v.res + tx)) * v.s;
-  float a1 = 0.0f, a2 = 0.0f;
-  for (uint32_t k = 0; k < v.s; k++) {
-    const float4 r = h[k];
-    const float dist = (__float_as_int(r.x) >= 0) ? f_min(r.y, v.max_distance) : v.max_distance;
-    a1 = a1 + dist;
-    a2 = a2 + dist * dist;
-  }
-  atlas[i] = make_float2(a1 / (float)v.s, a2 / (float)v.s);
+  pvv_border_source(v.res, b % T, b / T, tx, ty);
+  atlas[i] = pvv_moments(v, hits + ((size_t)p * (v.res * v.res) + (ty * v.res + tx)) * v.s);
 }
 
 // probes, points, out: k_pv_sample's; atlas: (res + 2)^2 float2 per probe (not read with both NO_ flags: may be null then).  Per point
@@ -213,5 +227,6 @@ __global__ __launch_bounds__(kPvvThreads) void k_pvv_sample(PvGrid g, PvvMap v, 
     out[i] = o;
   }
 }
+#endif  // HJ_PROBE_VIS_NO_KERNELS
 
 }  // namespace hj

@@ -2,6 +2,7 @@
 // around each.  include/hijiki_hip.h (hj_sample_probes) spells the arithmetic out; every operation here is float32, one rounding
 // each, uncontracted, in that order.  The SH basis is kernels/hj_sh9.h's, the gather's own.
 //   pv_axis       THE text of one axis' clamp: the two probe planes about a coordinate and their weights
+//   pv_resolve_record  THE text of the bake's resolve: a probe's gather record to its 27 coefficients and the validity weight
 //   k_pv_sample   a grid-stride loop over the points: eight 112-byte records per point as float4 loads, 27 sums in registers
 //                 (left out under HJ_PROBES_NO_SAMPLE_KERNEL: a unit that wants pv_axis and PvGrid alone)
 // Ordinary loads and stores, no LDS, no atomics and no inline assembly.  No index is formed from a value that has not been clamped:
@@ -31,6 +32,23 @@ HJ_DEV void pv_axis(float p, float origin, float spacing, uint32_t count, uint32
   i0 = min((uint32_t)g, m > 0u ? m - 1u : 0u);
   f = g - (float)i0;
   i1 = min(i0 + 1u, m);
+}
+
+// THE text of the bake's resolve, for k_pv_resolve (api/probe_volume.hip) and k_pu_resolve (hj_probe_update.h).  r: the 9 float4 of
+// one probe's gather record (hj_trace_irradiance's with HJ_GATHER_SH9).  v[3 j + c] = (sum[8 + 3 j + c] * s) * A_band(j), s =
+// 12.5663706f / (float)spp; the bands' clamped-cosine factors are pi, 2 pi / 3, pi / 4.  v[27]: 1.0f when the nearest first hit
+// (record word 5, +inf without one) is >= min_distance, else 0.0f.
+HJ_DEV void pv_resolve_record(const float4* __restrict__ r, float s, float min_distance, float (&v)[28]) {
+  constexpr float A0 = 3.14159274f, A1 = 2.09439516f, A2 = 0.785398185f;
+  const float nearest = r[1].y;
+#pragma unroll
+  for (uint32_t m = 0; m < kPvVec; m++) {
+    const float4 t = r[2 + m];
+    v[4 * m] = t.x; v[4 * m + 1] = t.y; v[4 * m + 2] = t.z; v[4 * m + 3] = t.w;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 27u; k++) v[k] = (v[k] * s) * (k < 3u ? A0 : k < 12u ? A1 : A2);
+  v[27] = (nearest >= min_distance) ? 1.0f : 0.0f;
 }
 
 #ifndef HJ_PROBES_NO_SAMPLE_KERNEL   // (hj_probe_vis.h takes the clamp and the grid above and leaves the kernel to api/probe_volume.hip)

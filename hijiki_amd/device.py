@@ -29,7 +29,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap", "hj_filter_lightmap",
            "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive", "hj_probe_points", "hj_bake_probes",
            "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains", "hj_probe_visibility_rays",
-           "hj_bake_probe_visibility", "hj_sample_probes_visible")
+           "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -107,6 +107,9 @@ def lib():
         L.hj_probe_visibility_rays.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), C.c_uint32, C.c_uint32, vp]
         L.hj_bake_probe_visibility.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), vp]   # (host or device pointers)
         L.hj_sample_probes_visible.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), vp, vp, vp, C.c_size_t, vp]
+        L.hj_update_probes.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeUpdate), C.c_uint32, C.POINTER(abi.RenderOpts), vp,
+                                       C.POINTER(abi.RenderStats)]
+        L.hj_update_probe_visibility.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), C.POINTER(abi.ProbeUpdate), vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -1110,6 +1113,83 @@ class Renderer:
         self._check(lib().hj_sample_probes_visible(self._h, C.byref(d), C.byref(v), vol.ctypes.data, atl.ctypes.data if atl is not None else None,
                                                    pts.ctypes.data, len(pts), out.ctypes.data))
         return out
+
+    @staticmethod
+    def _probe_update(what, n, frame, frame_stride, hysteresis, window, change):
+        """The hj_probe_update of the update calls, checked before any call.  window: (first_probe, num_probes), None: all n probes."""
+        first, num = (0, n) if window is None else (int(window[0]), int(window[1]))
+        if not (0 <= first and 0 <= num and first + num <= n):
+            raise ValueError(f"{what}: window {first} ... {first + num} of {n} probes")
+        for name, v in (("frame", frame), ("frame_stride", frame_stride)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{what}: {name} {v} is no uint32")
+        h = np.float32(hysteresis)
+        if not 0 <= h < 1:
+            raise ValueError(f"{what}: hysteresis {hysteresis} outside [0, 1)")
+        soft, hard = (np.float32(c) for c in change)
+        if not (soft >= 0 and hard >= 0):
+            raise ValueError(f"{what}: change {tuple(change)}: two thresholds >= 0 (inf: never) are needed")
+        return abi.ProbeUpdate(first, num, int(frame), int(frame_stride), float(h), float(soft), float(hard), 0)
+
+    def _update_target(self, what, array, shape):
+        """The array an update call reads and writes: a contiguous float32 torch tensor on the renderer's GPU (updated in place) or a
+        numpy array (a contiguous float32 copy is updated and returned) of `shape` -> (on_gpu, the array, its address)"""
+        if type(array).__module__.split(".")[0] == "torch":
+            if not (array.is_cuda and array.device.index == self.device and str(array.dtype) == "torch.float32" and array.is_contiguous()):
+                raise ValueError(f"{what}: a contiguous float32 tensor on cuda:{self.device} is needed")
+            if tuple(array.shape) != shape:
+                raise ValueError(f"{what}: an array of {shape} is needed (got {tuple(array.shape)})")
+            return True, array, array.data_ptr()
+        out = np.array(array, np.float32, order="C")
+        if out.shape != shape:
+            raise ValueError(f"{what}: an array of {shape} is needed (got {out.shape})")
+        return False, out, out.ctypes.data
+
+    def update_probes(self, desc, probes, spp, *, frame, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE, hysteresis, window=None,
+                      change=abi.PROBE_UPDATE_CHANGE, opts=None, stats=False):
+        """hj_update_probes: a window of a (nz, ny, nx, 28) probe volume re-baked from the uploaded scene at `spp` samples and folded
+        into `probes`.  desc: the grid as a dict of `bake_probes`' keywords (origin, spacing, count, and min_distance, seed,
+        seed_stride where they are not the defaults).  The fresh record of a probe is `bake_probes`' with the seed seed + frame *
+        frame_stride (uint32 wrap-around): give every update another `frame`.  new = old * hysteresis + fresh * (1 - hysteresis) per
+        coefficient; the validity is the fresh one, and a probe that was or becomes invalid takes the fresh coefficients alone.
+        change = (soft, hard): where the constant band moved by more than soft (hard) times its old magnitude the hysteresis drops by
+        0.15 (to 0); (inf, inf): never.  hysteresis = 0 writes the fresh bake whatever `probes` held, so a first update needs no
+        initialised volume.  window = (first_probe, num_probes) in the order p = (z * ny + y) * nx + x, None: the whole volume; probes
+        outside it keep every bit.  A contiguous float32 torch tensor on the renderer's GPU is updated in place (torch's current
+        stream is synchronised first) and returned; a numpy array gives an updated copy, of which the window alone travelled.
+        stats=True: returns (probes, the gather's statistics dict)."""
+        spp = int(spp)
+        if not 1 <= spp <= 65536:
+            raise ValueError(f"update_probes: spp {spp} outside [1, 65536]")
+        d = self._probe_desc("update_probes", **desc)
+        n = d.count[0] * d.count[1] * d.count[2]
+        u = self._probe_update("update_probes", n, frame, frame_stride, hysteresis, window, change)
+        on_gpu, vol, ptr = self._update_target("update_probes", probes, (d.count[2], d.count[1], d.count[0], abi.PROBE_WORDS))
+        st = abi.RenderStats()
+        if on_gpu:
+            import torch
+            d.flags = abi.PROBES_DEVICE_ARRAYS
+            torch.cuda.current_stream(vol.device).synchronize()       # (whatever wrote the tensor)
+        self._check(lib().hj_update_probes(self._h, C.byref(d), C.byref(u), spp, C.byref(opts) if opts is not None else None, ptr, C.byref(st)))
+        return (vol, stats_dict(st)) if stats else vol
+
+    def update_probe_visibility(self, desc, vis, atlas, *, frame, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE, hysteresis, window=None):
+        """hj_update_probe_visibility: a window of a (nz, ny, nx, res + 2, res + 2, 2) visibility atlas re-baked from the uploaded scene
+        and folded into `atlas`.  desc as in `update_probes`; vis: a dict of `bake_probe_visibility`'s keywords (res, rays_per_texel,
+        max_distance).  Per interior texel and moment new = old * hysteresis + fresh * (1 - hysteresis), the fresh value being
+        `bake_probe_visibility`'s under the seed seed + frame * frame_stride; every border texel then copies its interior texel's new
+        value.  hysteresis = 0 writes the fresh bake whatever the atlas held.  window, tensors and numpy arrays as in `update_probes`."""
+        d = self._probe_desc("update_probe_visibility", **desc)
+        v = self._probe_vis_desc("update_probe_visibility", **vis)
+        n = d.count[0] * d.count[1] * d.count[2]
+        u = self._probe_update("update_probe_visibility", n, frame, frame_stride, hysteresis, window, (0.0, 0.0))
+        on_gpu, atl, ptr = self._update_target("update_probe_visibility", atlas, (d.count[2], d.count[1], d.count[0], v.res + 2, v.res + 2, 2))
+        if on_gpu:
+            import torch
+            d.flags, v.flags = abi.PROBES_DEVICE_ARRAYS, v.flags | abi.PROBE_VIS_DEVICE_ARRAYS
+            torch.cuda.current_stream(atl.device).synchronize()       # (whatever wrote the tensor)
+        self._check(lib().hj_update_probe_visibility(self._h, C.byref(d), C.byref(v), C.byref(u), ptr))
+        return atl
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

@@ -962,7 +962,7 @@ int hj_sample_probes(hj_context* ctx, const hj_probe_desc* desc, const float* pr
  *   device arrays; m above 2^31 - 1; a bad position or normal in host arrays.  A null context: HJ_ERR_DEVICE in a process without a
  *   HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: hj_trace_rays' - an asynchronous frame in flight, frames submitted with
  *   HJ_RENDER_NO_DRAIN not yet drained, and for hj_bake_probe_visibility no scene.  A refused call writes nothing.
- * Not here: no adaptive bake, no blending of an atlas over time (the paper's hysteresis), no multi-GPU split, no CLI. */
+ * Not here: no adaptive bake, no multi-GPU split, no CLI.  (Blending an atlas over time: hj_update_probe_visibility, below.) */
 #define HJ_PROBE_VIS_DEVICE_ARRAYS 1u
 #define HJ_PROBE_VIS_NO_BACKFACE 2u    /* look-up only */
 #define HJ_PROBE_VIS_NO_CHEBYSHEV 4u   /* look-up only */
@@ -980,6 +980,62 @@ int hj_probe_visibility_rays(hj_context* ctx, const hj_probe_desc* desc, const h
 int hj_bake_probe_visibility(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, float* atlas /* n x HJ_PROBE_VIS_WORDS(res) */);
 int hj_sample_probes_visible(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes /* n x 28 */,
                              const float* atlas, const float* points /* m x 8 */, size_t m, float* out /* m x 4 */);
+
+/* Probe updates (ABI 0.22): a window of a probe volume, or of its visibility atlas, re-baked from the uploaded scene under a frame's
+ * own seeds and folded into the values the caller holds - the temporal blend ("hysteresis") of Majercik et al. 2019.  A scene that
+ * changes (hj_scene_update_shapes, hj_refit_bvh_device) is followed with a few samples per probe per frame instead of a whole bake at
+ * full spp, and a large volume is spread over several frames window by window.  No counterpart in the reference.  The numeric rules
+ * are the probe volumes' above: float32, one rounding per operation, no contraction; min and max are minNum and maxNum; a comparison
+ * with a NaN is false.
+ *
+ * The window and the fresh value.  The window is the probes first_probe ... first_probe + num_probes - 1 of desc's volume.  Let desc' be
+ *   desc with seed' = seed + frame * frame_stride (uint32 wrap-around) in place of seed.  The fresh record F of probe p is record p of
+ *   hj_bake_probes(desc', spp, opts); the fresh interior texels of probe p are those of hj_bake_probe_visibility(desc', vis).  A gather
+ *   point carries its own seed, seed' + p * seed_stride, and ray r of probe p has the seed seed' + p * seed_stride + r: F does not
+ *   depend on the window, nor on which other probes are updated with p.
+ *
+ * hj_update_probes: per probe of the window, with O the record now in `probes`, h = hysteresis and F[27] as hj_bake_probes defines it:
+ *       new[27] = F[27];   keep = (O[27] > 0.0f) && (F[27] > 0.0f)  (a NaN compares false);   hh = 0.0f without keep; with it
+ *       d = max(max(|F[0] - O[0]|, |F[1] - O[1]|), |F[2] - O[2]|);   m = max(max(|O[0]|, |O[1]|), |O[2]|)  - the constant band's three channels;
+ *       hh = h;   if d > change_hard * m: hh = 0.0f;   else if d > change_soft * m: hh = max(h - 0.15f, 0.0f);
+ *       for k = 0 ... 26:  new[k] = F[k] if hh == 0.0f, otherwise new[k] = O[k] * hh + F[k] * (1.0f - hh)  - two products and one sum,
+ *       1.0f - hh formed once.
+ *   The step 0.15 is the paper's, and its 0.25 and 0.8 are the Python wrapper's defaults for change_soft and change_hard: the paper's
+ *   starting point, not values tuned here.  An infinite threshold never triggers (with m == 0 its product is a NaN, and the comparison false).
+ *   With h == 0 the window becomes the fresh bake whatever the memory held before - NaN included, so a volume needs no
+ *   initialisation.  A probe that was or becomes invalid never mixes coefficients.  Probes outside the window keep every bit.
+ *   stats (may be NULL): the gather's.  spp and opts have hj_bake_probes' domain and refusals.
+ *
+ * hj_update_probe_visibility: per probe of the window, per interior texel, per moment, with O the old interior value and F the fresh one:
+ *       new = F if h == 0.0f, otherwise new = O * h + F * (1.0f - h).
+ *   Every border texel is then the new value of the interior texel it copies (the bake's mapping, under "The atlas" above).  A border
+ *   texel's old value is never read: an atlas whose border disagreed with its interior is repaired by one update.  change_soft and
+ *   change_hard are checked and not used.  A NaN in O (with h > 0) gives a NaN, of no defined sign or payload.  The call works in slabs of whole probes of at most HJ_PROBE_VIS_SLAB_RAYS rays, as the bake
+ *   does; the result does not depend on the slab size or a launch shape.
+ *
+ * Arrays: with the device-array flags of the descs `probes` and `atlas` are device pointers, 16-byte aligned, updated in place on the
+ *   context's stream.  Without them they are host arrays, of which the window's part alone is staged in, blended and copied back
+ *   (hj_update_probe_visibility: slab by slab).  The context keeps 176 bytes per probe of the window (points and records) or one slab's
+ *   rays and hits, and the staging of a host-side window or slab: memory that grows with the window, never with the volume.
+ * HJ_ERR_INVALID, checked before anything else and without a device, in this order: the refusals of hj_bake_probes (of
+ *   hj_bake_probe_visibility) up to and including the descs', in their order - a null desc, vis or array argument first -; a null
+ *   update; non-zero update flags; first_probe + num_probes (in 64 bits) above the volume's probes; a hysteresis outside [0, 1), a
+ *   NaN included; a change_soft, then a change_hard that is negative or a NaN (+inf is allowed: never); then spp == 0 or above 65536,
+ *   misaligned device arrays and the refusals of opts (hj_update_probes).  A null context and HJ_ERR_STATE as for the bakes: both calls
+ *   need a scene.  num_probes == 0: HJ_OK after all of these, nothing touched.  A refused call writes nothing.
+ * Not here: no probe relocation or classification, no adaptive update (a per-probe spp), no multi-GPU split, no CLI flag. */
+#define HJ_PROBE_UPDATE_WORDS 8u
+typedef struct hj_probe_update {
+  uint32_t first_probe, num_probes;   /* the window: probes first_probe ... first_probe + num_probes - 1, inside the volume     */
+  uint32_t frame, frame_stride;       /* this update's seeds: desc->seed + frame * frame_stride (uint32 wrap-around)            */
+  float    hysteresis;                /* h, 0 <= h < 1: the share of the old value that is kept                                 */
+  float    change_soft, change_hard;  /* >= 0, +inf allowed (= never), NaN refused; hj_update_probes only                       */
+  uint32_t flags;                     /* must be 0                                                                              */
+} hj_probe_update;                    /* 32 bytes */
+int hj_update_probes(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_update* update, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
+                     float* probes /* n x 28, read and written */, hj_render_stats* stats /* may be NULL */);
+int hj_update_probe_visibility(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const hj_probe_update* update,
+                               float* atlas /* n x HJ_PROBE_VIS_WORDS(res), read and written */);
 
 /* ------------------------------------------------------------------- probes */
 
