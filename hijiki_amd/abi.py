@@ -47,6 +47,9 @@ PROBE_UPDATE_WORDS = 8            # words of hj_probe_update
 PROBE_UPDATE_SOFT_STEP = 0.15     # what a change beyond change_soft takes off the hysteresis (Majercik et al. 2019)
 PROBE_UPDATE_CHANGE = (0.25, 0.8)  # the wrapper's defaults for change_soft, change_hard: the paper's starting point, not tuned
 PROBE_UPDATE_FRAME_STRIDE = 0x9E3779B1   # the wrapper's default frame_stride: odd, so that 2^32 frames have 2^32 seeds
+PROBE_PLACE_WORDS = 4             # words of a probe's placement: the offset (float32 x 3), the state (uint32: 0 active)
+PROBE_PLACE_NO_RELOCATE, PROBE_PLACE_NO_CLASSIFY = 1, 2   # hj_probe_place flags
+PROBE_PLACE_BACKFACE_SHARE, PROBE_PLACE_MAX_OFFSET = 0.25, 0.45   # the wrapper's defaults: the paper's and RTXGI's starting points, not tuned
 
 
 def probe_vis_words(res):
@@ -224,6 +227,12 @@ class ProbeUpdate(C.Structure):
     hj_update_probe_visibility."""
     _fields_ = [("first_probe", u32), ("num_probes", u32), ("frame", u32), ("frame_stride", u32), ("hysteresis", f32), ("change_soft", f32),
                 ("change_hard", f32), ("flags", u32)]
+
+
+class ProbePlace(C.Structure):
+    """hj_probe_place (ABI 0.23): the probe window, the frame's seeds and the thresholds of hj_place_probes."""
+    _fields_ = [("first_probe", u32), ("num_probes", u32), ("frame", u32), ("frame_stride", u32), ("min_front_distance", f32),
+                ("backface_share", f32), ("max_offset", f32), ("flags", u32)]
 
 
 class RenderStats(C.Structure):

@@ -62,6 +62,12 @@
 //                         one pass); per slab k_pvv_rays and hj_trace_rays, then k_pu_reduce (moments, blend and border in one pass)
 //                         (includes kernels/hj_probe_update.h; beside it the functions of hj_probes.h and hj_probe_vis.h, without
 //                         their kernels, and hj_num.h alone)
+//   api/probe_place.hip   hj_place_probes: per probe an offset and an active / inactive state from a slab's rays, hits and surface
+//                         records (k_pp_rays, hj_trace_rays, k_pp_reduce: one wave per probe); hj_update_probes_placed,
+//                         hj_update_probe_visibility_placed: the updates over the window's active probes, compacted in order
+//                         (k_pp_count, k_pp_scan, k_pp_scatter; k_pp_points, k_pp_resolve; k_pp_rays, k_pp_blend);
+//                         hj_sample_probes_visible_placed (k_pp_sample) (includes kernels/hj_probe_place.h; beside it the functions
+//                         of hj_probe_update.h, hj_probe_vis.h and hj_probes.h without their kernels, hj_compact.h and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -431,6 +437,12 @@ struct hj_context {
   // hj_update_probe_visibility (api/probe_update.hip) uses rays, hits and - for host arrays - atlas, each for one slab of its window.
   struct ProbeVis { hjapi::DevBuf rays, hits, atlas, volume, in_points, out; } probe_vis;
 
+  // hj_place_probes and the placed calls (api/probe_place.hip): one slab's surface records (64 bytes a ray) beside probe_vis' rays
+  // and hits; the staging of a host-side placement (16 bytes a probe: a slab's, a window's, the look-up's whole); the tile counts and
+  // the list of a window's active probes (4 bytes a probe).  The placed updates use probes' and probe_vis' buffers as the updates do,
+  // a host-side atlas staged for the whole window.  Grown on demand, reused by every call, freed with the context.
+  struct ProbePlace { hjapi::DevBuf surface, placement, counts, list; } probe_place;
+
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
   hjapi::Tuning tuning;
@@ -494,6 +506,15 @@ void probe_points_enqueue(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, u
 // api/probe_visibility.hip: what hj_bake_probe_visibility refuses of the two descs, in the header's order -> g, n, v; and the enqueue
 // of the bake's rays for the probes first ... first + probes - 1 (at most a slab's) under `seed`
 int probe_vis_bake_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, const hj_probe_vis_desc* vis, hj::PvGrid& g, uint32_t& n, hj::PvvMap& v);
+// ... and the host side of hj_sample_probes_visible, which api/probe_place.hip's placed look-up enters with its placement and a launch
+// of its own kernel (placed == nullptr: no placement); probe_place_check_offsets: a host-side placement's offsets must be finite
+using ProbeVisSampleLaunch = void (*)(hipStream_t s, uint32_t blocks, const hj::PvGrid& g, const hj::PvvMap& v, const float4* d_probes, const float2* d_atlas,
+                                      const float4* d_place, const float4* d_points, uint32_t m, float4* d_out);
+int probe_vis_sample(hj_context* ctx, const char* fn, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes, const float* atlas,
+                     const float* points, size_t m, float* out, const float* placement, ProbeVisSampleLaunch placed);
+int probe_place_check_offsets(hj_context* ctx, const char* fn, const float* placement, uint32_t first, uint32_t num);
+// api/probe_update.hip: what the updates refuse of an hj_probe_update behind the descs' refusals, in the header's order (n: the volume's probes)
+int probe_update_check(hj_context* ctx, const char* fn, const hj_probe_update* u, uint32_t n);
 void probe_vis_rays_enqueue(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t probes,
                             float4* d_rays);
 // The light-map filter for both of its entry points (api/lightmap_filter.hip):

@@ -15,11 +15,10 @@
 
 using namespace hjapi;
 
-namespace {
-
-// What both entry points refuse of an update, without a device, behind the descs' refusals (fn: the entry point's name; n: the
-// volume's probes)
-int check_update(hj_context* ctx, const char* fn, const hj_probe_update* u, uint32_t n) {
+namespace hjapi {   // for api/probe_place.hip too (hj_internal.h)
+// What both entry points - and api/probe_place.hip's placed ones - refuse of an update, without a device, behind the descs' refusals
+// (fn: the entry point's name; n: the volume's probes)
+int probe_update_check(hj_context* ctx, const char* fn, const hj_probe_update* u, uint32_t n) {
   if (!u) return set_error(ctx, HJ_ERR_INVALID, "%s: null update", fn);
   if (u->flags != 0u) return set_error(ctx, HJ_ERR_INVALID, "%s: unknown update flag bits 0x%x", fn, u->flags);
   if ((uint64_t)u->first_probe + u->num_probes > n)
@@ -29,6 +28,9 @@ int check_update(hj_context* ctx, const char* fn, const hj_probe_update* u, uint
   if (!(u->change_hard >= 0.0f)) return set_error(ctx, HJ_ERR_INVALID, "%s: change_hard %g: >= 0 is needed", fn, (double)u->change_hard);
   return HJ_OK;
 }
+}  // namespace hjapi
+
+namespace {
 
 bool misaligned(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15u) != 0; }
 
@@ -45,7 +47,7 @@ int hj_update_probes(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_
   hj::PvGrid g{};
   uint32_t n = 0;
   HJ_TRY(probe_desc_check(ctx, __func__, desc, g, n));
-  HJ_TRY(check_update(ctx, __func__, upd, n));
+  HJ_TRY(probe_update_check(ctx, __func__, upd, n));
   const bool on_device = (desc->flags & HJ_PROBES_DEVICE_ARRAYS) != 0;
   if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "hj_update_probes: spp %u outside [1, 65536]", spp);
   if (on_device && misaligned(probes)) return set_error(ctx, HJ_ERR_INVALID, "hj_update_probes: device arrays must be 16-byte aligned");
@@ -89,7 +91,7 @@ int hj_update_probe_visibility(hj_context* ctx, const hj_probe_desc* desc, const
   hj::PvvMap v{};
   uint32_t n = 0;
   HJ_TRY(probe_vis_bake_check(ctx, __func__, desc, vis, g, n, v));
-  HJ_TRY(check_update(ctx, __func__, upd, n));
+  HJ_TRY(probe_update_check(ctx, __func__, upd, n));
   const bool on_device = (vis->flags & HJ_PROBE_VIS_DEVICE_ARRAYS) != 0;
   if (on_device && misaligned(atlas)) return set_error(ctx, HJ_ERR_INVALID, "hj_update_probe_visibility: device arrays must be 16-byte aligned");
   HJ_TRY(query_gate(ctx, __func__));

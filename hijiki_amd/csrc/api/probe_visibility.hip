@@ -60,13 +60,86 @@ void enqueue_rays(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, uin
 
 }  // namespace
 
-namespace hjapi {   // for api/probe_update.hip (hj_internal.h)
+namespace hjapi {   // for api/probe_update.hip and api/probe_place.hip (hj_internal.h)
 int probe_vis_bake_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, const hj_probe_vis_desc* vis, hj::PvGrid& g, uint32_t& n, hj::PvvMap& v) {
   return check_descs(ctx, fn, Call::kBake, d, vis, g, n, v);
 }
 void probe_vis_rays_enqueue(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t probes,
                             float4* d_rays) {
   enqueue_rays(ctx, g, v, seed, seed_stride, first, probes, d_rays);
+}
+// A host-side placement: the offsets of the probes first ... first + num - 1 must be finite
+int probe_place_check_offsets(hj_context* ctx, const char* fn, const float* placement, uint32_t first, uint32_t num) {
+  for (uint32_t p = first; p < first + num; p++)
+    for (int a = 0; a < 3; a++)
+      if (!std::isfinite(placement[HJ_PROBE_PLACE_WORDS * (size_t)p + a])) return set_error(ctx, HJ_ERR_INVALID, "%s: probe %u has a non-finite offset", fn, p);
+  return HJ_OK;
+}
+
+// The host side of hj_sample_probes_visible and, with a launch of its kernel, of hj_sample_probes_visible_placed (api/probe_place.hip):
+// one text of the refusals, the staging and the launch shape.  placed == nullptr: no placement (the argument is not looked at).
+int probe_vis_sample(hj_context* ctx, const char* fn, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes, const float* atlas,
+                     const float* points, size_t m, float* out, const float* placement, ProbeVisSampleLaunch placed) {
+  const uint32_t both_off = HJ_PROBE_VIS_NO_BACKFACE | HJ_PROBE_VIS_NO_CHEBYSHEV;
+  const bool reads_atlas = vis && (vis->flags & both_off) != both_off;
+  const bool no_place = placed && !placement;            // (a null placement is refused whatever m is)
+  if (!desc || !vis || no_place || (m != 0 && (!probes || (reads_atlas && !atlas) || !points || !out)))
+    return set_error(ctx, HJ_ERR_INVALID, "%s: null %s", fn,
+                     !desc ? "desc" : !vis ? "vis" : no_place ? "placement" : !probes ? "probes" : (reads_atlas && !atlas) ? "atlas" : !points ? "points" : "out");
+  hj::PvGrid g{};
+  hj::PvvMap v{};
+  uint32_t np = 0;
+  HJ_TRY(check_descs(ctx, fn, Call::kSample, desc, vis, g, np, v));
+  const bool on_device = (vis->flags & HJ_PROBE_VIS_DEVICE_ARRAYS) != 0;
+  if (on_device && m != 0 && (misaligned(probes, reads_atlas ? atlas : nullptr, points, out) || (placed && misaligned(placement))))
+    return set_error(ctx, HJ_ERR_INVALID, "%s: device arrays must be 16-byte aligned", fn);
+  if (m > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "%s: %zu points, at most 2^31 - 1 a call", fn, m);
+  if (!on_device) {                            // (device arrays: the caller's contract; the kernel clamps whatever it is given)
+    for (size_t i = 0; i < m; i++) {
+      const float* p = points + 8 * i;
+      for (int k = 0; k < 6; k++)
+        if (!std::isfinite(p[k]))
+          return set_error(ctx, HJ_ERR_INVALID, "%s: point %zu has a non-finite %s", fn, i, k < 3 ? "position" : "normal");
+      if (p[3] == 0.f && p[4] == 0.f && p[5] == 0.f) return set_error(ctx, HJ_ERR_INVALID, "%s: point %zu has an all-zero normal", fn, i);
+    }
+    if (placed && m != 0) HJ_TRY(probe_place_check_offsets(ctx, fn, placement, 0u, np));
+  }
+  HJ_TRY(context_gate(ctx, fn));
+  if (m == 0) return HJ_OK;
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const float4 *d_probes = reinterpret_cast<const float4*>(probes), *d_points = reinterpret_cast<const float4*>(points);
+  const float2* d_atlas = reads_atlas ? reinterpret_cast<const float2*>(atlas) : nullptr;
+  const float4* d_place = reinterpret_cast<const float4*>(placement);
+  float4* d_out = reinterpret_cast<float4*>(out);
+  if (!on_device) {
+    hj_context::ProbeVis& pv = ctx->probe_vis;
+    const size_t atlas_bytes = sizeof(float) * HJ_PROBE_VIS_WORDS(v.res) * (size_t)np;
+    HJ_TRY(dev_alloc(ctx, pv.volume, sizeof(float4) * hj::kPvVec * (size_t)np));
+    if (reads_atlas) HJ_TRY(dev_alloc(ctx, pv.atlas, atlas_bytes));
+    HJ_TRY(dev_alloc(ctx, pv.in_points, sizeof(float4) * 2 * m));
+    HJ_TRY(dev_alloc(ctx, pv.out, sizeof(float4) * m));
+    if (placed) HJ_TRY(dev_alloc(ctx, ctx->probe_place.placement, sizeof(float4) * (size_t)np));   // (the placement whole, 16 bytes a probe)
+    hipError_t e = hipMemcpyAsync(pv.volume.p, probes, sizeof(float4) * hj::kPvVec * (size_t)np, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && reads_atlas) e = hipMemcpyAsync(pv.atlas.p, atlas, atlas_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(pv.in_points.p, points, sizeof(float4) * 2 * m, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && placed) {
+      e = hipMemcpyAsync(ctx->probe_place.placement.p, placement, sizeof(float4) * (size_t)np, hipMemcpyHostToDevice, s);
+      d_place = static_cast<const float4*>(ctx->probe_place.placement.p);
+    }
+    if (e != hipSuccess) return drain(ctx, fn, e);
+    d_probes = static_cast<const float4*>(pv.volume.p);
+    d_atlas = reads_atlas ? static_cast<const float2*>(pv.atlas.p) : nullptr;
+    d_points = static_cast<const float4*>(pv.in_points.p);
+    d_out = static_cast<float4*>(pv.out.p);
+  }
+  // enough workgroups to fill the device, no more than the points need; the kernel strides over the rest
+  const uint32_t blocks = (uint32_t)std::min<size_t>((m + hj::kPvvThreads - 1u) / hj::kPvvThreads, (size_t)ctx->num_cus * 8u);
+  if (placed) placed(s, blocks, g, v, d_probes, d_atlas, d_place, d_points, (uint32_t)m, d_out);
+  else hipLaunchKernelGGL(hj::k_pvv_sample, dim3(blocks), dim3(hj::kPvvThreads), 0, s, g, v, d_probes, d_atlas, d_points, (uint32_t)m, d_out);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d_out, sizeof(float4) * m, hipMemcpyDeviceToHost, s);
+  return drain(ctx, fn, e);
 }
 }  // namespace hjapi
 
@@ -136,57 +209,7 @@ int hj_bake_probe_visibility(hj_context* ctx, const hj_probe_desc* desc, const h
 
 int hj_sample_probes_visible(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes, const float* atlas,
                              const float* points, size_t m, float* out) {
-  const uint32_t both_off = HJ_PROBE_VIS_NO_BACKFACE | HJ_PROBE_VIS_NO_CHEBYSHEV;
-  const bool reads_atlas = vis && (vis->flags & both_off) != both_off;
-  if (!desc || !vis || (m != 0 && (!probes || (reads_atlas && !atlas) || !points || !out)))
-    return set_error(ctx, HJ_ERR_INVALID, "hj_sample_probes_visible: null %s",
-                     !desc ? "desc" : !vis ? "vis" : !probes ? "probes" : (reads_atlas && !atlas) ? "atlas" : !points ? "points" : "out");
-  hj::PvGrid g{};
-  hj::PvvMap v{};
-  uint32_t np = 0;
-  HJ_TRY(check_descs(ctx, __func__, Call::kSample, desc, vis, g, np, v));
-  const bool on_device = (vis->flags & HJ_PROBE_VIS_DEVICE_ARRAYS) != 0;
-  if (on_device && m != 0 && misaligned(probes, reads_atlas ? atlas : nullptr, points, out))
-    return set_error(ctx, HJ_ERR_INVALID, "hj_sample_probes_visible: device arrays must be 16-byte aligned");
-  if (m > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_sample_probes_visible: %zu points, at most 2^31 - 1 a call", m);
-  if (!on_device) {                            // (device arrays: the caller's contract; the kernel clamps whatever it is given)
-    for (size_t i = 0; i < m; i++) {
-      const float* p = points + 8 * i;
-      for (int k = 0; k < 6; k++)
-        if (!std::isfinite(p[k]))
-          return set_error(ctx, HJ_ERR_INVALID, "hj_sample_probes_visible: point %zu has a non-finite %s", i, k < 3 ? "position" : "normal");
-      if (p[3] == 0.f && p[4] == 0.f && p[5] == 0.f) return set_error(ctx, HJ_ERR_INVALID, "hj_sample_probes_visible: point %zu has an all-zero normal", i);
-    }
-  }
-  HJ_TRY(context_gate(ctx, __func__));
-  if (m == 0) return HJ_OK;
-  HJ_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const float4 *d_probes = reinterpret_cast<const float4*>(probes), *d_points = reinterpret_cast<const float4*>(points);
-  const float2* d_atlas = reads_atlas ? reinterpret_cast<const float2*>(atlas) : nullptr;
-  float4* d_out = reinterpret_cast<float4*>(out);
-  if (!on_device) {
-    hj_context::ProbeVis& pv = ctx->probe_vis;
-    const size_t atlas_bytes = sizeof(float) * HJ_PROBE_VIS_WORDS(v.res) * (size_t)np;
-    HJ_TRY(dev_alloc(ctx, pv.volume, sizeof(float4) * hj::kPvVec * (size_t)np));
-    if (reads_atlas) HJ_TRY(dev_alloc(ctx, pv.atlas, atlas_bytes));
-    HJ_TRY(dev_alloc(ctx, pv.in_points, sizeof(float4) * 2 * m));
-    HJ_TRY(dev_alloc(ctx, pv.out, sizeof(float4) * m));
-    hipError_t e = hipMemcpyAsync(pv.volume.p, probes, sizeof(float4) * hj::kPvVec * (size_t)np, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && reads_atlas) e = hipMemcpyAsync(pv.atlas.p, atlas, atlas_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(pv.in_points.p, points, sizeof(float4) * 2 * m, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return drain(ctx, __func__, e);
-    d_probes = static_cast<const float4*>(pv.volume.p);
-    d_atlas = reads_atlas ? static_cast<const float2*>(pv.atlas.p) : nullptr;
-    d_points = static_cast<const float4*>(pv.in_points.p);
-    d_out = static_cast<float4*>(pv.out.p);
-  }
-  // enough workgroups to fill the device, no more than the points need; the kernel strides over the rest
-  const uint32_t blocks = (uint32_t)std::min<size_t>((m + hj::kPvvThreads - 1u) / hj::kPvvThreads, (size_t)ctx->num_cus * 8u);
-  hipLaunchKernelGGL(hj::k_pvv_sample, dim3(blocks), dim3(hj::kPvvThreads), 0, s, g, v, d_probes, d_atlas, d_points, (uint32_t)m, d_out);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d_out, sizeof(float4) * m, hipMemcpyDeviceToHost, s);
-  return drain(ctx, __func__, e);
+  return probe_vis_sample(ctx, __func__, desc, vis, probes, atlas, points, m, out, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 // order.  The fresh values are the bakes' own texts: pv_resolve_record (hj_probes.h), pvv_moments and pvv_border_source
 // (hj_probe_vis.h); neither header's kernels are compiled here.
 //   pu_blend      THE text of one blend: old * hh + fresh * (1 - hh), the fresh value itself at hh == 0
+//   pu_resolve_probe, pu_reduce_texel  THE texts of the two kernels' threads, for them and for hj_probe_place.h's placed kernels, which
+//                 find their probe through a list (the kernels are left out under HJ_PROBE_UPDATE_NO_KERNELS)
 //   k_pu_resolve  one thread per probe of the window: the gather's record resolved and blended into the probe's record in place
 //   k_pu_reduce   one thread per INTERIOR texel of a slab's probes: its rays' moments blended into the texel in place, and the result
 //                 written to every border texel that copies it
@@ -30,18 +32,15 @@ HJ_DEV float pu_blend(float o, float f, float hh, float g) { return (hh == 0.0f)
 // each, read and written.  F = pv_resolve_record; O the old record.  keep = O[27] > 0 && F[27] > 0 (a NaN compares false); without
 // it hh = 0.  Otherwise d = max |F[c] - O[c]| and m = max |O[c]| over the constant band's three channels, hh = h, 0 if d > hard * m,
 // else max(h - 0.15f, 0) if d > soft * m.  Word k < 27: pu_blend(O[k], F[k], hh); word 27: F[27].
-__global__ __launch_bounds__(kPuThreads) void k_pu_resolve(const float4* __restrict__ records, uint32_t n, float s, float min_distance, float h, float soft,
-                                                          float hard, float4* __restrict__ probes) {
-  const uint32_t i = blockIdx.x * kPuThreads + threadIdx.x;
-  if (i >= n) return;
-  float4* __restrict__ rec = probes + kPvVec * (size_t)i;
+// (THE text of a thread: record, the probe's 9 float4 of the gather; rec, its kPvVec float4 in the volume.)
+HJ_DEV void pu_resolve_probe(const float4* __restrict__ record, float s, float min_distance, float h, float soft, float hard, float4* __restrict__ rec) {
   float o[28], f[28];
 #pragma unroll
   for (uint32_t m = 0; m < kPvVec; m++) {
     const float4 t = rec[m];
     o[4 * m] = t.x; o[4 * m + 1] = t.y; o[4 * m + 2] = t.z; o[4 * m + 3] = t.w;
   }
-  pv_resolve_record(records + 9 * (size_t)i, s, min_distance, f);
+  pv_resolve_record(record, s, min_distance, f);
   float hh = 0.0f;
   if (o[27] > 0.0f && f[27] > 0.0f) {
     const float d = f_max(f_max(__builtin_fabsf(f[0] - o[0]), __builtin_fabsf(f[1] - o[1])), __builtin_fabsf(f[2] - o[2]));
@@ -61,13 +60,11 @@ __global__ __launch_bounds__(kPuThreads) void k_pu_resolve(const float4* __restr
 // read and written.  Thread i: interior texel t = i % res^2 of probe i / res^2.  Its border copies are the inverse of
 // pvv_border_source: row 0 mirrors interior row 0 in x and row T - 1 the last row (border x = res - tx), column 0 mirrors interior
 // column 0 in y and column T - 1 the last column (border y = res - ty), a corner is the diagonally opposite interior corner.
-__global__ __launch_bounds__(kPuThreads) void k_pu_reduce(PvvMap v, const float4* __restrict__ hits, uint32_t probes, float h, float2* __restrict__ atlas) {
-  const uint32_t res = v.res, T = res + 2u, last = res - 1u, per = res * res;
-  const uint32_t i = blockIdx.x * kPuThreads + threadIdx.x;
-  if (i >= probes * per) return;
-  const uint32_t p = i / per, t = i % per, tx = t % res, ty = t / res;
-  float2* __restrict__ map = atlas + (size_t)p * (T * T);
-  const float2 fr = pvv_moments(v, hits + (size_t)i * v.s);
+// (THE text of a thread: h4, the v.s hit records of interior texel t's rays; map, the probe's (res + 2)^2 float2.)
+HJ_DEV void pu_reduce_texel(const PvvMap& v, const float4* __restrict__ h4, uint32_t t, float h, float2* __restrict__ map) {
+  const uint32_t res = v.res, T = res + 2u, last = res - 1u;
+  const uint32_t tx = t % res, ty = t / res;
+  const float2 fr = pvv_moments(v, h4);
   const float2 old = map[(ty + 1u) * T + (tx + 1u)];
   const float g = 1.0f - h;
   const float2 nv = make_float2(pu_blend(old.x, fr.x, h, g), pu_blend(old.y, fr.y, h, g));
@@ -79,5 +76,21 @@ __global__ __launch_bounds__(kPuThreads) void k_pu_reduce(PvvMap v, const float4
   if (x1) map[(res - ty) * T + (T - 1u)] = nv;                  // border (T - 1, res - ty)
   if ((x0 || x1) && (y0 || y1)) map[(y0 ? T - 1u : 0u) * T + (x0 ? T - 1u : 0u)] = nv;   // the diagonally opposite corner of the border
 }
+
+#ifndef HJ_PROBE_UPDATE_NO_KERNELS   // (hj_probe_place.h takes the functions above and leaves the kernels to api/probe_update.hip)
+__global__ __launch_bounds__(kPuThreads) void k_pu_resolve(const float4* __restrict__ records, uint32_t n, float s, float min_distance, float h, float soft,
+                                                          float hard, float4* __restrict__ probes) {
+  const uint32_t i = blockIdx.x * kPuThreads + threadIdx.x;
+  if (i >= n) return;
+  pu_resolve_probe(records + 9 * (size_t)i, s, min_distance, h, soft, hard, probes + kPvVec * (size_t)i);
+}
+
+__global__ __launch_bounds__(kPuThreads) void k_pu_reduce(PvvMap v, const float4* __restrict__ hits, uint32_t probes, float h, float2* __restrict__ atlas) {
+  const uint32_t per = v.res * v.res, T = v.res + 2u;
+  const uint32_t i = blockIdx.x * kPuThreads + threadIdx.x;
+  if (i >= probes * per) return;
+  pu_reduce_texel(v, hits + (size_t)i * v.s, i % per, h, atlas + (size_t)(i / per) * (T * T));
+}
+#endif  // HJ_PROBE_UPDATE_NO_KERNELS
 
 }  // namespace hj

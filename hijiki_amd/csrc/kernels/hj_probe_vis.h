@@ -7,6 +7,8 @@
 //   pvv_position    a probe's position from its index: k_pv_points' expression
 //   pvv_oct_decode  a point of the octahedral square [-1, 1]^2 to its (unnormalised) direction;  pvv_oct_encode: the way back
 //   pvv_border_source  THE text of the border: the interior texel an atlas texel copies;  pvv_moments: THE text of a texel's two moments
+//   pvv_ray         THE text of a bake ray: sample r of probe p from a given origin (k_pvv_rays; hj_probe_place.h's k_pp_rays)
+//   pvv_corner_fetch  THE text of a corner's Chebyshev loads (k_pvv_sample; hj_probe_place.h's k_pp_sample)
 //   (the kernels are left out under HJ_PROBE_VIS_NO_KERNELS: a unit that wants the functions above alone)
 //   k_pvv_rays      one thread per ray: hj_trace_rays' record of sample k of a texel of a probe
 //   k_pvv_reduce    one thread per atlas texel, border included: the two moments of its s distances, summed in ascending k
@@ -90,6 +92,40 @@ HJ_DEV float2 pvv_moments(const PvvMap& v, const float4* __restrict__ h) {
   return make_float2(a1 / (float)v.s, a2 / (float)v.s);
 }
 
+// THE text of a bake ray: sample r of probe p (seed + p * seed_stride + r) from the origin o -> rec[0], rec[1], hj_trace_rays' record
+// (origin.xyz, dir.x | dir.yz, tMin = 0, tMax = max_distance).
+HJ_DEV void pvv_ray(const PvvMap& v, uint32_t seed, uint32_t seed_stride, uint32_t p, uint32_t r, v3 o, float4* __restrict__ rec) {
+  const uint32_t t = r / v.s, tx = t % v.res, ty = t / v.res;
+  uint32_t state = rng_seed(seed + p * seed_stride + r);
+  const float u = rng_float(state), w = rng_float(state);
+  const float scale = 2.0f / (float)v.res;
+  const float ex = ((float)tx + u) * scale - 1.0f, ey = ((float)ty + w) * scale - 1.0f;
+  const v3 d = normalize3(pvv_oct_decode(ex, ey));
+  rec[0] = make_float4(o.x, o.y, o.z, d.x);
+  rec[1] = make_float4(d.y, d.z, 0.0f, v.max_distance);
+}
+
+// THE text of one corner's loads for the Chebyshev factor, for k_pvv_sample and hj_probe_place.h's k_pp_sample (P: the corner's
+// probe position, m: its map): whether the factor applies, rr, the bilinear weights and the four texels.  (Of the look-up's three
+// per-corner pieces this is the one both kernels call: with it k_pvv_sample keeps its 228 VGPRs; the back-face factor or the bound as
+// functions too gave 226 or 230 - DESIGN.md 4, "Probe placement".)
+HJ_DEV void pvv_corner_fetch(v3 xb, v3 P, float fres, uint32_t T, const float2* __restrict__ m, bool& away, float& rr, float& tfx, float& tfy, float2& t00,
+                             float2& t10, float2& t01, float2& t11) {
+  const v3 e = xb - P;
+  away = !(e.x == 0.0f && e.y == 0.0f && e.z == 0.0f);
+  rr = len3(e);
+  float px, py;
+  pvv_oct_encode(e, px, py);
+  const float ax = (px * 0.5f + 0.5f) * fres + 0.5f, ay = (py * 0.5f + 0.5f) * fres + 0.5f;
+  uint32_t ix0, ix1, iy0, iy1;
+  pv_axis(ax, 0.0f, 1.0f, T, ix0, ix1, tfx);
+  pv_axis(ay, 0.0f, 1.0f, T, iy0, iy1, tfy);
+  t00 = m[iy0 * T + ix0];
+  t10 = m[iy0 * T + ix1];
+  t01 = m[iy1 * T + ix0];
+  t11 = m[iy1 * T + ix1];
+}
+
 #ifndef HJ_PROBE_VIS_NO_KERNELS   // (hj_probe_update.h takes the functions above and leaves the kernels to api/probe_visibility.hip)
 // rays: count records of two float4 (origin.xyz, dir.x | dir.yz, tMin = 0, tMax = max_distance); ray i of the launch is ray
 // r = i % (res^2 s) of probe first + i / (res^2 s).  (count <= kPvvSlabRays or a caller's window, below 2^32 either way.)
@@ -99,15 +135,7 @@ __global__ __launch_bounds__(kPvvThreads) void k_pvv_rays(PvGrid g, PvvMap v, ui
   if (i >= count) return;
   const uint32_t per = v.res * v.res * v.s;
   const uint32_t p = first + i / per, r = i % per;
-  const uint32_t t = r / v.s, tx = t % v.res, ty = t / v.res;
-  uint32_t state = rng_seed(seed + p * seed_stride + r);
-  const float u = rng_float(state), w = rng_float(state);
-  const float scale = 2.0f / (float)v.res;
-  const float ex = ((float)tx + u) * scale - 1.0f, ey = ((float)ty + w) * scale - 1.0f;
-  const v3 d = normalize3(pvv_oct_decode(ex, ey));
-  const v3 o = pvv_position(g, p);
-  rays[2 * (size_t)i] = make_float4(o.x, o.y, o.z, d.x);
-  rays[2 * (size_t)i + 1] = make_float4(d.y, d.z, 0.0f, v.max_distance);
+  pvv_ray(v, seed, seed_stride, p, r, pvv_position(g, p), rays + 2 * (size_t)i);
 }
 
 // hits: hj_trace_rays' records of the slab's rays (probes * res^2 * s float4); atlas: the slab's part, probes * (res + 2)^2 float2.
@@ -161,22 +189,7 @@ __global__ __launch_bounds__(kPvvThreads) void k_pvv_sample(PvGrid g, PvvMap v, 
         wb[c] = h * h + 0.2f;
       }
       away[c] = false;
-      if (chebyshev) {
-        const v3 e = xb - P;
-        away[c] = !(e.x == 0.0f && e.y == 0.0f && e.z == 0.0f);
-        rr[c] = len3(e);
-        float px, py;
-        pvv_oct_encode(e, px, py);
-        const float ax = (px * 0.5f + 0.5f) * fres + 0.5f, ay = (py * 0.5f + 0.5f) * fres + 0.5f;
-        uint32_t ix0, ix1, iy0, iy1;
-        pv_axis(ax, 0.0f, 1.0f, T, ix0, ix1, tfx[c]);
-        pv_axis(ay, 0.0f, 1.0f, T, iy0, iy1, tfy[c]);
-        const float2* __restrict__ m = atlas + (size_t)p * (T * T);
-        t00[c] = m[iy0 * T + ix0];
-        t10[c] = m[iy0 * T + ix1];
-        t01[c] = m[iy1 * T + ix0];
-        t11[c] = m[iy1 * T + ix1];
-      }
+      if (chebyshev) pvv_corner_fetch(xb, P, fres, T, atlas + (size_t)p * (T * T), away[c], rr[c], tfx[c], tfy[c], t00[c], t10[c], t01[c], t11[c]);
     }
     float w[8], wsum = 0.0f;
 #pragma unroll

@@ -29,7 +29,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_trace_irradiance", "hj_optimize_bvh_device", "hj_lightmap_texels", "hj_bake_lightmap", "hj_filter_lightmap",
            "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive", "hj_probe_points", "hj_bake_probes",
            "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains", "hj_probe_visibility_rays",
-           "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility")
+           "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
+           "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -110,6 +111,11 @@ def lib():
         L.hj_update_probes.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeUpdate), C.c_uint32, C.POINTER(abi.RenderOpts), vp,
                                        C.POINTER(abi.RenderStats)]
         L.hj_update_probe_visibility.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), C.POINTER(abi.ProbeUpdate), vp]
+        L.hj_place_probes.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), C.POINTER(abi.ProbePlace), vp]
+        L.hj_update_probes_placed.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeUpdate), C.c_uint32, C.POINTER(abi.RenderOpts), vp, vp,
+                                              C.POINTER(abi.RenderStats)]
+        L.hj_update_probe_visibility_placed.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), C.POINTER(abi.ProbeUpdate), vp, vp]
+        L.hj_sample_probes_visible_placed.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), vp, vp, vp, C.c_size_t, vp, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -1058,14 +1064,16 @@ class Renderer:
         return atlas
 
     def sample_probes_visible(self, volume, atlas, origin, spacing, points, normal_bias=0.0, backface=True, chebyshev=True, normals=None,
-                              device=None):
+                              device=None, placement=None):
         """hj_sample_probes_visible: `sample_probes` with the weights against light leaks -> (n, 4) float32.  Each of the eight probes
         about a point is weighted further by a back-face factor (((dot(direction to the probe, normal) + 1) / 2)^2 + 0.2: probes
         behind the surface count less) and by Chebyshev's bound, cubed and at least 0.05, on the share of the probe's rays that reach
         as far as the point moved `normal_bias` along its normal, from the two moments `atlas` (`bake_probe_visibility` on the same
         grid: (nz, ny, nx, res + 2, res + 2, 2); res comes from its shape) holds in the point's direction.  backface=False /
         chebyshev=False switch a factor off; with both off atlas may be None and the result is `sample_probes`'.  volume, points,
-        normals and the numpy / torch rules as in `sample_probes`."""
+        normals and the numpy / torch rules as in `sample_probes`.  placement (None: the grid as it is): the (nz, ny, nx, 4) array of
+        `place_probes`, of the volume's kind - hj_sample_probes_visible_placed: both factors see a probe where its offset put it, and
+        an inactive probe counts nothing."""
         on_gpu = type(volume).__module__.split(".")[0] == "torch" if device is None else bool(device)
         if volume.ndim != 4 or volume.shape[3] != abi.PROBE_WORDS:
             raise ValueError(f"sample_probes_visible: a volume of (nz, ny, nx, {abi.PROBE_WORDS}) is needed (got {tuple(volume.shape)})")
@@ -1081,6 +1089,8 @@ class Renderer:
             res = int(atlas.shape[3]) - 2
         d = self._probe_desc("sample_probes_visible", origin, spacing, count, device=on_gpu)
         v = self._probe_vis_desc("sample_probes_visible", res, normal_bias=normal_bias, backface=backface, chebyshev=chebyshev, device=on_gpu)
+        if placement is not None:
+            _, placement, place_ptr = self._placement("sample_probes_visible", placement, d, on_gpu)
         if normals is not None:
             if points.ndim != 2 or points.shape[1] != 3 or tuple(normals.shape) != tuple(points.shape):
                 raise ValueError("sample_probes_visible: with normals, points and normals are (n, 3) each")
@@ -1089,7 +1099,7 @@ class Renderer:
         if on_gpu:
             import torch
             for name, t in ((("volume", volume), ("points", points)) + ((("atlas", atlas),) if atlas is not None else ())
-                            + ((("normals", normals),) if normals is not None else ())):
+                            + ((("normals", normals),) if normals is not None else ())):  # (a placement: checked by _placement)
                 if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous()):
                     raise ValueError(f"sample_probes_visible: {name} must be a contiguous float32 tensor on cuda:{self.device}")
             if normals is not None:
@@ -1097,6 +1107,11 @@ class Renderer:
             n = int(points.shape[0])
             out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
             torch.cuda.current_stream(points.device).synchronize()    # (the allocations and whatever wrote the tensors)
+            if placement is not None:
+                self._check(lib().hj_sample_probes_visible_placed(self._h, C.byref(d), C.byref(v), volume.data_ptr(),
+                                                                  atlas.data_ptr() if atlas is not None else None, points.data_ptr() if n else None, n,
+                                                                  place_ptr, out.data_ptr() if n else None))
+                return out
             self._check(lib().hj_sample_probes_visible(self._h, C.byref(d), C.byref(v), volume.data_ptr(), atlas.data_ptr() if atlas is not None else None,
                                                        points.data_ptr() if n else None, n, out.data_ptr() if n else None))
             return out
@@ -1110,6 +1125,10 @@ class Renderer:
             i = int(np.argmax(bad))
             raise ValueError(f"sample_probes_visible: point {i} ({pts[i, 0:6].tolist()}): finite positions and finite normals that are not all zero are needed")
         out = np.zeros((len(pts), 4), np.float32)
+        if placement is not None:
+            self._check(lib().hj_sample_probes_visible_placed(self._h, C.byref(d), C.byref(v), vol.ctypes.data, atl.ctypes.data if atl is not None else None,
+                                                              pts.ctypes.data, len(pts), place_ptr, out.ctypes.data))
+            return out
         self._check(lib().hj_sample_probes_visible(self._h, C.byref(d), C.byref(v), vol.ctypes.data, atl.ctypes.data if atl is not None else None,
                                                    pts.ctypes.data, len(pts), out.ctypes.data))
         return out
@@ -1146,7 +1165,7 @@ class Renderer:
         return False, out, out.ctypes.data
 
     def update_probes(self, desc, probes, spp, *, frame, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE, hysteresis, window=None,
-                      change=abi.PROBE_UPDATE_CHANGE, opts=None, stats=False):
+                      change=abi.PROBE_UPDATE_CHANGE, opts=None, stats=False, placement=None):
         """hj_update_probes: a window of a (nz, ny, nx, 28) probe volume re-baked from the uploaded scene at `spp` samples and folded
         into `probes`.  desc: the grid as a dict of `bake_probes`' keywords (origin, spacing, count, and min_distance, seed,
         seed_stride where they are not the defaults).  The fresh record of a probe is `bake_probes`' with the seed seed + frame *
@@ -1157,7 +1176,9 @@ class Renderer:
         initialised volume.  window = (first_probe, num_probes) in the order p = (z * ny + y) * nx + x, None: the whole volume; probes
         outside it keep every bit.  A contiguous float32 torch tensor on the renderer's GPU is updated in place (torch's current
         stream is synchronised first) and returned; a numpy array gives an updated copy, of which the window alone travelled.
-        stats=True: returns (probes, the gather's statistics dict)."""
+        stats=True: returns (probes, the gather's statistics dict).  placement (None: the grid as it is): the (nz, ny, nx, 4) array of
+        `place_probes`, of `probes`' kind - hj_update_probes_placed: the gather points sit at the placed positions, and the window's
+        inactive probes are neither traced nor written."""
         spp = int(spp)
         if not 1 <= spp <= 65536:
             raise ValueError(f"update_probes: spp {spp} outside [1, 65536]")
@@ -1170,15 +1191,23 @@ class Renderer:
             import torch
             d.flags = abi.PROBES_DEVICE_ARRAYS
             torch.cuda.current_stream(vol.device).synchronize()       # (whatever wrote the tensor)
-        self._check(lib().hj_update_probes(self._h, C.byref(d), C.byref(u), spp, C.byref(opts) if opts is not None else None, ptr, C.byref(st)))
+        o = C.byref(opts) if opts is not None else None
+        if placement is not None:
+            _, held, place_ptr = self._placement("update_probes", placement, d, on_gpu)     # (held: a converted copy lives until the call returns)
+            self._check(lib().hj_update_probes_placed(self._h, C.byref(d), C.byref(u), spp, o, place_ptr, ptr, C.byref(st)))
+            del held
+        else:
+            self._check(lib().hj_update_probes(self._h, C.byref(d), C.byref(u), spp, o, ptr, C.byref(st)))
         return (vol, stats_dict(st)) if stats else vol
 
-    def update_probe_visibility(self, desc, vis, atlas, *, frame, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE, hysteresis, window=None):
+    def update_probe_visibility(self, desc, vis, atlas, *, frame, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE, hysteresis, window=None, placement=None):
         """hj_update_probe_visibility: a window of a (nz, ny, nx, res + 2, res + 2, 2) visibility atlas re-baked from the uploaded scene
         and folded into `atlas`.  desc as in `update_probes`; vis: a dict of `bake_probe_visibility`'s keywords (res, rays_per_texel,
         max_distance).  Per interior texel and moment new = old * hysteresis + fresh * (1 - hysteresis), the fresh value being
         `bake_probe_visibility`'s under the seed seed + frame * frame_stride; every border texel then copies its interior texel's new
-        value.  hysteresis = 0 writes the fresh bake whatever the atlas held.  window, tensors and numpy arrays as in `update_probes`."""
+        value.  hysteresis = 0 writes the fresh bake whatever the atlas held.  window, tensors and numpy arrays as in `update_probes`;
+        placement as there: hj_update_probe_visibility_placed - the rays start at the placed positions and an inactive probe's texels,
+        border included, keep every bit."""
         d = self._probe_desc("update_probe_visibility", **desc)
         v = self._probe_vis_desc("update_probe_visibility", **vis)
         n = d.count[0] * d.count[1] * d.count[2]
@@ -1188,8 +1217,70 @@ class Renderer:
             import torch
             d.flags, v.flags = abi.PROBES_DEVICE_ARRAYS, v.flags | abi.PROBE_VIS_DEVICE_ARRAYS
             torch.cuda.current_stream(atl.device).synchronize()       # (whatever wrote the tensor)
-        self._check(lib().hj_update_probe_visibility(self._h, C.byref(d), C.byref(v), C.byref(u), ptr))
+        if placement is not None:
+            _, held, place_ptr = self._placement("update_probe_visibility", placement, d, on_gpu)   # (held until the call returns)
+            self._check(lib().hj_update_probe_visibility_placed(self._h, C.byref(d), C.byref(v), C.byref(u), place_ptr, ptr))
+            del held
+        else:
+            self._check(lib().hj_update_probe_visibility(self._h, C.byref(d), C.byref(v), C.byref(u), ptr))
         return atl
+
+    def _placement(self, what, placement, d, on_gpu, copy=False):
+        """A placement array beside a call's other arrays: (nz, ny, nx, 4) float32 of their kind - a contiguous tensor on the renderer's
+        GPU, or a numpy array with finite offsets -> (on_gpu, the array, its address)"""
+        shape = (d.count[2], d.count[1], d.count[0], abi.PROBE_PLACE_WORDS)
+        is_torch = type(placement).__module__.split(".")[0] == "torch"
+        if on_gpu is not None and is_torch != bool(on_gpu):
+            raise ValueError(f"{what}: the placement must be a {'tensor on the GPU' if on_gpu else 'numpy array'}, as the call's other arrays are")
+        if is_torch:
+            return self._update_target(what, placement, shape)
+        arr = np.array(placement, np.float32, order="C") if copy else np.ascontiguousarray(placement, np.float32)
+        if arr.shape != shape:
+            raise ValueError(f"{what}: a placement of {shape} is needed (got {arr.shape})")
+        if not np.isfinite(arr[..., 0:3]).all():
+            raise ValueError(f"{what}: the placement holds a non-finite offset")
+        return False, arr, arr.ctypes.data
+
+    @staticmethod
+    def new_placement(count, device=None):
+        """A placement of every probe on its grid point, active: zeros of (nz, ny, nx, 4) float32 - numpy, or with device (a torch
+        device) a tensor there.  Word 3 of a probe holds its state as uint32 bits: `placement[..., 3].view(uint32)`."""
+        shape = (int(count[2]), int(count[1]), int(count[0]), abi.PROBE_PLACE_WORDS)
+        if device is None:
+            return np.zeros(shape, np.float32)
+        import torch
+        return torch.zeros(shape, dtype=torch.float32, device=device)
+
+    def place_probes(self, desc, vis, placement, *, frame, min_front_distance, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE,
+                     backface_share=abi.PROBE_PLACE_BACKFACE_SHARE, max_offset=abi.PROBE_PLACE_MAX_OFFSET, window=None, relocate=True, classify=True):
+        """hj_place_probes: one relocation-and-classification step (Majercik et al. 2021) over a window of a (nz, ny, nx, 4) placement
+        (`new_placement`): per probe an offset in world units (words 0-2) and a state (word 3 as uint32 bits, 0 active).  desc, vis, frame,
+        frame_stride and window as in `update_probe_visibility` (vis: res, rays_per_texel, max_distance).  From the probe's rays a probe
+        that sees more than `backface_share` back faces moves through the nearest one, a probe with a front face nearer than
+        `min_front_distance` moves away from it, a probe that has room moves back towards its grid point; no offset leaves
+        `max_offset` spacings.  A probe inside geometry, or with no front face within its eight cells, becomes inactive.  The defaults
+        0.25 and 0.45 are the paper's and RTXGI's starting points, not tuned here.  relocate / classify = False leave the offsets / the
+        states alone.  A tensor on the renderer's GPU is updated in place and returned; a numpy array gives an updated copy."""
+        d = self._probe_desc("place_probes", **desc)
+        v = self._probe_vis_desc("place_probes", **vis)
+        n = d.count[0] * d.count[1] * d.count[2]
+        u = self._probe_update("place_probes", n, frame, frame_stride, 0.0, window, (0.0, 0.0))
+        mfd, share, mo = np.float32(min_front_distance), np.float32(backface_share), np.float32(max_offset)
+        if not (np.isfinite(mfd) and mfd > 0):
+            raise ValueError(f"place_probes: min_front_distance {min_front_distance}: finite and > 0 is needed")
+        if not 0 <= share <= 1:
+            raise ValueError(f"place_probes: backface_share {backface_share} outside [0, 1]")
+        if not 0 <= mo < 0.5:
+            raise ValueError(f"place_probes: max_offset {max_offset} outside [0, 0.5)")
+        on_gpu, arr, ptr = self._placement("place_probes", placement, d, None, copy=True)
+        flags = (0 if relocate else abi.PROBE_PLACE_NO_RELOCATE) | (0 if classify else abi.PROBE_PLACE_NO_CLASSIFY)
+        pl = abi.ProbePlace(u.first_probe, u.num_probes, u.frame, u.frame_stride, float(mfd), float(share), float(mo), flags)
+        if on_gpu:
+            import torch
+            d.flags, v.flags = abi.PROBES_DEVICE_ARRAYS, v.flags | abi.PROBE_VIS_DEVICE_ARRAYS
+            torch.cuda.current_stream(arr.device).synchronize()       # (whatever wrote the tensor)
+        self._check(lib().hj_place_probes(self._h, C.byref(d), C.byref(v), C.byref(pl), ptr))
+        return arr
 
     def texture_lookup(self, texture, uv):
         """hj_debug_texture_lookup: the colour the shade stage takes from `texture` at (n, 2) float32 uv -> (n, 3) float32."""

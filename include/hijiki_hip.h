@@ -962,7 +962,8 @@ int hj_sample_probes(hj_context* ctx, const hj_probe_desc* desc, const float* pr
  *   device arrays; m above 2^31 - 1; a bad position or normal in host arrays.  A null context: HJ_ERR_DEVICE in a process without a
  *   HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: hj_trace_rays' - an asynchronous frame in flight, frames submitted with
  *   HJ_RENDER_NO_DRAIN not yet drained, and for hj_bake_probe_visibility no scene.  A refused call writes nothing.
- * Not here: no adaptive bake, no multi-GPU split, no CLI.  (Blending an atlas over time: hj_update_probe_visibility, below.) */
+ * Not here: no adaptive bake, no multi-GPU split, no CLI.  (Blending an atlas over time: hj_update_probe_visibility, below; probes that sit in
+ *   or against a wall and a look-up that knows where they moved to: "Probe placement", hj_sample_probes_visible_placed, below.) */
 #define HJ_PROBE_VIS_DEVICE_ARRAYS 1u
 #define HJ_PROBE_VIS_NO_BACKFACE 2u    /* look-up only */
 #define HJ_PROBE_VIS_NO_CHEBYSHEV 4u   /* look-up only */
@@ -1023,7 +1024,8 @@ int hj_sample_probes_visible(hj_context* ctx, const hj_probe_desc* desc, const h
  *   NaN included; a change_soft, then a change_hard that is negative or a NaN (+inf is allowed: never); then spp == 0 or above 65536,
  *   misaligned device arrays and the refusals of opts (hj_update_probes).  A null context and HJ_ERR_STATE as for the bakes: both calls
  *   need a scene.  num_probes == 0: HJ_OK after all of these, nothing touched.  A refused call writes nothing.
- * Not here: no probe relocation or classification, no adaptive update (a per-probe spp), no multi-GPU split, no CLI flag. */
+ * Not here: no adaptive update (a per-probe spp), no multi-GPU split, no CLI flag.  (Probe relocation and classification: hj_place_probes
+ *   and the _placed updates, "Probe placement" below.) */
 #define HJ_PROBE_UPDATE_WORDS 8u
 typedef struct hj_probe_update {
   uint32_t first_probe, num_probes;   /* the window: probes first_probe ... first_probe + num_probes - 1, inside the volume     */
@@ -1036,6 +1038,95 @@ int hj_update_probes(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_
                      float* probes /* n x 28, read and written */, hj_render_stats* stats /* may be NULL */);
 int hj_update_probe_visibility(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const hj_probe_update* update,
                                float* atlas /* n x HJ_PROBE_VIS_WORDS(res), read and written */);
+
+/* Probe placement (ABI 0.23): per probe an offset from its grid point and an active / inactive state, found from the uploaded scene -
+ * the probe relocation and classification of Majercik et al. 2021, "Scaling Probe-Based Real-Time Dynamic Global Illumination" - and
+ * the updates and the look-up that read them.  A probe that the grid puts inside a wall, or nearer to one than min_distance, is
+ * switched off whole by hj_bake_probes' validity word, and the look-up loses a corner exactly where surfaces are: relocation moves it
+ * out of the wall instead.  A probe with no geometry in any of its eight cells is gathered and traced by every update for nobody:
+ * classification marks it inactive, and the placed updates leave it out.  No counterpart in the reference.  The numeric rules are the
+ * probe volumes' above: float32, one rounding per operation, no contraction; dot and length are the numeric contract's; min is
+ * minNum; a comparison with a NaN is false.
+ *
+ * The placement array.  HJ_PROBE_PLACE_WORDS = 4 words per probe, n x 4, in probe order: words 0-2 the offset o in world units
+ *   (float32), word 3 the state as uint32 bits - 0: active, anything else: inactive (the calls write 1).  The placed position of probe
+ *   (x, y, z) is P[a] = (origin[a] + (float)i_a * spacing[a]) + o[a]: the existing product and sum, then one more sum.  An array of
+ *   zero bits places every probe on its grid point, active.  Whether it is a host or a device array follows the descs' device-array
+ *   flag; a device array is 16-byte aligned.  A host array with a non-finite offset (in the window; the look-up: anywhere) is
+ *   refused; with device arrays a non-finite offset is the caller's contract and yields NaN, never a fault: no index is formed from
+ *   a value that has not been clamped or compared.
+ *
+ * hj_place_probes: one relocation-and-classification step over the window first_probe ... first_probe + num_probes - 1, in place.
+ *   The call works in slabs of whole probes of at most HJ_PROBE_VIS_SLAB_RAYS rays, exactly as hj_bake_probe_visibility does; the
+ *   context keeps one slab's rays, hits and surface records (112 bytes a ray, 56 MB at most) and nothing that grows with the volume.
+ *   Per probe p of the window, with O its old offset: the R = res * res * rays_per_texel rays are hj_probe_visibility_rays' rays of
+ *   desc' (seed' = seed + frame * frame_stride, uint32 wrap-around) - directions and seeds identical -, the origin the placed position
+ *   under O.  Every probe of the window is traced, inactive ones included, so that they can wake up; by hj_trace_rays with device
+ *   arrays, closest hit, with the surface record.  Per ray r, ascending, with d = ray words 3-5 and n = surface words 3-5:
+ *       hit = objectID >= 0;   dist = hit ? min(t, max_distance) : max_distance;   back = hit && dot(d, n) > 0.0f.
+ *   nb = the number of back rays;  (cb, rb) = the least dist over back rays and its ray;  (cf, rf) = the least dist over non-back rays,
+ *   misses included;  (ff, rq) = the greatest dist over non-back rays;  ties go to the lowest r.  inside = (float)nb > backface_share * (float)R.
+ *   Relocation (skipped with HJ_PROBE_PLACE_NO_RELOCATE: the offset keeps its bits).  cand = O; the first case that matches:
+ *       inside:                                                cand = O + d[rb] * (cb + min_front_distance * 0.5f);
+ *       else a non-back ray exists and cf < min_front_distance:  if dot(d[rf], d[rq]) <= 0.5f:  cand = O + d[rq] * min(ff, min_front_distance);
+ *       else a non-back ray exists and cf > min_front_distance:  L = length(O);  if L > 0.0f:  back = min(cf - min_front_distance, L);
+ *                                                                cand[a] = O[a] - (O[a] / L) * back.
+ *     Each vector step is one product and one sum per component.  The new offset is cand when |cand[a]| <= max_offset * spacing[a]
+ *     on every axis (a NaN compares false); otherwise the offset stays O, bit for bit.
+ *   Classification (skipped with HJ_PROBE_PLACE_NO_CLASSIFY: the state keeps its bits), from the same rays and the old O: inactive if
+ *     inside; otherwise active exactly when some ray has hit && !back and |O[a] + d[a] * t| <= spacing[a] on all three axes - a
+ *     front face lies inside the eight cells the probe serves; otherwise inactive.
+ *   The reduction runs one wave per probe; its count is an integer and its extremes are (dist, r) keys, so the result depends on
+ *   (scene, desc, vis, place, old placement) alone, not on the slab size or a launch shape.  backface_share 0.25 and max_offset 0.45
+ *   (the Python wrapper's defaults) are the paper's and RTXGI's starting points, not values tuned here.  Of vis the call uses res,
+ *   rays_per_texel and max_distance.
+ *
+ * The placed consumers take `const float* placement` in front of the array they write.
+ * hj_update_probes_placed: hj_update_probes with the gather points at the placed positions.  The window's inactive probes are left
+ *   out of the gather: they get no point, are not traced, and their records keep every bit.  The active probes are compacted in order
+ *   on the device; their number comes back to the host once, to size the gather.  All inactive: HJ_OK, nothing written (stats
+ *   included).  stats counts only what was traced.
+ * hj_update_probe_visibility_placed: hj_update_probe_visibility by the same rule with the same list: the rays start at the placed
+ *   positions, slabs are cut from the list, and an inactive probe's texels, border included, keep every bit.  A host-side atlas
+ *   travels the window at a time.
+ * hj_sample_probes_visible_placed: hj_sample_probes_visible with two changes.  P is the placed position in both the back-face and the
+ *   Chebyshev factor; the cell indices and the trilinear weights stay the unplaced grid's, as in the paper.  A corner whose probe is
+ *   inactive has w = 0 and is skipped whatever its record holds: an inactive probe's record may never have been written.
+ * With a placement of all +0 offsets and state 0 each of the three is bit for bit its unplaced counterpart, with one exception:
+ *   x + 0.0f turns a probe coordinate of -0 into +0.
+ * There are no placed bakes: with hysteresis 0 over the whole volume an update is the bake (ABI 0.22).
+ *
+ * HJ_ERR_INVALID, checked before anything else and without a device, in this order.  hj_place_probes: a null desc, vis or placement;
+ *   the refusals of hj_bake_probe_visibility's descs in their order; a null place; unknown place flags; first_probe + num_probes (in
+ *   64 bits) above the volume's probes; a min_front_distance that is not finite or not > 0; a backface_share outside [0, 1]; a
+ *   max_offset outside [0, 0.5) (a NaN is outside); a misaligned device array; a bad host offset.  The placed consumers: their unplaced
+ *   counterpart's refusals in its order, with a null placement among the null arguments (the look-up: whatever m is), placement
+ *   among the misaligned device arrays, and a bad host offset last.  A null context and HJ_ERR_STATE as for the unplaced calls:
+ *   hj_place_probes and the placed updates need a scene.  num_probes == 0: HJ_OK after all of these, nothing touched.  A refused
+ *   call writes nothing.
+ * Not here: no CLI flag, no multi-GPU split, no fusion of the placement rays with the visibility update's trace (hj_place_probes
+ *   and hj_update_probe_visibility_placed each trace their own rays). */
+#define HJ_PROBE_PLACE_WORDS 4u
+#define HJ_PROBE_PLACE_NO_RELOCATE 1u
+#define HJ_PROBE_PLACE_NO_CLASSIFY 2u
+typedef struct hj_probe_place {
+  uint32_t first_probe, num_probes;   /* the window: probes first_probe ... first_probe + num_probes - 1, inside the volume     */
+  uint32_t frame, frame_stride;       /* this step's seeds: desc->seed + frame * frame_stride (uint32 wrap-around)              */
+  float    min_front_distance;        /* finite, > 0: how near a front face may be                                              */
+  float    backface_share;            /* in [0, 1]: more back-face rays than this share of R, and the probe is inside geometry  */
+  float    max_offset;                /* in [0, 0.5): the offset stays within this share of the spacing on every axis           */
+  uint32_t flags;                     /* HJ_PROBE_PLACE_*                                                                       */
+} hj_probe_place;                     /* 32 bytes */
+int hj_place_probes(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const hj_probe_place* place,
+                    float* placement /* n x 4, read and written */);
+int hj_update_probes_placed(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_update* update, uint32_t spp,
+                            const hj_render_opts* opts /* NULL = defaults */, const float* placement /* n x 4 */,
+                            float* probes /* n x 28, read and written */, hj_render_stats* stats /* may be NULL */);
+int hj_update_probe_visibility_placed(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const hj_probe_update* update,
+                                      const float* placement /* n x 4 */, float* atlas /* n x HJ_PROBE_VIS_WORDS(res), read and written */);
+int hj_sample_probes_visible_placed(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes /* n x 28 */,
+                                    const float* atlas, const float* points /* m x 8 */, size_t m, const float* placement /* n x 4 */,
+                                    float* out /* m x 4 */);
 
 /* ------------------------------------------------------------------- probes */
 
