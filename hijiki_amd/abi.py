@@ -50,6 +50,9 @@ PROBE_UPDATE_FRAME_STRIDE = 0x9E3779B1   # the wrapper's default frame_stride: o
 PROBE_PLACE_WORDS = 4             # words of a probe's placement: the offset (float32 x 3), the state (uint32: 0 active)
 PROBE_PLACE_NO_RELOCATE, PROBE_PLACE_NO_CLASSIFY = 1, 2   # hj_probe_place flags
 PROBE_PLACE_BACKFACE_SHARE, PROBE_PLACE_MAX_OFFSET = 0.25, 0.45   # the wrapper's defaults: the paper's and RTXGI's starting points, not tuned
+CLOSEST_DEVICE_ARRAYS = 1         # hj_closest_points flag
+CLOSEST_WORDS = 8                 # words of a closest-point record: shape index, distance, q.xyz, u, v, side
+DISTANCE_UNSIGNED = 1             # hj_distance_field flag
 
 
 def probe_vis_words(res):

@@ -68,6 +68,10 @@
 //                         (k_pp_count, k_pp_scan, k_pp_scatter; k_pp_points, k_pp_resolve; k_pp_rays, k_pp_blend);
 //                         hj_sample_probes_visible_placed (k_pp_sample) (includes kernels/hj_probe_place.h; beside it the functions
 //                         of hj_probe_update.h, hj_probe_vis.h and hj_probes.h without their kernels, hj_compact.h and hj_num.h alone)
+//   api/closest_query.hip hj_closest_points, hj_distance_field: the nearest surface point to caller-given points, one lane per point
+//                         over the second copy of the uploaded tree (k_cq_walk), and a grid of such distances (k_pv_points through
+//                         probe_points_enqueue, k_cq_pack, k_cq_walk, k_cq_resolve) (includes kernels/hj_closest.h; beside it
+//                         hj_intersect.h, the grid struct of hj_probes.h and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -442,6 +446,12 @@ struct hj_context {
   // the list of a window's active probes (4 bytes a probe).  The placed updates use probes' and probe_vis' buffers as the updates do,
   // a host-side atlas staged for the whole window.  Grown on demand, reused by every call, freed with the context.
   struct ProbePlace { hjapi::DevBuf surface, placement, counts, list; } probe_place;
+
+  // hj_closest_points / hj_distance_field (api/closest_query.hip): device staging of host arrays - one chunk of points (16 bytes a
+  // point) and their records (32 bytes a point) -, the statistics' partial sums (16 bytes a workgroup); the field's gather points (32
+  // bytes a point of a chunk) and the staging of a host-side field (4 bytes a point).  The sibling of RayQuery: grown on demand,
+  // reused by every call, freed with the context.
+  struct ClosestQuery { hjapi::DevBuf points, out, partial, grid, field; } closest;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment

@@ -57,6 +57,7 @@ struct Tuning {
   X(trace_persistent, "HJ_TRACE_PERSISTENT", 1, 0, 1)      /* 1 the persistent walk with ray replacement (k_rq_walk), 0 one thread per ray (k_rq_plain) */ \
   X(trace_wg_rays, "HJ_TRACE_WG_RAYS", 2048, 64, 1 << 24)  /* rays per workgroup segment of the persistent form */                      \
   X(trace_chunk, "HJ_TRACE_CHUNK", 1 << 22, 64, 0x7FFFFFFF) /* rays per launch (and per staging buffer of host arrays) */               \
+  X(closest_ordered, "HJ_CLOSEST_ORDERED", 1, 0, 1)      /* hj_closest_points: 1 nearer child first with an LDS stack, 0 the stackless walk alone */ \
   /* hj_trace_paths (read like hj_trace_rays' rows).  Path state costs about 250 B per position (181 B, 213 B with tinted glass, 4 B more   \
      with an environment, rounded up), a sample 32 B: the defaults bound a query's path state at 2048 x 2048 x 250 B = 1 GB - as many    \
      workgroups as a 256-CU device keeps resident at 8 per CU, each with 32 rounds' worth of a full workgroup in flight - and its       \

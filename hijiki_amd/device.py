@@ -30,7 +30,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_bake_lightmap_filtered", "hj_trace_irradiance_adaptive", "hj_bake_lightmap_adaptive", "hj_probe_points", "hj_bake_probes",
            "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains", "hj_probe_visibility_rays",
            "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
-           "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed")
+           "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
+           "hj_distance_field")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -116,6 +117,8 @@ def lib():
                                               C.POINTER(abi.RenderStats)]
         L.hj_update_probe_visibility_placed.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), C.POINTER(abi.ProbeUpdate), vp, vp]
         L.hj_sample_probes_visible_placed.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), vp, vp, vp, C.c_size_t, vp, vp]
+        L.hj_closest_points.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.POINTER(C.c_uint64)]   # (host or device pointers)
+        L.hj_distance_field.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.c_float, C.c_uint32, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -555,6 +558,73 @@ class Renderer:
                                         surf.ctypes.data if surface else None))
         out = (hits[:, 0].copy().view(np.int32), hits[:, 1], hits[:, 2], hits[:, 3])
         return out + ((surf,) if surface else ())
+
+    def closest_points(self, points, radius=float("inf"), stats=False, device=None):
+        """hj_closest_points: the nearest surface point of the uploaded scene to each of n points -> (n, 8) float32 records: the shape
+        index as int32 bits (-1: a miss), the distance, q (3), u, v, side; a miss is -1 and seven zeros.  points: (n, 4) = position
+        and search radius, or (n, 3) with `radius` a scalar or (n,) values (+inf: unbounded).  A shape counts when its squared
+        distance is <= radius^2; ties resolve to the lower shape index; a NaN or negative radius or a non-finite position is a miss.
+        `side` is the facing of the nearest shape (+1: the side its normal cross(edge1, edge2) points to, or outside a sphere), not a
+        robust inside / outside test.  A float32 numpy array gives a numpy array.  A float32 torch tensor on the renderer's GPU is
+        read in place (an (n, 3) one is packed with its radii on that GPU first) and gives a tensor there; torch's current stream is
+        synchronised first.  device: True / False demands a tensor / an array; None takes what comes.  stats=True: returns (records,
+        {"nodes_visited", "shapes_tested"}) - functions of the points and the uploaded tree alone."""
+        is_torch = type(points).__module__.split(".")[0] == "torch"
+        if device is not None and bool(device) != is_torch:
+            raise ValueError(f"closest_points: device={device} but points is a {'torch tensor' if is_torch else 'host array'}")
+        st = (C.c_uint64 * 2)(0, 0)
+        sp = st if stats else None
+        if is_torch:
+            import torch
+            if not (points.is_cuda and points.device.index == self.device and points.dtype == torch.float32 and points.dim() == 2
+                    and points.shape[1] in (3, 4)):
+                raise ValueError(f"closest_points: a float32 tensor of (n, 3) or (n, 4) on GPU {self.device} is needed"
+                                 f" (got {tuple(points.shape)} {points.dtype} on {points.device})")
+            n = points.shape[0]
+            if points.shape[1] == 3:
+                r = torch.as_tensor(radius, dtype=torch.float32, device=points.device).expand(n) if not hasattr(radius, "shape") or radius.ndim == 0 \
+                    else torch.as_tensor(radius, dtype=torch.float32, device=points.device).reshape(n)
+                points = torch.cat([points, r.reshape(n, 1)], 1)
+            points = points.contiguous()
+            out = torch.empty((n, abi.CLOSEST_WORDS), dtype=torch.float32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()    # (the allocations and whatever wrote `points`)
+            self._check(lib().hj_closest_points(self._h, points.data_ptr() if n else None, n, abi.CLOSEST_DEVICE_ARRAYS,
+                                                out.data_ptr() if n else None, sp))
+        else:
+            points = np.asarray(points)
+            if points.dtype != np.float32 or points.ndim != 2 or points.shape[1] not in (3, 4):
+                raise ValueError(f"closest_points: a float32 array of (n, 3) or (n, 4) is needed (got {points.shape} {points.dtype})")
+            n = len(points)
+            if points.shape[1] == 3:
+                points = np.concatenate([points, np.broadcast_to(np.asarray(radius, np.float32).reshape(-1, 1), (n, 1))], 1)
+            points = np.ascontiguousarray(points, np.float32)
+            out = np.zeros((n, abi.CLOSEST_WORDS), np.float32)
+            self._check(lib().hj_closest_points(self._h, points.ctypes.data, n, 0, out.ctypes.data, sp))
+        return (out, dict(nodes_visited=int(st[0]), shapes_tested=int(st[1]))) if stats else out
+
+    def distance_field(self, origin, spacing, count, max_distance=float("inf"), signed=True, device=False):
+        """hj_distance_field: the distance to the nearest surface of the uploaded scene on the grid of `probe_points` - point (x, y, z)
+        at origin + (x, y, z) * spacing -, computed without the points leaving the device -> (nz, ny, nx) float32: side * distance
+        (signed) or the distance alone.  Only shapes within `max_distance` count; a grid point without one gets max_distance
+        (signed: +max_distance).  `side` is the facing of the nearest shape - which side of its plane, or of a sphere's surface, the
+        point is on -, not a robust inside / outside test: near edges shared by faces that face differently the sign follows the
+        shape with the lower index.  device=True: a torch tensor on the renderer's GPU."""
+        d = self._probe_desc("distance_field", origin, spacing, count, 0, 1, 0.0, device)
+        md = float(np.float32(max_distance))
+        if not md >= 0:
+            raise ValueError(f"distance_field: max_distance {max_distance}: >= 0 is needed (inf: no limit)")
+        flags = 0 if signed else abi.DISTANCE_UNSIGNED
+        shape = (d.count[2], d.count[1], d.count[0])
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            field = torch.empty(shape, dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            self._check(lib().hj_distance_field(self._h, C.byref(d), md, flags, field.data_ptr()))
+            return field
+        field = np.zeros(shape, np.float32)
+        self._check(lib().hj_distance_field(self._h, C.byref(d), md, flags, field.ctypes.data))
+        return field
 
     def trace_paths(self, rays, seeds=None, spp=1, opts=None, stats=False):
         """hj_trace_paths: the path-traced radiance along (n, 8) rays (origin, direction of any length, a uint32 seed as the bits of

@@ -1265,6 +1265,67 @@ int hj_debug_vote_exchange(hj_context* ctx, const hj_bvh_node* nodes, size_t N, 
                            hj_bvh_node* out_nodes, size_t capacity, uint32_t info[4]);
 int hj_debug_vote_gains(hj_context* ctx, const hj_scene_desc* scene, size_t paths, uint64_t* gain_l, uint64_t* gain_r, size_t capacity);
 
+/* ---------------------------------------------------------- distance queries */
+
+/* Distance queries (ABI 0.24): the nearest surface point of the uploaded scene to caller-given points - the query that starts from no
+ * ray (no counterpart in the reference).  Every arithmetic operation below is float32, one rounding per operation, no contraction
+ * except dot3 / cross3 of the numeric contract (dot3(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)), len3 = sqrt of
+ * dot3); `/` and sqrt are IEEE.  kernels/hj_closest.h and tests/closest_ref.py are the two texts of this one specification.
+ *
+ * Per shape, a pure function of the point p and the shape's uploaded record -> (q, d2, u, v, side):
+ *   sphere (c, r):  w = p - c, l = len3(w);  q = c + w * (r / l), and c + (r, 0, 0) when l == 0;  d2 = (l - r) * (l - r);  u = v = 0;
+ *     side = +1 when l >= r, else -1.
+ *   triangle (a, b, c):  on ab = b - a, ac = c - a, ap = p - a, bp = ap - ab, cp = ap - ac, the region walk of Ericson, Real-Time
+ *     Collision Detection 5.1.5 - the three vertices, then the edges ab, ac, bc, then the face - with every dot product a dot3;
+ *     kernels/hj_closest.h states the seven tests and their order.  (u, v) are the coefficients of ab and ac, the barycentric pair
+ *     of hj_trace_rays' raw hit;  q = (a + ab * u) + ac * v;  d2 = dot3(p - q, p - q);  side = +1 when
+ *     dot3(p - q, cross3(ab, ac)) >= 0, else -1.  A degenerate triangle comes out as that text computes it, NaN included.
+ *   quad (origin, edge1, edge2), a parallelogram:  w = p - origin;  s = dot3(w, edge1) / dot3(edge1, edge1),
+ *     t = dot3(w, edge2) / dot3(edge2, edge2), each clamped to [0, 1] (a NaN stays);  (u, v) = (s, t);
+ *     q = (origin + edge1 * s) + edge2 * t;  d2 and side as for the triangle, with cross3(edge1, edge2).  The two separate
+ *     projections give the nearest point for rectangles only; for a sheared quad q is a point of the quad, not the nearest.
+ * The answer for a point (p, r), r the search radius (+inf: unbounded), r2 = r * r: a shape is a candidate when its d2 is not NaN and
+ *   d2 <= r2; the answer is the candidate with the smallest key (d2 as uint32 bits, global shape index), so ties resolve to the lower
+ *   index.  A NaN or negative r, a non-finite coordinate of p, or no candidate gives a miss.  The answer depends on the point and
+ *   the shapes alone: not on the tree, the visiting order, the launch shape or the lane that carried the point.
+ * The tree only decides what is skipped, by a bound on the COMPUTED d2 with an absolute slack of 2^-18 times the largest coordinate
+ *   magnitude of the root box (DESIGN.md has the derivation).  Equality with the brute-force answer over all shapes is claimed for
+ *   trees whose boxes bound their subtrees: every tree the host compiler, hj_build_bvh_device, hj_refit_bvh_device,
+ *   hj_optimize_bvh_device and hj_scene_update_shapes produce.  For caller-supplied boxes that do not bound their subtrees the
+ *   answer is whatever the skipping gives.  Magnitudes: a sphere or quad gets an answer while the squares of
+ *   coordinate differences stay finite (below 2^60); a triangle multiplies two dot products and gets one only while coordinate
+ *   differences stay below about 2^31 - beyond that its areas are inf - inf, its d2 is NaN and it is no candidate.
+ * side is the facing of the nearest shape - which side of its plane, or of the sphere's surface, p is on.  It is not a robust
+ *   inside / outside test: at an edge or a vertex shared by faces that face differently, the shape with the lower index decides.
+ *
+ * hj_closest_points:  points: n x 4 floats (p.xyz, r).  out: n x HJ_CLOSEST_WORDS floats - [0] the shape index as int32 bits or -1,
+ *     [1] sqrt(d2), [2..4] q, [5] u, [6] v, [7] side; a miss is -1 followed by seven zeros.
+ *   stats (may be NULL; always a host pointer): [0] nodes visited, [1] shapes tested, over all points of the call; a function of the
+ *     points and the uploaded tree alone.
+ *   HJ_CLOSEST_DEVICE_ARRAYS: points / out are device pointers on the context's GPU, 16-byte aligned, read and written in place (the
+ *     caller orders its own streams before the call).  Without it they are host arrays, staged through buffers the context keeps.
+ *   Runs on the context's stream and returns when the results are complete.  n == 0: HJ_OK, nothing touched.
+ *   HJ_ERR_INVALID, checked before anything else and before the device is touched, in this order: null points or out (n > 0);
+ *     unknown flag bits; n above 2^31 - 1; with device arrays, points or out misaligned, or stats given as anything but a host pointer.  With a
+ *     null context the text is in hj_last_error(NULL).  A refused call writes nothing.
+ *   A null context: HJ_ERR_DEVICE in a process without a HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: hj_trace_rays' - no
+ *     scene, an asynchronous frame in flight, frames submitted with HJ_RENDER_NO_DRAIN not yet drained.
+ *
+ * hj_distance_field:  the grid of desc (hj_probe_points' positions; of desc the seeds and min_distance are not used) through the
+ *     query with r = max_distance, without the points or the records leaving the device.  field: count[0] * count[1] * count[2]
+ *     floats in ascending p: side * sqrt(d2), or sqrt(d2) alone with HJ_DISTANCE_UNSIGNED; a miss gives max_distance (signed: +).
+ *   desc->flags HJ_PROBES_DEVICE_ARRAYS: field is a device pointer, 16-byte aligned.
+ *   HJ_ERR_INVALID, in this order: a null desc or field; the refusals of desc (hj_probe_points'); unknown distance flag bits; a
+ *     max_distance that is NaN or negative; a misaligned device array.  Then hj_closest_points' gate.
+ * Not here: no surface record or material at q (hj_trace_rays' surface is for ray hits); no multi-GPU split; probe validity and
+ *   relocation still come from rays. */
+#define HJ_CLOSEST_DEVICE_ARRAYS 1u
+#define HJ_CLOSEST_WORDS 8u
+#define HJ_DISTANCE_UNSIGNED 1u
+int hj_closest_points(hj_context* ctx, const float* points /* n x 4: p.xyz, radius */, size_t n, uint32_t flags,
+                      float* out /* n x 8 */, uint64_t* stats /* may be NULL: [0] nodes visited, [1] shapes tested */);
+int hj_distance_field(hj_context* ctx, const hj_probe_desc* desc, float max_distance, uint32_t flags, float* field);
+
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host
  * library's ImageBlockGenerator and restated by the oracle. */
