@@ -53,6 +53,11 @@ PROBE_PLACE_BACKFACE_SHARE, PROBE_PLACE_MAX_OFFSET = 0.25, 0.45   # the wrapper'
 CLOSEST_DEVICE_ARRAYS = 1         # hj_closest_points flag
 CLOSEST_WORDS = 8                 # words of a closest-point record: shape index, distance, q.xyz, u, v, side
 DISTANCE_UNSIGNED = 1             # hj_distance_field flag
+ALLHITS_DEVICE_ARRAYS = 1         # hj_trace_rays_all flag
+ALLHITS_MAX_HITS = 8              # the most hit records a ray of hj_trace_rays_all gets
+INSIDE_DEVICE_ARRAYS, INSIDE_PARITY = 1, 2   # hj_points_inside flags
+# the three directions of hj_points_inside (HJ_INSIDE_DIR0 .. 2): the float32 nearest each literal
+INSIDE_DIRECTIONS = ((0.28284273, 0.51961523, 0.8062258), (-0.84261495, 0.2236068, -0.48989794), (0.5477226, -0.7745967, -0.31622776))
 
 
 def probe_vis_words(res):

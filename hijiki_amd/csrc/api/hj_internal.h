@@ -72,6 +72,10 @@
 //                         over the second copy of the uploaded tree (k_cq_walk), and a grid of such distances (k_pv_points through
 //                         probe_points_enqueue, k_cq_pack, k_cq_walk, k_cq_resolve) (includes kernels/hj_closest.h; beside it
 //                         hj_intersect.h, the grid struct of hj_probes.h and hj_num.h alone)
+//   api/multi_hit.hip     hj_trace_rays_all, hj_points_inside: every hit along caller-given rays, one lane per ray over the second
+//                         copy of the uploaded tree with the range never shrunk (k_mh_walk: the K nearest in LDS, the count, the
+//                         signed crossing sum), and containment of points by three such counts (k_mh_inside) (includes
+//                         kernels/hj_multihit.h; beside it hj_intersect.h and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -452,6 +456,11 @@ struct hj_context {
   // bytes a point of a chunk) and the staging of a host-side field (4 bytes a point).  The sibling of RayQuery: grown on demand,
   // reused by every call, freed with the context.
   struct ClosestQuery { hjapi::DevBuf points, out, partial, grid, field; } closest;
+
+  // hj_trace_rays_all / hj_points_inside (api/multi_hit.hip): device staging of host arrays - one chunk of rays (32 bytes a ray; of
+  // points: 16 bytes a point), their count pairs (8 bytes a ray or point) and their hit lists (16 * max_hits bytes a ray).  The
+  // sibling of RayQuery: grown on demand, reused by every call, freed with the context.
+  struct AllHits { hjapi::DevBuf rays, counts, hits; } allhits;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment

@@ -31,7 +31,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains", "hj_probe_visibility_rays",
            "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
-           "hj_distance_field")
+           "hj_distance_field", "hj_trace_rays_all", "hj_points_inside")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -119,6 +119,8 @@ def lib():
         L.hj_sample_probes_visible_placed.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.POINTER(abi.ProbeVisDesc), vp, vp, vp, C.c_size_t, vp, vp]
         L.hj_closest_points.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.POINTER(C.c_uint64)]   # (host or device pointers)
         L.hj_distance_field.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.c_float, C.c_uint32, vp]
+        L.hj_trace_rays_all.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp]         # (host or device pointers)
+        L.hj_points_inside.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -625,6 +627,66 @@ class Renderer:
         field = np.zeros(shape, np.float32)
         self._check(lib().hj_distance_field(self._h, C.byref(d), md, flags, field.ctypes.data))
         return field
+
+    def _query_input(self, what, a, words):
+        """(array or tensor, is_torch) of a query's (n, words) float32 input, by trace_rays' conventions"""
+        if type(a).__module__.split(".")[0] == "torch":
+            import torch
+            if not (a.is_cuda and a.device.index == self.device and a.dtype == torch.float32 and a.is_contiguous() and a.dim() == 2
+                    and a.shape[1] == words):
+                raise ValueError(f"{what}: a contiguous float32 tensor of (n, {words}) on GPU {self.device} is needed"
+                                 f" (got {tuple(a.shape)} {a.dtype} on {a.device})")
+            return a, True
+        a = np.asarray(a)
+        if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != words:
+            raise ValueError(f"{what}: a float32 array of (n, {words}) is needed (got {a.shape} {a.dtype})")
+        return np.ascontiguousarray(a), False
+
+    def trace_rays_all(self, rays, max_hits=abi.ALLHITS_MAX_HITS):
+        """hj_trace_rays_all: every hit of (n, 8) rays (origin, direction of any length, tMin, tMax) with the uploaded scene, the range
+        never shrunk -> (counts (n,) uint32: the number of candidates; crossings (n,) int32: +1 for each that leaves through a surface,
+        -1 for each that enters; hits (n, max_hits, 4) float32: per ray the min(count, max_hits) candidates nearest first as
+        (shape index as int32 bits, t, u, v), the rest (-1, 0, 0, 0)).  max_hits: 0 ... abi.ALLHITS_MAX_HITS; 0 counts only.  Equal t
+        goes to the lower shape index; a sphere gives its two roots (u = 0: the near one, 1: the far one).  The candidates are those
+        of the query's own box test, not the closest-hit walk's.  A float32 numpy array gives numpy arrays.  A contiguous float32
+        torch tensor on the renderer's GPU is read in place and gives tensors on that GPU; torch's current stream is synchronised
+        first."""
+        K = int(max_hits)
+        if not 0 <= K <= abi.ALLHITS_MAX_HITS:
+            raise ValueError(f"trace_rays_all: max_hits {max_hits}: 0 ... {abi.ALLHITS_MAX_HITS}")
+        rays, is_torch = self._query_input("trace_rays_all", rays, 8)
+        n = rays.shape[0]
+        if is_torch:
+            import torch
+            counts = torch.empty((n, 2), dtype=torch.int32, device=rays.device)
+            hits = torch.empty((n, K, 4), dtype=torch.float32, device=rays.device)
+            torch.cuda.current_stream(rays.device).synchronize()      # (the allocations and whatever wrote `rays`)
+            self._check(lib().hj_trace_rays_all(self._h, rays.data_ptr() if n else None, n, K, abi.ALLHITS_DEVICE_ARRAYS,
+                                                counts.data_ptr() if n else None, hits.data_ptr() if n and K else None))
+            return counts[:, 0], counts[:, 1], hits
+        counts, hits = np.zeros((n, 2), np.uint32), np.zeros((n, K, 4), np.float32)
+        self._check(lib().hj_trace_rays_all(self._h, rays.ctypes.data, n, K, 0, counts.ctypes.data, hits.ctypes.data if K else None))
+        return counts[:, 0].copy(), counts[:, 1].copy().view(np.int32), hits
+
+    def points_inside(self, points, parity=False):
+        """hj_points_inside: whether each of (n, 4) points (position, one reserved word) lies inside closed geometry of the uploaded
+        scene, by the signed crossings of three fixed rays (abi.INSIDE_DIRECTIONS) computed without leaving the device -> (inside (n,)
+        uint32: 1 when at least two rays vote inside; votes (n,) uint32: how many did).  A ray votes inside when its crossing sum is
+        > 0 - surfaces oriented outward -; parity=True: when it crosses an odd number of surfaces, for geometry without a consistent
+        orientation.  Arrays and tensors as for trace_rays_all (tensors: counts as int32, torch has no uint32 arithmetic)."""
+        flags = abi.INSIDE_PARITY if parity else 0
+        points, is_torch = self._query_input("points_inside", points, 4)
+        n = points.shape[0]
+        if is_torch:
+            import torch
+            out = torch.empty((n, 2), dtype=torch.int32, device=points.device)
+            torch.cuda.current_stream(points.device).synchronize()    # (the allocation and whatever wrote `points`)
+            self._check(lib().hj_points_inside(self._h, points.data_ptr() if n else None, n, flags | abi.INSIDE_DEVICE_ARRAYS,
+                                               out.data_ptr() if n else None))
+            return out[:, 0], out[:, 1]
+        out = np.zeros((n, 2), np.uint32)
+        self._check(lib().hj_points_inside(self._h, points.ctypes.data, n, flags, out.ctypes.data))
+        return out[:, 0].copy(), out[:, 1].copy()
 
     def trace_paths(self, rays, seeds=None, spp=1, opts=None, stats=False):
         """hj_trace_paths: the path-traced radiance along (n, 8) rays (origin, direction of any length, a uint32 seed as the bits of

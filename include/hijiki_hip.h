@@ -1326,6 +1326,74 @@ int hj_closest_points(hj_context* ctx, const float* points /* n x 4: p.xyz, radi
                       float* out /* n x 8 */, uint64_t* stats /* may be NULL: [0] nodes visited, [1] shapes tested */);
 int hj_distance_field(hj_context* ctx, const hj_probe_desc* desc, float max_distance, uint32_t flags, float* field);
 
+/* ---------------------------------------------------------- all-hit queries */
+
+/* All-hit queries (ABI 0.25): every hit along a ray - the third form beside hj_trace_rays' closest hit and HJ_TRACE_ANY_HIT: the K
+ * nearest hits in order, how many there are, and the signed sum of their crossings; and from that sum whether a point lies inside
+ * closed geometry (no counterpart in the reference; multi-hit traversal: Gribble et al. 2014).  Every arithmetic
+ * operation below is float32, one rounding per operation, no contraction except dot3 / cross3 of the numeric contract;
+ * `/` and sqrt are IEEE.  kernels/hj_multihit.h and tests/allhits_ref.py are the two texts of this one specification.
+ *
+ * The contract is a function of the ray (o, d, tMin, tMax) and the uploaded tree alone:
+ *   Candidates: the pre-order skip-link walk of the uploaded tree as it was uploaded (every node, every leaf), with the caller's
+ *     [tMin, tMax] never shrunk.  An inner node is entered iff its box passes the box test below; leaf boxes are not tested; every
+ *     shape whose leaf is reached is tested with the caller's range.  A quad or a triangle gives one candidate (t, u, v) when the
+ *     shape test of hj_trace_rays accepts it.  A sphere gives up to two: with l = o - c, b = 2 * dot3(d, l), cc = dot3(l, l) - r * r,
+ *     D = b * b - 4 * cc (no candidate when D < 0), s = sqrt(D), t0 = -0.5 * (b + s), t1 = -0.5 * (b - s) - the closest-hit test's
+ *     arithmetic, which takes d as a unit vector -, each root with tMin <= t <= tMax is a candidate, with u = 0 for t0, 1 for t1,
+ *     and v = 0.
+ *   Box test, without fused multiply-add: inv = 1 / d per axis;  t1 = (lo - o) * inv, t2 = (hi - o) * inv;  tn = t1 < t2 ? t1 : t2,
+ *     tp = t1 < t2 ? t2 : t1;  T0 = the three tn folded x, y, z by a < b ? b : a;  T1 = the three tp folded by a < b ? a : b;
+ *     enter iff !(T0 > T1) && !(T0 > tMax) && !(T1 < tMin).  A NaN T0, T1, tMin or tMax never culls.  This is not the closest-hit walk's test (fused,
+ *     with an epsilon, against a shrinking tMax): a shape whose box a ray grazes may be a candidate here and no hit there, or the
+ *     reverse.  Like every slab test it can miss a box that a ray with a zero direction component touches on its face.
+ *   Key: (t as a float, shape index, root), compared in that order: equal t goes to the lower shape index, a sphere's t0 before t1.
+ *   Crossing: +1 for a candidate that leaves through its surface (dot3(d, n_g) > 0), -1 for one that enters (< 0), 0 otherwise;
+ *     n_g = cross3(edge1, edge2) for a quad, cross3(b - a, c - a) for a triangle; a sphere's t0 enters, its t1 leaves.  A point
+ *     inside a closed surface whose n_g point outward gets +1 along any direction.
+ *   Record i depends on ray i and the scene alone: not on the lane, the workgroup, the launch or the chunk that carried it.
+ *
+ * hj_trace_rays_all:  rays: n x 8 floats in hj_trace_rays' layout (origin, direction of any length, tMin, tMax).  max_hits K: 0 ...
+ *     HJ_ALLHITS_MAX_HITS; with K = 0 hits may be NULL (counting only).
+ *   counts: n x 2 words - [0] (uint32) the number of candidates, [1] (int32) the signed crossing sum.
+ *   hits: n x K x 4 floats - record j of ray i is (objectID bits, t, u, v) as hj_trace_rays writes it; the first min(count, K)
+ *     records are the candidates with the smallest key in ascending key order, the rest are (-1, 0, 0, 0).
+ *   HJ_ALLHITS_DEVICE_ARRAYS: rays / counts / hits are device pointers on the context's GPU, 16-byte aligned, read and written in
+ *     place (the caller orders its own streams before the call).  Without it they are host arrays, staged in chunks of
+ *     HJ_TRACE_CHUNK rays through buffers the context keeps.
+ *   Runs on the context's stream and returns when the results are complete.  n == 0: HJ_OK, nothing touched.
+ *   HJ_ERR_INVALID, checked before anything else and before the device is touched, in this order: null rays or counts (n > 0); null
+ *     hits with K > 0 (n > 0); K above HJ_ALLHITS_MAX_HITS; unknown flag bits; n above 2^31 - 1; with device arrays, a misaligned
+ *     array.  With a null context the text is in hj_last_error(NULL).  A refused call writes nothing.
+ *   A null context: HJ_ERR_DEVICE in a process without a HIP device, HJ_ERR_INVALID otherwise.  HJ_ERR_STATE: hj_trace_rays'.
+ *
+ * hj_points_inside:  points: n x 4 floats (p.xyz, reserved).  Per point three rays from p with tMin = 0, tMax = +inf along
+ *     HJ_INSIDE_DIR0, 1, 2 below - fixed, pairwise non-parallel, no zero component and no two components of one direction equal in
+ *     magnitude, so that axis-aligned scenes are in general position; of length 1 to float32's rounding - through the counting walk
+ *     without leaving the device.  A ray votes inside when its crossing sum is > 0; with HJ_INSIDE_PARITY, for surfaces without a
+ *     consistent orientation, when its number of candidates is odd.
+ *   out: n x 2 uint32 - [0] 1 when at least two rays vote inside, else 0; [1] the number of rays that voted inside.
+ *   HJ_INSIDE_DEVICE_ARRAYS: as above.  HJ_ERR_INVALID in this order: null points or out (n > 0); unknown flag bits; n above
+ *     2^31 - 1; a misaligned device array.  Then hj_trace_rays_all's gate.
+ * Not here: a surface record per hit (the caller has id, t, u, v); K above 8; a multi-GPU split; hj_distance_field's sign and the
+ *   probe classification do not use the count. */
+#define HJ_ALLHITS_DEVICE_ARRAYS 1u
+#define HJ_ALLHITS_MAX_HITS 8u
+#define HJ_INSIDE_DEVICE_ARRAYS 1u
+#define HJ_INSIDE_PARITY 2u
+#define HJ_INSIDE_DIR0_X 0.28284273f
+#define HJ_INSIDE_DIR0_Y 0.51961523f
+#define HJ_INSIDE_DIR0_Z 0.8062258f
+#define HJ_INSIDE_DIR1_X -0.84261495f
+#define HJ_INSIDE_DIR1_Y 0.2236068f
+#define HJ_INSIDE_DIR1_Z -0.48989794f
+#define HJ_INSIDE_DIR2_X 0.5477226f
+#define HJ_INSIDE_DIR2_Y -0.7745967f
+#define HJ_INSIDE_DIR2_Z -0.31622776f
+int hj_trace_rays_all(hj_context* ctx, const float* rays /* n x 8 */, size_t n, uint32_t max_hits, uint32_t flags,
+                      uint32_t* counts /* n x 2 */, float* hits /* n x max_hits x 4; may be NULL with max_hits 0 */);
+int hj_points_inside(hj_context* ctx, const float* points /* n x 4: p.xyz, reserved */, size_t n, uint32_t flags, uint32_t* out /* n x 2 */);
+
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host
  * library's ImageBlockGenerator and restated by the oracle. */
