@@ -58,6 +58,11 @@ ALLHITS_MAX_HITS = 8              # the most hit records a ray of hj_trace_rays_
 INSIDE_DEVICE_ARRAYS, INSIDE_PARITY = 1, 2   # hj_points_inside flags
 # the three directions of hj_points_inside (HJ_INSIDE_DIR0 .. 2): the float32 nearest each literal
 INSIDE_DIRECTIONS = ((0.28284273, 0.51961523, 0.8062258), (-0.84261495, 0.2236068, -0.48989794), (0.5477226, -0.7745967, -0.31622776))
+MATERIALS_DEVICE_ARRAYS = 1       # hj_eval_materials flag
+MATERIALS_WORDS = 8               # words of a material record: albedo.rgb, material word, emission.rgb, 0
+MATERIAL_MISS = 0xFFFFFFFF        # ... its word 3 for a miss
+AOV_DEVICE_ARRAY = 1              # hj_render_aovs / hj_render_aovs_frame flag
+AOV_WORDS = 12                    # words of an AOV pixel: albedo.rgb, samples | normal.xyz, t | emission.rgb, hits - each a sum
 
 
 def probe_vis_words(res):

@@ -76,6 +76,10 @@
 //                         copy of the uploaded tree with the range never shrunk (k_mh_walk: the K nearest in LDS, the count, the
 //                         signed crossing sum), and containment of points by three such counts (k_mh_inside) (includes
 //                         kernels/hj_multihit.h; beside it hj_intersect.h and hj_num.h alone)
+//   api/aov.hip           hj_eval_materials, hj_render_aovs, hj_render_aovs_frame: the material of (hit, surface) records, and a
+//                         frame's albedo / normal / depth sums from its own primary rays (includes kernels/hj_aov.h, which includes
+//                         the kernel headers up to hj_stages.h and edits none: k_mat_eval; k_aov_walk, the persistent walk with a
+//                         fetch that builds the camera ray from the sample index; k_aov_resolve, run by run of disjoint blocks)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -462,6 +466,12 @@ struct hj_context {
   // sibling of RayQuery: grown on demand, reused by every call, freed with the context.
   struct AllHits { hjapi::DevBuf rays, counts, hits; } allhits;
 
+  // hj_eval_materials / hj_render_aovs (api/aov.hip): the call's block list (40 bytes a block), the hit records of one walk launch
+  // (16 bytes a sample slot, 16384 slots a block), the staging of a host-side AOV image (48 bytes a pixel); hj_eval_materials' staging
+  // of host arrays - one chunk of hit records, surface records and material records (16, 64 and 32 bytes a record).  The sibling of
+  // RayQuery: grown on demand, reused by every call, freed with the context.  Never the batch slots' or the framebuffer.
+  struct Aov { hjapi::DevBuf blocks, hits, image, in_hits, in_surface, out; } aov;
+
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
   hjapi::Tuning tuning;
@@ -644,6 +654,16 @@ void launch_trace_shadow(const hj::BatchState& st, const hj::DeviceScene& sc, bo
 void launch_reconstruct(const hj::BatchState& st, float stddev, const uint32_t* tiles, uint32_t tiles_x, uint32_t tiles_y,
                         float4* accum, uint32_t width, uint32_t height, hipStream_t s);
 void launch_debug_trace(const hj::DeviceScene& sc, const float* rays, uint32_t n, bool bvh, bool any_hit, float4* hits, hipStream_t s);
+
+// The blocks of passes [p0, p1) of a frame that `rank` of `world` renders, in the frame's order (pass by pass, raster order inside a
+// pass), appended to `out`: ONE text for hj_render_frame (api/render_calls.hip) and hj_render_aovs_frame (api/aov.hip, world 1).
+inline void frame_blocks_append(const hijiki::BlockGrid& grid, uint64_t master_seed, uint32_t p0, uint32_t p1, uint32_t rank, uint32_t world,
+                                bool static_deal, std::vector<hj_image_block>& out) {
+  const uint32_t per_pass = grid.per_pass();
+  for (uint32_t p = p0; p < p1; p++)
+    for (uint32_t j = 0; j < per_pass; j++)
+      if (grid.owner(static_deal ? 0u : p, j, world) == rank) out.push_back(grid.make(master_seed, p, j));
+}
 
 // The scene as a render call's kernels see it: the light-shaft grid (api/light_grid.cpp) answers "no shape of the TREE lies
 // between this cell and that emitter", so it is taken away from a linear-scan render (scene.glsl:134-158 tests every shape of

@@ -479,9 +479,7 @@ int render_frame_impl(hj_context* ctx, uint32_t spp, uint64_t master_seed, uint3
   if (rc != HJ_OK) return rc;
   for (uint32_t p0 = pass_begin; p0 < pass_end && rc == HJ_OK; p0 += passes_per_chunk) {
     const uint32_t p1 = std::min(pass_end, p0 + passes_per_chunk);
-    for (uint32_t p = p0; p < p1; p++)
-      for (uint32_t j = 0; j < per_pass; j++)
-        if (grid.owner(static_deal ? 0u : p, j, world) == rank) chunk.push_back(grid.make(master_seed, p, j));
+    frame_blocks_append(grid, master_seed, p0, p1, rank, world, static_deal, chunk);
     // whole batches now (the slots keep running while the next chunk is generated); the remainder joins the next chunk
     const size_t full = p1 == pass_end ? chunk.size() : chunk.size() / run.batch * run.batch;
     rc = run_submit(ctx, run, chunk.data(), full);

@@ -3,7 +3,7 @@
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
 //              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] [--env FILE [--env-scale S]]
 //              [--bake-lightmap WxH [--gutter 2] [--filter N[,sp[,sn[,sc]]]] [--adaptive min,step,max,rel[,floor]] [--sample-map FILE]]
-//              <scene.obj | synthetic:KIND>
+//              [--aovs PREFIX] <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
 // no preview window, so --present-interval is accepted and ignored; --seed replaces the OS-seeded block RNG; --textures (not
@@ -16,6 +16,9 @@
 // --adaptive min,step,max,rel[,floor] (not upstream) bakes with hj_bake_lightmap_adaptive: every texel gets `min` samples, then `step`
 // more a round up to `max`, until the standard error of its mean luminance is at most rel * max(mean, floor) (floor: 0.01 unless
 // given); -s is then ignored, with a note on stderr.  --sample-map FILE writes the samples each texel received as a one-channel PFM.
+// --aovs PREFIX (not upstream) writes, beside the frame, PREFIX_albedo.pfm, PREFIX_normal.pfm and PREFIX_depth.pfm (the depth in all
+// three channels): hj_render_aovs_frame for the frame's own -s and --seed, its sums divided by the sample count (albedo) or the hit
+// count (normal, depth), 0 where the count is 0.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -45,6 +48,7 @@ struct Opt {
   hj_adaptive_opts adaptive{0u, 0u, 0u, 0.0f, 0.01f};      // --adaptive min,step,max,rel[,floor]
   bool adaptive_given = false, samples_given = false;      // (samples_given: -s was on the command line)
   std::string sample_map;                                  // --sample-map FILE
+  std::string aovs;                                        // --aovs PREFIX
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -66,6 +70,9 @@ struct Opt {
                "                                                 min samples, then step more a round up to max, until the standard error of the\n"
                "                                                 mean luminance is at most rel * max(mean, floor [0.01]); -s is ignored\n"
                "        --sample-map <file>                      (not upstream) with --adaptive: the samples per texel as a one-channel PFM\n"
+               "        --aovs <prefix>                          (not upstream) beside the frame: <prefix>_albedo.pfm, <prefix>_normal.pfm and\n"
+               "                                                 <prefix>_depth.pfm - the means over the frame's own primary rays of the first\n"
+               "                                                 hit's albedo, shading normal and distance (0 where nothing was hit)\n"
                "OPTIONS:\n    -h, --height <height>                        [default: 600]\n"
                "    -o, --output-image <output-image>            [default: /tmp/output.exr] (.exr, .pfm or .png)\n"
                "        --present-interval <present-interval>    [default: 128] (ignored: no preview window)\n"
@@ -141,6 +148,7 @@ Opt parse(int argc, char** argv) {
       o.adaptive_given = true;
     }
     else if (a == "--sample-map") o.sample_map = value(i);
+    else if (a == "--aovs") o.aovs = value(i);
     else if (a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown flag " + a).c_str());
     else if (o.scene.empty()) o.scene = a;
@@ -152,6 +160,7 @@ Opt parse(int argc, char** argv) {
   if (o.filter_given && o.bake_w == 0) usage("--filter without --bake-lightmap");
   if (o.adaptive_given && o.bake_w == 0) usage("--adaptive without --bake-lightmap");
   if (!o.sample_map.empty() && !o.adaptive_given) usage("--sample-map without --adaptive");
+  if (!o.aovs.empty() && o.bake_w != 0) usage("--aovs belongs to a frame, not to --bake-lightmap");
   if (o.adaptive_given && o.samples_given) std::fprintf(stderr, "note: --adaptive decides the samples per texel; -s %u is ignored\n", o.sample_count);
   if (o.filter_given && o.filter_sp < 0.0f && o.device_bvh) usage("--filter with --device-bvh needs its sigma_position (no root box on the host)");
   return o;
@@ -286,6 +295,25 @@ int main(int argc, char** argv) {
     std::vector<float> rgb((size_t)opt.width * opt.height * 3);
     check(ctx, hj_framebuffer_resolve(ctx, rgb.data()), "read-back");  // Renderer::save_image, src/main.rs:1493
     save(opt.width, opt.height, rgb.data());
+    if (!opt.aovs.empty()) {
+      // the frame's own primary rays again (same spp and seed): sums per pixel, resolved as the Python wrapper's resolve_aovs does -
+      // albedo over the sample count, normal and depth over the hit count, 0 where the count is 0
+      const size_t px = (size_t)opt.width * opt.height;
+      std::vector<float> aov(px * HJ_AOV_WORDS), albedo(px * 3), normal(px * 3), depth(px * 3);
+      check(ctx, hj_render_aovs_frame(ctx, opt.width, opt.height, opt.sample_count, opt.seed, 0, opt.sample_count, 0u, aov.data()), "AOVs");
+      for (size_t i = 0; i < px; i++) {
+        const float* a = &aov[i * HJ_AOV_WORDS];
+        const float samples = a[3], hits = a[11];
+        for (int c = 0; c < 3; c++) {
+          albedo[3 * i + c] = samples > 0.0f ? a[c] / samples : 0.0f;
+          normal[3 * i + c] = hits > 0.0f ? a[4 + c] / hits : 0.0f;
+          depth[3 * i + c] = hits > 0.0f ? a[7] / hits : 0.0f;
+        }
+      }
+      hijiki::write_pfm(opt.aovs + "_albedo.pfm", opt.width, opt.height, albedo.data());
+      hijiki::write_pfm(opt.aovs + "_normal.pfm", opt.width, opt.height, normal.data());
+      hijiki::write_pfm(opt.aovs + "_depth.pfm", opt.width, opt.height, depth.data());
+    }
     hj_context_destroy(ctx);
     return 0;
   } catch (const std::exception& e) {

@@ -31,7 +31,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains", "hj_probe_visibility_rays",
            "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
-           "hj_distance_field", "hj_trace_rays_all", "hj_points_inside")
+           "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -121,6 +121,9 @@ def lib():
         L.hj_distance_field.argtypes = [vp, C.POINTER(abi.ProbeDesc), C.c_float, C.c_uint32, vp]
         L.hj_trace_rays_all.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp]         # (host or device pointers)
         L.hj_points_inside.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp]
+        L.hj_eval_materials.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]                     # (host or device pointers)
+        L.hj_render_aovs.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.hj_render_aovs_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -178,6 +181,29 @@ def env_distribution(textures, env):
 
 def device_count():
     return lib().hj_device_count()
+
+
+def resolve_aovs(aov):
+    """The (height, width, 12) sums of `Renderer.render_aovs` as means -> dict(albedo (H, W, 3): words 0..2 over the sample count
+    (word 3); normal (H, W, 3), depth (H, W): words 4..6 and 7 over the hit count (word 11); emission (H, W, 3): words 8..10 over the
+    sample count; coverage (H, W): hits over samples), each 0 where its count is 0.  The normal mean is not renormalised.  A numpy
+    array gives numpy arrays, a torch tensor tensors on its device."""
+    if type(aov).__module__.split(".")[0] == "torch":
+        import torch
+        where, zero = torch.where, torch.zeros((), dtype=aov.dtype, device=aov.device)
+    else:
+        aov = np.asarray(aov, np.float32)
+        where, zero = np.where, np.float32(0)
+    if aov.ndim != 3 or aov.shape[2] != abi.AOV_WORDS:
+        raise ValueError(f"resolve_aovs: (height, width, {abi.AOV_WORDS}) is needed (got {tuple(aov.shape)})")
+    samples, hits = aov[..., 3], aov[..., 11]
+
+    def mean(x, count):
+        c = count if x.ndim == count.ndim else count[..., None]
+        return where(c > 0, x / where(c > 0, c, zero + 1), zero)
+
+    return dict(albedo=mean(aov[..., 0:3], samples), normal=mean(aov[..., 4:7], hits), depth=mean(aov[..., 7], hits),
+                emission=mean(aov[..., 8:11], samples), coverage=mean(hits, samples))
 
 
 class Comm:
@@ -687,6 +713,58 @@ class Renderer:
         out = np.zeros((n, 2), np.uint32)
         self._check(lib().hj_points_inside(self._h, points.ctypes.data, n, flags, out.ctypes.data))
         return out[:, 0].copy(), out[:, 1].copy()
+
+    def eval_materials(self, hits, surface):
+        """hj_eval_materials: the material at each of n hits -> (n, 8) float32 records: albedo (3), the uploaded material word as bits
+        (abi.MATERIAL_MISS for a miss), emitted radiance (3), 0.  hits (n, 4) and surface (n, 16) are hj_trace_rays' two arrays - the
+        hit records (shape id bits, t, u, v; `trace_rays` returns their columns: stack ids.view(float32), t, u, v) and the surface
+        records.  Diffuse: its colour; checkerboard and image texture: evaluated at the surface record's (u, v); mirror and glass:
+        albedo 1; an emitter: albedo 0 and its power as emission; a miss: zeros.  float32 numpy arrays give a numpy array.
+        Contiguous float32 torch tensors on the renderer's GPU are read in place and give a tensor on that GPU; torch's current
+        stream is synchronised first."""
+        hits, is_torch = self._query_input("eval_materials", hits, 4)
+        surface, surf_torch = self._query_input("eval_materials", surface, 16)
+        if is_torch != surf_torch or hits.shape[0] != surface.shape[0]:
+            raise ValueError(f"eval_materials: hits {tuple(hits.shape)} and surface {tuple(surface.shape)} must be n records of one kind (arrays or tensors)")
+        n = hits.shape[0]
+        if is_torch:
+            import torch
+            out = torch.empty((n, abi.MATERIALS_WORDS), dtype=torch.float32, device=hits.device)
+            torch.cuda.current_stream(hits.device).synchronize()      # (the allocation and whatever wrote the inputs)
+            self._check(lib().hj_eval_materials(self._h, hits.data_ptr() if n else None, surface.data_ptr() if n else None, n,
+                                                abi.MATERIALS_DEVICE_ARRAYS, out.data_ptr() if n else None))
+            return out
+        out = np.zeros((n, abi.MATERIALS_WORDS), np.float32)
+        self._check(lib().hj_eval_materials(self._h, hits.ctypes.data, surface.ctypes.data, n, 0, out.ctypes.data))
+        return out
+
+    def render_aovs(self, width, height, blocks=None, spp=None, master_seed=0, passes=None, device=False):
+        """hj_render_aovs / hj_render_aovs_frame: the first-hit AOVs of a frame's primary rays -> (height, width, 12) float32: per pixel
+        the float32 sums, in block order, of its samples' records (albedo.rgb, 1 | shading normal.xyz, t | emission.rgb, 1 on a
+        hit; a miss: 0, 0, 0, 1 and zeros) - `resolve_aovs` turns them into means.  blocks: a ctypes array (or list) of
+        abi.ImageBlock, each with original_dimension == (width, height) and dimension <= 128; or spp [, master_seed, passes =
+        (begin, end)]: the blocks `render_frame(spp, master_seed, begin, end)` renders on a width x height framebuffer.  Needs no
+        framebuffer and leaves it alone.  device=True: a torch tensor on the renderer's GPU, written in place."""
+        if (blocks is None) == (spp is None):
+            raise ValueError("render_aovs: either blocks or spp is needed")
+        width, height = int(width), int(height)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            aov = torch.empty((height, width, abi.AOV_WORDS), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            ptr, flags = aov.data_ptr(), abi.AOV_DEVICE_ARRAY
+        else:
+            aov = np.zeros((height, width, abi.AOV_WORDS), np.float32)
+            ptr, flags = aov.ctypes.data, 0
+        if blocks is not None:
+            if not isinstance(blocks, C.Array):
+                blocks = (abi.ImageBlock * len(blocks))(*blocks)
+            self._check(lib().hj_render_aovs(self._h, blocks, len(blocks), width, height, flags, ptr))
+        else:
+            begin, end = (0, int(spp)) if passes is None else (int(passes[0]), int(passes[1]))
+            self._check(lib().hj_render_aovs_frame(self._h, width, height, int(spp), int(master_seed), begin, end, flags, ptr))
+        return aov
 
     def trace_paths(self, rays, seeds=None, spp=1, opts=None, stats=False):
         """hj_trace_paths: the path-traced radiance along (n, 8) rays (origin, direction of any length, a uint32 seed as the bits of

@@ -1394,6 +1394,65 @@ int hj_trace_rays_all(hj_context* ctx, const float* rays /* n x 8 */, size_t n, 
                       uint32_t* counts /* n x 2 */, float* hits /* n x max_hits x 4; may be NULL with max_hits 0 */);
 int hj_points_inside(hj_context* ctx, const float* points /* n x 4: p.xyz, reserved */, size_t n, uint32_t flags, uint32_t* out /* n x 2 */);
 
+/* ------------------------------------------- frame AOVs and material queries */
+
+/* Frame AOVs and material queries (ABI 0.26): what colour a surface has, and a frame's auxiliary buffers - albedo, normal, depth,
+ * emission, coverage - from the frame's own primary rays (no counterpart in the reference, which evaluates a material only inside
+ * its path loop).  The colour functions are the shade stage's own - the checkerboard (shader/materials/diffusecb.glsl) and the image
+ * texture look-up (hj_texture above) -, called through one tag dispatch (kernels/hj_aov.h eval_material); tests/aov_ref.py restates
+ * the contract in numpy.
+ *
+ * A material record, 8 floats: [0..2] albedo, [3] the uploaded material word as bits (tag << 24 | index), [4..6] emitted radiance,
+ *   [7] 0.  By tag: HJ_MAT_DIFFUSE: albedo = the material's colour.  HJ_MAT_DIFFUSECBOARD: with fu = (0.5 * u) / scale_u and
+ *   fv = (0.5 * v) / scale_v, each minus its floor, albedo = color_b when (fu < 0.5) != (fv < 0.5), else color_a - every operation
+ *   float32.  HJ_MAT_DIFFUSE_TEXTURED: the texture look-up of texture `index` at (u, v).  HJ_MAT_MIRROR, HJ_MAT_DIELECTRIC: albedo
+ *   (1, 1, 1).  HJ_MAT_EMISSIVE: albedo 0, emission = the material's power - what a path adds for a discrete hit at throughput 1.
+ *   Everything not named is 0.  A miss - an id outside [0, shapes), -1 included - is all zero except word 3 = 0xFFFFFFFF.
+ *
+ * hj_eval_materials:  hits (n x 4) and surface (n x 16) are the two arrays hj_trace_rays writes: the shape id is hits[4i] as bits,
+ *     (u, v) are surface[16i + 6] and surface[16i + 7].  The material word is read from the uploaded scene by id, not from
+ *     surface[16i + 14]: a miss's all-zero record would read as "diffuse, index 0".  out: n material records.
+ *   HJ_MATERIALS_DEVICE_ARRAYS: the three arrays are device pointers on the context's GPU, 16-byte aligned, used in place (the caller
+ *     orders its own streams before the call).  Without it they are host arrays, staged in chunks of HJ_TRACE_CHUNK records.
+ *   Runs on the context's stream and returns when the results are complete.  n == 0: HJ_OK, nothing touched.
+ *   HJ_ERR_INVALID, checked before anything else and before the device is touched, in this order: a null array (n > 0); unknown flag
+ *     bits; n above 2^31 - 1; with device arrays, a misaligned array.  With a null context the text is in hj_last_error(NULL).  A
+ *     refused call writes nothing.  Then hj_trace_rays' gate: a null context (HJ_ERR_DEVICE in a process without a HIP device,
+ *     HJ_ERR_INVALID otherwise); HJ_ERR_STATE for an asynchronous frame in flight, undrained frames, no scene.
+ *
+ * hj_render_aovs:  for every sample of every block - local pixel (lx, ly) with lx < dimension.x, ly < dimension.y and both inside
+ *     original_dimension, exactly the samples hj_render_blocks takes - the camera ray of that sample (origin camera.position,
+ *     tMin = eps, tMax = +inf) goes through the uploaded tree by the path kernel's walk, and its first hit is populated as the path
+ *     kernel populates it (hit point fma(t, d, o)).  The sample's record, HJ_AOV_WORDS floats:
+ *       [0..3] albedo.rgb, 1     [4..7] shading normal n.xyz, t     [8..11] emission.rgb, 1
+ *     with albedo and emission as in a material record; a miss gives 0, 0, 0, 1 and eight zeros.
+ *   aov: height x width x HJ_AOV_WORDS floats, OVERWRITTEN: pixel (origin + l) is the float32 sum of its samples' records, block by
+ *     block in the order of the list, starting from +0; a pixel no sample covers is twelve zeros (a sample whose pixel lies outside
+ *     the image is dropped).  So word 3 is the sample count, word 11 the hit count, words 4..6 over word 11 the mean normal, word 7
+ *     over word 11 the mean depth of the hits, words 0..2 over word 3 the mean albedo.  A record depends on the blocks, the scene
+ *     and the camera alone: not on HJ_TRACE_CHUNK, the workgroup count or the lane that carried a ray.
+ *   Every block needs original_dimension == (width, height) and dimension <= HJ_BLOCK_SIZE per axis.  No framebuffer is needed, and
+ *     the framebuffer and the batch slots are left alone, as by the queries.
+ *   HJ_AOV_DEVICE_ARRAY: aov is a device pointer on the context's GPU, 16-byte aligned, written in place.
+ *   HJ_ERR_INVALID, before the device is touched, in this order: null blocks (num_blocks > 0) or aov; unknown flag bits; a zero width
+ *     or height or one above 16384; a block whose original_dimension differs or whose dimension is above HJ_BLOCK_SIZE; a misaligned
+ *     device array.  Then hj_trace_rays' gate.  num_blocks == 0: HJ_OK behind the gate, with an all-zero output.
+ * hj_render_aovs_frame:  hj_render_aovs over exactly the block list hj_render_frame generates for world == 1 with the same spp,
+ *     master_seed and pass range (width x height takes the framebuffer's place): the AOVs of that frame's primary rays.  Behind the
+ *     refusals above: pass_begin > pass_end or pass_end > spp is HJ_ERR_INVALID.  An empty pass range: HJ_OK, an all-zero output.
+ * Not here: an environment's radiance for a miss; following mirror or glass to the first diffuse surface; a material at a
+ *   closest-point or all-hit record (those carry no texture coordinates yet); a multi-GPU split; a denoiser. */
+#define HJ_MATERIALS_DEVICE_ARRAYS 1u
+#define HJ_MATERIALS_WORDS 8
+#define HJ_AOV_DEVICE_ARRAY 1u
+#define HJ_AOV_WORDS 12
+int hj_eval_materials(hj_context* ctx, const float* hits /* n x 4 */, const float* surface /* n x 16 */, size_t n, uint32_t flags,
+                      float* out /* n x 8 */);
+int hj_render_aovs(hj_context* ctx, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags,
+                   float* aov /* height x width x 12 */);
+int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
+                         uint32_t pass_end, uint32_t flags, float* aov /* height x width x 12 */);
+
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host
  * library's ImageBlockGenerator and restated by the oracle. */
