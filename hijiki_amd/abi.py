@@ -63,6 +63,8 @@ MATERIALS_WORDS = 8               # words of a material record: albedo.rgb, mate
 MATERIAL_MISS = 0xFFFFFFFF        # ... its word 3 for a miss
 AOV_DEVICE_ARRAY = 1              # hj_render_aovs / hj_render_aovs_frame flag
 AOV_WORDS = 12                    # words of an AOV pixel: albedo.rgb, samples | normal.xyz, t | emission.rgb, hits - each a sum
+DENOISE_DEVICE_ARRAYS = 1         # hj_denoise_opts flag
+DENOISE_MAX_ITERATIONS = 8        # hj_denoise_opts: iteration i uses the step 1 << i
 
 
 def probe_vis_words(res):
@@ -221,6 +223,11 @@ class LightmapDesc(C.Structure):
 class LightmapFilter(C.Structure):
     """hj_lightmap_filter (ABI 0.17): the iterations and the edge stops of hj_filter_lightmap / hj_bake_lightmap_filtered."""
     _fields_ = [("iterations", u32), ("sigma_position", f32), ("sigma_normal", f32), ("sigma_color", f32), ("flags", u32)]
+
+
+class DenoiseOpts(C.Structure):
+    """hj_denoise_opts (ABI 0.27): the iterations and the edge stops of hj_denoise_frame."""
+    _fields_ = [("iterations", u32), ("sigma_normal", f32), ("sigma_depth", f32), ("sigma_luminance", f32), ("sigma_albedo", f32), ("flags", u32)]
 
 
 class ProbeDesc(C.Structure):

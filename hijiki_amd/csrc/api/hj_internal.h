@@ -80,6 +80,9 @@
 //                         frame's albedo / normal / depth sums from its own primary rays (includes kernels/hj_aov.h, which includes
 //                         the kernel headers up to hj_stages.h and edits none: k_mat_eval; k_aov_walk, the persistent walk with a
 //                         fetch that builds the camera ray from the sample index; k_aov_resolve, run by run of disjoint blocks)
+//   api/denoise.hip       hj_denoise_frame: the variance-guided a-trous filter over a frame's albedo-demodulated light, guided by the
+//                         frame's AOV sums (includes kernels/hj_denoise.h and hj_num.h alone: k_dn_prepare, k_dn_variance, the
+//                         iteration as k_dn_filter_lds or k_dn_filter_direct, k_dn_finish)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -471,6 +474,11 @@ struct hj_context {
   // of host arrays - one chunk of hit records, surface records and material records (16, 64 and 32 bytes a record).  The sibling of
   // RayQuery: grown on demand, reused by every call, freed with the context.  Never the batch slots' or the framebuffer.
   struct Aov { hjapi::DevBuf blocks, hits, image, in_hits, in_surface, out; } aov;
+
+  // hj_denoise_frame (api/denoise.hip): the guide (48 bytes a pixel: normal and depth, albedo and valid word, depth slope) and the
+  // two working images (16 bytes a pixel each); the staging of host arrays - beauty, AOV image, result (16, 48 and 16 bytes a
+  // pixel).  Grown on demand, reused by every call, freed with the context.  The framebuffer is read, never written.
+  struct Denoise { hjapi::DevBuf guide, image[2], in_beauty, in_aov, out; } denoise;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment

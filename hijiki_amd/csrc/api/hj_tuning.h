@@ -71,7 +71,9 @@ struct Tuning {
   X(lightmap_lane_texels, "HJ_LIGHTMAP_LANE_TEXELS", 64, 0, 1 << 28) /* k_lm_owner: a texel box up to this size is one lane's, a larger one k_lm_owner_wide's */ \
   X(lightmap_slices, "HJ_LIGHTMAP_SLICES", kUnset, 1, 256) /* grid rows of k_lm_owner_wide that share a box: as many as fill the device, at most 256 */ \
   /* hj_filter_lightmap / hj_bake_lightmap_filtered (read like the rows above) */                                                        \
-  X(lightmap_filter_lds_step, "HJ_LIGHTMAP_FILTER_LDS_STEP", 128, 0, 128) /* steps up to this take k_lm_filter_lds, larger ones k_lm_filter_direct: 0 never, 128 always (measured faster at every step) */
+  X(lightmap_filter_lds_step, "HJ_LIGHTMAP_FILTER_LDS_STEP", 128, 0, 128) /* steps up to this take k_lm_filter_lds, larger ones k_lm_filter_direct: 0 never, 128 always (measured faster at every step) */ \
+  /* hj_denoise_frame (read like the rows above) */                                                                                      \
+  X(denoise_lds_step, "HJ_DENOISE_LDS_STEP", 8, 0, 128)    /* steps up to this take k_dn_filter_lds, larger ones k_dn_filter_direct: 0 never, 128 always (measured: faster up to step 8, slower at 16) */
   // presence flags (debugging aids): set to anything = on
 #define HJ_TUNING_FLAGS(X)                                                                                                              \
   X(trace_bounces, "HJ_TRACE_BOUNCES")                     /* per-bounce table of the split-kernel path on stderr */                    \

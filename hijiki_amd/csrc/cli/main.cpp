@@ -3,7 +3,7 @@
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
 //              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] [--env FILE [--env-scale S]]
 //              [--bake-lightmap WxH [--gutter 2] [--filter N[,sp[,sn[,sc]]]] [--adaptive min,step,max,rel[,floor]] [--sample-map FILE]]
-//              [--aovs PREFIX] <scene.obj | synthetic:KIND>
+//              [--aovs PREFIX] [--denoise FILE [--denoise-params iters,sn,sz,sl,sa]] <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
 // no preview window, so --present-interval is accepted and ignored; --seed replaces the OS-seeded block RNG; --textures (not
@@ -19,6 +19,10 @@
 // --aovs PREFIX (not upstream) writes, beside the frame, PREFIX_albedo.pfm, PREFIX_normal.pfm and PREFIX_depth.pfm (the depth in all
 // three channels): hj_render_aovs_frame for the frame's own -s and --seed, its sums divided by the sample count (albedo) or the hit
 // count (normal, depth), 0 where the count is 0.
+// --denoise FILE (not upstream) writes, beside the frame, the frame denoised: hj_render_aovs_frame for the frame's own -s and --seed,
+// then hj_denoise_frame over the framebuffer on the device (beauty = NULL); the rgb goes to FILE through the writer its extension
+// chooses.  --denoise-params iters,sn,sz,sl,sa: the iterations (5) and the sigmas of normal (0.5), depth (1), luminance (4) and
+// albedo (0.1) - SVGF's starting points where it has them, guesses elsewhere, not tuned.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -49,6 +53,9 @@ struct Opt {
   bool adaptive_given = false, samples_given = false;      // (samples_given: -s was on the command line)
   std::string sample_map;                                  // --sample-map FILE
   std::string aovs;                                        // --aovs PREFIX
+  std::string denoise;                                     // --denoise FILE
+  hj_denoise_opts denoise_opts{5u, 0.5f, 1.0f, 4.0f, 0.1f, 0u};   // --denoise-params iters,sn,sz,sl,sa
+  bool denoise_params_given = false;
 };
 
 [[noreturn]] void usage(const char* msg) {
@@ -73,6 +80,10 @@ struct Opt {
                "        --aovs <prefix>                          (not upstream) beside the frame: <prefix>_albedo.pfm, <prefix>_normal.pfm and\n"
                "                                                 <prefix>_depth.pfm - the means over the frame's own primary rays of the first\n"
                "                                                 hit's albedo, shading normal and distance (0 where nothing was hit)\n"
+               "        --denoise <file>                         (not upstream) beside the frame: the frame denoised by the AOV-guided a-trous\n"
+               "                                                 filter (.exr, .pfm or .png)\n"
+               "        --denoise-params <iters>,<sn>,<sz>,<sl>,<sa>  (not upstream) iterations 0 ... 8 [5] and the sigmas of normal [0.5], depth [1],\n"
+               "                                                 luminance [4] and albedo [0.1] of --denoise: starting points, not tuned\n"
                "OPTIONS:\n    -h, --height <height>                        [default: 600]\n"
                "    -o, --output-image <output-image>            [default: /tmp/output.exr] (.exr, .pfm or .png)\n"
                "        --present-interval <present-interval>    [default: 128] (ignored: no preview window)\n"
@@ -149,6 +160,19 @@ Opt parse(int argc, char** argv) {
     }
     else if (a == "--sample-map") o.sample_map = value(i);
     else if (a == "--aovs") o.aovs = value(i);
+    else if (a == "--denoise") o.denoise = value(i);
+    else if (a == "--denoise-params") {
+      const std::string v = value(i);
+      unsigned n = 0;
+      float sg[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      char tail = 0;
+      const int got = std::sscanf(v.c_str(), "%u,%f,%f,%f,%f%c", &n, &sg[0], &sg[1], &sg[2], &sg[3], &tail);
+      bool ok = got == 5 && n <= HJ_DENOISE_MAX_ITERATIONS && v.find_first_not_of("0123456789.,eE+-") == std::string::npos;
+      for (int k = 0; ok && k < 4; k++) ok = sg[k] >= 0.0f && sg[k] <= 3.0e38f;
+      if (!ok) usage(("bad --denoise-params " + v + " (iters,sn,sz,sl,sa: iters = 0 ... 8, sigmas finite and >= 0)").c_str());
+      o.denoise_opts = hj_denoise_opts{n, sg[0], sg[1], sg[2], sg[3], 0u};
+      o.denoise_params_given = true;
+    }
     else if (a == "--help") usage(nullptr);
     else if (!a.empty() && a[0] == '-') usage(("unknown flag " + a).c_str());
     else if (o.scene.empty()) o.scene = a;
@@ -161,6 +185,8 @@ Opt parse(int argc, char** argv) {
   if (o.adaptive_given && o.bake_w == 0) usage("--adaptive without --bake-lightmap");
   if (!o.sample_map.empty() && !o.adaptive_given) usage("--sample-map without --adaptive");
   if (!o.aovs.empty() && o.bake_w != 0) usage("--aovs belongs to a frame, not to --bake-lightmap");
+  if (!o.denoise.empty() && o.bake_w != 0) usage("--denoise belongs to a frame, not to --bake-lightmap");
+  if (o.denoise_params_given && o.denoise.empty()) usage("--denoise-params without --denoise");
   if (o.adaptive_given && o.samples_given) std::fprintf(stderr, "note: --adaptive decides the samples per texel; -s %u is ignored\n", o.sample_count);
   if (o.filter_given && o.filter_sp < 0.0f && o.device_bvh) usage("--filter with --device-bvh needs its sigma_position (no root box on the host)");
   return o;
@@ -226,12 +252,13 @@ int main(int argc, char** argv) {
     } else {
       check(ctx, opt.textures ? hj_scene_upload_textured(ctx, &desc, &tex) : hj_scene_upload(ctx, &desc), "scene upload");
     }
-    const auto save = [&](uint32_t w, uint32_t h, const float* rgb) {
-      const std::string ext = opt.output_image.size() > 4 ? opt.output_image.substr(opt.output_image.size() - 4) : "";
-      if (ext == ".pfm") hijiki::write_pfm(opt.output_image, w, h, rgb);
-      else if (ext == ".png") hijiki::write_png(opt.output_image, w, h, rgb);   // the preview image
-      else hijiki::write_exr(opt.output_image, w, h, rgb);
+    const auto save_to = [](const std::string& path, uint32_t w, uint32_t h, const float* rgb) {
+      const std::string ext = path.size() > 4 ? path.substr(path.size() - 4) : "";
+      if (ext == ".pfm") hijiki::write_pfm(path, w, h, rgb);
+      else if (ext == ".png") hijiki::write_png(path, w, h, rgb);   // the preview image
+      else hijiki::write_exr(path, w, h, rgb);
     };
+    const auto save = [&](uint32_t w, uint32_t h, const float* rgb) { save_to(opt.output_image, w, h, rgb); };
     if (opt.bake_w != 0) {                                             // --bake-lightmap: the atlas instead of a frame
       const hj_lightmap_desc lm{opt.bake_w, opt.bake_h, 0u, 0u, (uint32_t)opt.seed, 1u, 1e-3f, 0u};
       std::vector<float> rgba((size_t)opt.bake_w * opt.bake_h * 4), rgb((size_t)opt.bake_w * opt.bake_h * 3);
@@ -313,6 +340,16 @@ int main(int argc, char** argv) {
       hijiki::write_pfm(opt.aovs + "_albedo.pfm", opt.width, opt.height, albedo.data());
       hijiki::write_pfm(opt.aovs + "_normal.pfm", opt.width, opt.height, normal.data());
       hijiki::write_pfm(opt.aovs + "_depth.pfm", opt.width, opt.height, depth.data());
+    }
+    if (!opt.denoise.empty()) {
+      // the frame's own primary rays again (same spp and seed) for the guides, then the filter over the framebuffer where it lies
+      const size_t px = (size_t)opt.width * opt.height;
+      std::vector<float> aov(px * HJ_AOV_WORDS), rgba(px * 4), clean(px * 3);
+      check(ctx, hj_render_aovs_frame(ctx, opt.width, opt.height, opt.sample_count, opt.seed, 0, opt.sample_count, 0u, aov.data()), "AOVs");
+      check(ctx, hj_denoise_frame(ctx, opt.width, opt.height, nullptr, aov.data(), &opt.denoise_opts, rgba.data()), "denoise");
+      for (size_t i = 0; i < px; i++)
+        for (int c = 0; c < 3; c++) clean[3 * i + c] = rgba[4 * i + c];
+      save_to(opt.denoise, opt.width, opt.height, clean.data());
     }
     hj_context_destroy(ctx);
     return 0;

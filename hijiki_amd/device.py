@@ -31,7 +31,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_sample_probes", "hj_debug_vote_cast", "hj_debug_vote_exchange", "hj_debug_vote_gains", "hj_probe_visibility_rays",
            "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
-           "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame")
+           "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame",
+           "hj_denoise_frame")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -124,6 +125,7 @@ def lib():
         L.hj_eval_materials.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]                     # (host or device pointers)
         L.hj_render_aovs.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_render_aovs_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.hj_denoise_frame.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), vp]   # (host or device pointers)
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -765,6 +767,51 @@ class Renderer:
             begin, end = (0, int(spp)) if passes is None else (int(passes[0]), int(passes[1]))
             self._check(lib().hj_render_aovs_frame(self._h, width, height, int(spp), int(master_seed), begin, end, flags, ptr))
         return aov
+
+    def denoise_frame(self, aov, beauty=None, iterations=5, sigma_normal=0.5, sigma_depth=1.0, sigma_luminance=4.0, sigma_albedo=0.1, device=False):
+        """hj_denoise_frame: the variance-guided a-trous filter of SVGF over one frame -> a new (height, width, 4) float32 image: the
+        denoised rgb and, in word 3, the filtered variance of the demodulated luminance.  aov: the (height, width, 12) sums of
+        `render_aovs` for the same frame.  beauty: (height, width, 4) in the framebuffer's format, (sum w * rgb, sum w) - what
+        `read` returns; None: the renderer's own framebuffer, read on the device and left as it is (it must
+        be width x height).  The light is divided by the first hit's mean albedo (floored at 1 / 64), filtered by `iterations`
+        (0 ... 8) 5 x 5 B3-spline passes at the steps 1, 2, 4, ... with edge stops on normal (`sigma_normal`), depth in units of
+        the local depth slope (`sigma_depth`), albedo (`sigma_albedo`) and luminance in standard deviations of a filtered
+        per-pixel variance (`sigma_luminance`), and multiplied by the albedo again; a sigma of 0 switches its stop off.  Pixels
+        without a hit or without a sample keep their colour, and so do a directly seen emitter's pixels and the pixels within two
+        of them (the reach of the framebuffer's reconstruction filter).  The defaults are SVGF's starting points where it has them (depth,
+        luminance) and guesses elsewhere: not tuned.  device=True: `aov` (and `beauty`) are contiguous float32 torch tensors on the
+        renderer's GPU, read in place; the result is a new tensor there; torch's current stream is synchronised first."""
+        iterations = int(iterations)
+        sig = [float(sigma_normal), float(sigma_depth), float(sigma_luminance), float(sigma_albedo)]
+        if not 0 <= iterations <= abi.DENOISE_MAX_ITERATIONS:
+            raise ValueError(f"denoise_frame: {iterations} iterations: 0 ... {abi.DENOISE_MAX_ITERATIONS}")
+        for name, v in zip(("sigma_normal", "sigma_depth", "sigma_luminance", "sigma_albedo"), sig):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"denoise_frame: {name} {v}: finite and >= 0 is needed")
+        o = abi.DenoiseOpts(iterations, *sig, abi.DENOISE_DEVICE_ARRAYS if device else 0)
+        if device:
+            import torch
+            for name, t in (("aov", aov), ("beauty", beauty)):
+                if t is None and name == "beauty":
+                    continue
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"denoise_frame: {name} must be a contiguous float32 tensor on cuda:{self.device}")
+            if aov.dim() != 3 or aov.shape[2] != abi.AOV_WORDS or (beauty is not None and tuple(beauty.shape) != (aov.shape[0], aov.shape[1], 4)):
+                raise ValueError("denoise_frame: aov (height, width, 12) and beauty (height, width, 4) are needed")
+            h, w = int(aov.shape[0]), int(aov.shape[1])
+            out = torch.empty((h, w, 4), dtype=torch.float32, device=aov.device)
+            torch.cuda.current_stream(aov.device).synchronize()       # (the allocation and whatever wrote the inputs)
+            self._check(lib().hj_denoise_frame(self._h, w, h, None if beauty is None else beauty.data_ptr(), aov.data_ptr(), C.byref(o), out.data_ptr()))
+            return out
+        aov = np.ascontiguousarray(aov, np.float32)
+        if beauty is not None:
+            beauty = np.ascontiguousarray(beauty, np.float32)
+        if aov.ndim != 3 or aov.shape[2] != abi.AOV_WORDS or (beauty is not None and beauty.shape != (aov.shape[0], aov.shape[1], 4)):
+            raise ValueError("denoise_frame: aov (height, width, 12) and beauty (height, width, 4) are needed")
+        out = np.zeros((aov.shape[0], aov.shape[1], 4), np.float32)
+        self._check(lib().hj_denoise_frame(self._h, aov.shape[1], aov.shape[0], None if beauty is None else beauty.ctypes.data, aov.ctypes.data, C.byref(o),
+                                           out.ctypes.data))
+        return out
 
     def trace_paths(self, rays, seeds=None, spp=1, opts=None, stats=False):
         """hj_trace_paths: the path-traced radiance along (n, 8) rays (origin, direction of any length, a uint32 seed as the bits of

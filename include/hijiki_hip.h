@@ -1441,7 +1441,7 @@ int hj_points_inside(hj_context* ctx, const float* points /* n x 4: p.xyz, reser
  *     master_seed and pass range (width x height takes the framebuffer's place): the AOVs of that frame's primary rays.  Behind the
  *     refusals above: pass_begin > pass_end or pass_end > spp is HJ_ERR_INVALID.  An empty pass range: HJ_OK, an all-zero output.
  * Not here: an environment's radiance for a miss; following mirror or glass to the first diffuse surface; a material at a
- *   closest-point or all-hit record (those carry no texture coordinates yet); a multi-GPU split; a denoiser. */
+ *   closest-point or all-hit record (those carry no texture coordinates yet); a multi-GPU split.  (A denoiser: hj_denoise_frame below.) */
 #define HJ_MATERIALS_DEVICE_ARRAYS 1u
 #define HJ_MATERIALS_WORDS 8
 #define HJ_AOV_DEVICE_ARRAY 1u
@@ -1452,6 +1452,86 @@ int hj_render_aovs(hj_context* ctx, const hj_image_block* blocks, size_t num_blo
                    float* aov /* height x width x 12 */);
 int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
                          uint32_t pass_end, uint32_t flags, float* aov /* height x width x 12 */);
+
+/* ------------------------------------------- frame denoiser */
+
+/* hj_denoise_frame (ABI 0.27): the spatial filter of SVGF (Schied et al. 2017: its variance-guided a-trous stage) over one frame on
+ * the device, guided by the frame's AOVs - the first consumer of hj_render_aovs.  It filters albedo-demodulated light, so textures
+ * and the checkerboard stay sharp; a 5 x 5 B3-spline kernel whose taps move apart by powers of two, with edge stops on normal,
+ * depth (relative to the local depth slope), albedo and luminance, the last scaled by a per-pixel variance that is itself
+ * filtered.  No counterpart in the reference; tests/denoise_ref.py restates the contract in numpy.
+ *   beauty: height x width x 4 floats in the framebuffer's format, (sum w * rgb, sum w), row y = 0 first.  NULL: the context's
+ *     bound framebuffer is read on the device; it must be width x height (HJ_ERR_INVALID behind the gate otherwise; HJ_ERR_STATE
+ *     when the context has none).  The framebuffer is read, never written.
+ *   aov: height x width x HJ_AOV_WORDS floats, as hj_render_aovs writes it.      out: height x width x 4 floats; never aliases an input.
+ *   Every operation is float32 with one rounding and no contraction: no fused multiply-add outside hj_exp; / and sqrtf are IEEE.
+ *       sq(v) = (v.x * v.x + v.y * v.y) + v.z * v.z        Y(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b
+ *       k = {0.375f, 0.25f, 0.0625f}
+ *   Computed on the host, once: inn = sigma_normal > 0 ? 1.0f / (sigma_normal * sigma_normal) : 0.0f; ia the same of sigma_albedo;
+ *   sz = sigma_depth and sl = sigma_luminance, where 0 switches the term off.
+ *   PREPARE, per pixel, with S = aov[3], Hc = aov[11], bw = beauty[3]:  a pixel is LIT when aov[8], aov[9] or aov[10] is above 0 -
+ *     a sample of it saw an emitter directly.  The pixel is GUIDED when Hc > 0 and bw > 0 and no in-image pixel of the 5 x 5
+ *     window around it, itself included, is lit.  (The framebuffer holds light spread by the reconstruction filter, radius 2: a
+ *     directly seen emitter's radiance reaches the pixels within two of it, while the AOVs are per pixel and know nothing of
+ *     that.  Those pixels, and the emitter's own - noise-free but for their edges - are passed through, or the filter would pull
+ *     the halo down to its surroundings' level and raise the frame's error instead of lowering it.)
+ *     c = beauty.rgb / bw per channel, or +0 when bw is not above 0.
+ *     A_ch = fmaxf(aov[ch] / S, 0.015625f) for ch = 0, 1, 2 - the floor keeps black surfaces (albedo 0) finite: such pixels are
+ *       filtered undemodulated up to a constant.          I = c / A per channel.
+ *     n = aov[4..6] / Hc, not renormalised.          z = aov[7] / Hc.
+ *     A pixel that is not guided has the output (c, 0); it is copied through every iteration and is never a tap.
+ *   SLOPE AND INITIAL VARIANCE, per guided pixel at (x, y):
+ *     gz.x: of the forward difference z[x + 1] - z and the backward difference z - z[x - 1] the one with the smaller magnitude;
+ *       only differences whose neighbour is in the image and guided count; a tie takes the forward one; none: +0.  (The smaller
+ *       one keeps a depth edge from inflating its own slope.)          gz.y: the same along y.
+ *     V: over the guided in-image pixels q of the 5 x 5 window at step 1 (dy = -2 ... 2 outer, dx = -2 ... 2 inner, the pixel
+ *       itself included), from m1 = m2 = cnt = +0:  m1 = m1 + Y(I_q);  m2 = m2 + Y(I_q) * Y(I_q);  cnt = cnt + 1.0f.  Then
+ *       mu = m1 / cnt and V = fmaxf(m2 / cnt - mu * mu, 0.0f).
+ *   ITERATION i = 0 ... iterations - 1, step s = 1 << i, reads (I, V) and writes (I', V'), per guided pixel p = (x, y):
+ *     vbar: over the guided in-image pixels q of the 3 x 3 window at step 1 WHATEVER s is (dy = -1 ... 1 outer, dx = -1 ... 1
+ *       inner), with g = {0.25f, 0.125f, 0.0625f}[|dx| + |dy|], from vsum = gsum = +0:  vsum = vsum + V_q * g;  gsum = gsum + g.
+ *       vbar = vsum / gsum.          sd = sqrtf(vbar).
+ *     sum = (+0, +0, +0), vs = +0, ws = +0, then for dy = -2 ... 2 (outer), dx = -2 ... 2 (inner):
+ *       0. the tap is q = (x + dx * s, y + dy * s); it is skipped when it lies outside the image or is not guided;
+ *       1. h = k[|dx|] * k[|dy|] (the products are exact);
+ *       2. en = sq(n_q - n) * inn;
+ *       3. ez = fabsf(z_q - z) / (sz * fabsf(gz.x * (float)(dx * s) + gz.y * (float)(dy * s)) + 1e-6f), or +0 when sz == 0;
+ *       4. el = fabsf(Y(I_q) - Y(I)) / (sl * sd + 1e-6f), or +0 when sl == 0;
+ *       5. ea = sq(A_q - A) * ia;
+ *       6. w = h * hj_exp(-(((en + ez) + el) + ea)) - the numeric contract's exp (kernels/hj_num.h; HJ_NUM_EXP of hj_debug_num);
+ *       7. sum.r = sum.r + I_q.r * w, likewise g and b;  vs = vs + V_q * (w * w);  ws = ws + w.
+ *     I' = sum / ws, one division per channel;  V' = vs / (ws * ws).  For finite data the centre tap alone gives ws >= 0.140625.
+ *   FINISH: for a guided pixel out.rgb = I * A, one multiply per channel, and out.a = V.
+ *   iterations == 0: the prepare stage still runs; the output is the demodulate / remodulate round trip with the initial variance
+ *   in word 3.  The result depends on (width, height, beauty, aov, opts) alone: not on the kernel form (HJ_DENOISE_LDS_STEP), the
+ *   launch shape or any tuning switch.  Agreement bit for bit with this text is claimed for finite inputs; non-finite values
+ *   just propagate.
+ *   HJ_DENOISE_DEVICE_ARRAYS (opts->flags): beauty (when not NULL), aov and out are device pointers on the context's GPU, 16-byte
+ *     aligned, used in place on the context's stream; the call returns after one synchronisation, and the inputs are left as they
+ *     were.  Without the flag they are host arrays, staged through buffers the context keeps.
+ * The context keeps 48 bytes per pixel of guide data and two working images, grown on demand, freed with the context.
+ * HJ_ERR_INVALID, before the device is touched, in this order, each with its text in hj_last_error behind "hj_denoise_frame:": a
+ *   null opts, aov or out; unknown flag bits; iterations above 8; a negative or non-finite sigma; a zero width or height or one
+ *   above 16384; a misaligned device array.  A refused call writes nothing.  Then hj_trace_rays' gate - a null context
+ *   (HJ_ERR_DEVICE in a process without a HIP device, HJ_ERR_INVALID otherwise); HJ_ERR_STATE for an asynchronous frame in flight or
+ *   undrained frames - except that no scene is needed: this call traces nothing.
+ * The defaults of the Python wrapper and the command line (5 iterations; sigmas 0.5 normal, 1 depth, 4 luminance, 0.1 albedo) are
+ *   SVGF's starting points where it has them (depth, luminance) and guesses elsewhere: they are not tuned.
+ * Not here: temporal accumulation and reprojection; a multi-GPU split; tuned defaults. */
+#define HJ_DENOISE_DEVICE_ARRAYS 1u
+#define HJ_DENOISE_MAX_ITERATIONS 8u
+typedef struct hj_denoise_opts {
+  uint32_t iterations;       /* 0 ... 8; iteration i uses the step s = 1 << i */
+  float    sigma_normal;     /* on |n_q - n|; 0 = stop off */
+  float    sigma_depth;      /* in units of the local depth slope; 0 = off */
+  float    sigma_luminance;  /* in standard deviations of the demodulated luminance; 0 = off */
+  float    sigma_albedo;     /* on |A_q - A|; 0 = off */
+  uint32_t flags;            /* HJ_DENOISE_DEVICE_ARRAYS */
+} hj_denoise_opts;
+int hj_denoise_frame(hj_context* ctx, uint32_t width, uint32_t height,
+                     const float* beauty /* H x W x 4; NULL = the context's framebuffer */,
+                     const float* aov    /* H x W x HJ_AOV_WORDS, as hj_render_aovs writes it */,
+                     const hj_denoise_opts* opts, float* out /* H x W x 4 */);
 
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host
