@@ -65,6 +65,9 @@ AOV_DEVICE_ARRAY = 1              # hj_render_aovs / hj_render_aovs_frame flag
 AOV_WORDS = 12                    # words of an AOV pixel: albedo.rgb, samples | normal.xyz, t | emission.rgb, hits - each a sum
 DENOISE_DEVICE_ARRAYS = 1         # hj_denoise_opts flag
 DENOISE_MAX_ITERATIONS = 8        # hj_denoise_opts: iteration i uses the step 1 << i
+TEMPORAL_WORDS = 12               # words of a history record: I.rgb, N | m1, m2, z, valid word | n.xyz, 0
+TEMPORAL_FEEDBACK = 1             # hj_temporal_opts flag: the first iteration's light goes into the history
+TEMPORAL_VARIANCE_FRAMES = 4      # a history this long gives the variance of its temporal moments
 
 
 def probe_vis_words(res):
@@ -228,6 +231,12 @@ class LightmapFilter(C.Structure):
 class DenoiseOpts(C.Structure):
     """hj_denoise_opts (ABI 0.27): the iterations and the edge stops of hj_denoise_frame."""
     _fields_ = [("iterations", u32), ("sigma_normal", f32), ("sigma_depth", f32), ("sigma_luminance", f32), ("sigma_albedo", f32), ("flags", u32)]
+
+
+class TemporalOpts(C.Structure):
+    """hj_temporal_opts (ABI 0.28): the two cameras, the blend weights and the history tests of hj_denoise_frame_temporal."""
+    _fields_ = [("camera", Camera), ("prev_camera", Camera), ("alpha", f32), ("alpha_moments", f32), ("depth_tolerance", f32), ("normal_cos", f32),
+                ("max_history", u32), ("flags", u32)]
 
 
 class ProbeDesc(C.Structure):

@@ -155,7 +155,7 @@ int drain(hj_context* ctx, const char* fn, hipError_t e) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (27u << 8) | 0u; }   // 0.27.0: hj_denoise_frame
+uint32_t hj_version(void) { return (0u << 16) | (28u << 8) | 0u; }   // 0.28.0: hj_denoise_frame_temporal
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

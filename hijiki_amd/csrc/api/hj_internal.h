@@ -82,7 +82,12 @@
 //                         fetch that builds the camera ray from the sample index; k_aov_resolve, run by run of disjoint blocks)
 //   api/denoise.hip       hj_denoise_frame: the variance-guided a-trous filter over a frame's albedo-demodulated light, guided by the
 //                         frame's AOV sums (includes kernels/hj_denoise.h and hj_num.h alone: k_dn_prepare, k_dn_variance, the
-//                         iteration as k_dn_filter_lds or k_dn_filter_direct, k_dn_finish)
+//                         iteration as k_dn_filter_lds or k_dn_filter_direct, k_dn_finish); the checks, the buffers, the prepare
+//                         stage and the iterations for both denoiser calls (denoise_check ... denoise_filter_enqueue below)
+//   api/denoise_temporal.hip  hj_denoise_frame_temporal: reprojected history in front of that filter - k_dt_accumulate (reproject, blend,
+//                         history record), k_dt_variance (spatial or temporal variance), k_dt_feedback (the first iteration's light
+//                         into the history) between api/denoise.hip's stages (includes kernels/hj_denoise_temporal.h; beside it the
+//                         functions of hj_denoise.h, without its kernels, and hj_num.h alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -478,7 +483,8 @@ struct hj_context {
   // hj_denoise_frame (api/denoise.hip): the guide (48 bytes a pixel: normal and depth, albedo and valid word, depth slope) and the
   // two working images (16 bytes a pixel each); the staging of host arrays - beauty, AOV image, result (16, 48 and 16 bytes a
   // pixel).  Grown on demand, reused by every call, freed with the context.  The framebuffer is read, never written.
-  struct Denoise { hjapi::DevBuf guide, image[2], in_beauty, in_aov, out; } denoise;
+  // hj_denoise_frame_temporal (api/denoise_temporal.hip) adds the staging of the two histories (48 bytes a pixel each).
+  struct Denoise { hjapi::DevBuf guide, image[2], in_beauty, in_aov, out, in_history, out_history; } denoise;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
@@ -569,6 +575,25 @@ inline int lightmap_atlas_check(hj_context* ctx, const char* fn, uint32_t w, uin
 int lightmap_filter_check(hj_context* ctx, const char* fn, const hj_lightmap_filter* f);
 int lightmap_filter_enqueue(hj_context* ctx, const hj_lightmap_filter& f, uint32_t W, uint32_t H, const float4* d_points, uint32_t count, float4* const img[2],
                             uint32_t& cur);
+// The frame denoiser for both of its entry points (api/denoise.hip):
+//   denoise_check            what both refuse of (opts, width, height) behind their null checks, without a device
+//   denoise_begin            the gate (no scene is needed), beauty == NULL against the framebuffer, the context's buffers, the staging
+//                            of host arrays: on HJ_OK f holds the call's device arrays and f.e the first error of the copies enqueued
+//   denoise_prepare_enqueue  k_dn_prepare: the guide's first two records, (I, 0) or (c, 0) into f.work[1]
+//   denoise_filter_enqueue   iterations [i0, i1) from f.work[cur], cur flipped by each; finish: the last of them stores the remodulated
+//                            result into f.out, and with none to run (i0 == i1) f.work[cur] is remodulated alone
+constexpr uint32_t kDenoiseMaxSide = 16384u;
+struct DenoiseFrame {
+  uint32_t W, H;
+  const float4 *beauty, *aov;
+  float4 *guide, *work[2], *out;
+  hipError_t e;
+};
+int denoise_check(hj_context* ctx, const char* fn, uint32_t width, uint32_t height, const hj_denoise_opts* opts);
+int denoise_begin(hj_context* ctx, const char* fn, uint32_t width, uint32_t height, const float* beauty, const float* aov, float* out, bool on_device,
+                  DenoiseFrame& f);
+void denoise_prepare_enqueue(hj_context* ctx, const DenoiseFrame& f);
+void denoise_filter_enqueue(hj_context* ctx, const hj_denoise_opts& o, const DenoiseFrame& f, uint32_t& cur, uint32_t i0, uint32_t i1, bool finish);
 // The statistics read-back of a pass's launches (kStatWords x G words each), summed on the host once the stream has drained.
 // on == false (the caller wants no statistics): every member does nothing.
 struct QueryStats {

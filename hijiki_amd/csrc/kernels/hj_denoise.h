@@ -11,6 +11,7 @@
 // one ran never shows in a bit.  Every operation is float32, one rounding each, uncontracted.  Ordinary loads and stores, no
 // inline assembly, no global atomic.  Shares no kernel with hj_lightmap_filter.h (its spline and sq are restated here: including
 // that header would define its kernels a second time).
+//   (the kernels are left out under HJ_DENOISE_NO_KERNELS: hj_denoise_temporal.h takes the functions alone)
 #pragma once
 #include "../../../include/hijiki_hip.h"
 #include "hj_num.h"
@@ -91,6 +92,8 @@ HJ_DEV float4 dn_result(const DnAcc& acc, const DnCentre& p, const DnArgs& a) {
   const float r = acc.r / acc.ws, g = acc.g / acc.ws, b = acc.b / acc.ws, v = acc.vs / (acc.ws * acc.ws);
   return a.finish != 0u ? make_float4(r * p.A.x, g * p.A.y, b * p.A.z, v) : make_float4(r, g, b, v);
 }
+
+#ifndef HJ_DENOISE_NO_KERNELS   // (hj_denoise_temporal.h takes the functions above and leaves the kernels to api/denoise.hip)
 
 // Grid (ceil(W / 32), ceil(H / 8)), one thread per pixel: aov is three float4 a pixel (albedo sum, samples | normal sum, depth sum |
 // emission sum, hits).  A pixel with a lit pixel in its 5 x 5 window - the reach of the framebuffer's reconstruction filter - is
@@ -264,5 +267,7 @@ __global__ __launch_bounds__(kDnThreads) void k_dn_finish(const float4* __restri
   const float4 ci = in[t], g1 = guide[3 * (size_t)t + 1];
   out[t] = __float_as_uint(g1.w) != 0u ? make_float4(ci.x * g1.x, ci.y * g1.y, ci.z * g1.z, ci.w) : ci;
 }
+
+#endif  // HJ_DENOISE_NO_KERNELS
 
 }  // namespace hj

@@ -32,7 +32,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
            "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame",
-           "hj_denoise_frame")
+           "hj_denoise_frame", "hj_denoise_frame_temporal")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -126,6 +126,7 @@ def lib():
         L.hj_render_aovs.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_render_aovs_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_denoise_frame.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), vp]   # (host or device pointers)
+        L.hj_denoise_frame_temporal.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -812,6 +813,61 @@ class Renderer:
         self._check(lib().hj_denoise_frame(self._h, aov.shape[1], aov.shape[0], None if beauty is None else beauty.ctypes.data, aov.ctypes.data, C.byref(o),
                                            out.ctypes.data))
         return out
+
+    def denoise_frame_temporal(self, aov, camera, prev_camera, history=None, beauty=None, iterations=5, sigma_normal=0.5, sigma_depth=1.0, sigma_luminance=4.0,
+                               sigma_albedo=0.1, alpha=0.2, alpha_moments=0.2, depth_tolerance=0.1, normal_cos=0.9, max_history=64, feedback=True, device=False):
+        """hj_denoise_frame_temporal: `denoise_frame` behind SVGF's temporal accumulation -> (out, history): the (height, width, 4)
+        denoised image and the new (height, width, 12) history to pass as `history` with the next frame.  camera: the abi.Camera
+        (beauty, aov) were rendered with; prev_camera: the camera of the frame that wrote `history`.  history None: the first frame
+        (the output is `denoise_frame`'s).  Each guided pixel's world point - its depth along its camera ray - is projected into the
+        previous camera; the history's four bilinear taps there count when their depth is within `depth_tolerance` (relative) of the
+        point's distance and their normal within `normal_cos` of the pixel's; the pixel's light and luminance moments are blended
+        with what they give, the new frame's weight being max(alpha, 1 / N) for a history of N frames (N capped at `max_history`,
+        1 ... 65535).  A history of 4 frames or more gives the filter its temporal variance.  feedback: the first iteration's light
+        goes into the history (SVGF's feedback).  A moved shape is met by the two tests alone.  alpha and alpha_moments 0.2 are
+        SVGF's; depth_tolerance 0.1, normal_cos 0.9 and max_history 64 are guesses: not tuned.  Everything else as `denoise_frame`;
+        device=True: `aov`, `history` and `beauty` are contiguous float32 torch tensors on the renderer's GPU, read in place, and
+        both results are new tensors there."""
+        iterations = int(iterations)
+        sig = [float(sigma_normal), float(sigma_depth), float(sigma_luminance), float(sigma_albedo)]
+        if not 0 <= iterations <= abi.DENOISE_MAX_ITERATIONS:
+            raise ValueError(f"denoise_frame_temporal: {iterations} iterations: 0 ... {abi.DENOISE_MAX_ITERATIONS}")
+        for name, v in zip(("sigma_normal", "sigma_depth", "sigma_luminance", "sigma_albedo"), sig):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"denoise_frame_temporal: {name} {v}: finite and >= 0 is needed")
+        o = abi.DenoiseOpts(iterations, *sig, abi.DENOISE_DEVICE_ARRAYS if device else 0)
+        t = abi.TemporalOpts(camera, prev_camera, float(alpha), float(alpha_moments), float(depth_tolerance), float(normal_cos), int(max_history),
+                             abi.TEMPORAL_FEEDBACK if feedback else 0)
+        if device:
+            import torch
+            for name, x in (("aov", aov), ("beauty", beauty), ("history", history)):
+                if x is None and name != "aov":
+                    continue
+                if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == torch.float32 and x.is_contiguous()):
+                    raise ValueError(f"denoise_frame_temporal: {name} must be a contiguous float32 tensor on cuda:{self.device}")
+            if (aov.dim() != 3 or aov.shape[2] != abi.AOV_WORDS or (beauty is not None and tuple(beauty.shape) != (aov.shape[0], aov.shape[1], 4))
+                    or (history is not None and tuple(history.shape) != (aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS))):
+                raise ValueError("denoise_frame_temporal: aov (height, width, 12), beauty (height, width, 4) and history (height, width, 12) are needed")
+            h, w = int(aov.shape[0]), int(aov.shape[1])
+            out = torch.empty((h, w, 4), dtype=torch.float32, device=aov.device)
+            hist = torch.empty((h, w, abi.TEMPORAL_WORDS), dtype=torch.float32, device=aov.device)
+            torch.cuda.current_stream(aov.device).synchronize()       # (the allocations and whatever wrote the inputs)
+            self._check(lib().hj_denoise_frame_temporal(self._h, w, h, None if beauty is None else beauty.data_ptr(), aov.data_ptr(), C.byref(o), C.byref(t),
+                                                        None if history is None else history.data_ptr(), hist.data_ptr(), out.data_ptr()))
+            return out, hist
+        aov = np.ascontiguousarray(aov, np.float32)
+        if beauty is not None:
+            beauty = np.ascontiguousarray(beauty, np.float32)
+        if history is not None:
+            history = np.ascontiguousarray(history, np.float32)
+        if (aov.ndim != 3 or aov.shape[2] != abi.AOV_WORDS or (beauty is not None and beauty.shape != (aov.shape[0], aov.shape[1], 4))
+                or (history is not None and history.shape != (aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS))):
+            raise ValueError("denoise_frame_temporal: aov (height, width, 12), beauty (height, width, 4) and history (height, width, 12) are needed")
+        out = np.zeros((aov.shape[0], aov.shape[1], 4), np.float32)
+        hist = np.zeros((aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS), np.float32)
+        self._check(lib().hj_denoise_frame_temporal(self._h, aov.shape[1], aov.shape[0], None if beauty is None else beauty.ctypes.data, aov.ctypes.data, C.byref(o),
+                                                    C.byref(t), None if history is None else history.ctypes.data, hist.ctypes.data, out.ctypes.data))
+        return out, hist
 
     def trace_paths(self, rays, seeds=None, spp=1, opts=None, stats=False):
         """hj_trace_paths: the path-traced radiance along (n, 8) rays (origin, direction of any length, a uint32 seed as the bits of

@@ -1517,7 +1517,7 @@ int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint3
  *   undrained frames - except that no scene is needed: this call traces nothing.
  * The defaults of the Python wrapper and the command line (5 iterations; sigmas 0.5 normal, 1 depth, 4 luminance, 0.1 albedo) are
  *   SVGF's starting points where it has them (depth, luminance) and guesses elsewhere: they are not tuned.
- * Not here: temporal accumulation and reprojection; a multi-GPU split; tuned defaults. */
+ * Not here: a multi-GPU split; tuned defaults.  (Temporal accumulation and reprojection: hj_denoise_frame_temporal below.) */
 #define HJ_DENOISE_DEVICE_ARRAYS 1u
 #define HJ_DENOISE_MAX_ITERATIONS 8u
 typedef struct hj_denoise_opts {
@@ -1532,6 +1532,82 @@ int hj_denoise_frame(hj_context* ctx, uint32_t width, uint32_t height,
                      const float* beauty /* H x W x 4; NULL = the context's framebuffer */,
                      const float* aov    /* H x W x HJ_AOV_WORDS, as hj_render_aovs writes it */,
                      const hj_denoise_opts* opts, float* out /* H x W x 4 */);
+
+/* hj_denoise_frame_temporal (ABI 0.28): the temporal half of SVGF in front of hj_denoise_frame's filter - the last frame's
+ * accumulated light and luminance moments are reprojected into this frame through the two cameras, tested against this frame's depth
+ * and normal, and blended with the new sample; the filter then runs over the accumulated light, and a pixel whose history is
+ * HJ_TEMPORAL_VARIANCE_FRAMES long is given its temporal variance instead of the 5 x 5 spatial estimate.  No counterpart in the
+ * reference; tests/temporal_ref.py restates the contract in numpy.
+ *   beauty, aov, opts and out mean exactly what they mean for hj_denoise_frame, beauty == NULL included; HJ_DENOISE_DEVICE_ARRAYS in
+ *     opts->flags covers all five arrays.  The cameras come in the options, not from a scene: as with hj_denoise_frame, no scene is
+ *     needed and the call traces nothing.  The caller holds the history, as it holds a probe volume's values across
+ *     hj_update_probes, and swaps the two history arrays between frames.
+ *   A history record, HJ_TEMPORAL_WORDS floats per pixel: [0..2] the accumulated demodulated light I; [3] the history length N as a
+ *     float; [4] m1 and [5] m2, the moments of Y(I); [6] z; [7] the valid word (1u as bits, or 0); [8..10] n; [11] 0.  A pixel
+ *     that is not guided writes twelve zeros.
+ *   Every operation is float32 with one rounding and no contraction, except inside the camera arithmetic named below, which is the
+ *   shader's: its dot3 and cross3 are the numeric contract's (kernels/hj_num.h: fmaf inside; HJ_NUM_DOT3, HJ_NUM_CROSS3 and
+ *   HJ_NUM_NORMALIZE3 of hj_debug_num).  sq and Y are hj_denoise_frame's.
+ *       rotate(v, q): with qv = q.xyz, qw = q.w:  tw = qw * 0.0f - dot3(qv, v);  c1 = cross3(qv, v);
+ *         t = (c1 + qv * 0.0f) + v * qw per channel;  c2 = cross3(t, -qv);  the result is (c2 + t * qw) + (-qv) * tw per channel
+ *         (quaternionRotate, shader/quaternion.glsl, in camera_ray's operation order).        conj(q) = (-q.xyz, q.w).
+ *       tan(cam) = (float)tan((double)(0.5f * cam.fov) * (3.14159265358979323846 / 180.0)), computed on the host as the upload computes it.
+ *   1. PREPARE is hj_denoise_frame's, unchanged: guided or not, c, A, I_cur = I, n and z.
+ *   2. REPROJECT, per guided pixel (x, y), when history_in is not NULL, with W = (float)width, H = (float)height:
+ *     d is camera_ray's arithmetic with px = (float)x + 0.5f, py = (float)y + 0.5f and topts->camera:  u = px - 0.5f * W,
+ *       v = py - 0.5f * H;  u = (u * tan(camera)) / (0.5f * W), v = (v * tan(camera)) / (0.5f * W);
+ *       d = normalize3(rotate((u, -v, -1.0f), camera.rotation)).
+ *     P = position + z * d, one multiply and one add per channel.          v = P - prev.position.
+ *     c = rotate(v, conj(prev.rotation)).          There is no history unless c.z < 0.
+ *     k = (0.5f * W) / tan(prev).     sx = (c.x / -c.z) * k + 0.5f * W.     sy = (-c.y / -c.z) * k + 0.5f * H.
+ *     fx = sx - 0.5f, ix = floorf(fx), tx = fx - ix; the same along y.          zp = sqrtf(sq(v)).
+ *     The four taps (ix + a, iy + b), a, b = 0, 1, are taken in the order b outer, a inner, from sum = +0 and ws = +0.  A tap has the
+ *       bilinear weight w = wx * wy, wx = 1.0f - tx for a = 0 and tx for a = 1, wy likewise of ty and b.  A tap counts when it is in
+ *       the image, its valid word is not 0, fabsf(z_h - zp) <= depth_tolerance * zp, and
+ *       (n_h.x * n.x + n_h.y * n.y) + n_h.z * n.z >= normal_cos.  For a tap that counts: sum = sum + value_h * w for each of
+ *       I.r, I.g, I.b, m1, m2 and N;  ws = ws + w.
+ *     There is no history when no tap counts or ws is not above 0.  Otherwise I_prev, m1_prev, m2_prev and N_prev are sum / ws,
+ *       one division each.
+ *   3. ACCUMULATE:  without history I = I_cur, m1 = Y(I_cur), m2 = m1 * m1, N = 1.  With history
+ *       N = fminf(N_prev + 1.0f, (float)max_history);  a = fmaxf(alpha, 1.0f / N);  I = I_prev * (1.0f - a) + I_cur * a per channel;
+ *       am = fmaxf(alpha_moments, 1.0f / N);  m1 = m1_prev * (1.0f - am) + Y(I_cur) * am;  m2 = m2_prev * (1.0f - am) + (Y(I_cur) * Y(I_cur)) * am.
+ *   4. VARIANCE:  the slope gz is hj_denoise_frame's.  V is its 5 x 5 spatial estimate over the accumulated I when
+ *       N < HJ_TEMPORAL_VARIANCE_FRAMES; otherwise V = fmaxf(m2 - m1 * m1, 0.0f).
+ *   5. ITERATIONS and FINISH are hj_denoise_frame's, over (I, V).
+ *   6. HISTORY OUT:  a guided pixel writes (I, N), (m1, m2, z, valid) and (n, 0).  With HJ_TEMPORAL_FEEDBACK and iterations >= 1, I in
+ *       the history is the I' of the first iteration (step 1) - SVGF's feedback; without the flag it is the accumulated I of step 3.
+ *   So history_in == NULL gives an out that is hj_denoise_frame's bit for bit, and so does a history whose valid words are all 0 or
+ *   a prev_camera that looks the other way - in either kernel form.  Agreement bit for bit with this text is claimed for finite
+ *   inputs; non-finite values just propagate.  A moved shape is met by the depth and normal tests alone, which reset its history.
+ * The context keeps, beside hj_denoise_frame's buffers, the staging of the two histories when they are host arrays.
+ * HJ_ERR_INVALID, before the device is touched, in this order, each with its text in hj_last_error behind
+ *   "hj_denoise_frame_temporal:": hj_denoise_frame's own list up to the image size, with topts and history_out joining the null
+ *   check (opts, topts, aov, history_out, out); unknown topts->flags bits; alpha or alpha_moments outside [0, 1] or NaN;
+ *   depth_tolerance negative or non-finite; normal_cos outside [-1, 1] or NaN; max_history 0 or above 65535; a camera field that is
+ *   not finite, or a fov outside (0, 180); history_out aliasing any input or out; a misaligned device array.  A refused call
+ *   writes nothing.  Then hj_denoise_frame's gate.
+ * The defaults of the Python wrapper: alpha 0.2 and alpha_moments 0.2 are SVGF's; depth_tolerance 0.1, normal_cos 0.9 and
+ *   max_history 64 are guesses: they are not tuned.
+ * Not here: motion vectors for moved shapes; SVGF's 3 x 3 fallback search when the bilinear taps fail; history for pixels that are
+ *   not guided (lit or missed); a flag of the command line; a multi-GPU split; tuned defaults. */
+#define HJ_TEMPORAL_WORDS 12
+#define HJ_TEMPORAL_FEEDBACK 1u
+#define HJ_TEMPORAL_VARIANCE_FRAMES 4u
+typedef struct hj_temporal_opts {
+  hj_camera camera;          /* the camera (beauty, aov) were rendered with */
+  hj_camera prev_camera;     /* the camera of the frame that wrote history_in */
+  float     alpha;           /* floor of the new colour's blend weight, 0 ... 1 */
+  float     alpha_moments;   /* the same for the two luminance moments */
+  float     depth_tolerance; /* relative: |z_hist - zp| <= depth_tolerance * zp; finite, >= 0 */
+  float     normal_cos;      /* a tap needs dot(n_hist, n) >= normal_cos; -1 ... 1 */
+  uint32_t  max_history;     /* 1 ... 65535: cap of the stored history length */
+  uint32_t  flags;           /* HJ_TEMPORAL_FEEDBACK */
+} hj_temporal_opts;
+int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, const float* beauty, const float* aov,
+                              const hj_denoise_opts* opts, const hj_temporal_opts* topts,
+                              const float* history_in  /* H x W x 12, or NULL: no history */,
+                              float* history_out       /* H x W x 12, never aliases an input */,
+                              float* out               /* H x W x 4 */);
 
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host

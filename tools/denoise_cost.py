@@ -1,6 +1,8 @@
 """What hj_denoise_frame costs, and which form of its iteration to take at which step: on arrays that stay on the device (torch
 tensors), a fabricated, fully guided --size x --size frame (the denoiser needs no scene),
 
+    temporal:          hj_denoise_frame_temporal at 0 and --iterations iterations in the default form, with a full valid history under
+                       a camera shifted by a few pixels and with no history, beside hj_denoise_frame in the same rounds
     denoise_frame:     hj_denoise_frame at 0 ... --iterations iterations, once with every step in the LDS form
                        (HJ_DENOISE_LDS_STEP=128) and once with every step in the direct form (0); the cost of the iteration at step
                        1 << i is the difference between i + 1 and i iterations, the cost of prepare + variance + finish is the row
@@ -71,6 +73,17 @@ calls = {}
 for form, r in made.items():
     for it in ([a.iterations] if form == "default" else range(a.iterations + 1)):
         calls[f"denoise_frame {form} {it} iterations"] = (lambda r=r, it=it: r.denoise_frame(t_aov, t_beauty, it, device=True))
+# hj_denoise_frame_temporal beside it: a full valid history (the frame's own, written by a first call) under a camera shifted by a few
+# pixels, so that every pixel reads four history taps off its own position; feedback on (one more pass over the history's light)
+from hijiki_amd import abi  # noqa: E402
+cam, prev = abi.Camera(), abi.Camera()
+cam.position[:], cam.rotation[:], cam.fov = (0.0, 0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0), 60.0
+prev.position[:], prev.rotation[:], prev.fov = (0.01, 0.004, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0), 60.0
+t_history = made["default"].denoise_frame_temporal(t_aov, cam, cam, None, t_beauty, 0, device=True)[1]
+for it in (0, a.iterations):
+    calls[f"temporal default {it} iterations"] = (lambda it=it: made["default"].denoise_frame_temporal(t_aov, cam, prev, t_history, t_beauty, it, device=True))
+    calls[f"temporal default {it} iterations, no history"] = (lambda it=it: made["default"].denoise_frame_temporal(t_aov, cam, cam, None, t_beauty, it, device=True))
+calls[f"denoise_frame default 0 iterations"] = lambda: made["default"].denoise_frame(t_aov, t_beauty, 0, device=True)
 calls[f"filter_lightmap {a.iterations} iterations"] = lambda: yard.filter_lightmap(t_atlas.clone(), t_points, a.iterations, 0.01, 0.5, 0.5, device=True)
 calls["(the atlas's clone alone)"] = lambda: (t_atlas.clone(), torch.cuda.synchronize())
 
@@ -96,5 +109,11 @@ for it in range(a.iterations):
     lds = med[f"denoise_frame lds {it + 1} iterations"] - med[f"denoise_frame lds {it} iterations"]
     direct = med[f"denoise_frame direct {it + 1} iterations"] - med[f"denoise_frame direct {it} iterations"]
     print(f"the iteration at step {1 << it}: LDS form {lds:.3f} ms, direct form {direct:.3f} ms")
+found = made["default"].denoise_frame_temporal(t_aov, cam, prev, t_history, t_beauty, 0, device=True)[1][..., 3]
+print(f"temporal: {float((found > 1).float().mean()):.4f} of the pixels found their history under the shifted camera")
+for it in (0, a.iterations):
+    extra = med[f"temporal default {it} iterations"] - med[f"denoise_frame default {it} iterations"]
+    print(f"temporal over denoise_frame at {it} iterations: + {extra:.3f} ms with a history, "
+          f"+ {med[f'temporal default {it} iterations, no history'] - med[f'denoise_frame default {it} iterations']:.3f} ms without")
 for r in list(made.values()) + [yard]:
     r.close()
