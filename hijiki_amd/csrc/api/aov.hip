@@ -3,7 +3,7 @@
 //
 // The kernels are kernels/hj_aov.h's; that header includes the kernel headers up to hj_stages.h and edits none, and no other unit's
 // machine code depends on this one.
-//   materials:  k_mat_eval, one lane per record; host arrays staged in chunks of HJ_TRACE_CHUNK through hj_context::Aov
+//   materials:  k_mat_eval, one lane per record; chunks and staging through hj_context::Aov are chunked_query's (api/hj_internal.h)
 //   AOVs:       the ordered block list is cut into RUNS - maximal stretches of blocks with pairwise disjoint pixel rectangles (a
 //               frame's pass is one) - and into walk launches of HJ_TRACE_CHUNK sample slots, rounded to whole blocks.  A walk
 //               launch (k_aov_walk) may span several runs; behind it every run's part of it resolves in a launch of its own
@@ -19,8 +19,6 @@ using namespace hjapi;
 namespace {
 
 constexpr uint32_t kAovMaxSide = 16384u;
-
-dim3 per_lane(uint32_t n) { return dim3((n + hj::kBlockThreads - 1u) / hj::kBlockThreads); }
 
 // Where each run of `blocks` ends: run k is blocks [ends[k - 1], ends[k]).  A block's pixels are origin + [0, min(dimension,
 // image)) clipped to the image, as k_aov_resolve writes them (camera_ray compares the LOCAL pixel with the image size); a block
@@ -75,7 +73,7 @@ int aov_check(hj_context* ctx, const char* fn, const hj_image_block* blocks, siz
     if (b.dimension[0] > HJ_BLOCK_SIZE || b.dimension[1] > HJ_BLOCK_SIZE)
       return set_error(ctx, HJ_ERR_INVALID, "%s: block %zu: dimension %u x %u above %u", fn, i, b.dimension[0], b.dimension[1], (unsigned)HJ_BLOCK_SIZE);
   }
-  if ((flags & HJ_AOV_DEVICE_ARRAY) && (reinterpret_cast<uintptr_t>(aov) & 15u) != 0)
+  if ((flags & HJ_AOV_DEVICE_ARRAY) && misaligned(aov))
     return set_error(ctx, HJ_ERR_INVALID, "%s: a device array must be 16-byte aligned", fn);
   return HJ_OK;
 }
@@ -112,9 +110,7 @@ int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, si
   for (size_t c0 = 0; c0 < num_blocks && e == hipSuccess; c0 += per_launch) {
     const size_t c1 = std::min(num_blocks, c0 + per_launch);
     const uint32_t nb = (uint32_t)(c1 - c0), n = nb * hj::kSlotsPerBlock;
-    // sample slots per workgroup: hj_trace_rays' rule (HJ_TRACE_WG_RAYS, fewer when CUs would be left without a workgroup)
-    const uint32_t per_cu = ((n + (uint32_t)ctx->num_cus - 1u) / (uint32_t)ctx->num_cus + 63u) / 64u * 64u;
-    const uint32_t wg_rays = std::min<uint32_t>((uint32_t)ctx->tuning.trace_wg_rays, std::max<uint32_t>(per_cu, (uint32_t)hj::kBlockThreads));
+    const uint32_t wg_rays = walk_wg_rays(ctx, n);                   // sample slots per workgroup: hj_trace_rays' rule
     const dim3 grid((n + wg_rays - 1u) / wg_rays);
     if (sc.has_pairs != 0) hipLaunchKernelGGL(hj::k_aov_walk<true>, grid, blk, 0, s, sc, d_blocks + c0, nb, wg_rays, d_hits);
     else hipLaunchKernelGGL(hj::k_aov_walk<false>, grid, blk, 0, s, sc, d_blocks + c0, nb, wg_rays, d_hits);
@@ -145,39 +141,19 @@ int hj_eval_materials(hj_context* ctx, const float* hits, const float* surface, 
   const bool on_device = (flags & HJ_MATERIALS_DEVICE_ARRAYS) != 0;
   if (n != 0) {
     if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_eval_materials: %zu records, at most 2^31 - 1 a call", n);
-    if (on_device && ((reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surface) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
+    if (on_device && misaligned(hits, surface, out))
       return set_error(ctx, HJ_ERR_INVALID, "hj_eval_materials: device arrays must be 16-byte aligned");
   }
   HJ_TRY(query_gate(ctx, __func__));
   if (n == 0) return HJ_OK;
-  HJ_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t chunk = (size_t)ctx->tuning.trace_chunk, most = std::min(n, chunk), f4 = sizeof(float4);
   hj_context::Aov& q = ctx->aov;
-  float4 *d_hits = nullptr, *d_surface = nullptr, *d_out = nullptr;
-  if (!on_device) {
-    HJ_TRY(dev_alloc(ctx, q.in_hits, most * f4));
-    HJ_TRY(dev_alloc(ctx, q.in_surface, most * 4 * f4));
-    HJ_TRY(dev_alloc(ctx, q.out, most * 2 * f4));
-    d_hits = static_cast<float4*>(q.in_hits.p); d_surface = static_cast<float4*>(q.in_surface.p); d_out = static_cast<float4*>(q.out.p);
-  }
-  hipError_t e = hipSuccess;
-  for (size_t at = 0; at < n && e == hipSuccess; at += chunk) {
-    const uint32_t cnt = (uint32_t)std::min(chunk, n - at);
-    if (on_device) {
-      d_hits = reinterpret_cast<float4*>(const_cast<float*>(hits)) + at;
-      d_surface = reinterpret_cast<float4*>(const_cast<float*>(surface)) + 4 * at;
-      d_out = reinterpret_cast<float4*>(out) + 2 * at;
-    } else {
-      e = hipMemcpyAsync(d_hits, hits + 4 * at, cnt * f4, hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_surface, surface + 16 * at, cnt * 4 * f4, hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) break;
-    }
-    hipLaunchKernelGGL(hj::k_mat_eval, per_lane(cnt), dim3(hj::kBlockThreads), 0, ctx->stream, ctx->scene, static_cast<const float4*>(d_hits),
-                       static_cast<const float4*>(d_surface), cnt, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out + 8 * at, d_out, cnt * 2 * f4, hipMemcpyDeviceToHost, ctx->stream);
-  }
-  return drain(ctx, __func__, e);
+  const size_t f4 = sizeof(float4);
+  const QueryArray arrays[] = {{hits, &q.in_hits, f4, false}, {surface, &q.in_surface, 4 * f4, false}, {out, &q.out, 2 * f4, true}};
+  return chunked_query(ctx, __func__, n, on_device, arrays, [&](void* const d[], uint32_t cnt, size_t) {
+    hipLaunchKernelGGL(hj::k_mat_eval, per_lane(cnt), dim3(hj::kBlockThreads), 0, ctx->stream, ctx->scene, static_cast<const float4*>(d[0]),
+                       static_cast<const float4*>(d[1]), cnt, static_cast<float4*>(d[2]));
+    return hipGetLastError();
+  });
 }
 
 int hj_render_aovs(hj_context* ctx, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags, float* aov) {

@@ -120,7 +120,7 @@ int hj_denoise_frame(hj_context* ctx, uint32_t width, uint32_t height, const flo
   if (!opts || !aov || !out) return set_error(ctx, HJ_ERR_INVALID, "hj_denoise_frame: null %s", !opts ? "opts" : !aov ? "aov" : "out");
   HJ_TRY(denoise_check(ctx, __func__, width, height, opts));
   const bool on_device = (opts->flags & HJ_DENOISE_DEVICE_ARRAYS) != 0;
-  if (on_device && ((reinterpret_cast<uintptr_t>(beauty) | reinterpret_cast<uintptr_t>(aov) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
+  if (on_device && misaligned(beauty, aov, out))
     return set_error(ctx, HJ_ERR_INVALID, "hj_denoise_frame: device arrays must be 16-byte aligned");
   DenoiseFrame f;
   HJ_TRY(denoise_begin(ctx, __func__, width, height, beauty, aov, out, on_device, f));

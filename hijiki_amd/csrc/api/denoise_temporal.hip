@@ -59,8 +59,7 @@ int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, 
       overlap(history_out, 3 * f4 * n, out, f4 * n))
     return set_error(ctx, HJ_ERR_INVALID, "%s: history_out aliases an input or out", kFn);
   const bool on_device = (opts->flags & HJ_DENOISE_DEVICE_ARRAYS) != 0;
-  if (on_device && ((reinterpret_cast<uintptr_t>(beauty) | reinterpret_cast<uintptr_t>(aov) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(history_in) |
-                     reinterpret_cast<uintptr_t>(history_out)) & 15u) != 0)
+  if (on_device && misaligned(beauty, aov, out, history_in, history_out))
     return set_error(ctx, HJ_ERR_INVALID, "%s: device arrays must be 16-byte aligned", kFn);
   DenoiseFrame f;
   HJ_TRY(denoise_begin(ctx, kFn, width, height, beauty, aov, out, on_device, f));

@@ -123,7 +123,7 @@ int hj_trace_irradiance_adaptive(hj_context* ctx, const float* points, size_t n,
   HJ_TRY(adaptive_opts_check(ctx, __func__, aopts, q.a));
   if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance_adaptive: %zu points, at most 2^31 - 1 a call", n);
   if (n != 0 && on_device &&
-      ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(moments)) & 15u) != 0)
+      misaligned(points, out, moments))
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance_adaptive: device arrays must be 16-byte aligned");
   HJ_TRY(query_render_opts(ctx, __func__, opts, q.o));
   if (!sphere && !on_device) HJ_TRY(gather_normals_check(ctx, __func__, points, n));   // (device arrays: the caller's contract)

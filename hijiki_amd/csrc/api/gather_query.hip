@@ -196,7 +196,7 @@ static void gather_chunk(const FixedSppQuery& fq, hj::BatchState& st, const hj::
   const uint32_t spp = fq.spp;
   gather_query_pass(st, sc, G, d_pts, cnt, spp, fq.o, fq.flags, s);
   const dim3 blk(hj::kBlockThreads);
-  const dim3 rgrid((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads);
+  const dim3 rgrid = per_lane(cnt);
   if (sh9)
     hipLaunchKernelGGL(hj::k_gq_resolve<true>, rgrid, blk, 0, s, static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd),
                        d_pts, spp, cnt, d_out);
@@ -218,7 +218,7 @@ int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t
   if (sh9 && !sphere) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: HJ_GATHER_SH9 only together with HJ_GATHER_SPHERE");
   if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: spp %u outside [1, 65536]", spp);
   if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: %zu points, at most 2^31 - 1 a call", n);
-  if (n != 0 && on_device && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0)
+  if (n != 0 && on_device && misaligned(points, out))
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: device arrays must be 16-byte aligned");
   FixedSppQuery q{__func__, points, n, spp, sh9 ? 9u : 2u, on_device, out, stats, {}, gather_chunk, flags};
   HJ_TRY(query_render_opts(ctx, __func__, opts, q.o));

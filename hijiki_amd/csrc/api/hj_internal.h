@@ -25,7 +25,7 @@
 //   api/path_query.hip    hj_trace_paths: path-traced radiance along caller-given rays (includes the kernel headers up to hj_stages.h and
 //                         defines its own kernels beside the path kernels: the round loop of api/query_round_loop.h with a top-up from a
 //                         ray array); its path state is hj_context::PathQuery, a PathState.  Also the host code the queries share:
-//                         path_query_plan / path_query_pass, query_render_opts, query_gate, QueryStats, fixed_spp_query (below)
+//                         path_query_plan / path_query_pass, query_render_opts, query_gate, per_lane, QueryStats, fixed_spp_query (below)
 //   api/query_round.h     the tail threshold, register budget and group deal of the queries' path kernels
 //   api/query_round_loop.h the text of their round loop: no include guard, included inside the bodies of k_pq_paths and k_gq_paths
 //   api/path_adaptive.hip hj_trace_paths_adaptive: rounds of that path kernel (path_query_pass) over the rays still active, with the
@@ -750,6 +750,63 @@ int upload(DevBufs& bufs, const T* src, size_t count, const T** out) {
   if (count) HJ_HIP(bufs.ctx, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
   *out = p;
   return HJ_OK;
+}
+
+// Device arrays must be 16-byte aligned (the kernels read and write them as float4 / uint4): true when a pointer is not; null
+// pointers - an optional array the caller left out - do not count.
+template <class... P>
+bool misaligned(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ... | uintptr_t(0)) & 15u) != 0; }
+
+// The grid of a kernel with one lane per element and workgroups of kBlockThreads (api/path_query.hip)
+dim3 per_lane(uint32_t n);
+// Rays (or sample slots) per workgroup of a persistent walk over n of them: k_rq_walk and k_aov_walk (api/ray_query.hip)
+uint32_t walk_wg_rays(const hj_context* ctx, uint32_t n);
+
+// A flat per-element query behind its entry point's argument checks and its gate (n > 0): hj_trace_rays, hj_trace_rays_all,
+// hj_points_inside, hj_closest_points, hj_eval_materials.  One lane per element, in launches of HJ_TRACE_CHUNK elements, which bounds
+// the staging buffers of host arrays; device arrays take the same loop and the same launches, element `at` of the caller's own
+// pointer used in place, and nothing is allocated.  chunked_query owns hipSetDevice, the staging allocations - every one before
+// anything is enqueued, in the table's order -, the loop, the copies up and down and the ONE hipStreamSynchronize (drain): a failed
+// upload or launch ends the loop and the call still drains.  `launch` enqueues the kernels of one chunk on ctx->stream - d[i]: where
+// array i's cnt elements are on the device, nullptr for an absent one; k: the launch's index - and returns hipGetLastError() or the
+// first error of what it enqueued behind the kernels.
+struct QueryArray {
+  const void* user;                      // the caller's array; nullptr: absent - no buffer, no copy
+  DevBuf* stage;                         // the context's staging buffer for it (host arrays)
+  size_t bytes;                          // per element; 0: absent
+  bool out;                              // copied down behind the launch; otherwise up in front of it
+};
+template <size_t N, class L>
+int chunked_query(hj_context* ctx, const char* fn, size_t n, bool on_device, const QueryArray (&arrays)[N], L&& launch) {
+  HJ_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t chunk = (size_t)ctx->tuning.trace_chunk;
+  char* user[N];
+  void* d[N] = {};
+  for (size_t i = 0; i < N; i++) {
+    const QueryArray& a = arrays[i];
+    user[i] = a.bytes ? static_cast<char*>(const_cast<void*>(a.user)) : nullptr;
+    if (on_device || !user[i]) continue;
+    HJ_TRY(dev_alloc(ctx, *a.stage, std::min(n, chunk) * a.bytes));
+    d[i] = a.stage->p;
+  }
+  hipError_t e = hipSuccess;
+  size_t k = 0;
+  for (size_t at = 0; at < n && e == hipSuccess; at += chunk, k++) {
+    const uint32_t cnt = (uint32_t)std::min(chunk, n - at);
+    for (size_t i = 0; i < N && e == hipSuccess; i++) {
+      if (!user[i]) continue;
+      const QueryArray& a = arrays[i];
+      if (on_device) d[i] = user[i] + at * a.bytes;
+      else if (!a.out) e = hipMemcpyAsync(d[i], user[i] + at * a.bytes, cnt * a.bytes, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e != hipSuccess) break;
+    e = launch(d, cnt, k);
+    for (size_t i = 0; i < N && e == hipSuccess; i++) {
+      const QueryArray& a = arrays[i];
+      if (!on_device && user[i] && a.out) e = hipMemcpyAsync(user[i] + at * a.bytes, d[i], cnt * a.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+  }
+  return drain(ctx, fn, e);
 }
 
 }  // namespace hjapi

@@ -94,9 +94,9 @@ int bake(hj_context* ctx, const char* fn, const hj_lightmap_desc* desc, uint32_t
   if (adaptive) HJ_TRY(adaptive_opts_check(ctx, fn, aopts, ad));
   else if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "%s: spp %u outside [1, 65536]", fn, spp);
   if (gutter > HJ_LIGHTMAP_MAX_GUTTER) return set_error(ctx, HJ_ERR_INVALID, "%s: gutter %u above %u passes", fn, gutter, HJ_LIGHTMAP_MAX_GUTTER);
-  if (on_device && (reinterpret_cast<uintptr_t>(image) & 15u) != 0)
+  if (on_device && misaligned(image))
     return set_error(ctx, HJ_ERR_INVALID, "%s: a device image must be 16-byte aligned", fn);
-  if (on_device && adaptive && (reinterpret_cast<uintptr_t>(sample_map) & 15u) != 0)
+  if (on_device && adaptive && misaligned(sample_map))
     return set_error(ctx, HJ_ERR_INVALID, "%s: a device sample map must be 16-byte aligned", fn);
   if (filter) HJ_TRY(lightmap_filter_check(ctx, fn, filter));
   const uint32_t iterations = filter ? filter->iterations : 0u;
@@ -188,7 +188,7 @@ int hj_lightmap_texels(hj_context* ctx, const hj_lightmap_desc* desc, float* poi
   if (!desc || !out_count) return set_error(ctx, HJ_ERR_INVALID, "hj_lightmap_texels: null %s", !desc ? "desc" : "out_count");
   HJ_TRY(check_desc(ctx, __func__, desc));
   const bool on_device = (desc->flags & HJ_LIGHTMAP_DEVICE_ARRAYS) != 0;
-  if (on_device && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(owner)) & 15u) != 0)
+  if (on_device && misaligned(points, owner))
     return set_error(ctx, HJ_ERR_INVALID, "hj_lightmap_texels: device arrays must be 16-byte aligned");
   HJ_TRY(query_gate(ctx, __func__));
   hj::LmArgs a{};

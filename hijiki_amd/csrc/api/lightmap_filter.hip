@@ -70,7 +70,7 @@ int hj_filter_lightmap(hj_context* ctx, uint32_t width, uint32_t height, const f
   const size_t n = (size_t)width * height;
   if (count > n) return set_error(ctx, HJ_ERR_INVALID, "hj_filter_lightmap: %zu points for %zu texels", count, n);
   const bool on_device = (filter->flags & HJ_LIGHTMAP_DEVICE_ARRAYS) != 0;
-  if (on_device && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(image)) & 15u) != 0)
+  if (on_device && misaligned(points, image))
     return set_error(ctx, HJ_ERR_INVALID, "hj_filter_lightmap: device arrays must be 16-byte aligned");
   if (!on_device) {                            // (device arrays: the caller's contract; the kernels skip what names no texel)
     for (size_t i = 0; i < count; i++) {

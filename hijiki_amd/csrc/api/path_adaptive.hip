@@ -283,7 +283,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
   HJ_TRY(adaptive_opts_check(ctx, __func__, aopts, q.a));
   if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: %zu rays, at most 2^31 - 1 a call", n);
   if (n != 0 && on_device &&
-      ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(moments)) & 15u) != 0)
+      misaligned(rays, samples, moments))
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths_adaptive: device arrays must be 16-byte aligned");
   HJ_TRY(query_render_opts(ctx, __func__, opts, q.o));
   HJ_TRY(query_gate(ctx, __func__));

@@ -9,8 +9,8 @@
 //   k_pq_resolve            one thread per ray: the float32 sum of its spp samples in ascending order, first-hit normal and t
 // The one-wave tail of the path kernel (HJ_TAIL1 there, kQueryTail here) is KEPT: a query's last long paths are as few as a batch's.
 // Host code the queries share lives here too (namespace hjapi, declared in hj_internal.h): path_query_plan and path_query_pass, the
-// render-opts check and the context gate of the entry points, the statistics read-back (QueryStats), and fixed_spp_query, the
-// driver of hj_trace_paths and hj_trace_irradiance.
+// render-opts check and the context gate of the entry points, per_lane, the statistics read-back (QueryStats), and fixed_spp_query,
+// the driver of hj_trace_paths and hj_trace_irradiance.
 #include "hj_internal.h"
 #include <type_traits>
 #include "../kernels/hj_stages.h"
@@ -134,6 +134,8 @@ void path_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, 
 
 // ---- what the query entry points share (declared in hj_internal.h; host code only) ----
 
+dim3 per_lane(uint32_t n) { return dim3((n + hj::kBlockThreads - 1u) / hj::kBlockThreads); }
+
 // opts (NULL: the defaults) into o, and the refusals every path-type query has for them
 int query_render_opts(hj_context* ctx, const char* fn, const hj_render_opts* opts, hj_render_opts& o) {
   if (opts) o = *opts;
@@ -254,7 +256,7 @@ int fixed_spp_query(hj_context* ctx, const FixedSppQuery& q) {
 static void paths_chunk(const FixedSppQuery& q, hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_rays, uint32_t cnt,
                         float4* d_out, hipStream_t s) {
   path_query_pass(st, sc, G, d_rays, cnt, q.spp, q.o, s);
-  hipLaunchKernelGGL(hj::k_pq_resolve, dim3((cnt + hj::kBlockThreads - 1u) / hj::kBlockThreads), dim3(hj::kBlockThreads), 0, s,
+  hipLaunchKernelGGL(hj::k_pq_resolve, per_lane(cnt), dim3(hj::kBlockThreads), 0, s,
                      static_cast<const float4*>(st.smp_rgb), static_cast<const float4*>(st.smp_nd), q.spp, cnt, d_out);
 }
 
@@ -268,7 +270,7 @@ int hj_trace_paths(hj_context* ctx, const float* rays, size_t n, uint32_t spp, c
   const bool on_device = (flags & HJ_PATHS_DEVICE_ARRAYS) != 0;
   if (spp == 0 || spp > 65536u) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths: spp %u outside [1, 65536]", spp);
   if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths: %zu rays, at most 2^31 - 1 a call", n);
-  if (n != 0 && on_device && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(samples)) & 15u) != 0)
+  if (n != 0 && on_device && misaligned(rays, samples))
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_paths: device arrays must be 16-byte aligned");
   FixedSppQuery q{__func__, rays, n, spp, 2, on_device, samples, stats, {}, paths_chunk, flags};
   HJ_TRY(query_render_opts(ctx, __func__, opts, q.o));

@@ -23,11 +23,6 @@ namespace {
 
 constexpr uint32_t kPlaceWords = HJ_PROBE_PLACE_WORDS;
 
-bool misaligned(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d) |
-           reinterpret_cast<uintptr_t>(e)) & 15u) != 0;
-}
-
 dim3 per_item(uint32_t n) { return dim3((n + hj::kPpThreads - 1u) / hj::kPpThreads); }
 
 // The window's part of the placement on the device: the caller's own (device arrays) or a staged copy, enqueued -> d_place

@@ -32,8 +32,6 @@ int probe_update_check(hj_context* ctx, const char* fn, const hj_probe_update* u
 
 namespace {
 
-bool misaligned(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15u) != 0; }
-
 dim3 per_item(uint32_t n) { return dim3((n + hj::kPuThreads - 1u) / hj::kPuThreads); }
 
 }  // namespace

@@ -43,10 +43,6 @@ int check_descs(hj_context* ctx, const char* fn, Call call, const hj_probe_desc*
   return HJ_OK;
 }
 
-bool misaligned(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15u) != 0;
-}
-
 dim3 per_item(uint32_t n) { return dim3((n + hj::kPvvThreads - 1u) / hj::kPvvThreads); }
 
 // whole probes of a slab: at most kPvvSlabRays rays (res^2 s <= 16384: at least 32 probes)

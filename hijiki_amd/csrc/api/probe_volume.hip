@@ -71,10 +71,6 @@ int check_desc(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGr
   return HJ_OK;
 }
 
-bool misaligned(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15u) != 0;
-}
-
 dim3 per_probe(uint32_t n) { return dim3((n + hj::kPvThreads - 1u) / hj::kPvThreads); }
 
 // the gather points of the probes first ... first + n - 1 (n > 0) under `seed`, on the context's stream

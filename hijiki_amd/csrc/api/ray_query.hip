@@ -91,19 +91,26 @@ __global__ __launch_bounds__(kBlockThreads) void k_rq_surface(DeviceScene sc, co
 
 }  // namespace hj
 
+namespace hjapi {
+
+// rays per workgroup: HJ_TRACE_WG_RAYS, fewer when the launch would otherwise leave CUs without a workgroup (never below one
+// ray per thread)
+uint32_t walk_wg_rays(const hj_context* ctx, uint32_t n) {
+  const uint32_t per_cu = ((n + (uint32_t)ctx->num_cus - 1u) / (uint32_t)ctx->num_cus + 63u) / 64u * 64u;
+  return std::min<uint32_t>((uint32_t)ctx->tuning.trace_wg_rays, std::max<uint32_t>(per_cu, (uint32_t)hj::kBlockThreads));
+}
+
+}  // namespace hjapi
+
 namespace {
 
 // one launch: rays [0, n) at `rays` -> `hits` (and `surface` unless null), all on the device
 void launch_query(hj_context* ctx, const float4* rays, uint32_t n, bool any, float4* hits, float4* surface) {
   const hj::DeviceScene& sc = ctx->scene;
-  const Tuning& tn = ctx->tuning;
   hipStream_t s = ctx->stream;
   const dim3 blk(hj::kBlockThreads);
-  if (tn.trace_persistent != 0) {
-    // rays per workgroup: HJ_TRACE_WG_RAYS, fewer when the launch would otherwise leave CUs without a workgroup (never below one
-    // ray per thread)
-    const uint32_t per_cu = ((n + (uint32_t)ctx->num_cus - 1u) / (uint32_t)ctx->num_cus + 63u) / 64u * 64u;
-    const uint32_t wg_rays = std::min<uint32_t>((uint32_t)tn.trace_wg_rays, std::max<uint32_t>(per_cu, (uint32_t)hj::kBlockThreads));
+  if (ctx->tuning.trace_persistent != 0) {
+    const uint32_t wg_rays = walk_wg_rays(ctx, n);
     const dim3 grid((n + wg_rays - 1u) / wg_rays);
     const bool pairs = sc.has_pairs != 0;
     if (any && pairs) hipLaunchKernelGGL((hj::k_rq_walk<true, true>), grid, blk, 0, s, sc, rays, n, wg_rays, hits);
@@ -111,14 +118,10 @@ void launch_query(hj_context* ctx, const float4* rays, uint32_t n, bool any, flo
     else if (pairs) hipLaunchKernelGGL((hj::k_rq_walk<false, true>), grid, blk, 0, s, sc, rays, n, wg_rays, hits);
     else hipLaunchKernelGGL((hj::k_rq_walk<false, false>), grid, blk, 0, s, sc, rays, n, wg_rays, hits);
   } else {
-    const dim3 grid((n + hj::kBlockThreads - 1u) / hj::kBlockThreads);
-    if (any) hipLaunchKernelGGL(hj::k_rq_plain<true>, grid, blk, 0, s, sc, rays, n, hits);
-    else hipLaunchKernelGGL(hj::k_rq_plain<false>, grid, blk, 0, s, sc, rays, n, hits);
+    if (any) hipLaunchKernelGGL(hj::k_rq_plain<true>, per_lane(n), blk, 0, s, sc, rays, n, hits);
+    else hipLaunchKernelGGL(hj::k_rq_plain<false>, per_lane(n), blk, 0, s, sc, rays, n, hits);
   }
-  if (surface) {
-    const dim3 grid((n + hj::kBlockThreads - 1u) / hj::kBlockThreads);
-    hipLaunchKernelGGL(hj::k_rq_surface, grid, blk, 0, s, sc, rays, static_cast<const float4*>(hits), n, surface);
-  }
+  if (surface) hipLaunchKernelGGL(hj::k_rq_surface, per_lane(n), blk, 0, s, sc, rays, static_cast<const float4*>(hits), n, surface);
 }
 
 }  // namespace
@@ -135,44 +138,18 @@ int hj_trace_rays(hj_context* ctx, const float* rays, size_t n, uint32_t flags, 
     if (!rays || !hits) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: null %s", !rays ? "rays" : "hits");
     if (n > 0x7FFFFFFFu) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: %zu rays, at most 2^31 - 1 a call", n);
     if (surface && any) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: an any-hit record is no closest hit: no surface with HJ_TRACE_ANY_HIT");
-    if (on_device && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surface)) & 15u) != 0)
+    if (on_device && misaligned(rays, hits, surface))
       return set_error(ctx, HJ_ERR_INVALID, "hj_trace_rays: device arrays must be 16-byte aligned");
   }
   HJ_TRY(query_gate(ctx, __func__));
   if (n == 0) return HJ_OK;
-  HJ_HIP(ctx, hipSetDevice(ctx->device));
-  // rays of one launch (HJ_TRACE_CHUNK): bounds the staging buffers of host arrays; device arrays take the same loop
-  const size_t chunk = (size_t)ctx->tuning.trace_chunk;
+  hj_context::RayQuery& q = ctx->query;
   const size_t f4 = sizeof(float4);
-  float4 *d_rays = nullptr, *d_hits = nullptr, *d_surface = nullptr;
-  if (!on_device) {
-    hj_context::RayQuery& q = ctx->query;
-    const size_t most = std::min(n, chunk);
-    HJ_TRY(dev_alloc(ctx, q.rays, most * 2 * f4));
-    HJ_TRY(dev_alloc(ctx, q.hits, most * f4));
-    if (surface) HJ_TRY(dev_alloc(ctx, q.surface, most * 4 * f4));
-    d_rays = static_cast<float4*>(q.rays.p); d_hits = static_cast<float4*>(q.hits.p);
-    d_surface = surface ? static_cast<float4*>(q.surface.p) : nullptr;
-  }
-  hipError_t e = hipSuccess;
-  for (size_t at = 0; at < n && e == hipSuccess; at += chunk) {
-    const uint32_t cnt = (uint32_t)std::min(chunk, n - at);
-    if (on_device) {
-      d_rays = reinterpret_cast<float4*>(const_cast<float*>(rays)) + 2 * at;
-      d_hits = reinterpret_cast<float4*>(hits) + at;
-      d_surface = surface ? reinterpret_cast<float4*>(surface) + 4 * at : nullptr;
-    } else {
-      e = hipMemcpyAsync(d_rays, rays + 8 * at, cnt * 2 * f4, hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) break;
-    }
-    launch_query(ctx, d_rays, cnt, any, d_hits, d_surface);
-    e = hipGetLastError();
-    if (!on_device) {
-      if (e == hipSuccess) e = hipMemcpyAsync(hits + 4 * at, d_hits, cnt * f4, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess && surface) e = hipMemcpyAsync(surface + 16 * at, d_surface, cnt * 4 * f4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-  }
-  return drain(ctx, __func__, e);
+  const QueryArray arrays[] = {{rays, &q.rays, 2 * f4, false}, {hits, &q.hits, f4, true}, {surface, &q.surface, 4 * f4, true}};
+  return chunked_query(ctx, __func__, n, on_device, arrays, [&](void* const d[], uint32_t cnt, size_t) {
+    launch_query(ctx, static_cast<const float4*>(d[0]), cnt, any, static_cast<float4*>(d[1]), static_cast<float4*>(d[2]));
+    return hipGetLastError();
+  });
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 """hj_closest_points and hj_distance_field on the GPU against closest_ref - brute force over all shapes - bit for bit on all eight
 words: a single sphere under a hand-written one-record tree, and four scenes through the three routes into an upload, five point counts, the radius cases, moved shapes from host and device
-arrays, device tensors against host arrays, the statistics, the field."""
+arrays, device tensors against host arrays, the statistics, launches cut by HJ_TRACE_CHUNK, the field."""
 import ctypes as C
 import functools
 
@@ -295,6 +295,28 @@ def test_device_tensors_in_place_and_statistics(rq):
     out = torch.full((len(pts), 8), 7.0, device=t.device)
     rc = device.lib().hj_closest_points(rq._h, t.data_ptr(), len(pts), abi.CLOSEST_DEVICE_ARRAYS, out.data_ptr(), C.cast(word.data_ptr(), C.POINTER(C.c_uint64)))
     assert rc == abi.HJ_ERR_INVALID and (out == 7.0).all().item()
+
+
+def test_chunks_give_the_same_bits_and_the_same_statistics(rq, monkeypatch):
+    """HJ_TRACE_CHUNK=1000 cuts the 4097 points into five launches, the last of 97: the records on bits, and the statistics - counted
+    per point in its own lane, summed per workgroup and read back per launch - equal to the one launch's, from host arrays and from
+    device tensors."""
+    import torch
+    cs, sh, pts, want = case("mesh")
+    assert len(pts) >= 2001 and len(pts) % 1000 and len(pts) % 256
+    rq.upload_scene(cs)
+    whole, st_whole = rq.closest_points(pts, stats=True)
+    assert st_whole["nodes_visited"] > 0 and st_whole["shapes_tested"] > 0
+    monkeypatch.setenv("HJ_TRACE_CHUNK", "1000")
+    with device.Renderer(0) as r:
+        r.upload_scene(cs)
+        got, st = r.closest_points(pts, stats=True)
+        assert_records(got, whole, "host arrays in chunks of 1000")
+        assert st == st_whole
+        t = torch.from_numpy(np.array(pts)).to(f"cuda:{r.device}")
+        got, st = r.closest_points(t, stats=True, device=True)
+        assert_records(got.cpu().numpy(), whole, "device tensors in chunks of 1000")
+        assert st == st_whole
 
 
 @pytest.mark.parametrize("from_device", [False, True])
