@@ -68,6 +68,10 @@ DENOISE_MAX_ITERATIONS = 8        # hj_denoise_opts: iteration i uses the step 1
 TEMPORAL_WORDS = 12               # words of a history record: I.rgb, N | m1, m2, z, valid word | n.xyz, 0
 TEMPORAL_FEEDBACK = 1             # hj_temporal_opts flag: the first iteration's light goes into the history
 TEMPORAL_VARIANCE_FRAMES = 4      # a history this long gives the variance of its temporal moments
+MOTION_WORDS = 4                  # words of a motion record (hj_render_motion): sx, sy, zp, id bits
+MOTION_NONE = 0xFFFFFFFF          # ... its word 3 for a pixel without a previous position
+MOTION_DEVICE_SHAPES = 1          # hj_render_motion flag: the previous shape arrays are device pointers
+MOTION_DEVICE_OUT = 2             # ... the motion image is a device pointer
 
 
 def probe_vis_words(res):

@@ -155,7 +155,7 @@ int drain(hj_context* ctx, const char* fn, hipError_t e) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (28u << 8) | 0u; }   // 0.28.0: hj_denoise_frame_temporal
+uint32_t hj_version(void) { return (0u << 16) | (29u << 8) | 0u; }   // 0.29.0: hj_render_motion, hj_denoise_frame_temporal_motion
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

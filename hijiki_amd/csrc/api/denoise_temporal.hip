@@ -1,9 +1,11 @@
 // hj_denoise_frame_temporal: the last frame's history reprojected into this one, in front of hj_denoise_frame's filter (DESIGN.md 4,
-// "Temporal accumulation").
+// "Temporal accumulation").  hj_denoise_frame_temporal_motion: the same host routine, reprojecting through hj_render_motion's records
+// ("Motion for the temporal denoiser").
 //
 // The kernels are kernels/hj_denoise_temporal.h's; prepare, the iterations and finish are api/denoise.hip's, through hj_internal.h:
 //   k_dn_prepare  ->  k_dt_accumulate  ->  k_dt_variance  ->  the iterations (HJ_TEMPORAL_FEEDBACK: the first one into a working image,
 //   k_dt_feedback behind it, and k_dn_finish when it was the only one)
+// k_dt_accumulate<false> is this unit's; with a motion image the routine enters api/motion.hip's launch of k_dt_accumulate<true>.
 #include "hj_internal.h"
 #include "../kernels/hj_denoise_temporal.h"
 
@@ -13,33 +15,14 @@ using namespace hjapi;
 
 namespace {
 
-constexpr const char* kFn = "hj_denoise_frame_temporal";
-
-bool camera_ok(const hj_camera& c) {
-  for (int k = 0; k < 3; k++)
-    if (!std::isfinite(c.position[k])) return false;
-  for (int k = 0; k < 4; k++)
-    if (!std::isfinite(c.rotation[k])) return false;
-  return std::isfinite(c.fov) && c.fov > 0.0f && c.fov < 180.0f;
-}
-
-// tan_half_fov as the upload computes it (api/scene_upload.hip)
-hj::DtCamera device_camera(const hj_camera& c) {
-  return hj::DtCamera{hj::v3{c.position[0], c.position[1], c.position[2]}, hj::v3{c.rotation[0], c.rotation[1], c.rotation[2]}, c.rotation[3],
-                      (float)std::tan((double)(0.5f * c.fov) * (3.14159265358979323846 / 180.0))};
-}
-
 bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
   return a && b && pa < pb + nb && pb < pa + na;
 }
 
-}  // namespace
-
-extern "C" {
-
-int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, const float* beauty, const float* aov, const hj_denoise_opts* opts,
-                              const hj_temporal_opts* topts, const float* history_in, float* history_out, float* out) {
+// Both entry points (kFn: which one, for the messages).  motion == nullptr: hj_denoise_frame_temporal.
+int temporal(hj_context* ctx, const char* kFn, uint32_t width, uint32_t height, const float* beauty, const float* aov, const hj_denoise_opts* opts,
+             const hj_temporal_opts* topts, const float* motion, const float* history_in, float* history_out, float* out) {
   if (!opts || !topts || !aov || !history_out || !out)
     return set_error(ctx, HJ_ERR_INVALID, "%s: null %s", kFn, !opts ? "opts" : !topts ? "topts" : !aov ? "aov" : !history_out ? "history_out" : "out");
   HJ_TRY(denoise_check(ctx, kFn, width, height, opts));
@@ -56,23 +39,29 @@ int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, 
   if (!camera_ok(to.prev_camera)) return set_error(ctx, HJ_ERR_INVALID, "%s: prev_camera: finite position and rotation and a fov inside (0, 180) are needed", kFn);
   const size_t n = (size_t)width * height, f4 = sizeof(float4);
   if (overlap(history_out, 3 * f4 * n, beauty, f4 * n) || overlap(history_out, 3 * f4 * n, aov, 3 * f4 * n) || overlap(history_out, 3 * f4 * n, history_in, 3 * f4 * n) ||
-      overlap(history_out, 3 * f4 * n, out, f4 * n))
+      overlap(history_out, 3 * f4 * n, out, f4 * n) || overlap(history_out, 3 * f4 * n, motion, f4 * n))
     return set_error(ctx, HJ_ERR_INVALID, "%s: history_out aliases an input or out", kFn);
   const bool on_device = (opts->flags & HJ_DENOISE_DEVICE_ARRAYS) != 0;
-  if (on_device && misaligned(beauty, aov, out, history_in, history_out))
+  if (on_device && misaligned(beauty, aov, out, history_in, history_out, motion))
     return set_error(ctx, HJ_ERR_INVALID, "%s: device arrays must be 16-byte aligned", kFn);
   DenoiseFrame f;
   HJ_TRY(denoise_begin(ctx, kFn, width, height, beauty, aov, out, on_device, f));
   hj_context::Denoise& dn = ctx->denoise;
   const float4* d_hin = reinterpret_cast<const float4*>(history_in);
+  const float4* d_motion = reinterpret_cast<const float4*>(motion);
   float4* d_hout = reinterpret_cast<float4*>(history_out);
   hipStream_t s = ctx->stream;
   hipError_t e = f.e;
   if (!on_device) {
     int rc = dev_alloc(ctx, dn.out_history, 3 * f4 * n);
     if (rc == HJ_OK && history_in) rc = dev_alloc(ctx, dn.in_history, 3 * f4 * n);
+    if (rc == HJ_OK && motion) rc = dev_alloc(ctx, dn.in_motion, f4 * n);
     if (rc != HJ_OK) return drain(ctx, kFn, rc);
     d_hout = static_cast<float4*>(dn.out_history.p);
+    if (motion) {
+      if (e == hipSuccess) e = hipMemcpyAsync(dn.in_motion.p, motion, f4 * n, hipMemcpyHostToDevice, s);
+      d_motion = static_cast<const float4*>(dn.in_motion.p);
+    }
     if (history_in) {
       if (e == hipSuccess) e = hipMemcpyAsync(dn.in_history.p, history_in, 3 * f4 * n, hipMemcpyHostToDevice, s);
       d_hin = static_cast<const float4*>(dn.in_history.p);
@@ -83,9 +72,10 @@ int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, 
     const dim3 tile_grid((W + hj::kDnTX - 1u) / hj::kDnTX, (H + hj::kDnTY - 1u) / hj::kDnTY), blk(hj::kDnTX * hj::kDnTY);
     const dim3 lane_grid(((uint32_t)n + hj::kDnThreads - 1u) / hj::kDnThreads);
     denoise_prepare_enqueue(ctx, f);
-    const hj::DtArgs a{f.guide, f.work[1], d_hin, d_hout, W, H, device_camera(to.camera), device_camera(to.prev_camera), to.alpha, to.alpha_moments,
-                       to.depth_tolerance, to.normal_cos, (float)to.max_history};
-    hipLaunchKernelGGL(hj::k_dt_accumulate, tile_grid, blk, 0, s, a);
+    const hj::DtArgs a{f.guide, f.work[1], d_hin, d_motion, d_hout, W, H, hj::dt_host_camera(to.camera), hj::dt_host_camera(to.prev_camera), to.alpha,
+                       to.alpha_moments, to.depth_tolerance, to.normal_cos, (float)to.max_history};
+    if (motion) dt_accumulate_motion_enqueue(ctx, a);
+    else hipLaunchKernelGGL(hj::k_dt_accumulate<false>, tile_grid, blk, 0, s, a);
     hipLaunchKernelGGL(hj::k_dt_variance, tile_grid, blk, 0, s, f.guide, static_cast<const float4*>(f.work[1]), f.work[0], static_cast<const float4*>(d_hout), W, H);
     uint32_t cur = 0;
     if ((to.flags & HJ_TEMPORAL_FEEDBACK) != 0 && opts->iterations >= 1u) {
@@ -102,6 +92,20 @@ int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, 
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, f.out, f4 * n, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(history_out, d_hout, 3 * f4 * n, hipMemcpyDeviceToHost, s);
   return drain(ctx, kFn, e);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, const float* beauty, const float* aov, const hj_denoise_opts* opts,
+                              const hj_temporal_opts* topts, const float* history_in, float* history_out, float* out) {
+  return temporal(ctx, __func__, width, height, beauty, aov, opts, topts, nullptr, history_in, history_out, out);
+}
+
+int hj_denoise_frame_temporal_motion(hj_context* ctx, uint32_t width, uint32_t height, const float* beauty, const float* aov, const hj_denoise_opts* opts,
+                                     const hj_temporal_opts* topts, const float* motion, const float* history_in, float* history_out, float* out) {
+  return temporal(ctx, __func__, width, height, beauty, aov, opts, topts, motion, history_in, history_out, out);
 }
 
 }  // extern "C"

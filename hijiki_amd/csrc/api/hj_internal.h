@@ -87,7 +87,13 @@
 //   api/denoise_temporal.hip  hj_denoise_frame_temporal: reprojected history in front of that filter - k_dt_accumulate (reproject, blend,
 //                         history record), k_dt_variance (spatial or temporal variance), k_dt_feedback (the first iteration's light
 //                         into the history) between api/denoise.hip's stages (includes kernels/hj_denoise_temporal.h; beside it the
-//                         functions of hj_denoise.h, without its kernels, and hj_num.h alone)
+//                         functions of hj_denoise.h, without its kernels, and hj_num.h alone); hj_denoise_frame_temporal_motion: the same
+//                         host routine with k_dt_accumulate<true>, which api/motion.hip instantiates (dt_accumulate_motion_enqueue below)
+//   api/motion.hip        hj_render_motion: per pixel where the surface point its centre ray sees was in the previous frame - k_mv_walk,
+//                         the persistent walk with a fetch that builds the centre ray from the pixel, its raw hit into the pixel's
+//                         record; k_mv_resolve, the previous point from the previous shape arrays projected into the previous camera,
+//                         in place (includes kernels/hj_motion.h, which includes the kernel headers up to hj_stages.h and the functions
+//                         of hj_denoise_temporal.h and edits none); and the one instantiation of k_dt_accumulate<true>
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -484,7 +490,12 @@ struct hj_context {
   // two working images (16 bytes a pixel each); the staging of host arrays - beauty, AOV image, result (16, 48 and 16 bytes a
   // pixel).  Grown on demand, reused by every call, freed with the context.  The framebuffer is read, never written.
   // hj_denoise_frame_temporal (api/denoise_temporal.hip) adds the staging of the two histories (48 bytes a pixel each).
-  struct Denoise { hjapi::DevBuf guide, image[2], in_beauty, in_aov, out, in_history, out_history; } denoise;
+  // hj_denoise_frame_temporal_motion adds the staging of a host-side motion image (16 bytes a pixel).
+  struct Denoise { hjapi::DevBuf guide, image[2], in_beauty, in_aov, out, in_history, out_history, in_motion; } denoise;
+
+  // hj_render_motion (api/motion.hip): the staging of host-side previous shape arrays (16 / 48 / 32 bytes a sphere / quad / vertex)
+  // and of a host-side motion image (16 bytes a pixel).  Grown on demand, reused by every call, freed with the context.
+  struct Motion { hjapi::DevBuf spheres, quads, vertices, image; } motion;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
@@ -594,6 +605,20 @@ int denoise_begin(hj_context* ctx, const char* fn, uint32_t width, uint32_t heig
                   DenoiseFrame& f);
 void denoise_prepare_enqueue(hj_context* ctx, const DenoiseFrame& f);
 void denoise_filter_enqueue(hj_context* ctx, const hj_denoise_opts& o, const DenoiseFrame& f, uint32_t& cur, uint32_t i0, uint32_t i1, bool finish);
+// A camera both temporal calls and hj_render_motion accept: finite position and rotation, a fov inside (0, 180)
+inline bool camera_ok(const hj_camera& c) {
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(c.position[k])) return false;
+  for (int k = 0; k < 4; k++)
+    if (!std::isfinite(c.rotation[k])) return false;
+  return std::isfinite(c.fov) && c.fov > 0.0f && c.fov < 180.0f;
+}
+}  // namespace hjapi
+namespace hj { struct DtArgs; }                  // kernels/hj_denoise_temporal.h
+namespace hjapi {
+// api/motion.hip: k_dt_accumulate<true> over a's image on the context's stream (hj_denoise_frame_temporal_motion; the temporal unit
+// itself holds the <false> instantiation alone)
+void dt_accumulate_motion_enqueue(hj_context* ctx, const hj::DtArgs& a);
 // The statistics read-back of a pass's launches (kStatWords x G words each), summed on the host once the stream has drained.
 // on == false (the caller wants no statistics): every member does nothing.
 struct QueryStats {

@@ -1,8 +1,10 @@
 // The temporal half of the frame denoiser ("Temporal accumulation"; include/hijiki_hip.h: hj_denoise_frame_temporal),
 // for the unit api/denoise_temporal.hip: the history of the last frame reprojected into this one, in front of hj_denoise.h's filter.
-//   k_dt_accumulate  one thread per pixel: the guided pixel's world point from its depth and its camera ray, projected into the
-//                    previous camera; the four bilinear taps of the history that pass the depth and the normal test; the blend of
-//                    light and luminance moments; the working image (I, 0) in place and the history record
+//   k_dt_accumulate<MOTION>  one thread per pixel: the guided pixel's world point from its depth and its camera ray, projected into the
+//                    previous camera (MOTION: the position and the distance come from the pixel's motion record, hj_motion.h's,
+//                    instead); the four bilinear taps of the history that pass the depth and the normal test; the blend of
+//                    light and luminance moments; the working image (I, 0) in place and the history record.  The unit launches
+//                    <false>; <true> is instantiated by api/motion.hip alone (dt_accumulate_motion_enqueue)
 //   k_dt_variance    k_dn_variance's text with one more branch: a pixel whose history is HJ_TEMPORAL_VARIANCE_FRAMES long takes the
 //                    variance of its temporal moments, a younger one the 5 x 5 spatial estimate
 //   k_dt_feedback    the first iteration's I' into the history record's light (HJ_TEMPORAL_FEEDBACK)
@@ -10,6 +12,8 @@
 // and cross3 are hj_num.h's, fmaf and all.  Everything else is float32, one rounding each, uncontracted.  Ordinary loads and stores,
 // no inline assembly, no global atomic; no LDS: the taps are data dependent, but neighbouring pixels reproject to neighbouring
 // texels, so a row's loads stay in a few cache lines.
+// HJ_DENOISE_TEMPORAL_NO_KERNELS leaves k_dt_variance and k_dt_feedback out: api/motion.hip takes the camera functions and the
+// accumulate template alone.
 #pragma once
 #define HJ_DENOISE_NO_KERNELS   // the functions of hj_denoise.h; its kernels stay api/denoise.hip's
 #include "hj_denoise.h"
@@ -25,6 +29,7 @@ struct DtArgs {
   const float4* guide;
   float4* img;                  // (I_cur, 0) on entry, (I, 0) on return, in place: a thread touches its own pixel alone
   const float4* hist_in;        // nullptr: no history
+  const float4* motion;         // MOTION: (sx, sy, zp, id bits or HJ_MOTION_NONE) per pixel; otherwise not read
   float4* hist_out;
   uint32_t W, H;
   DtCamera cam, prev;
@@ -49,7 +54,16 @@ HJ_DEV v3 dt_camera_dir(const DtCamera& c, float px, float py, float W, float H)
   return normalize3(dt_rotate(V(x, -y, -1.0f), c.qv, c.qw));
 }
 
+// the host's camera as the kernels take it: tan_half as the upload computes it (api/scene_upload.hip)
+inline DtCamera dt_host_camera(const hj_camera& c) {
+  return DtCamera{v3{c.position[0], c.position[1], c.position[2]}, v3{c.rotation[0], c.rotation[1], c.rotation[2]}, c.rotation[3],
+                  (float)std::tan((double)(0.5f * c.fov) * (3.14159265358979323846 / 180.0))};
+}
+
 // Grid (ceil(W / 32), ceil(H / 8)), one thread per pixel.  Per history tap the valid word first, the three records only behind it.
+// MOTION: (sx, sy, zp) are words 0, 1, 2 of the pixel's motion record, and a record whose word 3 is 0xFFFFFFFF (HJ_MOTION_NONE) gives
+// no history; the text from fx on is one text for both.
+template <bool MOTION>
 __global__ __launch_bounds__(kDnTX * kDnTY) void k_dt_accumulate(DtArgs a) {
   const uint32_t x = blockIdx.x * kDnTX + (threadIdx.x & (kDnTX - 1u)), y = blockIdx.y * kDnTY + threadIdx.x / kDnTX;
   if (x >= a.W || y >= a.H) return;
@@ -67,20 +81,30 @@ __global__ __launch_bounds__(kDnTX * kDnTY) void k_dt_accumulate(DtArgs a) {
   float sm1 = 0.0f, sm2 = 0.0f, sN = 0.0f, ws = 0.0f;
   if (a.hist_in != nullptr) {
     const float Wf = (float)a.W, Hf = (float)a.H;
-    const v3 d = dt_camera_dir(a.cam, (float)x + 0.5f, (float)y + 0.5f, Wf, Hf);
-    const v3 P = V(a.cam.pos.x + z * d.x, a.cam.pos.y + z * d.y, a.cam.pos.z + z * d.z);
-    const v3 v = P - a.prev.pos;
-    const v3 c = dt_rotate(v, -a.prev.qv, a.prev.qw);
-    if (c.z < 0.0f) {
+    bool front;
+    float sx, sy, zp;
+    if constexpr (MOTION) {
+      const float4 mv = a.motion[t];
+      front = __float_as_uint(mv.w) != 0xFFFFFFFFu;
+      sx = mv.x; sy = mv.y; zp = mv.z;
+    } else {
+      const v3 d = dt_camera_dir(a.cam, (float)x + 0.5f, (float)y + 0.5f, Wf, Hf);
+      const v3 P = V(a.cam.pos.x + z * d.x, a.cam.pos.y + z * d.y, a.cam.pos.z + z * d.z);
+      const v3 v = P - a.prev.pos;
+      const v3 c = dt_rotate(v, -a.prev.qv, a.prev.qw);
+      front = c.z < 0.0f;
       const float k = (0.5f * Wf) / a.prev.tan_half;
-      const float sx = (c.x / -c.z) * k + 0.5f * Wf, sy = (-c.y / -c.z) * k + 0.5f * Hf;
+      sx = (c.x / -c.z) * k + 0.5f * Wf;
+      sy = (-c.y / -c.z) * k + 0.5f * Hf;
+      zp = __builtin_sqrtf(dn_sq(v));
+    }
+    if (front) {
       const float fx = sx - 0.5f, fy = sy - 0.5f;
       // ix = floorf(fx) in [-1, W - 1], iy likewise: otherwise no tap lies in the image (a NaN fails every comparison)
       if (fx >= -1.0f && fx < Wf && fy >= -1.0f && fy < Hf) {
         const float fix = __builtin_floorf(fx), fiy = __builtin_floorf(fy);
         const float tx = fx - fix, ty = fy - fiy;
         const int ix = (int)fix, iy = (int)fiy;
-        const float zp = __builtin_sqrtf(dn_sq(v));
         const float wx[2] = {1.0f - tx, tx}, wy[2] = {1.0f - ty, ty};
         const uint32_t* hw = reinterpret_cast<const uint32_t*>(a.hist_in);
 #pragma unroll
@@ -122,6 +146,8 @@ __global__ __launch_bounds__(kDnTX * kDnTY) void k_dt_accumulate(DtArgs a) {
   a.hist_out[3 * (size_t)t + 1] = make_float4(m1, m2, z, __uint_as_float(1u));
   a.hist_out[3 * (size_t)t + 2] = make_float4(n.x, n.y, n.z, 0.0f);
 }
+
+#ifndef HJ_DENOISE_TEMPORAL_NO_KERNELS
 
 // k_dn_variance's text (hj_denoise.h; that kernel and its machine code stay as they are) with the temporal branch: hist is the
 // history k_dt_accumulate wrote for this frame.  Grid (ceil(W / 32), ceil(H / 8)).
@@ -174,5 +200,7 @@ __global__ __launch_bounds__(kDnThreads) void k_dt_feedback(const float4* __rest
   const float4 ci = in[t];
   hist[3 * (size_t)t] = make_float4(ci.x, ci.y, ci.z, hist[3 * (size_t)t].w);
 }
+
+#endif  // HJ_DENOISE_TEMPORAL_NO_KERNELS
 
 }  // namespace hj

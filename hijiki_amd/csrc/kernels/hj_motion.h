@@ -1,0 +1,136 @@
+// Per-pixel motion for the temporal denoiser ("Motion for the temporal denoiser"; include/hijiki_hip.h: hj_render_motion):
+// for every pixel where the surface point its centre ray sees was in the previous frame, as a position in the previous image and a
+// distance from the previous camera.  The walk is the path kernel's (trace_persistent, hj_walk.h), the centre ray's direction is the
+// temporal stage's (dt_camera_dir, hj_denoise_temporal.h), the sphere normal is populate_sphere's divs (hj_shade.h) - included here
+// and edited nowhere.  No global atomics, no inline assembly of its own; loads and stores are the compiler's.
+//   k_mv_walk<PAIRS>   the persistent walk over the image's pixels, a wave's 64 rays together in the image; the raw hit
+//                      (id bits, t, u, v) goes into the pixel's own record of `motion`: no ray array and no hit array exist
+//   k_mv_resolve       one lane per pixel: the raw hit read back, the previous point from the previous shape arrays, its projection
+//                      into the previous camera, the record overwritten in place
+// The previous-point arithmetic stays out of the walk's finish: inside it it would take the walk's registers.
+#pragma once
+#include "hj_stages.h"
+#define HJ_DENOISE_TEMPORAL_NO_KERNELS   // dt_camera_dir, dt_rotate, dn_sq and the accumulate template; the temporal unit's kernels stay its own
+#include "hj_denoise_temporal.h"
+
+#pragma clang fp contract(off)
+
+namespace hj {
+
+constexpr uint32_t kMvNone = 0xFFFFFFFFu;   // HJ_MOTION_NONE: word 3 of a record without a previous position
+constexpr uint32_t kMvPad = 0xFFFFFFFFu;    // the slot of a walk entry beyond the image (no pixel has this index: at most 2^28)
+
+// The previous frame as k_mv_resolve reads it: shape arrays with the uploaded scene's counts, and the camera
+struct MvPrev {
+  const float4* spheres;        // hj_sphere
+  const float4* quads;          // hj_quad as 3 x float4
+  const float4* vertices;       // hj_vertex as 2 x float4 (pos.xyz, u | normal.xyz, v)
+  DtCamera cam;
+};
+
+// the uploaded scene's camera as dt_camera_dir takes it
+HJ_DEV DtCamera mv_camera(const DeviceScene& sc) {
+  return DtCamera{V(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]),
+                  V(sc.camera.rotation[0], sc.camera.rotation[1], sc.camera.rotation[2]), sc.camera.rotation[3], sc.tan_half_fov};
+}
+
+// Walk entries of a W x H image: 64-entry groups, a group either an 8 x 8 pixel tile (tile != 0: DeviceScene::group_tile, as the
+// camera packets over a large tree) or a run of 64 pixels of a row; groups in raster order of tiles / runs.  The image is padded to
+// whole groups, so every pixel is exactly one entry: a bijection between the pixels and the entries that are no padding.
+__host__ __device__ inline uint32_t mv_entries(uint32_t W, uint32_t H, uint32_t tile) {
+  return tile != 0u ? ((W + 7u) >> 3) * ((H + 7u) >> 3) * 64u : ((W + 63u) >> 6) * H * 64u;
+}
+// ... entry q's pixel; false: padding
+HJ_DEV bool mv_pixel(uint32_t q, uint32_t W, uint32_t H, uint32_t tile, uint32_t& x, uint32_t& y) {
+  const uint32_t grp = q >> 6, lane = q & 63u;
+  if (tile != 0u) {
+    const uint32_t across = (W + 7u) >> 3;
+    x = ((grp % across) << 3) | (lane & 7u);
+    y = ((grp / across) << 3) | (lane >> 3);
+  } else {
+    const uint32_t across = (W + 63u) >> 6;
+    x = ((grp % across) << 6) | lane;
+    y = grp / across;
+  }
+  return x < W && y < H;
+}
+
+// Entries [0, n = mv_entries) of the image.  Workgroup g walks entries [g * wg_rays, ...) as k_rq_walk's does.  An entry's ray is
+// built from its pixel - origin = the uploaded camera's position, d = dt_camera_dir through (x + 0.5, y + 0.5), tMin = eps, tMax =
+// +inf - and its raw hit (objectID bits, t, u, v; a miss: (-1, 0, 0, 0)) goes to motion[y * W + x]: which lane or workgroup
+// carried a pixel, and which grouping, shows in no record.  A padding entry is fetched as a ray with the empty range [+inf, -inf]:
+// it fails every box and shape test, leaves the tree at the first node and writes nothing.
+template <bool PAIRS>
+__global__ __launch_bounds__(kBlockThreads) void k_mv_walk(DeviceScene sc, uint32_t W, uint32_t H, uint32_t n, uint32_t wg_rays,
+                                                           float4* __restrict__ motion) {
+  __shared__ WgShared sh;
+  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(n / wg_rays): first < n)
+  const uint32_t cnt = n - first < wg_rays ? n - first : wg_rays;
+  if (threadIdx.x == 0) sh.head = 0;
+  load_hot_nodes(sc, sh);
+  __syncthreads();
+  const DtCamera cam = mv_camera(sc);
+  const float Wf = (float)W, Hf = (float)H;
+  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
+    uint32_t x, y;
+    const bool valid = mv_pixel(first + i, W, H, sc.group_tile, x, y);
+    slot = valid ? y * W + x : kMvPad;
+    any = false;
+    r.o = cam.pos;
+    r.d = valid ? dt_camera_dir(cam, (float)x + 0.5f, (float)y + 0.5f, Wf, Hf) : V(0.f, 0.f, 0.f);
+    r.tmin = valid ? kEps : kInf;                                  // render.glsl:33
+    r.tmax = valid ? kInf : -kInf;
+    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
+  };
+  auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
+    if (done && slot != kMvPad) {
+      const bool hit = h.id >= 0;
+      motion[slot] = make_float4(__int_as_float(hit ? h.id : -1), hit ? h.t : 0.f, hit ? h.u : 0.f, hit ? h.v : 0.f);
+    }
+  };
+  trace_persistent<0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+}
+
+// One lane per pixel t = y * W + x, in place: motion[t] holds the walk's raw hit on entry and the pixel's record on return, so a
+// lane touches its own record alone.  The contract's arithmetic (include/hijiki_hip.h, hj_render_motion), operation for operation:
+// one rounding each, uncontracted, except dt_camera_dir, dt_rotate and divs, which are the numeric contract's, and the hit point's fmaf.
+__global__ __launch_bounds__(kBlockThreads) void k_mv_resolve(DeviceScene sc, MvPrev prev, uint32_t W, uint32_t H, float4* __restrict__ motion) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= W * H) return;
+  const float4 hr = motion[t];
+  const uint32_t id = __float_as_uint(hr.x);
+  float4 out = make_float4(0.f, 0.f, 0.f, __uint_as_float(kMvNone));
+  if (id < sc.ns + sc.nq + sc.nt) {                                // (a miss is 0xFFFFFFFF; any other id outside the scene is one too)
+    const float u = hr.z, v = hr.w;
+    v3 Pp;
+    if (id < sc.ns) {
+      const uint32_t x = t % W, y = t / W;
+      const DtCamera cam = mv_camera(sc);
+      const v3 d = dt_camera_dir(cam, (float)x + 0.5f, (float)y + 0.5f, (float)W, (float)H);
+      const v3 P = V(fmaf(hr.y, d.x, cam.pos.x), fmaf(hr.y, d.y, cam.pos.y), fmaf(hr.y, d.z, cam.pos.z));   // scene.glsl:164
+      const float4 sp = sc.spheres[id], pp = prev.spheres[id];
+      const v3 n = divs(P - xyz(sp), sp.w);                        // populate_sphere's normal
+      Pp = V(pp.x + n.x * pp.w, pp.y + n.y * pp.w, pp.z + n.z * pp.w);
+    } else if (id < sc.ns + sc.nq) {
+      const float4* __restrict__ q = prev.quads + 3 * (size_t)(id - sc.ns);
+      const float4 o = q[0], e1 = q[1], e2 = q[2];
+      Pp = V((o.x + e1.x * u) + e2.x * v, (o.y + e1.y * u) + e2.y * v, (o.z + e1.z * u) + e2.z * v);
+    } else {
+      const hj_triangle tri = sc.triangles[id - sc.ns - sc.nq];
+      const float4 a = prev.vertices[2 * (size_t)tri.v[0]], b = prev.vertices[2 * (size_t)tri.v[1]], c = prev.vertices[2 * (size_t)tri.v[2]];
+      const float l0 = (1.0f - u) - v;
+      Pp = V((a.x * l0 + b.x * u) + c.x * v, (a.y * l0 + b.y * u) + c.y * v, (a.z * l0 + b.z * u) + c.z * v);
+    }
+    const v3 vv = Pp - prev.cam.pos;
+    const v3 c = dt_rotate(vv, -prev.cam.qv, prev.cam.qw);
+    if (c.z < 0.0f) {
+      const float Wf = (float)W, Hf = (float)H;
+      const float k = (0.5f * Wf) / prev.cam.tan_half;
+      const float sx = (c.x / -c.z) * k + 0.5f * Wf, sy = (-c.y / -c.z) * k + 0.5f * Hf;
+      out = make_float4(sx, sy, __builtin_sqrtf(dn_sq(vv)), __uint_as_float(id));
+    }
+  }
+  motion[t] = out;
+}
+
+}  // namespace hj

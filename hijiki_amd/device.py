@@ -32,7 +32,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
            "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame",
-           "hj_denoise_frame", "hj_denoise_frame_temporal")
+           "hj_denoise_frame", "hj_denoise_frame_temporal", "hj_render_motion", "hj_denoise_frame_temporal_motion")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -127,6 +127,8 @@ def lib():
         L.hj_render_aovs_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_denoise_frame.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), vp]   # (host or device pointers)
         L.hj_denoise_frame_temporal.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp]
+        L.hj_denoise_frame_temporal_motion.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp, vp]
+        L.hj_render_motion.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp]   # (host or device pointers)
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -207,6 +209,15 @@ def resolve_aovs(aov):
 
     return dict(albedo=mean(aov[..., 0:3], samples), normal=mean(aov[..., 4:7], hits), depth=mean(aov[..., 7], hits),
                 emission=mean(aov[..., 8:11], samples), coverage=mean(hits, samples))
+
+
+def motion_ids(m):
+    """word 3 of `render_motion`'s records as uint32 (height, width): the shape the pixel's centre ray hits, abi.MOTION_NONE for a
+    pixel without a previous position.  m: the (height, width, 4) float32 array or tensor; a view where the type allows one."""
+    if isinstance(m, np.ndarray):
+        return np.ascontiguousarray(m, np.float32).view(np.uint32)[..., 3]
+    import torch
+    return m.contiguous().view(torch.int32)[..., 3].cpu().numpy().view(np.uint32)
 
 
 class Comm:
@@ -769,6 +780,42 @@ class Renderer:
             self._check(lib().hj_render_aovs_frame(self._h, width, height, int(spp), int(master_seed), begin, end, flags, ptr))
         return aov
 
+    def render_motion(self, prev, width, height, device_arrays=None, device=False):
+        """hj_render_motion: per-pixel motion for `denoise_frame_temporal` -> (height, width, 4) float32: per pixel (sx, sy, zp, id
+        bits) - where the surface point the pixel's centre ray sees in the uploaded scene was in the previous image, its distance
+        from the previous camera, and the shape - or (0, 0, 0, abi.MOTION_NONE) for a miss or a point behind the previous camera
+        (`motion_ids` views word 3).  prev: how the scene stood in the previous frame - a compiled scene, or anything with `.desc`
+        (camera, spheres, quads, vertices with the uploaded counts; a NULL array: that kind did not move), as `update_shapes` takes
+        it.  The current frame is the scene as uploaded or as the last `update_shapes` left it.  device_arrays: the dict of torch
+        tensors `update_shapes` takes, read in place of prev's host arrays (a kind it lacks did not move).  device=True: the result
+        is a torch tensor on the renderer's GPU, written in place.  Not followed: a sphere's rotation about its centre, what a
+        mirror or glass shows, moving lights' shadows."""
+        d = abi.SceneDesc()
+        C.memmove(C.byref(d), C.byref(prev.desc), C.sizeof(abi.SceneDesc))
+        width, height = int(width), int(height)
+        flags = 0
+        if device_arrays is not None:
+            import torch
+            flags |= abi.MOTION_DEVICE_SHAPES
+            for name, count, words, rec in (("spheres", d.num_spheres, 4, abi.Sphere), ("quads", d.num_quads, 12, abi.Quad), ("vertices", d.num_vertices, 8, abi.Vertex)):
+                t = device_arrays.get(name)
+                if t is not None and not (t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == count * words):
+                    raise ValueError(f"device_arrays['{name}']: a contiguous float32 tensor of {count} x {words} on GPU {self.device} is needed"
+                                     f" (got {tuple(t.shape)} {t.dtype} on {t.device})")
+                setattr(d, name, C.cast(C.c_void_p(t.data_ptr() if t is not None and count else None), C.POINTER(rec)))
+            torch.cuda.current_stream().synchronize()
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            motion = torch.empty((height, width, abi.MOTION_WORDS), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()              # (the allocation)
+            ptr, flags = motion.data_ptr(), flags | abi.MOTION_DEVICE_OUT
+        else:
+            motion = np.zeros((height, width, abi.MOTION_WORDS), np.float32)
+            ptr = motion.ctypes.data
+        self._check(lib().hj_render_motion(self._h, C.byref(d), width, height, flags, ptr))
+        return motion
+
     def denoise_frame(self, aov, beauty=None, iterations=5, sigma_normal=0.5, sigma_depth=1.0, sigma_luminance=4.0, sigma_albedo=0.1, device=False):
         """hj_denoise_frame: the variance-guided a-trous filter of SVGF over one frame -> a new (height, width, 4) float32 image: the
         denoised rgb and, in word 3, the filtered variance of the demodulated luminance.  aov: the (height, width, 12) sums of
@@ -815,7 +862,8 @@ class Renderer:
         return out
 
     def denoise_frame_temporal(self, aov, camera, prev_camera, history=None, beauty=None, iterations=5, sigma_normal=0.5, sigma_depth=1.0, sigma_luminance=4.0,
-                               sigma_albedo=0.1, alpha=0.2, alpha_moments=0.2, depth_tolerance=0.1, normal_cos=0.9, max_history=64, feedback=True, device=False):
+                               sigma_albedo=0.1, alpha=0.2, alpha_moments=0.2, depth_tolerance=0.1, normal_cos=0.9, max_history=64, feedback=True, device=False,
+                               motion=None):
         """hj_denoise_frame_temporal: `denoise_frame` behind SVGF's temporal accumulation -> (out, history): the (height, width, 4)
         denoised image and the new (height, width, 12) history to pass as `history` with the next frame.  camera: the abi.Camera
         (beauty, aov) were rendered with; prev_camera: the camera of the frame that wrote `history`.  history None: the first frame
@@ -827,7 +875,9 @@ class Renderer:
         goes into the history (SVGF's feedback).  A moved shape is met by the two tests alone.  alpha and alpha_moments 0.2 are
         SVGF's; depth_tolerance 0.1, normal_cos 0.9 and max_history 64 are guesses: not tuned.  Everything else as `denoise_frame`;
         device=True: `aov`, `history` and `beauty` are contiguous float32 torch tensors on the renderer's GPU, read in place, and
-        both results are new tensors there."""
+        both results are new tensors there.  motion: the (height, width, 4) image of `render_motion` for this frame
+        (hj_denoise_frame_temporal_motion; a tensor with device=True): the history is read where each pixel's surface point was -
+        moved shapes keep theirs -, a record of abi.MOTION_NONE has none, and the two cameras are checked but not used."""
         iterations = int(iterations)
         sig = [float(sigma_normal), float(sigma_depth), float(sigma_luminance), float(sigma_albedo)]
         if not 0 <= iterations <= abi.DENOISE_MAX_ITERATIONS:
@@ -840,20 +890,27 @@ class Renderer:
                              abi.TEMPORAL_FEEDBACK if feedback else 0)
         if device:
             import torch
-            for name, x in (("aov", aov), ("beauty", beauty), ("history", history)):
+            for name, x in (("aov", aov), ("beauty", beauty), ("history", history), ("motion", motion)):
                 if x is None and name != "aov":
                     continue
                 if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == torch.float32 and x.is_contiguous()):
                     raise ValueError(f"denoise_frame_temporal: {name} must be a contiguous float32 tensor on cuda:{self.device}")
             if (aov.dim() != 3 or aov.shape[2] != abi.AOV_WORDS or (beauty is not None and tuple(beauty.shape) != (aov.shape[0], aov.shape[1], 4))
-                    or (history is not None and tuple(history.shape) != (aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS))):
-                raise ValueError("denoise_frame_temporal: aov (height, width, 12), beauty (height, width, 4) and history (height, width, 12) are needed")
+                    or (history is not None and tuple(history.shape) != (aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS))
+                    or (motion is not None and tuple(motion.shape) != (aov.shape[0], aov.shape[1], abi.MOTION_WORDS))):
+                raise ValueError("denoise_frame_temporal: aov (height, width, 12), beauty (height, width, 4), history (height, width, 12) and motion "
+                                 "(height, width, 4) are needed")
             h, w = int(aov.shape[0]), int(aov.shape[1])
             out = torch.empty((h, w, 4), dtype=torch.float32, device=aov.device)
             hist = torch.empty((h, w, abi.TEMPORAL_WORDS), dtype=torch.float32, device=aov.device)
             torch.cuda.current_stream(aov.device).synchronize()       # (the allocations and whatever wrote the inputs)
-            self._check(lib().hj_denoise_frame_temporal(self._h, w, h, None if beauty is None else beauty.data_ptr(), aov.data_ptr(), C.byref(o), C.byref(t),
-                                                        None if history is None else history.data_ptr(), hist.data_ptr(), out.data_ptr()))
+            args = (None if history is None else history.data_ptr(), hist.data_ptr(), out.data_ptr())
+            if motion is not None:
+                self._check(lib().hj_denoise_frame_temporal_motion(self._h, w, h, None if beauty is None else beauty.data_ptr(), aov.data_ptr(), C.byref(o),
+                                                                   C.byref(t), motion.data_ptr(), *args))
+            else:
+                self._check(lib().hj_denoise_frame_temporal(self._h, w, h, None if beauty is None else beauty.data_ptr(), aov.data_ptr(), C.byref(o), C.byref(t),
+                                                            *args))
             return out, hist
         aov = np.ascontiguousarray(aov, np.float32)
         if beauty is not None:
@@ -861,12 +918,20 @@ class Renderer:
         if history is not None:
             history = np.ascontiguousarray(history, np.float32)
         if (aov.ndim != 3 or aov.shape[2] != abi.AOV_WORDS or (beauty is not None and beauty.shape != (aov.shape[0], aov.shape[1], 4))
-                or (history is not None and history.shape != (aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS))):
-            raise ValueError("denoise_frame_temporal: aov (height, width, 12), beauty (height, width, 4) and history (height, width, 12) are needed")
+                or (history is not None and history.shape != (aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS))
+                or (motion is not None and np.shape(motion) != (aov.shape[0], aov.shape[1], abi.MOTION_WORDS))):
+            raise ValueError("denoise_frame_temporal: aov (height, width, 12), beauty (height, width, 4), history (height, width, 12) and motion "
+                             "(height, width, 4) are needed")
         out = np.zeros((aov.shape[0], aov.shape[1], 4), np.float32)
         hist = np.zeros((aov.shape[0], aov.shape[1], abi.TEMPORAL_WORDS), np.float32)
-        self._check(lib().hj_denoise_frame_temporal(self._h, aov.shape[1], aov.shape[0], None if beauty is None else beauty.ctypes.data, aov.ctypes.data, C.byref(o),
-                                                    C.byref(t), None if history is None else history.ctypes.data, hist.ctypes.data, out.ctypes.data))
+        args = (None if history is None else history.ctypes.data, hist.ctypes.data, out.ctypes.data)
+        if motion is not None:
+            motion = np.ascontiguousarray(motion, np.float32)
+            self._check(lib().hj_denoise_frame_temporal_motion(self._h, aov.shape[1], aov.shape[0], None if beauty is None else beauty.ctypes.data,
+                                                               aov.ctypes.data, C.byref(o), C.byref(t), motion.ctypes.data, *args))
+        else:
+            self._check(lib().hj_denoise_frame_temporal(self._h, aov.shape[1], aov.shape[0], None if beauty is None else beauty.ctypes.data, aov.ctypes.data,
+                                                        C.byref(o), C.byref(t), *args))
         return out, hist
 
     def trace_paths(self, rays, seeds=None, spp=1, opts=None, stats=False):

@@ -1578,7 +1578,8 @@ int hj_denoise_frame(hj_context* ctx, uint32_t width, uint32_t height,
  *       the history is the I' of the first iteration (step 1) - SVGF's feedback; without the flag it is the accumulated I of step 3.
  *   So history_in == NULL gives an out that is hj_denoise_frame's bit for bit, and so does a history whose valid words are all 0 or
  *   a prev_camera that looks the other way - in either kernel form.  Agreement bit for bit with this text is claimed for finite
- *   inputs; non-finite values just propagate.  A moved shape is met by the depth and normal tests alone, which reset its history.
+ *   inputs; non-finite values just propagate.  A moved shape is met by the depth and normal tests alone, which reset its history
+ *   (hj_denoise_frame_temporal_motion follows it).
  * The context keeps, beside hj_denoise_frame's buffers, the staging of the two histories when they are host arrays.
  * HJ_ERR_INVALID, before the device is touched, in this order, each with its text in hj_last_error behind
  *   "hj_denoise_frame_temporal:": hj_denoise_frame's own list up to the image size, with topts and history_out joining the null
@@ -1588,8 +1589,9 @@ int hj_denoise_frame(hj_context* ctx, uint32_t width, uint32_t height,
  *   writes nothing.  Then hj_denoise_frame's gate.
  * The defaults of the Python wrapper: alpha 0.2 and alpha_moments 0.2 are SVGF's; depth_tolerance 0.1, normal_cos 0.9 and
  *   max_history 64 are guesses: they are not tuned.
- * Not here: motion vectors for moved shapes; SVGF's 3 x 3 fallback search when the bilinear taps fail; history for pixels that are
- *   not guided (lit or missed); a flag of the command line; a multi-GPU split; tuned defaults. */
+ * Not here: motion vectors for moved shapes: hj_render_motion and hj_denoise_frame_temporal_motion below; SVGF's 3 x 3 fallback search
+ *   when the bilinear taps fail; history for pixels that are not guided (lit or missed); a flag of the command line; a multi-GPU
+ *   split; tuned defaults. */
 #define HJ_TEMPORAL_WORDS 12
 #define HJ_TEMPORAL_FEEDBACK 1u
 #define HJ_TEMPORAL_VARIANCE_FRAMES 4u
@@ -1608,6 +1610,74 @@ int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, 
                               const float* history_in  /* H x W x 12, or NULL: no history */,
                               float* history_out       /* H x W x 12, never aliases an input */,
                               float* out               /* H x W x 4 */);
+
+/* hj_render_motion (ABI 0.29): per-pixel motion for the temporal denoiser - for every pixel (x, y), where the surface point that the
+ * pixel's centre ray sees in the CURRENT frame was in the PREVIOUS frame: a position in the previous image and a distance from the
+ * previous camera, the (sx, sy, zp) of hj_denoise_frame_temporal's step 2 with the point carried back onto the previous shape.  No
+ * counterpart in the reference; tests/motion_ref.py restates the contract in numpy.
+ *   The current frame is the scene as uploaded - after hj_scene_update_shapes the updated shapes and camera.  prev says how the scene
+ *     stood in the previous frame, in the form hj_scene_update_shapes reads: prev->camera is the previous camera; prev->spheres,
+ *     prev->quads and prev->vertices carry the same counts as the uploaded scene.  bvh, triangles, materials, emitters and the
+ *     material records are not read: the index triples are the uploaded ones.  A shape array that is NULL with its count equal to
+ *     the uploaded count means that kind did not move: the uploaded array stands in for it.  The ordinary frame loop: move the
+ *     shapes, hj_scene_update_shapes, hj_render_motion against the old arrays.
+ *   motion: height x width records of HJ_MOTION_WORDS floats, pixel (x, y) at record y * width + x:  (sx, sy, zp, id as bits), or
+ *     (0, 0, 0, HJ_MOTION_NONE) for a pixel without a previous position.
+ *   Every operation is float32 with one rounding and no contraction, except inside rotate, normalize3, dot3, cross3 (the numeric
+ *   contract's, as for hj_denoise_frame_temporal) and the hit point.  rotate, conj, tan and sq are hj_denoise_frame_temporal's;
+ *   W = (float)width, H = (float)height.
+ *   RAY.  d is step 2's d with px = (float)x + 0.5f, py = (float)y + 0.5f, the uploaded scene's camera and its tan as the upload
+ *     computes it.  The ray has the origin o = camera.position, tMin = eps (1e-4f) and tMax = +inf, and goes through the uploaded
+ *     tree by the path kernel's walk, as a frame's primary rays and hj_trace_rays' do: the result is hj_trace_rays' (id, t, u, v).
+ *   MISS.  A miss is an id outside [0, shapes): the record is (0, 0, 0, HJ_MOTION_NONE).
+ *   PREVIOUS POINT Pp, per channel:
+ *     sphere id:   P = fma(t, d, o), the shade stage's hit point.  n = (P - c) * (1.0f / r) with (c, r) the uploaded sphere: one
+ *                  reciprocal, then one multiply per channel (the numeric contract's vector / scalar, as the shade stage's sphere
+ *                  normal).  Pp = c' + n * r' with (c', r') the previous sphere.
+ *     quad:        Pp = (o' + e1' * u) + e2' * v with (o', e1', e2') the previous quad.
+ *     triangle:    l0 = (1.0f - u) - v.  Pp = (a' * l0 + b' * u) + c' * v with a', b', c' the previous positions of the uploaded
+ *                  index triple.
+ *   PROJECTION, step 2's words with prev->camera:  vv = Pp - prev.position.  c = rotate(vv, conj(prev.rotation)).  If c.z < 0 is
+ *     false the record is (0, 0, 0, HJ_MOTION_NONE).  Otherwise k = (0.5f * W) / tan(prev);  sx = (c.x / -c.z) * k + 0.5f * W;
+ *     sy = (-c.y / -c.z) * k + 0.5f * H;  zp = sqrtf(sq(vv)).  The record is (sx, sy, zp, id as bits).
+ *   A record depends on the uploaded scene, prev and (width, height) alone: not on the lane, the workgroup count, the grouping of
+ *   pixels into waves or any tuning switch.  Agreement bit for bit with this text is claimed for finite inputs.
+ *   HJ_MOTION_DEVICE_SHAPES: prev->spheres / quads / vertices are device pointers (as HJ_UPDATE_DEVICE_ARRAYS), used in place on the
+ *     context's stream.  HJ_MOTION_DEVICE_OUT: motion is a device pointer, 16-byte aligned, written in place.
+ * The context keeps the staging of previous shape arrays that come from the host - 48 / 16 / 32 bytes per quad / sphere / vertex -
+ *   and 16 bytes a pixel when motion is a host array.  No second width x height buffer exists: the walk writes each pixel's raw hit
+ *   into its record and the resolve overwrites it in place.
+ * HJ_ERR_INVALID, before the device is touched, in this order, each with its text in hj_last_error behind "hj_render_motion:":
+ *   null prev or motion; unknown flag bits; a zero width or height, or one above 16384; a prev->camera field that is not finite, or
+ *   a fov outside (0, 180); a misaligned device array.  A refused call writes nothing.  Then hj_trace_rays' gate: HJ_ERR_STATE without
+ *   a scene, with a frame in flight, or with undrained frames.  Behind the gate, in this order: counts that differ from the uploaded
+ *   scene's (HJ_ERR_INVALID); with host arrays, a previous coordinate or radius that is not finite (HJ_ERR_INVALID) - device arrays
+ *   are the caller's word, as for hj_scene_update_shapes.
+ * Not here: rotation of a sphere about its own centre, which a record of centre and radius cannot express; what a mirror or glass
+ *   shows; moving lights' shadows on static surfaces; a change of topology or counts; a multi-GPU split; a CLI flag. */
+#define HJ_MOTION_WORDS 4
+#define HJ_MOTION_NONE 0xFFFFFFFFu
+#define HJ_MOTION_DEVICE_SHAPES 1u   /* prev->spheres / quads / vertices are device pointers (as HJ_UPDATE_DEVICE_ARRAYS) */
+#define HJ_MOTION_DEVICE_OUT    2u   /* motion is a device pointer, 16-byte aligned, written in place */
+int hj_render_motion(hj_context* ctx, const hj_scene_desc* prev, uint32_t width, uint32_t height, uint32_t flags,
+                     float* motion /* height x width x 4 */);
+
+/* hj_denoise_frame_temporal_motion (ABI 0.29): hj_denoise_frame_temporal reprojecting through a motion image.
+ *   motion == NULL: the call is hj_denoise_frame_temporal, bit for bit (one host routine).
+ *   Otherwise step 2 (REPROJECT) changes for a guided pixel: if word 3 of the pixel's motion record is HJ_MOTION_NONE there is no
+ *     history; otherwise sx, sy and zp are words 0, 1 and 2 of the record, and everything from fx = sx - 0.5f on is step 2
+ *     unchanged - the window test, the four taps, their order, and the depth and normal tests against zp and the pixel's own n.
+ *     The two cameras of topts are still validated but not used.
+ *   HJ_DENOISE_DEVICE_ARRAYS covers motion too; motion joins the alias check against history_out and the alignment check.  The
+ *   context keeps the staging of a host-side motion image, 16 bytes a pixel.  Every refusal is hj_denoise_frame_temporal's, behind
+ *   "hj_denoise_frame_temporal_motion:".
+ *   So a motion image holding the static projection's own (sx, sy, zp) - and HJ_MOTION_NONE where c.z < 0 is false - gives
+ *   hj_denoise_frame_temporal's results bit for bit, and an image of HJ_MOTION_NONE alone gives hj_denoise_frame's out.
+ * Not here: what hj_render_motion does not follow (its list). */
+int hj_denoise_frame_temporal_motion(hj_context* ctx, uint32_t width, uint32_t height, const float* beauty, const float* aov,
+                                     const hj_denoise_opts* opts, const hj_temporal_opts* topts,
+                                     const float* motion /* H x W x HJ_MOTION_WORDS, or NULL */,
+                                     const float* history_in, float* history_out, float* out);
 
 /* The deterministic replacement of `rand::random()` in the block generator.
  * Pure functions (no context); the same definitions are used by the host
