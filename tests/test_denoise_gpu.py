@@ -2,7 +2,8 @@
 frames from 1 x 1 to 70 x 41 (no multiple of the 32 x 8 tile; at step 16 the taps lie +-32 away, past a tile and past the image),
 both forms of the iteration forced through HJ_DENOISE_LDS_STEP and a mix of them, holes of every kind, flat regions, albedos at and
 below the floor, every sigma off alone and all off, 0 and 8 iterations, device tensors in place; beauty = NULL over a rendered
-frame; the command line; and the one condition a denoiser has to meet: less error than the frame it was given."""
+frame; 517 x 131 and 517 x 259 (several lattice tiles a residue class in both axes up to step 16) and the side limit of 16384;
+the command line; and the one condition a denoiser has to meet: less error than the frame it was given."""
 import os
 import subprocess
 
@@ -117,6 +118,44 @@ def want(W, H, iterations, sigmas=DEFAULTS):
     return _WANT[key][iterations]
 
 
+BIG = (517, 131)      # ceil(517 / 16) = 33 > 32 and ceil(131 / 16) = 9 > 8: at every step up to 16 a residue class has two lattice tiles in x and in y, the last ragged
+# 517 / 32 and 131 / 8 are nearly equal: there tiles_x == tiles_y at every step (17, 9, 5, 3, 2), and a decode that took one for the other
+# would not show.  517 x 259: tiles_x, tiles_y = (17, 33), (9, 17), (5, 9), (3, 5), (2, 3) at the steps 1 ... 16, both above 1 and never equal.
+TALL = (517, 259)
+_BIG = {}
+
+
+def big_frame(size=BIG):
+    """frame(W, H) of a size in (BIG, TALL) with its holes near the origin, and hits = 0 (the AOV's normal, depth, emission and hit
+    count zero) at about 1 % of the pixels, so that the last lattice tile of a residue class - the pixels from (512, 128) or
+    (512, 256) on - holds holes and guided pixels both.  The premise is asserted here, before any GPU call."""
+    if size not in _BIG:
+        W, H = size
+        y0 = (H - 1) // 128 * 128
+        assert W > 512 and H - y0 == 3
+        beauty, aov = frame(W, H)
+        aov = aov.copy()
+        holes = np.random.default_rng([W, H, 2030]).random((H, W)) < 0.01
+        holes[H - 2, 513] = True                                        # (one inside the last tile that is not frame()'s corner pixel)
+        aov[holes, 4:12] = 0
+        G = D.prepare(beauty, aov)[0]
+        assert 0.007 * W * H < holes.sum() < 0.013 * W * H and not G[holes].any()
+        assert (~G)[y0:, 512:].any() and G[y0:, 512:].any() and (~G)[H - 2, 513] and G.mean() > 0.9
+        aov.setflags(write=False)
+        _BIG[size] = (beauty, aov)
+    return _BIG[size]
+
+
+def big_want(size=BIG):
+    """the reference for big_frame(size), five iterations (steps 1 ... 16), once"""
+    key = ("want", size)
+    if key not in _BIG:
+        _BIG[key] = D.run(*big_frame(size), 5)
+        assert np.isfinite(_BIG[key]).all()
+        _BIG[key].setflags(write=False)
+    return _BIG[key]
+
+
 def test_the_fabricated_frame_holds_what_the_cases_need():
     beauty, aov = frame(70, 41)
     G, c, A, I, n, z = D.prepare(beauty, aov)
@@ -137,6 +176,48 @@ def test_every_size_in_every_form(forms, size, step):
     W, H, it = size
     beauty, aov = frame(W, H)
     same_bits(forms[step].denoise_frame(aov, beauty, it), want(W, H, it), f"{W} x {H}, {it} iterations, HJ_DENOISE_LDS_STEP={step}")
+
+
+@pytest.mark.parametrize("step", ["0", "128", None])
+def test_lattice_tiles_beyond_one_a_residue_class(forms, step):
+    """517 x 131: k_dn_filter_lds' block decode (rx * tiles_x + tx, ry * tiles_y + ty) with tiles_x > 1 and tiles_y > 1 at the steps
+    4, 8 and 16, a ragged last tile in both axes, holes inside it"""
+    beauty, aov = big_frame()
+    same_bits(forms[step].denoise_frame(aov, beauty, 5), big_want(), f"517 x 131, HJ_DENOISE_LDS_STEP={step}")
+
+
+def test_lattice_tiles_with_other_counts_in_x_than_in_y(forms):
+    """517 x 259 in the LDS form at every step: tiles_x != tiles_y and both above 1 at every step up to 16 - at 517 x 131 the two are
+    equal at every step, and a decode that divided by the wrong one would pass there"""
+    W, H = TALL
+    up = lambda a, b: -(-a // b)                                        # noqa: E731
+    for s in (1, 2, 4, 8, 16):
+        tx, ty = up(up(W, s), 32), up(up(H, s), 8)
+        assert tx > 1 and ty > 1 and tx != ty, (s, tx, ty)
+        bx, by = up(up(BIG[0], s), 32), up(up(BIG[1], s), 8)
+        assert bx == by > 1, (s, bx, by)
+    beauty, aov = big_frame(TALL)
+    same_bits(forms["128"].denoise_frame(aov, beauty, 5), big_want(TALL), "517 x 259, HJ_DENOISE_LDS_STEP=128")
+
+
+SIDE = [(16384, 1), (1, 16384)]       # kDenoiseMaxSide; at step 128 the lattice grid is 128 x tiles blocks, nearly all of them apron
+
+
+@pytest.mark.parametrize("step", ["0", "128"])
+@pytest.mark.parametrize("size", SIDE)
+def test_the_side_limit_in_both_forms(forms, size, step):
+    W, H = size
+    beauty, aov = frame(W, H)
+    w = want(W, H, 8)
+    assert np.isfinite(w).all() and not (w == want(W, H, 7)).all()
+    same_bits(forms[step].denoise_frame(aov, beauty, 8), w, f"{W} x {H}, 8 iterations, HJ_DENOISE_LDS_STEP={step}")
+
+
+def test_one_pixel_past_the_side_limit_is_refused(forms):
+    for W, H in ((16385, 1), (1, 16385)):
+        with pytest.raises(abi.HijikiError) as e:
+            forms[None].denoise_frame(np.zeros((H, W, 12), F), np.zeros((H, W, 4), F), 1)
+        assert e.value.status == abi.HJ_ERR_INVALID and "hj_denoise_frame:" in str(e.value) and "1 ... 16384 each" in str(e.value), str(e.value)
 
 
 @pytest.mark.parametrize("sigmas", [(0.0, 1.0, 4.0, 0.1), (0.5, 0.0, 4.0, 0.1), (0.5, 1.0, 0.0, 0.1), (0.5, 1.0, 4.0, 0.0), (0.0, 0.0, 0.0, 0.0)])

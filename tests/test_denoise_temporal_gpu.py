@@ -13,7 +13,7 @@ import denoise_ref as D
 import path_query_ref as P
 import temporal_ref as T
 from hijiki_amd import abi, device, host
-from test_denoise_gpu import frame, same_bits
+from test_denoise_gpu import BIG, SIDE, big_frame, frame, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -157,6 +157,28 @@ def test_every_size_in_every_form(forms, size, step):
     for prev in ("identical", "translated"):
         got = forms[step].denoise_frame_temporal(frame(W, H)[1], CAM, PREV[prev], history(W, H), frame(W, H)[0], it)
         both(got, want(W, H, prev, it), f"{W} x {H}, {prev}, {it} iterations, HJ_DENOISE_LDS_STEP={step}")
+
+
+def test_lattice_tiles_beyond_one_a_residue_class(forms):
+    """test_denoise_gpu's 517 x 131 frame behind the temporal stage, the LDS form at every step: two lattice tiles a residue class
+    in both axes up to step 16, the temporal variance where the history is long enough"""
+    W, H = BIG
+    beauty, aov = big_frame()
+    out, hist, s = T.run(beauty, aov, CAM, PREV["translated"], history(W, H), 5, keep=True)
+    assert 10000 < s["has"].sum() < s["G"].sum() - 10000 and (s["N"][s["has"]] >= T.VARIANCE_FRAMES).sum() > 1000
+    assert s["has"][128:, 480:].any()                                   # (history found in the last tiles too)
+    both(forms["128"].denoise_frame_temporal(aov, CAM, PREV["translated"], history(W, H), beauty, 5), (out, hist), "517 x 131, translated, form 128")
+
+
+@pytest.mark.parametrize("size", SIDE)
+def test_the_side_limit(forms, size):
+    """16384 x 1 and 1 x 16384 with an identical camera pair: the accumulate and variance kernels at the side limit, then eight
+    iterations in the LDS form"""
+    W, H = size
+    beauty, aov = frame(W, H)
+    out, hist, s = T.run(beauty, aov, CAM, CAM, history(W, H), 8, keep=True)
+    assert np.isfinite(out).all() and np.isfinite(hist).all() and 1000 < s["has"].sum() < s["G"].sum() - 1000
+    both(forms["128"].denoise_frame_temporal(aov, CAM, CAM, history(W, H), beauty, 8), (out, hist), f"{W} x {H}, identical, form 128")
 
 
 @pytest.mark.parametrize("prev", sorted(PREV))

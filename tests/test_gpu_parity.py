@@ -1369,6 +1369,8 @@ def test_four_contexts_in_flight_on_one_gpu(cbox, monkeypatch):
     {"HJ_PAIR_LEAVES": "0", "HJ_STREAM_STATE": "1"},                # the plain-leaf instantiation with streamed state
     {"HJ_COLLAPSE_PCT": "0", "HJ_NODE_ORDER": "1"},                 # no collapse, sibling groups
     {"HJ_SLOTS": "1", "HJ_WG_PER_CU": "1", "batch_blocks": "1"},    # one batch slot, 256 workgroups, one ImageBlock per batch
+    {"HJ_GROUP_TILE": "1"},                                         # camera packets of 8 x 8 tiles, as a large tree's
+    {"HJ_GROUP_TILE": "1", "HJ_PAIR_LEAVES": "0", "HJ_STREAM_STATE": "1"},   # ... through the explicit top-up of the plain-leaf kernel
 ], ids=lambda e: ",".join(f"{k.replace('HJ_', '')}={v}" for k, v in e.items()))
 def test_tuning_switches_never_change_a_bit(oracle, cbox_spheres, monkeypatch, env):
     """DESIGN.md section 4's tuning switches (read by the library at context creation / scene upload) steer scheduling
@@ -1389,20 +1391,31 @@ def test_tuning_switches_never_change_a_bit(oracle, cbox_spheres, monkeypatch, e
     assert st["closest_rays"] == ctr["closest_calls"] and st["shadow_rays"] == ctr["shadow_calls"]
 
 
+_RAGGED_ROWS = {}
+
+
 @pytest.mark.gpu
-def test_small_pool_with_partial_block_rows(oracle, cbox_spheres, monkeypatch):
+@pytest.mark.parametrize("tile", [None, "1"], ids=["rows", "tiles"])
+def test_small_pool_with_partial_block_rows(oracle, cbox_spheres, monkeypatch, tile):
     """A pool of ONE 64-sample group per workgroup on a frame whose bottom block row is 3 pixels high: most top-ups of the
     workgroups that own that row append nothing (every sample of the group lies outside its block) and the round is skipped
     without a shade - the path through k_path_wavefront's `continue`, which must not find an older round's path count again
-    (samples would be shaded twice).  Mirror + glass + emitter scene, exact."""
+    (samples would be shaded twice).  Mirror + glass + emitter scene, exact.  With HJ_GROUP_TILE=1 a group is an 8 x 8 tile: in
+    the bottom block row (3 pixels high) it has 24 live lanes of 64, in the right block column (72 wide) whole tiles lie outside
+    the block."""
     monkeypatch.setenv("HJ_POOL", "64")
     monkeypatch.setenv("HJ_WG_PER_CU", "1")
+    monkeypatch.delenv("HJ_GROUP_TILE", raising=False)
+    if tile is not None:
+        monkeypatch.setenv("HJ_GROUP_TILE", tile)
     W, H = 200, 131
     blocks = host.make_blocks(W, H, 3, 17)
-    want, ctr, _ = oracle.render_blocks(cbox_spheres, blocks, W, H)
+    if not _RAGGED_ROWS:                                                # (the oracle's frame once for both groupings)
+        _RAGGED_ROWS["oracle"] = oracle.render_blocks(cbox_spheres, blocks, W, H)
+    want, ctr, _ = _RAGGED_ROWS["oracle"]
     with device.Renderer(0) as r:
         got, st = render(r, cbox_spheres, W, H, blocks)
-    assert_same(got, want, "pool 64, ragged rows")
+    assert_same(got, want, f"pool 64, ragged rows, HJ_GROUP_TILE={tile}")
     assert st["closest_rays"] == ctr["closest_calls"] and st["shadow_rays"] == ctr["shadow_calls"]
 
 

@@ -12,7 +12,7 @@ import motion_ref as M
 import temporal_ref as T
 from hijiki_amd import abi, device, host
 from refit_scenes import Deformation, refit_numpy, shape_boxes
-from test_denoise_gpu import frame, same_bits
+from test_denoise_gpu import BIG, big_frame, frame, same_bits
 from test_denoise_temporal_gpu import CAM, FORMS, PREV, forms, history   # noqa: F401  (forms: the fixture)
 
 pytestmark = pytest.mark.gpu
@@ -280,6 +280,16 @@ def test_temporal_motion_in_every_form(forms, size, step):            # noqa: F8
         if W * H > 2000:
             s = M.run(beauty, aov, m, history(W, H), 0, keep=True)[2]
             assert 100 < s["has"].sum() < s["G"].sum() - 100, name          # (taps pass and taps fail)
+
+
+def test_temporal_motion_with_lattice_tiles_beyond_one_a_residue_class(forms):       # noqa: F811
+    """test_denoise_gpu's 517 x 131 frame through a motion image, the LDS form at every step up to 16"""
+    W, H = BIG
+    beauty, aov = big_frame()
+    m = motions(W, H)["fractional"]
+    out, hist, s = M.run(beauty, aov, m, history(W, H), 5, keep=True)
+    assert 10000 < s["has"].sum() < s["G"].sum() - 10000 and s["has"][128:, 480:].any()
+    both(forms["128"].denoise_frame_temporal(aov, CAM, PREV["translated"], history(W, H), beauty, 5, motion=m), (out, hist), "517 x 131, fractional, form 128")
 
 
 def test_temporal_motion_anchors(forms):                               # noqa: F811
