@@ -1,7 +1,8 @@
 // Every environment switch of libhijiki_hip.so, in ONE table, read in ONE place (hjapi::Tuning::from_env): an entry point that
 // uses a switch reads the table once at its start and passes the struct down - no getenv anywhere else in the library.
-// None of the switches changes a result bit (tests/test_gpu_parity.py::test_tuning_switches_never_change_a_bit); the defaults
-// are the measured optima (DESIGN.md section 4 "Tuning switches", profiles/NOTES.md).  Plain C++: api/light_grid.cpp (g++) includes it too.
+// None of the switches changes a result bit (tests/test_gpu_parity.py::test_tuning_switches_never_change_a_bit on a frame,
+// tests/test_switch_matrix_gpu.py through every query and render call; tests/test_tuning_table_host.py demands a test for every
+// row added here); the defaults are the measured optima (DESIGN.md section 4 "Tuning switches", profiles/NOTES.md).  Plain C++: api/light_grid.cpp (g++) includes it too.
 #pragma once
 #include <algorithm>
 #include <cstdlib>

@@ -17,6 +17,9 @@ its own, the pairs one after the other); a few scenes (MATRIX_SCENES) under all 
   morton 64       HJ_LBVH_SAH=0 HJ_LBVH_CLUSTER=64         the same below a taller host top
   vote            HJ_LBVH_VOTE_PATHS=2000                  the exchange pass at the end of the build, over the wave kernel's records
   thread vote     ... HJ_LBVH_CLUSTER=64                   ... over the one-thread kernel's
+  top as built    HJ_LBVH_TOP_ROTATE=0                     the host's top without its rotation passes
+  top rotated     HJ_LBVH_TOP_ROTATE=64                    ... with as many as the table allows (by default 8 on tops below 4096 items)
+  timing          HJ_LBVH_TIMING=1                         the stage clocks' synchronisations between the kernels; times on stderr
 
 HJ_LBVH_VOTE_PATHS is 0 wherever it is not named (its default is 60000); HJ_LBVH_BIG_PCT is 0 on the blob scenes (nothing is "big")
 and the default elsewhere, with one big-shape scene also at 0."""
@@ -45,8 +48,12 @@ PAIRS = {
     "morton 64": {"HJ_LBVH_SAH": "0", "HJ_LBVH_CLUSTER": "64"},
     "vote": {"HJ_LBVH_VOTE_PATHS": "2000"},
     "thread vote": {"HJ_LBVH_VOTE_PATHS": "2000", "HJ_LBVH_CLUSTER": "64"},
+    "top as built": {"HJ_LBVH_TOP_ROTATE": "0"},
+    "top rotated": {"HJ_LBVH_TOP_ROTATE": "64"},
+    "timing": {"HJ_LBVH_TIMING": "1"},
 }
-DEFAULTS = {"HJ_LBVH_CLUSTER": "512", "HJ_LBVH_SAH": "1", "HJ_LBVH_VOTE_PATHS": "0", "HJ_BVH_CHILD_ORDER": "3"}
+DEFAULTS = {"HJ_LBVH_CLUSTER": "512", "HJ_LBVH_SAH": "1", "HJ_LBVH_VOTE_PATHS": "0", "HJ_BVH_CHILD_ORDER": "3", "HJ_LBVH_TOP_ROTATE": "-1",
+            "HJ_LBVH_TIMING": "0"}
 HOME_WAVE, HOME_THREAD = ("wave", "wave as split"), ("thread", "thread as split")
 HOME_SMALL = ("wave", "thread", "one cluster", "leaf clusters", "morton")
 
@@ -133,6 +140,20 @@ def test_build_and_refit(r, monkeypatch, key, pairs):
             assert both >= 1, pair
             side = 4 if key[1] == "upper" else 0
             assert built[0, side] == (E.POS_ZERO if key[1] == "upper" else E.NEG_ZERO), pair
+
+
+def test_top_rotation_takes_effect(r, monkeypatch):
+    """the premise of the two HJ_LBVH_TOP_ROTATE rows: with clusters of one or two leaves the host's top is most of the tree, and
+    its rotation passes move records of 520 random shapes - both trees valid, the same leaves, other links"""
+    key = _blob("random", 65, 520, 512)
+    cs = _scene(key)
+    built = {}
+    for passes in ("0", "64"):
+        with monkeypatch.context() as m:
+            _setenv(m, key, "pairs")
+            m.setenv("HJ_LBVH_TOP_ROTATE", passes)
+            built[passes] = _build_and_refit(r, m, cs)
+    assert built["0"].shape == built["64"].shape and (built["0"] != built["64"]).any(), "64 rotation passes left the top as it was built"
 
 
 @pytest.mark.parametrize("kind,n", E.ZERO_SCENES)
