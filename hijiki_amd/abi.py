@@ -63,6 +63,8 @@ MATERIALS_WORDS = 8               # words of a material record: albedo.rgb, mate
 MATERIAL_MISS = 0xFFFFFFFF        # ... its word 3 for a miss
 AOV_DEVICE_ARRAY = 1              # hj_render_aovs / hj_render_aovs_frame flag
 AOV_WORDS = 12                    # words of an AOV pixel: albedo.rgb, samples | normal.xyz, t | emission.rgb, hits - each a sum
+AOV_MAX_FOLLOW = 8                # hj_render_aovs_followed / hj_render_aovs_frame_followed: the most continuations of a chain
+FOLLOW_DEVICE_ARRAYS = 1          # hj_follow_specular flag
 DENOISE_DEVICE_ARRAYS = 1         # hj_denoise_opts flag
 DENOISE_MAX_ITERATIONS = 8        # hj_denoise_opts: iteration i uses the step 1 << i
 TEMPORAL_WORDS = 12               # words of a history record: I.rgb, N | m1, m2, z, valid word | n.xyz, 0

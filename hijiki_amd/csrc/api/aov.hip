@@ -9,6 +9,8 @@
 //               launch (k_aov_walk) may span several runs; behind it every run's part of it resolves in a launch of its own
 //               (k_aov_resolve), in order on the context's stream: inside a launch no two samples share a pixel, across launches
 //               the stream orders them - block order without an atomic.
+//   followed:   hj_render_aovs_followed, hj_render_aovs_frame_followed: the same checks, runs and camera walk; behind each walk launch
+//               the follow rounds and in k_aov_resolve's place the followed resolve, both api/follow.hip's (kernels/hj_follow.h)
 #include "hj_internal.h"
 #include "../kernels/hj_aov.h"
 
@@ -78,9 +80,11 @@ int aov_check(hj_context* ctx, const char* fn, const hj_image_block* blocks, siz
   return HJ_OK;
 }
 
-// Behind the checks and the gate: the image zeroed, then walk launches and their runs' resolves in list order.
+// Behind the checks and the gate: the image zeroed, then walk launches and their runs' resolves in list order.  max_follow > 0
+// (the followed calls): behind each walk launch the follow rounds of api/follow.hip, and a launch that took one resolves through its
+// resolve; max_follow == 0 enqueues exactly what it always did.
 int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags,
-               float* aov) {
+               float* aov, uint32_t max_follow = 0u) {
   HJ_HIP(ctx, hipSetDevice(ctx->device));
   const bool on_device = (flags & HJ_AOV_DEVICE_ARRAY) != 0;
   const size_t image_bytes = (size_t)width * height * HJ_AOV_WORDS * sizeof(float);
@@ -97,6 +101,7 @@ int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, si
   if (num_blocks != 0) {
     HJ_TRY(dev_alloc(ctx, q.blocks, num_blocks * sizeof(hj_image_block)));
     HJ_TRY(dev_alloc(ctx, q.hits, std::min(num_blocks, per_launch) * hj::kSlotsPerBlock * sizeof(float4)));
+    if (max_follow != 0) HJ_TRY(aov_follow_reserve(ctx, std::min(num_blocks, per_launch) * hj::kSlotsPerBlock));
     d_blocks = static_cast<const hj_image_block*>(q.blocks.p);
     d_hits = static_cast<float4*>(q.hits.p);
   }
@@ -115,13 +120,16 @@ int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, si
     if (sc.has_pairs != 0) hipLaunchKernelGGL(hj::k_aov_walk<true>, grid, blk, 0, s, sc, d_blocks + c0, nb, wg_rays, d_hits);
     else hipLaunchKernelGGL(hj::k_aov_walk<false>, grid, blk, 0, s, sc, d_blocks + c0, nb, wg_rays, d_hits);
     e = hipGetLastError();
+    bool followed = false;
+    if (e == hipSuccess && max_follow != 0) e = aov_follow_rounds(ctx, d_blocks + c0, nb, d_hits, max_follow, followed);
     // the parts of the runs that lie in [c0, c1), in order
     for (size_t at = c0; at < c1 && e == hipSuccess;) {
       while (ends[run] <= at) run++;
       const size_t to = std::min(c1, ends[run]);
       const uint32_t b0 = (uint32_t)(at - c0), cnt = (uint32_t)(to - at);
-      hipLaunchKernelGGL(hj::k_aov_resolve, per_lane(cnt * hj::kSlotsPerBlock), blk, 0, s, sc, d_blocks + c0, nb, b0, cnt,
-                         static_cast<const float4*>(d_hits), width, height, d_aov);
+      if (followed) aov_follow_resolve(ctx, d_blocks + c0, nb, b0, cnt, d_hits, width, height, d_aov);
+      else hipLaunchKernelGGL(hj::k_aov_resolve, per_lane(cnt * hj::kSlotsPerBlock), blk, 0, s, sc, d_blocks + c0, nb, b0, cnt,
+                              static_cast<const float4*>(d_hits), width, height, d_aov);
       e = hipGetLastError();
       at = to;
     }
@@ -162,21 +170,41 @@ int hj_render_aovs(hj_context* ctx, const hj_image_block* blocks, size_t num_blo
   return aov_render(ctx, __func__, blocks, num_blocks, width, height, flags, aov);
 }
 
-// The block list is hj_render_frame's for world == 1 (frame_blocks_append: one text for both), whole: 40 bytes a block.
-int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin, uint32_t pass_end,
-                         uint32_t flags, float* aov) {
-  HJ_TRY(aov_check(ctx, __func__, nullptr, 0, width, height, flags, aov));
-  if (pass_begin > pass_end || pass_end > spp) return set_error(ctx, HJ_ERR_INVALID, "hj_render_aovs_frame: bad pass range [%u,%u) of %u", pass_begin, pass_end, spp);
+// hj_render_aovs with the chains followed through at most max_follow specular surfaces (api/follow.hip); 0: hj_render_aovs' launches
+int hj_render_aovs_followed(hj_context* ctx, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t max_follow,
+                            uint32_t flags, float* aov) {
+  HJ_TRY(aov_check(ctx, __func__, blocks, num_blocks, width, height, flags, aov));
+  if (max_follow > HJ_AOV_MAX_FOLLOW) return set_error(ctx, HJ_ERR_INVALID, "%s: max_follow %u above %u", __func__, max_follow, (unsigned)HJ_AOV_MAX_FOLLOW);
   HJ_TRY(query_gate(ctx, __func__));
+  return aov_render(ctx, __func__, blocks, num_blocks, width, height, flags, aov, max_follow);
+}
+
+// The block list is hj_render_frame's for world == 1 (frame_blocks_append: one text for both), whole: 40 bytes a block.
+static int aov_render_frame(hj_context* ctx, const char* fn, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
+                            uint32_t pass_end, uint32_t max_follow, uint32_t flags, float* aov) {
+  HJ_TRY(aov_check(ctx, fn, nullptr, 0, width, height, flags, aov));
+  if (max_follow > HJ_AOV_MAX_FOLLOW) return set_error(ctx, HJ_ERR_INVALID, "%s: max_follow %u above %u", fn, max_follow, (unsigned)HJ_AOV_MAX_FOLLOW);
+  if (pass_begin > pass_end || pass_end > spp) return set_error(ctx, HJ_ERR_INVALID, "%s: bad pass range [%u,%u) of %u", fn, pass_begin, pass_end, spp);
+  HJ_TRY(query_gate(ctx, fn));
   std::vector<hj_image_block> blocks;
   try {
     const hijiki::BlockGrid grid(width, height, HJ_BLOCK_SIZE);
     blocks.reserve((size_t)(pass_end - pass_begin) * grid.per_pass());
     frame_blocks_append(grid, master_seed, pass_begin, pass_end, 0u, 1u, false, blocks);
   } catch (const std::bad_alloc&) {
-    return set_error(ctx, HJ_ERR_NOMEM, "hj_render_aovs_frame: no memory for the block list of %u passes", pass_end - pass_begin);
+    return set_error(ctx, HJ_ERR_NOMEM, "%s: no memory for the block list of %u passes", fn, pass_end - pass_begin);
   }
-  return aov_render(ctx, __func__, blocks.data(), blocks.size(), width, height, flags, aov);
+  return aov_render(ctx, fn, blocks.data(), blocks.size(), width, height, flags, aov, max_follow);
+}
+
+int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin, uint32_t pass_end,
+                         uint32_t flags, float* aov) {
+  return aov_render_frame(ctx, __func__, width, height, spp, master_seed, pass_begin, pass_end, 0u, flags, aov);
+}
+
+int hj_render_aovs_frame_followed(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
+                                  uint32_t pass_end, uint32_t max_follow, uint32_t flags, float* aov) {
+  return aov_render_frame(ctx, __func__, width, height, spp, master_seed, pass_begin, pass_end, max_follow, flags, aov);
 }
 
 }  // extern "C"

@@ -80,6 +80,11 @@
 //                         frame's albedo / normal / depth sums from its own primary rays (includes kernels/hj_aov.h, which includes
 //                         the kernel headers up to hj_stages.h and edits none: k_mat_eval; k_aov_walk, the persistent walk with a
 //                         fetch that builds the camera ray from the sample index; k_aov_resolve, run by run of disjoint blocks)
+//   api/follow.hip        hj_follow_specular, and the follow rounds of hj_render_aovs_followed / hj_render_aovs_frame_followed (whose entry
+//                         points, checks and camera walk are api/aov.hip's): the chain through mirror and glass as a deterministic
+//                         query (includes kernels/hj_follow.h, which includes hj_aov.h and hj_compact.h and edits none: k_follow;
+//                         k_af_count / k_af_scan / k_af_scatter, the live chains in order; k_aov_follow, the persistent walk with a
+//                         fetch that continues a chain from its state; k_aov_resolve_followed)
 //   api/denoise.hip       hj_denoise_frame: the variance-guided a-trous filter over a frame's albedo-demodulated light, guided by the
 //                         frame's AOV sums (includes kernels/hj_denoise.h and hj_num.h alone: k_dn_prepare, k_dn_variance, the
 //                         iteration as k_dn_filter_lds or k_dn_filter_direct, k_dn_finish); the checks, the buffers, the prepare
@@ -484,7 +489,9 @@ struct hj_context {
   // (16 bytes a sample slot, 16384 slots a block), the staging of a host-side AOV image (48 bytes a pixel); hj_eval_materials' staging
   // of host arrays - one chunk of hit records, surface records and material records (16, 64 and 32 bytes a record).  The sibling of
   // RayQuery: grown on demand, reused by every call, freed with the context.  Never the batch slots' or the framebuffer.
-  struct Aov { hjapi::DevBuf blocks, hits, image, in_hits, in_surface, out; } aov;
+  // hj_render_aovs_followed (api/follow.hip) adds, per sample slot of one walk launch, the chain state (32 bytes), the list of live
+  // slots (4 bytes) and a count per tile of 256; hj_follow_specular the staging of host-side rays in and out (32 bytes a record each).
+  struct Aov { hjapi::DevBuf blocks, hits, image, in_hits, in_surface, out, state, counts, list, in_rays, out_rays; } aov;
 
   // hj_denoise_frame (api/denoise.hip): the guide (48 bytes a pixel: normal and depth, albedo and valid word, depth slope) and the
   // two working images (16 bytes a pixel each); the staging of host arrays - beauty, AOV image, result (16, 48 and 16 bytes a
@@ -613,6 +620,13 @@ inline bool camera_ok(const hj_camera& c) {
     if (!std::isfinite(c.rotation[k])) return false;
   return std::isfinite(c.fov) && c.fov > 0.0f && c.fov < 180.0f;
 }
+// api/follow.hip, for api/aov.hip's aov_render with max_follow > 0: room for walk launches of at most `slots` sample slots; the follow
+// rounds behind a walk launch of nb blocks (-> followed: a round ran and the launch's runs resolve through aov_follow_resolve); and
+// that resolve's launch for blocks [b0, b0 + cnt) of the launch
+int aov_follow_reserve(hj_context* ctx, size_t slots);
+hipError_t aov_follow_rounds(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, float4* d_hits, uint32_t max_follow, bool& followed);
+void aov_follow_resolve(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, uint32_t b0, uint32_t cnt, const float4* d_hits, uint32_t width,
+                        uint32_t height, float4* d_aov);
 }  // namespace hjapi
 namespace hj { struct DtArgs; }                  // kernels/hj_denoise_temporal.h
 namespace hjapi {

@@ -3,7 +3,7 @@
 //   hijiki-hip [--put-cbox-spheres] [--use-bvh] [-w/--width 800] [-h/--height 600] [--present-interval 128]
 //              [-s/--sample-count 64] [-o/--output-image /tmp/output.exr] [--seed 1] [--textures] [--env FILE [--env-scale S]]
 //              [--bake-lightmap WxH [--gutter 2] [--filter N[,sp[,sn[,sc]]]] [--adaptive min,step,max,rel[,floor]] [--sample-map FILE]]
-//              [--aovs PREFIX] [--denoise FILE [--denoise-params iters,sn,sz,sl,sa]] <scene.obj | synthetic:KIND>
+//              [--aovs PREFIX [--aov-follow N]] [--denoise FILE [--denoise-params iters,sn,sz,sl,sa]] <scene.obj | synthetic:KIND>
 //
 // Same flags and defaults (including `-h` meaning height and brute-force traversal unless --use-bvh).  There is
 // no preview window, so --present-interval is accepted and ignored; --seed replaces the OS-seeded block RNG; --textures (not
@@ -19,6 +19,7 @@
 // --aovs PREFIX (not upstream) writes, beside the frame, PREFIX_albedo.pfm, PREFIX_normal.pfm and PREFIX_depth.pfm (the depth in all
 // three channels): hj_render_aovs_frame for the frame's own -s and --seed, its sums divided by the sample count (albedo) or the hit
 // count (normal, depth), 0 where the count is 0.
+// --aov-follow N (not upstream, with --aovs) follows mirror and glass through up to N specular surfaces: hj_render_aovs_frame_followed.
 // --denoise FILE (not upstream) writes, beside the frame, the frame denoised: hj_render_aovs_frame for the frame's own -s and --seed,
 // then hj_denoise_frame over the framebuffer on the device (beauty = NULL); the rgb goes to FILE through the writer its extension
 // chooses.  --denoise-params iters,sn,sz,sl,sa: the iterations (5) and the sigmas of normal (0.5), depth (1), luminance (4) and
@@ -53,6 +54,8 @@ struct Opt {
   bool adaptive_given = false, samples_given = false;      // (samples_given: -s was on the command line)
   std::string sample_map;                                  // --sample-map FILE
   std::string aovs;                                        // --aovs PREFIX
+  uint32_t aov_follow = 0;                                 // --aov-follow N: mirror and glass followed through N surfaces
+  bool aov_follow_given = false;
   std::string denoise;                                     // --denoise FILE
   hj_denoise_opts denoise_opts{5u, 0.5f, 1.0f, 4.0f, 0.1f, 0u};   // --denoise-params iters,sn,sz,sl,sa
   bool denoise_params_given = false;
@@ -80,6 +83,8 @@ struct Opt {
                "        --aovs <prefix>                          (not upstream) beside the frame: <prefix>_albedo.pfm, <prefix>_normal.pfm and\n"
                "                                                 <prefix>_depth.pfm - the means over the frame's own primary rays of the first\n"
                "                                                 hit's albedo, shading normal and distance (0 where nothing was hit)\n"
+               "        --aov-follow <n>                         (not upstream) with --aovs: mirror and glass are followed through up to n\n"
+               "                                                 (0 ... 8) specular surfaces and show what they show [default: 0]\n"
                "        --denoise <file>                         (not upstream) beside the frame: the frame denoised by the AOV-guided a-trous\n"
                "                                                 filter (.exr, .pfm or .png)\n"
                "        --denoise-params <iters>,<sn>,<sz>,<sl>,<sa>  (not upstream) iterations 0 ... 8 [5] and the sigmas of normal [0.5], depth [1],\n"
@@ -160,6 +165,15 @@ Opt parse(int argc, char** argv) {
     }
     else if (a == "--sample-map") o.sample_map = value(i);
     else if (a == "--aovs") o.aovs = value(i);
+    else if (a == "--aov-follow") {
+      const std::string v = value(i);
+      unsigned n = 0;
+      char tail = 0;
+      if (std::sscanf(v.c_str(), "%u%c", &n, &tail) != 1 || v.find_first_not_of("0123456789") != std::string::npos || n > HJ_AOV_MAX_FOLLOW)
+        usage(("bad --aov-follow " + v + " (0 ... 8)").c_str());
+      o.aov_follow = n;
+      o.aov_follow_given = true;
+    }
     else if (a == "--denoise") o.denoise = value(i);
     else if (a == "--denoise-params") {
       const std::string v = value(i);
@@ -185,6 +199,7 @@ Opt parse(int argc, char** argv) {
   if (o.adaptive_given && o.bake_w == 0) usage("--adaptive without --bake-lightmap");
   if (!o.sample_map.empty() && !o.adaptive_given) usage("--sample-map without --adaptive");
   if (!o.aovs.empty() && o.bake_w != 0) usage("--aovs belongs to a frame, not to --bake-lightmap");
+  if (o.aov_follow_given && o.aovs.empty()) usage("--aov-follow without --aovs");
   if (!o.denoise.empty() && o.bake_w != 0) usage("--denoise belongs to a frame, not to --bake-lightmap");
   if (o.denoise_params_given && o.denoise.empty()) usage("--denoise-params without --denoise");
   if (o.adaptive_given && o.samples_given) std::fprintf(stderr, "note: --adaptive decides the samples per texel; -s %u is ignored\n", o.sample_count);
@@ -327,7 +342,8 @@ int main(int argc, char** argv) {
       // albedo over the sample count, normal and depth over the hit count, 0 where the count is 0
       const size_t px = (size_t)opt.width * opt.height;
       std::vector<float> aov(px * HJ_AOV_WORDS), albedo(px * 3), normal(px * 3), depth(px * 3);
-      check(ctx, hj_render_aovs_frame(ctx, opt.width, opt.height, opt.sample_count, opt.seed, 0, opt.sample_count, 0u, aov.data()), "AOVs");
+      check(ctx, hj_render_aovs_frame_followed(ctx, opt.width, opt.height, opt.sample_count, opt.seed, 0, opt.sample_count, opt.aov_follow, 0u, aov.data()),
+            "AOVs");
       for (size_t i = 0; i < px; i++) {
         const float* a = &aov[i * HJ_AOV_WORDS];
         const float samples = a[3], hits = a[11];

@@ -37,6 +37,7 @@ HJ_DEV void eval_material(const DeviceScene& sc, uint32_t id, float u, float v, 
   }
 }
 
+#ifndef HJ_AOV_NO_KERNELS   // (kernels/hj_follow.h takes the functions and brings kernels of its own)
 // hits: hj_trace_rays' records (objectID bits, t, u, v); surface: its four float4 per ray (u, v = words 6, 7).  out: two float4
 // per record = albedo.rgb, material word bits | emission.rgb, 0.  The word comes from the scene by id, never from the surface
 // record: a miss's all-zero record would read as "diffuse, index 0".
@@ -58,6 +59,8 @@ __global__ __launch_bounds__(kBlockThreads) void k_mat_eval(DeviceScene sc, cons
   out[2 * (size_t)i + 1] = o1;
 }
 
+#endif  // HJ_AOV_NO_KERNELS
+
 // The blocks of a launch as camera_ray reads them: it touches blocks and num_blocks of the batch (and the scene's camera), and
 // group_sample the scene's group_tile, nothing else.
 HJ_DEV BatchState aov_batch(const hj_image_block* blocks, uint32_t num_blocks) {
@@ -67,6 +70,7 @@ HJ_DEV BatchState aov_batch(const hj_image_block* blocks, uint32_t num_blocks) {
   return st;
 }
 
+#ifndef HJ_AOV_NO_KERNELS
 // Sample slots [0, n = num_blocks * kSlotsPerBlock) of the launch's blocks.  Workgroup g walks queue entries [g * wg_rays, ...) as
 // k_rq_walk's does; entry i is lane i & 63 of 64-sample group i >> 6 (group_sample: a block row's 64 pixels, or an 8 x 8 tile over
 // a large tree - the grouping the camera packets use, a bijection of the slots either way), and its hit record (objectID bits, t,
@@ -106,11 +110,56 @@ __global__ __launch_bounds__(kBlockThreads) void k_aov_walk(DeviceScene sc, cons
   trace_persistent<0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
 }
 
+#endif  // HJ_AOV_NO_KERNELS
+
+// The 12-word record of a sample whose ray (o, d) ended in hit record hr (objectID bits, t, u, v): the hit populated as the shade
+// stage populates it (hit point fma(t, d, o), scene.glsl:164), the material evaluated by eval_material -> albedo.rgb, 1 | n.xyz, t |
+// emission.rgb, 1; a miss (an id outside the scene): 0, 0, 0, 1 and eight zeros.  ONE text for k_aov_resolve and the followed
+// resolve of kernels/hj_follow.h.  -> a hit
+HJ_DEV bool aov_record(const DeviceScene& sc, v3 o, v3 d, float4 hr, float4& r0, float4& r1, float4& r2) {
+  const uint32_t id = __float_as_uint(hr.x);
+  r0 = make_float4(0.f, 0.f, 0.f, 1.f);
+  r1 = make_float4(0.f, 0.f, 0.f, 0.f);
+  r2 = r1;
+  if (id >= sc.ns + sc.nq + sc.nt) return false;
+  Its its;
+  its.p = V(fmaf(hr.y, d.x, o.x), fmaf(hr.y, d.y, o.y), fmaf(hr.y, d.z, o.z));
+  if (id < sc.ns) populate_sphere(sc.spheres[id], its);
+  else if (id < sc.ns + sc.nq) populate_quad(sc, id - sc.ns, hr.z, hr.w, its);
+  else populate_triangle(sc, id - sc.ns - sc.nq, hr.z, hr.w, its);
+  v3 albedo, emission;
+  uint32_t word;
+  eval_material(sc, id, its.u, its.v, albedo, emission, word);
+  r0 = make_float4(albedo.x, albedo.y, albedo.z, 1.f);
+  r1 = make_float4(its.n.x, its.n.y, its.n.z, hr.y);
+  r2 = make_float4(emission.x, emission.y, emission.z, 1.f);
+  return true;
+}
+
+// The pixel (origin + l) of sample slot smp, a sample camera_ray has accepted -> false outside width x height (no wrap-around)
+HJ_DEV bool aov_pixel(const hj_image_block* __restrict__ blocks, uint32_t smp, uint32_t width, uint32_t height, uint32_t& px, uint32_t& py) {
+  const hj_image_block b = blocks[smp / kSlotsPerBlock];
+  const uint32_t lx = smp & (HJ_BLOCK_SIZE - 1u), ly = (smp / HJ_BLOCK_SIZE) & (HJ_BLOCK_SIZE - 1u);
+  if (b.origin[0] >= width || lx >= width - b.origin[0] || b.origin[1] >= height || ly >= height - b.origin[1]) return false;
+  px = b.origin[0] + lx;
+  py = b.origin[1] + ly;
+  return true;
+}
+
+// The record added to pixel p's three float4: a read-add-write, which races with nothing inside a run
+HJ_DEV void aov_add(float4* __restrict__ p, float4 r0, float4 r1, float4 r2) {
+  float4 a0 = p[0], a1 = p[1], a2 = p[2];
+  a0.x += r0.x; a0.y += r0.y; a0.z += r0.z; a0.w += r0.w;
+  a1.x += r1.x; a1.y += r1.y; a1.z += r1.z; a1.w += r1.w;
+  a2.x += r2.x; a2.y += r2.y; a2.z += r2.z; a2.w += r2.w;
+  p[0] = a0; p[1] = a1; p[2] = a2;
+}
+
+#ifndef HJ_AOV_NO_KERNELS
 // A RUN: blocks [b0, b0 + nb) of the launch's block list, whose pixel rectangles are pairwise disjoint (the host cuts the list so),
 // so every pixel gets at most one sample of this launch and the read-add-write below races with nothing.  One lane per sample slot:
-// the ray is rebuilt (camera_ray), the hit populated as the shade stage populates it (hit point fma(t, d, o), scene.glsl:164), the
-// material evaluated by eval_material, and the record (albedo.rgb, 1 | n.xyz, t | emission.rgb, hit ? 1 : 0; a miss: 0, 0, 0, 1 and
-// eight zeros) added to pixel (origin + l) of aov, 12 floats a pixel.  A pixel outside width x height is not written.
+// the ray is rebuilt (camera_ray) and the record (aov_record: albedo.rgb, 1 | n.xyz, t | emission.rgb, hit ? 1 : 0; a miss: 0, 0, 0,
+// 1 and eight zeros) added to pixel (origin + l) of aov, 12 floats a pixel.  A pixel outside width x height is not written.
 __global__ __launch_bounds__(kBlockThreads) void k_aov_resolve(DeviceScene sc, const hj_image_block* __restrict__ blocks, uint32_t num_blocks,
                                                                uint32_t b0, uint32_t nb, const float4* __restrict__ hits, uint32_t width,
                                                                uint32_t height, float4* __restrict__ aov) {
@@ -121,33 +170,13 @@ __global__ __launch_bounds__(kBlockThreads) void k_aov_resolve(DeviceScene sc, c
   uint32_t rng_unused = 0;
   v3 d = V(0.f, 0.f, 0.f);
   if (!camera_ray(st, sc, smp, rng_unused, d)) return;
-  const hj_image_block b = blocks[smp / kSlotsPerBlock];
-  const uint32_t lx = smp & (HJ_BLOCK_SIZE - 1u), ly = (smp / HJ_BLOCK_SIZE) & (HJ_BLOCK_SIZE - 1u);
-  if (b.origin[0] >= width || lx >= width - b.origin[0] || b.origin[1] >= height || ly >= height - b.origin[1]) return;   // (no wrap-around)
-  const uint32_t px = b.origin[0] + lx, py = b.origin[1] + ly;
-  const float4 hr = hits[smp];
-  const uint32_t id = __float_as_uint(hr.x);
-  float4 r0 = make_float4(0.f, 0.f, 0.f, 1.f), r1 = make_float4(0.f, 0.f, 0.f, 0.f), r2 = r1;
-  if (id < sc.ns + sc.nq + sc.nt) {
-    const v3 o = V(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
-    Its its;
-    its.p = V(fmaf(hr.y, d.x, o.x), fmaf(hr.y, d.y, o.y), fmaf(hr.y, d.z, o.z));
-    if (id < sc.ns) populate_sphere(sc.spheres[id], its);
-    else if (id < sc.ns + sc.nq) populate_quad(sc, id - sc.ns, hr.z, hr.w, its);
-    else populate_triangle(sc, id - sc.ns - sc.nq, hr.z, hr.w, its);
-    v3 albedo, emission;
-    uint32_t word;
-    eval_material(sc, id, its.u, its.v, albedo, emission, word);
-    r0 = make_float4(albedo.x, albedo.y, albedo.z, 1.f);
-    r1 = make_float4(its.n.x, its.n.y, its.n.z, hr.y);
-    r2 = make_float4(emission.x, emission.y, emission.z, 1.f);
-  }
-  float4* __restrict__ p = aov + 3 * ((size_t)py * width + px);
-  float4 a0 = p[0], a1 = p[1], a2 = p[2];
-  a0.x += r0.x; a0.y += r0.y; a0.z += r0.z; a0.w += r0.w;
-  a1.x += r1.x; a1.y += r1.y; a1.z += r1.z; a1.w += r1.w;
-  a2.x += r2.x; a2.y += r2.y; a2.z += r2.z; a2.w += r2.w;
-  p[0] = a0; p[1] = a1; p[2] = a2;
+  uint32_t px, py;
+  if (!aov_pixel(blocks, smp, width, height, px, py)) return;
+  float4 r0, r1, r2;
+  (void)aov_record(sc, V(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]), d, hits[smp], r0, r1, r2);
+  aov_add(aov + 3 * ((size_t)py * width + px), r0, r1, r2);
 }
+
+#endif  // HJ_AOV_NO_KERNELS
 
 }  // namespace hj

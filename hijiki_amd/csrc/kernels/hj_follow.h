@@ -1,0 +1,210 @@
+// Followed AOVs and the specular continuation ("Followed AOVs"; include/hijiki_hip.h hj_follow_specular,
+// hj_render_aovs_followed): what a mirror or glass SHOWS - the chain through specular surfaces that the path kernel takes, as a
+// deterministic query.  The functions a hit needs are the shade stage's - populate_*, reflect3 - and kernels/hj_aov.h's (aov_record,
+// eval_material behind it), included here and edited nowhere: this header adds the continuation (follow_continue, ONE text for the
+// per-record query and the frame kernel) and the kernels around it.  No global atomics, no inline assembly of its own.
+//   k_follow                 one lane per (ray, hit) record pair of hj_trace_rays: the continued ray, or the empty ray
+//   k_af_count / _scan / _scatter   the live chains of a walk launch's sample slots, in slot order, as a list (kernels/hj_compact.h's
+//                            tile compaction); the first round's scatter also sets every sample's chain state from its camera ray
+//   k_aov_follow<PAIRS>      one round: the persistent walk over the list with a fetch that continues a chain from its state and last
+//                            hit - no ray array exists - and a finish that stores the new hit
+//   k_aov_resolve_followed   k_aov_resolve with the chain's last segment in place of the camera ray (aov_record: one text of the record)
+// The chain state of a sample slot, two float4 beside its hit record: (segment origin.xyz, depth so far) (segment direction.xyz,
+// continuations taken as bits).
+#pragma once
+#define HJ_AOV_NO_KERNELS   // the functions of hj_aov.h, no kernel of its: api/aov.hip holds those
+#include "hj_aov.h"
+#include "hj_compact.h"
+
+#pragma clang fp contract(off)
+
+namespace hj {
+
+constexpr uint32_t kAfThreads = 256u;               // threads of a k_af_* workgroup: a compaction tile
+constexpr uint32_t kFollowLeft = 0xFFFFFFFEu;       // word 0 of a hit record whose chain left a specular surface and hit nothing:
+                                                    // words 1..3 hold that surface's normal (no shape id: a miss to everything else)
+static_assert(kSlotsPerBlock % kAfThreads == 0, "a launch's sample slots are whole tiles");
+
+// The ray (o, d) hit the scene at hr (objectID bits, t, u, v).  Does its chain go on, and with which ray?  Hit point and populate
+// as stage_shade has them (hj_stages.h:506-510); the material word from the scene by id.  A mirror reflects about the stored normal;
+// a dielectric takes the expressions of hj_stages.h:560-583 word for word, and in place of the random draw the branch the path kernel
+// takes more often than not: reflect when k <= 0 or fr >= 0.5f, else refract (direction not normalised, as the reference leaves
+// it).  Every other tag, a miss, an id outside the scene: false, nothing written.  -> p: the hit point, the next origin; wo: the next
+// direction; n: the surface's shading normal
+HJ_DEV bool follow_continue(const DeviceScene& sc, v3 o, v3 d, float4 hr, v3& p, v3& wo, v3& n) {
+  const uint32_t id = __float_as_uint(hr.x);
+  if (id >= sc.ns + sc.nq + sc.nt) return false;
+  const uint32_t mat = sc.materials[id];
+  const uint32_t tag = mat >> HJ_MATERIAL_TAG_SHIFT, midx = mat & HJ_MATERIAL_INDEX_MASK;
+  if (tag != HJ_MAT_MIRROR && tag != HJ_MAT_DIELECTRIC) return false;
+  Its its;
+  its.p = V(fmaf(hr.y, d.x, o.x), fmaf(hr.y, d.y, o.y), fmaf(hr.y, d.z, o.z));   // scene.glsl:164
+  if (id < sc.ns) populate_sphere(sc.spheres[id], its);
+  else if (id < sc.ns + sc.nq) populate_quad(sc, id - sc.ns, hr.z, hr.w, its);
+  else populate_triangle(sc, id - sc.ns - sc.nq, hr.z, hr.w, its);
+  p = its.p;
+  n = its.n;
+  if (tag == HJ_MAT_MIRROR) {
+    wo = reflect3(d, its.n);
+    return true;
+  }
+  const float4 m = sc.dielectric[midx];                                            // material.glsl:50-87
+  float eta = m.w;
+  float etaInv = 1.0f / eta;
+  float cosI = -dot3(its.n, d);
+  v3 normal = its.n;
+  if (cosI < 0.0f) { eta = etaInv; etaInv = 1.0f / eta; normal = -normal; cosI = -cosI; }
+  const float k = 1.0f - (etaInv * etaInv) * (1.0f - cosI * cosI);
+  bool reflect = k <= 0.0f;
+  float cosO = 0.0f;
+  if (!reflect) {
+    cosO = __builtin_sqrtf(k);
+    const float rpar = (eta * cosI - cosO) / (eta * cosI + cosO);
+    const float rorth = (cosI - eta * cosO) / (cosI + eta * cosO);
+    const float fr = 0.5f * (rpar * rpar + rorth * rorth);
+    reflect = fr >= 0.5f;
+  }
+  if (reflect) {
+    wo = reflect3(d, normal);
+  } else {
+    const v3 par = d - normal * dot3(d, normal);
+    wo = par * etaInv - normal * cosO;
+  }
+  return true;
+}
+
+// rays: two float4 per record (origin.xyz, direction.x | direction.yz, tMin, tMax), hits: (objectID bits, t, u, v) - hj_trace_rays'
+// arrays.  out: the continued ray (p, wo, tMin = eps, tMax = +inf: the next segment of a path), or where the chain ends the empty ray
+// (zeros, tMin = +inf, tMax = -inf).
+__global__ __launch_bounds__(kBlockThreads) void k_follow(DeviceScene sc, const float4* __restrict__ rays, const float4* __restrict__ hits, uint32_t n,
+                                                          float4* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];
+  float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = make_float4(0.f, 0.f, kInf, -kInf);
+  v3 p, wo, nrm;
+  if (follow_continue(sc, V(a.x, a.y, a.z), V(a.w, b.x, b.y), hits[i], p, wo, nrm)) {
+    o0 = make_float4(p.x, p.y, p.z, wo.x);
+    o1 = make_float4(wo.y, wo.z, kEps, kInf);
+  }
+  out[2 * (size_t)i] = o0;
+  out[2 * (size_t)i + 1] = o1;
+}
+
+// Is the chain of sample slot `slot` (< n) live: its last hit on a mirror or a dielectric, fewer than max_follow continuations taken?
+// FIRST: behind the camera walk no state exists yet and no continuation has been taken.
+template <bool FIRST>
+HJ_DEV bool follow_live(const DeviceScene& sc, const float4* __restrict__ hits, const float4* __restrict__ state, uint32_t slot, uint32_t n,
+                        uint32_t max_follow) {
+  if (slot >= n) return false;
+  const uint32_t id = __float_as_uint(hits[slot].x);
+  if (id >= sc.ns + sc.nq + sc.nt) return false;                  // (a miss, kFollowLeft)
+  const uint32_t tag = sc.materials[id] >> HJ_MATERIAL_TAG_SHIFT;
+  if (tag != HJ_MAT_MIRROR && tag != HJ_MAT_DIELECTRIC) return false;
+  return FIRST || __float_as_uint(state[2 * (size_t)slot + 1].w) < max_follow;
+}
+
+// The live slots of a launch's n sample slots in ascending order -> list.  Tiles of kAfThreads slots; counts: a word per tile and the
+// total behind them (the host reads it: it sizes the round's grid).
+template <bool FIRST>
+__global__ __launch_bounds__(kAfThreads) void k_af_count(DeviceScene sc, const float4* __restrict__ hits, const float4* __restrict__ state, uint32_t n,
+                                                         uint32_t max_follow, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t wave_cnt[kAfThreads / 64u];
+  (void)compact_wave_counts(follow_live<FIRST>(sc, hits, state, blockIdx.x * kAfThreads + threadIdx.x, n, max_follow), wave_cnt);
+  if (threadIdx.x == 0) counts[blockIdx.x] = compact_tile_count<kAfThreads>(wave_cnt);
+}
+
+__global__ __launch_bounds__(kAfThreads) void k_af_scan(uint32_t* __restrict__ counts, uint32_t nb) { compact_scan_tiles<kAfThreads>(counts, nb); }
+
+// FIRST: every slot with a sample (camera_ray says so) also gets its chain state - the camera ray, depth 0, no continuation -, so the
+// followed resolve reads one kind of record for every sample of the launch.
+template <bool FIRST>
+__global__ __launch_bounds__(kAfThreads) void k_af_scatter(DeviceScene sc, const hj_image_block* __restrict__ blocks, uint32_t num_blocks,
+                                                           const float4* __restrict__ hits, float4* __restrict__ state, uint32_t n, uint32_t max_follow,
+                                                           const uint32_t* __restrict__ offsets, uint32_t* __restrict__ list) {
+  __shared__ uint32_t wave_cnt[kAfThreads / 64u];
+  const uint32_t slot = blockIdx.x * kAfThreads + threadIdx.x;
+  if (FIRST && slot < n) {
+    const BatchState st = aov_batch(blocks, num_blocks);
+    uint32_t rng_unused = 0;
+    v3 d = V(0.f, 0.f, 0.f);
+    if (camera_ray(st, sc, slot, rng_unused, d)) {
+      state[2 * (size_t)slot] = make_float4(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2], 0.f);
+      state[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(0u));
+    }
+  }
+  const bool keep = follow_live<FIRST>(sc, hits, state, slot, n, max_follow);
+  const unsigned long long mask = compact_wave_counts(keep, wave_cnt);
+  if (!keep) return;
+  HJ_COMPACT_RANK(pos, offsets[blockIdx.x], wave_cnt, mask);
+  list[pos] = slot;
+}
+
+// One round over the `count` live slots of list.  Workgroup g walks list entries [g * wg_rays, ...) as k_aov_walk's walks its queue
+// entries.  fetch: the chain's state and last hit -> follow_continue -> the walk's ray (p, wo, eps, +inf); the state becomes the new
+// segment's (p, depth + t | wo, continuations + 1) and the hit record (kFollowLeft, n) - what the resolve needs of the surface that
+// was left should the new segment hit nothing.  The walk's finish hook sees the hit and not the ray, so the segment is stored here,
+// in the service phase, where the walk issues its stores anyway.  finish: a hit replaces the record; a miss leaves it.  A slot is
+// in the list once, so one lane reads and writes its records; which lane or workgroup carried a chain shows in no result.
+template <bool PAIRS>
+__global__ __launch_bounds__(kBlockThreads) void k_aov_follow(DeviceScene sc, const uint32_t* __restrict__ list, uint32_t count, uint32_t wg_rays,
+                                                              float4* __restrict__ hits, float4* __restrict__ state) {
+  __shared__ WgShared sh;
+  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(count / wg_rays): first < count)
+  const uint32_t cnt = count - first < wg_rays ? count - first : wg_rays;
+  if (threadIdx.x == 0) sh.head = 0;
+  load_hot_nodes(sc, sh);
+  __syncthreads();
+  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
+    slot = list[first + i];
+    any = false;
+    const float4 s0 = state[2 * (size_t)slot], s1 = state[2 * (size_t)slot + 1];
+    const float4 hr = hits[slot];
+    v3 p = V(0.f, 0.f, 0.f), wo = p, nrm = p;
+    const bool go = follow_continue(sc, xyz(s0), xyz(s1), hr, p, wo, nrm);   // (true for every entry the scatter listed)
+    r.o = p;
+    r.d = wo;
+    r.tmin = go ? kEps : kInf;                                     // render.glsl:33
+    r.tmax = go ? kInf : -kInf;
+    if (go) {
+      state[2 * (size_t)slot] = make_float4(p.x, p.y, p.z, s0.w + hr.y);
+      state[2 * (size_t)slot + 1] = make_float4(wo.x, wo.y, wo.z, __uint_as_float(__float_as_uint(s1.w) + 1u));
+      hits[slot] = make_float4(__uint_as_float(kFollowLeft), nrm.x, nrm.y, nrm.z);
+    }
+    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
+  };
+  auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
+    if (done && h.id >= 0) hits[slot] = make_float4(__int_as_float(h.id), h.t, h.u, h.v);
+  };
+  trace_persistent<0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+}
+
+// k_aov_resolve over a run whose launch was followed: the sample's record is the record of its chain's last hit - aov_record over
+// the chain's last segment, the depth word the float32 sum of the chain's t values in chain order -, and for a chain that left a
+// specular surface and hit nothing the record of that surface: albedo 1, its normal, the sum so far, hit 1.
+__global__ __launch_bounds__(kBlockThreads) void k_aov_resolve_followed(DeviceScene sc, const hj_image_block* __restrict__ blocks, uint32_t num_blocks,
+                                                                        uint32_t b0, uint32_t nb, const float4* __restrict__ hits,
+                                                                        const float4* __restrict__ state, uint32_t width, uint32_t height,
+                                                                        float4* __restrict__ aov) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nb * kSlotsPerBlock) return;
+  const uint32_t smp = b0 * kSlotsPerBlock + j;
+  const BatchState st = aov_batch(blocks, num_blocks);
+  uint32_t rng_unused = 0;
+  v3 d = V(0.f, 0.f, 0.f);
+  if (!camera_ray(st, sc, smp, rng_unused, d)) return;
+  uint32_t px, py;
+  if (!aov_pixel(blocks, smp, width, height, px, py)) return;
+  const float4 hr = hits[smp], s0 = state[2 * (size_t)smp], s1 = state[2 * (size_t)smp + 1];
+  float4 r0, r1, r2;
+  if (__float_as_uint(hr.x) == kFollowLeft) {
+    r0 = make_float4(1.f, 1.f, 1.f, 1.f);
+    r1 = make_float4(hr.y, hr.z, hr.w, s0.w);
+    r2 = make_float4(0.f, 0.f, 0.f, 1.f);
+  } else if (aov_record(sc, xyz(s0), xyz(s1), hr, r0, r1, r2)) {
+    r1.w = s0.w + hr.y;
+  }
+  aov_add(aov + 3 * ((size_t)py * width + px), r0, r1, r2);
+}
+
+}  // namespace hj

@@ -32,7 +32,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_bake_probe_visibility", "hj_sample_probes_visible", "hj_update_probes", "hj_update_probe_visibility", "hj_place_probes",
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
            "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame",
-           "hj_denoise_frame", "hj_denoise_frame_temporal", "hj_render_motion", "hj_denoise_frame_temporal_motion")
+           "hj_denoise_frame", "hj_denoise_frame_temporal", "hj_render_motion", "hj_denoise_frame_temporal_motion",
+           "hj_follow_specular", "hj_render_aovs_followed", "hj_render_aovs_frame_followed")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -125,6 +126,9 @@ def lib():
         L.hj_eval_materials.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]                     # (host or device pointers)
         L.hj_render_aovs.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_render_aovs_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.hj_follow_specular.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]                    # (host or device pointers)
+        L.hj_render_aovs_followed.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.hj_render_aovs_frame_followed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_denoise_frame.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), vp]   # (host or device pointers)
         L.hj_denoise_frame_temporal.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp]
         L.hj_denoise_frame_temporal_motion.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp, vp]
@@ -752,15 +756,45 @@ class Renderer:
         self._check(lib().hj_eval_materials(self._h, hits.ctypes.data, surface.ctypes.data, n, 0, out.ctypes.data))
         return out
 
-    def render_aovs(self, width, height, blocks=None, spp=None, master_seed=0, passes=None, device=False):
+    def follow_specular(self, rays, hits):
+        """hj_follow_specular: the specular continuation of n rays at their hits -> (n, 8) float32 rays in `trace_rays`' layout: where
+        the hit is a mirror or a dielectric the next segment of the chain (hit point, reflected or refracted direction, tMin = eps,
+        tMax = inf - a dielectric reflects when k <= 0 or fr >= 0.5, else refracts: no random draw), elsewhere - another material, a
+        miss - the empty ray (zeros, tMin = inf, tMax = -inf), which `trace_rays` answers with a miss.  rays (n, 8) and hits (n, 4) are
+        hj_trace_rays' arrays (stack ids.view(float32), t, u, v).  Alternated with `trace_rays` it gives the chains of
+        `render_aovs(..., follow=N)`.  Arrays and tensors as for `eval_materials`."""
+        rays, is_torch = self._query_input("follow_specular", rays, 8)
+        hits, hits_torch = self._query_input("follow_specular", hits, 4)
+        if is_torch != hits_torch or rays.shape[0] != hits.shape[0]:
+            raise ValueError(f"follow_specular: rays {tuple(rays.shape)} and hits {tuple(hits.shape)} must be n records of one kind (arrays or tensors)")
+        n = rays.shape[0]
+        if is_torch:
+            import torch
+            out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+            torch.cuda.current_stream(rays.device).synchronize()      # (the allocation and whatever wrote the inputs)
+            self._check(lib().hj_follow_specular(self._h, rays.data_ptr() if n else None, hits.data_ptr() if n else None, n,
+                                                 abi.FOLLOW_DEVICE_ARRAYS, out.data_ptr() if n else None))
+            return out
+        out = np.zeros((n, 8), np.float32)
+        self._check(lib().hj_follow_specular(self._h, rays.ctypes.data, hits.ctypes.data, n, 0, out.ctypes.data))
+        return out
+
+    def render_aovs(self, width, height, blocks=None, spp=None, master_seed=0, passes=None, device=False, follow=0):
         """hj_render_aovs / hj_render_aovs_frame: the first-hit AOVs of a frame's primary rays -> (height, width, 12) float32: per pixel
         the float32 sums, in block order, of its samples' records (albedo.rgb, 1 | shading normal.xyz, t | emission.rgb, 1 on a
         hit; a miss: 0, 0, 0, 1 and zeros) - `resolve_aovs` turns them into means.  blocks: a ctypes array (or list) of
         abi.ImageBlock, each with original_dimension == (width, height) and dimension <= 128; or spp [, master_seed, passes =
         (begin, end)]: the blocks `render_frame(spp, master_seed, begin, end)` renders on a width x height framebuffer.  Needs no
-        framebuffer and leaves it alone.  device=True: a torch tensor on the renderer's GPU, written in place."""
+        framebuffer and leaves it alone.  device=True: a torch tensor on the renderer's GPU, written in place.
+        follow (0 ... abi.AOV_MAX_FOLLOW): hj_render_aovs_followed / hj_render_aovs_frame_followed - a sample whose hit is a mirror or
+        glass is followed through up to that many specular surfaces (`follow_specular`'s rule) and gets the record of its chain's last
+        hit, its depth the sum of the chain's distances; a chain that ends in nothing keeps the record of the surface it left, so
+        the hit count is unchanged.  0: the first hit, as ever."""
         if (blocks is None) == (spp is None):
             raise ValueError("render_aovs: either blocks or spp is needed")
+        follow = int(follow)
+        if not 0 <= follow <= abi.AOV_MAX_FOLLOW:
+            raise ValueError(f"render_aovs: follow {follow}: 0 ... {abi.AOV_MAX_FOLLOW}")
         width, height = int(width), int(height)
         if device:
             import torch
@@ -774,10 +808,16 @@ class Renderer:
         if blocks is not None:
             if not isinstance(blocks, C.Array):
                 blocks = (abi.ImageBlock * len(blocks))(*blocks)
-            self._check(lib().hj_render_aovs(self._h, blocks, len(blocks), width, height, flags, ptr))
+            if follow:
+                self._check(lib().hj_render_aovs_followed(self._h, blocks, len(blocks), width, height, follow, flags, ptr))
+            else:
+                self._check(lib().hj_render_aovs(self._h, blocks, len(blocks), width, height, flags, ptr))
         else:
             begin, end = (0, int(spp)) if passes is None else (int(passes[0]), int(passes[1]))
-            self._check(lib().hj_render_aovs_frame(self._h, width, height, int(spp), int(master_seed), begin, end, flags, ptr))
+            if follow:
+                self._check(lib().hj_render_aovs_frame_followed(self._h, width, height, int(spp), int(master_seed), begin, end, follow, flags, ptr))
+            else:
+                self._check(lib().hj_render_aovs_frame(self._h, width, height, int(spp), int(master_seed), begin, end, flags, ptr))
         return aov
 
     def render_motion(self, prev, width, height, device_arrays=None, device=False):

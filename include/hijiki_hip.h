@@ -1440,8 +1440,9 @@ int hj_points_inside(hj_context* ctx, const float* points /* n x 4: p.xyz, reser
  * hj_render_aovs_frame:  hj_render_aovs over exactly the block list hj_render_frame generates for world == 1 with the same spp,
  *     master_seed and pass range (width x height takes the framebuffer's place): the AOVs of that frame's primary rays.  Behind the
  *     refusals above: pass_begin > pass_end or pass_end > spp is HJ_ERR_INVALID.  An empty pass range: HJ_OK, an all-zero output.
- * Not here: an environment's radiance for a miss; following mirror or glass to the first diffuse surface; a material at a
- *   closest-point or all-hit record (those carry no texture coordinates yet); a multi-GPU split.  (A denoiser: hj_denoise_frame below.) */
+ * Not here: an environment's radiance for a miss; a material at a closest-point or all-hit record (those carry no texture
+ *   coordinates yet); a multi-GPU split.  (Following mirror or glass to the first diffuse surface: hj_render_aovs_followed below.  A
+ *   denoiser: hj_denoise_frame below.) */
 #define HJ_MATERIALS_DEVICE_ARRAYS 1u
 #define HJ_MATERIALS_WORDS 8
 #define HJ_AOV_DEVICE_ARRAY 1u
@@ -1452,6 +1453,61 @@ int hj_render_aovs(hj_context* ctx, const hj_image_block* blocks, size_t num_blo
                    float* aov /* height x width x 12 */);
 int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
                          uint32_t pass_end, uint32_t flags, float* aov /* height x width x 12 */);
+
+/* Followed AOVs (ABI 0.30): what a mirror or glass SHOWS.  hj_render_aovs stops at the first hit, so a pixel on a mirror or on glass
+ * gets the guide of the mirror itself - albedo 1, the sphere's normal, the sphere's depth - and nothing in it separates the red wall
+ * from the white floor inside a reflection.  The calls below take the chain through specular surfaces that the path kernel takes
+ * (kernels/hj_stages.h stage_shade), made deterministic: an AOV cannot toss the Fresnel coin.  The continuation is one text
+ * (kernels/hj_follow.h follow_continue) for the per-record query and the frame kernel; tests/follow_ref.py restates it in numpy.
+ *
+ * The specular continuation of a ray (o, d) with raw hit (id, t, u, v):  hit point p = fma(t, d, o), populated as the path kernel
+ *   populates it (shading normal n).  The material word is read from the uploaded scene by id.
+ *     HJ_MAT_MIRROR:      wo = reflect(d, n) = d - n * (2 * dot(n, d)) - about the stored normal, from the back side too.
+ *     HJ_MAT_DIELECTRIC:  the path kernel's expressions, float32, no contraction, in this order: eta = the material's, etaInv = 1 / eta,
+ *       cosI = -dot(n, d), normal = n; when cosI < 0: eta = etaInv, etaInv = 1 / eta, normal = -normal, cosI = -cosI.
+ *       k = 1 - (etaInv * etaInv) * (1 - cosI * cosI).  When k > 0: cosO = sqrt(k), rpar = (eta * cosI - cosO) / (eta * cosI + cosO),
+ *       rorth = (cosI - eta * cosO) / (cosI + eta * cosO), fr = 0.5 * (rpar * rpar + rorth * rorth).
+ *       The branch, without the random draw: reflect when k <= 0 or fr >= 0.5f, else refract - the branch the path kernel takes more
+ *       often than not.  Reflect: wo = reflect(d, normal).  Refract: par = d - normal * dot(d, normal), wo = par * etaInv - normal *
+ *       cosO, not normalised, as the reference leaves it.
+ *     Every other tag, a miss, an id outside the scene: the chain ends here.
+ *   The continued ray is (p, wo, tMin = eps, tMax = +inf): the next segment of a path.
+ *
+ * hj_follow_specular:  rays (n x 8) and hits (n x 4) are hj_trace_rays' ray layout and hit records; out_rays (n x 8) gets per record
+ *     the continued ray in the same layout, and where the chain ends the empty ray: origin and direction 0, tMin = +inf, tMax = -inf -
+ *     hj_trace_rays answers it with a miss.  hj_follow_specular and hj_trace_rays alternated by the caller give exactly the chain of
+ *     the frame calls below.
+ *   HJ_FOLLOW_DEVICE_ARRAYS: the three arrays are device pointers on the context's GPU, 16-byte aligned, used in place.  Without it
+ *     they are host arrays, staged in chunks of HJ_TRACE_CHUNK records.  Runs on the context's stream and returns when the results
+ *     are complete.  n == 0: HJ_OK, nothing touched.
+ *   HJ_ERR_INVALID, before the device is touched, in this order: a null array (n > 0); unknown flag bits; n above 2^31 - 1; with
+ *     device arrays, a misaligned array.  A refused call writes nothing.  Then hj_trace_rays' gate.
+ *
+ * hj_render_aovs_followed:  hj_render_aovs with one more argument, max_follow in 0 ... HJ_AOV_MAX_FOLLOW.  Same image layout, same
+ *     block order, same flags.  A sample's chain starts with its camera ray, exactly as there.  While the last hit is a mirror or a
+ *     dielectric and fewer than max_follow continuations have been taken, the chain continues by the rule above and is walked again -
+ *     the same closest-hit walk.  The sample's record is the record of the chain's LAST hit: albedo and emission of the material at
+ *     that hit, its shading normal, 1 for the hit; the depth word [7] is the float32 sum of the chain's t values in chain order,
+ *     (t0 + t1) + t2 ... - the point at that depth along the camera ray is where a planar mirror's virtual image lies.
+ *   A continuation that hits nothing leaves the record of the surface it left: albedo 1, that surface's normal, the sum so far, hit
+ *     1 - so coverage, word 11, is exactly hj_render_aovs'.  A chain cut off by max_follow ends on its last specular hit the same way.
+ *     A camera ray that misses gives the miss record.  max_follow == 0 is hj_render_aovs bit for bit, through the same launches.
+ *   A record depends on the blocks, the scene, the camera and max_follow alone: not on HJ_TRACE_CHUNK or the lane that carried a chain.
+ *   The context holds 36 bytes more per sample slot of one walk launch (HJ_TRACE_CHUNK): never a frame's worth.
+ *   HJ_ERR_INVALID, before the device is touched: hj_render_aovs' refusals in their order, then max_follow above HJ_AOV_MAX_FOLLOW.
+ *     Then hj_trace_rays' gate.
+ * hj_render_aovs_frame_followed:  hj_render_aovs_frame with max_follow.  hj_render_aovs' refusals, then max_follow above
+ *     HJ_AOV_MAX_FOLLOW, then the bad pass range; then the gate.
+ * Not here: glass extinction does not tint the followed albedo (a dielectric's albedo stays 1 along the chain); a glossy lobe - the
+ *   project has no such material; hj_render_motion still stops at the first hit; a multi-GPU split. */
+#define HJ_AOV_MAX_FOLLOW 8
+#define HJ_FOLLOW_DEVICE_ARRAYS 1u
+int hj_follow_specular(hj_context* ctx, const float* rays /* n x 8, hj_trace_rays' layout */, const float* hits /* n x 4, hj_trace_rays' records */,
+                       size_t n, uint32_t flags, float* out_rays /* n x 8 */);
+int hj_render_aovs_followed(hj_context* ctx, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height,
+                            uint32_t max_follow, uint32_t flags, float* aov /* height x width x 12 */);
+int hj_render_aovs_frame_followed(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
+                                  uint32_t pass_end, uint32_t max_follow, uint32_t flags, float* aov /* height x width x 12 */);
 
 /* ------------------------------------------- frame denoiser */
 
