@@ -74,6 +74,8 @@ MOTION_WORDS = 4                  # words of a motion record (hj_render_motion):
 MOTION_NONE = 0xFFFFFFFF          # ... its word 3 for a pixel without a previous position
 MOTION_DEVICE_SHAPES = 1          # hj_render_motion flag: the previous shape arrays are device pointers
 MOTION_DEVICE_OUT = 2             # ... the motion image is a device pointer
+MOTION_LEFT = 0xFFFFFFFE          # hj_render_motion_followed: word 3 of a pixel whose chain left a specular surface and hit nothing
+VERSION = (0, 31, 0)              # the ABI this mirror describes: hj_version() == (major << 16) | (minor << 8) | patch
 
 
 def probe_vis_words(res):

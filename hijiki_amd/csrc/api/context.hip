@@ -155,7 +155,7 @@ int drain(hj_context* ctx, const char* fn, hipError_t e) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (30u << 8) | 0u; }   // 0.30.0: hj_follow_specular, hj_render_aovs_followed, hj_render_aovs_frame_followed
+uint32_t hj_version(void) { return (0u << 16) | (31u << 8) | 0u; }   // 0.31.0: hj_render_motion_followed
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

@@ -98,7 +98,13 @@
 //                         the persistent walk with a fetch that builds the centre ray from the pixel, its raw hit into the pixel's
 //                         record; k_mv_resolve, the previous point from the previous shape arrays projected into the previous camera,
 //                         in place (includes kernels/hj_motion.h, which includes the kernel headers up to hj_stages.h and the functions
-//                         of hj_denoise_temporal.h and edits none); and the one instantiation of k_dt_accumulate<true>
+//                         of hj_denoise_temporal.h and edits none); and the one instantiation of k_dt_accumulate<true>; motion_render, the
+//                         host routine of both motion calls
+//   api/motion_follow.hip hj_render_motion_followed: the motion image through mirrors and glass - between k_mv_walk and the resolve the
+//                         rounds k_mf_count / k_mf_scan / k_mf_scatter, the live pixels in order, and k_mf_follow, the persistent walk
+//                         with a fetch that continues a chain from its state and carries the product of its reflections; k_mf_resolve
+//                         (includes kernels/hj_motion_follow.h, which includes hj_motion.h and hj_follow.h without their kernels and
+//                         hj_compact.h and edits none)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -502,7 +508,9 @@ struct hj_context {
 
   // hj_render_motion (api/motion.hip): the staging of host-side previous shape arrays (16 / 48 / 32 bytes a sphere / quad / vertex)
   // and of a host-side motion image (16 bytes a pixel).  Grown on demand, reused by every call, freed with the context.
-  struct Motion { hjapi::DevBuf spheres, quads, vertices, image; } motion;
+  // hj_render_motion_followed (api/motion_follow.hip) adds, per pixel of the image, the chain state (32 bytes), the product of the
+  // chain's reflections (48 bytes), the list of live pixels (4 bytes) and a count per tile of 256.
+  struct Motion { hjapi::DevBuf spheres, quads, vertices, image, state, mat, counts, list; } motion;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
@@ -633,6 +641,18 @@ namespace hjapi {
 // api/motion.hip: k_dt_accumulate<true> over a's image on the context's stream (hj_denoise_frame_temporal_motion; the temporal unit
 // itself holds the <false> instantiation alone)
 void dt_accumulate_motion_enqueue(hj_context* ctx, const hj::DtArgs& a);
+// api/motion.hip: the host routine of hj_render_motion (max_follow == 0) and hj_render_motion_followed, behind the name fn
+int motion_render(hj_context* ctx, const char* fn, const hj_scene_desc* prev, uint32_t width, uint32_t height, uint32_t max_follow, uint32_t flags,
+                  float* motion);
+}  // namespace hjapi
+namespace hj { struct MvPrev; }                  // kernels/hj_motion.h
+namespace hjapi {
+// api/motion_follow.hip, for motion_render with max_follow > 0: room for the rounds over an image of `pixels` pixels; the follow rounds
+// behind k_mv_walk, whose raw hits are at d_motion (-> followed: a round ran, every pixel's chain state is set and the image resolves
+// through motion_follow_resolve); and that resolve's launch
+int motion_follow_reserve(hj_context* ctx, size_t pixels);
+hipError_t motion_follow_rounds(hj_context* ctx, uint32_t width, uint32_t height, float4* d_motion, uint32_t max_follow, bool& followed);
+void motion_follow_resolve(hj_context* ctx, const hj::MvPrev& prev, uint32_t width, uint32_t height, float4* d_motion);
 // The statistics read-back of a pass's launches (kStatWords x G words each), summed on the host once the stream has drained.
 // on == false (the caller wants no statistics): every member does nothing.
 struct QueryStats {

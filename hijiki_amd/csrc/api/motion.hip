@@ -7,6 +7,8 @@
 //                 raw hits straight into the motion image - the caller's, or the context's staging of a host array
 //   k_mv_resolve  behind it on the context's stream, in place: the previous point from the previous shape arrays - the caller's device
 //                 arrays, the context's staging of host arrays, or the uploaded array where a kind did not move - and its projection
+// motion_render is also hj_render_motion_followed's host routine (api/motion_follow.hip: the rounds between the two launches, and the
+// followed resolve in k_mv_resolve's place once a round ran).
 // Also the one instantiation of k_dt_accumulate<true> (dt_accumulate_motion_enqueue, for api/denoise_temporal.hip): the temporal
 // unit keeps the three kernels it had.
 #include "hj_internal.h"
@@ -19,7 +21,6 @@ using namespace hjapi;
 namespace {
 
 constexpr uint32_t kMotionMaxSide = 16384u;
-constexpr const char* kFn = "hj_render_motion";
 
 bool finite3(const float* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
 
@@ -32,12 +33,11 @@ void dt_accumulate_motion_enqueue(hj_context* ctx, const hj::DtArgs& a) {
   hipLaunchKernelGGL(hj::k_dt_accumulate<true>, grid, blk, 0, ctx->stream, a);
 }
 
-}  // namespace hjapi
-
-extern "C" {
-
-// The argument checks come first, in hj_trace_rays' style, and need neither a device nor a context's state; then the queries' gate.
-int hj_render_motion(hj_context* ctx, const hj_scene_desc* prev, uint32_t width, uint32_t height, uint32_t flags, float* motion) {
+// hj_render_motion (max_follow == 0, its own two launches and nothing else) and hj_render_motion_followed (api/motion_follow.hip) behind
+// the name kFn: one host routine, so the checks, their order and their texts are one.  The argument checks come first, in
+// hj_trace_rays' style, and need neither a device nor a context's state; then the queries' gate.
+int motion_render(hj_context* ctx, const char* kFn, const hj_scene_desc* prev, uint32_t width, uint32_t height, uint32_t max_follow, uint32_t flags,
+                  float* motion) {
   if (!prev || !motion) return set_error(ctx, HJ_ERR_INVALID, "%s: null %s", kFn, !prev ? "prev" : "motion");
   if (flags & ~(uint32_t)(HJ_MOTION_DEVICE_SHAPES | HJ_MOTION_DEVICE_OUT)) return set_error(ctx, HJ_ERR_INVALID, "%s: unknown flag bits 0x%x", kFn, flags);
   if (width == 0 || height == 0 || width > kMotionMaxSide || height > kMotionMaxSide)
@@ -46,6 +46,7 @@ int hj_render_motion(hj_context* ctx, const hj_scene_desc* prev, uint32_t width,
   const bool dev_shapes = (flags & HJ_MOTION_DEVICE_SHAPES) != 0, dev_out = (flags & HJ_MOTION_DEVICE_OUT) != 0;
   if ((dev_out && misaligned(motion)) || (dev_shapes && misaligned(prev->spheres, prev->quads, prev->vertices)))
     return set_error(ctx, HJ_ERR_INVALID, "%s: a device array must be 16-byte aligned", kFn);
+  if (max_follow > HJ_AOV_MAX_FOLLOW) return set_error(ctx, HJ_ERR_INVALID, "%s: max_follow %u above %u", kFn, max_follow, (uint32_t)HJ_AOV_MAX_FOLLOW);
   HJ_TRY(query_gate(ctx, kFn));
   const hj::DeviceScene& sc = ctx->scene;
   const size_t ns = sc.ns, nq = sc.nq, nv = ctx->update.num_vertices;
@@ -82,6 +83,7 @@ int hj_render_motion(hj_context* ctx, const hj_scene_desc* prev, uint32_t width,
     HJ_TRY(dev_alloc(ctx, q.image, image_bytes));
     d_motion = static_cast<float4*>(q.image.p);
   }
+  if (max_follow != 0) HJ_TRY(motion_follow_reserve(ctx, (size_t)width * height));
   hipStream_t s = ctx->stream;
   hipError_t e = hipSuccess;
   for (int k = 0; k < 3 && e == hipSuccess; k++)
@@ -94,14 +96,25 @@ int hj_render_motion(hj_context* ctx, const hj_scene_desc* prev, uint32_t width,
     else hipLaunchKernelGGL(hj::k_mv_walk<false>, grid, blk, 0, s, sc, width, height, n, wg_rays, d_motion);
     e = hipGetLastError();
   }
+  bool followed = false;
+  if (e == hipSuccess && max_follow != 0) e = motion_follow_rounds(ctx, width, height, d_motion, max_follow, followed);
   if (e == hipSuccess) {
     const hj::MvPrev p{static_cast<const float4*>(d_kind[0]), static_cast<const float4*>(d_kind[1]), static_cast<const float4*>(d_kind[2]),
                        hj::dt_host_camera(prev->camera)};
-    hipLaunchKernelGGL(hj::k_mv_resolve, per_lane(width * height), dim3(hj::kBlockThreads), 0, s, sc, p, width, height, d_motion);
+    if (followed) motion_follow_resolve(ctx, p, width, height, d_motion);
+    else hipLaunchKernelGGL(hj::k_mv_resolve, per_lane(width * height), dim3(hj::kBlockThreads), 0, s, sc, p, width, height, d_motion);
     e = hipGetLastError();
   }
   if (e == hipSuccess && !dev_out) e = hipMemcpyAsync(motion, d_motion, image_bytes, hipMemcpyDeviceToHost, s);
   return drain(ctx, kFn, e);
+}
+
+}  // namespace hjapi
+
+extern "C" {
+
+int hj_render_motion(hj_context* ctx, const hj_scene_desc* prev, uint32_t width, uint32_t height, uint32_t flags, float* motion) {
+  return motion_render(ctx, "hj_render_motion", prev, width, height, 0, flags, motion);
 }
 
 }  // extern "C"

@@ -30,8 +30,9 @@ static_assert(kSlotsPerBlock % kAfThreads == 0, "a launch's sample slots are who
 // a dielectric takes the expressions of hj_stages.h:560-583 word for word, and in place of the random draw the branch the path kernel
 // takes more often than not: reflect when k <= 0 or fr >= 0.5f, else refract (direction not normalised, as the reference leaves
 // it).  Every other tag, a miss, an id outside the scene: false, nothing written.  -> p: the hit point, the next origin; wo: the next
-// direction; n: the surface's shading normal
-HJ_DEV bool follow_continue(const DeviceScene& sc, v3 o, v3 d, float4 hr, v3& p, v3& wo, v3& n) {
+// direction; n: the surface's shading normal; reflected: the continuation is a reflection (a mirror, a dielectric's reflect branch) and
+// not a refraction - what the followed motion image (kernels/hj_motion_follow.h) multiplies its Householder matrices by
+HJ_DEV bool follow_continue_branch(const DeviceScene& sc, v3 o, v3 d, float4 hr, v3& p, v3& wo, v3& n, bool& reflected) {
   const uint32_t id = __float_as_uint(hr.x);
   if (id >= sc.ns + sc.nq + sc.nt) return false;
   const uint32_t mat = sc.materials[id];
@@ -44,6 +45,7 @@ HJ_DEV bool follow_continue(const DeviceScene& sc, v3 o, v3 d, float4 hr, v3& p,
   else populate_triangle(sc, id - sc.ns - sc.nq, hr.z, hr.w, its);
   p = its.p;
   n = its.n;
+  reflected = true;
   if (tag == HJ_MAT_MIRROR) {
     wo = reflect3(d, its.n);
     return true;
@@ -69,9 +71,30 @@ HJ_DEV bool follow_continue(const DeviceScene& sc, v3 o, v3 d, float4 hr, v3& p,
   } else {
     const v3 par = d - normal * dot3(d, normal);
     wo = par * etaInv - normal * cosO;
+    reflected = false;
   }
   return true;
 }
+// ... for the callers that do not ask which branch
+HJ_DEV bool follow_continue(const DeviceScene& sc, v3 o, v3 d, float4 hr, v3& p, v3& wo, v3& n) {
+  bool reflected_unused = false;
+  return follow_continue_branch(sc, o, d, hr, p, wo, n, reflected_unused);
+}
+
+// Is the chain of sample slot `slot` (< n) live: its last hit on a mirror or a dielectric, fewer than max_follow continuations taken?
+// FIRST: behind the camera walk no state exists yet and no continuation has been taken.
+template <bool FIRST>
+HJ_DEV bool follow_live(const DeviceScene& sc, const float4* __restrict__ hits, const float4* __restrict__ state, uint32_t slot, uint32_t n,
+                        uint32_t max_follow) {
+  if (slot >= n) return false;
+  const uint32_t id = __float_as_uint(hits[slot].x);
+  if (id >= sc.ns + sc.nq + sc.nt) return false;                  // (a miss, kFollowLeft)
+  const uint32_t tag = sc.materials[id] >> HJ_MATERIAL_TAG_SHIFT;
+  if (tag != HJ_MAT_MIRROR && tag != HJ_MAT_DIELECTRIC) return false;
+  return FIRST || __float_as_uint(state[2 * (size_t)slot + 1].w) < max_follow;
+}
+
+#ifndef HJ_FOLLOW_NO_KERNELS   // (kernels/hj_motion_follow.h takes the functions above alone: api/follow.hip holds these kernels)
 
 // rays: two float4 per record (origin.xyz, direction.x | direction.yz, tMin, tMax), hits: (objectID bits, t, u, v) - hj_trace_rays'
 // arrays.  out: the continued ray (p, wo, tMin = eps, tMax = +inf: the next segment of a path), or where the chain ends the empty ray
@@ -89,19 +112,6 @@ __global__ __launch_bounds__(kBlockThreads) void k_follow(DeviceScene sc, const 
   }
   out[2 * (size_t)i] = o0;
   out[2 * (size_t)i + 1] = o1;
-}
-
-// Is the chain of sample slot `slot` (< n) live: its last hit on a mirror or a dielectric, fewer than max_follow continuations taken?
-// FIRST: behind the camera walk no state exists yet and no continuation has been taken.
-template <bool FIRST>
-HJ_DEV bool follow_live(const DeviceScene& sc, const float4* __restrict__ hits, const float4* __restrict__ state, uint32_t slot, uint32_t n,
-                        uint32_t max_follow) {
-  if (slot >= n) return false;
-  const uint32_t id = __float_as_uint(hits[slot].x);
-  if (id >= sc.ns + sc.nq + sc.nt) return false;                  // (a miss, kFollowLeft)
-  const uint32_t tag = sc.materials[id] >> HJ_MATERIAL_TAG_SHIFT;
-  if (tag != HJ_MAT_MIRROR && tag != HJ_MAT_DIELECTRIC) return false;
-  return FIRST || __float_as_uint(state[2 * (size_t)slot + 1].w) < max_follow;
 }
 
 // The live slots of a launch's n sample slots in ascending order -> list.  Tiles of kAfThreads slots; counts: a word per tile and the
@@ -206,5 +216,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_aov_resolve_followed(DeviceSc
   }
   aov_add(aov + 3 * ((size_t)py * width + px), r0, r1, r2);
 }
+
+#endif  // HJ_FOLLOW_NO_KERNELS
 
 }  // namespace hj

@@ -55,6 +55,58 @@ HJ_DEV bool mv_pixel(uint32_t q, uint32_t W, uint32_t H, uint32_t tile, uint32_t
   return x < W && y < H;
 }
 
+// The contract's arithmetic (include/hijiki_hip.h, hj_render_motion), operation for operation - one rounding each, uncontracted, except
+// dt_camera_dir, dt_rotate and divs, which are the numeric contract's, and the hit point's fmaf - as ONE text for k_mv_resolve and for
+// the followed resolve (kernels/hj_motion_follow.h), whose pixels without a continuation take mv_record as it stands.
+// ... the sphere normal at the hit point P of sphere id of the uploaded scene: populate_sphere's
+HJ_DEV v3 mv_sphere_normal(const DeviceScene& sc, uint32_t id, v3 P) {
+  const float4 sp = sc.spheres[id];
+  return divs(P - xyz(sp), sp.w);
+}
+// ... the point of shape id (< shapes) on the shape arrays given: a sphere's at the normal n, a quad's and a triangle's at (u, v); the
+// index triple is the uploaded one
+HJ_DEV v3 mv_shape_point(const DeviceScene& sc, const float4* __restrict__ spheres, const float4* __restrict__ quads, const float4* __restrict__ vertices,
+                         uint32_t id, v3 n, float u, float v) {
+  if (id < sc.ns) {
+    const float4 pp = spheres[id];
+    return V(pp.x + n.x * pp.w, pp.y + n.y * pp.w, pp.z + n.z * pp.w);
+  }
+  if (id < sc.ns + sc.nq) {
+    const float4* __restrict__ q = quads + 3 * (size_t)(id - sc.ns);
+    const float4 o = q[0], e1 = q[1], e2 = q[2];
+    return V((o.x + e1.x * u) + e2.x * v, (o.y + e1.y * u) + e2.y * v, (o.z + e1.z * u) + e2.z * v);
+  }
+  const hj_triangle tri = sc.triangles[id - sc.ns - sc.nq];
+  const float4 a = vertices[2 * (size_t)tri.v[0]], b = vertices[2 * (size_t)tri.v[1]], c = vertices[2 * (size_t)tri.v[2]];
+  const float l0 = (1.0f - u) - v;
+  return V((a.x * l0 + b.x * u) + c.x * v, (a.y * l0 + b.y * u) + c.y * v, (a.z * l0 + b.z * u) + c.z * v);
+}
+// ... PROJECTION of the point Pp into the previous camera -> the record, its word 3 `word`; (0, 0, 0, HJ_MOTION_NONE) behind the camera
+HJ_DEV float4 mv_project(const DtCamera& pc, v3 Pp, uint32_t W, uint32_t H, uint32_t word) {
+  const v3 vv = Pp - pc.pos;
+  const v3 c = dt_rotate(vv, -pc.qv, pc.qw);
+  if (!(c.z < 0.0f)) return make_float4(0.f, 0.f, 0.f, __uint_as_float(kMvNone));
+  const float Wf = (float)W, Hf = (float)H;
+  const float k = (0.5f * Wf) / pc.tan_half;
+  const float sx = (c.x / -c.z) * k + 0.5f * Wf, sy = (-c.y / -c.z) * k + 0.5f * Hf;
+  return make_float4(sx, sy, __builtin_sqrtf(dn_sq(vv)), __uint_as_float(word));
+}
+// ... hj_render_motion's record of pixel t = y * W + x whose centre ray's raw hit is hr
+HJ_DEV float4 mv_record(const DeviceScene& sc, const MvPrev& prev, uint32_t t, uint32_t W, uint32_t H, float4 hr) {
+  const uint32_t id = __float_as_uint(hr.x);
+  if (id >= sc.ns + sc.nq + sc.nt) return make_float4(0.f, 0.f, 0.f, __uint_as_float(kMvNone));   // (a miss is 0xFFFFFFFF; any other id outside the scene is one too)
+  v3 n = V(0.f, 0.f, 0.f);
+  if (id < sc.ns) {
+    const uint32_t x = t % W, y = t / W;
+    const DtCamera cam = mv_camera(sc);
+    const v3 d = dt_camera_dir(cam, (float)x + 0.5f, (float)y + 0.5f, (float)W, (float)H);
+    n = mv_sphere_normal(sc, id, V(fmaf(hr.y, d.x, cam.pos.x), fmaf(hr.y, d.y, cam.pos.y), fmaf(hr.y, d.z, cam.pos.z)));   // scene.glsl:164
+  }
+  return mv_project(prev.cam, mv_shape_point(sc, prev.spheres, prev.quads, prev.vertices, id, n, hr.z, hr.w), W, H, id);
+}
+
+#ifndef HJ_MOTION_NO_KERNELS   // (kernels/hj_motion_follow.h takes the functions above alone: api/motion.hip holds these kernels)
+
 // Entries [0, n = mv_entries) of the image.  Workgroup g walks entries [g * wg_rays, ...) as k_rq_walk's does.  An entry's ray is
 // built from its pixel - origin = the uploaded camera's position, d = dt_camera_dir through (x + 0.5, y + 0.5), tMin = eps, tMax =
 // +inf - and its raw hit (objectID bits, t, u, v; a miss: (-1, 0, 0, 0)) goes to motion[y * W + x]: which lane or workgroup
@@ -92,45 +144,13 @@ __global__ __launch_bounds__(kBlockThreads) void k_mv_walk(DeviceScene sc, uint3
 }
 
 // One lane per pixel t = y * W + x, in place: motion[t] holds the walk's raw hit on entry and the pixel's record on return, so a
-// lane touches its own record alone.  The contract's arithmetic (include/hijiki_hip.h, hj_render_motion), operation for operation:
-// one rounding each, uncontracted, except dt_camera_dir, dt_rotate and divs, which are the numeric contract's, and the hit point's fmaf.
+// lane touches its own record alone.  The record: mv_record above.
 __global__ __launch_bounds__(kBlockThreads) void k_mv_resolve(DeviceScene sc, MvPrev prev, uint32_t W, uint32_t H, float4* __restrict__ motion) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= W * H) return;
-  const float4 hr = motion[t];
-  const uint32_t id = __float_as_uint(hr.x);
-  float4 out = make_float4(0.f, 0.f, 0.f, __uint_as_float(kMvNone));
-  if (id < sc.ns + sc.nq + sc.nt) {                                // (a miss is 0xFFFFFFFF; any other id outside the scene is one too)
-    const float u = hr.z, v = hr.w;
-    v3 Pp;
-    if (id < sc.ns) {
-      const uint32_t x = t % W, y = t / W;
-      const DtCamera cam = mv_camera(sc);
-      const v3 d = dt_camera_dir(cam, (float)x + 0.5f, (float)y + 0.5f, (float)W, (float)H);
-      const v3 P = V(fmaf(hr.y, d.x, cam.pos.x), fmaf(hr.y, d.y, cam.pos.y), fmaf(hr.y, d.z, cam.pos.z));   // scene.glsl:164
-      const float4 sp = sc.spheres[id], pp = prev.spheres[id];
-      const v3 n = divs(P - xyz(sp), sp.w);                        // populate_sphere's normal
-      Pp = V(pp.x + n.x * pp.w, pp.y + n.y * pp.w, pp.z + n.z * pp.w);
-    } else if (id < sc.ns + sc.nq) {
-      const float4* __restrict__ q = prev.quads + 3 * (size_t)(id - sc.ns);
-      const float4 o = q[0], e1 = q[1], e2 = q[2];
-      Pp = V((o.x + e1.x * u) + e2.x * v, (o.y + e1.y * u) + e2.y * v, (o.z + e1.z * u) + e2.z * v);
-    } else {
-      const hj_triangle tri = sc.triangles[id - sc.ns - sc.nq];
-      const float4 a = prev.vertices[2 * (size_t)tri.v[0]], b = prev.vertices[2 * (size_t)tri.v[1]], c = prev.vertices[2 * (size_t)tri.v[2]];
-      const float l0 = (1.0f - u) - v;
-      Pp = V((a.x * l0 + b.x * u) + c.x * v, (a.y * l0 + b.y * u) + c.y * v, (a.z * l0 + b.z * u) + c.z * v);
-    }
-    const v3 vv = Pp - prev.cam.pos;
-    const v3 c = dt_rotate(vv, -prev.cam.qv, prev.cam.qw);
-    if (c.z < 0.0f) {
-      const float Wf = (float)W, Hf = (float)H;
-      const float k = (0.5f * Wf) / prev.cam.tan_half;
-      const float sx = (c.x / -c.z) * k + 0.5f * Wf, sy = (-c.y / -c.z) * k + 0.5f * Hf;
-      out = make_float4(sx, sy, __builtin_sqrtf(dn_sq(vv)), __uint_as_float(id));
-    }
-  }
-  motion[t] = out;
+  motion[t] = mv_record(sc, prev, t, W, H, motion[t]);
 }
+
+#endif  // HJ_MOTION_NO_KERNELS
 
 }  // namespace hj

@@ -33,7 +33,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
            "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame",
            "hj_denoise_frame", "hj_denoise_frame_temporal", "hj_render_motion", "hj_denoise_frame_temporal_motion",
-           "hj_follow_specular", "hj_render_aovs_followed", "hj_render_aovs_frame_followed")
+           "hj_follow_specular", "hj_render_aovs_followed", "hj_render_aovs_frame_followed", "hj_render_motion_followed")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -133,6 +133,7 @@ def lib():
         L.hj_denoise_frame_temporal.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp]
         L.hj_denoise_frame_temporal_motion.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp, vp]
         L.hj_render_motion.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_uint32, vp]   # (host or device pointers)
+        L.hj_render_motion_followed.argtypes = [vp, C.POINTER(abi.SceneDesc), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_debug_samples.argtypes = [vp, C.POINTER(abi.ImageBlock), C.POINTER(abi.RenderOpts), C.POINTER(C.c_float)]
         L.hj_build_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.POINTER(C.c_size_t)]
         L.hj_tune_bvh_device.argtypes = [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.BvhNode), C.c_size_t, C.c_size_t]
@@ -820,7 +821,7 @@ class Renderer:
                 self._check(lib().hj_render_aovs_frame(self._h, width, height, int(spp), int(master_seed), begin, end, flags, ptr))
         return aov
 
-    def render_motion(self, prev, width, height, device_arrays=None, device=False):
+    def render_motion(self, prev, width, height, device_arrays=None, device=False, follow=0):
         """hj_render_motion: per-pixel motion for `denoise_frame_temporal` -> (height, width, 4) float32: per pixel (sx, sy, zp, id
         bits) - where the surface point the pixel's centre ray sees in the uploaded scene was in the previous image, its distance
         from the previous camera, and the shape - or (0, 0, 0, abi.MOTION_NONE) for a miss or a point behind the previous camera
@@ -828,8 +829,16 @@ class Renderer:
         (camera, spheres, quads, vertices with the uploaded counts; a NULL array: that kind did not move), as `update_shapes` takes
         it.  The current frame is the scene as uploaded or as the last `update_shapes` left it.  device_arrays: the dict of torch
         tensors `update_shapes` takes, read in place of prev's host arrays (a kind it lacks did not move).  device=True: the result
-        is a torch tensor on the renderer's GPU, written in place.  Not followed: a sphere's rotation about its centre, what a
-        mirror or glass shows, moving lights' shadows."""
+        is a torch tensor on the renderer's GPU, written in place.  Not followed: a sphere's rotation about its centre, moving
+        lights' shadows, and with follow = 0 what a mirror or glass shows.
+        follow (0 ... abi.AOV_MAX_FOLLOW): hj_render_motion_followed - a pixel whose centre ray hits a mirror or glass is followed
+        through up to that many specular surfaces, as `render_aovs(..., follow=N)` follows it, and its record is the previous
+        position of the virtual point a followed guide describes (zp beside the guide's summed depth), word 3 the last hit's shape,
+        or abi.MOTION_LEFT where the chain ended in nothing.  Exact for a static planar mirror; a curved one by its tangent plane, a
+        refraction passes the displacement on unchanged.  0: hj_render_motion, as ever."""
+        follow = int(follow)
+        if not 0 <= follow <= abi.AOV_MAX_FOLLOW:
+            raise ValueError(f"render_motion: follow {follow}: 0 ... {abi.AOV_MAX_FOLLOW}")
         d = abi.SceneDesc()
         C.memmove(C.byref(d), C.byref(prev.desc), C.sizeof(abi.SceneDesc))
         width, height = int(width), int(height)
@@ -853,7 +862,10 @@ class Renderer:
         else:
             motion = np.zeros((height, width, abi.MOTION_WORDS), np.float32)
             ptr = motion.ctypes.data
-        self._check(lib().hj_render_motion(self._h, C.byref(d), width, height, flags, ptr))
+        if follow:
+            self._check(lib().hj_render_motion_followed(self._h, C.byref(d), width, height, follow, flags, ptr))
+        else:
+            self._check(lib().hj_render_motion(self._h, C.byref(d), width, height, flags, ptr))
         return motion
 
     def denoise_frame(self, aov, beauty=None, iterations=5, sigma_normal=0.5, sigma_depth=1.0, sigma_luminance=4.0, sigma_albedo=0.1, device=False):

@@ -1499,7 +1499,8 @@ int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint3
  * hj_render_aovs_frame_followed:  hj_render_aovs_frame with max_follow.  hj_render_aovs' refusals, then max_follow above
  *     HJ_AOV_MAX_FOLLOW, then the bad pass range; then the gate.
  * Not here: glass extinction does not tint the followed albedo (a dielectric's albedo stays 1 along the chain); a glossy lobe - the
- *   project has no such material; hj_render_motion still stops at the first hit; a multi-GPU split. */
+ *   project has no such material; hj_render_motion still stops at the first hit: hj_render_motion_followed (ABI 0.31) follows these
+ *   chains; a multi-GPU split. */
 #define HJ_AOV_MAX_FOLLOW 8
 #define HJ_FOLLOW_DEVICE_ARRAYS 1u
 int hj_follow_specular(hj_context* ctx, const float* rays /* n x 8, hj_trace_rays' layout */, const float* hits /* n x 4, hj_trace_rays' records */,
@@ -1710,13 +1711,62 @@ int hj_denoise_frame_temporal(hj_context* ctx, uint32_t width, uint32_t height, 
  *   scene's (HJ_ERR_INVALID); with host arrays, a previous coordinate or radius that is not finite (HJ_ERR_INVALID) - device arrays
  *   are the caller's word, as for hj_scene_update_shapes.
  * Not here: rotation of a sphere about its own centre, which a record of centre and radius cannot express; what a mirror or glass
- *   shows; moving lights' shadows on static surfaces; a change of topology or counts; a multi-GPU split; a CLI flag. */
+ *   shows (hj_render_motion_followed below follows it); moving lights' shadows on static surfaces; a change of topology or counts; a multi-GPU split; a CLI flag. */
 #define HJ_MOTION_WORDS 4
 #define HJ_MOTION_NONE 0xFFFFFFFFu
 #define HJ_MOTION_DEVICE_SHAPES 1u   /* prev->spheres / quads / vertices are device pointers (as HJ_UPDATE_DEVICE_ARRAYS) */
 #define HJ_MOTION_DEVICE_OUT    2u   /* motion is a device pointer, 16-byte aligned, written in place */
 int hj_render_motion(hj_context* ctx, const hj_scene_desc* prev, uint32_t width, uint32_t height, uint32_t flags,
                      float* motion /* height x width x 4 */);
+
+/* hj_render_motion_followed (ABI 0.31): hj_render_motion through mirrors and glass - the motion image that composes with the followed
+ * AOVs' guides.  A followed guide's depth on a specular pixel is the depth of what the surface SHOWS (the sum of the chain's t), and
+ * hj_denoise_frame_temporal_motion tests the history's depth against the record's zp: hj_render_motion's zp is the distance to the
+ * mirror itself, so with followed guides every tap on a mirror fails and the pixel restarts every frame.  This call follows the chain
+ * the followed AOVs follow, for the pixel's centre ray, and gives the previous position of the VIRTUAL point the guide describes.
+ * No counterpart in the reference; tests/motion_follow_ref.py restates the contract in numpy.
+ *   Arguments, flags, the record layout, the staging and the device forms are hj_render_motion's, with max_follow in 0 ...
+ *   HJ_AOV_MAX_FOLLOW in front of flags.  Every operation is float32 with one rounding and no contraction, except where hj_render_motion
+ *   excepts it, inside the specular continuation (Followed AOVs above: its own fixed expressions) and the hit points' fma.
+ *   THE CHAIN starts as hj_render_motion's RAY and is continued at each hit by the specular continuation of hj_follow_specular (a
+ *     mirror reflects; a dielectric reflects when k <= 0 or fr >= 0.5f, else refracts): origin p, direction wo, tMin = eps, tMax =
+ *     +inf.  It ends after max_follow continuations, at a hit that is neither mirror nor dielectric, or at a continuation that hits
+ *     nothing: hj_render_aovs_followed's chain for a sample through the pixel's centre.
+ *   NO CONTINUATION TAKEN - max_follow == 0, a first hit that is not specular, a miss: the record is hj_render_motion's, bit for bit,
+ *     by its own arithmetic.  max_follow == 0 is hj_render_motion through the same two launches and nothing else.
+ *   AT LEAST ONE CONTINUATION TAKEN, and a last hit (id, t, u, v) on the segment (o, d):
+ *     D = the float32 sum of the chain's t values in chain order, (t0 + t1) + t2 ...: the followed AOVs' depth word.
+ *     d0 = the RAY's d.  Pv = camera.position + D * d0 per channel (one multiply, one add): the virtual point, where step 2 of
+ *       hj_denoise_frame_temporal would put a guide of depth D.
+ *     X_now and X_prev: the hit point re-expressed on the uploaded and on the previous shape by ONE expression, so that an unmoved
+ *       shape gives X_prev - X_now == 0 exactly.  sphere: P = fma(t, d, o); n = (P - c) * (1.0f / r) with (c, r) the uploaded sphere;
+ *       X = c* + n * r* with (c*, r*) the uploaded, then the previous sphere.  quad: X = (o* + e1* * u) + e2* * v.  triangle:
+ *       l0 = (1.0f - u) - v; X = (a* * l0 + b* * u) + c* * v with the uploaded index triple.
+ *     delta = X_prev - X_now.
+ *     M = the product of the Householder matrices of the chain's REFLECT events in chain order, M_k = M_(k-1) H_k, starting as the
+ *       identity; a refraction leaves M as it is.  A reflect event with shading normal n (the populated normal, not turned towards
+ *       the ray) takes M to M - 2 (M n) n^T in this order: w_i = (M_i0 * n.x + M_i1 * n.y) + M_i2 * n.z;  w2_i = 2.0f * w_i;
+ *       M_ij = M_ij - w2_i * n_j.
+ *     Pv_prev_i = Pv_i + ((M_i0 * delta.x + M_i1 * delta.y) + M_i2 * delta.z).
+ *     The record is hj_render_motion's PROJECTION of Pv_prev in Pp's place: (sx, sy, zp = |Pv_prev - prev.position|, id as bits), or
+ *       (0, 0, 0, HJ_MOTION_NONE) where c.z < 0 is false.
+ *   A CHAIN WHOSE LAST CONTINUATION HITS NOTHING: D = the sum so far and Pv_prev = Pv itself (no delta is added); the record is
+ *     its PROJECTION with word 3 = HJ_MOTION_LEFT - the followed guide keeps the record of the surface that was left at that depth.
+ *     HJ_MOTION_LEFT is not HJ_MOTION_NONE: hj_denoise_frame_temporal_motion reads the record as a position.
+ *   A record depends on the uploaded scene, prev, (width, height) and max_follow alone, as hj_render_motion's.
+ * The context keeps, beside hj_render_motion's staging, 84 bytes a pixel of the whole image while max_follow > 0: the chain state
+ *   (32), M (48), the list of live pixels (4), and a count per 256 pixels.  An image that does not fit is HJ_ERR_NOMEM; the image is
+ *   not banded.  The stream is synchronised once a round, for the count of live chains.
+ * HJ_ERR_INVALID, before the device is touched: hj_render_motion's refusals in their order with their texts behind
+ *   "hj_render_motion_followed:", then max_follow above HJ_AOV_MAX_FOLLOW.  Then hj_trace_rays' gate, and behind it hj_render_motion's
+ *   two checks.
+ * Not here: on a planar static mirror the record is exact (tests/test_motion_follow_host.py judges it in float64); a curved mirror
+ *   is treated by its tangent plane at the hit; a refraction carries the displacement through unchanged; a specular surface that
+ *   itself moved is not accounted for; an environment seen after a mirror is treated as static; the chain is the centre ray's, not a
+ *   mean over a pixel's samples; what hj_render_motion leaves out. */
+#define HJ_MOTION_LEFT 0xFFFFFFFEu
+int hj_render_motion_followed(hj_context* ctx, const hj_scene_desc* prev, uint32_t width, uint32_t height, uint32_t max_follow,
+                              uint32_t flags, float* motion /* height x width x 4 */);
 
 /* hj_denoise_frame_temporal_motion (ABI 0.29): hj_denoise_frame_temporal reprojecting through a motion image.
  *   motion == NULL: the call is hj_denoise_frame_temporal, bit for bit (one host routine).
