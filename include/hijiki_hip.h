@@ -1472,6 +1472,9 @@ int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint3
  *       cosO, not normalised, as the reference leaves it.
  *     Every other tag, a miss, an id outside the scene: the chain ends here.
  *   The continued ray is (p, wo, tMin = eps, tMax = +inf): the next segment of a path.
+ *   A record no walk gives - t, d, u or v not finite, or a product that overflows - can make words of p and wo NaN.  Such a word is
+ *   a NaN and no more is promised of it: the sign and payload of a NaN that an operation generates (inf - inf, 0 * inf) differ
+ *   between processors.  Which words are NaN, and every bit of every other word, is as the expressions above say.
  *
  * hj_follow_specular:  rays (n x 8) and hits (n x 4) are hj_trace_rays' ray layout and hit records; out_rays (n x 8) gets per record
  *     the continued ray in the same layout, and where the chain ends the empty ray: origin and direction 0, tMin = +inf, tMax = -inf -

@@ -61,7 +61,9 @@ def dielectric(eta, d, n):
 def continue_rays(cs, rays, hits, surface, detail=False):
     """The continuation of rays (n, 8) at hits (n, 4: shape id bits, t, u, v) whose populated records are surface (n, 16: hit point
     0..2, shading normal 3..5) -> (out (n, 8): the continued ray (p, wo, eps, +inf) or the empty ray, classes (n,) of END ...
-    REFLECT_TIR) [, detail: dict(reflect, refract (n, 3): a dielectric's two candidates, zeros elsewhere; k, fr)]."""
+    REFLECT_TIR) [, detail: dict(reflect, refract (n, 3): a dielectric's two candidates, zeros elsewhere; k, fr)].
+    Records no walk gives (t, d, u, v not finite) can make words of out NaN: the contract fixes which words, not a NaN's sign or
+    payload - this processor's differ from the GPU's for a NaN an operation generates (nan_equal compares by that rule)."""
     rays, hits, surface = (np.asarray(a, F).reshape(-1, w) for a, w in ((rays, 8), (hits, 4), (surface, 16)))
     n = len(rays)
     ids = hits[:, 0].copy().view(np.int32).astype(np.int64)
@@ -91,6 +93,14 @@ def continue_rays(cs, rays, hits, surface, detail=False):
     go = cls != END
     out[go, 0:3], out[go, 3:6], out[go, 6], out[go, 7] = p[go], wo[go], KEPS, np.inf
     return (out, cls, cand) if detail else (out, cls)
+
+
+def nan_equal(got, want):
+    """(n, w) float32 arrays by the contract's rule for fabricated records -> the words that differ: a NaN word of `want` must be a
+    NaN in `got`, of any sign and payload; every other word must have want's bits"""
+    got, want = np.ascontiguousarray(got, F), np.ascontiguousarray(want, F)
+    nan = np.isnan(want)
+    return np.where(nan, ~np.isnan(got), got.view(U) != want.view(U))
 
 
 def records(cs, hits, surface):

@@ -4,9 +4,11 @@ test_gpu_parity.py::test_tuning_switches_never_change_a_bit holds one rendered f
 MATRIX: the upload and walk switches, and HJ_STREAM_MIN_NODES=0 - with one number the whole large-tree configuration: streamed
 path state, 8 x 8 camera packets, no light-shaft grid -, each with a context of its own through EVERY query that walks the
 uploaded tree with a kernel of its own: hj_trace_rays (closest hit with surface records, any-hit), hj_trace_paths with and without
-an environment, hj_trace_irradiance in both forms, hj_bake_probes, hj_render_aovs, hj_render_motion, hj_closest_points and
-hj_trace_rays_all.  The expected values are the oracle's or the numpy restatements', as the query modules cache them; hj_render_aovs'
-are the restatement over the hit records of a renderer no switch has touched (`plain`).  Never a context under the switch.
+an environment, hj_trace_irradiance in both forms, hj_bake_probes, hj_render_aovs, hj_render_motion, hj_closest_points,
+hj_trace_rays_all, and the followed calls: hj_follow_specular, hj_render_aovs_followed, hj_render_aovs_frame_followed and
+hj_render_motion_followed.  The expected values are the oracle's or the numpy restatements', as the query modules cache them; hj_render_aovs'
+and the followed calls' are the restatements over the hit records of a renderer no switch has touched (`plain`).  Never a context
+under the switch.
 FRAMES: the switches of the render calls - how the work is dealt to workgroups, batches and slots - on rendered frames against the
 oracle with the ray counts.
 Each environment also shows that it took effect where the library lets one see it; where it does not, a comment says so.
@@ -23,12 +25,14 @@ import pytest
 import allhits_cases
 import allhits_ref
 import gather_ref as G
+import motion_follow_ref as MF
 import motion_ref as M
 import path_query_ref as P
 import probe_ref
 import relayout_check as RC
 import test_allhits_gpu as AH
 import test_closest_gpu as CP
+import test_follow_gpu as FG
 import test_gather_gpu as GQ
 import test_path_query_gpu as PQ
 import test_probes_gpu as PV
@@ -99,6 +103,7 @@ ELSEWHERE = {
 N_PATHS, N_FLAT, K_ALL = 513, 1025, 3                                   # rays of a path query; points and rays of the flat queries; hits kept per ray
 GATHER = ("hemisphere-1", "sphere-sh9-4")                               # gather_ref.MODES: the hemisphere and the sphere form
 MOTION_SIZES = ((9, 9), (70, 41))
+FOLLOW_AOVS, FOLLOW_MOTION, FOLLOW_SIZE = 2, 8, (70, 41)                # max_follow of the followed AOV calls and of the followed motion image; its size
 
 
 def _id(env):
@@ -148,6 +153,15 @@ def plain():
             out["counts"], out["walk"] = tree_counts(r, _scene())
             r.upload_scene(P.scene("cbox"))
             out["free"] = r.trace_paths(P.ray_set("cbox")[:N_PATHS], opts=P.options(40), stats=True)[1]["shadow_rays_proven_free"]
+            # the followed calls: the per-record query's records and restatement, the followed sums of the ragged block list and of
+            # the 64 x 64 frame at max_follow 2, and the followed motion image at 8 with every kind moved - all on "rich" but the records
+            out["follow"] = FG.records(r)[0:4:3] + (FG.records(r)[1],)
+            out["followed"] = {key: FG.expected(r, "rich", key, FOLLOW_AOVS)[0] for key in ("ragged", "64")}
+            cs = P.scene("rich")
+            r.upload_scene(cs)
+            out["prev"] = M.Prev(cs, _cameras(cs)["translated"], **_moved(cs, 5))
+            out["motion followed"], det = MF.render_motion_followed(cs, out["prev"], *FOLLOW_SIZE, FOLLOW_MOTION, FG.gpu_trace(r), detail=True)
+            assert det["went"].sum() > 50 and det["count"].max() >= 3 and det["left"].any()
     finally:
         os.environ.update(saved)
     w, c = out["aovs"], out["counts"]
@@ -212,6 +226,14 @@ def queries(r, oracle, plain, what):
     r.upload_scene(cs)
     for W, H in MOTION_SIZES:
         check(r, oracle, cs, prev, W, H, "rest", f"render_motion {W} x {H}, {what}")
+    # hj_follow_specular on the box's records; the followed AOVs in block and in frame form and the followed motion image on "rich"
+    rays, want, hits = plain["follow"]
+    r.upload_scene(P.scene("cbox"))
+    same_bits(r.follow_specular(rays, hits), want, f"follow_specular, {what}")
+    r.upload_scene(P.scene("rich"))
+    same_bits(r.render_aovs(40, 24, blocks=FG.ragged_blocks(), follow=FOLLOW_AOVS), plain["followed"]["ragged"], f"render_aovs followed, blocks, {what}")
+    same_bits(r.render_aovs(64, 64, spp=2, master_seed=31, follow=FOLLOW_AOVS), plain["followed"]["64"], f"render_aovs followed, frame, {what}")
+    same_bits(r.render_motion(plain["prev"], *FOLLOW_SIZE, follow=FOLLOW_MOTION), plain["motion followed"], f"render_motion followed, {what}")
     # hj_closest_points and hj_trace_rays_all read the verbatim copy at root2: no re-layout switch may move them
     cs, _, pts, want = CP.case("mesh")
     fed = AH.upload(r, cs, "host_tree")                                 # (asserts that the second copy is the uploaded array)

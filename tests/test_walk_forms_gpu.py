@@ -4,6 +4,8 @@ itself: the 8 x 8 tile grouping (HJ_GROUP_TILE=1; by default from HJ_STREAM_MIN_
 The motion image against motion_ref over the oracle's first hits, from 1 x 1 over sizes one pixel into the next tile to the side
 limit of 16384; every pixel written exactly once and nothing beyond the image, into a view in the middle of a tensor of sentinels;
 the tile form against the row form.  The AOV sums against aov_ref over hj_trace_rays' records of a renderer WITHOUT a switch.
+The followed calls - hj_render_motion_followed at max_follow 8, hj_render_aovs_followed and its frame form at 2 - in the same forms,
+against motion_follow_ref and follow_ref over that renderer's records: their rounds walk lists in the switched segments.
 A switch is in the environment before the test's own renderer is created and its scene uploaded: the table is read there."""
 import ctypes as C
 import os
@@ -11,8 +13,11 @@ import os
 import numpy as np
 import pytest
 
+import motion_follow_ref as MF
 import motion_ref as M
 import path_query_ref as P
+import test_follow_gpu as FG
+import test_motion_follow_gpu as MFG
 from hijiki_amd import abi, device, host
 from test_abi import ROOT
 from test_aov_gpu import expected_aovs, ragged_blocks, same_bits
@@ -208,3 +213,53 @@ def test_aovs_in_every_form(plain, monkeypatch, name, env):
         one = r.render_aovs(32, 32, blocks=[P.camera_block()])
         same_bits(one[..., 4:8], want["samples"][..., 4:8], f"normal and t, {what}")
         assert (one[..., 3] == 1).all() and ((one[..., 11] == 1) == (want["samples"][..., 7] != 0)).all() and (one[..., 11] == 1).any()
+
+
+# ------------------------------------------------------------------------------------------------------------ the followed calls
+
+FOLLOWED_KEYS = ("ragged", "overlapping", "130")                        # test_follow_gpu.BLOCKS: the two 40 x 24 lists and FRAME
+_FOLLOWED_MOTION = {}
+
+
+def expected_followed_motion(plain, name):
+    """once, on the renderer without a switch and before any is set: motion_follow_ref's images at max_follow 8 over hj_trace_rays'
+    records, every kind moved -> (prev, {size: image})"""
+    if name not in _FOLLOWED_MOTION:
+        assert not any(k in os.environ for k in (TILE, PAIRS, WG))
+        cs = P.scene(name)
+        plain.upload_scene(cs)
+        prev = MFG._prev(cs)
+        out = {}
+        for W, H in SIZES:
+            out[W, H], det = MF.render_motion_followed(cs, prev, W, H, 8, FG.gpu_trace(plain), detail=True)
+            out[W, H].setflags(write=False)
+        assert det["went"].sum() > 50 and (det["count"].max() >= 3 or name == "cbox")         # (70 x 41)
+        _FOLLOWED_MOTION[name] = (prev, out)
+    return _FOLLOWED_MOTION[name]
+
+
+@pytest.mark.parametrize("env", SWITCHES, ids=_id)
+@pytest.mark.parametrize("name", ["cbox", "rich"])
+def test_followed_motion_at_every_size_in_every_form(plain, monkeypatch, name, env):
+    """hj_render_motion_followed: k_mv_walk's entries in the switched form, then the rounds' lists in segments of 64 or 100"""
+    prev, want = expected_followed_motion(plain, name)
+    switch_on(monkeypatch, env)
+    with device.Renderer(0) as r:
+        r.upload_scene(P.scene(name))
+        for W, H in SIZES:
+            same_bits(r.render_motion(prev, W, H, follow=8), want[W, H], f"followed motion {name} {W} x {H}, {_id(env)}")
+
+
+@pytest.mark.parametrize("env", SWITCHES, ids=_id)
+@pytest.mark.parametrize("name", ["cbox", "rich"])
+def test_followed_aovs_in_every_form(plain, monkeypatch, name, env):
+    """hj_render_aovs_followed and its frame form at max_follow 2 against follow_ref's chains over the plain renderer's records"""
+    wants = {key: FG.expected(plain, name, key, 2)[0] for key in FOLLOWED_KEYS}
+    what = f"{name}, {_id(env)}"
+    switch_on(monkeypatch, env)
+    with device.Renderer(0) as r:
+        r.upload_scene(P.scene(name))
+        for key in ("ragged", "overlapping"):
+            same_bits(r.render_aovs(40, 24, blocks=FG.BLOCKS[key][2](), follow=2), wants[key], f"followed {key} blocks, {what}")
+        W, H, spp, seed = FRAME
+        same_bits(r.render_aovs(W, H, spp=spp, master_seed=seed, follow=2), wants["130"], f"followed frame form, {what}")
