@@ -75,7 +75,8 @@ MOTION_NONE = 0xFFFFFFFF          # ... its word 3 for a pixel without a previou
 MOTION_DEVICE_SHAPES = 1          # hj_render_motion flag: the previous shape arrays are device pointers
 MOTION_DEVICE_OUT = 2             # ... the motion image is a device pointer
 MOTION_LEFT = 0xFFFFFFFE          # hj_render_motion_followed: word 3 of a pixel whose chain left a specular surface and hit nothing
-VERSION = (0, 31, 0)              # the ABI this mirror describes: hj_version() == (major << 16) | (minor << 8) | patch
+PROBE_LIT_WORDS = 4               # words of a probe-lit pixel (hj_render_probe_lit): the sums of L.rgb, the sample count
+VERSION = (0, 32, 0)              # the ABI this mirror describes: hj_version() == (major << 16) | (minor << 8) | patch
 
 
 def probe_vis_words(res):
@@ -257,6 +258,13 @@ class ProbeVisDesc(C.Structure):
     """hj_probe_vis_desc (ABI 0.21): the octahedral map, the bake's rays and the look-up's bias and switches of
     hj_probe_visibility_rays / hj_bake_probe_visibility / hj_sample_probes_visible."""
     _fields_ = [("res", u32), ("rays_per_texel", u32), ("max_distance", f32), ("normal_bias", f32), ("flags", u32)]
+
+
+class ProbeLighting(C.Structure):
+    """hj_probe_lighting (ABI 0.32): the volume hj_render_probe_lit / hj_render_probe_lit_frame light a frame from - the grid, the
+    visibility desc (NULL: hj_sample_probes' weights alone) and the probes, atlas and placement as the selected look-up takes them."""
+    _fields_ = [("desc", C.POINTER(ProbeDesc)), ("vis", C.POINTER(ProbeVisDesc)), ("probes", C.c_void_p), ("atlas", C.c_void_p),
+                ("placement", C.c_void_p)]
 
 
 class ProbeUpdate(C.Structure):

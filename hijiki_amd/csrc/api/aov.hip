@@ -11,6 +11,8 @@
 //               the stream orders them - block order without an atomic.
 //   followed:   hj_render_aovs_followed, hj_render_aovs_frame_followed: the same checks, runs and camera walk; behind each walk launch
 //               the follow rounds and in k_aov_resolve's place the followed resolve, both api/follow.hip's (kernels/hj_follow.h)
+//   for api/probe_lit.hip: aov_check, aov_frame_blocks and aov_render with an AovStage (hj_internal.h) - its image, its stage behind
+//               the follow rounds and its resolve in the AOV resolves' place; without one aov_render enqueues what it always did
 #include "hj_internal.h"
 #include "../kernels/hj_aov.h"
 
@@ -59,6 +61,10 @@ std::vector<size_t> cut_runs(const hj_image_block* blocks, size_t n, uint32_t wi
   return ends;
 }
 
+}  // namespace
+
+namespace hjapi {
+
 // What both AOV calls refuse of (blocks, image, flags, aov), without a device, in the header's order
 int aov_check(hj_context* ctx, const char* fn, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags,
               const float* aov) {
@@ -82,12 +88,13 @@ int aov_check(hj_context* ctx, const char* fn, const hj_image_block* blocks, siz
 
 // Behind the checks and the gate: the image zeroed, then walk launches and their runs' resolves in list order.  max_follow > 0
 // (the followed calls): behind each walk launch the follow rounds of api/follow.hip, and a launch that took one resolves through its
-// resolve; max_follow == 0 enqueues exactly what it always did.
+// resolve; max_follow == 0 enqueues exactly what it always did.  stage (api/probe_lit.hip): the image has stage->words floats a pixel,
+// stage->points runs behind the rounds of each walk launch and stage->resolve takes the place of both resolves.
 int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags,
-               float* aov, uint32_t max_follow = 0u) {
+               float* aov, uint32_t max_follow, const AovStage* stage) {
   HJ_HIP(ctx, hipSetDevice(ctx->device));
   const bool on_device = (flags & HJ_AOV_DEVICE_ARRAY) != 0;
-  const size_t image_bytes = (size_t)width * height * HJ_AOV_WORDS * sizeof(float);
+  const size_t image_bytes = (size_t)width * height * (stage ? stage->words : (uint32_t)HJ_AOV_WORDS) * sizeof(float);
   hj_context::Aov& q = ctx->aov;
   float4* d_aov = reinterpret_cast<float4*>(aov);
   if (!on_device) {
@@ -102,6 +109,7 @@ int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, si
     HJ_TRY(dev_alloc(ctx, q.blocks, num_blocks * sizeof(hj_image_block)));
     HJ_TRY(dev_alloc(ctx, q.hits, std::min(num_blocks, per_launch) * hj::kSlotsPerBlock * sizeof(float4)));
     if (max_follow != 0) HJ_TRY(aov_follow_reserve(ctx, std::min(num_blocks, per_launch) * hj::kSlotsPerBlock));
+    if (stage) HJ_TRY(stage->reserve(ctx, *stage, std::min(num_blocks, per_launch) * hj::kSlotsPerBlock));
     d_blocks = static_cast<const hj_image_block*>(q.blocks.p);
     d_hits = static_cast<float4*>(q.hits.p);
   }
@@ -122,12 +130,14 @@ int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, si
     e = hipGetLastError();
     bool followed = false;
     if (e == hipSuccess && max_follow != 0) e = aov_follow_rounds(ctx, d_blocks + c0, nb, d_hits, max_follow, followed);
+    if (e == hipSuccess && stage) e = stage->points(ctx, *stage, d_blocks + c0, nb, d_hits, followed);
     // the parts of the runs that lie in [c0, c1), in order
     for (size_t at = c0; at < c1 && e == hipSuccess;) {
       while (ends[run] <= at) run++;
       const size_t to = std::min(c1, ends[run]);
       const uint32_t b0 = (uint32_t)(at - c0), cnt = (uint32_t)(to - at);
-      if (followed) aov_follow_resolve(ctx, d_blocks + c0, nb, b0, cnt, d_hits, width, height, d_aov);
+      if (stage) stage->resolve(ctx, *stage, d_blocks + c0, nb, b0, cnt, d_hits, followed, width, height, d_aov);
+      else if (followed) aov_follow_resolve(ctx, d_blocks + c0, nb, b0, cnt, d_hits, width, height, d_aov);
       else hipLaunchKernelGGL(hj::k_aov_resolve, per_lane(cnt * hj::kSlotsPerBlock), blk, 0, s, sc, d_blocks + c0, nb, b0, cnt,
                               static_cast<const float4*>(d_hits), width, height, d_aov);
       e = hipGetLastError();
@@ -138,7 +148,20 @@ int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, si
   return drain(ctx, fn, e);
 }
 
-}  // namespace
+// The block list of hj_render_frame for world == 1 (frame_blocks_append: one text for both), whole: 40 bytes a block.
+int aov_frame_blocks(hj_context* ctx, const char* fn, uint32_t width, uint32_t height, uint64_t master_seed, uint32_t pass_begin, uint32_t pass_end,
+                     std::vector<hj_image_block>& blocks) {
+  try {
+    const hijiki::BlockGrid grid(width, height, HJ_BLOCK_SIZE);
+    blocks.reserve((size_t)(pass_end - pass_begin) * grid.per_pass());
+    frame_blocks_append(grid, master_seed, pass_begin, pass_end, 0u, 1u, false, blocks);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, HJ_ERR_NOMEM, "%s: no memory for the block list of %u passes", fn, pass_end - pass_begin);
+  }
+  return HJ_OK;
+}
+
+}  // namespace hjapi
 
 extern "C" {
 
@@ -167,7 +190,7 @@ int hj_eval_materials(hj_context* ctx, const float* hits, const float* surface, 
 int hj_render_aovs(hj_context* ctx, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags, float* aov) {
   HJ_TRY(aov_check(ctx, __func__, blocks, num_blocks, width, height, flags, aov));
   HJ_TRY(query_gate(ctx, __func__));
-  return aov_render(ctx, __func__, blocks, num_blocks, width, height, flags, aov);
+  return aov_render(ctx, __func__, blocks, num_blocks, width, height, flags, aov, 0u, nullptr);
 }
 
 // hj_render_aovs with the chains followed through at most max_follow specular surfaces (api/follow.hip); 0: hj_render_aovs' launches
@@ -176,10 +199,9 @@ int hj_render_aovs_followed(hj_context* ctx, const hj_image_block* blocks, size_
   HJ_TRY(aov_check(ctx, __func__, blocks, num_blocks, width, height, flags, aov));
   if (max_follow > HJ_AOV_MAX_FOLLOW) return set_error(ctx, HJ_ERR_INVALID, "%s: max_follow %u above %u", __func__, max_follow, (unsigned)HJ_AOV_MAX_FOLLOW);
   HJ_TRY(query_gate(ctx, __func__));
-  return aov_render(ctx, __func__, blocks, num_blocks, width, height, flags, aov, max_follow);
+  return aov_render(ctx, __func__, blocks, num_blocks, width, height, flags, aov, max_follow, nullptr);
 }
 
-// The block list is hj_render_frame's for world == 1 (frame_blocks_append: one text for both), whole: 40 bytes a block.
 static int aov_render_frame(hj_context* ctx, const char* fn, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
                             uint32_t pass_end, uint32_t max_follow, uint32_t flags, float* aov) {
   HJ_TRY(aov_check(ctx, fn, nullptr, 0, width, height, flags, aov));
@@ -187,14 +209,8 @@ static int aov_render_frame(hj_context* ctx, const char* fn, uint32_t width, uin
   if (pass_begin > pass_end || pass_end > spp) return set_error(ctx, HJ_ERR_INVALID, "%s: bad pass range [%u,%u) of %u", fn, pass_begin, pass_end, spp);
   HJ_TRY(query_gate(ctx, fn));
   std::vector<hj_image_block> blocks;
-  try {
-    const hijiki::BlockGrid grid(width, height, HJ_BLOCK_SIZE);
-    blocks.reserve((size_t)(pass_end - pass_begin) * grid.per_pass());
-    frame_blocks_append(grid, master_seed, pass_begin, pass_end, 0u, 1u, false, blocks);
-  } catch (const std::bad_alloc&) {
-    return set_error(ctx, HJ_ERR_NOMEM, "%s: no memory for the block list of %u passes", fn, pass_end - pass_begin);
-  }
-  return aov_render(ctx, fn, blocks.data(), blocks.size(), width, height, flags, aov, max_follow);
+  HJ_TRY(aov_frame_blocks(ctx, fn, width, height, master_seed, pass_begin, pass_end, blocks));
+  return aov_render(ctx, fn, blocks.data(), blocks.size(), width, height, flags, aov, max_follow, nullptr);
 }
 
 int hj_render_aovs_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin, uint32_t pass_end,

@@ -85,6 +85,11 @@
 //                         query (includes kernels/hj_follow.h, which includes hj_aov.h and hj_compact.h and edits none: k_follow;
 //                         k_af_count / k_af_scan / k_af_scatter, the live chains in order; k_aov_follow, the persistent walk with a
 //                         fetch that continues a chain from its state; k_aov_resolve_followed)
+//   api/probe_lit.hip     hj_render_probe_lit, hj_render_probe_lit_frame: hj_render_aovs_followed's samples lit at their last diffuse hit by a
+//                         probe volume - aov_render (api/aov.hip) with an AovStage: behind each walk launch and its follow rounds
+//                         k_pl_points, the volume's own look-up kernel over those points (probe_sample_enqueue,
+//                         probe_vis_sample_enqueue: the units that hold the kernels launch them) and per run k_pl_resolve (includes
+//                         kernels/hj_probe_lit.h, which includes hj_follow.h without its kernels and edits none)
 //   api/denoise.hip       hj_denoise_frame: the variance-guided a-trous filter over a frame's albedo-demodulated light, guided by the
 //                         frame's AOV sums (includes kernels/hj_denoise.h and hj_num.h alone: k_dn_prepare, k_dn_variance, the
 //                         iteration as k_dn_filter_lds or k_dn_filter_direct, k_dn_finish); the checks, the buffers, the prepare
@@ -499,6 +504,11 @@ struct hj_context {
   // slots (4 bytes) and a count per tile of 256; hj_follow_specular the staging of host-side rays in and out (32 bytes a record each).
   struct Aov { hjapi::DevBuf blocks, hits, image, in_hits, in_surface, out, state, counts, list, in_rays, out_rays; } aov;
 
+  // hj_render_probe_lit (api/probe_lit.hip): per sample slot of one walk launch 64 bytes - the look-up point (32), the look-up's
+  // record (16), the side record (16) -; the staging of a host-side volume, atlas and placement, once a call.  The block list, the hit
+  // records, the chain state and a host-side image's staging (16 bytes a pixel) are Aov's.  Grown on demand, freed with the context.
+  struct ProbeLit { hjapi::DevBuf points, lookup, side, volume, atlas, placement; } probe_lit;
+
   // hj_denoise_frame (api/denoise.hip): the guide (48 bytes a pixel: normal and depth, albedo and valid word, depth slope) and the
   // two working images (16 bytes a pixel each); the staging of host arrays - beauty, AOV image, result (16, 48 and 16 bytes a
   // pixel).  Grown on demand, reused by every call, freed with the context.  The framebuffer is read, never written.
@@ -635,6 +645,39 @@ int aov_follow_reserve(hj_context* ctx, size_t slots);
 hipError_t aov_follow_rounds(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, float4* d_hits, uint32_t max_follow, bool& followed);
 void aov_follow_resolve(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, uint32_t b0, uint32_t cnt, const float4* d_hits, uint32_t width,
                         uint32_t height, float4* d_aov);
+// api/aov.hip, for api/probe_lit.hip: the AOV calls' refusals (aov_check), the frame forms' block list (aov_frame_blocks) and their
+// host routine (aov_render) with a stage that takes the resolves' place.  stage == nullptr: the AOV calls themselves.
+//   words    floats a pixel of the stage's image (the AOV image: HJ_AOV_WORDS)
+//   reserve  room for walk launches of at most `slots` sample slots, before anything of the call is enqueued
+//   points   behind the camera walk and the follow rounds of a walk launch of nb blocks (followed: a round ran, the chain state is set)
+//   resolve  in k_aov_resolve's / aov_follow_resolve's place, for blocks [b0, b0 + cnt) of that launch: a run's part
+struct AovStage {
+  uint32_t words;
+  int (*reserve)(hj_context* ctx, const AovStage& st, size_t slots);
+  hipError_t (*points)(hj_context* ctx, const AovStage& st, const hj_image_block* d_blocks, uint32_t nb, const float4* d_hits, bool followed);
+  void (*resolve)(hj_context* ctx, const AovStage& st, const hj_image_block* d_blocks, uint32_t nb, uint32_t b0, uint32_t cnt, const float4* d_hits,
+                  bool followed, uint32_t width, uint32_t height, float4* d_image);
+  void* self;
+};
+int aov_check(hj_context* ctx, const char* fn, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags,
+              const float* aov);
+int aov_frame_blocks(hj_context* ctx, const char* fn, uint32_t width, uint32_t height, uint64_t master_seed, uint32_t pass_begin, uint32_t pass_end,
+                     std::vector<hj_image_block>& blocks);
+int aov_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t flags,
+               float* aov, uint32_t max_follow, const AovStage* stage);
+// The look-ups' launches for api/probe_lit.hip, each by the unit that holds the kernel, over m (> 0) device points on the context's
+// stream: api/probe_volume.hip's k_pv_sample; api/probe_visibility.hip's k_pvv_sample, or with `placed` (api/probe_place.hip's
+// probe_place_sample_launch) and d_place k_pp_sample.  The launch shape is the public calls' own: they enter here too.
+void probe_sample_enqueue(hj_context* ctx, const hj::PvGrid& g, const float4* d_probes, const float4* d_points, uint32_t m, float4* d_out);
+void probe_vis_sample_enqueue(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, const float4* d_probes, const float2* d_atlas, const float4* d_place,
+                              const float4* d_points, uint32_t m, float4* d_out, ProbeVisSampleLaunch placed);
+void probe_place_sample_launch(hipStream_t s, uint32_t blocks, const hj::PvGrid& g, const hj::PvvMap& v, const float4* d_probes, const float2* d_atlas,
+                               const float4* d_place, const float4* d_points, uint32_t m, float4* d_out);
+// api/probe_visibility.hip: what hj_sample_probes_visible (placed: hj_sample_probes_visible_placed) refuses of a volume - the descs, the
+// probes, the atlas, the placement - in that call's order, the points and `out` aside -> g, n, v, reads_atlas.  any: the call has points
+// (the look-ups accept null arrays without).
+int probe_vis_volume_check(hj_context* ctx, const char* fn, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes, const float* atlas,
+                           const float* placement, bool placed, bool any, hj::PvGrid& g, uint32_t& n, hj::PvvMap& v, bool& reads_atlas);
 }  // namespace hjapi
 namespace hj { struct DtArgs; }                  // kernels/hj_denoise_temporal.h
 namespace hjapi {

@@ -64,6 +64,13 @@ void launch_placed_sample(hipStream_t s, uint32_t blocks, const hj::PvGrid& g, c
 
 }  // namespace
 
+namespace hjapi {   // for api/probe_lit.hip (hj_internal.h)
+void probe_place_sample_launch(hipStream_t s, uint32_t blocks, const hj::PvGrid& g, const hj::PvvMap& v, const float4* d_probes, const float2* d_atlas,
+                               const float4* d_place, const float4* d_points, uint32_t m, float4* d_out) {
+  launch_placed_sample(s, blocks, g, v, d_probes, d_atlas, d_place, d_points, m, d_out);
+}
+}  // namespace hjapi
+
 extern "C" {
 
 // The argument checks come first and need neither a device nor a context's state (hj_update_probe_visibility's order and style).

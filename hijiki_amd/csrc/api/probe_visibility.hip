@@ -72,6 +72,31 @@ int probe_place_check_offsets(hj_context* ctx, const char* fn, const float* plac
   return HJ_OK;
 }
 
+// k_pvv_sample - or through `placed` k_pp_sample - over m (> 0) device points: enough workgroups to fill the device, no more than the
+// points need; the kernel strides over the rest
+void probe_vis_sample_enqueue(hj_context* ctx, const hj::PvGrid& g, const hj::PvvMap& v, const float4* d_probes, const float2* d_atlas, const float4* d_place,
+                              const float4* d_points, uint32_t m, float4* d_out, ProbeVisSampleLaunch placed) {
+  const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)m + hj::kPvvThreads - 1u) / hj::kPvvThreads, (size_t)ctx->num_cus * 8u);
+  if (placed) placed(ctx->stream, blocks, g, v, d_probes, d_atlas, d_place, d_points, m, d_out);
+  else hipLaunchKernelGGL(hj::k_pvv_sample, dim3(blocks), dim3(hj::kPvvThreads), 0, ctx->stream, g, v, d_probes, d_atlas, d_points, m, d_out);
+}
+
+// probe_vis_sample's refusals of the volume alone, in its order, for hj_render_probe_lit (api/probe_lit.hip), which brings the points itself
+int probe_vis_volume_check(hj_context* ctx, const char* fn, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes, const float* atlas,
+                           const float* placement, bool placed, bool any, hj::PvGrid& g, uint32_t& n, hj::PvvMap& v, bool& reads_atlas) {
+  const uint32_t both_off = HJ_PROBE_VIS_NO_BACKFACE | HJ_PROBE_VIS_NO_CHEBYSHEV;
+  reads_atlas = vis && (vis->flags & both_off) != both_off;
+  const bool no_place = placed && !placement;
+  if (!desc || !vis || no_place || (any && (!probes || (reads_atlas && !atlas))))
+    return set_error(ctx, HJ_ERR_INVALID, "%s: null %s", fn, !desc ? "desc" : !vis ? "vis" : no_place ? "placement" : !probes ? "probes" : "atlas");
+  HJ_TRY(check_descs(ctx, fn, Call::kSample, desc, vis, g, n, v));
+  const bool on_device = (vis->flags & HJ_PROBE_VIS_DEVICE_ARRAYS) != 0;
+  if (on_device && any && (misaligned(probes, reads_atlas ? atlas : nullptr) || (placed && misaligned(placement))))
+    return set_error(ctx, HJ_ERR_INVALID, "%s: device arrays must be 16-byte aligned", fn);
+  if (!on_device && placed && any) HJ_TRY(probe_place_check_offsets(ctx, fn, placement, 0u, n));
+  return HJ_OK;
+}
+
 // The host side of hj_sample_probes_visible and, with a launch of its kernel, of hj_sample_probes_visible_placed (api/probe_place.hip):
 // one text of the refusals, the staging and the launch shape.  placed == nullptr: no placement (the argument is not looked at).
 int probe_vis_sample(hj_context* ctx, const char* fn, const hj_probe_desc* desc, const hj_probe_vis_desc* vis, const float* probes, const float* atlas,
@@ -129,10 +154,7 @@ int probe_vis_sample(hj_context* ctx, const char* fn, const hj_probe_desc* desc,
     d_points = static_cast<const float4*>(pv.in_points.p);
     d_out = static_cast<float4*>(pv.out.p);
   }
-  // enough workgroups to fill the device, no more than the points need; the kernel strides over the rest
-  const uint32_t blocks = (uint32_t)std::min<size_t>((m + hj::kPvvThreads - 1u) / hj::kPvvThreads, (size_t)ctx->num_cus * 8u);
-  if (placed) placed(s, blocks, g, v, d_probes, d_atlas, d_place, d_points, (uint32_t)m, d_out);
-  else hipLaunchKernelGGL(hj::k_pvv_sample, dim3(blocks), dim3(hj::kPvvThreads), 0, s, g, v, d_probes, d_atlas, d_points, (uint32_t)m, d_out);
+  probe_vis_sample_enqueue(ctx, g, v, d_probes, d_atlas, d_place, d_points, (uint32_t)m, d_out, placed);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d_out, sizeof(float4) * m, hipMemcpyDeviceToHost, s);
   return drain(ctx, fn, e);

@@ -85,6 +85,11 @@ int probe_desc_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj
 void probe_points_enqueue(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t n, float4* d_points) {
   enqueue_points(ctx, g, seed, seed_stride, first, n, d_points);
 }
+// k_pv_sample over m (> 0) device points: enough workgroups to fill the device, no more than the points need; the kernel strides over the rest
+void probe_sample_enqueue(hj_context* ctx, const hj::PvGrid& g, const float4* d_probes, const float4* d_points, uint32_t m, float4* d_out) {
+  const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)m + hj::kPvThreads - 1u) / hj::kPvThreads, (size_t)ctx->num_cus * 8u);
+  hipLaunchKernelGGL(hj::k_pv_sample, dim3(blocks), dim3(hj::kPvThreads), 0, ctx->stream, g, d_probes, d_points, m, d_out);
+}
 }  // namespace hjapi
 
 extern "C" {
@@ -180,9 +185,7 @@ int hj_sample_probes(hj_context* ctx, const hj_probe_desc* desc, const float* pr
     d_points = static_cast<const float4*>(pv.in_points.p);
     d_out = static_cast<float4*>(pv.out.p);
   }
-  // enough workgroups to fill the device, no more than the points need; the kernel strides over the rest
-  const uint32_t blocks = (uint32_t)std::min<size_t>((n + hj::kPvThreads - 1u) / hj::kPvThreads, (size_t)ctx->num_cus * 8u);
-  hipLaunchKernelGGL(hj::k_pv_sample, dim3(blocks), dim3(hj::kPvThreads), 0, s, g, d_probes, d_points, (uint32_t)n, d_out);
+  probe_sample_enqueue(ctx, g, d_probes, d_points, (uint32_t)n, d_out);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d_out, sizeof(float4) * n, hipMemcpyDeviceToHost, s);
   return drain(ctx, __func__, e);

@@ -33,7 +33,8 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_update_probes_placed", "hj_update_probe_visibility_placed", "hj_sample_probes_visible_placed", "hj_closest_points",
            "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame",
            "hj_denoise_frame", "hj_denoise_frame_temporal", "hj_render_motion", "hj_denoise_frame_temporal_motion",
-           "hj_follow_specular", "hj_render_aovs_followed", "hj_render_aovs_frame_followed", "hj_render_motion_followed")
+           "hj_follow_specular", "hj_render_aovs_followed", "hj_render_aovs_frame_followed", "hj_render_motion_followed",
+           "hj_render_probe_lit", "hj_render_probe_lit_frame")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -129,6 +130,10 @@ def lib():
         L.hj_follow_specular.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp]                    # (host or device pointers)
         L.hj_render_aovs_followed.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.hj_render_aovs_frame_followed.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.hj_render_probe_lit.argtypes = [vp, C.POINTER(abi.ImageBlock), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.POINTER(abi.ProbeLighting), vp]
+        L.hj_render_probe_lit_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(abi.ProbeLighting), vp]
         L.hj_denoise_frame.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), vp]   # (host or device pointers)
         L.hj_denoise_frame_temporal.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp]
         L.hj_denoise_frame_temporal_motion.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp, vp]
@@ -214,6 +219,21 @@ def resolve_aovs(aov):
 
     return dict(albedo=mean(aov[..., 0:3], samples), normal=mean(aov[..., 4:7], hits), depth=mean(aov[..., 7], hits),
                 emission=mean(aov[..., 8:11], samples), coverage=mean(hits, samples))
+
+
+def resolve_probe_lit(image):
+    """The (height, width, 4) sums of `Renderer.render_probe_lit` as the mean radiance -> (height, width, 3): words 0..2 over the
+    sample count (word 3), 0 where no sample fell.  A numpy array gives a numpy array, a torch tensor a tensor on its device."""
+    if type(image).__module__.split(".")[0] == "torch":
+        import torch
+        where, zero = torch.where, torch.zeros((), dtype=image.dtype, device=image.device)
+    else:
+        image = np.asarray(image, np.float32)
+        where, zero = np.where, np.float32(0)
+    if image.ndim != 3 or image.shape[2] != abi.PROBE_LIT_WORDS:
+        raise ValueError(f"resolve_probe_lit: (height, width, {abi.PROBE_LIT_WORDS}) is needed (got {tuple(image.shape)})")
+    c = image[..., 3:4]
+    return where(c > 0, image[..., 0:3] / where(c > 0, c, zero + 1), zero)
 
 
 def motion_ids(m):
@@ -820,6 +840,65 @@ class Renderer:
             else:
                 self._check(lib().hj_render_aovs_frame(self._h, width, height, int(spp), int(master_seed), begin, end, flags, ptr))
         return aov
+
+    def render_probe_lit(self, volume, origin, spacing, width, height, atlas=None, placement=None, normal_bias=0.0, backface=True, chebyshev=True,
+                         blocks=None, spp=None, master_seed=0, passes=None, follow=0, device=None):
+        """hj_render_probe_lit / hj_render_probe_lit_frame: the frame a probe volume is for -> (height, width, 4) float32: per pixel
+        the float32 sums, in block order, of its samples' radiance L and the sample count - `resolve_probe_lit` gives the mean.  The
+        samples and their chains through up to `follow` (0 ... abi.AOV_MAX_FOLLOW) mirrors and glass surfaces are `render_aovs(...,
+        follow=)`'s; a chain's last hit gets L = emission + albedo * E / pi with E the look-up of the (nz, ny, nx, 28) `volume` at the
+        hit point under the hit's shading normal: `sample_probes` without an atlas, `sample_probes_visible` with one (normal_bias,
+        backface, chebyshev as there), its placed form with a `placement`.  A chain the cap cuts on a mirror or on glass gives 0, a
+        miss the uploaded environment's radiance or 0.  blocks, or spp [, master_seed, passes], as in `render_aovs`.  numpy arrays give a
+        numpy array; contiguous float32 torch tensors on the renderer's GPU (volume, atlas and placement alike; device=None decides by
+        the volume's type) are read in place and give a tensor on that GPU; torch's current stream is synchronised first.  Needs no
+        framebuffer and leaves it alone."""
+        what = "render_probe_lit"
+        if (blocks is None) == (spp is None):
+            raise ValueError(f"{what}: either blocks or spp is needed")
+        follow = int(follow)
+        if not 0 <= follow <= abi.AOV_MAX_FOLLOW:
+            raise ValueError(f"{what}: follow {follow}: 0 ... {abi.AOV_MAX_FOLLOW}")
+        on_gpu = type(volume).__module__.split(".")[0] == "torch" if device is None else bool(device)
+        if volume.ndim != 4 or volume.shape[3] != abi.PROBE_WORDS:
+            raise ValueError(f"{what}: a volume of (nz, ny, nx, {abi.PROBE_WORDS}) is needed (got {tuple(volume.shape)})")
+        if placement is not None and atlas is None:
+            raise ValueError(f"{what}: a placement needs an atlas")
+        if atlas is not None and (atlas.ndim != 6 or tuple(atlas.shape[0:3]) != tuple(volume.shape[0:3]) or atlas.shape[3] != atlas.shape[4] or atlas.shape[5] != 2):
+            raise ValueError(f"{what}: an atlas of (nz, ny, nx, res + 2, res + 2, 2) on the volume's grid is needed (got {tuple(atlas.shape)})")
+        count = (int(volume.shape[2]), int(volume.shape[1]), int(volume.shape[0]))
+        d = self._probe_desc(what, origin, spacing, count, device=on_gpu)
+        v = None
+        if atlas is not None:
+            v = self._probe_vis_desc(what, int(atlas.shape[3]) - 2, normal_bias=normal_bias, backface=backface, chebyshev=chebyshev, device=on_gpu)
+        place_ptr = None
+        if placement is not None:
+            _, placement, place_ptr = self._placement(what, placement, d, on_gpu)
+        width, height = int(width), int(height)
+        if on_gpu:
+            import torch
+            for name, t in (("volume", volume),) + ((("atlas", atlas),) if atlas is not None else ()):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                    raise ValueError(f"{what}: {name} must be a contiguous float32 tensor on cuda:{self.device}")
+            image = torch.empty((height, width, abi.PROBE_LIT_WORDS), dtype=torch.float32, device=volume.device)
+            torch.cuda.current_stream(volume.device).synchronize()    # (the allocation and whatever wrote the tensors)
+            ptr, flags = image.data_ptr(), abi.AOV_DEVICE_ARRAY
+            vol_ptr, atlas_ptr = volume.data_ptr(), atlas.data_ptr() if atlas is not None else None
+        else:
+            vol = np.ascontiguousarray(volume, np.float32)
+            atl = np.ascontiguousarray(atlas, np.float32) if atlas is not None else None
+            image = np.zeros((height, width, abi.PROBE_LIT_WORDS), np.float32)
+            ptr, flags = image.ctypes.data, 0
+            vol_ptr, atlas_ptr = vol.ctypes.data, atl.ctypes.data if atl is not None else None
+        lighting = abi.ProbeLighting(C.pointer(d), C.pointer(v) if v is not None else None, vol_ptr, atlas_ptr, place_ptr)
+        if blocks is not None:
+            if not isinstance(blocks, C.Array):
+                blocks = (abi.ImageBlock * len(blocks))(*blocks)
+            self._check(lib().hj_render_probe_lit(self._h, blocks, len(blocks), width, height, follow, flags, C.byref(lighting), ptr))
+        else:
+            begin, end = (0, int(spp)) if passes is None else (int(passes[0]), int(passes[1]))
+            self._check(lib().hj_render_probe_lit_frame(self._h, width, height, int(spp), int(master_seed), begin, end, follow, flags, C.byref(lighting), ptr))
+        return image
 
     def render_motion(self, prev, width, height, device_arrays=None, device=False, follow=0):
         """hj_render_motion: per-pixel motion for `denoise_frame_temporal` -> (height, width, 4) float32: per pixel (sx, sy, zp, id

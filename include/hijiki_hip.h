@@ -1513,6 +1513,64 @@ int hj_render_aovs_followed(hj_context* ctx, const hj_image_block* blocks, size_
 int hj_render_aovs_frame_followed(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
                                   uint32_t pass_end, uint32_t max_follow, uint32_t flags, float* aov /* height x width x 12 */);
 
+/* Probe-lit frames (ABI 0.32): the frame a probe volume is for.  The samples are exactly hj_render_aovs_followed's - the same blocks,
+ * seeds and sample offsets, the same chains through at most max_follow specular surfaces - and each sample's last diffuse hit is lit
+ * from the volume by the look-up the caller selects: noise-free diffuse lighting at the cost of a first-hit walk, with mirrors and
+ * glass showing the lit scene.  No counterpart in the reference; tests/probe_lit_ref.py restates the contract in numpy.
+ *
+ * hj_probe_lighting:  desc is the volume's grid (hj_probe_desc, as the look-ups take it); its flags - with vis, vis->flags, which must
+ *     agree - say whether probes, atlas and placement are host arrays or device pointers, as in the look-up selected:
+ *       vis == NULL                      hj_sample_probes: the trilinear and validity weights alone; atlas and placement are not read
+ *       vis != NULL, placement == NULL   hj_sample_probes_visible, with vis' normal_bias and its two switches
+ *       vis != NULL, placement != NULL   hj_sample_probes_visible_placed
+ *     Host arrays are staged once a call.
+ * hj_render_probe_lit:  every sample's chain is hj_render_aovs_followed's.  Its radiance L, float32:
+ *     - the chain's last hit is a mirror or a dielectric (the cap, max_follow, cut it there; max_follow == 0: the first hit is one):
+ *       L = that surface's emission, which a material record has as 0.  No diffuse term.
+ *     - any other hit: with (albedo, n, Le) the words of hj_render_aovs' record at the last hit and p the populated hit point the
+ *       record is built from (fma(t, d, o) over the chain's last segment), E = words 0..2 of the selected look-up at the 8-word point
+ *       (p, n, 0, 0), bit for bit what that call writes to `out`, and
+ *           L[c] = Le[c] + (albedo[c] * E[c]) * 0.318309886f
+ *       one rounding each, no contraction, in that order.  The constant is the shade stage's own 1 / pi (1.0f / 3.14159274f), whose
+ *       bits are the literal's.
+ *     - nothing was hit, from the camera or after leaving a specular surface, and hj_scene_upload_env is in effect: L = the
+ *       environment's radiance along the last segment's direction, as hj_debug_env_lookup gives it for that direction.
+ *     - nothing was hit and there is no environment: L = 0.
+ *   image: height x width x HJ_PROBE_LIT_WORDS floats, OVERWRITTEN: words 0..2 of pixel (origin + l) are the float32 sums of L over its
+ *     samples, block by block in the order of the list, starting from +0; word 3 is the count of its samples, every one of them, so
+ *     rgb / count is the mean radiance.  A pixel no sample covers is four zeros.  A sample depends on the blocks, the scene, the
+ *     camera, max_follow and the volume alone: not on HJ_TRACE_CHUNK or the lane that carried a chain.
+ *   What E holds is what the volume was baked from: hj_bake_probes' gather counts a first segment that ends on an emitter (or leaves
+ *     into the environment) with its radiance, so DIRECT light is in E beside the indirect, band-limited to nine SH coefficients a
+ *     probe and interpolated between probes - soft where a traced shadow is sharp.  An emitter seen directly adds its Le here.
+ *   HJ_AOV_DEVICE_ARRAY: image is a device pointer on the context's GPU, 16-byte aligned, written in place.
+ *   No framebuffer is needed, and the framebuffer and the batch slots are left alone.  The context holds 64 bytes more per sample slot
+ *     of one walk launch (HJ_TRACE_CHUNK) - the look-up point, the look-up's record, a side record (Le, kind) - beside
+ *     hj_render_aovs_followed's, and the staging of host-side volume arrays.
+ *   HJ_ERR_INVALID, before the device is touched, in this order: hj_render_aovs' refusals (the image in aov's place); max_follow above
+ *     HJ_AOV_MAX_FOLLOW; a null lighting; a placement without vis; then the refusals of the look-up selected, in that call's order, the
+ *     points and `out` - this call's own - aside: a null desc, vis, placement, probes or atlas (probes and a read atlas: with
+ *     num_blocks > 0), the descs' refusals, misaligned device arrays, a non-finite offset in a host-side placement.  A refused call
+ *     writes nothing.  Then hj_trace_rays' gate.  num_blocks == 0: HJ_OK behind the gate, an all-zero image.
+ * hj_render_probe_lit_frame:  hj_render_probe_lit over exactly the block list hj_render_frame generates for world == 1 with the same
+ *     spp, master_seed and pass range.  The bad pass range (pass_begin > pass_end or pass_end > spp) is refused behind max_follow, before
+ *     the lighting.  An empty pass range: HJ_OK, an all-zero image.
+ * Not here: a glossy lobe - the project has no such material; glass extinction along the chain; lighting from a baked light map; a
+ *   multi-GPU split; a flag of the command-line tool; separately traced direct shadows - direct light is as soft as the volume has it. */
+#define HJ_PROBE_LIT_WORDS 4
+typedef struct hj_probe_lighting {
+  const hj_probe_desc*     desc;       /* the volume's grid; its flags say host or device arrays for probes / atlas / placement */
+  const hj_probe_vis_desc* vis;        /* NULL: hj_sample_probes' weights alone                                                   */
+  const float*             probes;     /* n x 28                                                                                   */
+  const float*             atlas;      /* with vis, as hj_sample_probes_visible takes it                                           */
+  const float*             placement;  /* NULL, or n x 4 as hj_sample_probes_visible_placed takes it (needs vis)                   */
+} hj_probe_lighting;
+int hj_render_probe_lit(hj_context* ctx, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height,
+                        uint32_t max_follow, uint32_t flags, const hj_probe_lighting* lighting, float* image /* height x width x 4 */);
+int hj_render_probe_lit_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
+                              uint32_t pass_end, uint32_t max_follow, uint32_t flags, const hj_probe_lighting* lighting,
+                              float* image /* height x width x 4 */);
+
 /* ------------------------------------------- frame denoiser */
 
 /* hj_denoise_frame (ABI 0.27): the spatial filter of SVGF (Schied et al. 2017: its variance-guided a-trous stage) over one frame on
