@@ -1,15 +1,16 @@
 // hj_follow_specular, and the follow rounds of hj_render_aovs_followed / hj_render_aovs_frame_followed: what a mirror or glass shows
 // ("Followed AOVs").
 //
-// The kernels are kernels/hj_follow.h's; that header includes kernels/hj_aov.h - and through it the kernel headers up to hj_stages.h -
-// and hj_compact.h and edits none, and no other unit's machine code depends on this one.  The two frame entry points themselves, their
-// checks, the runs and the camera walk are api/aov.hip's (aov_render), which enters here behind each walk launch:
-//   per round   k_af_count -> k_af_scan -> (the live count to the host: it sizes the grid; none: the rounds end, nothing is launched)
-//               -> k_af_scatter -> k_aov_follow over the list
+// The kernels are kernels/hj_follow.h's and, behind it, kernels/hj_chain.h's: the rounds' shared text, whose count and scan kernels
+// this unit alone instantiates (api/motion_follow.hip launches them through chain_count_enqueue).  The two frame entry points
+// themselves, their checks, the runs and the camera walk are api/aov.hip's (aov_render), which enters here behind each walk launch:
+//   per round   (chain_rounds, api/chain_rounds.h) k_chain_count -> k_chain_scan -> (the live count to the host: it sizes the grid;
+//               none: the rounds end, nothing is launched) -> k_af_scatter -> k_aov_follow over the list
 //   resolve     k_aov_resolve_followed in k_aov_resolve's place for a launch that took a round
 //   per record  k_follow, one lane per record; chunks and staging through hj_context::Aov are chunked_query's (api/hj_internal.h)
 #include "hj_internal.h"
 #include "../kernels/hj_follow.h"
+#include "chain_rounds.h"
 
 #pragma clang fp contract(off)
 
@@ -17,55 +18,42 @@ using namespace hjapi;
 
 namespace hjapi {
 
-// Room for the rounds over walk launches of at most `slots` sample slots: the chain state (32 bytes a slot), the tile counts and
-// the list (4 bytes a slot).  Before anything of the call is enqueued.
-int aov_follow_reserve(hj_context* ctx, size_t slots) {
-  hj_context::Aov& q = ctx->aov;
-  HJ_TRY(dev_alloc(ctx, q.state, slots * 2 * sizeof(float4)));
-  HJ_TRY(dev_alloc(ctx, q.counts, (slots / hj::kAfThreads + 1u) * sizeof(uint32_t)));
-  return dev_alloc(ctx, q.list, slots * sizeof(uint32_t));
+// The one copy of the count and scan kernels (kernels/hj_chain.h), for this unit's rounds and api/motion_follow.hip's: the live chains
+// of n slots per tile of kChainThreads into d_counts, then their offsets in place and the total behind them.
+void chain_count_enqueue(hj_context* ctx, bool first, const float4* d_hits, const float4* d_state, uint32_t n, uint32_t max_follow, uint32_t* d_counts) {
+  const uint32_t tiles = (n + hj::kChainThreads - 1u) / hj::kChainThreads;
+  const dim3 tile(hj::kChainThreads);
+  if (first) hipLaunchKernelGGL(hj::k_chain_count<true>, dim3(tiles), tile, 0, ctx->stream, ctx->scene, d_hits, d_state, n, max_follow, d_counts);
+  else hipLaunchKernelGGL(hj::k_chain_count<false>, dim3(tiles), tile, 0, ctx->stream, ctx->scene, d_hits, d_state, n, max_follow, d_counts);
+  hipLaunchKernelGGL(hj::k_chain_scan, dim3(1), tile, 0, ctx->stream, d_counts, tiles);
 }
 
-// Behind the camera walk of nb blocks at d_blocks, whose hit records are at d_hits: at most max_follow (> 0) rounds, each over the
-// chains still live.  The stream is synchronised once a round, for the live count.  -> followed: a round ran, so the chain state is
-// set for every sample of the launch and its runs resolve through aov_follow_resolve.
+// Room for the rounds over walk launches of at most `slots` sample slots.  Before anything of the call is enqueued.
+int aov_follow_reserve(hj_context* ctx, size_t slots) { return chain_reserve(ctx, ctx->aov.chain, slots); }
+
+// Behind the camera walk of nb blocks at d_blocks, whose hit records are at d_hits: chain_rounds over the launch's sample slots.
+// -> followed: a round ran, so the chain state is set for every sample of the launch and its runs resolve through aov_follow_resolve.
 hipError_t aov_follow_rounds(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, float4* d_hits, uint32_t max_follow, bool& followed) {
-  hj_context::Aov& q = ctx->aov;
   const hj::DeviceScene& sc = ctx->scene;
   hipStream_t s = ctx->stream;
-  const uint32_t n = nb * hj::kSlotsPerBlock, tiles = n / hj::kAfThreads;
-  float4* d_state = static_cast<float4*>(q.state.p);
-  uint32_t *d_counts = static_cast<uint32_t*>(q.counts.p), *d_list = static_cast<uint32_t*>(q.list.p);
-  const dim3 tile(hj::kAfThreads);
-  followed = false;
-  for (uint32_t round = 0; round < max_follow; round++) {
-    const bool first = round == 0;
-    if (first) hipLaunchKernelGGL(hj::k_af_count<true>, dim3(tiles), tile, 0, s, sc, static_cast<const float4*>(d_hits), static_cast<const float4*>(d_state), n, max_follow, d_counts);
-    else hipLaunchKernelGGL(hj::k_af_count<false>, dim3(tiles), tile, 0, s, sc, static_cast<const float4*>(d_hits), static_cast<const float4*>(d_state), n, max_follow, d_counts);
-    hipLaunchKernelGGL(hj::k_af_scan, dim3(1), tile, 0, s, d_counts, tiles);
-    hipError_t e = hipGetLastError();
-    uint32_t count = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&count, d_counts + tiles, sizeof count, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    if (count == 0) break;                                         // (no grid of zero workgroups is ever launched)
-    if (first) hipLaunchKernelGGL(hj::k_af_scatter<true>, dim3(tiles), tile, 0, s, sc, d_blocks, nb, static_cast<const float4*>(d_hits), d_state, n, max_follow, static_cast<const uint32_t*>(d_counts), d_list);
-    else hipLaunchKernelGGL(hj::k_af_scatter<false>, dim3(tiles), tile, 0, s, sc, d_blocks, nb, static_cast<const float4*>(d_hits), d_state, n, max_follow, static_cast<const uint32_t*>(d_counts), d_list);
-    const uint32_t wg_rays = walk_wg_rays(ctx, count);              // list entries per workgroup: hj_trace_rays' rule
-    const dim3 grid((count + wg_rays - 1u) / wg_rays);
-    if (sc.has_pairs != 0) hipLaunchKernelGGL(hj::k_aov_follow<true>, grid, dim3(hj::kBlockThreads), 0, s, sc, static_cast<const uint32_t*>(d_list), count, wg_rays, d_hits, d_state);
-    else hipLaunchKernelGGL(hj::k_aov_follow<false>, grid, dim3(hj::kBlockThreads), 0, s, sc, static_cast<const uint32_t*>(d_list), count, wg_rays, d_hits, d_state);
-    if (e = hipGetLastError(); e != hipSuccess) return e;
-    followed = true;
-  }
-  return hipSuccess;
+  const uint32_t n = nb * hj::kSlotsPerBlock;
+  return chain_rounds(
+      ctx, ctx->aov.chain, d_hits, n, max_follow,
+      [&](auto first, dim3 tiles, float4* d_state, const uint32_t* d_offsets, uint32_t* d_list) {
+        hipLaunchKernelGGL(hj::k_af_scatter<decltype(first)::value>, tiles, dim3(hj::kChainThreads), 0, s, sc, d_blocks, nb, static_cast<const float4*>(d_hits),
+                           d_state, n, max_follow, d_offsets, d_list);
+      },
+      [&](auto pairs, dim3 grid, const uint32_t* d_list, uint32_t count, uint32_t wg_rays, float4* d_state) {
+        hipLaunchKernelGGL(hj::k_aov_follow<decltype(pairs)::value>, grid, dim3(hj::kBlockThreads), 0, s, sc, d_list, count, wg_rays, d_hits, d_state);
+      },
+      followed);
 }
 
 // k_aov_resolve's launch for a run of a followed walk launch
 void aov_follow_resolve(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, uint32_t b0, uint32_t cnt, const float4* d_hits, uint32_t width,
                         uint32_t height, float4* d_aov) {
   hipLaunchKernelGGL(hj::k_aov_resolve_followed, per_lane(cnt * hj::kSlotsPerBlock), dim3(hj::kBlockThreads), 0, ctx->stream, ctx->scene, d_blocks, nb, b0, cnt,
-                     d_hits, static_cast<const float4*>(ctx->aov.state.p), width, height, d_aov);
+                     d_hits, static_cast<const float4*>(ctx->aov.chain.state.p), width, height, d_aov);
 }
 
 }  // namespace hjapi

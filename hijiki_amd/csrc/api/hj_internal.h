@@ -82,9 +82,13 @@
 //                         fetch that builds the camera ray from the sample index; k_aov_resolve, run by run of disjoint blocks)
 //   api/follow.hip        hj_follow_specular, and the follow rounds of hj_render_aovs_followed / hj_render_aovs_frame_followed (whose entry
 //                         points, checks and camera walk are api/aov.hip's): the chain through mirror and glass as a deterministic
-//                         query (includes kernels/hj_follow.h, which includes hj_aov.h and hj_compact.h and edits none: k_follow;
-//                         k_af_count / k_af_scan / k_af_scatter, the live chains in order; k_aov_follow, the persistent walk with a
-//                         fetch that continues a chain from its state; k_aov_resolve_followed)
+//                         query (includes kernels/hj_follow.h, which includes hj_aov.h and hj_chain.h and edits none: k_follow;
+//                         k_chain_count / k_chain_scan - the one copy, chain_count_enqueue below - and k_af_scatter, the live chains
+//                         in order; k_aov_follow, the persistent walk with a fetch that continues a chain from its state;
+//                         k_aov_resolve_followed)
+//   api/chain_rounds.h    the host side of a chain's rounds for api/follow.hip and api/motion_follow.hip: ChainBufs' reserve and the
+//                         loop count -> scan -> live count to the host -> scatter -> round (the kernels' shared bodies:
+//                         kernels/hj_chain.h, on kernels/hj_walk_segment.h, the shell of the flat segment walks)
 //   api/probe_lit.hip     hj_render_probe_lit, hj_render_probe_lit_frame: hj_render_aovs_followed's samples lit at their last diffuse hit by a
 //                         probe volume - aov_render (api/aov.hip) with an AovStage: behind each walk launch and its follow rounds
 //                         k_pl_points, the volume's own look-up kernel over those points (probe_sample_enqueue,
@@ -106,10 +110,10 @@
 //                         of hj_denoise_temporal.h and edits none); and the one instantiation of k_dt_accumulate<true>; motion_render, the
 //                         host routine of both motion calls
 //   api/motion_follow.hip hj_render_motion_followed: the motion image through mirrors and glass - between k_mv_walk and the resolve the
-//                         rounds k_mf_count / k_mf_scan / k_mf_scatter, the live pixels in order, and k_mf_follow, the persistent walk
-//                         with a fetch that continues a chain from its state and carries the product of its reflections; k_mf_resolve
-//                         (includes kernels/hj_motion_follow.h, which includes hj_motion.h and hj_follow.h without their kernels and
-//                         hj_compact.h and edits none)
+//                         rounds api/follow.hip's count and scan, k_mf_scatter, the live pixels in order, and k_mf_follow, the
+//                         persistent walk with a fetch that continues a chain from its state and carries the product of its
+//                         reflections; k_mf_resolve (includes kernels/hj_motion_follow.h, which includes hj_motion.h and hj_chain.h
+//                         without their kernels and edits none)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -158,6 +162,10 @@ struct DevBuf {
 };
 
 int dev_alloc(hj_context* ctx, DevBuf& b, size_t bytes);
+
+// The buffers of a specular chain's rounds over n slots (api/chain_rounds.h): per slot the chain state (32 bytes) and the list of
+// live slots (4 bytes), and a count per tile of 256 slots with the total behind them.
+struct ChainBufs { DevBuf state, counts, list; };
 
 // The device buffers a call (or the scene, or a batch slot) owns: freed together with the set unless moved on first - a call
 // allocates into a set of its own and hands it over when everything it needed has succeeded.  ctx: where allocation errors go
@@ -500,9 +508,9 @@ struct hj_context {
   // (16 bytes a sample slot, 16384 slots a block), the staging of a host-side AOV image (48 bytes a pixel); hj_eval_materials' staging
   // of host arrays - one chunk of hit records, surface records and material records (16, 64 and 32 bytes a record).  The sibling of
   // RayQuery: grown on demand, reused by every call, freed with the context.  Never the batch slots' or the framebuffer.
-  // hj_render_aovs_followed (api/follow.hip) adds, per sample slot of one walk launch, the chain state (32 bytes), the list of live
-  // slots (4 bytes) and a count per tile of 256; hj_follow_specular the staging of host-side rays in and out (32 bytes a record each).
-  struct Aov { hjapi::DevBuf blocks, hits, image, in_hits, in_surface, out, state, counts, list, in_rays, out_rays; } aov;
+  // hj_render_aovs_followed (api/follow.hip) adds the rounds' buffers over the sample slots of one walk launch (chain: 36 bytes a slot
+  // and a count per tile); hj_follow_specular the staging of host-side rays in and out (32 bytes a record each).
+  struct Aov { hjapi::DevBuf blocks, hits, image, in_hits, in_surface, out, in_rays, out_rays; hjapi::ChainBufs chain; } aov;
 
   // hj_render_probe_lit (api/probe_lit.hip): per sample slot of one walk launch 64 bytes - the look-up point (32), the look-up's
   // record (16), the side record (16) -; the staging of a host-side volume, atlas and placement, once a call.  The block list, the hit
@@ -518,9 +526,9 @@ struct hj_context {
 
   // hj_render_motion (api/motion.hip): the staging of host-side previous shape arrays (16 / 48 / 32 bytes a sphere / quad / vertex)
   // and of a host-side motion image (16 bytes a pixel).  Grown on demand, reused by every call, freed with the context.
-  // hj_render_motion_followed (api/motion_follow.hip) adds, per pixel of the image, the chain state (32 bytes), the product of the
-  // chain's reflections (48 bytes), the list of live pixels (4 bytes) and a count per tile of 256.
-  struct Motion { hjapi::DevBuf spheres, quads, vertices, image, state, mat, counts, list; } motion;
+  // hj_render_motion_followed (api/motion_follow.hip) adds the rounds' buffers over the pixels of the image (chain: 36 bytes a pixel
+  // and a count per tile) and, per pixel, the product of the chain's reflections (48 bytes).
+  struct Motion { hjapi::DevBuf spheres, quads, vertices, image, mat; hjapi::ChainBufs chain; } motion;
 
   // the library's environment switches (api/hj_tuning.h) as the entry point in progress read them: hj_context_create, then every
   // hj_scene_upload / render call / BVH build refreshes the copy at its start; nothing below an entry point reads the environment
@@ -641,6 +649,10 @@ inline bool camera_ok(const hj_camera& c) {
 // api/follow.hip, for api/aov.hip's aov_render with max_follow > 0: room for walk launches of at most `slots` sample slots; the follow
 // rounds behind a walk launch of nb blocks (-> followed: a round ran and the launch's runs resolve through aov_follow_resolve); and
 // that resolve's launch for blocks [b0, b0 + cnt) of the launch
+// api/follow.hip, which alone holds kernels/hj_chain.h's count and scan kernels, for api/chain_rounds.h's loop in any unit: over n slots
+// k_chain_count<first> (the live chains per tile of 256 into d_counts) and k_chain_scan (their offsets in place, the total at
+// d_counts[tiles]) on the context's stream
+void chain_count_enqueue(hj_context* ctx, bool first, const float4* d_hits, const float4* d_state, uint32_t n, uint32_t max_follow, uint32_t* d_counts);
 int aov_follow_reserve(hj_context* ctx, size_t slots);
 hipError_t aov_follow_rounds(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, float4* d_hits, uint32_t max_follow, bool& followed);
 void aov_follow_resolve(hj_context* ctx, const hj_image_block* d_blocks, uint32_t nb, uint32_t b0, uint32_t cnt, const float4* d_hits, uint32_t width,

@@ -45,7 +45,7 @@ hipError_t lit_points(hj_context* ctx, const AovStage& st, const hj_image_block*
   hj_context::ProbeLit& q = ctx->probe_lit;
   const uint32_t n = nb * hj::kSlotsPerBlock;
   float4 *d_points = static_cast<float4*>(q.points.p), *d_lookup = static_cast<float4*>(q.lookup.p);
-  const float4* d_state = followed ? static_cast<const float4*>(ctx->aov.state.p) : nullptr;
+  const float4* d_state = followed ? static_cast<const float4*>(ctx->aov.chain.state.p) : nullptr;
   hipLaunchKernelGGL(hj::k_pl_points, per_lane(n), dim3(hj::kBlockThreads), 0, ctx->stream, ctx->scene, d_blocks, nb, d_hits, d_state, d_points,
                      static_cast<float4*>(q.side.p));
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -58,7 +58,7 @@ hipError_t lit_points(hj_context* ctx, const AovStage& st, const hj_image_block*
 void lit_resolve(hj_context* ctx, const AovStage&, const hj_image_block* d_blocks, uint32_t nb, uint32_t b0, uint32_t cnt, const float4* d_hits,
                  bool followed, uint32_t width, uint32_t height, float4* d_image) {
   hj_context::ProbeLit& q = ctx->probe_lit;
-  const float4* d_state = followed ? static_cast<const float4*>(ctx->aov.state.p) : nullptr;
+  const float4* d_state = followed ? static_cast<const float4*>(ctx->aov.chain.state.p) : nullptr;
   hipLaunchKernelGGL(hj::k_pl_resolve, per_lane(cnt * hj::kSlotsPerBlock), dim3(hj::kBlockThreads), 0, ctx->stream, ctx->scene, d_blocks, nb, b0, cnt, d_hits,
                      d_state, static_cast<const float4*>(q.lookup.p), static_cast<const float4*>(q.side.p), width, height, d_image);
 }

@@ -2,13 +2,14 @@
 //
 // The walk is the path kernel's own (kernels/hj_walk.h trace_persistent: in-wave ray replacement, merged first step, the LDS copy
 // of the hot nodes, pair nodes, the second tree for rays outside general position), instantiated here with a fetch that reads the
-// caller's ray array and a finish that writes one hit record per ray.  Nothing of the kernel headers is restated or edited: this
-// unit includes them (as api/render.hip does for the path kernels) and defines kernels of its own beside theirs.
+// caller's ray array and a finish that writes one hit record per ray, behind the shell the flat segment walks share
+// (kernels/hj_walk_segment.h).  Nothing of the kernel headers is restated or edited: this unit includes them (as api/render.hip
+// does for the path kernels) and defines kernels of its own beside theirs.
 //   k_rq_walk<ANY, PAIRS>   persistent form: a workgroup owns a contiguous segment of the rays and walks it with ray replacement
 //   k_rq_plain<ANY>         plain form: one thread per ray through traverse() - the A/B partner (HJ_TRACE_PERSISTENT=0)
 //   k_rq_surface            second pass, one thread per ray: the populated intersection and the material word of every hit
 #include "hj_internal.h"
-#include "../kernels/hj_stages.h"
+#include "../kernels/hj_walk_segment.h"
 
 #pragma clang fp contract(off)
 
@@ -21,11 +22,6 @@ HJ_DEV Ray rq_ray(float4 a, float4 b) {
   Ray r; r.o = V(a.x, a.y, a.z); r.d = V(a.w, b.x, b.y); r.tmin = b.z; r.tmax = b.w;
   return r;
 }
-// the record of a finished ray: (objectID bits, t, u, v); a miss: (-1, 0, 0, 0)
-HJ_DEV float4 rq_hit(const RawHit& h) {
-  const bool hit = h.id >= 0;
-  return make_float4(__int_as_float(hit ? h.id : -1), hit ? h.t : 0.f, hit ? h.u : 0.f, hit ? h.v : 0.f);
-}
 
 // Workgroup g walks rays [g * wg_rays, min(n, (g + 1) * wg_rays)): its waves pull them from the segment's head in LDS, a free lane
 // takes the next index (consecutive free lanes read consecutive rays), a finished ray's record goes to its own index - so which
@@ -33,24 +29,20 @@ HJ_DEV float4 rq_hit(const RawHit& h) {
 template <bool ANY, bool PAIRS>
 __global__ __launch_bounds__(kBlockThreads) void k_rq_walk(DeviceScene sc, const float4* __restrict__ rays, uint32_t n, uint32_t wg_rays,
                                                            float4* __restrict__ hits) {
-  __shared__ WgShared sh;
-  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(n / wg_rays): first < n)
-  const uint32_t cnt = n - first < wg_rays ? n - first : wg_rays;
-  if (threadIdx.x == 0) sh.head = 0;
-  load_hot_nodes(sc, sh);
-  __syncthreads();
+  const uint32_t first = blockIdx.x * wg_rays;                    // (walk_segment's: the arrays are addressed from the segment's start)
   const float4* __restrict__ seg_rays = rays + 2 * (size_t)first;
   float4* __restrict__ seg_hits = hits + first;
-  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
+  auto fetch = [&](uint32_t q, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
+    const uint32_t i = q - first;
     slot = i;
     any = ANY;
     r = rq_ray(seg_rays[2 * i], seg_rays[2 * i + 1]);
-    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
+    walk_reset(h);
   };
   auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
-    if (done) seg_hits[slot] = rq_hit(h);
+    if (done) seg_hits[slot] = walk_hit_record(h);
   };
-  trace_persistent<ANY ? 1 : 0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+  walk_segment<ANY ? 1 : 0, PAIRS>(sc, n, wg_rays, fetch, finish);
 }
 
 template <bool ANY>
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_rq_plain(DeviceScene sc, cons
   if (i >= n) return;
   RawHit h; h.t = 0.f; h.u = 0.f; h.v = 0.f;
   traverse<true, ANY>(sc, rq_ray(rays[2 * (size_t)i], rays[2 * (size_t)i + 1]), h);
-  hits[i] = rq_hit(h);
+  hits[i] = walk_hit_record(h);
 }
 
 // surface: four float4 per ray = p.xyz, n.xyz, u, v, ft.xyz, fb.xyz, material word, 0.  The hit point and populate* are the shade

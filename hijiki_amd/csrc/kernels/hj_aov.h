@@ -1,14 +1,14 @@
 // Frame AOVs and material queries ("Frame AOVs and material queries"; include/hijiki_hip.h hj_eval_materials,
 // hj_render_aovs): what colour a surface has at (u, v), and a frame's albedo / normal / depth from the frame's own primary rays.
 // The functions a hit needs are the shade stage's - camera_ray (hj_stages.h), populate_*, checkerboard (hj_shade.h), texture_rgb
-// (hj_texture.h), trace_persistent (hj_walk.h) - included here and edited nowhere: this header adds the tag dispatch of a material
+// (hj_texture.h), walk_segment (hj_walk_segment.h) - included here and edited nowhere: this header adds the tag dispatch of a material
 // that LEAVES the kernel (eval_material: stage_shade's own dispatch multiplies the colour into the path throughput) and the
 // kernels around it.  No global atomics, no inline assembly of its own.
 //   k_mat_eval            one lane per (hit, surface) record pair of hj_trace_rays
 //   k_aov_walk<PAIRS>     the persistent walk with a fetch that builds the camera ray from the sample index: no ray array exists
 //   k_aov_resolve         one lane per sample slot of a run of blocks: the sample's 12-word record added to its pixel
 #pragma once
-#include "hj_stages.h"
+#include "hj_walk_segment.h"
 
 #pragma clang fp contract(off)
 
@@ -71,8 +71,8 @@ HJ_DEV BatchState aov_batch(const hj_image_block* blocks, uint32_t num_blocks) {
 }
 
 #ifndef HJ_AOV_NO_KERNELS
-// Sample slots [0, n = num_blocks * kSlotsPerBlock) of the launch's blocks.  Workgroup g walks queue entries [g * wg_rays, ...) as
-// k_rq_walk's does; entry i is lane i & 63 of 64-sample group i >> 6 (group_sample: a block row's 64 pixels, or an 8 x 8 tile over
+// Sample slots [0, n = num_blocks * kSlotsPerBlock) of the launch's blocks.  Workgroup g walks queue entries [g * wg_rays, ...)
+// (walk_segment); entry i is lane i & 63 of 64-sample group i >> 6 (group_sample: a block row's 64 pixels, or an 8 x 8 tile over
 // a large tree - the grouping the camera packets use, a bijection of the slots either way), and its hit record (objectID bits, t,
 // u, v; a miss: (-1, 0, 0, 0)) goes to hits[slot]: which lane or workgroup carried a sample shows in no result.  A slot without a
 // sample (outside its block's dimension or the image: camera_ray says so) is fetched as a ray with the empty range [+inf, -inf]:
@@ -80,34 +80,21 @@ HJ_DEV BatchState aov_batch(const hj_image_block* blocks, uint32_t num_blocks) {
 template <bool PAIRS>
 __global__ __launch_bounds__(kBlockThreads) void k_aov_walk(DeviceScene sc, const hj_image_block* __restrict__ blocks, uint32_t num_blocks,
                                                             uint32_t wg_rays, float4* __restrict__ hits) {
-  __shared__ WgShared sh;
-  const uint32_t n = num_blocks * kSlotsPerBlock;
-  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(n / wg_rays): first < n)
-  const uint32_t cnt = n - first < wg_rays ? n - first : wg_rays;
-  if (threadIdx.x == 0) sh.head = 0;
-  load_hot_nodes(sc, sh);
-  __syncthreads();
   const BatchState st = aov_batch(blocks, num_blocks);
-  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
-    const uint32_t q = first + i;
+  auto fetch = [&](uint32_t q, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
     const uint32_t smp = group_sample(q >> 6, q & 63u, sc.group_tile);
     slot = smp;
     any = false;
     uint32_t rng_unused = 0;
     r.o = V(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
     r.d = V(0.f, 0.f, 0.f);
-    const bool valid = camera_ray(st, sc, smp, rng_unused, r.d);
-    r.tmin = valid ? kEps : kInf;                                  // render.glsl:33
-    r.tmax = valid ? kInf : -kInf;
-    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
+    walk_empty_range(r, camera_ray(st, sc, smp, rng_unused, r.d));
+    walk_reset(h);
   };
   auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
-    if (done) {
-      const bool hit = h.id >= 0;
-      hits[slot] = make_float4(__int_as_float(hit ? h.id : -1), hit ? h.t : 0.f, hit ? h.u : 0.f, hit ? h.v : 0.f);
-    }
+    if (done) hits[slot] = walk_hit_record(h);
   };
-  trace_persistent<0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+  walk_segment<0, PAIRS>(sc, num_blocks * kSlotsPerBlock, wg_rays, fetch, finish);
 }
 
 #endif  // HJ_AOV_NO_KERNELS

@@ -4,26 +4,22 @@
 // eval_material behind it), included here and edited nowhere: this header adds the continuation (follow_continue, ONE text for the
 // per-record query and the frame kernel) and the kernels around it.  No global atomics, no inline assembly of its own.
 //   k_follow                 one lane per (ray, hit) record pair of hj_trace_rays: the continued ray, or the empty ray
-//   k_af_count / _scan / _scatter   the live chains of a walk launch's sample slots, in slot order, as a list (kernels/hj_compact.h's
-//                            tile compaction); the first round's scatter also sets every sample's chain state from its camera ray
-//   k_aov_follow<PAIRS>      one round: the persistent walk over the list with a fetch that continues a chain from its state and last
-//                            hit - no ray array exists - and a finish that stores the new hit
+//   k_af_scatter<FIRST>      the live chains of a walk launch's sample slots, in slot order, as a list; the first round's also sets
+//                            every sample's chain state from its camera ray (kernels/hj_chain.h's chain_scatter, behind its count and scan)
+//   k_aov_follow<PAIRS>      one round: the persistent walk over the list (hj_chain.h's chain_round), which leaves (kFollowLeft, n)
+//                            in the record of a chain it continues
 //   k_aov_resolve_followed   k_aov_resolve with the chain's last segment in place of the camera ray (aov_record: one text of the record)
-// The chain state of a sample slot, two float4 beside its hit record: (segment origin.xyz, depth so far) (segment direction.xyz,
-// continuations taken as bits).
+// The chain state of a sample slot: hj_chain.h's.
 #pragma once
 #define HJ_AOV_NO_KERNELS   // the functions of hj_aov.h, no kernel of its: api/aov.hip holds those
 #include "hj_aov.h"
-#include "hj_compact.h"
 
 #pragma clang fp contract(off)
 
 namespace hj {
 
-constexpr uint32_t kAfThreads = 256u;               // threads of a k_af_* workgroup: a compaction tile
 constexpr uint32_t kFollowLeft = 0xFFFFFFFEu;       // word 0 of a hit record whose chain left a specular surface and hit nothing:
                                                     // words 1..3 hold that surface's normal (no shape id: a miss to everything else)
-static_assert(kSlotsPerBlock % kAfThreads == 0, "a launch's sample slots are whole tiles");
 
 // The ray (o, d) hit the scene at hr (objectID bits, t, u, v).  Does its chain go on, and with which ray?  Hit point and populate
 // as stage_shade has them (hj_stages.h:506-510); the material word from the scene by id.  A mirror reflects about the stored normal;
@@ -94,7 +90,14 @@ HJ_DEV bool follow_live(const DeviceScene& sc, const float4* __restrict__ hits, 
   return FIRST || __float_as_uint(state[2 * (size_t)slot + 1].w) < max_follow;
 }
 
-#ifndef HJ_FOLLOW_NO_KERNELS   // (kernels/hj_motion_follow.h takes the functions above alone: api/follow.hip holds these kernels)
+}  // namespace hj
+
+#ifndef HJ_FOLLOW_NO_KERNELS   // (hj_chain.h, hj_motion_follow.h and hj_probe_lit.h take the functions above alone: api/follow.hip holds these kernels)
+#include "hj_chain.h"
+
+namespace hj {
+
+static_assert(kSlotsPerBlock % kChainThreads == 0, "a launch's sample slots are whole tiles");
 
 // rays: two float4 per record (origin.xyz, direction.x | direction.yz, tMin, tMax), hits: (objectID bits, t, u, v) - hj_trace_rays'
 // arrays.  out: the continued ray (p, wo, tMin = eps, tMax = +inf: the next segment of a path), or where the chain ends the empty ray
@@ -114,79 +117,29 @@ __global__ __launch_bounds__(kBlockThreads) void k_follow(DeviceScene sc, const 
   out[2 * (size_t)i + 1] = o1;
 }
 
-// The live slots of a launch's n sample slots in ascending order -> list.  Tiles of kAfThreads slots; counts: a word per tile and the
-// total behind them (the host reads it: it sizes the round's grid).
+// chain_scatter over a launch's n sample slots.  A slot's first ray is its camera ray (camera_ray says whether it has a sample).
 template <bool FIRST>
-__global__ __launch_bounds__(kAfThreads) void k_af_count(DeviceScene sc, const float4* __restrict__ hits, const float4* __restrict__ state, uint32_t n,
-                                                         uint32_t max_follow, uint32_t* __restrict__ counts) {
-  __shared__ uint32_t wave_cnt[kAfThreads / 64u];
-  (void)compact_wave_counts(follow_live<FIRST>(sc, hits, state, blockIdx.x * kAfThreads + threadIdx.x, n, max_follow), wave_cnt);
-  if (threadIdx.x == 0) counts[blockIdx.x] = compact_tile_count<kAfThreads>(wave_cnt);
+__global__ __launch_bounds__(kChainThreads) void k_af_scatter(DeviceScene sc, const hj_image_block* __restrict__ blocks, uint32_t num_blocks,
+                                                              const float4* __restrict__ hits, float4* __restrict__ state, uint32_t n, uint32_t max_follow,
+                                                              const uint32_t* __restrict__ offsets, uint32_t* __restrict__ list) {
+  chain_scatter<FIRST>(
+      sc, hits, state, n, max_follow, offsets, list,
+      [&](uint32_t slot, v3& o, v3& d) {
+        const BatchState st = aov_batch(blocks, num_blocks);
+        uint32_t rng_unused = 0;
+        o = V(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2]);
+        return camera_ray(st, sc, slot, rng_unused, d);
+      },
+      [](uint32_t) {});
 }
 
-__global__ __launch_bounds__(kAfThreads) void k_af_scan(uint32_t* __restrict__ counts, uint32_t nb) { compact_scan_tiles<kAfThreads>(counts, nb); }
-
-// FIRST: every slot with a sample (camera_ray says so) also gets its chain state - the camera ray, depth 0, no continuation -, so the
-// followed resolve reads one kind of record for every sample of the launch.
-template <bool FIRST>
-__global__ __launch_bounds__(kAfThreads) void k_af_scatter(DeviceScene sc, const hj_image_block* __restrict__ blocks, uint32_t num_blocks,
-                                                           const float4* __restrict__ hits, float4* __restrict__ state, uint32_t n, uint32_t max_follow,
-                                                           const uint32_t* __restrict__ offsets, uint32_t* __restrict__ list) {
-  __shared__ uint32_t wave_cnt[kAfThreads / 64u];
-  const uint32_t slot = blockIdx.x * kAfThreads + threadIdx.x;
-  if (FIRST && slot < n) {
-    const BatchState st = aov_batch(blocks, num_blocks);
-    uint32_t rng_unused = 0;
-    v3 d = V(0.f, 0.f, 0.f);
-    if (camera_ray(st, sc, slot, rng_unused, d)) {
-      state[2 * (size_t)slot] = make_float4(sc.camera.position[0], sc.camera.position[1], sc.camera.position[2], 0.f);
-      state[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(0u));
-    }
-  }
-  const bool keep = follow_live<FIRST>(sc, hits, state, slot, n, max_follow);
-  const unsigned long long mask = compact_wave_counts(keep, wave_cnt);
-  if (!keep) return;
-  HJ_COMPACT_RANK(pos, offsets[blockIdx.x], wave_cnt, mask);
-  list[pos] = slot;
-}
-
-// One round over the `count` live slots of list.  Workgroup g walks list entries [g * wg_rays, ...) as k_aov_walk's walks its queue
-// entries.  fetch: the chain's state and last hit -> follow_continue -> the walk's ray (p, wo, eps, +inf); the state becomes the new
-// segment's (p, depth + t | wo, continuations + 1) and the hit record (kFollowLeft, n) - what the resolve needs of the surface that
-// was left should the new segment hit nothing.  The walk's finish hook sees the hit and not the ray, so the segment is stored here,
-// in the service phase, where the walk issues its stores anyway.  finish: a hit replaces the record; a miss leaves it.  A slot is
-// in the list once, so one lane reads and writes its records; which lane or workgroup carried a chain shows in no result.
+// chain_round over the live slots.  What a continuation leaves in the hit record: (kFollowLeft, n), the normal of the surface that
+// was left, which k_aov_resolve_followed records should the new segment hit nothing.
 template <bool PAIRS>
 __global__ __launch_bounds__(kBlockThreads) void k_aov_follow(DeviceScene sc, const uint32_t* __restrict__ list, uint32_t count, uint32_t wg_rays,
                                                               float4* __restrict__ hits, float4* __restrict__ state) {
-  __shared__ WgShared sh;
-  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(count / wg_rays): first < count)
-  const uint32_t cnt = count - first < wg_rays ? count - first : wg_rays;
-  if (threadIdx.x == 0) sh.head = 0;
-  load_hot_nodes(sc, sh);
-  __syncthreads();
-  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
-    slot = list[first + i];
-    any = false;
-    const float4 s0 = state[2 * (size_t)slot], s1 = state[2 * (size_t)slot + 1];
-    const float4 hr = hits[slot];
-    v3 p = V(0.f, 0.f, 0.f), wo = p, nrm = p;
-    const bool go = follow_continue(sc, xyz(s0), xyz(s1), hr, p, wo, nrm);   // (true for every entry the scatter listed)
-    r.o = p;
-    r.d = wo;
-    r.tmin = go ? kEps : kInf;                                     // render.glsl:33
-    r.tmax = go ? kInf : -kInf;
-    if (go) {
-      state[2 * (size_t)slot] = make_float4(p.x, p.y, p.z, s0.w + hr.y);
-      state[2 * (size_t)slot + 1] = make_float4(wo.x, wo.y, wo.z, __uint_as_float(__float_as_uint(s1.w) + 1u));
-      hits[slot] = make_float4(__uint_as_float(kFollowLeft), nrm.x, nrm.y, nrm.z);
-    }
-    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
-  };
-  auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
-    if (done && h.id >= 0) hits[slot] = make_float4(__int_as_float(h.id), h.t, h.u, h.v);
-  };
-  trace_persistent<0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+  chain_round<PAIRS>(sc, list, count, wg_rays, hits, state,
+                     [](uint32_t, v3 nrm, bool) { return make_float4(__uint_as_float(kFollowLeft), nrm.x, nrm.y, nrm.z); });
 }
 
 // k_aov_resolve over a run whose launch was followed: the sample's record is the record of its chain's last hit - aov_record over
@@ -217,6 +170,6 @@ __global__ __launch_bounds__(kBlockThreads) void k_aov_resolve_followed(DeviceSc
   aov_add(aov + 3 * ((size_t)py * width + px), r0, r1, r2);
 }
 
-#endif  // HJ_FOLLOW_NO_KERNELS
-
 }  // namespace hj
+
+#endif  // HJ_FOLLOW_NO_KERNELS

@@ -1,6 +1,6 @@
 // Per-pixel motion for the temporal denoiser ("Motion for the temporal denoiser"; include/hijiki_hip.h: hj_render_motion):
 // for every pixel where the surface point its centre ray sees was in the previous frame, as a position in the previous image and a
-// distance from the previous camera.  The walk is the path kernel's (trace_persistent, hj_walk.h), the centre ray's direction is the
+// distance from the previous camera.  The walk is the path kernel's behind walk_segment (hj_walk_segment.h), the centre ray's direction is the
 // temporal stage's (dt_camera_dir, hj_denoise_temporal.h), the sphere normal is populate_sphere's divs (hj_shade.h) - included here
 // and edited nowhere.  No global atomics, no inline assembly of its own; loads and stores are the compiler's.
 //   k_mv_walk<PAIRS>   the persistent walk over the image's pixels, a wave's 64 rays together in the image; the raw hit
@@ -9,7 +9,7 @@
 //                      into the previous camera, the record overwritten in place
 // The previous-point arithmetic stays out of the walk's finish: inside it it would take the walk's registers.
 #pragma once
-#include "hj_stages.h"
+#include "hj_walk_segment.h"
 #define HJ_DENOISE_TEMPORAL_NO_KERNELS   // dt_camera_dir, dt_rotate, dn_sq and the accumulate template; the temporal unit's kernels stay its own
 #include "hj_denoise_temporal.h"
 
@@ -107,7 +107,7 @@ HJ_DEV float4 mv_record(const DeviceScene& sc, const MvPrev& prev, uint32_t t, u
 
 #ifndef HJ_MOTION_NO_KERNELS   // (kernels/hj_motion_follow.h takes the functions above alone: api/motion.hip holds these kernels)
 
-// Entries [0, n = mv_entries) of the image.  Workgroup g walks entries [g * wg_rays, ...) as k_rq_walk's does.  An entry's ray is
+// Entries [0, n = mv_entries) of the image.  Workgroup g walks entries [g * wg_rays, ...) (walk_segment).  An entry's ray is
 // built from its pixel - origin = the uploaded camera's position, d = dt_camera_dir through (x + 0.5, y + 0.5), tMin = eps, tMax =
 // +inf - and its raw hit (objectID bits, t, u, v; a miss: (-1, 0, 0, 0)) goes to motion[y * W + x]: which lane or workgroup
 // carried a pixel, and which grouping, shows in no record.  A padding entry is fetched as a ray with the empty range [+inf, -inf]:
@@ -115,32 +115,22 @@ HJ_DEV float4 mv_record(const DeviceScene& sc, const MvPrev& prev, uint32_t t, u
 template <bool PAIRS>
 __global__ __launch_bounds__(kBlockThreads) void k_mv_walk(DeviceScene sc, uint32_t W, uint32_t H, uint32_t n, uint32_t wg_rays,
                                                            float4* __restrict__ motion) {
-  __shared__ WgShared sh;
-  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(n / wg_rays): first < n)
-  const uint32_t cnt = n - first < wg_rays ? n - first : wg_rays;
-  if (threadIdx.x == 0) sh.head = 0;
-  load_hot_nodes(sc, sh);
-  __syncthreads();
   const DtCamera cam = mv_camera(sc);
   const float Wf = (float)W, Hf = (float)H;
-  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
+  auto fetch = [&](uint32_t q, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
     uint32_t x, y;
-    const bool valid = mv_pixel(first + i, W, H, sc.group_tile, x, y);
+    const bool valid = mv_pixel(q, W, H, sc.group_tile, x, y);
     slot = valid ? y * W + x : kMvPad;
     any = false;
     r.o = cam.pos;
     r.d = valid ? dt_camera_dir(cam, (float)x + 0.5f, (float)y + 0.5f, Wf, Hf) : V(0.f, 0.f, 0.f);
-    r.tmin = valid ? kEps : kInf;                                  // render.glsl:33
-    r.tmax = valid ? kInf : -kInf;
-    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
+    walk_empty_range(r, valid);
+    walk_reset(h);
   };
   auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
-    if (done && slot != kMvPad) {
-      const bool hit = h.id >= 0;
-      motion[slot] = make_float4(__int_as_float(hit ? h.id : -1), hit ? h.t : 0.f, hit ? h.u : 0.f, hit ? h.v : 0.f);
-    }
+    if (done && slot != kMvPad) motion[slot] = walk_hit_record(h);
   };
-  trace_persistent<0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+  walk_segment<0, PAIRS>(sc, n, wg_rays, fetch, finish);
 }
 
 // One lane per pixel t = y * W + x, in place: motion[t] holds the walk's raw hit on entry and the pixel's record on return, so a

@@ -1,28 +1,26 @@
 // The followed motion image ("Followed motion"; include/hijiki_hip.h: hj_render_motion_followed): hj_render_motion's
 // record for what a mirror or glass SHOWS - the chain the followed AOVs follow, for the pixel's centre ray, and at its end the
 // displacement of the surface it reaches carried back through the chain's reflections onto the virtual point the temporal stage
-// reprojects.  The continuation is kernels/hj_follow.h's (follow_continue_branch, follow_live), the first-hit record and the point on
-// a shape are kernels/hj_motion.h's (mv_record, mv_shape_point, mv_project), the compaction is kernels/hj_compact.h's - included here
-// and edited nowhere; round 0 is api/motion.hip's k_mv_walk.  No global atomics, no inline assembly; loads and stores are the compiler's.
-//   k_mf_count / _scan / _scatter   the live pixels of the image in pixel order as a list; the first round's scatter also sets every
-//                        pixel's chain state from its centre ray
-//   k_mf_follow<PAIRS>   one round: the persistent walk over the list with a fetch that continues a chain from its state and last hit,
-//                        stores the new segment and multiplies M by the reflection's Householder matrix; a finish that stores the hit
+// reprojects.  The rounds are kernels/hj_chain.h's (the continuation of kernels/hj_follow.h behind them), the first-hit record and the
+// point on a shape are kernels/hj_motion.h's (mv_record, mv_shape_point, mv_project) - included here and edited nowhere; round 0 is
+// api/motion.hip's k_mv_walk.  No global atomics, no inline assembly; loads and stores are the compiler's.
+//   k_mf_scatter<FIRST>  the live pixels of the image in pixel order as a list; the first round's also sets every pixel's chain state
+//                        from its centre ray (hj_chain.h's chain_scatter, behind its count and scan, which api/follow.hip holds)
+//   k_mf_follow<PAIRS>   one round: the persistent walk over the list (hj_chain.h's chain_round), which multiplies M by a reflection's
+//                        Householder matrix
 //   k_mf_resolve         one lane per pixel, in place: mv_record for a pixel that took no continuation, the followed record otherwise
-// The chain state of a pixel: two float4 in `state` - (segment origin.xyz, depth so far) (segment direction.xyz, continuations taken
-// as bits), as the followed AOVs keep it - and three float4 in `mat`, the columns of M (word 3 unused).  mat is written when a pixel
-// takes its first continuation and read for no other pixel.
+// The chain state of a pixel: hj_chain.h's two float4 in `state`, as the followed AOVs keep it, and three float4 in `mat`, the columns
+// of M (word 3 unused).  mat is written when a pixel takes its first continuation and read for no other pixel.
 #pragma once
 #define HJ_MOTION_NO_KERNELS   // the functions of hj_motion.h, no kernel of its: api/motion.hip holds those
 #include "hj_motion.h"
-#define HJ_FOLLOW_NO_KERNELS   // follow_continue_branch and follow_live, no kernel of hj_follow.h's: api/follow.hip holds those
-#include "hj_follow.h"
+#define HJ_CHAIN_NO_KERNELS    // chain_scatter and chain_round, not the count and scan kernels: api/follow.hip holds those
+#include "hj_chain.h"
 
 #pragma clang fp contract(off)
 
 namespace hj {
 
-constexpr uint32_t kMfThreads = 256u;            // threads of a k_mf_count / _scan / _scatter workgroup: a compaction tile
 constexpr uint32_t kMvLeft = kFollowLeft;        // HJ_MOTION_LEFT: word 3 of a record whose chain left a specular surface and hit nothing;
                                                  // between the rounds word 0 of such a pixel's hit record (a miss to follow_live)
 
@@ -35,91 +33,43 @@ HJ_DEV void mf_householder(v3& m0, v3& m1, v3& m2, v3 n) {
   m2 = V(m2.x - w2.x * n.z, m2.y - w2.y * n.z, m2.z - w2.z * n.z);
 }
 
-// The live pixels of the image's n = W * H in ascending order -> list.  Tiles of kMfThreads pixels; counts: a word per tile and the
-// total behind them (the host reads it: it sizes the round's grid).  FIRST: behind k_mv_walk no state exists yet.
+// chain_scatter over the image's n = W * H pixels.  A pixel's first ray is its centre ray; a listed pixel also gets M = the identity.
 template <bool FIRST>
-__global__ __launch_bounds__(kMfThreads) void k_mf_count(DeviceScene sc, const float4* __restrict__ hits, const float4* __restrict__ state, uint32_t n,
-                                                         uint32_t max_follow, uint32_t* __restrict__ counts) {
-  __shared__ uint32_t wave_cnt[kMfThreads / 64u];
-  (void)compact_wave_counts(follow_live<FIRST>(sc, hits, state, blockIdx.x * kMfThreads + threadIdx.x, n, max_follow), wave_cnt);
-  if (threadIdx.x == 0) counts[blockIdx.x] = compact_tile_count<kMfThreads>(wave_cnt);
+__global__ __launch_bounds__(kChainThreads) void k_mf_scatter(DeviceScene sc, uint32_t W, uint32_t H, const float4* __restrict__ hits, float4* __restrict__ state,
+                                                              float4* __restrict__ mat, uint32_t n, uint32_t max_follow, const uint32_t* __restrict__ offsets,
+                                                              uint32_t* __restrict__ list) {
+  chain_scatter<FIRST>(
+      sc, hits, state, n, max_follow, offsets, list,
+      [&](uint32_t t, v3& o, v3& d) {
+        const DtCamera cam = mv_camera(sc);
+        d = dt_camera_dir(cam, (float)(t % W) + 0.5f, (float)(t / W) + 0.5f, (float)W, (float)H);
+        o = cam.pos;
+        return true;
+      },
+      [&](uint32_t t) {
+        mat[3 * (size_t)t] = make_float4(1.f, 0.f, 0.f, 0.f);
+        mat[3 * (size_t)t + 1] = make_float4(0.f, 1.f, 0.f, 0.f);
+        mat[3 * (size_t)t + 2] = make_float4(0.f, 0.f, 1.f, 0.f);
+      });
 }
 
-__global__ __launch_bounds__(kMfThreads) void k_mf_scan(uint32_t* __restrict__ counts, uint32_t nb) { compact_scan_tiles<kMfThreads>(counts, nb); }
-
-// FIRST: every pixel also gets its chain state - the centre ray, depth 0, no continuation -, so the resolve reads one kind of record
-// for every pixel; a listed pixel also gets M = the identity.
-template <bool FIRST>
-__global__ __launch_bounds__(kMfThreads) void k_mf_scatter(DeviceScene sc, uint32_t W, uint32_t H, const float4* __restrict__ hits, float4* __restrict__ state,
-                                                           float4* __restrict__ mat, uint32_t n, uint32_t max_follow, const uint32_t* __restrict__ offsets,
-                                                           uint32_t* __restrict__ list) {
-  __shared__ uint32_t wave_cnt[kMfThreads / 64u];
-  const uint32_t t = blockIdx.x * kMfThreads + threadIdx.x;
-  if (FIRST && t < n) {
-    const DtCamera cam = mv_camera(sc);
-    const v3 d = dt_camera_dir(cam, (float)(t % W) + 0.5f, (float)(t / W) + 0.5f, (float)W, (float)H);
-    state[2 * (size_t)t] = make_float4(cam.pos.x, cam.pos.y, cam.pos.z, 0.f);
-    state[2 * (size_t)t + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(0u));
-  }
-  const bool keep = follow_live<FIRST>(sc, hits, state, t, n, max_follow);
-  const unsigned long long mask = compact_wave_counts(keep, wave_cnt);
-  if (!keep) return;
-  if (FIRST) {
-    mat[3 * (size_t)t] = make_float4(1.f, 0.f, 0.f, 0.f);
-    mat[3 * (size_t)t + 1] = make_float4(0.f, 1.f, 0.f, 0.f);
-    mat[3 * (size_t)t + 2] = make_float4(0.f, 0.f, 1.f, 0.f);
-  }
-  HJ_COMPACT_RANK(pos, offsets[blockIdx.x], wave_cnt, mask);
-  list[pos] = t;
-}
-
-// One round over the `count` live pixels of list.  Workgroup g walks list entries [g * wg_rays, ...) as k_mv_walk walks its entries.
-// fetch: the chain's state and last hit -> follow_continue_branch -> the walk's ray (p, wo, eps, +inf); the state becomes the new
-// segment's (p, depth + t | wo, continuations + 1), a reflection multiplies M by its Householder matrix, and the hit record becomes
-// (kMvLeft, 0, 0, 0) - what the resolve reads should the new segment hit nothing.  The walk's finish hook sees the hit and not the
-// ray, so the segment is stored here, in the service phase, where the walk issues its stores anyway; M is read and written inside the
-// reflect branch alone and is dead before the ray enters the walk.  finish: a hit replaces the record; a miss leaves it.  A pixel is
-// in the list once, so one lane reads and writes its records; which lane or workgroup carried a chain shows in no result.
+// chain_round over the live pixels.  A reflection multiplies M by its Householder matrix - M is read and written inside the reflect
+// branch alone and is dead before the ray enters the walk -, and what a continuation leaves in the hit record is (kMvLeft, 0, 0, 0):
+// what the resolve reads should the new segment hit nothing.
 template <bool PAIRS>
 __global__ __launch_bounds__(kBlockThreads) void k_mf_follow(DeviceScene sc, const uint32_t* __restrict__ list, uint32_t count, uint32_t wg_rays,
                                                              float4* __restrict__ hits, float4* __restrict__ state, float4* __restrict__ mat) {
-  __shared__ WgShared sh;
-  const uint32_t first = blockIdx.x * wg_rays;                    // (the grid is ceil(count / wg_rays): first < count)
-  const uint32_t cnt = count - first < wg_rays ? count - first : wg_rays;
-  if (threadIdx.x == 0) sh.head = 0;
-  load_hot_nodes(sc, sh);
-  __syncthreads();
-  auto fetch = [&](uint32_t i, uint32_t& slot, Ray& r, bool& any, RawHit& h) {
-    slot = list[first + i];
-    any = false;
-    const float4 s0 = state[2 * (size_t)slot], s1 = state[2 * (size_t)slot + 1];
-    const float4 hr = hits[slot];
-    v3 p = V(0.f, 0.f, 0.f), wo = p, nrm = p;
-    bool reflected = false;
-    const bool go = follow_continue_branch(sc, xyz(s0), xyz(s1), hr, p, wo, nrm, reflected);   // (true for every entry the scatter listed)
-    r.o = p;
-    r.d = wo;
-    r.tmin = go ? kEps : kInf;                                     // render.glsl:33
-    r.tmax = go ? kInf : -kInf;
-    if (go) {
-      state[2 * (size_t)slot] = make_float4(p.x, p.y, p.z, s0.w + hr.y);
-      state[2 * (size_t)slot + 1] = make_float4(wo.x, wo.y, wo.z, __uint_as_float(__float_as_uint(s1.w) + 1u));
-      hits[slot] = make_float4(__uint_as_float(kMvLeft), 0.f, 0.f, 0.f);
-      if (reflected) {
-        float4* __restrict__ m = mat + 3 * (size_t)slot;
-        v3 m0 = xyz(m[0]), m1 = xyz(m[1]), m2 = xyz(m[2]);
-        mf_householder(m0, m1, m2, nrm);
-        m[0] = make_float4(m0.x, m0.y, m0.z, 0.f);
-        m[1] = make_float4(m1.x, m1.y, m1.z, 0.f);
-        m[2] = make_float4(m2.x, m2.y, m2.z, 0.f);
-      }
+  chain_round<PAIRS>(sc, list, count, wg_rays, hits, state, [&](uint32_t slot, v3 nrm, bool reflected) {
+    if (reflected) {
+      float4* __restrict__ m = mat + 3 * (size_t)slot;
+      v3 m0 = xyz(m[0]), m1 = xyz(m[1]), m2 = xyz(m[2]);
+      mf_householder(m0, m1, m2, nrm);
+      m[0] = make_float4(m0.x, m0.y, m0.z, 0.f);
+      m[1] = make_float4(m1.x, m1.y, m1.z, 0.f);
+      m[2] = make_float4(m2.x, m2.y, m2.z, 0.f);
     }
-    h.t = 0.f; h.u = 0.f; h.v = 0.f; h.id = -1;
-  };
-  auto finish = [&](bool done, uint32_t slot, const RawHit& h, bool) {
-    if (done && h.id >= 0) hits[slot] = make_float4(__int_as_float(h.id), h.t, h.u, h.v);
-  };
-  trace_persistent<0, PAIRS>(sc, cnt, &sh.head, sh.nodes, fetch, finish);
+    return make_float4(__uint_as_float(kMvLeft), 0.f, 0.f, 0.f);
+  });
 }
 
 // One lane per pixel t = y * W + x, in place: motion[t] holds the chain's last raw hit - or kMvLeft - on entry and the pixel's record

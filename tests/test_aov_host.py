@@ -143,6 +143,11 @@ def test_aov_kernels_use_no_scratch(tmp_path):
     assert "atomic" not in src.replace("No global atomics", "") and "asm" not in src.replace("no inline assembly", "")
     assert "#pragma clang fp contract(off)" in src
     assert "#pragma clang fp contract(off)" in open(os.path.join(ROOT, "hijiki_amd", "csrc", "api", "aov.hip")).read()
+    # the walk's shell is hj_walk_segment.h's; k_aov_walk does not restate it
+    segment = open(os.path.join(ROOT, "hijiki_amd", "csrc", "kernels", "hj_walk_segment.h")).read()
+    assert "__shared__ WgShared sh;" in segment and "load_hot_nodes(sc, sh);" in segment and "trace_persistent<MODE, PAIRS>(" in segment
+    assert "walk_segment<0, PAIRS>(" in src and "walk_hit_record(h)" in src and "walk_empty_range(" in src
+    assert "__shared__ WgShared" not in src and "load_hot_nodes(" not in src and "trace_persistent<" not in src and "hit ? h.t" not in src
 
 
 # ------------------------------------------------------------------------------------------------- the reference against itself

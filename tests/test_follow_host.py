@@ -112,8 +112,8 @@ def test_argument_refusals_come_before_the_device_in_order():
 # ------------------------------------------------------------------------------------------------------------- the compiled unit
 
 def test_follow_kernels_use_no_scratch(tmp_path):
-    """The compiler's resource report for api/follow.hip (the Makefile's flags): exactly the kernels of hj_follow.h - none of
-    hj_aov.h's, which api/aov.hip holds -; no kernel has scratch and none spills a register: a reload inside the walk's loops would be
+    """The compiler's resource report for api/follow.hip (the Makefile's flags): exactly the kernels of hj_follow.h and the one copy
+    of hj_chain.h's count and scan - none of hj_aov.h's, which api/aov.hip holds -; no kernel has scratch and none spills a register: a reload inside the walk's loops would be
     a dependent memory trip per node.  LDS: the path kernels' WgShared in the walk, the scan's partial sums, a word per wave in the
     count and the scatter.  Registers and occupancy are printed, not gated."""
     mk = open(os.path.join(ROOT, "Makefile")).read()
@@ -126,17 +126,26 @@ def test_follow_kernels_use_no_scratch(tmp_path):
     out = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, TMPDIR=str(tmp_path)))
     assert out.returncode == 0, out.stderr[-2000:]
     report = _report(out.stderr)
-    names = {re.search(r"k_(follow|af_scan|aov_resolve_followed|af_count<\w+>|af_scatter<\w+>|aov_follow<\w+>)", k).group(0): v for k, v in report.items()}
-    assert sorted(names) == ["k_af_count<false>", "k_af_count<true>", "k_af_scan", "k_af_scatter<false>", "k_af_scatter<true>", "k_aov_follow<false>",
-                             "k_aov_follow<true>", "k_aov_resolve_followed", "k_follow"] and len(report) == 9, sorted(report)
+    names = {re.search(r"k_(follow|chain_scan|aov_resolve_followed|chain_count<\w+>|af_scatter<\w+>|aov_follow<\w+>)", k).group(0): v for k, v in report.items()}
+    assert sorted(names) == ["k_af_scatter<false>", "k_af_scatter<true>", "k_aov_follow<false>", "k_aov_follow<true>", "k_aov_resolve_followed",
+                             "k_chain_count<false>", "k_chain_count<true>", "k_chain_scan", "k_follow"] and len(report) == 9, sorted(report)
     for k, v in names.items():
         assert v["ScratchSize"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (k, v)
         assert (v["LDS Size"] > 16 * 1024) == k.startswith("k_aov_follow<") and v["LDS Size"] <= 20 * 1024, (k, v)
         print(f"{k}: {v['VGPRs']} VGPRs, {v['TotalSGPRs']} SGPRs, LDS {v['LDS Size']} B, occupancy {v['Occupancy']} waves per SIMD")
-    src = open(os.path.join(ROOT, "hijiki_amd", "csrc", "kernels", "hj_follow.h")).read()
-    assert "atomic" not in src.replace("No global atomics", "") and "asm" not in src.replace("no inline assembly", "") and "getenv" not in src
-    assert "#pragma clang fp contract(off)" in src and "aov_record(" in src and "HJ_DEV bool aov_record" not in src          # (included, not restated)
-    assert '#include "hj_stages.h"' not in src and "compact_scan_tiles<" in src and "HJ_COMPACT_RANK(" in src
+    kernels = os.path.join(ROOT, "hijiki_amd", "csrc", "kernels")
+    src, chain, segment = (open(os.path.join(kernels, f)).read() for f in ("hj_follow.h", "hj_chain.h", "hj_walk_segment.h"))
+    for text in (src, chain, segment):
+        assert "atomic" not in text.replace("No global atomics", "") and "asm" not in text.replace("no inline assembly", "") and "getenv" not in text
+        assert "#pragma clang fp contract(off)" in text
+    assert "aov_record(" in src and "HJ_DEV bool aov_record" not in src                                                       # (included, not restated)
+    # the rounds' text is hj_chain.h's, once: the compaction, the continuation's call and the walk's shell are nowhere else
+    assert '#include "hj_stages.h"' not in src and '#include "hj_stages.h"' not in chain and '#include "hj_chain.h"' in src
+    assert "compact_scan_tiles<" in chain and "HJ_COMPACT_RANK(" in chain and "compact_scan_tiles<" not in src and "HJ_COMPACT_RANK(" not in src
+    assert "chain_scatter<FIRST>(" in src and "chain_round<PAIRS>(" in src and "walk_segment<0, PAIRS>(" in chain
+    assert "trace_persistent<" not in src and "trace_persistent<" not in chain and "load_hot_nodes(" not in src + chain
+    assert "trace_persistent<MODE, PAIRS>(" in segment and "load_hot_nodes(sc, sh);" in segment
+    assert '#include "hj_follow.h"' in chain and '#include "hj_compact.h"' in chain and "HJ_FOLLOW_NO_KERNELS" in chain and "HJ_CHAIN_NO_KERNELS" in chain
     assert "#pragma clang fp contract(off)" in open(os.path.join(ROOT, "hijiki_amd", "csrc", "api", "follow.hip")).read()
 
 

@@ -92,7 +92,8 @@ def test_refusals_come_before_the_device_in_order():
 
 def test_motion_follow_kernels_use_no_scratch(tmp_path):
     """The compiler's resource report for api/motion_follow.hip (the Makefile's flags): exactly the kernels of hj_motion_follow.h -
-    not k_mv_walk or k_mv_resolve, which api/motion.hip holds, nor a kernel of hj_follow.h, which api/follow.hip holds -; no kernel
+    not k_mv_walk or k_mv_resolve, which api/motion.hip holds, nor a kernel of hj_follow.h or the count and scan of hj_chain.h, which
+    api/follow.hip holds -; no kernel
     has scratch and none spills a register.  LDS: the path kernels' WgShared in the walk, the scan's partial sums, a word per wave
     in the count and the scatter.  Registers and occupancy are printed, not gated."""
     mk = open(os.path.join(ROOT, "Makefile")).read()
@@ -105,9 +106,8 @@ def test_motion_follow_kernels_use_no_scratch(tmp_path):
     out = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, TMPDIR=str(tmp_path)))
     assert out.returncode == 0, out.stderr[-2000:]
     report = _report(out.stderr)
-    names = {re.search(r"k_mf_(scan|resolve|count<\w+>|scatter<\w+>|follow<\w+>)", k).group(0): v for k, v in report.items()}
-    assert sorted(names) == ["k_mf_count<false>", "k_mf_count<true>", "k_mf_follow<false>", "k_mf_follow<true>", "k_mf_resolve", "k_mf_scan",
-                             "k_mf_scatter<false>", "k_mf_scatter<true>"] and len(report) == 8, sorted(report)
+    names = {re.search(r"k_mf_(resolve|scatter<\w+>|follow<\w+>)", k).group(0): v for k, v in report.items()}
+    assert sorted(names) == ["k_mf_follow<false>", "k_mf_follow<true>", "k_mf_resolve", "k_mf_scatter<false>", "k_mf_scatter<true>"] and len(report) == 5, sorted(report)
     for k, v in names.items():
         assert v["ScratchSize"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (k, v)
         assert (v["LDS Size"] > 16 * 1024) == k.startswith("k_mf_follow<") and v["LDS Size"] <= 20 * 1024, (k, v)
@@ -115,7 +115,11 @@ def test_motion_follow_kernels_use_no_scratch(tmp_path):
     src = open(os.path.join(ROOT, "hijiki_amd", "csrc", "kernels", "hj_motion_follow.h")).read()
     assert "atomic" not in src.replace("No global atomics", "") and "asm" not in src.replace("no inline assembly", "") and "getenv" not in src
     assert "#pragma clang fp contract(off)" in src and "mv_record(" in src and "HJ_DEV float4 mv_record" not in src               # (included, not restated)
-    assert "follow_continue_branch(" in src and "compact_scan_tiles<" in src and "HJ_COMPACT_RANK(" in src
+    chain = open(os.path.join(ROOT, "hijiki_amd", "csrc", "kernels", "hj_chain.h")).read()
+    assert "follow_continue_branch(" in chain and "compact_scan_tiles<" in chain and "HJ_COMPACT_RANK(" in chain                 # (the rounds' text, once)
+    assert "follow_continue_branch(" not in src and "compact_scan_tiles<" not in src and "HJ_COMPACT_RANK(" not in src and "trace_persistent<" not in src
+    assert '#include "hj_chain.h"' in src and "HJ_CHAIN_NO_KERNELS" in src and "chain_scatter<FIRST>(" in src and "chain_round<PAIRS>(" in src
+    assert "mf_householder(m0, m1, m2, nrm)" in src
     assert "#pragma clang fp contract(off)" in open(os.path.join(ROOT, "hijiki_amd", "csrc", "api", "motion_follow.hip")).read()
 
 

@@ -107,3 +107,10 @@ def test_walk_kernels_use_no_scratch(tmp_path):
     for k, v in walks.items():
         assert 16384 <= v["LDS Size"] <= 17408, (k, v)               # the head word and the hot nodes
         assert v["Occupancy"] >= 7, (k, v)                            # no worse than the path kernel's own walk
+    # the walk's shell and the hit record are hj_walk_segment.h's; the unit does not restate them
+    src = open(os.path.join(ROOT, "hijiki_amd", "csrc", "api", "ray_query.hip")).read()
+    segment = open(os.path.join(ROOT, "hijiki_amd", "csrc", "kernels", "hj_walk_segment.h")).read()
+    assert "__shared__ WgShared sh;" in segment and "load_hot_nodes(sc, sh);" in segment and "trace_persistent<MODE, PAIRS>(" in segment
+    assert "HJ_DEV float4 walk_hit_record(const RawHit& h)" in segment and "hit ? h.id : -1" in segment
+    assert "walk_segment<ANY ? 1 : 0, PAIRS>(" in src and src.count("walk_hit_record(h)") == 2
+    assert "__shared__ WgShared" not in src and "load_hot_nodes(" not in src and "trace_persistent<" not in src and "hit ? h.t" not in src
