@@ -13,12 +13,12 @@ HOST_SRC = hijiki_amd/csrc/host/scene.cpp hijiki_amd/csrc/host/tree_opt.cpp hiji
            hijiki_amd/csrc/host/obj_loader.cpp hijiki_amd/csrc/host/image_io.cpp hijiki_amd/csrc/host/host_api.cpp
 HOST_HDR = hijiki_amd/csrc/host/scene.hpp hijiki_amd/csrc/host/blockgen.hpp include/hijiki_hip.h include/hijiki_host.h
 # libhijiki_hip.so: its translation units (hijiki_amd/csrc/api/hj_internal.h lists them); render.hip, scene_relayout.hip,
-# scene_update.hip, lbvh_build.hip, tree_vote.hip, texture.hip, environment.hip, step_probe.hip, ray_query.hip, path_query.hip, path_adaptive.hip, gather_query.hip, probe_volume.hip, probe_visibility.hip, probe_update.hip, probe_place.hip, closest_query.hip, multi_hit.hip, aov.hip, follow.hip, probe_lit.hip, denoise.hip, denoise_temporal.hip, motion.hip, motion_follow.hip, gather_adaptive.hip, lightmap_filter.hip, lightmap.hip and tree_reinsert.hip hold device code.  The register / scratch / LDS report of the path kernels: hijiki_amd/lib/resource_usage.txt
+# scene_update.hip, lbvh_build.hip, tree_vote.hip, texture.hip, environment.hip, step_probe.hip, ray_query.hip, path_query.hip, path_adaptive.hip, gather_query.hip, probe_volume.hip, probe_visibility.hip, probe_update.hip, probe_place.hip, closest_query.hip, multi_hit.hip, aov.hip, follow.hip, probe_lit.hip, direct_lit.hip, denoise.hip, denoise_temporal.hip, motion.hip, motion_follow.hip, gather_adaptive.hip, lightmap_filter.hip, lightmap.hip and tree_reinsert.hip hold device code.  The register / scratch / LDS report of the path kernels: hijiki_amd/lib/resource_usage.txt
 # (render.hip's kernels, then behind the line '# gather_query.hip' the gather query's, behind '# probe_volume.hip' the probe volumes', behind '# gather_adaptive.hip' the adaptive gather's, behind '# lightmap_filter.hip' the light-map filter's, then behind '# lightmap.hip' the light-map kernels': report_unit below).
-# HIP_HDR: every unit is rebuilt when a header changes; kernels/*.h by wildcard, so a new kernel header (hj_compact.h, hj_lightmap_filter.h, hj_probe_vis.h, hj_probe_update.h, hj_probe_place.h, hj_closest.h, hj_multihit.h, hj_aov.h, hj_denoise.h, hj_denoise_temporal.h, hj_motion.h, hj_follow.h, hj_motion_follow.h, hj_chain.h, hj_walk_segment.h, hj_probe_lit.h) needs no line here.  probe_visibility.hip, probe_update.hip, probe_place.hip, closest_query.hip, multi_hit.hip, aov.hip, follow.hip, denoise.hip, denoise_temporal.hip, motion.hip and motion_follow.hip have no section in the report: their own tests compile them for one.
-HIP_UNITS = context scene_upload scene_relayout scene_update render render_calls comm lbvh_build tree_vote texture environment step_probe ray_query path_query path_adaptive gather_query probe_volume probe_visibility probe_update probe_place closest_query multi_hit aov follow probe_lit denoise denoise_temporal motion motion_follow gather_adaptive lightmap_filter lightmap tree_reinsert
+# HIP_HDR: every unit is rebuilt when a header changes; kernels/*.h by wildcard, so a new kernel header (hj_compact.h, hj_lightmap_filter.h, hj_probe_vis.h, hj_probe_update.h, hj_probe_place.h, hj_closest.h, hj_multihit.h, hj_aov.h, hj_denoise.h, hj_denoise_temporal.h, hj_motion.h, hj_follow.h, hj_motion_follow.h, hj_chain.h, hj_walk_segment.h, hj_probe_lit.h, hj_direct_lit.h) needs no line here.  probe_visibility.hip, probe_update.hip, probe_place.hip, closest_query.hip, multi_hit.hip, aov.hip, follow.hip, probe_lit.hip, direct_lit.hip, denoise.hip, denoise_temporal.hip, motion.hip and motion_follow.hip have no section in the report: their own tests compile them for one.
+HIP_UNITS = context scene_upload scene_relayout scene_update render render_calls comm lbvh_build tree_vote texture environment step_probe ray_query path_query path_adaptive gather_query probe_volume probe_visibility probe_update probe_place closest_query multi_hit aov follow probe_lit direct_lit denoise denoise_temporal motion motion_follow gather_adaptive lightmap_filter lightmap tree_reinsert
 HIP_OBJ = $(HIP_UNITS:%=build/obj/%.o) build/obj/blockgen.o build/obj/light_grid.o
-HIP_HDR = $(wildcard hijiki_amd/csrc/kernels/*.h) hijiki_amd/csrc/api/hj_internal.h hijiki_amd/csrc/api/hj_tuning.h hijiki_amd/csrc/api/light_grid.hpp hijiki_amd/csrc/api/scene_relayout.hpp hijiki_amd/csrc/api/refit_pass.hpp hijiki_amd/csrc/api/guard_box.hpp hijiki_amd/csrc/api/tree_vote.hpp hijiki_amd/csrc/api/tree_reinsert.h hijiki_amd/csrc/api/query_round.h hijiki_amd/csrc/api/query_round_loop.h hijiki_amd/csrc/api/chain_rounds.h hijiki_amd/csrc/api/adaptive_stop.h include/hijiki_hip.h hijiki_amd/csrc/host/blockgen.hpp
+HIP_HDR = $(wildcard hijiki_amd/csrc/kernels/*.h) hijiki_amd/csrc/api/hj_internal.h hijiki_amd/csrc/api/hj_tuning.h hijiki_amd/csrc/api/light_grid.hpp hijiki_amd/csrc/api/scene_relayout.hpp hijiki_amd/csrc/api/refit_pass.hpp hijiki_amd/csrc/api/guard_box.hpp hijiki_amd/csrc/api/tree_vote.hpp hijiki_amd/csrc/api/tree_reinsert.h hijiki_amd/csrc/api/query_round.h hijiki_amd/csrc/api/query_round_loop.h hijiki_amd/csrc/api/chain_rounds.h hijiki_amd/csrc/api/probe_lit_volume.h hijiki_amd/csrc/api/adaptive_stop.h include/hijiki_hip.h hijiki_amd/csrc/host/blockgen.hpp
 HIP_FLAGS = --offload-arch=$(ARCH) -std=c++17 -O3 -fPIC $(FP_STRICT) -fhip-fp32-correctly-rounded-divide-sqrt -fvisibility=hidden \
             -Wall -Wno-unused-function $(HIP_EXTRA)
 

@@ -31,11 +31,13 @@ PATHS_DEVICE_ARRAYS = 1           # hj_trace_paths flag
 GATHER_DEVICE_ARRAYS = 1          # hj_trace_irradiance flags
 GATHER_SPHERE = 2
 GATHER_SH9 = 4                    # (only together with GATHER_SPHERE)
+GATHER_INDIRECT = 16              # the first segment's emission is left out (8 is reserved: refused)
 LIGHTMAP_DEVICE_ARRAYS = 1        # hj_lightmap_desc flag
 LIGHTMAP_MAX_GUTTER = 64          # hj_bake_lightmap: dilation passes a call
 LIGHTMAP_NONE = 0xFFFFFFFF        # owner word of a texel nobody owns
 LIGHTMAP_FILTER_MAX_ITERATIONS = 8  # hj_lightmap_filter: iteration i uses the step 1 << i
-PROBES_DEVICE_ARRAYS = 1          # hj_probe_desc flag
+PROBES_DEVICE_ARRAYS = 1          # hj_probe_desc flags
+PROBES_INDIRECT_ONLY = 4          # the bakes and updates gather with GATHER_INDIRECT (2 is reserved: refused)
 PROBE_WORDS = 28                  # words of a probe record: 27 SH coefficients of the irradiance, the validity weight
 PROBE_MAX_COUNT, PROBE_MAX_PROBES = 1024, 1 << 22   # probes along an axis, probes of a volume
 PROBE_VIS_DEVICE_ARRAYS, PROBE_VIS_NO_BACKFACE, PROBE_VIS_NO_CHEBYSHEV = 1, 2, 4   # hj_probe_vis_desc flags
@@ -76,7 +78,7 @@ MOTION_DEVICE_SHAPES = 1          # hj_render_motion flag: the previous shape ar
 MOTION_DEVICE_OUT = 2             # ... the motion image is a device pointer
 MOTION_LEFT = 0xFFFFFFFE          # hj_render_motion_followed: word 3 of a pixel whose chain left a specular surface and hit nothing
 PROBE_LIT_WORDS = 4               # words of a probe-lit pixel (hj_render_probe_lit): the sums of L.rgb, the sample count
-VERSION = (0, 32, 0)              # the ABI this mirror describes: hj_version() == (major << 16) | (minor << 8) | patch
+VERSION = (0, 33, 0)              # the ABI this mirror describes: hj_version() == (major << 16) | (minor << 8) | patch
 
 
 def probe_vis_words(res):

@@ -155,7 +155,7 @@ int drain(hj_context* ctx, const char* fn, hipError_t e) {
 
 extern "C" {
 
-uint32_t hj_version(void) { return (0u << 16) | (32u << 8) | 0u; }   // 0.32.0: hj_render_probe_lit, hj_render_probe_lit_frame
+uint32_t hj_version(void) { return (0u << 16) | (33u << 8) | 0u; }   // 0.33.0: hj_render_direct_lit, hj_render_direct_lit_frame, HJ_GATHER_INDIRECT, HJ_PROBES_INDIRECT_ONLY
 
 void hj_default_render_opts(hj_render_opts* o) {
   if (!o) return;

@@ -115,7 +115,7 @@ extern "C" {
 int hj_trace_irradiance_adaptive(hj_context* ctx, const float* points, size_t n, const hj_adaptive_opts* aopts, const hj_render_opts* opts, uint32_t flags,
                                  float* out, float* moments, hj_render_stats* stats) {
   if (n != 0 && (!points || !out)) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance_adaptive: null %s", !points ? "points" : "out");
-  if (flags & ~(uint32_t)(HJ_GATHER_DEVICE_ARRAYS | HJ_GATHER_SPHERE | HJ_GATHER_SH9))
+  if (flags & ~(uint32_t)(HJ_GATHER_DEVICE_ARRAYS | HJ_GATHER_SPHERE | HJ_GATHER_SH9 | HJ_GATHER_INDIRECT))
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance_adaptive: unknown flag bits 0x%x", flags);
   if (flags & HJ_GATHER_SH9) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance_adaptive: HJ_GATHER_SH9 is not available in the adaptive gather");
   const bool on_device = (flags & HJ_GATHER_DEVICE_ARRAYS) != 0, sphere = (flags & HJ_GATHER_SPHERE) != 0;

@@ -30,6 +30,7 @@ struct GatherArgs {
   uint32_t num_samples;
   uint32_t max_bounces;
   uint32_t rr_start;
+  uint32_t start;         // the flags word a path starts with: 1u (wasDiscrete, bounce 0), or 0u with HJ_GATHER_INDIRECT
 };
 
 // The direction of sample k of the point (a, b) - the ONE text of it: the top-up draws it, the SH reduction draws it again.
@@ -54,10 +55,12 @@ HJ_DEV v3 gq_direction(float4 a, float4 b, uint32_t k, uint32_t& rng) {
 // starts at the point as a sample of hj_trace_paths starts at its ray's origin - throughput 1, extinction 0, wasDiscrete, bounce 0,
 // kCameraFlag beside the sample index so that the walk gives the first segment tMin = eps - along gq_direction, with the RNG state
 // CONTINUED behind the direction's two draws.  The lanes of a group mostly share a point: its two float4 are broadcast loads.
+// start: GatherArgs' - with HJ_GATHER_INDIRECT wasDiscrete is clear, so the first segment's emission (an emitter it ends on, the
+// environment it leaves into) is not counted; nothing else of a path differs.
 // (A group index is below 2^25 and the last group's samples below 2^31 + 64: no 32-bit wrap.)
 template <bool SPHERE>
 HJ_DEV void stage_gen_points(const BatchState& st, const DeviceScene& sc, const float4* __restrict__ points, uint32_t spp, uint32_t num_samples,
-                             uint32_t g, WgShared& sh, uint32_t parity, uint32_t n0, uint32_t k0, uint32_t ngen, uint32_t waves) {
+                             uint32_t g, WgShared& sh, uint32_t parity, uint32_t n0, uint32_t k0, uint32_t ngen, uint32_t waves, uint32_t start) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t seg = g * st.pool + n0;
   for (uint32_t k = k0 + wave; k < k0 + ngen; k += waves) {
@@ -73,7 +76,7 @@ HJ_DEV void stage_gen_points(const BatchState& st, const DeviceScene& sc, const 
       // the sample index rides in origin.w, the RNG state in direction.w
       stp<false>(st.ray_o[parity], pos, make_float4(a.x, a.y, a.z, __uint_as_float(s | kCameraFlag)));
       stp<false>(st.ray_d[parity], pos, make_float4(d.x, d.y, d.z, __uint_as_float(rng)));
-      stp<false>(st.thr[parity], pos, make_float4(1.f, 1.f, 1.f, __uint_as_float(1u)));   // wasDiscrete = true, bounce 0
+      stp<false>(st.thr[parity], pos, make_float4(1.f, 1.f, 1.f, __uint_as_float(start)));   // wasDiscrete = true (indirect: false), bounce 0
       if (sc.has_extinction) stp<false>(st.ext[parity], pos, make_float4(0.f, 0.f, 0.f, 0.f));
       stp<false>(st.smp_rgb, s, make_float4(0.f, 0.f, 0.f, 1.f));
       stp<false>(st.smp_nd, s, make_float4(0.f, 0.f, 0.f, 0.f));
@@ -87,17 +90,17 @@ HJ_DEV void stage_gen_points(const BatchState& st, const DeviceScene& sc, const 
 template <bool ENV, bool SPHERE>
 __device__ __attribute__((noinline)) void stage_gen_points_call(uint32_t ka_lo, uint32_t ka_hi, uint32_t pts_lo, uint32_t pts_hi, uint32_t spp,
                                                                  uint32_t num_samples, uint32_t g, uint32_t sh_lds, uint32_t parity, uint32_t n0,
-                                                                 uint32_t k0, uint32_t ngen, uint32_t waves) {
+                                                                 uint32_t k0, uint32_t ngen, uint32_t waves, uint32_t start) {
   const StageCtx c = stage_ctx(ka_lo, ka_hi, sh_lds);
   const float4* points = (const float4*)(((uint64_t)uni(pts_hi) << 32) | (uint64_t)uni(pts_lo));
-  stage_gen_points<SPHERE>(c.st, c.sc, points, uni(spp), uni(num_samples), uni(g), c.sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves));
+  stage_gen_points<SPHERE>(c.st, c.sc, points, uni(spp), uni(num_samples), uni(g), c.sh, uni(parity), uni(n0), uni(k0), uni(ngen), uni(waves), uni(start));
 }
 
 // One persistent launch per chunk of samples: the round loop of api/query_round_loop.h with the top-up above.
 template <bool PAIRS, bool ENV, bool SPHERE>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(HJ_QUERY_WAVES, 8))) void k_gq_paths(BatchState st, DeviceScene sc, GatherArgs q) {
   __shared__ std::conditional_t<ENV, WgSharedEnv, WgShared> sh;
-#define HJ_QUERY_TOP_UP stage_gen_points_call<ENV, SPHERE>
+#define HJ_QUERY_TOP_UP(...) stage_gen_points_call<ENV, SPHERE>(__VA_ARGS__, q.start)   // (the start word: wave-uniform, from the argument segment)
 #include "query_round_loop.h"
 #undef HJ_QUERY_TOP_UP
 }
@@ -168,7 +171,7 @@ void gather_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G
   const bool pairs = sc.has_pairs != 0, env = sc.env_alias != nullptr;
   const uint32_t num_samples = cnt * spp;                  // (<= 2^31 - 1: HJ_PATHS_CHUNK's upper bound, or one point's spp)
   set_num_wg(st, std::min<uint32_t>(G, (num_samples + 63u) / 64u));
-  const hj::GatherArgs q{d_pts, spp, num_samples, o.max_bounces, o.rr_start};
+  const hj::GatherArgs q{d_pts, spp, num_samples, o.max_bounces, o.rr_start, (flags & HJ_GATHER_INDIRECT) != 0 ? 0u : 1u};
   const dim3 grid(st.num_wg), blk(hj::kBlockThreads);
   if (pairs && env) hj::launch_gq_paths<true, true>(sphere, grid, blk, s, st, sc, q);
   else if (pairs) hj::launch_gq_paths<true, false>(sphere, grid, blk, s, st, sc, q);
@@ -212,7 +215,7 @@ extern "C" {
 int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t spp, const hj_render_opts* opts, uint32_t flags, float* out,
                         hj_render_stats* stats) {
   if (n != 0 && (!points || !out)) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: null %s", !points ? "points" : "out");
-  if (flags & ~(uint32_t)(HJ_GATHER_DEVICE_ARRAYS | HJ_GATHER_SPHERE | HJ_GATHER_SH9))
+  if (flags & ~(uint32_t)(HJ_GATHER_DEVICE_ARRAYS | HJ_GATHER_SPHERE | HJ_GATHER_SH9 | HJ_GATHER_INDIRECT))
     return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: unknown flag bits 0x%x", flags);
   const bool on_device = (flags & HJ_GATHER_DEVICE_ARRAYS) != 0, sphere = (flags & HJ_GATHER_SPHERE) != 0, sh9 = (flags & HJ_GATHER_SH9) != 0;
   if (sh9 && !sphere) return set_error(ctx, HJ_ERR_INVALID, "hj_trace_irradiance: HJ_GATHER_SH9 only together with HJ_GATHER_SPHERE");

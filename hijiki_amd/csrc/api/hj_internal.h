@@ -93,7 +93,13 @@
 //                         probe volume - aov_render (api/aov.hip) with an AovStage: behind each walk launch and its follow rounds
 //                         k_pl_points, the volume's own look-up kernel over those points (probe_sample_enqueue,
 //                         probe_vis_sample_enqueue: the units that hold the kernels launch them) and per run k_pl_resolve (includes
-//                         kernels/hj_probe_lit.h, which includes hj_follow.h without its kernels and edits none)
+//                         kernels/hj_probe_lit.h, which includes hj_follow.h without its kernels and edits none); for the next unit the
+//                         stage's volume, its checks, staging, reserve and points hook (api/probe_lit_volume.h)
+//   api/direct_lit.hip    hj_render_direct_lit, hj_render_direct_lit_frame: the probe-lit frame with one traced next-event sample at each
+//                         chain's last diffuse hit - the same AovStage with, behind lit_points, k_dl_sample, the compaction of the
+//                         slots that want a shadow ray (k_dl_count, k_dl_scan, the count to the host, k_dl_scatter), k_dl_shadow over
+//                         the list and per run k_dl_resolve (includes kernels/hj_direct_lit.h, which includes hj_probe_lit.h without
+//                         its kernels and edits none)
 //   api/denoise.hip       hj_denoise_frame: the variance-guided a-trous filter over a frame's albedo-demodulated light, guided by the
 //                         frame's AOV sums (includes kernels/hj_denoise.h and hj_num.h alone: k_dn_prepare, k_dn_variance, the
 //                         iteration as k_dn_filter_lds or k_dn_filter_direct, k_dn_finish); the checks, the buffers, the prepare
@@ -517,6 +523,11 @@ struct hj_context {
   // records, the chain state and a host-side image's staging (16 bytes a pixel) are Aov's.  Grown on demand, freed with the context.
   struct ProbeLit { hjapi::DevBuf points, lookup, side, volume, atlas, placement; } probe_lit;
 
+  // hj_render_direct_lit (api/direct_lit.hip): per sample slot of one walk launch 48 bytes - the shadow ray (32) and the pending direct
+  // term (16).  The list of the slots that want a ray and its tile counts are Aov's chain buffers (the rounds of a launch are over
+  // before its shadow rays are listed); everything else is ProbeLit's and Aov's.  Grown on demand, freed with the context.
+  struct DirectLit { hjapi::DevBuf rays; } direct_lit;
+
   // hj_denoise_frame (api/denoise.hip): the guide (48 bytes a pixel: normal and depth, albedo and valid word, depth slope) and the
   // two working images (16 bytes a pixel each); the staging of host arrays - beauty, AOV image, result (16, 48 and 16 bytes a
   // pixel).  Grown on demand, reused by every call, freed with the context.  The framebuffer is read, never written.
@@ -587,7 +598,11 @@ int context_gate(hj_context* ctx, const char* fn);
 namespace hj { struct PvGrid; struct PvvMap; }   // kernels/hj_probes.h, kernels/hj_probe_vis.h
 namespace hjapi {
 // api/probe_volume.hip: what every probe entry point refuses of a desc, without a device, in the header's order -> g, n = the probes;
-// and the enqueue, on the context's stream, of the gather points of the probes first ... first + n - 1 (n > 0) under `seed`
+// and the enqueue, on the context's stream, of the gather points of the probes first ... first + n - 1 (n > 0) under `seed`.
+// probe_desc_check alone knows the mask of a desc's flags; probe_gather_flags: what the calls that gather (hj_bake_probes,
+// hj_update_probes, hj_update_probes_placed) hand hj_trace_irradiance - sphere, SH9, device arrays, and HJ_GATHER_INDIRECT for a
+// desc with HJ_PROBES_INDIRECT_ONLY
+uint32_t probe_gather_flags(const hj_probe_desc* d);
 int probe_desc_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGrid& g, uint32_t& n);
 void probe_points_enqueue(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t n, float4* d_points);
 // api/probe_visibility.hip: what hj_bake_probe_visibility refuses of the two descs, in the header's order -> g, n, v; and the enqueue
@@ -739,7 +754,7 @@ struct FixedSppQuery {
 };
 int fixed_spp_query(hj_context* ctx, const FixedSppQuery& q);
 // api/gather_query.hip: the gather's counterpart of path_query_pass - one launch of k_gq_paths over cnt device points at spp samples
-// each into st's sample arrays, without the resolve (flags: HJ_GATHER_SPHERE) - and the check of host points' normals in
+// each into st's sample arrays, without the resolve (flags: HJ_GATHER_SPHERE, HJ_GATHER_INDIRECT) - and the check of host points' normals in
 // hemisphere mode (finite, not all zero), for both gather entry points
 void gather_query_pass(hj::BatchState& st, const hj::DeviceScene& sc, uint32_t G, const float4* d_pts, uint32_t cnt, uint32_t spp, const hj_render_opts& o,
                        uint32_t flags, hipStream_t s);

@@ -9,28 +9,17 @@
 //                    k_pp_sample (api/probe_place.hip)
 //   per run part     k_pl_resolve in k_aov_resolve's / k_aov_resolve_followed's place
 // A host-side volume, atlas and placement are staged once a call, before aov_render enqueues anything.
+// For api/direct_lit.hip (probe_lit_volume.h): the stage's volume (Lit), its checks and staging, its reserve and its points hook -
+// with no volume (a null Lit) k_pl_points alone.
 #include "hj_internal.h"
 #include "../kernels/hj_probe_lit.h"
-#define HJ_PROBE_VIS_NO_KERNELS        // PvGrid and PvvMap, by value in the stage below: the look-up kernels stay in the units that hold them
-#include "../kernels/hj_probe_vis.h"
+#include "probe_lit_volume.h"
 
 #pragma clang fp contract(off)
 
 using namespace hjapi;
 
-namespace {
-
-enum class Lookup { kPlain, kVisible, kPlaced };
-
-// What a call's stage carries: the volume on the device and which look-up reads it
-struct Lit {
-  Lookup lookup;
-  hj::PvGrid g;
-  hj::PvvMap v;
-  const float4* d_probes;
-  const float2* d_atlas;
-  const float4* d_place;
-};
+namespace hjapi {
 
 int lit_reserve(hj_context* ctx, const AovStage&, size_t slots) {
   hj_context::ProbeLit& q = ctx->probe_lit;
@@ -40,20 +29,25 @@ int lit_reserve(hj_context* ctx, const AovStage&, size_t slots) {
 }
 
 // Behind the walk and the rounds of a launch of nb blocks: the points of its n sample slots, then the look-up over all n of them
+// (st.self == nullptr - hj_render_direct_lit without a lighting -: the points and side records alone)
 hipError_t lit_points(hj_context* ctx, const AovStage& st, const hj_image_block* d_blocks, uint32_t nb, const float4* d_hits, bool followed) {
-  const Lit& lit = *static_cast<const Lit*>(st.self);
   hj_context::ProbeLit& q = ctx->probe_lit;
   const uint32_t n = nb * hj::kSlotsPerBlock;
   float4 *d_points = static_cast<float4*>(q.points.p), *d_lookup = static_cast<float4*>(q.lookup.p);
   const float4* d_state = followed ? static_cast<const float4*>(ctx->aov.chain.state.p) : nullptr;
   hipLaunchKernelGGL(hj::k_pl_points, per_lane(n), dim3(hj::kBlockThreads), 0, ctx->stream, ctx->scene, d_blocks, nb, d_hits, d_state, d_points,
                      static_cast<float4*>(q.side.p));
-  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (lit.lookup == Lookup::kPlain) probe_sample_enqueue(ctx, lit.g, lit.d_probes, d_points, n, d_lookup);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess || !st.self) return e;
+  const Lit& lit = *static_cast<const Lit*>(st.self);
+  if (lit.lookup == LitLookup::kPlain) probe_sample_enqueue(ctx, lit.g, lit.d_probes, d_points, n, d_lookup);
   else probe_vis_sample_enqueue(ctx, lit.g, lit.v, lit.d_probes, lit.d_atlas, lit.d_place, d_points, n, d_lookup,
-                                lit.lookup == Lookup::kPlaced ? probe_place_sample_launch : nullptr);
+                                lit.lookup == LitLookup::kPlaced ? probe_place_sample_launch : nullptr);
   return hipGetLastError();
 }
+
+}  // namespace hjapi
+
+namespace {
 
 void lit_resolve(hj_context* ctx, const AovStage&, const hj_image_block* d_blocks, uint32_t nb, uint32_t b0, uint32_t cnt, const float4* d_hits,
                  bool followed, uint32_t width, uint32_t height, float4* d_image) {
@@ -63,6 +57,10 @@ void lit_resolve(hj_context* ctx, const AovStage&, const hj_image_block* d_block
                      d_state, static_cast<const float4*>(q.lookup.p), static_cast<const float4*>(q.side.p), width, height, d_image);
 }
 
+}  // namespace
+
+namespace hjapi {
+
 // The volume's refusals, without a device: a null lighting, a placement without vis, then those of the look-up `lighting` selects in that
 // call's order (the points and the results are this call's own).  any: the call has blocks -> lit's look-up, grid and map; np
 int lit_check(hj_context* ctx, const char* fn, const hj_probe_lighting* l, bool any, Lit& lit, uint32_t& np, bool& reads_atlas) {
@@ -71,14 +69,14 @@ int lit_check(hj_context* ctx, const char* fn, const hj_probe_lighting* l, bool 
   lit = Lit{};
   reads_atlas = false;
   if (!l->vis) {                                                    // hj_sample_probes
-    lit.lookup = Lookup::kPlain;
+    lit.lookup = LitLookup::kPlain;
     if (!l->desc || (any && !l->probes)) return set_error(ctx, HJ_ERR_INVALID, "%s: null %s", fn, !l->desc ? "desc" : "probes");
     HJ_TRY(probe_desc_check(ctx, fn, l->desc, lit.g, np));
     if ((l->desc->flags & HJ_PROBES_DEVICE_ARRAYS) != 0 && any && misaligned(l->probes))
       return set_error(ctx, HJ_ERR_INVALID, "%s: device arrays must be 16-byte aligned", fn);
     return HJ_OK;
   }
-  lit.lookup = l->placement ? Lookup::kPlaced : Lookup::kVisible;  // hj_sample_probes_visible, hj_sample_probes_visible_placed
+  lit.lookup = l->placement ? LitLookup::kPlaced : LitLookup::kVisible;  // hj_sample_probes_visible, hj_sample_probes_visible_placed
   return probe_vis_volume_check(ctx, fn, l->desc, l->vis, l->probes, l->atlas, l->placement, l->placement != nullptr, any, lit.g, np, lit.v, reads_atlas);
 }
 
@@ -105,6 +103,10 @@ int lit_stage(hj_context* ctx, const char* fn, const hj_probe_lighting* l, uint3
   lit.d_place = l->placement ? static_cast<const float4*>(q.placement.p) : nullptr;
   return HJ_OK;
 }
+
+}  // namespace hjapi
+
+namespace {
 
 int lit_render(hj_context* ctx, const char* fn, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height, uint32_t max_follow,
                uint32_t flags, const hj_probe_lighting* lighting, uint32_t np, bool reads_atlas, Lit& lit, float* image) {

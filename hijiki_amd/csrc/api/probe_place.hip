@@ -174,7 +174,7 @@ int hj_update_probes_placed(hj_context* ctx, const hj_probe_desc* desc, const hj
   float4 *d_points = static_cast<float4*>(pv.points.p), *d_records = static_cast<float4*>(pv.records.p);
   hipLaunchKernelGGL(hj::k_pp_points, per_item(m), dim3(hj::kPpThreads), 0, ctx->stream, g, seed, desc->seed_stride, d_list, m, first, d_place, d_points);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, __func__, e);
-  const int rc = hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), m, spp, &o, HJ_GATHER_SPHERE | HJ_GATHER_SH9 | HJ_GATHER_DEVICE_ARRAYS,
+  const int rc = hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), m, spp, &o, probe_gather_flags(desc),
                                      reinterpret_cast<float*>(d_records), stats);
   if (rc != HJ_OK) return drain(ctx, __func__, rc);
   // 4. resolve and blend in one pass, in place: the record of point i is the one its word 7 names

@@ -71,7 +71,7 @@ int hj_update_probes(hj_context* ctx, const hj_probe_desc* desc, const hj_probe_
   float4 *d_points = static_cast<float4*>(pv.points.p), *d_records = static_cast<float4*>(pv.records.p);
   probe_points_enqueue(ctx, g, seed, desc->seed_stride, first, cnt, d_points);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, __func__, e);
-  const int rc = hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), cnt, spp, &o, HJ_GATHER_SPHERE | HJ_GATHER_SH9 | HJ_GATHER_DEVICE_ARRAYS,
+  const int rc = hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), cnt, spp, &o, probe_gather_flags(desc),
                                      reinterpret_cast<float*>(d_records), stats);
   if (rc != HJ_OK) return drain(ctx, __func__, rc);                   // (a host window's copy in: nothing of the call stays in flight)
   // 3. resolve and blend in one pass, in place

@@ -47,7 +47,8 @@ namespace {
 
 // What the three entry points refuse of a desc, without a device (fn: the entry point's name) -> g, n = the probes
 int check_desc(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGrid& g, uint32_t& n) {
-  if (d->flags & ~(uint32_t)HJ_PROBES_DEVICE_ARRAYS) return set_error(ctx, HJ_ERR_INVALID, "%s: unknown flag bits 0x%x", fn, d->flags);
+  // (HJ_PROBES_INDIRECT_ONLY: read by the calls that gather - probe_gather_flags -, accepted and ignored by every other reader of a desc)
+  if (d->flags & ~(uint32_t)(HJ_PROBES_DEVICE_ARRAYS | HJ_PROBES_INDIRECT_ONLY)) return set_error(ctx, HJ_ERR_INVALID, "%s: unknown flag bits 0x%x", fn, d->flags);
   uint64_t total = 1;
   for (int a = 0; a < 3; a++) {
     if (d->count[a] == 0 || d->count[a] > 1024u) total = ~0ull;
@@ -81,6 +82,9 @@ void enqueue_points(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, uint32_
 }  // namespace
 
 namespace hjapi {
+uint32_t probe_gather_flags(const hj_probe_desc* d) {
+  return HJ_GATHER_SPHERE | HJ_GATHER_SH9 | HJ_GATHER_DEVICE_ARRAYS | ((d->flags & HJ_PROBES_INDIRECT_ONLY) != 0 ? (uint32_t)HJ_GATHER_INDIRECT : 0u);
+}
 int probe_desc_check(hj_context* ctx, const char* fn, const hj_probe_desc* d, hj::PvGrid& g, uint32_t& n) { return check_desc(ctx, fn, d, g, n); }
 void probe_points_enqueue(hj_context* ctx, const hj::PvGrid& g, uint32_t seed, uint32_t seed_stride, uint32_t first, uint32_t n, float4* d_points) {
   enqueue_points(ctx, g, seed, seed_stride, first, n, d_points);
@@ -139,7 +143,7 @@ int hj_bake_probes(hj_context* ctx, const hj_probe_desc* desc, uint32_t spp, con
   float4 *d_points = static_cast<float4*>(pv.points.p), *d_records = static_cast<float4*>(pv.records.p);
   enqueue_points(ctx, g, desc->seed, desc->seed_stride, 0u, n, d_points);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return drain(ctx, __func__, e);
-  HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), n, spp, &o, HJ_GATHER_SPHERE | HJ_GATHER_SH9 | HJ_GATHER_DEVICE_ARRAYS,
+  HJ_TRY(hj_trace_irradiance(ctx, reinterpret_cast<const float*>(d_points), n, spp, &o, probe_gather_flags(desc),
                              reinterpret_cast<float*>(d_records), stats));
   // 3. the resolve
   const float s = 12.5663706f / (float)spp;

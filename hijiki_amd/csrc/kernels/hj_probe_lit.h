@@ -6,6 +6,7 @@
 // here.  No global atomics, no inline assembly.
 //   k_pl_points    one lane per sample slot of a walk launch: the slot's look-up point (p, n, 0, 0) and its side record (Le, kind)
 //   k_pl_resolve   one lane per sample slot of a run of blocks: L = Le + (albedo * E) * (1 / pi) added to its pixel, the count beside it
+// HJ_PROBE_LIT_NO_KERNELS (kernels/hj_direct_lit.h): the functions alone - pl_segment, pl_compose -; api/probe_lit.hip holds the kernels.
 #pragma once
 #define HJ_FOLLOW_NO_KERNELS   // the functions of hj_follow.h (and through it of hj_aov.h), no kernel of theirs
 #include "hj_follow.h"
@@ -34,6 +35,17 @@ HJ_DEV bool pl_segment(const DeviceScene& sc, const hj_image_block* __restrict__
   }
   return true;
 }
+
+// The radiance of a sample with a diffuse term (side record kPlDiffuse) whose chain's last segment (o, d) ended in hit record hr: the
+// albedo is aov_record's at that hit, recomputed here; e: the look-up's record of the slot's point, E in words 0..2.
+// L[c] = Le[c] + (albedo[c] * E[c]) * kInvPi, uncontracted, in that order.  ONE text for k_pl_resolve and kernels/hj_direct_lit.h's resolve.
+HJ_DEV v3 pl_compose(const DeviceScene& sc, v3 o, v3 d, float4 hr, float4 sd, float4 e) {
+  float4 r0, r1, r2;
+  (void)aov_record(sc, o, d, hr, r0, r1, r2);
+  return V(sd.x + (r0.x * e.x) * kInvPi, sd.y + (r0.y * e.y) * kInvPi, sd.z + (r0.z * e.z) * kInvPi);
+}
+
+#ifndef HJ_PROBE_LIT_NO_KERNELS
 
 // points: two float4 per slot, the look-ups' own layout (position.xyz, normal.x | normal.yz, 0, 0); side: (Le.rgb, kind bits).
 //   a hit on anything but a mirror or a dielectric: the populated hit point and shading normal aov_record builds its record from,
@@ -80,8 +92,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_pl_points(DeviceScene sc, con
 }
 
 // A RUN, as k_aov_resolve has it: blocks [b0, b0 + nb) of the launch's list have pairwise disjoint pixels, so the read-add-write below
-// races with nothing.  One lane per sample slot.  lookup: the look-up's record of the slot's point, E in words 0..2.  The albedo is
-// aov_record's at the chain's last hit, recomputed here; L[c] = Le[c] + (albedo[c] * E[c]) * kInvPi, uncontracted, in that order.
+// races with nothing.  One lane per sample slot.  lookup: the look-up's record of the slot's point, E in words 0..2; L: pl_compose's.
 // image: four floats a pixel, (sum of L.rgb, the count of samples); a pixel outside width x height is not written.
 __global__ __launch_bounds__(kBlockThreads) void k_pl_resolve(DeviceScene sc, const hj_image_block* __restrict__ blocks, uint32_t num_blocks,
                                                               uint32_t b0, uint32_t nb, const float4* __restrict__ hits,
@@ -97,16 +108,13 @@ __global__ __launch_bounds__(kBlockThreads) void k_pl_resolve(DeviceScene sc, co
   if (!aov_pixel(blocks, smp, width, height, px, py)) return;
   const float4 sd = side[smp];
   v3 L = xyz(sd);
-  if (__float_as_uint(sd.w) == kPlDiffuse) {
-    float4 r0, r1, r2;
-    (void)aov_record(sc, o, d, hits[smp], r0, r1, r2);
-    const float4 e = lookup[smp];
-    L = V(sd.x + (r0.x * e.x) * kInvPi, sd.y + (r0.y * e.y) * kInvPi, sd.z + (r0.z * e.z) * kInvPi);
-  }
+  if (__float_as_uint(sd.w) == kPlDiffuse) L = pl_compose(sc, o, d, hits[smp], sd, lookup[smp]);
   float4* p = image + ((size_t)py * width + px);
   float4 a = *p;
   a.x += L.x; a.y += L.y; a.z += L.z; a.w += 1.0f;
   *p = a;
 }
+
+#endif  // HJ_PROBE_LIT_NO_KERNELS
 
 }  // namespace hj

@@ -34,7 +34,7 @@ EXPORTS = ("hj_context_create", "hj_context_destroy", "hj_last_error", "hj_versi
            "hj_distance_field", "hj_trace_rays_all", "hj_points_inside", "hj_eval_materials", "hj_render_aovs", "hj_render_aovs_frame",
            "hj_denoise_frame", "hj_denoise_frame_temporal", "hj_render_motion", "hj_denoise_frame_temporal_motion",
            "hj_follow_specular", "hj_render_aovs_followed", "hj_render_aovs_frame_followed", "hj_render_motion_followed",
-           "hj_render_probe_lit", "hj_render_probe_lit_frame")
+           "hj_render_probe_lit", "hj_render_probe_lit_frame", "hj_render_direct_lit", "hj_render_direct_lit_frame")
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64, C.c_uint64)
 
@@ -134,6 +134,8 @@ def lib():
                                           C.POINTER(abi.ProbeLighting), vp]
         L.hj_render_probe_lit_frame.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                 C.POINTER(abi.ProbeLighting), vp]
+        L.hj_render_direct_lit.argtypes = L.hj_render_probe_lit.argtypes          # (lighting may be NULL)
+        L.hj_render_direct_lit_frame.argtypes = L.hj_render_probe_lit_frame.argtypes
         L.hj_denoise_frame.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), vp]   # (host or device pointers)
         L.hj_denoise_frame_temporal.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp]
         L.hj_denoise_frame_temporal_motion.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(abi.DenoiseOpts), C.POINTER(abi.TemporalOpts), vp, vp, vp, vp]
@@ -222,7 +224,7 @@ def resolve_aovs(aov):
 
 
 def resolve_probe_lit(image):
-    """The (height, width, 4) sums of `Renderer.render_probe_lit` as the mean radiance -> (height, width, 3): words 0..2 over the
+    """The (height, width, 4) sums of `Renderer.render_probe_lit` or `Renderer.render_direct_lit` as the mean radiance -> (height, width, 3): words 0..2 over the
     sample count (word 3), 0 where no sample fell.  A numpy array gives a numpy array, a torch tensor a tensor on its device."""
     if type(image).__module__.split(".")[0] == "torch":
         import torch
@@ -853,13 +855,51 @@ class Renderer:
         numpy array; contiguous float32 torch tensors on the renderer's GPU (volume, atlas and placement alike; device=None decides by
         the volume's type) are read in place and give a tensor on that GPU; torch's current stream is synchronised first.  Needs no
         framebuffer and leaves it alone."""
-        what = "render_probe_lit"
+        return Renderer._render_lit(self, "render_probe_lit", volume, origin, spacing, width, height, atlas, placement, normal_bias, backface, chebyshev, blocks, spp,
+                                    master_seed, passes, follow, device)             # (the class's: the argument checks need no renderer)
+
+    def render_direct_lit(self, width, height, volume=None, origin=None, spacing=None, atlas=None, placement=None, normal_bias=0.0, backface=True,
+                          chebyshev=True, blocks=None, spp=None, master_seed=0, passes=None, follow=0, device=None):
+        """hj_render_direct_lit / hj_render_direct_lit_frame: `render_probe_lit`'s frame with one traced next-event sample at each
+        chain's last diffuse hit -> (height, width, 4) float32 sums as there (`resolve_probe_lit` gives the mean).  A sample's radiance
+        is `render_probe_lit`'s plus the shade stage's direct term ((albedo * cos) / pi) * (emitted / pdf) of one emitter sample drawn
+        from the sample's own seed, counted when its any-hit shadow ray finds nothing: sharp shadows at the cost of one extra round.
+        volume=None: direct light alone (origin, spacing, atlas and placement are then not read; device=True gives a tensor).  A
+        volume baked with indirect_only=True holds the indirect light alone and the frame has direct light once; with a plain volume
+        it has it twice.  Everything else as in `render_probe_lit`."""
+        return Renderer._render_lit(self, "render_direct_lit", volume, origin, spacing, width, height, atlas, placement, normal_bias, backface, chebyshev, blocks, spp,
+                                    master_seed, passes, follow, device)             # (the class's: the argument checks need no renderer)
+
+    def _render_lit(self, what, volume, origin, spacing, width, height, atlas, placement, normal_bias, backface, chebyshev, blocks, spp, master_seed, passes,
+                    follow, device):
+        """the two lit frames behind their names: hj_<what> for a block list, hj_<what>_frame for spp [, master_seed, passes]"""
         if (blocks is None) == (spp is None):
             raise ValueError(f"{what}: either blocks or spp is needed")
         follow = int(follow)
         if not 0 <= follow <= abi.AOV_MAX_FOLLOW:
             raise ValueError(f"{what}: follow {follow}: 0 ... {abi.AOV_MAX_FOLLOW}")
         on_gpu = type(volume).__module__.split(".")[0] == "torch" if device is None else bool(device)
+        by_blocks, by_frame = getattr(lib(), "hj_" + what), getattr(lib(), "hj_" + what + "_frame")
+        width, height = int(width), int(height)
+        if volume is None:
+            if what != "render_direct_lit":
+                raise ValueError(f"{what}: a volume is needed")
+            if on_gpu:
+                import torch
+                image = torch.empty((height, width, abi.PROBE_LIT_WORDS), dtype=torch.float32, device=f"cuda:{self.device}")
+                torch.cuda.current_stream(image.device).synchronize()     # (the allocation)
+                ptr, flags = image.data_ptr(), abi.AOV_DEVICE_ARRAY
+            else:
+                image = np.zeros((height, width, abi.PROBE_LIT_WORDS), np.float32)
+                ptr, flags = image.ctypes.data, 0
+            if blocks is not None:
+                if not isinstance(blocks, C.Array):
+                    blocks = (abi.ImageBlock * len(blocks))(*blocks)
+                self._check(by_blocks(self._h, blocks, len(blocks), width, height, follow, flags, None, ptr))
+            else:
+                begin, end = (0, int(spp)) if passes is None else (int(passes[0]), int(passes[1]))
+                self._check(by_frame(self._h, width, height, int(spp), int(master_seed), begin, end, follow, flags, None, ptr))
+            return image
         if volume.ndim != 4 or volume.shape[3] != abi.PROBE_WORDS:
             raise ValueError(f"{what}: a volume of (nz, ny, nx, {abi.PROBE_WORDS}) is needed (got {tuple(volume.shape)})")
         if placement is not None and atlas is None:
@@ -874,7 +914,6 @@ class Renderer:
         place_ptr = None
         if placement is not None:
             _, placement, place_ptr = self._placement(what, placement, d, on_gpu)
-        width, height = int(width), int(height)
         if on_gpu:
             import torch
             for name, t in (("volume", volume),) + ((("atlas", atlas),) if atlas is not None else ()):
@@ -894,10 +933,10 @@ class Renderer:
         if blocks is not None:
             if not isinstance(blocks, C.Array):
                 blocks = (abi.ImageBlock * len(blocks))(*blocks)
-            self._check(lib().hj_render_probe_lit(self._h, blocks, len(blocks), width, height, follow, flags, C.byref(lighting), ptr))
+            self._check(by_blocks(self._h, blocks, len(blocks), width, height, follow, flags, C.byref(lighting), ptr))
         else:
             begin, end = (0, int(spp)) if passes is None else (int(passes[0]), int(passes[1]))
-            self._check(lib().hj_render_probe_lit_frame(self._h, width, height, int(spp), int(master_seed), begin, end, follow, flags, C.byref(lighting), ptr))
+            self._check(by_frame(self._h, width, height, int(spp), int(master_seed), begin, end, follow, flags, C.byref(lighting), ptr))
         return image
 
     def render_motion(self, prev, width, height, device_arrays=None, device=False, follow=0):
@@ -1160,7 +1199,7 @@ class Renderer:
         res = (out,) + ((mom,) if moments else ()) + ((stats_dict(st),) if stats else ())
         return res if len(res) > 1 else out
 
-    def trace_irradiance(self, points, seeds=None, spp=1, sphere=False, sh9=False, opts=None, stats=None):
+    def trace_irradiance(self, points, seeds=None, spp=1, sphere=False, sh9=False, opts=None, stats=None, indirect=False):
         """hj_trace_irradiance: the radiance gathered at (n, 8) points (position, normal of any length - used as given -, a uint32
         seed as the bits of word 6, a reserved word).  Sample k of point i draws its direction on the device from seedRng(seed_i + k):
         cosine-weighted about the normal, or with sphere=True uniform over the sphere (the normal is ignored), and the path goes on
@@ -1171,13 +1210,15 @@ class Renderer:
         seeds, opts and the array / tensor handling are `trace_paths'`: a numpy array gives a numpy array; a contiguous float32 torch
         tensor on the renderer's GPU is read in place and gives a tensor on that GPU, torch's current stream synchronised first.
         With host arrays in hemisphere mode a normal that is not finite or all zero is refused; with tensors that is the caller's
-        contract.  stats: true returns (records, statistics dict)."""
+        contract.  stats: true returns (records, statistics dict).  indirect=True (abi.GATHER_INDIRECT): a path starts with
+        wasDiscrete clear, so a first segment that ends on an emitter or leaves into the environment adds nothing - the light that
+        reaches the point directly is left out; everything else of a path and of a record is unchanged."""
         spp = int(spp)
         if not 1 <= spp <= 65536:
             raise ValueError(f"trace_irradiance: spp {spp} outside [1, 65536]")
         if sh9 and not sphere:
             raise ValueError("trace_irradiance: sh9 needs sphere=True (the basis is integrated over the whole sphere)")
-        flags = (abi.GATHER_SPHERE if sphere else 0) | (abi.GATHER_SH9 if sh9 else 0)
+        flags = (abi.GATHER_SPHERE if sphere else 0) | (abi.GATHER_SH9 if sh9 else 0) | (abi.GATHER_INDIRECT if indirect else 0)
         words = 36 if sh9 else 8
         st = abi.RenderStats()
         o = C.byref(opts) if opts is not None else None
@@ -1201,15 +1242,16 @@ class Renderer:
         return (out, stats_dict(st)) if stats else out
 
     def trace_irradiance_adaptive(self, points, seeds=None, spp_min=4, spp_step=4, spp_max=64, rel_error=0.05, floor=0.01, sphere=False, opts=None,
-                                  stats=False, moments=False):
+                                  stats=False, moments=False, indirect=False):
         """hj_trace_irradiance_adaptive: `trace_irradiance` with the number of samples decided per point on the device, by the rounds
         and the stop rule of `trace_paths_adaptive` (spp_min samples, then spp_step more a round up to spp_max, until the standard
         error of the mean luminance is at most rel_error * max(mean luminance, floor)).  -> (n, 8) float32 records as
         `trace_irradiance` gives them, word 3 = the samples the point received: record i is what `trace_irradiance` returns for point
         i with that spp.  There is no sh9.  points, seeds, sphere, opts, the normal check of host arrays and the array / tensor
-        handling are `trace_irradiance`'s; moments and stats are `trace_paths_adaptive`'s.  Returns records [, moments] [, statistics]."""
+        handling are `trace_irradiance`'s; moments and stats are `trace_paths_adaptive`'s; indirect as there.  Returns records [, moments]
+        [, statistics]."""
         a = self._adaptive_opts("trace_irradiance_adaptive", spp_min, spp_step, spp_max, rel_error, floor)
-        flags = abi.GATHER_SPHERE if sphere else 0
+        flags = (abi.GATHER_SPHERE if sphere else 0) | (abi.GATHER_INDIRECT if indirect else 0)
         st = abi.RenderStats()
         o = C.byref(opts) if opts is not None else None
         points, on_gpu = self._path_rays("trace_irradiance_adaptive", points, seeds)
@@ -1398,8 +1440,9 @@ class Renderer:
         return res if len(res) > 1 else img
 
     @staticmethod
-    def _probe_desc(what, origin, spacing, count, seed=0, seed_stride=1, min_distance=0.0, device=False):
-        """The desc of the probe calls, checked before any call.  count is (nx, ny, nz), as origin and spacing are (x, y, z)."""
+    def _probe_desc(what, origin, spacing, count, seed=0, seed_stride=1, min_distance=0.0, device=False, indirect_only=False):
+        """The desc of the probe calls, checked before any call.  count is (nx, ny, nz), as origin and spacing are (x, y, z).
+        indirect_only: abi.PROBES_INDIRECT_ONLY, which the calls that gather read and every other call ignores."""
         origin, spacing = np.asarray(origin, np.float32).reshape(-1), np.asarray(spacing, np.float32).reshape(-1)
         count = [int(c) for c in count]
         if len(origin) != 3 or len(spacing) != 3 or len(count) != 3:
@@ -1418,7 +1461,7 @@ class Renderer:
                 raise ValueError(f"{what}: {name} {v} is no uint32")
         f3, u3 = C.c_float * 3, C.c_uint32 * 3
         return abi.ProbeDesc(f3(*origin.tolist()), f3(*spacing.tolist()), u3(*count), int(seed), int(seed_stride), float(min_distance),
-                             abi.PROBES_DEVICE_ARRAYS if device else 0)
+                             (abi.PROBES_DEVICE_ARRAYS if device else 0) | (abi.PROBES_INDIRECT_ONLY if indirect_only else 0))
 
     def probe_points(self, origin, spacing, count, seed=0, seed_stride=1, device=False):
         """hj_probe_points: the gather points of a grid of count = (nx, ny, nz) probes, probe (x, y, z) at origin + (x, y, z) * spacing
@@ -1439,17 +1482,19 @@ class Renderer:
         self._check(lib().hj_probe_points(self._h, C.byref(d), pts.ctypes.data))
         return pts
 
-    def bake_probes(self, origin, spacing, count, spp, min_distance=0.0, seed=0, seed_stride=1, opts=None, stats=False, device=False):
+    def bake_probes(self, origin, spacing, count, spp, min_distance=0.0, seed=0, seed_stride=1, opts=None, stats=False, device=False, indirect_only=False):
         """hj_bake_probes: an irradiance probe volume of the uploaded scene, baked on the device - `probe_points`, the sphere gather of
         `trace_irradiance(sphere=True, sh9=True)` at `spp` samples over them, and the SH sums resolved to irradiance coefficients
         -> (nz, ny, nx, 28) float32: word 3 j + c of a probe is the coefficient of the j-th real spherical harmonic (bands 0..2, the
         gather's order) of the irradiance as a function of the surface normal, channel c; word 27 is 1 when no gather ray hit
         anything nearer than `min_distance`, else 0 (a probe inside or against a wall).  opts as in `trace_irradiance`.  device=True: a
-        torch tensor on the renderer's GPU.  stats=True: returns (volume, the gather's statistics dict).  `sample_probes` reads it."""
+        torch tensor on the renderer's GPU.  stats=True: returns (volume, the gather's statistics dict).  `sample_probes` reads it.
+        indirect_only=True (abi.PROBES_INDIRECT_ONLY): the gather is `trace_irradiance(..., indirect=True)` - the volume holds no light
+        that reaches a probe directly, which is what `render_direct_lit` adds by tracing."""
         spp = int(spp)
         if not 1 <= spp <= 65536:
             raise ValueError(f"bake_probes: spp {spp} outside [1, 65536]")
-        d = self._probe_desc("bake_probes", origin, spacing, count, seed, seed_stride, min_distance, device)
+        d = self._probe_desc("bake_probes", origin, spacing, count, seed, seed_stride, min_distance, device, indirect_only)
         shape = (d.count[2], d.count[1], d.count[0], abi.PROBE_WORDS)
         st = abi.RenderStats()
         o = C.byref(opts) if opts is not None else None
@@ -1674,7 +1719,7 @@ class Renderer:
         return False, out, out.ctypes.data
 
     def update_probes(self, desc, probes, spp, *, frame, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE, hysteresis, window=None,
-                      change=abi.PROBE_UPDATE_CHANGE, opts=None, stats=False, placement=None):
+                      change=abi.PROBE_UPDATE_CHANGE, opts=None, stats=False, placement=None, indirect_only=False):
         """hj_update_probes: a window of a (nz, ny, nx, 28) probe volume re-baked from the uploaded scene at `spp` samples and folded
         into `probes`.  desc: the grid as a dict of `bake_probes`' keywords (origin, spacing, count, and min_distance, seed,
         seed_stride where they are not the defaults).  The fresh record of a probe is `bake_probes`' with the seed seed + frame *
@@ -1687,18 +1732,19 @@ class Renderer:
         stream is synchronised first) and returned; a numpy array gives an updated copy, of which the window alone travelled.
         stats=True: returns (probes, the gather's statistics dict).  placement (None: the grid as it is): the (nz, ny, nx, 4) array of
         `place_probes`, of `probes`' kind - hj_update_probes_placed: the gather points sit at the placed positions, and the window's
-        inactive probes are neither traced nor written."""
+        inactive probes are neither traced nor written.  indirect_only=True (or the key in desc): the fresh record is
+        `bake_probes(..., indirect_only=True)`'s."""
         spp = int(spp)
         if not 1 <= spp <= 65536:
             raise ValueError(f"update_probes: spp {spp} outside [1, 65536]")
-        d = self._probe_desc("update_probes", **desc)
+        d = self._probe_desc("update_probes", **dict(desc, indirect_only=bool(indirect_only) or bool(desc.get("indirect_only", False))))
         n = d.count[0] * d.count[1] * d.count[2]
         u = self._probe_update("update_probes", n, frame, frame_stride, hysteresis, window, change)
         on_gpu, vol, ptr = self._update_target("update_probes", probes, (d.count[2], d.count[1], d.count[0], abi.PROBE_WORDS))
         st = abi.RenderStats()
         if on_gpu:
             import torch
-            d.flags = abi.PROBES_DEVICE_ARRAYS
+            d.flags |= abi.PROBES_DEVICE_ARRAYS
             torch.cuda.current_stream(vol.device).synchronize()       # (whatever wrote the tensor)
         o = C.byref(opts) if opts is not None else None
         if placement is not None:
@@ -1724,7 +1770,7 @@ class Renderer:
         on_gpu, atl, ptr = self._update_target("update_probe_visibility", atlas, (d.count[2], d.count[1], d.count[0], v.res + 2, v.res + 2, 2))
         if on_gpu:
             import torch
-            d.flags, v.flags = abi.PROBES_DEVICE_ARRAYS, v.flags | abi.PROBE_VIS_DEVICE_ARRAYS
+            d.flags, v.flags = d.flags | abi.PROBES_DEVICE_ARRAYS, v.flags | abi.PROBE_VIS_DEVICE_ARRAYS
             torch.cuda.current_stream(atl.device).synchronize()       # (whatever wrote the tensor)
         if placement is not None:
             _, held, place_ptr = self._placement("update_probe_visibility", placement, d, on_gpu)   # (held until the call returns)
@@ -1761,7 +1807,8 @@ class Renderer:
         return torch.zeros(shape, dtype=torch.float32, device=device)
 
     def place_probes(self, desc, vis, placement, *, frame, min_front_distance, frame_stride=abi.PROBE_UPDATE_FRAME_STRIDE,
-                     backface_share=abi.PROBE_PLACE_BACKFACE_SHARE, max_offset=abi.PROBE_PLACE_MAX_OFFSET, window=None, relocate=True, classify=True):
+                     backface_share=abi.PROBE_PLACE_BACKFACE_SHARE, max_offset=abi.PROBE_PLACE_MAX_OFFSET, window=None, relocate=True, classify=True,
+                     indirect_only=False):
         """hj_place_probes: one relocation-and-classification step (Majercik et al. 2021) over a window of a (nz, ny, nx, 4) placement
         (`new_placement`): per probe an offset in world units (words 0-2) and a state (word 3 as uint32 bits, 0 active).  desc, vis, frame,
         frame_stride and window as in `update_probe_visibility` (vis: res, rays_per_texel, max_distance).  From the probe's rays a probe
@@ -1769,8 +1816,9 @@ class Renderer:
         `min_front_distance` moves away from it, a probe that has room moves back towards its grid point; no offset leaves
         `max_offset` spacings.  A probe inside geometry, or with no front face within its eight cells, becomes inactive.  The defaults
         0.25 and 0.45 are the paper's and RTXGI's starting points, not tuned here.  relocate / classify = False leave the offsets / the
-        states alone.  A tensor on the renderer's GPU is updated in place and returned; a numpy array gives an updated copy."""
-        d = self._probe_desc("place_probes", **desc)
+        states alone.  A tensor on the renderer's GPU is updated in place and returned; a numpy array gives an updated copy.
+        indirect_only: the desc's abi.PROBES_INDIRECT_ONLY, accepted and not read - a placement step traces rays and gathers nothing."""
+        d = self._probe_desc("place_probes", **dict(desc, indirect_only=bool(indirect_only) or bool(desc.get("indirect_only", False))))
         v = self._probe_vis_desc("place_probes", **vis)
         n = d.count[0] * d.count[1] * d.count[2]
         u = self._probe_update("place_probes", n, frame, frame_stride, 0.0, window, (0.0, 0.0))
@@ -1786,7 +1834,7 @@ class Renderer:
         pl = abi.ProbePlace(u.first_probe, u.num_probes, u.frame, u.frame_stride, float(mfd), float(share), float(mo), flags)
         if on_gpu:
             import torch
-            d.flags, v.flags = abi.PROBES_DEVICE_ARRAYS, v.flags | abi.PROBE_VIS_DEVICE_ARRAYS
+            d.flags, v.flags = d.flags | abi.PROBES_DEVICE_ARRAYS, v.flags | abi.PROBE_VIS_DEVICE_ARRAYS
             torch.cuda.current_stream(arr.device).synchronize()       # (whatever wrote the tensor)
         self._check(lib().hj_place_probes(self._h, C.byref(d), C.byref(v), C.byref(pl), ptr))
         return arr

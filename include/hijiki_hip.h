@@ -640,6 +640,12 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
  *   HJ_GATHER_DEVICE_ARRAYS: points and out are device pointers on the context's GPU, 16-byte aligned, read and written in place on
  *     the context's stream (the caller orders its own streams before the call).  Without it they are host arrays, staged through
  *     buffers the context keeps.
+ *   HJ_GATHER_INDIRECT (ABI 0.33): the INDIRECT-only gather.  A path starts with wasDiscrete clear - its flags word is 0u where a
+ *     full gather's is 1u, bounce 0 - and everything else is unchanged: the directions, the RNG states, the first tMin, the records,
+ *     the hit count, the nearest t.  So a first segment that ends on an emitter adds nothing and ends; a first segment that leaves
+ *     into an uploaded environment adds nothing; from the first diffuse hit on the path is the integrator's, next-event samples
+ *     included.  What such a gather leaves out is exactly the light that reaches the point directly.  Bit 8u is reserved and stays
+ *     refused as an unknown flag bit.
  * A launch takes whole points (at most HJ_PATHS_CHUNK samples; one point when spp alone exceeds it); the path state is
  * hj_trace_paths' own, kept with the context.  Returns when the results are complete (one synchronisation).  n == 0: HJ_OK, nothing
  * touched.
@@ -655,6 +661,7 @@ int hj_trace_paths_adaptive(hj_context* ctx, const float* rays, size_t n, const 
 #define HJ_GATHER_DEVICE_ARRAYS 1u
 #define HJ_GATHER_SPHERE 2u
 #define HJ_GATHER_SH9 4u   /* only together with HJ_GATHER_SPHERE */
+#define HJ_GATHER_INDIRECT 16u   /* the first segment's emission is left out (8u is reserved: refused) */
 int hj_trace_irradiance(hj_context* ctx, const float* points, size_t n, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
                         uint32_t flags, float* out, hj_render_stats* stats /* may be NULL */);
 
@@ -785,7 +792,7 @@ int hj_bake_lightmap_filtered(hj_context* ctx, const hj_lightmap_desc* desc, uin
  * of a bake whose texels mostly converge in a handful of samples while penumbrae and corners need many.  points, opts, the origin
  * domain and the normal rules are exactly hj_trace_irradiance's; adaptive is hj_trace_paths_adaptive's hj_adaptive_opts with its
  * domain; no counterpart in the reference.
- *   flags: HJ_GATHER_DEVICE_ARRAYS, HJ_GATHER_SPHERE.  HJ_GATHER_SH9 is refused.
+ *   flags: HJ_GATHER_DEVICE_ARRAYS, HJ_GATHER_SPHERE, HJ_GATHER_INDIRECT (as in hj_trace_irradiance).  HJ_GATHER_SH9 is refused.
  *   Rounds.  As in hj_trace_paths_adaptive: round 0 gives every point spp_min samples; round r >= 1 gives every point that is still
  *     active min(spp_step, spp_max - n_i) samples, the sample index k continuing at n_i (sample k of point i starts from
  *     seedRng(seed_i + k) and draws its direction as in hj_trace_irradiance).  At most 64 rounds.
@@ -870,6 +877,11 @@ int hj_bake_lightmap_adaptive(hj_context* ctx, const hj_lightmap_desc* desc, con
  *   after the gather's and one more.  Without it they are host arrays, staged through buffers the context keeps (a volume whole, and
  *   48 bytes per sample point); hj_sample_probes then checks before anything is written that every position and normal is finite
  *   and that no normal is all zero - with device arrays that is the caller's contract, and a bad normal gives a NaN, not a fault.
+ * HJ_PROBES_INDIRECT_ONLY (desc->flags, ABI 0.33): the calls that gather - hj_bake_probes, hj_update_probes, hj_update_probes_placed -
+ *   pass HJ_GATHER_INDIRECT to hj_trace_irradiance, so the volume holds indirect light alone: the volume hj_render_direct_lit is
+ *   meant for.  Every other reader of a desc - the look-ups, hj_probe_points, the visibility calls, hj_place_probes (it traces rays
+ *   and gathers nothing), hj_distance_field, the lighting of hj_render_probe_lit and hj_render_direct_lit - accepts the bit and
+ *   ignores it.  Bit 2u is reserved and stays refused as an unknown flag bit.
  * HJ_ERR_INVALID, checked before anything else and without a device (with a null context the text is in hj_last_error(NULL)), in
  *   this order: a null desc or array argument (hj_sample_probes: only with n > 0); unknown flag bits; a count outside [1, 1024] or
  *   a product above 2^22; a non-finite origin; a spacing that is not finite or not > 0; a min_distance that is negative or not
@@ -880,6 +892,7 @@ int hj_bake_lightmap_adaptive(hj_context* ctx, const hj_lightmap_desc* desc, con
  * Not here: no adaptive probe bake (hj_trace_irradiance_adaptive refuses HJ_GATHER_SH9).  The weights against light leaks - back face and
  *   visibility (Chebyshev) - are hj_sample_probes_visible's, below; hj_sample_probes itself knows the min_distance rule alone. */
 #define HJ_PROBES_DEVICE_ARRAYS 1u
+#define HJ_PROBES_INDIRECT_ONLY 4u   /* the bakes and updates gather with HJ_GATHER_INDIRECT (2u is reserved: refused) */
 #define HJ_PROBE_WORDS 28u
 typedef struct hj_probe_desc {
   float    origin[3];          /* probe (0,0,0); finite                                              */
@@ -887,7 +900,7 @@ typedef struct hj_probe_desc {
   uint32_t count[3];           /* 1 ... 1024 each, product <= 2^22                                   */
   uint32_t seed, seed_stride;  /* probe p gets seed + p * seed_stride (uint32 wrap-around)           */
   float    min_distance;       /* finite, >= 0: a probe with a first hit nearer than this is invalid */
-  uint32_t flags;              /* HJ_PROBES_DEVICE_ARRAYS                                            */
+  uint32_t flags;              /* HJ_PROBES_DEVICE_ARRAYS, HJ_PROBES_INDIRECT_ONLY                   */
 } hj_probe_desc;
 int hj_probe_points(hj_context* ctx, const hj_probe_desc* desc, float* points /* n x 8 */);
 int hj_bake_probes(hj_context* ctx, const hj_probe_desc* desc, uint32_t spp, const hj_render_opts* opts /* NULL = defaults */,
@@ -1556,7 +1569,8 @@ int hj_render_aovs_frame_followed(hj_context* ctx, uint32_t width, uint32_t heig
  *     spp, master_seed and pass range.  The bad pass range (pass_begin > pass_end or pass_end > spp) is refused behind max_follow, before
  *     the lighting.  An empty pass range: HJ_OK, an all-zero image.
  * Not here: a glossy lobe - the project has no such material; glass extinction along the chain; lighting from a baked light map; a
- *   multi-GPU split; a flag of the command-line tool; separately traced direct shadows - direct light is as soft as the volume has it. */
+ *   multi-GPU split; a flag of the command-line tool; separately traced direct shadows - direct light is as soft as the volume has it.
+ *   (For those: hj_render_direct_lit, below, with a volume baked HJ_PROBES_INDIRECT_ONLY.) */
 #define HJ_PROBE_LIT_WORDS 4
 typedef struct hj_probe_lighting {
   const hj_probe_desc*     desc;       /* the volume's grid; its flags say host or device arrays for probes / atlas / placement */
@@ -1570,6 +1584,45 @@ int hj_render_probe_lit(hj_context* ctx, const hj_image_block* blocks, size_t nu
 int hj_render_probe_lit_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
                               uint32_t pass_end, uint32_t max_follow, uint32_t flags, const hj_probe_lighting* lighting,
                               float* image /* height x width x 4 */);
+
+/* Direct-lit frames (ABI 0.33): hj_render_probe_lit with one traced next-event sample at each chain's last diffuse hit - sharp direct
+ * shadows beside the volume's indirect light, at the cost of one extra any-hit round.  Arguments, samples, chains, blocks, runs and the
+ * block-order float32 sums are exactly hj_render_probe_lit's; lighting may be NULL, which means direct light alone.  No counterpart in
+ * the reference; tests/direct_lit_ref.py restates the contract in numpy over the oracle's shade step.
+ *
+ * hj_render_direct_lit:  per sample, with Lp the L hj_render_probe_lit defines (lighting == NULL: E is absent and Lp = Le for a hit, the
+ *     environment or 0 for a miss):
+ *     - the direct term applies when the chain's last hit carries one of the three diffuse tags (HJ_MAT_DIFFUSE, HJ_MAT_DIFFUSECBOARD,
+ *       HJ_MAT_DIFFUSE_TEXTURED).  Emitters, mirrors and glass (the cap cut the chain there) and misses get none.
+ *     - the sample: rng = seedRng(seed) of the sample's own seed (block.seed + lx + ly * dimension.x: the state the camera ray leaves;
+ *       a chain draws nothing, so a followed sample uses the same state); imp, sdir, stmax = the shade stage's next-event sample of
+ *       the emitters at p from rng (with an uploaded environment its environment form), (p, n, albedo) being the words of Lp's record.
+ *     - the term exists iff length(imp) > eps and dot(sdir, n) > 0, the shade stage's condition, and then
+ *           D = ((albedo * dot(n, sdir)) * 0.318309886f) * imp
+ *       in the shade stage's operation order with throughput 1, one rounding each, no contraction.
+ *     - D counts iff the shade stage's shadow ray finds nothing: from p along sdir with tMin = 2 eps and tMax = stmax (+inf for an
+ *       environment sample), any-hit, walked on the uploaded tree.
+ *     - L = Lp + D, one rounding a channel, when D counts; otherwise L = Lp and no addition is taken.
+ *   Corollary: with max_follow == 0 and lighting == NULL or an all-zero volume, a sample's L is bit for bit the radiance hj_trace_paths
+ *     returns for that camera ray with spp = 1, the sample's seed and max_bounces = 1 (the shade stage takes the first hit's next-event
+ *     sample before its bounce limit ends the path).
+ *   With a volume baked HJ_PROBES_INDIRECT_ONLY the frame has direct light once; with a plain volume it has it twice (E holds it
+ *     already).  The call does not and cannot check this.
+ *   image, HJ_AOV_DEVICE_ARRAY, the independence of HJ_TRACE_CHUNK: as hj_render_probe_lit.  The context holds 48 bytes more per sample
+ *     slot of one walk launch - the shadow ray and the pending D - and the list of the slots that want a ray (the chain rounds' own).
+ *   HJ_ERR_INVALID: hj_render_probe_lit's refusals in its order under this call's name, but a null lighting is accepted, and nothing
+ *     of a volume is then checked or staged.  A refused call writes nothing.  Then hj_trace_rays' gate.  num_blocks == 0: HJ_OK
+ *     behind the gate, an all-zero image.
+ * hj_render_direct_lit_frame:  hj_render_direct_lit over hj_render_probe_lit_frame's block list; the bad pass range as there.
+ * Not here: more than one light sample a hit, stratified lights; the light-shaft grid's proven-free shortcut (every wanted ray is
+ *   traced; the image would be the same bits either way); glass extinction along the chain; a glossy lobe; light-map indirect; a
+ *   multi-GPU split; a flag of the command-line tool. */
+int hj_render_direct_lit(hj_context* ctx, const hj_image_block* blocks, size_t num_blocks, uint32_t width, uint32_t height,
+                         uint32_t max_follow, uint32_t flags, const hj_probe_lighting* lighting /* may be NULL */,
+                         float* image /* height x width x 4 */);
+int hj_render_direct_lit_frame(hj_context* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t master_seed, uint32_t pass_begin,
+                               uint32_t pass_end, uint32_t max_follow, uint32_t flags, const hj_probe_lighting* lighting /* may be NULL */,
+                               float* image /* height x width x 4 */);
 
 /* ------------------------------------------- frame denoiser */
 

@@ -26,10 +26,10 @@ def kernels_sha256():
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(ROOT, "hijiki_amd/csrc/kernels/*.h"))) + [os.path.join(ROOT, "hijiki_amd/csrc/api/render.hip")]
     for f in files:
-        # (the BVH build, the vote, the light-map texels and filter, the tile compaction, the probe look-ups, updates and placement, the distance query, the all-hit query, the frame AOVs and their followed form, the frame denoiser, its temporal stage, the motion pass and its followed form, the chain rounds both followed forms share, the shell of the flat segment walks, the probe-lit frames, and the SH basis - the
+        # (the BVH build, the vote, the light-map texels and filter, the tile compaction, the probe look-ups, updates and placement, the distance query, the all-hit query, the frame AOVs and their followed form, the frame denoiser, its temporal stage, the motion pass and its followed form, the chain rounds both followed forms share, the shell of the flat segment walks, the probe-lit and direct-lit frames, and the SH basis - the
         # gather's reduction and the look-up include it, api/render.hip does not - are other kernels)
         if os.path.basename(f) in ("hj_lbvh.h", "hj_vote.h", "hj_lightmap.h", "hj_lightmap_const.h", "hj_lightmap_filter.h", "hj_compact.h",
-                                   "hj_probes.h", "hj_probe_vis.h", "hj_probe_update.h", "hj_probe_place.h", "hj_closest.h", "hj_multihit.h", "hj_aov.h", "hj_follow.h", "hj_denoise.h", "hj_denoise_temporal.h", "hj_motion.h", "hj_motion_follow.h", "hj_chain.h", "hj_walk_segment.h", "hj_probe_lit.h", "hj_sh9.h"):
+                                   "hj_probes.h", "hj_probe_vis.h", "hj_probe_update.h", "hj_probe_place.h", "hj_closest.h", "hj_multihit.h", "hj_aov.h", "hj_follow.h", "hj_denoise.h", "hj_denoise_temporal.h", "hj_motion.h", "hj_motion_follow.h", "hj_chain.h", "hj_walk_segment.h", "hj_probe_lit.h", "hj_direct_lit.h", "hj_sh9.h"):
             continue
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
